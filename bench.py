@@ -1,29 +1,37 @@
 #!/usr/bin/env python3
 """bench.py -- Mpixels/s of the fused encode (FDCT+quant) stage on MI355X, with its HBM roofline
-fraction and the CPU oracle timed beside it.
+fraction; with --full also the CPU oracle timed beside it and the other workloads.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--dump-outputs DIR] [--full]
 
 A *step* is one pass of the hot path over one batch of synthetic input that is already resident in HBM:
 the default workload is BASELINE.json configs[1], one 4096x4096 random-pixel frame per step.  Steps walk
 a ring of distinct frames whose inputs+outputs exceed the 256 MiB Infinity Cache, so the kernel really
 streams from HBM.  The K timed steps are a fixed sequence of K launches (one per step, on torch's
 current stream): they are captured once into a hipGraph; a *replay* of that graph is exactly K steps,
-bracketed by barrier + synchronize on both sides.  The replay is repeated R times (--repeats, default 11);
-`ms_per_step` is the MEDIAN replay divided by K (max over ranks per replay), min/max are reported beside it; the W warm-up
-steps are run again before every repetition's bracket (--rewarm 1), so that each repetition is the contract's own sequence.
+bracketed by barrier + synchronize on both sides.  A plain run times ONE replay: `ms_per_step` is its wall time divided
+by K (max over ranks).  With --full (or --repeats R) the replay is repeated R times (default 11 with --full) and
+`ms_per_step` is the MEDIAN replay divided by K, min/max reported beside it; the W warm-up steps are run again before
+every repetition's bracket (--rewarm 1), so that each repetition is the contract's own sequence.
+
+A plain run does only what the headline needs: set up, warm up, the timed steps, the outputs (--dump-outputs DIR: what the
+last timed step computed, as DIR/<name>.npy in float32 / float64, see dump_outputs) and the JSON line, whose roofline
+object is taken from the HIP events of the timed region itself.  Everything measured beside the headline in runs of its
+own -- the CPU oracle baseline, the other BASELINE workloads, the native multi-GPU entry, the long replay, the device-copy
+reference, the decode tolerance mode, the entropy-stage and Huffman-decoder rooflines, the configs[3] batch at N > 1 --
+runs only with --full.
 
 --gpus N > 1: when WORLD_SIZE is not set this process starts N copies of itself, one per GPU (RANK /
 LOCAL_RANK / WORLD_SIZE / MASTER_* in their environment) *before it touches the GPU*, and rank 0 prints the
 JSON line; under torch.distributed.run the ranks are taken from the environment as usual.  `value` at N > 1
 is the same workload on every rank (frames are independent: no data-path collective, weak scaling).
-In addition every N > 1 run (and N = 1 with --batch) measures BASELINE configs[3] as north_star states it --
+In addition every N > 1 run with --full (and N = 1 with --batch) measures BASELINE configs[3] as north_star states it --
 a batch of 4096 1920x1080 frames sharded by jpezy_amd.sharding.shard_range, strong scaling -- and reports it
 as the object "batch": kernel-only throughput, the RCCL gather of the coefficient buffers to the consumer
 rank, the pipelined end-to-end time (gather overlapped with the kernels chunk by chunk), and the speed-up
 over the same pipeline run on ONE GPU in the same job.
 
-Prints ONE JSON line (rank 0).  `oracle/` is used only for the cpu_baseline leg.
+Prints ONE JSON line (rank 0).  `oracle/` is used only for the cpu_baseline leg (--full).
 """
 import argparse
 import json
@@ -55,6 +63,9 @@ WORKLOADS = {
                        "4096x4096 .jpg bytes (host) -> GPU Huffman decoder -> dequant+IDCT+RGB planes in HBM"),
 }
 BATCH_W, BATCH_H, BATCH_FRAMES = 1920, 1080, 4096      # BASELINE configs[3]
+DUMP_MAX_BYTES = 64 << 20        # --dump-outputs: all files together
+DUMP_SAMPLE = 1 << 22            # elements kept of an output larger than this (a fixed, seeded sample)
+DUMP_SEED = 0x6A70657A64
 
 
 def algorithmic_bytes(W, H, gray, direction):
@@ -657,6 +668,34 @@ def measure_native_multi(J, ctx, n_dev, frames_per_dev=256, max_frames=1024):
         res["one_shot_16_frames"] = {"error": f"{type(e).__name__}: {e}"[:300]}
     return res
 
+
+# ------------------------------------------------------------------------------------------------------------------
+# --dump-outputs: what the timed path computed in its last step, so that two builds can be compared output for output
+# ------------------------------------------------------------------------------------------------------------------
+def dump_outputs(outdir, arrays):
+    """Write every array of `arrays` (name -> numpy array) as <outdir>/<name>.npy: float32 for 8- and 16-bit integers (exact),
+    float64 for wider ones.  An array of more than DUMP_SAMPLE elements is flattened and replaced by its elements at a fixed,
+    seeded, sorted sample of DUMP_SAMPLE indices (the same indices for the same size).  Raises, before writing anything, if the
+    files would exceed DUMP_MAX_BYTES together."""
+    import numpy as np
+    outdir = Path(outdir)
+    outdir.mkdir(parents=True, exist_ok=True)
+    idx_for, files, total = {}, {}, 0
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if a.size > DUMP_SAMPLE:
+            if a.size not in idx_for:
+                idx_for[a.size] = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, DUMP_SAMPLE, replace=False))
+            a = a.reshape(-1)[idx_for[a.size]]
+        a = a.astype(np.float32 if a.dtype.itemsize <= 2 else np.float64)
+        files[name] = a
+        total += a.nbytes
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} B exceed {DUMP_MAX_BYTES} B")
+    for name, a in files.items():
+        np.save(outdir / f"{name}.npy", a)
+
+
 # ------------------------------------------------------------------------------------------------------------------
 def run_rank(args):
     import torch
@@ -849,6 +888,21 @@ def run_rank(args):
     evms = [ev0.elapsed_time(ev1) for ev0, ev1 in evs]
     nfallback = ctx.fallback_count()
 
+    # --dump-outputs: what a caller of the timed path receives from its last step (ring slot (K-1) % ring), taken before
+    # anything else runs on the ring
+    if args.dump_outputs and rank == 0:
+        k = (args.steps - 1) % ring
+        if not direction.startswith("encode"):
+            outs = {"r": pr[k], "g": pg[k], "b": pb[k]}               # decoded planes [fps][H*W] u8
+        else:
+            outs = {"coefficients": co[k]}                            # [fps][ncoef] i16, zig-zag order, the 6- or 4-block layout
+            if with_entropy:
+                n = jsz[k].cpu()
+                outs["jpg"] = torch.cat([jpg[k][f, :int(n[f])] for f in range(fps)])    # the .jpg files, back to back
+                outs["jpg_sizes"] = n
+        dump_outputs(args.dump_outputs, {name: t_.cpu().numpy() for name, t_ in outs.items()})
+        del outs
+
     t = torch.tensor([wall, evms], dtype=torch.float64, device=red_dev)
     if multi:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)       # per replay: the slowest rank
@@ -860,7 +914,7 @@ def run_rank(args):
     # about 2 us per step at K = 20 -- inside its bracket.  Beside `value` (never instead of it) the same launches are timed
     # over a long replay, so that the line also carries the steady rate the rocprofv3 summaries show.
     long_run = None
-    if rank == 0 and graph is not None and args.steps < 100 and not with_entropy and args.streams == 1:
+    if args.full and rank == 0 and graph is not None and args.steps < 100 and not with_entropy and args.streams == 1:
         k_saved, args.steps = args.steps, 200
         gl = capture(step, 1)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -884,7 +938,7 @@ def run_rank(args):
     # every byte within one of the reference's, north_star's own bar) timed over the same ring -- an object of its own beside
     # `value`, never instead of it.  max_abs_diff is measured here, against the bit-exact kernel's output of the same frames.
     dec_tol = None
-    if rank == 0 and direction == "decode" and graph is not None and args.streams == 1 and not args.no_tolerant:
+    if args.full and rank == 0 and direction == "decode" and graph is not None and args.streams == 1 and not args.no_tolerant:
         dec(0)                                                       # the exact kernel's planes of ring slot 0
         torch.cuda.synchronize(dev)
         exact = [t[0].clone() for t in (pr, pg, pb)]
@@ -920,7 +974,7 @@ def run_rank(args):
     # besides the vendor peak, report a device-copy bandwidth measured on this box with the same byte count
     # and the same ring (one plain copy kernel per step: half the bytes read, half written)
     copy_gbs = None
-    if rank == 0:
+    if args.full and rank == 0:
         half = step_bytes // 2
         src_bufs = torch.empty((ring, half), dtype=torch.uint8, device=dev)
         dst_bufs = torch.empty((ring, half), dtype=torch.uint8, device=dev)
@@ -939,7 +993,7 @@ def run_rank(args):
     huffdec_roof = None
     # Huffman decoder alone (workload decode4096_jpg): K calls of jpezy_read_jpeg_gpu, HIP events on its stream around them.  The
     # call parses the header on the host, uploads the scan and synchronises between its passes, so this is the whole call.
-    if with_huffdec and rank == 0:
+    if args.full and with_huffdec and rank == 0:
         # the call is host-synchronous and works on the context's own stream: wall time around a device synchronise is the
         # honest clock (events on torch's stream would bracket nothing of it)
         hms, passes = [], 0
@@ -965,7 +1019,7 @@ def run_rank(args):
 
     # entropy stage alone (workload encode4096_jpg): its own launch sequence, timed with HIP events on the same stream
     entropy_roof = None
-    if with_entropy and rank == 0:
+    if args.full and with_entropy and rank == 0:
         torch.cuda.synchronize(dev)
         sizes = jsz[0].tolist()
         if min(sizes) <= 0:
@@ -1017,7 +1071,7 @@ def run_rank(args):
             ctxs.pop().close()
 
     batch = None
-    if (multi and not args.no_batch) or args.batch:
+    if (multi and args.full and not args.no_batch) or args.batch:
         del graph
         graph = None
         del pr, pg, pb, co
@@ -1029,14 +1083,14 @@ def run_rank(args):
             print(f"bench.py rank {rank}: batch measurement failed: {e}", file=sys.stderr)
 
     others = None
-    if rank == 0 and world == 1 and args.workload == "encode4096" and not args.no_others and args.variant in (None, 1) and not args.tolerant:
+    if args.full and rank == 0 and world == 1 and args.workload == "encode4096" and not args.no_others and args.variant in (None, 1) and not args.tolerant:
         try:
             others = measure_other_workloads(torch, J, ctx, dev, copy_gbs=copy_gbs)
         except Exception as e:
             others = {"error": f"{type(e).__name__}: {e}"[:300]}
 
     native = None
-    if rank == 0 and not args.no_native_multi and args.workload == "encode4096" and not args.rehearse_on_one_gpu:
+    if args.full and rank == 0 and not args.no_native_multi and args.workload == "encode4096" and not args.rehearse_on_one_gpu:
         try:
             native = measure_native_multi(J, ctx, min(world, torch.cuda.device_count()))
         except Exception as e:
@@ -1075,7 +1129,8 @@ def run_rank(args):
             "ms_per_step_min": round(min(wall) * 1e3 / args.steps, 5),
             "ms_per_step_max": round(max(wall) * 1e3 / args.steps, 5),
             "repeats": R,
-            "timing": f"median of {R} replays of exactly {args.steps} steps; each replay bracketed by barrier + synchronize, max over ranks",
+            "timing": (f"median of {R} replays" if R > 1 else "one replay") + f" of exactly {args.steps} steps; "
+                      "each replay bracketed by barrier + synchronize, max over ranks",
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
@@ -1094,18 +1149,20 @@ def run_rank(args):
             "exact_fallbacks_per_step": round(nfallback / max(1, args.steps * R), 2),
         }
         if with_huffdec:
-            out["roofline"] = huffdec_roof
+            if huffdec_roof:
+                out["roofline"] = huffdec_roof
             out["config"]["inputs"] = ".jpg files of iid uniform u8 frames (GPU coder's output), bytes on the host; coefficients and planes in HBM"
         elif not with_entropy:
             out["roofline"] = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                                "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": tsrc,
                                "kernel": kernel,
                                "algorithmic_bytes_per_launch": step_bytes, "avg_launch_ms_hip_events": round(kern_ms, 5),
-                               "avg_launch_ms_min_max": [round(min(evms) / args.steps, 5), round(max(evms) / args.steps, 5)],
-                               "device_copy_GBs_measured": round(copy_gbs, 1), "frac_of_device_copy": round(achieved / copy_gbs, 4)}
+                               "avg_launch_ms_min_max": [round(min(evms) / args.steps, 5), round(max(evms) / args.steps, 5)]}
+            if copy_gbs:
+                out["roofline"].update(device_copy_GBs_measured=round(copy_gbs, 1), frac_of_device_copy=round(achieved / copy_gbs, 4))
             if long_run:
                 out["roofline"]["long_run"] = long_run
-        else:
+        elif entropy_roof:
             out["roofline"] = entropy_roof
             out["roofline"]["note"] = ("the step's dominant cost is the entropy stage; the FDCT kernel's own roofline is the "
                                        "default workload's line")
@@ -1135,7 +1192,7 @@ def run_rank(args):
             out["other_workloads"] = others
         if native:
             out["native_multi_gpu"] = native
-        if not args.no_cpu:          # rank 0 only, after every timed region (the other ranks idle at the closing barrier)
+        if args.full and not args.no_cpu:          # rank 0 only, after every timed region (the other ranks idle at the closing barrier)
             out["cpu_baseline"] = cpu_baseline(W, H, gray, direction)
         print(json.dumps(out), flush=True)
 
@@ -1149,19 +1206,27 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--repeats", type=int, default=11, help="replays of the K-step sequence; ms_per_step is their median")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline (cpu_baseline, other_workloads, native_multi_gpu, the long "
+                         "replay, the device-copy reference, decode_tolerant, the entropy / Huffman-decoder rooflines, the batch "
+                         "at N > 1) and repeat the timed replay (--repeats default 11); off: only the headline's own work")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64; "
+                         "a fixed, seeded sample of an output larger than %d elements; %d MB at most)" % (DUMP_SAMPLE, DUMP_MAX_BYTES >> 20))
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="replays of the K-step sequence; ms_per_step is their median (default 1, 11 with --full)")
     ap.add_argument("--rewarm", type=int, default=1, help="1: the W warm-up steps are run again before every repetition's bracket "
                     "(each repetition then is `W warm-up steps, K timed steps`, as the first one is); 0: once, before the first")
     ap.add_argument("--workload", default="encode4096", choices=sorted(WORKLOADS))
     ap.add_argument("--ring", type=int, default=0, help="distinct batches in the ring (0 = enough to exceed 512 MiB)")
     ap.add_argument("--variant", type=int, default=None, help="encode kernel variant (0 FP64 butterflies, 1 packed-FP32 first level, one quad per wave [default], 2 / 3 the same arithmetic in persistent workgroups: loader waves + LDS ring / register prefetch)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline leg")
     ap.add_argument("--no-native-multi", action="store_true",
-                    help="default workload: skip the native_multi_gpu object (jpezy_encode_batch_multi timed by rank 0 after everything else)")
+                    help="--full, default workload: skip the native_multi_gpu object (jpezy_encode_batch_multi timed by rank 0 after everything else)")
     ap.add_argument("--no-others", action="store_true",
-                    help="default workload at N = 1: skip the other_workloads object (configs[2] and [4] measured after the timed region)")
+                    help="--full, default workload at N = 1: skip the other_workloads object (configs[2] and [4] measured after the timed region)")
     ap.add_argument("--batch", action="store_true", help="measure the configs[3] batch pipeline also at N = 1")
-    ap.add_argument("--no-batch", action="store_true", help="N > 1: skip the configs[3] batch measurement")
+    ap.add_argument("--no-batch", action="store_true", help="--full at N > 1: skip the configs[3] batch measurement")
     ap.add_argument("--batch-frames", type=int, default=None,
                     help=f"frames of the configs[3] batch (default {BATCH_FRAMES}; 16 in --rehearse-on-one-gpu)")
     ap.add_argument("--batch-chunk", type=int, default=64, help="frames per launch / per transfer of the batch pipeline")
@@ -1177,7 +1242,7 @@ def parse_args(argv=None):
                          "a 'pipelined' object beside value (off by default: the default command launches nothing but the "
                          "timed kernel, so that a rocprofv3 trace of it averages exactly the launches value is made of)")
     ap.add_argument("--no-tolerant", action="store_true",
-                    help="decode workloads: skip the decode_tolerant object (the opt-in tolerance mode timed after the timed region)")
+                    help="--full, decode workloads: skip the decode_tolerant object (the opt-in tolerance mode timed after the timed region)")
     ap.add_argument("--tolerant", action="store_true",
                     help="development aid: run the WHOLE decode bench in the opt-in tolerance mode (value is then not the bit-exact path's)")
     ap.add_argument("--no-graph", action="store_true",
@@ -1188,6 +1253,8 @@ def parse_args(argv=None):
                     help="development aid: run the N > 1 control flow with every rank on GPU 0, the gloo backend and host "
                          "staging (RCCL refuses two ranks on one device); the numbers mean nothing")
     args = ap.parse_args(argv)
+    if args.repeats is None:
+        args.repeats = 11 if args.full else 1
     if args.batch_frames is None:
         args.batch_frames = 16 if args.rehearse_on_one_gpu else BATCH_FRAMES
     return args

@@ -69,9 +69,9 @@ def mutate(d, rng):
     return bytes(b)
 
 
-def ppm_phase(n):
+def ppm_phase(n, bins):
     """the CLI's P3 reader (jpezy::encode_io) under the same sanitizers, on mutated text files"""
-    exe = Path(tempfile.gettempdir()) / "jpezy_ppm_fuzz"
+    exe = bins / "jpezy_ppm_fuzz"
     subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", str(ROOT / "include"),
                     str(ROOT / "tests" / "fuzz" / "ppm_fuzz.cpp"), "-o", str(exe), "-L", str(ROOT / "jpezy_amd"), "-ljpezy_hip",
                     "-Wl,-rpath," + str(ROOT / "jpezy_amd"), "-pthread"], check=True)
@@ -110,8 +110,14 @@ def ppm_phase(n):
 
 
 def main():
+    # the sanitizer builds go to a directory of this run's own: a fixed name in the shared temp directory may belong to another user
+    with tempfile.TemporaryDirectory(prefix="jpezy_fuzz_") as bins:
+        return run(Path(bins))
+
+
+def run(bins):
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 3000
-    exe = Path(tempfile.gettempdir()) / "jpezy_host_codec_fuzz"
+    exe = bins / "jpezy_host_codec_fuzz"
     src = [ROOT / "tests" / "fuzz" / "host_codec_fuzz.cpp", ROOT / "jpezy_amd" / "csrc" / "jpezy_host_codec.cpp"]
     subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
                     "-I", str(ROOT / "include"), *map(str, src), "-o", str(exe), "-pthread"], check=True)
@@ -135,7 +141,7 @@ def main():
             print(r.stderr[-4000:])
             return r.returncode
         # the core of the GPU Huffman decoder (tables + decode step) walked on the CPU over the same files, same sanitizers
-        exe2 = Path(tempfile.gettempdir()) / "jpezy_huffdec_core_fuzz"
+        exe2 = bins / "jpezy_huffdec_core_fuzz"
         src2 = [ROOT / "tests" / "fuzz" / "huffdec_core_fuzz.cpp", ROOT / "jpezy_amd" / "csrc" / "jpezy_host_codec.cpp"]
         subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
                         "-I", str(ROOT / "include"), *map(str, src2), "-o", str(exe2), "-pthread"], check=True)
@@ -145,7 +151,7 @@ def main():
         print(r.stderr[-4000:])
         return r.returncode
     if (ROOT / "jpezy_amd" / "libjpezy_hip.so").exists():       # the reader's header pulls in the class surface, which links the library
-        return ppm_phase(max(200, n // 4))
+        return ppm_phase(max(200, n // 4), bins)
     return 0
 
 

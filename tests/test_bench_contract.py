@@ -113,10 +113,11 @@ def test_traffic_json_is_what_the_cited_summaries_say():
         assert e["bytes_per_launch"] <= 1.10 * alg, (wl, e["bytes_per_launch"], alg)         # ... and no wasted re-reads either
 
 
-def test_other_workloads_and_native_multi_are_part_of_the_default_line():
-    """the default command measures BASELINE configs[2] and [4] and the native multi-GPU entry after the
-    timed region (objects of their own, never part of `value`); the run itself needs a GPU (tests/test_gpu_parity.py), here: the
-    pieces exist, name real workloads, and can be switched off for profiling passes."""
+def test_other_workloads_and_native_multi_are_part_of_the_full_line():
+    """`--full` measures BASELINE configs[2] and [4] and the native multi-GPU entry after the
+    timed region (objects of their own, never part of `value`); a plain run leaves them out.  The run itself needs a GPU
+    (tests/test_gpu_parity.py), here: the pieces exist, name real workloads, hang on --full, and can be switched off for
+    profiling passes."""
     import inspect
     b = _bench()
     src = inspect.getsource(b.measure_other_workloads)
@@ -124,7 +125,48 @@ def test_other_workloads_and_native_multi_are_part_of_the_default_line():
         assert name in b.WORKLOADS and f'"{name}"' in src
     assert set(b.OTHER_KERNELS) == {"encode", "decode"}
     assert "jpezy_encode_batch_multi" in inspect.getsource(b.measure_native_multi) or "encode_batch_multi" in inspect.getsource(b.measure_native_multi)
-    args = b.parse_args(["--no-others", "--no-native-multi"])
-    assert args.no_others and args.no_native_multi and not b.parse_args([]).no_others
+    args = b.parse_args(["--full", "--no-others", "--no-native-multi"])
+    assert args.full and args.no_others and args.no_native_multi and not b.parse_args(["--full"]).no_others
     run = inspect.getsource(b.run_rank)
     assert 'out["other_workloads"] = others' in run and 'out["native_multi_gpu"] = native' in run
+    assert "if args.full and rank == 0 and world == 1 and args.workload == \"encode4096\" and not args.no_others" in run
+    assert "if args.full and rank == 0 and not args.no_native_multi" in run
+    assert "if args.full and not args.no_cpu:" in run
+
+
+def test_plain_run_times_exactly_the_steps_it_is_given():
+    """a plain run replays the K captured steps once (ms_per_step = that replay / K); --full keeps the median of 11 replays"""
+    b = _bench()
+    plain, full = b.parse_args(["--steps", "37", "--warmup", "3"]), b.parse_args(["--full"])
+    assert not plain.full and plain.repeats == 1 and plain.steps == 37 and plain.warmup == 3 and plain.dump_outputs is None
+    assert full.full and full.repeats == 11
+    assert b.parse_args(["--repeats", "4"]).repeats == 4 and b.parse_args(["--full", "--repeats", "2"]).repeats == 2
+    assert b.parse_args(["--dump-outputs", "somewhere"]).dump_outputs == "somewhere"
+
+
+def test_dump_outputs_writes_float_arrays_and_a_fixed_sample_of_large_ones(tmp_path):
+    import numpy as np
+    b = _bench()
+    rng = np.random.default_rng(5)
+    big = rng.integers(-2048, 2048, (2, b.DUMP_SAMPLE + 1000), dtype=np.int16)
+    planes = rng.integers(0, 256, 1000, dtype=np.uint8)
+    sizes = np.array([123456789, 5], dtype=np.int64)
+    b.dump_outputs(tmp_path / "a", {"coefficients": big, "r": planes, "jpg_sizes": sizes})
+    b.dump_outputs(tmp_path / "b", {"coefficients": big})
+    c = np.load(tmp_path / "a" / "coefficients.npy")
+    assert c.dtype == np.float32 and c.shape == (b.DUMP_SAMPLE,)
+    assert np.array_equal(c, np.load(tmp_path / "b" / "coefficients.npy"))          # same size, same seeded sample
+    idx = np.sort(np.random.default_rng(b.DUMP_SEED).choice(big.size, b.DUMP_SAMPLE, replace=False))
+    assert np.array_equal(c, big.reshape(-1)[idx].astype(np.float32))                  # the values at those indices, exactly
+    r = np.load(tmp_path / "a" / "r.npy")
+    assert r.dtype == np.float32 and np.array_equal(r, planes)                            # small outputs whole, shape kept
+    s = np.load(tmp_path / "a" / "jpg_sizes.npy")
+    assert s.dtype == np.float64 and np.array_equal(s, sizes)                             # wide integers stay exact
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= b.DUMP_MAX_BYTES
+    many = {f"x{i}": big for i in range(5)}                                               # 5 x 16 MB: refused, nothing written
+    try:
+        b.dump_outputs(tmp_path / "c", many)
+        raise AssertionError("over the cap")
+    except SystemExit as e:
+        assert "exceed" in str(e)
+    assert not list((tmp_path / "c").glob("*.npy"))

@@ -90,7 +90,7 @@ def test_bench_gpus_2_rehearsal_on_one_gpu():
     with gloo + host staging.  Checks the control flow and that the sharded, gathered batch equals the one-GPU batch."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--rehearse-on-one-gpu", "--steps", "3",
-                        "--warmup", "1", "--repeats", "2", "--no-cpu", "--batch-frames", "10", "--batch-chunk", "3"],
+                        "--warmup", "1", "--repeats", "2", "--no-cpu", "--batch-frames", "10", "--batch-chunk", "3", "--full"],
                        env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     line = json.loads(p.stdout.strip().splitlines()[-1])
@@ -151,7 +151,7 @@ def test_bench_gpus_2_on_rccl_when_two_gpus_are_visible():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--repeats", "3",
-                        "--no-cpu", "--batch-frames", "96", "--batch-chunk", "16"],
+                        "--no-cpu", "--batch-frames", "96", "--batch-chunk", "16", "--full"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     line = json.loads(p.stdout.strip().splitlines()[-1])

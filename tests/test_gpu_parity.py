@@ -482,13 +482,13 @@ def test_short_soak_against_the_oracle():
 
 
 def test_bench_prints_one_contract_line():
-    """bench.py as the driver runs it (fewer steps): ONE JSON line with every key of the contract, the roofline and
-    cpu_baseline objects, and -- with --pipelined -- the two-frames-in-flight figure beside value, never inside it"""
+    """bench.py --full (fewer steps): ONE JSON line with every key of the contract, the roofline and cpu_baseline objects,
+    and -- with --pipelined -- the two-frames-in-flight figure beside value, never inside it"""
     import subprocess
     import sys
     from pathlib import Path
     root = Path(__file__).resolve().parent.parent
-    r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2", "--pipelined"],
+    r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2", "--pipelined", "--full"],
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -510,14 +510,15 @@ def test_bench_prints_one_contract_line():
 
 def test_bench_line_survives_a_failing_batch_leg_and_carries_the_other_workloads():
     """ADVICE r04: when run_batch raises, the headline JSON line is still printed (batch = {"error": ...}, no batch_strong_scaling);
-    VERDICT r04 item 2: the default command's line carries configs[2] and [4] as `other_workloads`, measured after the timed region."""
+    VERDICT r04 item 2: the --full line carries configs[2] and [4] as `other_workloads`, measured after the timed region."""
     import os
     import subprocess
     import sys
     from pathlib import Path
     root = Path(__file__).resolve().parent.parent
     env = dict(os.environ, JPEZY_BENCH_FAIL_BATCH="1")
-    r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--no-cpu", "--batch"],
+    r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--no-cpu", "--batch",
+                        "--full"],
                        capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -552,7 +553,8 @@ def test_bench_decode4096_jpg_line():
     import sys
     from pathlib import Path
     root = Path(__file__).resolve().parent.parent
-    r = subprocess.run([sys.executable, str(root / "bench.py"), "--workload", "decode4096_jpg", "--steps", "4", "--warmup", "1", "--no-cpu"],
+    r = subprocess.run([sys.executable, str(root / "bench.py"), "--workload", "decode4096_jpg", "--steps", "4", "--warmup", "1", "--no-cpu",
+                        "--full"],
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -564,6 +566,45 @@ def test_bench_decode4096_jpg_line():
     assert rf["algorithmic_bytes_per_step"] == rf["jpg_bytes_per_frame"] + 4096 * 4096 * 3
     assert abs(rf["frac"] - rf["achieved"] / rf["peak"]) < 1e-4
     assert abs(d["value"] - 4096 * 4096 / (d["ms_per_step"] * 1e-3) / 1e6) / d["value"] < 0.01
+
+
+def test_bench_plain_line_is_lean_and_dumps_the_last_step(tmp_path, oracle):
+    """the plain command (no --full): one contract line of exactly K timed steps and nothing measured beside it; --dump-outputs
+    writes the last timed step's coefficients -- a seeded sample of them -- which equal the oracle's for that step's frame"""
+    import subprocess
+    import sys
+    from pathlib import Path
+    import torch
+    root = Path(__file__).resolve().parent.parent
+    K = 7
+    r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", str(K), "--warmup", "2",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline"):
+        assert k in d, k
+    assert d["steps"] == K and d["repeats"] == 1 and d["ms_per_step"] > 0
+    assert abs(d["value"] - 4096 * 4096 / (d["ms_per_step"] * 1e-3) / 1e6) / d["value"] < 0.01
+    for k in ("cpu_baseline", "other_workloads", "native_multi_gpu", "batch", "pipelined"):
+        assert k not in d, k
+    assert "long_run" not in d["roofline"] and "device_copy_GBs_measured" not in d["roofline"]
+    assert sorted(p.name for p in tmp_path.iterdir()) == ["coefficients.npy"]
+    got = np.load(tmp_path / "coefficients.npy")
+    assert got.dtype == np.float32 and got.nbytes <= 64 << 20
+    # the frame of the last step: ring slot (K - 1) % ring of bench.py's seeded ring
+    ring, plane = d["config"]["ring_batches"], 4096 * 4096
+    gen = torch.Generator(device="cuda:0")
+    gen.manual_seed(0x6A70657A79)
+    k = (K - 1) % ring
+    rgb = [torch.randint(0, 256, (ring, 1, plane), dtype=torch.uint8, device="cuda:0", generator=gen)[k, 0].cpu().numpy()
+           for _ in range(3)]
+    want = oracle.encode_coeffs(*rgb, 4096, 4096).reshape(-1)
+    if want.size > got.size:
+        idx = np.sort(np.random.default_rng(0x6A70657A64).choice(want.size, got.size, replace=False))
+        want = want[idx]
+    assert np.array_equal(got, want.astype(np.float32))
 
 
 def test_misaligned_coefficient_pointer_is_refused_not_faulted(J):

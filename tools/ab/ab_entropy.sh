@@ -9,7 +9,7 @@ export TMPDIR=/tmp
 ROOT=$PWD
 for lib in $ROOT/ab/libjpezy_*.so; do
   name=$(basename $lib .so); name=${name#libjpezy_}
-  line=$(JPEZY_LIB=$lib timeout -k 10 200 python3 bench.py --workload encode4096_jpg --steps 100 --warmup 10 --repeats 5 --no-cpu 2>/dev/null | tail -1)
+  line=$(JPEZY_LIB=$lib timeout -k 10 200 python3 bench.py --workload encode4096_jpg --steps 100 --warmup 10 --repeats 5 --no-cpu --full 2>/dev/null | tail -1)
   echo "$name $(echo "$line" | python3 -c 'import sys,json; d=json.loads(sys.stdin.readline()); r=d["roofline"]; print("planes->jpg %.2f us/step, entropy stage %.2f us, frac %.4f" % (d["ms_per_step"]*1e3, r["avg_step_ms_hip_events"]*1e3, r["frac"]))' 2>&1 | tail -1)" | tee -a $OUT
   (cd /tmp && rm -rf /tmp/rp_en && JPEZY_LIB=$lib timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/rp_en -o en -- python3 $ROOT/tools/profile/entropy_profile.py > /dev/null 2>&1
    f=$(find /tmp/rp_en -name '*kernel_stats.csv' | head -1)

@@ -29,7 +29,7 @@ echo "scale_node: $HAVE GPU(s) visible, N up to $NMAX" >&2
 for N in 1 2 4 8; do
   [ "$N" -le "$NMAX" ] && [ "$N" -le "$HAVE" ] || continue
   echo "== harness (RCCL), N = $N" >&2
-  timeout -k 10 1500 python3 bench.py --gpus "$N" --steps 20 --warmup 5 --no-cpu --no-native-multi --no-others $([ "$N" = 1 ] && echo --batch) \
+  timeout -k 10 1500 python3 bench.py --gpus "$N" --steps 20 --warmup 5 --full --no-cpu --no-native-multi --no-others $([ "$N" = 1 ] && echo --batch) \
     | tail -1 | python3 -c 'import sys, json; d = json.loads(sys.stdin.readline()); d["leg"] = "harness_rccl"; print(json.dumps(d))' >> "$OUT" \
     || echo "{\"leg\": \"harness_rccl\", \"n_gpus\": $N, \"error\": \"bench.py failed\"}" >> "$OUT"
 done

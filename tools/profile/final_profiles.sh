@@ -13,8 +13,8 @@ cp gpurun_out/prof_${TAG}_dec/summary.txt $OUT/${TAG}_dec_summary.txt
 cp gpurun_out/prof_${TAG}_dec/kt_*kernel_stats.csv $OUT/${TAG}_dec_kernel_stats.csv 2>/dev/null
 tail -1 gpurun_out/prof_${TAG}_dec/kt.stdout > $OUT/${TAG}_bench_under_rocprof_decode4096.json
 for w in encode4096 decode4096 gray8k batch1080p gray8k_decode; do
-  python3 bench.py --workload $w 2>/dev/null | tail -1 > $OUT/${TAG}_bench_$w.json
-  python3 bench.py --workload $w --pipelined --no-cpu 2>/dev/null | tail -1 > $OUT/${TAG}_bench_pipelined_$w.json
+  python3 bench.py --workload $w --full 2>/dev/null | tail -1 > $OUT/${TAG}_bench_$w.json
+  python3 bench.py --workload $w --pipelined --no-cpu --full 2>/dev/null | tail -1 > $OUT/${TAG}_bench_pipelined_$w.json
   echo "$w done"
 done
 python3 tools/measure/measure_huffdec.py > $OUT/${TAG}_huffdec.txt 2>&1

@@ -47,7 +47,8 @@ enum jpezy_status {
     JPEZY_E_BADARG = -1,      /* null pointer, non-positive or > 65535 dimension, ...                */
     JPEZY_E_NODEVICE = -2,    /* no HIP device / device index out of range                           */
     JPEZY_E_HIP = -3,         /* a HIP runtime call failed (message in jpezy_hip_last_error)         */
-    JPEZY_E_UNSUPPORTED = -4, /* decode layout other than jpezy's own 2x2,1x1,1x1 3-component files  */
+    JPEZY_E_UNSUPPORTED = -4, /* decode layout other than jpezy's own 2x2,1x1,1x1 3-component files,
+                                 or a DC coefficient outside int16 (the reference's int predictor)   */
     JPEZY_E_FORMAT = -5,      /* malformed JPEG / Huffman stream (the reference throws runtime_error) */
     JPEZY_E_NOSPACE = -6      /* output buffer too small                                             */
 };

@@ -414,8 +414,13 @@ try {
     if (int r2 = c->h_small.reserve(sizeof(HD::ScanState))) return r2;
     if (int r2 = c->h_dcbuf.reserve(total_blocks * sizeof(int16_t) + 64)) return r2;
     size_t max_dc = 0;
-    for (int i = 0; i < info->ncomp; ++i) max_dc = std::max(max_dc, nmcu * (size_t)(info->H[i] * info->V[i]));
-    if (int r2 = c->h_dc.reserve(std::max((2 * max_dc + 2), (size_t)n_sub) * sizeof(unsigned long long))) return r2;
+    unsigned max_count = 1;
+    for (int i = 0; i < info->ncomp; ++i) {
+        max_dc = std::max(max_dc, nmcu * (size_t)(info->H[i] * info->V[i]));
+        max_count = std::max(max_count, (unsigned)(info->H[i] * info->V[i]));
+    }
+    if (int r2 = c->h_dc.reserve(std::max(std::max((2 * max_dc + 2), (size_t)n_sub) * sizeof(unsigned long long),
+                                          HD::dc_prefix_scratch_ints(nmcu, max_count) * sizeof(int)))) return r2;
     if (int r2 = c->e_tmp.reserve(E::scan_tmp_elems(std::max(std::max(nc, (size_t)n_sub), max_dc)) * sizeof(unsigned long long))) return r2;
 
     // tables
@@ -509,7 +514,8 @@ try {
                                 (const unsigned long long*)c->h_off.p, d_coeffs, (int16_t*)c->h_dcbuf.p, guarded, s));
         // DC differences -> values, all components in two launches (round 2: gather, two-launch scan, scatter per component = twelve)
         const StreamGeom g = jpezy_internal_stream_geom(*info);
-        HIP_TRY(HD::launch_dc_prefix(d_coeffs, (int16_t*)c->h_dcbuf.p, g.bpm, g.ncomp, g.cstart, g.ccount, nmcu, (int*)c->h_dc.p, guarded ? d_st : nullptr, s));
+        HIP_TRY(HD::launch_dc_prefix(d_coeffs, (int16_t*)c->h_dcbuf.p, g.bpm, g.ncomp, g.cstart, g.ccount, nmcu, (int*)c->h_dc.p, guarded ? d_st : nullptr,
+                                     &d_st->error, s));
         return JPEZY_OK;
     };
     if (!dbg)

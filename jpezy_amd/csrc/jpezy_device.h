@@ -153,4 +153,16 @@ struct GenericDecParams {
 };
 hipError_t launch_dequant_idct_generic(const GenericDecParams& p, hipStream_t stream);
 
+#if defined(__HIPCC__)
+// The reference's sample int(sum / 4 + sl) (ref decoder/jpezy_decoder.hpp:667) as its x86-64 build executes it: cvttsd2si truncates
+// toward zero and gives INT_MIN for every value outside [-2^31, 2^31) and for NaN, where v_cvt_i32_f64 saturates (INT_MAX above the
+// range: 255 instead of the reference's 0).  Every place where a reference-order sum becomes a sample goes through it; such sums
+// leave the range only with 16-bit quantisers (|sum| / 4 up to 64 * 32768 * 65535 / 4 = 3.4e10).  The fast paths' samples stay
+// below 2^28 by their coefficient gates and keep the plain conversion.  Same rule: oracle jo_ref_int.
+__device__ __forceinline__ int ref_int(double x)
+{
+    return (x >= -2147483648.0 && x < 2147483648.0) ? (int)x : (int)0x80000000u;
+}
+#endif
+
 }  // namespace jpezy_dev

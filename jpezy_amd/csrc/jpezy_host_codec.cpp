@@ -588,6 +588,11 @@ int read_jpeg_impl(const uint8_t* data, size_t len, jpezy_frame_info* info, int1
                 int cat = decode_symbol(r, dc);
                 if (cat < 0 || cat > 16) return fail(JPEZY_E_FORMAT, "read_jpeg: decode_huffman");
                 if (cat) pred[sc] += extend(r.get(cat), cat);
+                // the reference's predictor and dct[0] are int (:596-597, 692-693); the coefficients here are int16
+                if (pred[sc] < -32768 || pred[sc] > 32767)
+                    return fail(JPEZY_E_UNSUPPORTED, ("read_jpeg: DC of component " + std::to_string(sc) + " leaves int16 (" +
+                                                      std::to_string(pred[sc]) + ") in block " + std::to_string((z - coeffs) / 64) +
+                                                      " (MCU " + std::to_string(mcu) + ")").c_str());
                 z[0] = (int16_t)pred[sc];
                 int k = 1;
                 while (k < 64) {

@@ -49,13 +49,14 @@ hipError_t launch_emit_batch(const Setup* setups, const uint32_t* U, BatchFile* 
 // short streams that share ONE set of tables (setups[0]) and start in the known state: a lane walks a whole stream (symbols, coefficients, DC
 // predictors); needs the unstuffed streams (launch_unstuff_*_batch) and zeroed coefficients; sets F[].error / last_bit like the emit launch
 hipError_t launch_stream_per_lane(const Setup* setups, const uint32_t* U, BatchFile* F, unsigned n_files, int16_t* coeffs, hipStream_t s);
-hipError_t launch_dc_prefix_batch(int16_t* coeffs, const BatchFile* F, const unsigned* active, unsigned n_files, hipStream_t s);
+// F[f].error is set when a DC value of file f leaves int16 (the host decoder then refuses the file: jpezy_host::read_jpeg)
+hipError_t launch_dc_prefix_batch(int16_t* coeffs, BatchFile* F, const unsigned* active, unsigned n_files, hipStream_t s);
 
 // ---- single scan.  Round 4: the whole chain is enqueued without a host synchronisation in between -- the numbers the host used to fetch
 // after the unstuffing (where the segment ends, how many subsequences hold data) stay on the device in a ScanState, which the kernels read.
 struct ScanState {
     unsigned pad0;
-    unsigned error;                     // emit launch: an invalid code
+    unsigned error;                     // emit launch: an invalid code or a DC category 16; DC launches: a DC value outside int16
     unsigned long long last_bit;        // emit launch: the bit behind the last block (all ones: not reached)
     unsigned changed[4];                // first synchronisation launch (see launch_sync)
     unsigned long long first_marker;    // offset of the first marker in the uploaded bytes (all ones: none)
@@ -120,8 +121,9 @@ hipError_t launch_emit(const Setup* S, const uint32_t* U, size_t u_words, unsign
 size_t dc_prefix_scratch_ints(size_t nmcu, unsigned max_count);
 // guard (may be null): leave at once unless scan_settled(guard)
 // dc (may be null): the differences lie in dc[block] instead of the coefficients' DC slots (launch_emit's dc_out); the values go to the coefficients
+// range_error: set to 1 when a DC value leaves int16 (ScanState::error: the host decoder then refuses the file)
 hipError_t launch_dc_prefix(int16_t* coeffs, int16_t* dc, unsigned bpm, unsigned ncomp, const unsigned cstart[3], const unsigned ccount[3], size_t nmcu,
-                            int* scratch, const ScanState* guard, hipStream_t s);
+                            int* scratch, const ScanState* guard, unsigned* range_error, hipStream_t s);
 
 }  // namespace huffdec
 }  // namespace jpezy_dev

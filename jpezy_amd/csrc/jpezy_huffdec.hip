@@ -382,7 +382,10 @@ __global__ __launch_bounds__(WGS) void emit_kernel(const Setup* gS, const uint32
 // ---- DC differences -> absolute values, per component (pre_DC, ref :611-614); component q owns blocks [cstart[q], cstart[q] + ccount[q]) of
 // every MCU.  All components in THREE launches (grid.y = component; round 2 took four per component: gather, two-launch scan, scatter): (1) every workgroup turns its 2,048
 // DC differences into prefix sums inside the workgroup, in place, and leaves its total; (2) one workgroup per component scans the totals;
-// (3) every workgroup adds what came before it.  Sums wrap in 32 bits and are stored as int16: the low 16 bits are those of the true sum.
+// (3) every workgroup adds what came before it.  The differences fit int16 (a DC category 16 is an emit error), so the true value is known
+// as long as it stays inside int16; launch (1) leaves the smallest and largest running sum inside the workgroup as well, and launch (3) sets
+// range_error when what came before plus either leaves int16 -- the first workgroup where the value leaves it sees it (every value in front
+// was in range, so `before` is exact there).  The reference's predictor is an int (ref :596-597): such a file is the host decoder's to refuse.
 struct DcGeom { unsigned bpm, ncomp, cstart[3], ccount[3]; unsigned long long nmcu; };
 constexpr int DC_PER_WG = 2048;
 __device__ __forceinline__ size_t dc_slot(const DcGeom& g, unsigned comp, size_t j)
@@ -393,9 +396,10 @@ __device__ __forceinline__ size_t dc_slot(const DcGeom& g, unsigned comp, size_t
 }
 // dc (may be null; round 4): the DC differences lie in an array of their own, dc[block] (the coefficient launch put them there): the first launch
 // sums in place THERE -- 2 bytes per block instead of a 128-byte line per block -- and the second one writes the values to the coefficients.
+// totals[comp * wg_per_comp + wg]: the workgroup's total; the same index + 3 * wg_per_comp / + 6 * wg_per_comp: its smallest / largest running sum
 __global__ __launch_bounds__(256) void dc_local_kernel(int16_t* coeffs, int16_t* dc, DcGeom g, int* totals, unsigned wg_per_comp, const ScanState* guard)
 {
-    __shared__ int wsum[4];
+    __shared__ int wsum[4], wmin[4], wmax[4];
     if (guard && !scan_settled(guard->changed, guard->changed2, guard->n_sub)) return;
     const unsigned comp = blockIdx.y;
     const size_t nd = (size_t)g.nmcu * g.ccount[comp], j0 = (size_t)blockIdx.x * DC_PER_WG + (size_t)threadIdx.x * 8;
@@ -421,16 +425,30 @@ __global__ __launch_bounds__(256) void dc_local_kernel(int16_t* coeffs, int16_t*
         if (q < wv) woff += wsum[q];
         tot += wsum[q];
     }
-    int run = woff + inc - sum;
+    int run = woff + inc - sum, mn = 0x7FFFFFFF, mx = -0x7FFFFFFF - 1;
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
         run += v[q];
         if (j0 + q < nd) {
             if (dc) dc[dc_slot(g, comp, j0 + q) >> 6] = (int16_t)run;
             else coeffs[dc_slot(g, comp, j0 + q)] = (int16_t)run;
+            mn = min(mn, run);
+            mx = max(mx, run);
         }
     }
-    if (threadIdx.x == 0) totals[(size_t)comp * wg_per_comp + blockIdx.x] = tot;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        mn = min(mn, __shfl_xor(mn, d, 64));
+        mx = max(mx, __shfl_xor(mx, d, 64));
+    }
+    if (lane == 0) { wmin[wv] = mn; wmax[wv] = mx; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const size_t t = (size_t)comp * wg_per_comp + blockIdx.x;
+        totals[t] = tot;
+        totals[t + 3 * (size_t)wg_per_comp] = min(min(wmin[0], wmin[1]), min(wmin[2], wmin[3]));
+        totals[t + 6 * (size_t)wg_per_comp] = max(max(wmax[0], wmax[1]), max(wmax[2], wmax[3]));
+    }
 }
 // totals -> what came before each workgroup (exclusive), one workgroup per component, 256 totals per step with a running carry
 __global__ __launch_bounds__(256) void dc_totals_kernel(int* totals, DcGeom g, unsigned wg_per_comp, const ScanState* guard)
@@ -470,14 +488,13 @@ __global__ __launch_bounds__(256) void dc_totals_kernel(int* totals, DcGeom g, u
 constexpr unsigned DC_SELF_SUM_MAX = 1024;
 template <bool SELF_SUM>
 __global__ __launch_bounds__(256) void dc_add_kernel(int16_t* coeffs, const int16_t* dc, DcGeom g, const int* totals, unsigned wg_per_comp,
-                                                     const ScanState* guard)
+                                                     const ScanState* guard, unsigned* range_error)
 {
     __shared__ int red[4];
     if (guard && !scan_settled(guard->changed, guard->changed2, guard->n_sub)) return;
     const unsigned comp = blockIdx.y;
     const size_t nd = (size_t)g.nmcu * g.ccount[comp], j0 = (size_t)blockIdx.x * DC_PER_WG + (size_t)threadIdx.x * 8;
     if ((size_t)blockIdx.x * DC_PER_WG >= nd) return;
-    if (blockIdx.x == 0 && !dc) return;                                     // (nothing comes before the first workgroup; with dc it still has to deliver)
     int before;
     if (SELF_SUM) {
         int sum = 0;
@@ -490,6 +507,12 @@ __global__ __launch_bounds__(256) void dc_add_kernel(int16_t* coeffs, const int1
     } else {
         before = totals[(size_t)comp * wg_per_comp + blockIdx.x];
     }
+    if (threadIdx.x == 0) {
+        const size_t t = (size_t)comp * wg_per_comp + blockIdx.x;
+        if ((long long)before + totals[t + 3 * (size_t)wg_per_comp] < -32768 || (long long)before + totals[t + 6 * (size_t)wg_per_comp] > 32767)
+            *range_error = 1u;
+    }
+    if (blockIdx.x == 0 && !dc) return;                                     // (nothing comes before the first workgroup; with dc it still has to deliver)
 #pragma unroll
     for (int q = 0; q < 8; ++q)
         if (j0 + q < nd) {
@@ -816,7 +839,7 @@ __global__ __launch_bounds__(WGS) void emit_batch_kernel(const Setup* setups, co
 
 // DC differences -> absolute values (pre_DC, ref :611-614): one workgroup per (file, component) walks the component's DC terms in
 // scan order, 2048 per step with a running carry
-__global__ __launch_bounds__(256) void dc_prefix_batch_kernel(int16_t* coeffs, const BatchFile* F, const unsigned* active)
+__global__ __launch_bounds__(256) void dc_prefix_batch_kernel(int16_t* coeffs, BatchFile* F, const unsigned* active)
 {
     __shared__ long long wsum[4];
     const unsigned f = blockIdx.x, comp = blockIdx.y;
@@ -861,6 +884,7 @@ __global__ __launch_bounds__(256) void dc_prefix_batch_kernel(int16_t* coeffs, c
             if (j < nd) {
                 const size_t mcu = j / count, t = j - mcu * count;
                 co[(mcu * bpm + start + t) * 64] = (int16_t)run;
+                if (run < -32768 || run > 32767) F[f].error = 1u;      // the reference's int predictor leaves int16: the host decoder's
             }
         }
         carry += tot;
@@ -897,6 +921,7 @@ __global__ __launch_bounds__(WGS) void stream_per_lane_kernel(const Setup* setup
     for (unsigned blk = 0, b = 0; blk < total; ++blk) {
         const unsigned comp = (ncomp > 2 && b >= c2) ? 2u : (ncomp > 1 && b >= c1) ? 1u : 0u;
         const int v = pred[comp] + out[(size_t)blk * 64];
+        if (v < -32768 || v > 32767) F[f].error = 1u;                  // (as in dc_prefix_batch_kernel)
         pred[comp] = v;
         out[(size_t)blk * 64] = (int16_t)v;
         b = b + 1 == bpm ? 0 : b + 1;
@@ -957,9 +982,9 @@ hipError_t launch_emit(const Setup* S, const uint32_t* U, size_t u_words, unsign
                        blocks_before, out, dc_out, guarded ? 1 : 0);
     return hipGetLastError();
 }
-size_t dc_prefix_scratch_ints(size_t nmcu, unsigned max_count) { return 3 * ((nmcu * max_count + DC_PER_WG - 1) / DC_PER_WG + 1); }
+size_t dc_prefix_scratch_ints(size_t nmcu, unsigned max_count) { return 9 * ((nmcu * max_count + DC_PER_WG - 1) / DC_PER_WG + 1); }
 hipError_t launch_dc_prefix(int16_t* coeffs, int16_t* dc, unsigned bpm, unsigned ncomp, const unsigned cstart[3], const unsigned ccount[3], size_t nmcu,
-                            int* scratch, const ScanState* guard, hipStream_t s)
+                            int* scratch, const ScanState* guard, unsigned* range_error, hipStream_t s)
 {
     DcGeom g;
     g.bpm = bpm; g.ncomp = ncomp; g.nmcu = nmcu;
@@ -974,10 +999,12 @@ hipError_t launch_dc_prefix(int16_t* coeffs, int16_t* dc, unsigned bpm, unsigned
         return e ? (size_t)std::atoll(e) : (size_t)DC_SELF_SUM_MAX;
     }();
     if (wgs <= self_sum_max) {
-        hipLaunchKernelGGL(dc_add_kernel<true>, dim3((unsigned)wgs, ncomp), dim3(256), 0, s, coeffs, (const int16_t*)dc, g, (const int*)scratch, (unsigned)wgs + 1, guard);
+        hipLaunchKernelGGL(dc_add_kernel<true>, dim3((unsigned)wgs, ncomp), dim3(256), 0, s, coeffs, (const int16_t*)dc, g, (const int*)scratch, (unsigned)wgs + 1, guard,
+                           range_error);
     } else {
         hipLaunchKernelGGL(dc_totals_kernel, dim3(ncomp), dim3(256), 0, s, scratch, g, (unsigned)wgs + 1, guard);
-        hipLaunchKernelGGL(dc_add_kernel<false>, dim3((unsigned)wgs, ncomp), dim3(256), 0, s, coeffs, (const int16_t*)dc, g, (const int*)scratch, (unsigned)wgs + 1, guard);
+        hipLaunchKernelGGL(dc_add_kernel<false>, dim3((unsigned)wgs, ncomp), dim3(256), 0, s, coeffs, (const int16_t*)dc, g, (const int*)scratch, (unsigned)wgs + 1, guard,
+                           range_error);
     }
     return hipGetLastError();
 }
@@ -1042,7 +1069,7 @@ hipError_t launch_emit_batch(const Setup* setups, const uint32_t* U, BatchFile* 
     hipLaunchKernelGGL(emit_batch_kernel, dim3(n_wg), dim3(WGS), 0, s, setups, U, F, wg_file, wg_first, active, exit_state, blocks_before, coeffs);
     return hipGetLastError();
 }
-hipError_t launch_dc_prefix_batch(int16_t* coeffs, const BatchFile* F, const unsigned* active, unsigned n_files, hipStream_t s)
+hipError_t launch_dc_prefix_batch(int16_t* coeffs, BatchFile* F, const unsigned* active, unsigned n_files, hipStream_t s)
 {
     if (!n_files) return hipSuccess;
     hipLaunchKernelGGL(dc_prefix_batch_kernel, dim3(n_files, 3), dim3(256), 0, s, coeffs, F, active);

@@ -126,6 +126,8 @@ static_assert(TABLE_U16 == 2048u, "Walk::tdm places the table selector at the bi
 // it: the stream is bad); a synchronisation pass -- which may well be decoding from a wrong guess, i.e. garbage -- abandons the block
 // (one bit on for a non-code) and carries on, so that it can still fall into step further down.
 // EMIT: coefficients of blocks gidx + nblocks < total go to out (DC: the difference, made absolute by the DC pass; to dc_out[block] if given).
+// A DC category 16 (|difference| >= 32768: no int16 holds it, and only DC symbols have 16 value bits) returns false as well: such a
+// file is the host decoder's, which keeps the reference's int predictor and refuses the file if a DC value leaves int16.
 template <bool EMIT, class CursorT>
 JPEZY_HD bool decode_step(const uint16_t* tabs, unsigned bpm, unsigned tdmask, CursorT& c, Walk& s,
                                             unsigned long long gidx, unsigned total, int16_t* out, int16_t* dc_out = nullptr)
@@ -141,7 +143,7 @@ JPEZY_HD bool decode_step(const uint16_t* tabs, unsigned bpm, unsigned tdmask, C
     const unsigned kk = s.k + run + 1u;                               // zig-zag index after this symbol (beyond 63: the block is over)
     if (EMIT) {
         const unsigned sz = (e >> 5) & 31u;
-        if (sz == E_S_NONE || (run != E_RUN_END && kk > 64u)) return false;
+        if (sz >= 16u || (run != E_RUN_END && kk > 64u)) return false;         // (E_S_NONE = 31, or a DC category 16)
         const bool dc_sym = dc_out && s.k == 0u;                      // (a DC difference of zero has no value bits but is written all the same:
         if ((sz || dc_sym) && gidx + s.nblocks < total) {             //  dc_out is not zeroed beforehand)
             const unsigned len = skipm1 + 1u - sz;

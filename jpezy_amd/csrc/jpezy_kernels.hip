@@ -506,7 +506,7 @@ __device__ __forceinline__ int exact_idct_sample_sparse(const int2* __restrict__
         const double cv = (!v) ? JPEZY_S : 1.0, cu = (!u) ? JPEZY_S : 1.0;
         sum += cu * cv * e.y * c_cos[u * 8 + x] * c_cos[v * 8 + y];
     }
-    return (int)(sum / 4 + 128);
+    return ref_int(sum / 4 + 128);
 }
 
 // Sample of the reference, int(sum / 4 + 128) (ref :667), from the fast row sum, plus the guard key of the fast path.  v is
@@ -961,8 +961,9 @@ __global__ __launch_bounds__(64 * WPB, GRAY ? JPEZY_DEC_WAVES_GRAY : JPEZY_DEC_W
                     } else if (!GRAY) {
 #pragma unroll
                         for (int k = 0; k < 8; ++k) {
-                            if ((myflags >> (16 + k)) & 1u) Cb[k] = patch[lane * 16 + k] - 128;
-                            if ((myflags >> (24 + k)) & 1u) Cr[k] = patch[lane * 16 + 8 + k] - 128;
+                            // modulo 2^32: a sample of a forced wave may be INT_MIN (ref_int); step 5 takes it back exactly
+                            if ((myflags >> (16 + k)) & 1u) Cb[k] = (int)((unsigned)patch[lane * 16 + k] - 128u);
+                            if ((myflags >> (24 + k)) & 1u) Cr[k] = (int)((unsigned)patch[lane * 16 + 8 + k] - 128u);
                         }
                     }
                 }
@@ -1034,7 +1035,9 @@ __global__ __launch_bounds__(64 * WPB, GRAY ? JPEZY_DEC_WAVES_GRAY : JPEZY_DEC_W
 #pragma unroll
             for (int cc = 0; cc < 2; ++cc) {
                 const int c = 2 * q + cc;
-                const double up = (double)Cb[c], vp = (double)Cr[c];       // (sample - 128, subtracted as integers above)
+                // sample - 128, subtracted as integers above modulo 2^32: the sample is restored and the 128 subtracted in doubles,
+                // the reference's (up - 0x80) (ref :567-578) also for a sample of INT_MIN
+                const double up = (double)(int)((unsigned)Cb[c] + 128u) - 128.0, vp = (double)(int)((unsigned)Cr[c] + 128u) - 128.0;
                 const double pr_ = vp * 1.4020, pg1 = up * 0.3441, pg2 = vp * 0.7139, pb_ = up * 1.7718;
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {

@@ -154,7 +154,7 @@ __global__ __launch_bounds__(64) void generic_idct_kernel(GenericDecParams p, lo
                 sum += cu * cv * dct[v * 8 + uu] * c_cos[uu * 8 + x] * c_cos[v * 8 + y];
             }
         }
-        p.samples[gq * 64 + lane] = (int)(sum / 4 + p.level);
+        p.samples[gq * 64 + lane] = ref_int(sum / 4 + p.level);
         done += 64;
     }
     if (done && lane == 0) atomicAdd(p.fallback_count + (blockIdx.x & (COUNTER_SHARDS - 1)), (unsigned long long)done);

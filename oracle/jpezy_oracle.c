@@ -7,6 +7,7 @@
 #include "jpezy_oracle.h"
 #include "../include/jpezy_constants.h"
 
+#include <limits.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -713,6 +714,9 @@ static int decode_huffman(dstate* d, int sc, int pred_dct[3], int16_t* blk)
         return -1;
     }
     pred_dct[sc] += dc_diff;
+    /* the reference keeps the predictor and dct[0] as int (ref :596-597, 692-693); coefficients here are int16: a DC
+       outside it is reported (JO_E_DC_RANGE) rather than wrapped */
+    if (pred_dct[sc] < INT16_MIN || pred_dct[sc] > INT16_MAX) return JO_E_DC_RANGE;
     blk[0] = (int16_t)pred_dct[sc];
 
     for (int k = 1; k < 64;) {
@@ -767,7 +771,7 @@ int jo_read_jpeg(const uint8_t* data, size_t len, jo_frame_info* info, int16_t* 
         for (size_t m = 0; !rc && m < nmcu; ++m) {
             for (int sc = 0; !rc && sc < info->ncomp; ++sc)                   /* decode_mcu, :504-528 */
                 for (int kb = 0; kb < info->H[sc] * info->V[sc]; ++kb, out += 64)
-                    if (decode_huffman(d, sc, pred_dct, out)) { rc = -2; break; }
+                    if ((rc = decode_huffman(d, sc, pred_dct, out))) { if (rc != JO_E_DC_RANGE) rc = -2; break; }
             if (!rc && info->restart_interval) {                              /* :152-163 */
                 if (++restart_counter >= (size_t)info->restart_interval) {
                     restart_counter = 0;
@@ -779,6 +783,15 @@ int jo_read_jpeg(const uint8_t* data, size_t len, jo_frame_info* info, int16_t* 
     }
     free(d);
     return rc;
+}
+
+/* The reference's int(sum / 4 + sl) (ref :667) as its x86-64 build executes it: cvttsd2si truncates toward zero and returns
+   the "integer indefinite" INT_MIN for every value outside [-2^31, 2^31) (and for NaN).  A plain (int) cast of such a value
+   is undefined in C, and other hosts saturate: the rule is spelled out.  Reached with 16-bit quantisers only (|sum| / 4 up
+   to 64 * 32768 * 65535 / 4 = 3.4e10). */
+int jo_ref_int(double x)
+{
+    return (x >= -2147483648.0 && x < 2147483648.0) ? (int)x : INT_MIN;
 }
 
 /* ------------------------------------------------------------------------------------------------ */
@@ -798,7 +811,7 @@ void jo_idct_block(const int dct[64], int precision, int out[64])
                     sum += cu * cv * dct[v * 8 + u] * COS_TABLE[u * 8 + x] * COS_TABLE[v * 8 + y];
                 }
             }
-            out[y * 8 + x] = (int)(sum / 4 + sl);
+            out[y * 8 + x] = jo_ref_int(sum / 4 + sl);
         }
     }
 }

@@ -39,6 +39,7 @@ void jo_fdct_block(const int pic[64], int out[64]);          /* DCT(): int(sum*c
 void jo_quantize_block(int blk[64], int cs);                 /* quantization(cs): blk[i] /= qt[i] */
 /* ---- a12/a13 (ref decoder/jpezy_decoder.hpp:645-670) ---- */
 void jo_idct_block(const int dct[64], int precision, int out[64]);
+int jo_ref_int(double x);                                     /* int() of the reference on x86-64: INT_MIN outside the range */
 
 /* MCU grid (ref jpezy_encoder.hpp:55-56) */
 int jo_mcu_cols(int W);
@@ -85,8 +86,10 @@ typedef struct jo_frame_info {
  * a11 + marker parser (ref jpezy_decoder.hpp:171-502, 583-642): parse headers, Huffman-decode the scan.
  * coeffs: [mcu][blk][64] int16 in ZIG-ZAG order (position k holds the k-th decoded coefficient; the
  * reference stores it at dct[ZZ[k]]), DC already un-differenced.  Pass coeffs=NULL to parse headers only.
- * Returns 0 ok, negative on error (the reference returns an empty optional).
+ * Returns 0 ok, negative on error (the reference returns an empty optional); JO_E_DC_RANGE: the stream is valid but a
+ * DC predictor leaves int16 (the reference's int predictor, ref :596-597, holds it; these coefficients cannot).
  */
+#define JO_E_DC_RANGE (-4)
 int jo_read_jpeg(const uint8_t* data, size_t len, jo_frame_info* info, int16_t* coeffs, size_t coeff_cap);
 
 /*

@@ -71,6 +71,8 @@ def lib():
         L.jo_qt.argtypes = [C.c_int]
         L.jo_cos_table.restype = C.POINTER(C.c_double)
         L.jo_inv_sqrt2.restype = C.c_double
+        L.jo_ref_int.argtypes = [C.c_double]
+        L.jo_ref_int.restype = C.c_int
         _LIB = L
     return _LIB
 
@@ -120,6 +122,9 @@ def write_jpeg(coeffs, W, H, gray=False, comment=None):
 
 def encode_jpeg(r, g, b, W, H, gray=False):
     return write_jpeg(encode_coeffs(r, g, b, W, H, gray), W, H, gray)
+
+
+DC_RANGE = -4          # jo_read_jpeg: a DC predictor leaves int16 (JO_E_DC_RANGE)
 
 
 def read_jpeg(data):

@@ -71,3 +71,36 @@ def test_tolerance_mode_fp32_luma_error_is_below_one():
     assert err < (13 + 2) * 2.0 ** -24 * 2.0 ** 19 < 1.0, err      # the bound quoted in jpezy_kernels.hip: 0.47
     # and therefore truncated samples differ by at most one
     assert int(np.abs(np.trunc(got.astype(np.float64)) - np.trunc(ref.astype(np.float64))).max()) <= 1
+
+
+def ref_order(cq, cos, s2):
+    """the reference's own value sum / 4 + 128 (ref decoder/jpezy_decoder.hpp:657-667: v outer, u inner, FP64, its cos table and 1/sqrt2)
+    of [n, 8 (v), 8 (u)] products coefficient * quantiser -> [n, y, x]"""
+    cos = np.asarray(cos, dtype=np.float64).reshape(8, 8)
+    s = np.zeros((cq.shape[0], 8, 8))
+    for v in range(8):
+        cv = s2 if v == 0 else 1.0
+        for u in range(8):
+            cu = s2 if u == 0 else 1.0
+            s = s + ((cu * cv) * cq[:, v, u])[:, None, None] * cos[u][None, None, :] * cos[v][None, :, None]
+    return s / 4 + 128
+
+
+def _fast_vs_reference_order(oracle, limit, seed):
+    L = oracle.lib()
+    cos, s2 = [L.jo_cos_table()[i] for i in range(64)], L.jo_inv_sqrt2()
+    cq = _inputs(limit, np.random.default_rng(seed), n=2000)
+    return float(np.abs(samples(cq, np.float64) - ref_order(cq, cos, s2)).max())
+
+
+def test_exact_mode_guard_covers_the_reference_order_sum(oracle):
+    """what the 2^-18 guard band must cover is the distance of the fast path to the reference's OWN rounded sum (jpezy_capi.hip
+    upload_dequant: its rounding is the larger share), not to the true value: margin of at least 8 at |c * Q| = 2^23"""
+    err = _fast_vs_reference_order(oracle, 1 << 23, 7)
+    assert err * 8 <= 2.0 ** -18, err
+
+
+def test_generic_gate_covers_the_reference_order_sum(oracle):
+    """the generic kernel's fast path (FP64 butterflies, jpezy_kernels_generic.hip) at its gate |c * Q| <= 2^15 against its G_EPS = 2^-18"""
+    err = _fast_vs_reference_order(oracle, 1 << 15, 8)
+    assert err * 8 <= 2.0 ** -18, err

@@ -97,6 +97,9 @@ void jpezy_ctx_set_host_chunk_bytes(jpezy_ctx* ctx, size_t n);
  * consecutive frames of one plane (>= W*H); asynchronous on `stream`, a hipStream_t with HIP's own
  * meaning (NULL = the default stream; jpezy_ctx_stream() = the context's private stream).  Used by
  * batch drivers / the benchmark with inputs resident in HBM.
+ * Frame counts: any n_frames > 0.  The frame index is a grid dimension, so a batch of more than 65535 frames is enqueued as
+ * several launches of at most 65535 frames each (the same holds for jpezy_dequant_idct_dev and
+ * jpezy_dequant_idct_generic_batch_dev); the host-buffer entry points cut their chunks without regard to that limit.
  */
 int jpezy_fdct_quant_dev(jpezy_ctx* ctx, const uint8_t* d_r, const uint8_t* d_g, const uint8_t* d_b,
                          size_t plane_stride, int W, int H, int gray, int n_frames, int16_t* d_coeffs,
@@ -146,6 +149,7 @@ int jpezy_dequant_idct_generic_dev(jpezy_ctx* ctx, const int16_t* d_coeffs, cons
  * The same for n_frames frames of ONE layout, size and set of quantiser tables in one pair of launches (the loop a caller with many
  * small files of a layout would otherwise run): frame f's coefficients at d_coeffs + f * (blocks of a frame) * 64, its planes at
  * d_r/d_g/d_b + f * plane_stride (>= W*H, a multiple of 4).  jpezy_decode_jpeg_batch uses it for the layouts that are not jpezy's own.
+ * Any n_frames > 0: batches of more than 65535 frames go out as several pairs of launches (the frame index is a grid dimension).
  */
 int jpezy_dequant_idct_generic_batch_dev(jpezy_ctx* ctx, const int16_t* d_coeffs, const uint16_t qt[4][64], int ncomp,
                                          const uint8_t comp_h[3], const uint8_t comp_v[3], const uint8_t comp_tq[3], int precision,
@@ -193,7 +197,19 @@ long jpezy_ctx_last_fallback_count(jpezy_ctx* ctx);
  */
 long jpezy_write_jpeg(const int16_t* coeffs, int W, int H, int gray, const char* comment, uint8_t* out,
                       size_t cap);
-size_t jpezy_jpeg_bound(int W, int H);   /* a cap that always suffices */
+/*
+ * The longest comment (bytes before the terminating NUL) any writer accepts: jpezy_write_jpeg[_batch], jpezy_write_jpeg_gpu[_batch,
+ * _dev], jpezy_encode_jpeg and jpezy_multi_encode / jpezy_encode_batch_multi all refuse a longer one with JPEZY_E_BADARG.  It is
+ * what makes the header fit 1024 bytes: 623 bytes of markers and tables + a COM segment of n + 5 bytes (marker, length, text, NUL).
+ */
+#define JPEZY_MAX_COMMENT 396
+/*
+ * A cap that always suffices for a comment of up to JPEZY_MAX_COMMENT bytes: 1024 bytes of header + 2688 bytes per MCU.  The worst
+ * MCU codes 4 x 1658 + 2 x 1660 bits (every AC coefficient a 16-bit code + 10 value bits, the DC difference 9 or 11 + 11 bits), i.e.
+ * 1244 bytes, 2488 if every byte were 0xFF and stuffed; the pad bits (one byte, two if stuffed) and the 2-byte EOI fit in the
+ * 200 bytes per MCU left over (tests/test_jpeg_bound.py).
+ */
+size_t jpezy_jpeg_bound(int W, int H);
 /*
  * The same serial tail for a batch of independent frames, spread over `threads` host threads (0 = all cores):
  * frame f reads coeffs + f*jpezy_coeff_count(W,H,gray) and writes at most `cap` bytes at out + f*cap; sizes[f]
@@ -210,6 +226,8 @@ int jpezy_write_jpeg_batch(const int16_t* coeffs, int W, int H, int gray, int n_
  * block is coded once; the sum is formed per 256 blocks and across them afterwards); the 0xFF00 stuffing of the reference's
  * bofstream is a second prefix sum.  out/sizes are host memory: frame f writes at
  * most cap bytes at out + f*cap and sizes[f] receives its length or a negative status.  Synchronous.
+ * Frame counts (here and in jpezy_write_jpeg_gpu_dev): any n_frames > 0.  The batch is coded in passes of at most 65535 frames (the
+ * frame index is a grid dimension) and at most 1 GiB of worst-case stream (208 bytes per block; at least one frame per pass).
  */
 long jpezy_write_jpeg_gpu(jpezy_ctx* ctx, const int16_t* d_coeffs, int W, int H, int gray, const char* comment,
                           uint8_t* out, size_t cap);

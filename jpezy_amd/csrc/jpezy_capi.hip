@@ -523,9 +523,11 @@ int jpezy_internal_generic_dev_core(jpezy_ctx* c, const int16_t* d_coeffs, const
     if (!d_coeffs) return JPEZY_OK;                            // geometry only
     if (n_frames < 1 || (n_frames > 1 && (plane_stride < (size_t)W * H || (plane_stride & 3))))
         return set_err(JPEZY_E_BADARG, "generic decoder, batch form: plane stride must hold a plane and be a multiple of 4");
-    if (int rc = c->scratch.reserve(nblk * 64 * sizeof(int) * (size_t)n_frames)) return rc;
     p.n_frames = n_frames;
     p.plane_stride = plane_stride;
+    const int per = generic_frames_per_launch(p);            // samples scratch: the frames of one launch (launches run in stream order)
+    if (per < 1) return set_err(JPEZY_E_UNSUPPORTED, "generic decoder: frame of more than 2^31 blocks");
+    if (int rc = c->scratch.reserve(nblk * 64 * sizeof(int) * (size_t)std::min(n_frames, per))) return rc;
     // per-component dequantiser constants (fast path) and integer quantisers (reference-order path), cached in the context
     const uint8_t tq3[3] = { comp_tq[0], (uint8_t)(ncomp > 1 ? comp_tq[1] : 0), (uint8_t)(ncomp > 2 ? comp_tq[2] : 0) };
     if (int rc = upload_dequant(c, qt, tq3, s)) return rc;

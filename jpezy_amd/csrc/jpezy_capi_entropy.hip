@@ -9,6 +9,7 @@ int jpezy_write_jpeg_batch(const int16_t* coeffs, int W, int H, int gray, int n_
                            size_t cap, long* sizes, int threads)
 try {
     if (!coeffs || !out || !sizes || n_frames <= 0) return set_err(JPEZY_E_BADARG, "write_jpeg_batch: bad argument");
+    if (int rc = check_comment(comment, "write_jpeg_batch")) return rc;
     const size_t cpf = jpezy_coeff_count(W, H, gray);
     if (!cpf) return set_err(JPEZY_E_BADARG, "write_jpeg_batch: bad dimensions");
     unsigned nt = threads > 0 ? (unsigned)threads : std::thread::hardware_concurrency();
@@ -169,10 +170,12 @@ int jpezy_write_jpeg_gpu_dev(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H
     if (int rc = jpezy_internal_check_dims(c, W, H, n_frames)) return rc;
     if (!d_coeffs || !d_out || !d_sizes) return set_err(JPEZY_E_BADARG, "write_jpeg_gpu_dev: null pointer");
     if (!aligned16(d_coeffs)) return set_err(JPEZY_E_BADARG, "write_jpeg_gpu_dev: d_coeffs must be 16-byte aligned");
+    if (int rc = check_comment(comment, "write_jpeg_gpu_dev")) return rc;
     HIP_TRY(hipSetDevice(c->device));
     if (int rc = ensure_code_tables(c)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    // header bytes: cached on the device per (W, H, comment) -- uploaded outside any capture on first use
+    // header bytes: cached on the device per (W, H, comment) -- uploaded outside any capture on first use; 1024 bytes hold the
+    // header with the longest comment allowed (JPEZY_MAX_COMMENT)
     uint8_t hdr[1024];
     const size_t hdr_len = jpezy_host::write_header(W, H, comment, hdr, sizeof hdr);
     if (!hdr_len) return set_err(JPEZY_E_BADARG, "write_jpeg_gpu_dev: comment too long");
@@ -255,6 +258,7 @@ int jpezy_write_jpeg_gpu_batch(jpezy_ctx* c, const int16_t* d_coeffs, int W, int
 try {
     if (int rc = jpezy_internal_check_dims(c, W, H, n_frames)) return rc;
     if (!d_coeffs || !out || !sizes) return set_err(JPEZY_E_BADARG, "write_jpeg_gpu: null pointer");
+    if (int rc = check_comment(comment, "write_jpeg_gpu")) return rc;
     HIP_TRY(hipSetDevice(c->device));
     if (int rc = ensure_code_tables(c)) return rc;
     const size_t nblk = (size_t)jpezy_mcu_cols(W) * jpezy_mcu_rows(H) * 6;
@@ -288,6 +292,7 @@ long jpezy_encode_jpeg(jpezy_ctx* c, const uint8_t* r, const uint8_t* g, const u
 try {
     if (int rc = jpezy_internal_check_dims(c, W, H, 1)) return rc;
     if (!r || !g || !b || !out) return set_err(JPEZY_E_BADARG, "encode_jpeg: null pointer");
+    if (int rc = check_comment(comment, "encode_jpeg")) return rc;
     HIP_TRY(hipSetDevice(c->device));
     // the planes go up band by band (jpezy_hostpipe.h) while the bands before them are transformed into the frame's
     // coefficient buffer on the device; the Huffman stage then runs on the whole frame

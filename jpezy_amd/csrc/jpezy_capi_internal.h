@@ -36,6 +36,12 @@ inline int set_err(int code, const std::string& msg)
     g_err = msg;
     return code;
 }
+// one comment limit for every writer (include/jpezy_hip.h, JPEZY_MAX_COMMENT)
+inline int check_comment(const char* comment, const char* who)
+{
+    if (jpezy_host::comment_ok(comment)) return JPEZY_OK;
+    return set_err(JPEZY_E_BADARG, std::string(who) + ": comment longer than JPEZY_MAX_COMMENT (" + std::to_string(JPEZY_MAX_COMMENT) + " bytes)");
+}
 inline int hip_err(hipError_t e, const char* what)
 {
     return set_err(JPEZY_E_HIP, std::string(what) + ": " + hipGetErrorString(e));

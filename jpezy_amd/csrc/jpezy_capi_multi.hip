@@ -518,6 +518,7 @@ try {
     if (!r || !g || !b) return set_err(JPEZY_E_BADARG, "multi_encode: null pointer");
     if (int rc = check_out(out, "multi_encode")) return rc;
     if (n_frames <= 0) return set_err(JPEZY_E_BADARG, "n_frames must be positive");
+    if (int rc = check_comment(comment, "multi_encode")) return rc;
     DeviceRestore restore;
     Job J;
     J.src[0] = r; J.src[1] = g; J.src[2] = b;

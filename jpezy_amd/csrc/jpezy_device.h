@@ -152,6 +152,8 @@ struct GenericDecParams {
     size_t plane_stride = 0;
 };
 hipError_t launch_dequant_idct_generic(const GenericDecParams& p, hipStream_t stream);
+// frames of p's layout one pair of launches takes (the launcher loops over larger batches); 0: a frame too large for one launch
+int generic_frames_per_launch(const GenericDecParams& p);
 
 #if defined(__HIPCC__)
 // The reference's sample int(sum / 4 + sl) (ref decoder/jpezy_decoder.hpp:667) as its x86-64 build executes it: cvttsd2si truncates

@@ -189,8 +189,14 @@ void put_header(BitSink& o, int W, int H, const char* comment)
 
 }  // namespace
 
+bool comment_ok(const char* comment)
+{
+    return !comment || std::strlen(comment) <= JPEZY_MAX_COMMENT;      // the COM length field (n + 3) can then never wrap
+}
+
 size_t write_header(int W, int H, const char* comment, uint8_t* out, size_t cap)
 {
+    if (!comment_ok(comment)) return 0;
     BitSink o(out, cap);
     put_header(o, W, H, comment);
     return o.ok() ? o.size() : 0;
@@ -217,6 +223,10 @@ long write_jpeg(const int16_t* coeffs, int W, int H, bool gray, const char* comm
 {
     if (!coeffs || !out || W <= 0 || H <= 0 || W > 65535 || H > 65535) {
         if (err) *err = "write_jpeg: bad argument";
+        return JPEZY_E_BADARG;
+    }
+    if (!comment_ok(comment)) {
+        if (err) *err = "write_jpeg: comment longer than JPEZY_MAX_COMMENT (" + std::to_string(JPEZY_MAX_COMMENT) + " bytes)";
         return JPEZY_E_BADARG;
     }
     const EncTables& T = enc_tables();

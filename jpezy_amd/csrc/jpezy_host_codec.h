@@ -15,7 +15,10 @@ namespace jpezy_host {
 long write_jpeg(const int16_t* coeffs, int W, int H, bool gray, const char* comment, uint8_t* out, size_t cap,
                 std::string* err);
 size_t jpeg_bound(int W, int H);
-// the bytes before the entropy-coded segment (SOI .. SOS, 644 with the default comment); 0 if cap is too small
+// false for a comment longer than JPEZY_MAX_COMMENT: every writer refuses it (JPEZY_E_BADARG)
+bool comment_ok(const char* comment);
+// the bytes before the entropy-coded segment (SOI .. SOS, 644 with the default comment); 0 if cap is too small or the
+// comment too long
 size_t write_header(int W, int H, const char* comment, uint8_t* out, size_t cap);
 // canonical (code, length) per symbol of the four Annex-K tables in DHT order YDc, CDc, YAc, CAc (for the GPU coder)
 void enc_code_tables(uint16_t code[4][256], uint8_t len[4][256]);

@@ -255,14 +255,22 @@ __global__ __launch_bounds__(256) void generic_rgb_kernel(GenericDecParams p)
 
 }  // namespace generic
 
+int generic_frames_per_launch(const GenericDecParams& p)
+{
+    const long fblk = (long)p.mcu_cols * p.mcu_rows * p.blocks_per_mcu;
+    if (fblk <= 0 || fblk > 0x7FFFFFFFL) return 0;
+    const long per = 0x7FFFFFFFL / fblk;                   // the block index of a launch is 32-bit
+    return per < 65535 ? (int)per : 65535;                 // the frame index is grid.z
+}
+
 hipError_t launch_dequant_idct_generic(const GenericDecParams& p_in, hipStream_t s)
 {
     GenericDecParams p = p_in;
     const int nfr = p.n_frames < 1 ? 1 : p.n_frames;
-    const long nblk = (long)p.mcu_cols * p.mcu_rows * p.blocks_per_mcu * nfr;       // the block loop does not care where a frame ends
-    if (nblk <= 0) return hipSuccess;
-    if (nblk > 0x7FFFFFFFL || nfr > 65535) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(generic::generic_idct_kernel, dim3((unsigned)((nblk + generic::G_BLOCKS - 1) / generic::G_BLOCKS)), dim3(64), 0, s, p, nblk);
+    const long fblk = (long)p.mcu_cols * p.mcu_rows * p.blocks_per_mcu;       // the block loop does not care where a frame ends
+    if (fblk <= 0) return hipSuccess;
+    const int per = generic_frames_per_launch(p);
+    if (per < 1) return hipErrorInvalidValue;
     fast_div_setup((unsigned)p.hmax * 8u, &p.mw_magic, &p.mw_shift);
     fast_div_setup((unsigned)p.vmax * 8u, &p.mh_magic, &p.mh_shift);
     for (int c = 0; c < 3; ++c) {
@@ -270,8 +278,18 @@ hipError_t launch_dequant_idct_generic(const GenericDecParams& p_in, hipStream_t
         fast_div_setup((unsigned)(p.vmax / p.cv[c]), &p.dy_magic[c], &p.dy_shift[c]);
     }
     const unsigned gx = ((unsigned)p.W + 255u) / 256u, gy = ((unsigned)p.H + 3u) / 4u;
-    hipLaunchKernelGGL(generic::generic_rgb_kernel, dim3(gx, gy, (unsigned)nfr), dim3(256), 0, s, p);
-    return hipGetLastError();
+    // larger batches go out as several pairs of launches; the samples scratch (per frames of one launch) is reused in stream order
+    for (int f0 = 0; f0 < nfr; f0 += per) {
+        GenericDecParams q = p;
+        q.n_frames = nfr - f0 < per ? nfr - f0 : per;
+        q.coeffs += (size_t)f0 * (size_t)fblk * 64;
+        q.r += (size_t)f0 * p.plane_stride; q.g += (size_t)f0 * p.plane_stride; q.b += (size_t)f0 * p.plane_stride;
+        const long nblk = fblk * q.n_frames;
+        hipLaunchKernelGGL(generic::generic_idct_kernel, dim3((unsigned)((nblk + generic::G_BLOCKS - 1) / generic::G_BLOCKS)), dim3(64), 0, s, q, nblk);
+        hipLaunchKernelGGL(generic::generic_rgb_kernel, dim3(gx, gy, (unsigned)q.n_frames), dim3(256), 0, s, q);
+        if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 }  // namespace jpezy_dev

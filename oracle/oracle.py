@@ -112,7 +112,7 @@ def write_jpeg(coeffs, W, H, gray=False, comment=None):
     coeffs = np.ascontiguousarray(coeffs, dtype=np.int16)
     if comment is None:
         comment = b"Encoded by JPEZY" if gray else b"Encoded by jpezy"
-    cap = max(W * H * 3, 10240) + coeffs.size * 4 + 4096
+    cap = max(W * H * 3, 10240) + coeffs.size * 7 + len(comment) + 4096    # 7: 26 bits per coefficient at most, every byte stuffed
     buf = np.zeros(cap, dtype=np.uint8)
     n = lib().jo_write_jpeg(_i16(coeffs), W, H, int(gray), comment, _u8(buf), cap)
     if n < 0:

@@ -115,7 +115,7 @@ jpezy_ctx* jpezy_ctx_create(int device)
             for (int j = 0; j < 8; ++j) {
                 double worst = 0;
                 for (int i = 0; i < 8; ++i) {
-                    if (i == 0 && j == 0) continue;            // DC: exact table lookup, no guard band
+                    if (i == 0 && j == 0) continue;            // DC: an exact integer sum, no transform error (checked for every sum below)
                     const double cu = j ? 1.0 : S, cv = i ? 1.0 : S;
                     const double ks = cu * cv / (4.0 * kQt[t][i * 8 + j]);
                     const double amp = 128.0 * S1[i] * S1[j] * ks;
@@ -126,6 +126,19 @@ jpezy_ctx* jpezy_ctx_create(int device)
                 h.f32col[t][j].delta1[0] = h.f32col[t][j].delta1[1] = d1;
                 h.f32col[t][j].th = d1 + d1;               // exact: a doubling
             }
+        // The one-quad kernel sends the DC through that quantiser too (f32::quant_block_column, DCG): t' = fma(sum, ks, delta1), flagged
+        // <=> fract(t') < 2 delta1 -> dc_formula (verified above), else (int)t'.  The same FP32 operations for every sum against the table;
+        // a set of constants for which they do not reproduce it keeps the table lookup (dc_rq = 0).
+        for (int t = 0; t < 2; ++t) {
+            const F32Column& col = h.f32col[t][0];
+            bool ok = true;
+            for (int sum = -8192; sum <= 8192 && ok; ++sum) {
+                const float tp = std::fmaf((float)sum, col.ks[0], col.delta1[0]);
+                const bool flagged = tp - std::floor(tp) < col.th;         // v_fract_f32
+                ok = flagged || (int)tp == (int)h.dcq[t][sum + 8192];
+            }
+            if (!ok) c->dc_rq[t] = c->dc_bias[t] = 0.f;
+        }
     }
     for (int j = 0; j < 8; ++j)
         for (int hh = 0; hh < 2; ++hh) {

@@ -17,7 +17,9 @@
 // Colour conversion: Y = trunc(fma chain in FP32) is exact unless the exact value is an integer, which happens exactly
 //   when 299R+587G+114B is a multiple of 1000 (1 pixel in 1000): there the reference's own FP64 rounding decides and the
 //   FP64 formula is evaluated.  Same for Cb/Cr (multiples of 10000).  Also one-sided: the chain starts from a bias.
-// The DC coefficient is a sum of integers (exact in FP32) and is read from a table built in the reference's FP64 order.
+// The DC coefficient is a sum of integers (exact in FP32): it goes through the level-1 quantiser like any coefficient, and a
+//   DC that the guard test flags (its sum a multiple of 8 Q) is settled in place by a closed form (dc_formula).  With
+//   constants for which the host could not verify that (EncParams::dc_rq == 0) it is read from a table built in the reference's FP64 order.
 // Compiled with -ffp-contract=off; every FMA below is explicit.
 #pragma once
 #include "jpezy_device.h"
@@ -70,6 +72,9 @@ static __constant__ unsigned char c_zzinv[64] = JPEZY_ZZ_INV_INIT;
 #endif
 #ifndef JPEZY_PIN_CONSTANTS
 #define JPEZY_PIN_CONSTANTS 1
+#endif
+#ifndef JPEZY_CHROMA_CONSTS_EARLY
+#define JPEZY_CHROMA_CONSTS_EARLY 1  // the chroma quantiser record loaded ahead of the chroma row pass (0: in front of its use)
 #endif
 
 typedef float f2 __attribute__((ext_vector_type(2)));   // an aligned VGPR (or SGPR) pair: the operand of v_pk_*_f32
@@ -376,21 +381,33 @@ __device__ __forceinline__ int dc_lookup(float sum, const signed char* dcq)
 // truncated to 0), q = trunc(d * rq + bias) with rq = fl(1 / Q), bias = 1 / (2 Q): d <= 1023 puts d * rq within 6e-5 of d / Q, whose
 // fractional part is a multiple of 1 / Q.  jpezy_capi.hip evaluates exactly these operations for every sum in [-8192, 8192] against
 // DeviceTables::dcq at context creation and only then lets the kernel use them (EncParams::dc_rq[t] != 0).
-// Only the j == 0 lane's result is used (quant_block_column: `if (j == 0) q[0] = dc`); the other lanes feed it their X0 of some other
+// Only the j == 0 lane's result is used (quant_block_column); the other lanes feed it their X0 of some other
 // column -- an arbitrary float -- and throw the result away: no clamp is needed for them (an out-of-range v_cvt_i32_f32 saturates).
-__device__ __forceinline__ int dc_formula(float sum, float rq, float bias)
+__device__ __forceinline__ float dc_formula_f(float sum, float rq, float bias)    // the value as a float (an integer, |q| <= 64)
 {
     const float d = __builtin_truncf(FMAF(__builtin_fabsf(sum), 0.125f, -0.125f));
     const float q = __builtin_truncf(FMAF(d, rq, bias));
-    return (int)__builtin_copysignf(q, sum);
+    return __builtin_copysignf(q, sum);
 }
+__device__ __forceinline__ int dc_formula(float sum, float rq, float bias) { return (int)dc_formula_f(sum, rq, bias); }
+
+// The one-quad kernel's DC through the generic quantiser (DCG = true, chosen by the launcher when EncParams::dc_rq != 0 for both
+// tables): on the j == 0 lane F[0].x is the block's integer sample sum, t = sum / (8 Q) a multiple of 1 / (8 Q) >= 1e-3 and the FP32
+// error of fma(sum, ks, delta1) below 1e-5: the guard test flags the DC exactly when sum is a multiple of 8 Q (zero included), and
+// everywhere else (int)t' is the table's value.  A flagged DC evaluates dc_formula inside the candidate branch (0.6 % of blocks on
+// random pixels) and is never queued.  jpezy_ctx_create checks all of this for every sum with the same FP32 operations.
+#ifndef JPEZY_DC_GENERIC
+#define JPEZY_DC_GENERIC 1           // 0: the DC on a path of its own in every lane (dc_formula / dc_lookup ahead of the quantiser), A/B only
+#endif
 
 // Quantise one block column and stage it in zig-zag order.  F: the column pass' four output pairs (order pair_row);
 // ks: the quantiser scales in the same order; dd = (delta1, delta1), th = 2 delta1; j: natural column; dc: the block's
-// quantised DC (only the j == 0 lane uses it); base: LDS address of this lane's FIRST block, blk_off the byte offset of
+// quantised DC (!DCG; only the j == 0 lane uses it); rq, bias: dc_formula's constants (DCG); base: LDS address of this
+// lane's FIRST block, blk_off the byte offset of
 // the block to write (an immediate after inlining); zz_lo/zz_hi: byte p = LDS byte offset of the coefficient at pair
 // position p inside a block (2 * zig-zag index < 128), packed so that the eight addresses cost two registers.
-__device__ __forceinline__ void quant_block_column(const f2* F, const f2* ks, f2 dd, float th, int j, int dc,
+template <bool DCG>
+__device__ __forceinline__ void quant_block_column(const f2* F, const f2* ks, f2 dd, float th, int j, int dc, float rq, float bias,
                                                    bool live, char* base, uint32_t zz_lo, uint32_t zz_hi, int blk_off, int blk,
                                                    unsigned* queue, bool force
 #ifdef JPEZY_DUMP_T
@@ -420,7 +437,7 @@ __device__ __forceinline__ void quant_block_column(const f2* F, const f2* ks, f2
         q[p] = (int)tp;                                                   // v_cvt_i32_f32 truncates toward zero
         fr[p] = __builtin_amdgcn_fractf(tp);
     }
-    if (j == 0) { q[0] = dc; fr[0] = 1.f; }                               // the DC term: exact table, no guard band
+    if (!DCG && j == 0) { q[0] = dc; fr[0] = 1.f; }                       // the DC term on a path of its own: exact, no guard band
     // v_min3_f32: 3.5 instructions for 8 values
     const float fmin = __builtin_fminf(__builtin_fminf(__builtin_fminf(fr[0], fr[1]), __builtin_fminf(fr[2], fr[3])),
                                        __builtin_fminf(__builtin_fminf(fr[4], fr[5]), __builtin_fminf(fr[6], fr[7])));
@@ -428,7 +445,11 @@ __device__ __forceinline__ void quant_block_column(const f2* F, const f2* ks, f2
     // rare on noisy content; flat content (exact zeros) enters and finds nothing to queue.  (Lanes that are not live
     // repeat the quad's last MCU, so leaving them in the vote changes nothing and keeps it a bare v_cmp + s_cmp.)
     if (wave_any(cand)) {
-        if (cand && live) {       // Fully unrolled: a runtime index into the arrays would send them to scratch
+        // a flagged DC (sum a multiple of 8 Q): the closed form takes t'[0]'s place (which way (int)t' is off there depends on the
+        // constants header).  The conversions of a DCG build come behind this branch: as floats the values are live across it anyway
+        // (the queue loop reads them), as integers they would be eight registers more.
+        if (DCG && j == 0 && fr[0] < th) t[0].x = dc_formula_f(F[0].x, rq, bias);
+        if (cand && live) {     // Fully unrolled: a runtime index into the arrays would send them to scratch
 #pragma unroll
             for (int p = 0; p < 8; ++p) {
                 const float tp = p & 1 ? t[p >> 1].y : t[p >> 1].x;
@@ -444,11 +465,11 @@ __device__ __forceinline__ void quant_block_column(const f2* F, const f2* ks, f2
         }
     }
 #pragma unroll
-    for (int pp = 1; pp <= 8; ++pp) {      // p = 0 last: it waits for the DC lookup
+    for (int pp = 1; pp <= 8; ++pp) {      // p = 0 last: without DCG it waits for the DC lookup
         const int p = pp & 7;
         // (one SDWA add per store; the eight addresses formed once per lane and kept in registers measured 1 us slower)
         const uint32_t off = ((p < 4 ? zz_lo : zz_hi) >> (8 * (p & 3))) & 0xFFu;
-        *reinterpret_cast<int16_t*>(base + off + blk_off) = (int16_t)q[p];
+        *reinterpret_cast<int16_t*>(base + off + blk_off) = (int16_t)(DCG ? (int)(p & 1 ? t[p >> 1].y : t[p >> 1].x) : q[p]);
     }
 }
 
@@ -533,7 +554,8 @@ struct QuadTrace { unsigned long long t2; unsigned long long ph[8]; };
 #define PHASE_FENCE() do { if (!PS || JPEZY_PS_FENCES) __builtin_amdgcn_sched_barrier(0); } while (0)
 struct NoHook { __device__ __forceinline__ void operator()() const {} };
 // after_pixels(): called once the raw pixel registers R, G, B are dead (behind step 2b) -- variant 3 requests the next quad's there
-template <bool GRAY, int FORCE, bool PS, class AFTER_PIXELS>
+// DCG: the DC through the generic quantiser (quant_block_column); the one-quad kernel's launcher decides
+template <bool GRAY, int FORCE, bool PS, bool DCG = false, class AFTER_PIXELS>
 __device__ __forceinline__ void encode_quad_compute(const EncParams& p, const uint32_t* R, const uint32_t* G, const uint32_t* B, uint32_t* lds,
                                             int lane, int mcu_y, int quad_x, int frame, unsigned qidx, const LaneConsts* pre,
                                             const signed char* dcq_lds, const PsTables* pst, AFTER_PIXELS after_pixels QUAD_TRACE_PARAM)
@@ -645,15 +667,15 @@ __device__ __forceinline__ void encode_quad_compute(const EncParams& p, const ui
         {
             f2 F[4];
             fdct8p(TP, F, kc);
-            const int dc_top = DCF ? dc_formula(F[0].x, p.dc_rq[0], p.dc_bias[0]) : dc_lookup(F[0].x, dcq_l);
-            quant_block_column(F, ks, dd, th, j, dc_top, live, sbase, zz_lo, zz_hi, 0, m * BPM + bx, queue, FORCE != 0 DUMP_ARG);
+            const int dc_top = DCG ? 0 : DCF ? dc_formula(F[0].x, p.dc_rq[0], p.dc_bias[0]) : dc_lookup(F[0].x, dcq_l);
+            quant_block_column<DCG>(F, ks, dd, th, j, dc_top, p.dc_rq[0], p.dc_bias[0], live, sbase, zz_lo, zz_hi, 0, m * BPM + bx, queue, FORCE != 0 DUMP_ARG);
         }
         PHASE_FENCE();
         {
             f2 F[4];
             fdct8p(BT, F, kc);
-            const int dc_bot = DCF ? dc_formula(F[0].x, p.dc_rq[0], p.dc_bias[0]) : dc_lookup(F[0].x, dcq_l);
-            quant_block_column(F, ks, dd, th, j, dc_bot, live, sbase, zz_lo, zz_hi, 2 * STG_BLK, m * BPM + 2 + bx, queue, FORCE != 0 DUMP_ARG);
+            const int dc_bot = DCG ? 0 : DCF ? dc_formula(F[0].x, p.dc_rq[0], p.dc_bias[0]) : dc_lookup(F[0].x, dcq_l);
+            quant_block_column<DCG>(F, ks, dd, th, j, dc_bot, p.dc_rq[0], p.dc_bias[0], live, sbase, zz_lo, zz_hi, 2 * STG_BLK, m * BPM + 2 + bx, queue, FORCE != 0 DUMP_ARG);
         }
     }
 
@@ -664,6 +686,15 @@ __device__ __forceinline__ void encode_quad_compute(const EncParams& p, const ui
     // ---- 5. chroma row pass, transpose, column pass ----
     if (!GRAY) {
         const bool odd = (row & 1) != 0;
+#if JPEZY_CHROMA_CONSTS_EARLY
+        // the chroma quantiser record, requested ahead of the row pass (registers are free here): behind the column pass the three
+        // 16-byte loads would be issued and waited for back to back (the LDS statements' "memory" clobbers pin them there)
+        f2 ks[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) ks[k] = PRE ? pre->ks_c[k] : f2{ lcol[8].ks[2 * k], lcol[8].ks[2 * k + 1] };
+        const f2 dd = PRE ? pre->dd_c : f2{ lcol[8].delta1[0], lcol[8].delta1[1] };
+        const float th_c = PRE ? pre->th_c : lcol[8].th;
+#endif
         f2 cX[4];
         fdct8p(CS, cX, kc);
         f2* dst = reinterpret_cast<f2*>(ldsf + m * C_MCU + (odd ? C_COMP : 0) + (row >> 1) * C_PITCH);
@@ -676,13 +707,16 @@ __device__ __forceinline__ void encode_quad_compute(const EncParams& p, const ui
             f2 col[4];
             lds_column<C_PITCH>(ldsf + m * C_MCU + (cq >> 3) * C_COMP + (cq & 7), col);
             fdct8p(col, Fc, kc);
-            dc_c = DCF ? dc_formula(Fc[0].x, p.dc_rq[1], p.dc_bias[1]) : dc_lookup(Fc[0].x, dcq_c);
+            dc_c = DCG ? 0 : DCF ? dc_formula(Fc[0].x, p.dc_rq[1], p.dc_bias[1]) : dc_lookup(Fc[0].x, dcq_c);
         }
+#if !JPEZY_CHROMA_CONSTS_EARLY
         f2 ks[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) ks[k] = PRE ? pre->ks_c[k] : f2{ lcol[8].ks[2 * k], lcol[8].ks[2 * k + 1] };
         const f2 dd = PRE ? pre->dd_c : f2{ lcol[8].delta1[0], lcol[8].delta1[1] };
-        quant_block_column(Fc, ks, dd, PRE ? pre->th_c : lcol[8].th, j, dc_c, live, sbase, zz_lo, zz_hi, 4 * STG_BLK, m * BPM + 4 + bx, queue, FORCE != 0 DUMP_ARG);
+        const float th_c = PRE ? pre->th_c : lcol[8].th;
+#endif
+        quant_block_column<DCG>(Fc, ks, dd, th_c, j, dc_c, p.dc_rq[1], p.dc_bias[1], live, sbase, zz_lo, zz_hi, 4 * STG_BLK, m * BPM + 4 + bx, queue, FORCE != 0 DUMP_ARG);
     }
     wave_sync();
     PROBE_ALL();
@@ -825,12 +859,12 @@ __device__ __forceinline__ void encode_quad_store(const EncParams& p, uint32_t* 
     }
 }
 
-template <bool GRAY, int FORCE, bool PS>
+template <bool GRAY, int FORCE, bool PS, bool DCG = false>
 __device__ __forceinline__ void encode_quad(const EncParams& p, const uint32_t* R, const uint32_t* G, const uint32_t* B, uint32_t* lds,
                                             int lane, int mcu_y, int quad_x, int frame, unsigned qidx, const LaneConsts* pre,
                                             const signed char* dcq_lds, const PsTables* pst QUAD_TRACE_PARAM)
 {
-    encode_quad_compute<GRAY, FORCE, PS>(p, R, G, B, lds, lane, mcu_y, quad_x, frame, qidx, pre, dcq_lds, pst, NoHook()
+    encode_quad_compute<GRAY, FORCE, PS, DCG>(p, R, G, B, lds, lane, mcu_y, quad_x, frame, qidx, pre, dcq_lds, pst, NoHook()
 #ifdef JPEZY_TRACE
                                          , tr
 #endif

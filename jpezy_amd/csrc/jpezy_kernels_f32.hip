@@ -5,7 +5,7 @@
 namespace jpezy_dev {
 namespace f32 {
 
-template <bool GRAY, bool ALIGNED, int FORCE, int EWPB>
+template <bool GRAY, bool ALIGNED, int FORCE, int EWPB, bool DCG>
 __global__ __launch_bounds__(64 * EWPB, JPEZY_F32_WAVES) void fdct_quant_f32_kernel(EncParams p)
 {
     __shared__ __attribute__((aligned(16))) uint32_t lds_all[EWPB][WAVE_LDS_DWORDS];
@@ -139,7 +139,7 @@ __global__ __launch_bounds__(64 * EWPB, JPEZY_F32_WAVES) void fdct_quant_f32_ker
         return;
     }
 #endif
-    encode_quad<GRAY, FORCE, false>(p, R, G, B, lds, lane, mcu_y, quad_x, frame, qidx, nullptr, nullptr, nullptr QUAD_TRACE_ARG);
+    encode_quad<GRAY, FORCE, false, DCG>(p, R, G, B, lds, lane, mcu_y, quad_x, frame, qidx, nullptr, nullptr, nullptr QUAD_TRACE_ARG);
 #ifdef JPEZY_TRACE
     if (frame == 0 && qidx < 65536u) {
 #if JPEZY_TRACE > 1
@@ -167,17 +167,26 @@ __global__ __launch_bounds__(64 * EWPB, JPEZY_F32_WAVES) void fdct_quant_f32_ker
 
 }  // namespace f32
 
+template <bool GRAY, bool ALIGNED, int EW, bool DCG>
+static void enc_f32_launch3(const EncParams& p, int force, dim3 grid, hipStream_t s)
+{
+    if (force == 1)
+        hipLaunchKernelGGL((f32::fdct_quant_f32_kernel<GRAY, ALIGNED, 1, EW, DCG>), grid, dim3(64 * EW), 0, s, p);
+    else if (force == 2)
+        hipLaunchKernelGGL((f32::fdct_quant_f32_kernel<GRAY, ALIGNED, 2, EW, DCG>), grid, dim3(64 * EW), 0, s, p);
+    else if (force == 3)
+        hipLaunchKernelGGL((f32::fdct_quant_f32_kernel<GRAY, ALIGNED, 3, EW, DCG>), grid, dim3(64 * EW), 0, s, p);
+    else
+        hipLaunchKernelGGL((f32::fdct_quant_f32_kernel<GRAY, ALIGNED, 0, EW, DCG>), grid, dim3(64 * EW), 0, s, p);
+}
+
 template <bool GRAY, bool ALIGNED, int EW>
 static void enc_f32_launch2(const EncParams& p, int force, dim3 grid, hipStream_t s)
 {
-    if (force == 1)
-        hipLaunchKernelGGL((f32::fdct_quant_f32_kernel<GRAY, ALIGNED, 1, EW>), grid, dim3(64 * EW), 0, s, p);
-    else if (force == 2)
-        hipLaunchKernelGGL((f32::fdct_quant_f32_kernel<GRAY, ALIGNED, 2, EW>), grid, dim3(64 * EW), 0, s, p);
-    else if (force == 3)
-        hipLaunchKernelGGL((f32::fdct_quant_f32_kernel<GRAY, ALIGNED, 3, EW>), grid, dim3(64 * EW), 0, s, p);
-    else
-        hipLaunchKernelGGL((f32::fdct_quant_f32_kernel<GRAY, ALIGNED, 0, EW>), grid, dim3(64 * EW), 0, s, p);
+    // the DC through the generic quantiser where jpezy_ctx_create verified it for this build's constants (both tables), else on its
+    // own path from the exact table -- a second instance of the kernel, so that the common one carries no trace of the DC path
+    if (JPEZY_DC_GENERIC && p.dc_rq[0] != 0.f && p.dc_rq[1] != 0.f) enc_f32_launch3<GRAY, ALIGNED, EW, true>(p, force, grid, s);
+    else enc_f32_launch3<GRAY, ALIGNED, EW, false>(p, force, grid, s);
 }
 
 hipError_t launch_fdct_quant_f32(const EncParams& p0, bool gray, int force, hipStream_t stream)

@@ -191,11 +191,7 @@ void run_lane(const jpezy_multi& M, Lane& L, const Job& J)
     const size_t dstride = std::min(M.bound, (J.out.jpg_stride + 15) & ~(size_t)15);
     // drainers: two bring a tenth of the upload's bytes back (.jpg files); coefficients to host memory are as many bytes as the planes
     // and want as many copying threads as the way up
-#ifdef JPEZY_MULTI_FIXED_DRAIN       // A/B builds (tools/ab/ab_build.py)
-    const int n_drain = JPEZY_MULTI_FIXED_DRAIN;
-#else
     const int n_drain = want_coef && !to_root ? std::min(MAX_DRAIN, std::max(2, n_feed)) : 2;
-#endif
     L.stats = {};
     L.stats.device = L.dev;
     L.stats.frames = L.nf;

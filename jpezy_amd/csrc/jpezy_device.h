@@ -126,7 +126,7 @@ bool fdct_quant_f32_ps_applies(const EncParams& p);
 // variant 3: persistent workgroups of 16 compute waves, every wave prefetching its next quad's pixels into registers; any frame
 // with W % 16 == 0 and 16-byte aligned planes, anything else goes to variant 1's launch
 hipError_t launch_fdct_quant_f32_ps2(const EncParams& p, bool gray, int force, int n_cus, hipStream_t stream);
-// tolerant: luma in FP32 without guard band (samples within one of the reference's, jpezy_kernels.hip); chroma stays exact
+// tolerant: luma in FP32 without guard band (samples within one of the reference's, jpezy_kernels_decode.hip); chroma stays exact
 hipError_t launch_dequant_idct(const DecParams& p, bool gray, bool force_exact, bool tolerant, hipStream_t stream);
 
 // any-layout decode (jpezy_kernels_generic.hip)

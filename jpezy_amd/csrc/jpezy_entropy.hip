@@ -31,11 +31,7 @@ namespace entropy {
 struct alignas(16) LdsTables {
     uint32_t dc[2][16];
     uint32_t ac[2][256];
-#ifdef JPEZY_ENT_NOFAST
-    uint32_t fast[2][4];
-#else
     uint32_t fast[2][1024];         // CodeTables::fast
-#endif
 };
 static_assert(sizeof(LdsTables) <= sizeof(CodeTables) && sizeof(LdsTables) % 16 == 0, "table images must match");
 
@@ -102,28 +98,23 @@ __device__ __forceinline__ void code_ac(uint32_t m, int base, const int16_t* z, 
         // runs up to 15 -- every lane looks it up unconditionally (an index outside the table reads some other LDS word or, beyond
         // the workgroup's allocation, zero: never used) and appends once.  Larger values and runs over 15 (ZRL) are rare on
         // dense content: the wave enters the general path only when one of its lanes needs it (a wave-uniform branch; the
-        // branchy form -- fast path or general path per lane -- issued more instructions than the code it replaced).
+        // branchy form -- fast path or general path per lane -- issued more instructions than the code it replaced;
+        // with and without the table: profiles/r03_entropy_ab.txt).
         const unsigned v32 = (unsigned)(v + 32);
         uint32_t e = fast[((unsigned)run << 6) + v32];
-#ifdef JPEZY_ENT_NOFAST
-        const bool slow = true;
-#else
         const bool slow = v32 > 63u || run > 15;
-#endif
-        {
-            if (slow) {       // (a divergent branch is skipped by the whole wave when no lane takes it: s_cbranch_execz)
-                const unsigned a = (unsigned)(v < 0 ? -v : v);
-                amax = a > amax ? a : amax;
-                int sz = 32 - __builtin_clz(a);
-                sz = sz > 10 ? 10 : sz;
-                if (run > 15) {                          // ZRL codes in front of this coefficient (ref :198-206)
-                    for (int r = run >> 4; r > 0; --r) w.put(zrl >> 8, (int)(zrl & 0xFF));
-                    run &= 15;
-                }
-                const uint32_t g = ac[(run << 4) | sz];
-                // code and value bits: at most 16 + 10 bits, and 5 bits of length
-                e = ((((g >> 8) << sz) | ((uint32_t)(v + (v >> 31)) & ((1u << sz) - 1u))) << 5) | ((g & 0xFF) + (uint32_t)sz);
+        if (slow) {       // (a divergent branch is skipped by the whole wave when no lane takes it: s_cbranch_execz)
+            const unsigned a = (unsigned)(v < 0 ? -v : v);
+            amax = a > amax ? a : amax;
+            int sz = 32 - __builtin_clz(a);
+            sz = sz > 10 ? 10 : sz;
+            if (run > 15) {                          // ZRL codes in front of this coefficient (ref :198-206)
+                for (int r = run >> 4; r > 0; --r) w.put(zrl >> 8, (int)(zrl & 0xFF));
+                run &= 15;
             }
+            const uint32_t g = ac[(run << 4) | sz];
+            // code and value bits: at most 16 + 10 bits, and 5 bits of length
+            e = ((((g >> 8) << sz) | ((uint32_t)(v + (v >> 31)) & ((1u << sz) - 1u))) << 5) | ((g & 0xFF) + (uint32_t)sz);
         }
         w.put(e >> 5, (int)(e & 31u));
     }

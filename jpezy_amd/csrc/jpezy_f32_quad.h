@@ -22,7 +22,7 @@
 //   constants for which the host could not verify that (EncParams::dc_rq == 0) it is read from a table built in the reference's FP64 order.
 // Compiled with -ffp-contract=off; every FMA below is explicit.
 #pragma once
-#include "jpezy_device.h"
+#include "jpezy_wave.h"
 #include "../../include/jpezy_constants.h"
 
 #ifdef JPEZY_WITH_LAB
@@ -43,6 +43,7 @@
 namespace jpezy_dev {
 namespace f32 {
 
+// tables, colour formulas and transform of this path are its own on purpose: jpezy_kernels_f64.hip is the independent second encoder
 static __constant__ double c_cos[64] = JPEZY_COS_INIT;
 static __constant__ unsigned char c_zzinv[64] = JPEZY_ZZ_INV_INIT;
 
@@ -56,41 +57,18 @@ static __constant__ unsigned char c_zzinv[64] = JPEZY_ZZ_INV_INIT;
 #ifndef JPEZY_F32_WAVES
 #define JPEZY_F32_WAVES 5
 #endif
-// instruction-selection switches (same arithmetic, same results): packed FP32 forms of the transform / of the fused
-// multiply-adds of the luma and chroma estimates / of the quantiser's product-and-bias
-#ifndef JPEZY_PK_TRANSFORM
-#define JPEZY_PK_TRANSFORM 1
-#endif
-#ifndef JPEZY_PK_LUMA
-#define JPEZY_PK_LUMA 1
-#endif
-#ifndef JPEZY_PK_CHROMA
-#define JPEZY_PK_CHROMA 1
-#endif
-#ifndef JPEZY_PK_QUANT
-#define JPEZY_PK_QUANT 1
-#endif
-#ifndef JPEZY_PIN_CONSTANTS
-#define JPEZY_PIN_CONSTANTS 1
-#endif
-#ifndef JPEZY_CHROMA_CONSTS_EARLY
-#define JPEZY_CHROMA_CONSTS_EARLY 1  // the chroma quantiser record loaded ahead of the chroma row pass (0: in front of its use)
-#endif
 
 typedef float f2 __attribute__((ext_vector_type(2)));   // an aligned VGPR (or SGPR) pair: the operand of v_pk_*_f32
 
 // Workgroup = EWPB waves = EWPB horizontally adjacent quads (4: 256 pixels x 16 rows).  The waves share nothing but the
-// pixel load: with JPEZY_COOP_LOAD the workgroup fetches its rows in whole 256-byte pieces (16 lanes per row, 4 rows per
-// wave instruction, LDS-DMA) and every wave then picks its quad's 64-byte row segments out of LDS; without it each wave
+// pixel load: a 4-wave workgroup fetches its rows in whole 256-byte pieces (16 lanes per row, 4 rows per
+// wave instruction, LDS-DMA) and every wave then picks its quad's 64-byte row segments out of LDS; in a 2-wave workgroup each wave
 // loads its own 64-byte segments of 16 rows per instruction straight into registers -- the shape the texture addresser
 // handles worst (tools/ubench/mem_pattern.hip: the kernel's memory pattern alone, no arithmetic, 22.4 us per 4096^2
 // frame in that shape against 19.4 us in whole 256-byte pieces).
 // The launcher picks the 4-wave form where a row of quads divides into groups of four (4096 and 7680 wide frames: 64 and 120
 // quads per row) and 2-wave workgroups with direct loads elsewhere (1920 wide: 30 quads -- groups of four would leave two of
-// every 32 wave slots idle, measured +3.8 % on the 32 x 1080p batch).
-#ifndef JPEZY_COOP_LOAD
-#define JPEZY_COOP_LOAD 1
-#endif
+// every 32 wave slots idle, measured +3.8 % on the 32 x 1080p batch).  Cooperative against direct loads: profiles/r04_ab3.txt.
 
 // Level-1 guard bands on t = v/Q: DeviceTables::delta1[table][j].  Norm-wise bound of the FP32 error of F[i][j]:
 // gamma_13 * sum|cos_i| * sum|cos_j| * 128 (at most 13 roundings on any input->output path, u = 2^-24), times the
@@ -114,22 +92,6 @@ constexpr int TILE_BYTES = (4 * Y_MCU * 4 > CT_BYTES + STG_BYTES) ? 4 * Y_MCU * 
 #endif
 constexpr int QUEUE_CAP = 2 * (JPEZY_QUEUE_DWORDS - 1);   // entries; beyond it every coefficient of the quad is resolved (pathological input)
 constexpr int WAVE_LDS_DWORDS = TILE_BYTES / 4 + JPEZY_QUEUE_DWORDS;   // + count word + 16-bit entries
-
-__device__ __forceinline__ unsigned fast_div(unsigned n, unsigned magic, unsigned shift)
-{
-    const unsigned q = __umulhi(n, magic);
-    return magic ? (((n - q) >> 1) + q) >> shift : n;
-}
-
-// wave-uniform "some lane": one v_cmp into an SGPR pair + s_cmp (HIP's __any goes through a 0/1 VGPR)
-__device__ __forceinline__ bool wave_any(bool x) { return __builtin_amdgcn_ballot_w64(x) != 0ull; }
-
-__device__ __forceinline__ void wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // ---- the 8-point transform in packed FP32 ----------------------------------------------------------------------------
 // VOP3P on 64-bit operands: op_sel[i] picks the dword of source i that feeds the LOW result, op_sel_hi[i] the one that
@@ -160,20 +122,11 @@ __device__ __forceinline__ constexpr int pair_row(int p) { return (int)((0x75316
 //   X0 = e0 + e1, X4 = e0 - e1; X2 = fma(e3, K6, e2*K2), X6 = fma(-e3, K2, e2*K6);
 //   X1 = fma(d3,K7, fma(d2,K5, fma(d1,K3, d0*K1))), X3 = fma(-d3,K5, fma(-d2,K1, fma(-d1,K7, d0*K3))),
 //   X5 = fma(d3,K3, fma(d2,K7, fma(-d1,K1, d0*K5))), X7 = fma(-d3,K1, fma(d2,K3, fma(-d1,K5, d0*K7)))
-// (tests/test_f32_error_bound.py emulates exactly this), two results per instruction: 17 instructions.
+// (tests/test_f32_error_bound.py emulates exactly this), two results per instruction: 17 instructions.  Packed against scalar forms of
+// the transform, the colour estimates and the quantiser: profiles/r04_ab1.txt, r04_ab2.txt.
 #define FMAF(a, b, c) __builtin_fmaf((a), (b), (c))
 __device__ __forceinline__ void fdct8p(const f2* A, f2* X, const PkCos& c)
 {
-#if !JPEZY_PK_TRANSFORM
-    const float s0 = A[0].x + A[0].y, s1 = A[1].x + A[1].y, s2 = A[2].x + A[2].y, s3 = A[3].x + A[3].y;
-    const float d0 = A[0].x - A[0].y, d1 = A[1].x - A[1].y, d2 = A[2].x - A[2].y, d3 = A[3].x - A[3].y;
-    const float e0 = s0 + s3, e1 = s1 + s2, e2 = s0 - s3, e3 = s1 - s2;
-    X[0] = f2{ e0 + e1, e0 - e1 };
-    X[1] = f2{ FMAF(e3, K6, e2 * K2), FMAF(-e3, K2, e2 * K6) };
-    X[2] = f2{ FMAF(d3, K7, FMAF(d2, K5, FMAF(d1, K3, d0 * K1))), FMAF(-d3, K5, FMAF(-d2, K1, FMAF(-d1, K7, d0 * K3))) };
-    X[3] = f2{ FMAF(d3, K3, FMAF(d2, K7, FMAF(-d1, K1, d0 * K5))), FMAF(-d3, K1, FMAF(d2, K3, FMAF(-d1, K5, d0 * K7))) };
-    return;
-#endif
     f2 P0, P1, P2, P3, Q0, Q1, t, u;
     PK_ADD(P0, A[0], A[0], "op_sel:[0,1] op_sel_hi:[0,1] neg_hi:[0,1]");   // (s0, d0) = x0 +- x7
     PK_ADD(P1, A[1], A[1], "op_sel:[0,1] op_sel_hi:[0,1] neg_hi:[0,1]");
@@ -235,13 +188,8 @@ template <int B0, int B1>
 __device__ __forceinline__ void luma_px2(uint32_t r0, uint32_t g0, uint32_t b0, uint32_t r1, uint32_t g1, uint32_t b1, f2& y, f2& fr)
 {
     const f2 r = { ubyte<B0>(r0), ubyte<B1>(r1) }, g = { ubyte<B0>(g0), ubyte<B1>(g1) }, b = { ubyte<B0>(b0), ubyte<B1>(b1) };
-#if JPEZY_PK_LUMA
     const f2 c1 = { 0.299f, 0.299f }, c2 = { 0.587f, 0.587f }, c3 = { 0.114f, 0.114f }, c0 = { -128.f + LUMA_EPS, -128.f + LUMA_EPS };
     const f2 t = pk_fma(c3, b, pk_fma(c2, g, pk_fma(c1, r, c0)));
-#else
-    const f2 t = { FMAF(0.114f, b.x, FMAF(0.587f, g.x, FMAF(0.299f, r.x, -128.f + LUMA_EPS))),
-                   FMAF(0.114f, b.y, FMAF(0.587f, g.y, FMAF(0.299f, r.y, -128.f + LUMA_EPS))) };
-#endif
     y = f2{ __builtin_truncf(t.x), __builtin_truncf(t.y) };
     fr = f2{ __builtin_amdgcn_fractf(t.x), __builtin_amdgcn_fractf(t.y) };
 }
@@ -285,12 +233,8 @@ __device__ __forceinline__ void chroma_px2(uint32_t r0, uint32_t g0, uint32_t b0
                                            float k2, float k3, f2& c, f2& fr)
 {
     const f2 r = { ubyte<B0>(r0), ubyte<B1>(r1) }, g = { ubyte<B0>(g0), ubyte<B1>(g1) }, b = { ubyte<B0>(b0), ubyte<B1>(b1) };
-#if JPEZY_PK_CHROMA
     const f2 q1 = { k1, k1 }, q2 = { k2, k2 }, q3 = { k3, k3 }, q0 = { CHROMA_EPS, CHROMA_EPS };
     const f2 t = pk_fma(q3, b, pk_fma(q2, g, pk_fma(q1, r, q0)));
-#else
-    const f2 t = { FMAF(k3, b.x, FMAF(k2, g.x, FMAF(k1, r.x, CHROMA_EPS))), FMAF(k3, b.y, FMAF(k2, g.y, FMAF(k1, r.y, CHROMA_EPS))) };
-#endif
     c = f2{ __builtin_truncf(t.x), __builtin_truncf(t.y) };
     fr = f2{ __builtin_amdgcn_fractf(t.x), __builtin_amdgcn_fractf(t.y) };
 }
@@ -396,9 +340,7 @@ __device__ __forceinline__ int dc_formula(float sum, float rq, float bias) { ret
 // error of fma(sum, ks, delta1) below 1e-5: the guard test flags the DC exactly when sum is a multiple of 8 Q (zero included), and
 // everywhere else (int)t' is the table's value.  A flagged DC evaluates dc_formula inside the candidate branch (0.6 % of blocks on
 // random pixels) and is never queued.  jpezy_ctx_create checks all of this for every sum with the same FP32 operations.
-#ifndef JPEZY_DC_GENERIC
-#define JPEZY_DC_GENERIC 1           // 0: the DC on a path of its own in every lane (dc_formula / dc_lookup ahead of the quantiser), A/B only
-#endif
+// (Against the DC on a path of its own in every lane -- the !DCG instance: profiles/r07_dc_generic_ab.txt.)
 
 // Quantise one block column and stage it in zig-zag order.  F: the column pass' four output pairs (order pair_row);
 // ks: the quantiser scales in the same order; dd = (delta1, delta1), th = 2 delta1; j: natural column; dc: the block's
@@ -419,11 +361,7 @@ __device__ __forceinline__ void quant_block_column(const f2* F, const f2* ks, f2
     // fr = fract(t') < 2 delta1 <=> the unbiased t is within delta1 of an integer (header comment)
     f2 t[4];
 #pragma unroll
-#if JPEZY_PK_QUANT
     for (int p = 0; p < 4; ++p) t[p] = pk_fma(F[p], ks[p], dd);
-#else
-    for (int p = 0; p < 4; ++p) t[p] = f2{ FMAF(F[p].x, ks[p].x, dd.x), FMAF(F[p].y, ks[p].y, dd.x) };
-#endif
 #ifdef JPEZY_DUMP_T   // diagnostic build: the level-1 values as the guard test sees them, bias removed
     if (live && dump_quad)
 #pragma unroll
@@ -547,10 +485,6 @@ struct QuadTrace { unsigned long long t2; unsigned long long ph[8]; };
 // ([2][16385] bytes) and the cosine table in LDS; null in the one-quad kernel, which reads all three from global memory.
 // The scheduler fences between the phases of a quad keep the one-quad kernel at 79 VGPRs (6 waves per SIMD); the persistent kernel has
 // 128 registers per lane anyway (16 waves per CU) and may let the scheduler overlap the phases (JPEZY_PS_FENCES=0).
-#ifndef JPEZY_DC_FORMULA_ONEQUAD
-#define JPEZY_DC_FORMULA_ONEQUAD 2   // the one-quad kernel's quantised DC: 0 = table lookup (three byte loads per quad), 1 = dc_formula unchecked (A/B only),
-                                     // 2 = dc_formula where the host check allowed it (EncParams::dc_rq != 0), else the table.  26.45 against 26.79 us (five rounds)
-#endif
 #define PHASE_FENCE() do { if (!PS || JPEZY_PS_FENCES) __builtin_amdgcn_sched_barrier(0); } while (0)
 struct NoHook { __device__ __forceinline__ void operator()() const {} };
 // after_pixels(): called once the raw pixel registers R, G, B are dead (behind step 2b) -- variant 3 requests the next quad's there
@@ -578,11 +512,9 @@ __device__ __forceinline__ void encode_quad_compute(const EncParams& p, const ui
     if (lane == 0) queue[0] = 0;
     PROBE_ALL();
     PkCos kc = pk_cos();
-#if JPEZY_PIN_CONSTANTS
     // ten SGPRs for the whole kernel: left alone, hipcc rebuilds every constant pair with s_mov_b32 in front of the packed
-    // instruction that uses it (~100 scalar instructions per wave, which share the SIMD's issue with the vector ones)
+    // instruction that uses it (~100 scalar instructions per wave, which share the SIMD's issue with the vector ones; profiles/r04_ab5.txt)
     asm volatile("" : "+s"(kc.k13), "+s"(kc.k37), "+s"(kc.k51), "+s"(kc.k75), "+s"(kc.k26));
-#endif
     // ---- 2. luma + row pass of the left and right block, into the transpose tile.  The integer samples stay in
     //         registers as floats, paired as the transform wants them -- YL/YR[k] = (Y[k], Y[7-k]) of the left / right
     //         block row, CS[k] likewise for the chroma row -- for the chroma row pass and the rare levels 2 and 3. ----
@@ -654,8 +586,9 @@ __device__ __forceinline__ void encode_quad_compute(const EncParams& p, const ui
     const F32Column* lcol = PS && JPEZY_PS_CONSTS_LDS ? &pst->f32col[0][ju] : &tab->f32col[0][ju];   // from LDS / from global memory (one-quad kernel)
     const uint32_t zz_lo = PRE ? pre->zz_lo : lcol->zz_lo, zz_hi = PRE ? pre->zz_hi : lcol->zz_hi;
     // persistent kernels: the formula by build switch (their launchers check its validity); one-quad kernel: by the kernel argument
-    // (dc_rq == 0: the formula does not hold for this build's constants -- the table lookup stays)
-    const bool DCF = PS ? (bool)JPEZY_PS_DC_FORMULA : (JPEZY_DC_FORMULA_ONEQUAD == 1 || (JPEZY_DC_FORMULA_ONEQUAD == 2 && p.dc_rq[0] != 0.f && p.dc_rq[1] != 0.f));
+    // (dc_rq == 0: the formula does not hold for this build's constants -- the table lookup, three byte loads per quad, stays).
+    // Formula against table: 26.45 against 26.79 us (five rounds, profiles/r05_persistent_ab.txt)
+    const bool DCF = PS ? (bool)JPEZY_PS_DC_FORMULA : (p.dc_rq[0] != 0.f && p.dc_rq[1] != 0.f);
     const signed char* dcq_l = PS && JPEZY_PS_DCQ_LDS ? dcq_lds : p.dcq_luma;
     const signed char* dcq_c = PS && JPEZY_PS_DCQ_LDS ? dcq_lds + 16385 : p.dcq_chroma;
     {
@@ -686,15 +619,14 @@ __device__ __forceinline__ void encode_quad_compute(const EncParams& p, const ui
     // ---- 5. chroma row pass, transpose, column pass ----
     if (!GRAY) {
         const bool odd = (row & 1) != 0;
-#if JPEZY_CHROMA_CONSTS_EARLY
         // the chroma quantiser record, requested ahead of the row pass (registers are free here): behind the column pass the three
-        // 16-byte loads would be issued and waited for back to back (the LDS statements' "memory" clobbers pin them there)
+        // 16-byte loads would be issued and waited for back to back (the LDS statements' "memory" clobbers pin them there;
+        // profiles/r07_dc_generic_ab.txt)
         f2 ks[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) ks[k] = PRE ? pre->ks_c[k] : f2{ lcol[8].ks[2 * k], lcol[8].ks[2 * k + 1] };
         const f2 dd = PRE ? pre->dd_c : f2{ lcol[8].delta1[0], lcol[8].delta1[1] };
         const float th_c = PRE ? pre->th_c : lcol[8].th;
-#endif
         f2 cX[4];
         fdct8p(CS, cX, kc);
         f2* dst = reinterpret_cast<f2*>(ldsf + m * C_MCU + (odd ? C_COMP : 0) + (row >> 1) * C_PITCH);
@@ -709,13 +641,6 @@ __device__ __forceinline__ void encode_quad_compute(const EncParams& p, const ui
             fdct8p(col, Fc, kc);
             dc_c = DCG ? 0 : DCF ? dc_formula(Fc[0].x, p.dc_rq[1], p.dc_bias[1]) : dc_lookup(Fc[0].x, dcq_c);
         }
-#if !JPEZY_CHROMA_CONSTS_EARLY
-        f2 ks[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) ks[k] = PRE ? pre->ks_c[k] : f2{ lcol[8].ks[2 * k], lcol[8].ks[2 * k + 1] };
-        const f2 dd = PRE ? pre->dd_c : f2{ lcol[8].delta1[0], lcol[8].delta1[1] };
-        const float th_c = PRE ? pre->th_c : lcol[8].th;
-#endif
         quant_block_column<DCG>(Fc, ks, dd, th_c, j, dc_c, p.dc_rq[1], p.dc_bias[1], live, sbase, zz_lo, zz_hi, 4 * STG_BLK, m * BPM + 4 + bx, queue, FORCE != 0 DUMP_ARG);
     }
     wave_sync();
@@ -852,8 +777,7 @@ __device__ __forceinline__ void encode_quad_store(const EncParams& p, uint32_t* 
                 // streamed out, never re-read by this kernel: a non-temporal store leaves less dirty data in the L2s
                 // for the end-of-kernel write-back (measured: 2 us per 4096^2 frame)
                 const uint4 v = *reinterpret_cast<const uint4*>(stage + (c >> 3) * STG_BLK + (c & 7) * 16);
-                typedef unsigned v4u __attribute__((ext_vector_type(4)));
-                __builtin_nontemporal_store(v4u{v.x, v.y, v.z, v.w}, reinterpret_cast<v4u*>(g4 + c));
+                nt_store16(g4 + c, v);
             }
         }
     }

@@ -1,36 +1,33 @@
-// jpezy_kernels.hip -- hand-written gfx950 (MI355X / CDNA4) kernels for the jpezy hot path.
+// jpezy_kernels_decode.hip -- the production fused decode kernel for gfx950 (MI355X / CDNA4).
 //
-//   fdct_quant_kernel   : RGB->YCbCr + 4:2:0 decimation + 8x8 FDCT + Annex-K quantise + zig-zag
-//                         (ref encoder/jpezy_encoder.hpp:90-172, 244-256; jpezy.hpp:36-45,131-152)
 //   dequant_idct_kernel : de-zig-zag + dequantise + 8x8 IDCT + nearest upsample + YCbCr->RGB + clamp
 //                         (ref decoder/jpezy_decoder.hpp:504-578, 645-676)
+//     MODE 0  exact, with the coefficient range test
+//     MODE 1  exact, without it (every 8-bit quantiser table: launch_dequant_idct decides)
+//     MODE 2  opt-in tolerance mode: luma in FP32, samples within one of the reference's (jpezy_ctx_set_decode_tolerance)
 //
-// Work decomposition (both kernels): one 64-lane wavefront owns a "quad" = 4 horizontally adjacent
-// 16x16 MCUs (64x16 pixels, 24 blocks); a 256-thread workgroup is 4 independent waves (no s_barrier --
-// each wave has a private LDS slice and synchronises with itself only).  Lane = (row, m): row = lane>>2
-// is a pixel row of the MCU, m = lane&3 the MCU of the quad, so one lane streams a 16-pixel row segment
-// of each plane as a single 16-byte access (4 lanes = 64 contiguous bytes) and the 3 KB of coefficients
-// of a quad move as 3 coalesced 1 KB wave accesses.  The two separable 1-D passes run in registers (one
-// 8-point transform per lane-row/column, 2 independent transforms per lane for ILP) with a padded,
-// bank-conflict-free LDS transpose between them.  No MFMA: FP64 8x8 is VALU work.
+// Work decomposition: one 64-lane wavefront owns a "quad" = 4 horizontally adjacent 16x16 MCUs (64x16 pixels, 24 blocks); a
+// workgroup is WPB = 2 waves, two adjacent quads.  Each wave has a private LDS slice and synchronises with itself only; the
+// one exchange between the two waves is the whole-line store of the colour planes (one __syncthreads, step 5).  Lane = (row, m):
+// row = lane>>2 is a pixel row of the MCU, m = lane&3 the MCU of the quad, so one lane streams a 16-pixel row segment of each
+// plane as a single 16-byte access and the 3 KB of coefficients of a quad move as 3 coalesced 1 KB wave accesses.  The two
+// separable 1-D passes run in registers with a padded LDS transpose between them.  No MFMA: FP64 8x8 is VALU work.
 //
-// Exactness (DESIGN.md "exactness"): the reference truncates FP64 results, so the output depends on the
-// exact rounding sequence only where the true value sits on a quantiser / integer boundary.  The fast
-// separable transform (FMA allowed, error < 1e-9) is accepted when the fixed-point value is >= 2 units
-// of 2^-24 (2^-18 for samples) away from every boundary; otherwise the coefficient is re-evaluated by
-// exact_*() in the reference's exact operation order (plain IEEE mul/add, no contraction).  DC terms are
-// sums of integers and are always evaluated exactly.  Colour conversion is evaluated in the reference's
-// exact FP64 order everywhere.  This file must be compiled with -ffp-contract=off; every fused
-// multiply-add below is an explicit __builtin_fma in a fast-path estimate.
-#include "jpezy_device.h"
+// Exactness (DESIGN.md "exactness"): the reference truncates FP64 results, so the output depends on the exact rounding sequence
+// only where the true value sits on an integer boundary.  The fast separable transform (FMA allowed, error < 1e-9) is accepted
+// when the sample is further than 2^-18 from every integer; otherwise it is re-evaluated by exact_idct_sample_sparse() in the
+// reference's exact operation order (plain IEEE mul/add, no contraction).  Colour conversion: step 5.  This file must be
+// compiled with -ffp-contract=off; every fused multiply-add below is an explicit __builtin_fma in a fast-path estimate.
+#include "jpezy_wave.h"
 #include "../../include/jpezy_constants.h"
 
 namespace jpezy_dev {
 
-__constant__ double c_cos[64] = JPEZY_COS_INIT;            // [u*8+x] = cos((2x+1)u*pi/16)
-__constant__ unsigned char c_zzinv[64] = JPEZY_ZZ_INV_INIT;  // natural index -> zig-zag position
+// (static: jpezy_kernels_f64.hip has tables of the same names)
+static __constant__ double c_cos[64] = JPEZY_COS_INIT;            // [u*8+x] = cos((2x+1)u*pi/16)
+static __constant__ unsigned char c_zzinv[64] = JPEZY_ZZ_INV_INIT;  // natural index -> zig-zag position
 // the same table by COLUMN: c_zzcol[u] = the eight zig-zag positions of natural column u (rows v = 0..7), one byte each -- the decode kernel's
-// lane (column u) fetches its eight staging offsets with ONE 8-byte load instead of eight byte loads (JPEZY_DEC_ZZCOL)
+// lane (column u) fetches its eight staging offsets with ONE 8-byte load instead of eight byte loads (profiles/r06_ab_dec.txt)
 struct ZzCol { uint32_t lo, hi; };
 constexpr unsigned char kZzInvH[64] = JPEZY_ZZ_INV_INIT;
 constexpr ZzCol zz_col(int u)
@@ -39,31 +36,7 @@ constexpr ZzCol zz_col(int u)
     for (int v = 0; v < 4; ++v) { lo |= (uint32_t)kZzInvH[v * 8 + u] << (8 * v); hi |= (uint32_t)kZzInvH[(v + 4) * 8 + u] << (8 * v); }
     return ZzCol{ lo, hi };
 }
-__constant__ ZzCol c_zzcol[8] = { zz_col(0), zz_col(1), zz_col(2), zz_col(3), zz_col(4), zz_col(5), zz_col(6), zz_col(7) };
-#ifndef JPEZY_DEC_ZZCOL
-#define JPEZY_DEC_ZZCOL 1
-#endif
-
-__device__ __forceinline__ unsigned fast_div(unsigned n, unsigned magic, unsigned shift)   // see fast_div_setup
-{
-    const unsigned q = __umulhi(n, magic);
-    return magic ? (((n - q) >> 1) + q) >> shift : n;
-}
-
-// wave-uniform "some lane": one v_cmp into an SGPR pair + s_cmp (HIP's __any goes through a 0/1 VGPR)
-__device__ __forceinline__ bool wave_any(bool x) { return __builtin_amdgcn_ballot_w64(x) != 0ull; }
-
-// Outputs are streamed out and never re-read by the kernel: a non-temporal store leaves less dirty data in the eight
-// L2s for the end-of-kernel write-back (measured on the f32 encode kernel: 2 us per 4096^2 frame).
-#ifndef JPEZY_NO_NT
-__device__ __forceinline__ void nt_store16(uint4* dst, uint4 v)
-{
-    typedef unsigned v4u __attribute__((ext_vector_type(4)));
-    __builtin_nontemporal_store(v4u{v.x, v.y, v.z, v.w}, reinterpret_cast<v4u*>(dst));
-}
-#else
-__device__ __forceinline__ void nt_store16(uint4* dst, uint4 v) { *dst = v; }
-#endif
+static __constant__ ZzCol c_zzcol[8] = { zz_col(0), zz_col(1), zz_col(2), zz_col(3), zz_col(4), zz_col(5), zz_col(6), zz_col(7) };
 
 #define JPEZY_S JPEZY_INV_SQRT2
 
@@ -78,68 +51,24 @@ __device__ __forceinline__ void nt_store16(uint4* dst, uint4 v) { *dst = v; }
 
 #define FMA(a, b, c) __builtin_fma((a), (b), (c))
 
-// LDS geometry (dwords), chosen so that the column reads (ds_read_b64, 32-lane groups, 64 banks) are
-// conflict free: per-MCU stride == 16 (mod 64) dwords.  Row pitch 36 dwords keeps 16-byte alignment and
-// limits the ds_write_b128 conflicts to 2-way.
-constexpr int Y_PITCH = 36;                 // 16 doubles + 2 pad
-constexpr int Y_MCU = 16 * Y_PITCH + 16;    // 592
-constexpr int C_PITCH = 20;                 // 8 doubles + 2 pad
-constexpr int C_COMP = 8 * C_PITCH;         // 160
-constexpr int C_MCU = 2 * C_COMP + 16;      // 336
-constexpr int TILE_DWORDS = 4 * Y_MCU;      // 2368 dwords = 9472 B: transpose tiles / staging
-// Behind the tiles: the wave's queue of guard-band hits (count + entries), never overlapped by a tile.
-constexpr int QUEUE_CAP = 126;
-constexpr int WAVE_LDS_DWORDS = TILE_DWORDS + 64;   // 9728 B per wave, 38912 B per workgroup (4 per CU)
-
 // Decode kernel LDS slice (dwords): the luma tile is exchanged in two halves (left blocks, then right blocks) so that
 // the slice is 5.4 KB instead of 9.5 KB and LDS no longer caps the kernel at 4 waves per SIMD.
 // Geometry from tools/profile/lds_bank_model.py (the lane groups and bank functions of MI355X_MICROARCH.md): the coefficient
 // staging area has a 144-byte block pitch (the zig-zag-indexed 2-byte column reads of the four MCUs then start 24 banks
 // apart: 108 LDS cycles per wave instead of 192), the luma half tile an MCU stride == 8 (mod 32) dwords (conflict-free
 // ds_write_b64 columns; the ds_read_b128 rows become 2-way: 128 cycles for both instead of 160 -- no pitch makes both
-// directions conflict-free), the chroma tile unpadded rows (64 instead of 80).  Model: 456 -> 324 cycles per wave;
-// counters (profiles/r02e_ab_decode.txt): SQ_LDS_BANK_CONFLICT 219 -> 104, SQ_LDS_IDX_ACTIVE 487 -> 371 per wave -- and
-// 39.5 -> 39.3 us: the kernel is not bound by its LDS traffic.
-#ifdef JPEZY_DEC_LDS_R01     // round-1 geometry, kept for A/B counters (tools/ab/ab_build.py)
-constexpr int DH_PITCH = 20, DH_MCU = 16 * DH_PITCH + 16;                    // 336
-constexpr int DC_PITCH = 20, DC_COMP = 8 * DC_PITCH, DC_MCU = 2 * DC_COMP + 16;
-constexpr int DSTG_PITCH = 128;               // bytes per staged block
-#else
+// directions conflict-free), the chroma tile unpadded rows (64 instead of 80).  Against the round-1 geometry (pitches 20 / 20,
+// 128-byte staged blocks) the model says 456 -> 324 cycles per wave; counters (profiles/r02e_ab_decode.txt): SQ_LDS_BANK_CONFLICT
+// 219 -> 104, SQ_LDS_IDX_ACTIVE 487 -> 371 per wave -- and 39.5 -> 39.3 us: the kernel is not bound by its LDS traffic.
 constexpr int DH_PITCH = 20;                  // 8 doubles + 2 pad
 constexpr int DH_MCU = 16 * DH_PITCH + 8;     // 328
 constexpr int DC_PITCH = 16, DC_COMP = 8 * DC_PITCH, DC_MCU = 2 * DC_COMP + 8;    // 16 / 128 / 264
-constexpr int DSTG_PITCH = 144;
-#endif
+constexpr int DSTG_PITCH = 144;               // bytes per staged block
 constexpr int TF_PITCH = 16, TF_MCU = 16 * TF_PITCH + 8;   // tolerance mode: the luma tile as floats, 4 x 264 dwords
 constexpr int DEC_TILE_DWORDS = 4 * 336;      // 1344 dwords = 5376 B
 constexpr int DEC_LDS_DWORDS = DEC_TILE_DWORDS + 16;
 static_assert(4 * DC_MCU <= DEC_TILE_DWORDS && 4 * DH_MCU <= DEC_TILE_DWORDS && 24 * DSTG_PITCH <= DEC_TILE_DWORDS * 4 &&
               1024 + 128 <= DEC_TILE_DWORDS && 4 * TF_MCU <= DEC_TILE_DWORDS, "decode slice too small");
-
-__device__ __forceinline__ void wave_sync()
-{
-    // LDS traffic of one wave is executed in order; this only stops the compiler from moving LDS
-    // accesses of different lanes across the phase boundary.
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// X[u] = sum_x x[x] * cos((2x+1)u*pi/16), u = 0..7 ; X[0] is the plain (exact, for integers) sum.
-__device__ __forceinline__ void fdct8(const double* x, double* X)
-{
-    const double s0 = x[0] + x[7], s1 = x[1] + x[6], s2 = x[2] + x[5], s3 = x[3] + x[4];
-    const double d0 = x[0] - x[7], d1 = x[1] - x[6], d2 = x[2] - x[5], d3 = x[3] - x[4];
-    const double e0 = s0 + s3, e1 = s1 + s2, e2 = s0 - s3, e3 = s1 - s2;
-    X[0] = e0 + e1;
-    X[4] = (e0 - e1) * C4;
-    X[2] = FMA(e3, C6, e2 * C2);
-    X[6] = FMA(-e3, C2, e2 * C6);
-    X[1] = FMA(d3, C7, FMA(d2, C5, FMA(d1, C3, d0 * C1)));
-    X[3] = FMA(-d3, C5, FMA(-d2, C1, FMA(-d1, C7, d0 * C3)));
-    X[5] = FMA(d3, C3, FMA(d2, C7, FMA(-d1, C1, d0 * C5)));
-    X[7] = FMA(-d3, C1, FMA(d2, C3, FMA(-d1, C5, d0 * C7)));
-}
 
 // x[y] = sum_v X[v] * cos((2y+1)v*pi/16)   (X[0] already carries its 1/sqrt2)
 __device__ __forceinline__ void idct8(const double* X, double* x)
@@ -172,320 +101,6 @@ __device__ __forceinline__ void idct8f(const float* X, float* x)
     x[1] = E1 + O1; x[6] = E1 - O1;
     x[2] = E2 + O2; x[5] = E2 - O2;
     x[3] = E3 + O3; x[4] = E3 - O3;
-}
-
-// ---- colour conversion in the reference's exact order (ref jpezy_encoder.hpp:244-256) ----
-__device__ __forceinline__ double ref_y(double r, double g, double b)
-{
-    return __builtin_trunc((0.2990 * r) + (0.5870 * g) + (0.1140 * b) - 128.0);
-}
-__device__ __forceinline__ double ref_cb(double r, double g, double b)
-{
-    return __builtin_trunc(-(0.1687 * r) - (0.3313 * g) + (0.5000 * b));
-}
-__device__ __forceinline__ double ref_cr(double r, double g, double b)
-{
-    return __builtin_trunc((0.5000 * r) - (0.4187 * g) - (0.0813 * b));
-}
-
-// In-order sum of one double per lane, lane 0 first: sum = (((0 + t0) + t1) + ...) + t63, every add
-// rounded -- the reference's accumulation order.  Wave-uniform result.
-__device__ __forceinline__ double ordered_wave_sum(double t)
-{
-    const int lo = (int)(unsigned)(__builtin_bit_cast(unsigned long long, t) & 0xFFFFFFFFull);
-    const int hi = (int)(unsigned)(__builtin_bit_cast(unsigned long long, t) >> 32);
-    double sum = 0;
-#pragma unroll
-    for (int k = 0; k < 64; ++k) {
-        const unsigned long long bits = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane(hi, k) << 32) |
-                                        (unsigned)__builtin_amdgcn_readlane(lo, k);
-        sum += __builtin_bit_cast(double, bits);
-    }
-    return sum;
-}
-
-struct BlockRef {   // the frame's planes: what the exact path needs to find a block again
-    const uint8_t* r;
-    const uint8_t* g;
-    const uint8_t* b;
-    int W, H;
-};
-
-// ---- exact-order FDCT + quantise of ONE coefficient by the whole wave (ref jpezy_encoder.hpp:146-172) ----
-// All arguments are wave-uniform.  Lane k owns term k = y*8+x of the reference's double loop: it re-reads its
-// pixel, converts it, forms (pic*cos[j][x])*cos[i][y]; the 64 terms are then added in the reference's order.
-// comp 0: luma block with top-left pixel (px0,py0), step 1.  comp 1/2: Cb/Cr of the MCU at (px0,py0), step 2
-// (top-left sample of each 2x2, ref :134-142).  Coordinates clamp to the image (ref :101,104).
-__device__ __forceinline__ int exact_fdct_coef_wave(const BlockRef& img, int px0, int py0, int comp, int i, int j,
-                                                    int Q, int lane)
-{
-    const int step = comp ? 2 : 1;
-    const int y = lane >> 3, x = lane & 7;
-    const int yy = min(py0 + y * step, img.H - 1);
-    const int xx = min(px0 + x * step, img.W - 1);
-    const size_t idx = (size_t)yy * img.W + xx;
-    const double rf = (double)img.r[idx], gf = (double)img.g[idx], bf = (double)img.b[idx];
-    const double pic = comp == 0 ? ref_y(rf, gf, bf) : comp == 1 ? ref_cb(rf, gf, bf) : ref_cr(rf, gf, bf);
-    const double sum = ordered_wave_sum(pic * c_cos[j * 8 + x] * c_cos[i * 8 + y]);
-    const double cu = j ? 1.0 : JPEZY_S, cv = i ? 1.0 : JPEZY_S;
-    const int dct = (int)(sum * cu * cv / 4);
-    return dct / Q;
-}
-
-// Quantise the 8 coefficients F[i] (vertical frequency i, this lane's horizontal frequency j).
-// ks[i] = cu*cv/(4Q) * 2^24.  n[i] = trunc(v/Q * 2^24); q[i] = trunc-toward-zero(n / 2^24).
-// Returns true when some coefficient lies within 1 unit of a multiple of 2^24 (candidate for the exact path).
-__device__ __forceinline__ bool quant8(const double* F, const double* ks, bool dc_lane, double rq_dc, int* n, int* q)
-{
-    constexpr int MASK = (1 << QFRAC_BITS) - 1;
-    unsigned m[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        n[i] = (int)(F[i] * ks[i]);                          // v_cvt_i32_f64 truncates toward zero
-        q[i] = (n[i] + ((n[i] >> 31) & MASK)) >> QFRAC_BITS;  // trunc-toward-zero division by 2^24
-        m[i] = (unsigned)(n[i] + 1) & MASK;                  // 0,1,2 <=> within one unit of a boundary
-    }
-    // DC: F[0] of the j == 0 lane is the exact integer sum of the block, so the reference value
-    // int(sum*S*S/4) is reproduced bit for bit; (|iv|+0.5)/Q is never within 0.5/Q of an integer.
-    {
-        const double iv = __builtin_trunc(F[0] * JPEZY_S * JPEZY_S / 4);
-        int nq = (int)((__builtin_fabs(iv) + 0.5) * rq_dc);
-        nq = iv < 0 ? -nq : nq;
-        if (dc_lane) {
-            q[0] = nq;
-            m[0] = MASK;
-        }
-    }
-    const unsigned a = min(min(m[0], m[1]), m[2]), b = min(min(m[3], m[4]), m[5]), c = min(m[6], m[7]);
-    return min(min(a, b), c) <= 2u;
-}
-
-// byte offsets of the staging area: blocks padded to 144 B so that the 8 blocks written by one
-// ds_write_b16 wave-instruction fall on different banks
-constexpr int STG_BLK = 144;
-
-// Quantise one block column, write it (zig-zag) to the staging area and queue the guard-band hits.
-// blk = index of the block inside the quad (m*BPM + b).  Queue entry = blk << 6 | natural index.
-__device__ __forceinline__ void quant_block_column(const double* F, const double* ks, int j, double rq_dc,
-                                                   bool live, const int* zoff, char* stage_blk, int blk,
-                                                   unsigned* queue)
-{
-    constexpr int MASK = (1 << QFRAC_BITS) - 1;
-    int n[8], q[8];
-    const bool cand = quant8(F, ks, j == 0, rq_dc, n, q);
-    if (cand && live) {   // rare.  Fully unrolled: a runtime index into n[] would send the array to scratch
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            // within one unit of a multiple of 2^24 -- except around 0, which is not a truncation boundary;
-            // the DC term of the j == 0 lane is already exact
-            const bool f = ((unsigned)(n[i] + 1) & MASK) <= 2u && (unsigned)(n[i] + 1) > 2u && !(i == 0 && j == 0);
-            if (f) {
-                const unsigned slot = atomicAdd(&queue[0], 1u);
-                if (slot < (unsigned)QUEUE_CAP)
-                    reinterpret_cast<unsigned short*>(queue + 1)[slot] = (unsigned short)((blk << 6) | (i * 8 + j));
-            }
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) *reinterpret_cast<int16_t*>(stage_blk + zoff[i]) = (int16_t)q[i];
-}
-
-__device__ __forceinline__ double byte_of(const uint32_t* w, int k)
-{
-    return (double)((w[k >> 2] >> ((k & 3) * 8)) & 0xFFu);
-}
-
-// ======================================================================================================
-// ENCODE
-// ======================================================================================================
-template <bool GRAY, bool ALIGNED, bool FORCE_EXACT>
-__global__ __launch_bounds__(64 * WPB, 4) void fdct_quant_kernel(EncParams p)
-{
-    __shared__ __attribute__((aligned(16))) uint32_t lds_all[WPB][WAVE_LDS_DWORDS];
-    constexpr int BPM = GRAY ? 4 : 6;
-    constexpr int STG_BASE = 4 * C_MCU * 4;                   // bytes: staging sits behind the chroma tile
-    static_assert(STG_BASE + 4 * 6 * STG_BLK <= TILE_DWORDS * 4, "staging does not fit the tile area");
-
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;   // WPB waves per workgroup
-    const long quad = (long)blockIdx.x * WPB + wave;
-    const long quads_per_frame = (long)p.mcu_rows * p.quads_per_row;
-    if (quad >= quads_per_frame * p.n_frames) return;   // wave-uniform
-    const int frame = (int)(quad / quads_per_frame);
-    const int qrem = (int)(quad - (long)frame * quads_per_frame);
-    const int mcu_y = qrem / p.quads_per_row;
-    const int quad_x = qrem - mcu_y * p.quads_per_row;
-
-    uint32_t* lds = lds_all[wave];
-    unsigned* queue = lds + TILE_DWORDS;                        // [0] = count, then 16-bit entries
-    if (lane == 0) queue[0] = 0;
-    const int row = lane >> 2, m = lane & 3;
-    const int mcu_x_raw = quad_x * 4 + m;
-    const bool live = mcu_x_raw < p.mcu_cols;
-    const int mcu_x = live ? mcu_x_raw : p.mcu_cols - 1;
-    const int W = p.W, H = p.H;
-    const uint8_t* pr = p.r + (size_t)frame * p.plane_stride;
-    const uint8_t* pg = p.g + (size_t)frame * p.plane_stride;
-    const uint8_t* pb = p.b + (size_t)frame * p.plane_stride;
-    const BlockRef img = { pr, pg, pb, W, H };
-
-    // ---- 1. stream this lane's 16-pixel row segment of the three planes ----
-    uint32_t R[4], G[4], B[4];
-    {
-        const int y = min(mcu_y * 16 + row, H - 1);             // edge replication, ref :101
-        const size_t rowoff = (size_t)y * W;
-        if (ALIGNED) {
-            const size_t off = rowoff + (size_t)mcu_x * 16;
-            const uint4 vr = *reinterpret_cast<const uint4*>(pr + off);
-            const uint4 vg = *reinterpret_cast<const uint4*>(pg + off);
-            const uint4 vb = *reinterpret_cast<const uint4*>(pb + off);
-            R[0] = vr.x; R[1] = vr.y; R[2] = vr.z; R[3] = vr.w;
-            G[0] = vg.x; G[1] = vg.y; G[2] = vg.z; G[3] = vg.w;
-            B[0] = vb.x; B[1] = vb.y; B[2] = vb.z; B[3] = vb.w;
-        } else {
-#pragma unroll
-            for (int w4 = 0; w4 < 4; ++w4) {
-                uint32_t ar = 0, ag = 0, ab = 0;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const int x = min(mcu_x * 16 + w4 * 4 + k, W - 1);   // ref :104
-                    ar |= (uint32_t)pr[rowoff + x] << (8 * k);
-                    ag |= (uint32_t)pg[rowoff + x] << (8 * k);
-                    ab |= (uint32_t)pb[rowoff + x] << (8 * k);
-                }
-                R[w4] = ar; G[w4] = ag; B[w4] = ab;
-            }
-        }
-    }
-
-    // ---- 2. luma of the 16 pixels, row pass of the left / right block, into the transpose tile ----
-    {
-        double yv[16], X[16];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) yv[k] = ref_y(byte_of(R, k), byte_of(G, k), byte_of(B, k));
-        fdct8(yv, X);
-        fdct8(yv + 8, X + 8);
-        double2* dst = reinterpret_cast<double2*>(lds + m * Y_MCU + row * Y_PITCH);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) dst[k] = make_double2(X[2 * k], X[2 * k + 1]);
-    }
-    wave_sync();
-
-    // ---- 3. luma column pass: lane (cq, m) owns column cq of the 16x16 tile = column j of two blocks ----
-    const int cq = row;                 // 0..15
-    const int j = cq & 7;
-    const DeviceTables* tab = p.tab;
-    char* stage = reinterpret_cast<char*>(lds) + STG_BASE;
-    int zoff[8];                        // byte offset of natural coefficient (i, j) inside a staged block
-#pragma unroll
-    for (int i = 0; i < 8; ++i) zoff[i] = 2 * (int)c_zzinv[i * 8 + j];
-    {
-        double Ftop[8], Fbot[8];
-        {
-            double col[16];
-            const uint32_t* src = lds + m * Y_MCU + cq * 2;
-#pragma unroll
-            for (int rr = 0; rr < 16; ++rr) col[rr] = *reinterpret_cast<const double*>(src + rr * Y_PITCH);
-            fdct8(col, Ftop);
-            fdct8(col + 8, Fbot);
-        }
-        wave_sync();   // every lane has read the luma tile: the slice is reused from here on
-
-        // ---- 4. quantise + zig-zag the two luma block columns into the staging area ----
-        double ks[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) ks[i] = tab->qscale[0][j][i];
-        const double rq = tab->rq_dc[0];
-        const int bx = cq >> 3;   // 0: left blocks (Y0,Y2), 1: right blocks (Y1,Y3)
-        quant_block_column(Ftop, ks, j, rq, live, zoff, stage + (m * BPM + bx) * STG_BLK, m * BPM + bx, queue);
-        quant_block_column(Fbot, ks, j, rq, live, zoff, stage + (m * BPM + 2 + bx) * STG_BLK, m * BPM + 2 + bx, queue);
-    }
-
-    // ---- 5. chroma: top-left pixel of every 2x2 (ref :134-142) = even pixel rows, even columns.  The odd-row
-    //         lane fetches its even neighbour's pixels (DPP row_shr:4) and computes Cr while the even-row lane
-    //         computes Cb, so all 64 lanes carry one chroma row each. ----
-    if (!GRAY) {
-        const bool odd = (row & 1) != 0;
-        uint32_t R2[4], G2[4], B2[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            // row_shr:4 within each 16-lane DPP row, written only to lanes 4-7 and 12-15 (bank_mask 0b1010)
-            R2[k] = (uint32_t)__builtin_amdgcn_update_dpp((int)R[k], (int)R[k], 0x114, 0xF, 0xA, false);
-            G2[k] = (uint32_t)__builtin_amdgcn_update_dpp((int)G[k], (int)G[k], 0x114, 0xF, 0xA, false);
-            B2[k] = (uint32_t)__builtin_amdgcn_update_dpp((int)B[k], (int)B[k], 0x114, 0xF, 0xA, false);
-        }
-        // Cb = (-(0.1687 r) - 0.3313 g) + 0.5 b ; Cr = (0.5 r - 0.4187 g) - 0.0813 b  (ref :249-256), both as
-        // trunc((k1*r - k2*g) + k3*b): (-a)*r == -(a*r) and x - y == x + (-y) hold bit for bit in IEEE-754.
-        const double k1 = odd ? 0.5000 : -0.1687, k2 = odd ? 0.4187 : 0.3313, k3 = odd ? -0.0813 : 0.5000;
-        double cv[8], cX[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k)
-            cv[k] = __builtin_trunc((k1 * byte_of(R2, 2 * k) - k2 * byte_of(G2, 2 * k)) + k3 * byte_of(B2, 2 * k));
-        fdct8(cv, cX);
-        double2* dst = reinterpret_cast<double2*>(lds + m * C_MCU + (odd ? C_COMP : 0) + (row >> 1) * C_PITCH);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) dst[k] = make_double2(cX[2 * k], cX[2 * k + 1]);
-        wave_sync();
-
-        double Fc[8];
-        {
-            double col[8];
-            const uint32_t* src = lds + m * C_MCU + (cq >> 3) * C_COMP + j * 2;
-#pragma unroll
-            for (int rr = 0; rr < 8; ++rr) col[rr] = *reinterpret_cast<const double*>(src + rr * C_PITCH);
-            fdct8(col, Fc);
-        }
-        double ks[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) ks[i] = tab->qscale[1][j][i];
-        const int comp = 1 + (cq >> 3);
-        quant_block_column(Fc, ks, j, tab->rq_dc[1], live, zoff, stage + (m * BPM + 3 + comp) * STG_BLK,
-                           m * BPM + 3 + comp, queue);
-    }
-    wave_sync();
-
-    // ---- 5b. guard-band hits: re-evaluate in the reference's exact operation order, one coefficient at a
-    //          time, all 64 lanes cooperating (rare: ~0.7 % of blocks on random pixels).  FORCE_EXACT (test
-    //          hook) and a queue overflow send EVERY coefficient of the quad through this path. ----
-    {
-        const unsigned nq = queue[0];
-        const bool all = FORCE_EXACT || nq > (unsigned)QUEUE_CAP;
-        const unsigned total = all ? (unsigned)(4 * BPM * 64) : nq;
-        if (total) {
-            const int valid_mcus = min(4, p.mcu_cols - quad_x * 4);
-            unsigned done = 0;
-#pragma unroll 1
-            for (unsigned e = 0; e < total; ++e) {
-                const unsigned code = all ? e : reinterpret_cast<const unsigned short*>(queue + 1)[e];
-                const int blk = __builtin_amdgcn_readfirstlane((int)(code >> 6)), nat = __builtin_amdgcn_readfirstlane((int)(code & 63));
-                const int em = blk / BPM, eb = blk - em * BPM;
-                if (em >= valid_mcus) continue;
-                const int ei = nat >> 3, ej = nat & 7;
-                const int emx = quad_x * 4 + em;
-                int px0 = emx * 16, py0 = mcu_y * 16, comp = 0;
-                if (eb < 4) { px0 += (eb & 1) * 8; py0 += (eb >> 1) * 8; } else { comp = eb - 3; }
-                const int Q = tab->qt[comp ? 1 : 0][nat];
-                const int qv = exact_fdct_coef_wave(img, px0, py0, comp, ei, ej, Q, lane);
-                if (lane == 0) *reinterpret_cast<int16_t*>(stage + blk * STG_BLK + 2 * (int)c_zzinv[nat]) = (int16_t)qv;
-                ++done;
-            }
-            if (lane == 0 && done) atomicAdd(p.fallback_count + ((blockIdx.x * (unsigned)WPB + wave) & (COUNTER_SHARDS - 1)), (unsigned long long)done);
-            wave_sync();
-        }
-    }
-
-    // ---- 6. coalesced store of the quad's coefficients (BPM*128 bytes per MCU, contiguous) ----
-    {
-        const int valid_mcus = min(4, p.mcu_cols - quad_x * 4);
-        const int valid_chunks = valid_mcus * BPM * 8;         // 16-byte chunks
-        int16_t* gbase = p.coeffs + (size_t)frame * p.coeffs_per_frame +
-                         ((size_t)mcu_y * p.mcu_cols + (size_t)quad_x * 4) * (BPM * 64);
-        uint4* g4 = reinterpret_cast<uint4*>(gbase);
-#pragma unroll
-        for (int k = 0; k < BPM * 128 * 4 / 1024; ++k) {
-            const int c = k * 64 + lane;
-            if (c < valid_chunks) nt_store16(g4 + c, *reinterpret_cast<const uint4*>(stage + (c >> 3) * STG_BLK + (c & 7) * 16));
-        }
-    }
 }
 
 // ======================================================================================================
@@ -585,13 +200,7 @@ __device__ __forceinline__ int cvt_floor_neg(float x)
     asm("v_cvt_flr_i32_f32_e64 %0, -%1" : "=v"(r) : "v"(x));
     return r;
 }
-#ifndef JPEZY_DEC_INT_COLOUR
-#define JPEZY_DEC_INT_COLOUR 1        // integer colour offsets (step 5 of dequant_idct_kernel); 0: doubles for every wave, as until round 3
-#endif
-constexpr float DEC_CHROMA_BAND = 5e-5f, DEC_CHROMA_GATE = 512.f;      // tests/test_colour_offsets.py
-#ifndef JPEZY_DEC_FULLLINE
-#define JPEZY_DEC_FULLLINE 1          // colour planes leave as whole 128-byte lines (see the store section of dequant_idct_kernel)
-#endif
+constexpr float DEC_CHROMA_BAND = 5e-5f, DEC_CHROMA_GATE = 512.f;      // integer colour offsets (step 5 of dequant_idct_kernel); tests/test_colour_offsets.py
 // waves per SIMD the register budget is set for (colour: 87 VGPRs since the chroma column pass runs after the luma halves)
 #ifndef JPEZY_DEC_WAVES
 #define JPEZY_DEC_WAVES 5
@@ -643,17 +252,11 @@ __global__ __launch_bounds__(64 * WPB, GRAY ? JPEZY_DEC_WAVES_GRAY : JPEZY_DEC_W
     double dq[TOL ? 1 : 8];
     float dqf[TOL ? 8 : 1];
     unsigned char zp[8];
-#if JPEZY_DEC_ZZCOL
     const ZzCol zc = c_zzcol[u];
-#endif
 #pragma unroll
     for (int v = 0; v < 8; ++v) {
         if (TOL) dqf[v] = p.dqscale_f[u * 8 + v]; else dq[v] = p.dqscale[(0 * 8 + u) * 8 + v];
-#if JPEZY_DEC_ZZCOL
         zp[v] = (unsigned char)(((v < 4 ? zc.lo : zc.hi) >> (8 * (v & 3))) & 0xFFu);
-#else
-        zp[v] = c_zzinv[v * 8 + u];
-#endif
     }
 
     // ---- 1. coalesced load of the quad's 3 KB of coefficients into the staging area ----
@@ -762,9 +365,6 @@ __global__ __launch_bounds__(64 * WPB, GRAY ? JPEZY_DEC_WAVES_GRAY : JPEZY_DEC_W
     //         runs the row pass of its 8 left pixels; then the same for the right blocks ----
     int Y[16];
     unsigned yflags = 0;
-#ifdef JPEZY_DEC_INTERLEAVE
-    double gc_early[8];
-#endif
     if constexpr (TOL) {
         // the whole luma tile as floats (pitch 16, MCU stride 264 dwords: the column stores are conflict-free, the 16-byte row
         // reads 2-way -- tools/profile/lds_bank_model.py); one exchange instead of two, no guard keys
@@ -804,19 +404,6 @@ __global__ __launch_bounds__(64 * WPB, GRAY ? JPEZY_DEC_WAVES_GRAY : JPEZY_DEC_W
             }
         }
         wave_sync();
-#ifdef JPEZY_DEC_INTERLEAVE
-        if (!GRAY && half == 0) {
-            const int comp = 1 + (cq >> 3);
-            double cin[8];
-#pragma unroll
-            for (int v = 0; v < 8; ++v) {
-                const int cv_ = (int)(short)(cpk[v >> 1] >> ((v & 1) * 16));
-                cin[v] = (double)cv_ * p.dqscale[(comp * 8 + u) * 8 + v];
-            }
-            if (u == 0) cin[0] = (JPEZY_S * JPEZY_S) * (double)((int)(short)(cpk[0] & 0xFFFFu) * p.dqt[comp * 64]) * 0.25;
-            idct8(cin, gc_early);
-        }
-#endif
         {
             double in[8], out[8];
             const double2* src = reinterpret_cast<const double2*>(lds + m * DH_MCU + row * DH_PITCH);
@@ -836,24 +423,15 @@ __global__ __launch_bounds__(64 * WPB, GRAY ? JPEZY_DEC_WAVES_GRAY : JPEZY_DEC_W
     unsigned cflags = 0;
     if (!GRAY) {
         {
-            double gc[8];
-#ifdef JPEZY_DEC_INTERLEAVE
-            if (!TOL) {
+            const int comp = 1 + (cq >> 3);
+            double cin[8], gc[8];
 #pragma unroll
-                for (int y = 0; y < 8; ++y) gc[y] = gc_early[y];
-            } else
-#endif
-            {
-                const int comp = 1 + (cq >> 3);
-                double cin[8];
-#pragma unroll
-                for (int v = 0; v < 8; ++v) {
-                    const int cv_ = (int)(short)(cpk[v >> 1] >> ((v & 1) * 16));
-                    cin[v] = (double)cv_ * p.dqscale[(comp * 8 + u) * 8 + v];
-                }
-                if (u == 0) cin[0] = (JPEZY_S * JPEZY_S) * (double)((int)(short)(cpk[0] & 0xFFFFu) * p.dqt[comp * 64]) * 0.25;
-                idct8(cin, gc);
+            for (int v = 0; v < 8; ++v) {
+                const int cv_ = (int)(short)(cpk[v >> 1] >> ((v & 1) * 16));
+                cin[v] = (double)cv_ * p.dqscale[(comp * 8 + u) * 8 + v];
             }
+            if (u == 0) cin[0] = (JPEZY_S * JPEZY_S) * (double)((int)(short)(cpk[0] & 0xFFFFu) * p.dqt[comp * 64]) * 0.25;
+            idct8(cin, gc);
             uint32_t* dst = lds + m * DC_MCU + (cq >> 3) * DC_COMP + u * 2;
 #pragma unroll
             for (int y = 0; y < 8; ++y) *reinterpret_cast<double*>(dst + y * DC_PITCH) = gc[y];
@@ -988,10 +566,9 @@ __global__ __launch_bounds__(64 * WPB, GRAY ? JPEZY_DEC_WAVES_GRAY : JPEZY_DEC_W
     // outside the gate, or forced samples (their range is not bounded) -- converts in doubles, the reference's own sequence, as
     // every wave did before.  tests/test_colour_offsets.py enumerates every pair inside the gate: offsets equal to the integer
     // floors, flags equal to the integral pairs, results equal to the reference's formula.  (The conversion was 236 of the kernel's
-    // 767 vector instructions, all of the slow class: 34.2 -> see DESIGN.md 4.2.)
+    // 767 vector instructions, all of the slow class: 34.2 -> see DESIGN.md 4.2; against doubles for every wave: profiles/r04_ab_dec2.txt.)
     uint32_t Rw[4], Gw[4], Bw[4];
     bool int_colour = false;
-#if JPEZY_DEC_INT_COLOUR
     if (!GRAY) {
         int oR[8], oG[8], oB[8];
         float kmin = 2.f, amax = 0.f;
@@ -1024,7 +601,6 @@ __global__ __launch_bounds__(64 * WPB, GRAY ? JPEZY_DEC_WAVES_GRAY : JPEZY_DEC_W
             }
         }
     }
-#endif
     if (GRAY) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) Rw[q] = Gw[q] = Bw[q] = clamp_pack4(Y + 4 * q);
@@ -1052,7 +628,6 @@ __global__ __launch_bounds__(64 * WPB, GRAY ? JPEZY_DEC_WAVES_GRAY : JPEZY_DEC_W
             Bw[q] = clamp_pack4(bi);
         }
     }
-#if JPEZY_DEC_FULLLINE
     // The two waves of a workgroup hold the two 64-byte halves of every 128-byte line of their 16 pixel rows.  They swap through
     // LDS so that wave 0 stores rows 0..7 and wave 1 rows 8..15 of BOTH quads: eight lanes = one whole line.  The launch takes the
     // same time either way (34.2 us per 4096^2 frame, three interleaved rounds), but half-line non-temporal stores are counted --
@@ -1081,7 +656,6 @@ __global__ __launch_bounds__(64 * WPB, GRAY ? JPEZY_DEC_WAVES_GRAY : JPEZY_DEC_W
             return;
         }
     }
-#endif
     const int py = mcu_y * 16 + row;
     if (live && py < H) {
         uint8_t* orp = p.r + (size_t)frame * p.plane_stride + (size_t)py * W;
@@ -1120,32 +694,6 @@ __global__ __launch_bounds__(64 * WPB, GRAY ? JPEZY_DEC_WAVES_GRAY : JPEZY_DEC_W
 // ======================================================================================================
 // launchers
 // ======================================================================================================
-template <typename P>
-static bool is_aligned16(const P& p, const void* a, const void* b, const void* c)
-{
-    return (p.W % 16 == 0) && (p.plane_stride % 16 == 0) && (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) % 16 == 0);
-}
-
-template <bool GRAY, bool ALIGNED>
-static void enc_launch2(const EncParams& p, bool force, dim3 grid, hipStream_t s)
-{
-    if (force)
-        hipLaunchKernelGGL((fdct_quant_kernel<GRAY, ALIGNED, true>), grid, dim3(64 * WPB), 0, s, p);
-    else
-        hipLaunchKernelGGL((fdct_quant_kernel<GRAY, ALIGNED, false>), grid, dim3(64 * WPB), 0, s, p);
-}
-
-hipError_t launch_fdct_quant(const EncParams& p, bool gray, bool force_exact, hipStream_t stream)
-{
-    const long quads = (long)p.n_frames * p.mcu_rows * p.quads_per_row;
-    if (quads <= 0) return hipSuccess;
-    const dim3 grid((unsigned)((quads + WPB - 1) / WPB));
-    const bool al = is_aligned16(p, p.r, p.g, p.b);
-    if (gray) { if (al) enc_launch2<true, true>(p, force_exact, grid, stream); else enc_launch2<true, false>(p, force_exact, grid, stream); }
-    else      { if (al) enc_launch2<false, true>(p, force_exact, grid, stream); else enc_launch2<false, false>(p, force_exact, grid, stream); }
-    return hipGetLastError();
-}
-
 template <bool GRAY, bool ALIGNED>
 static void dec_launch2(const DecParams& p, bool force, bool tol, dim3 grid, hipStream_t s)
 {

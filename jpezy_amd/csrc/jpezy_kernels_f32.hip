@@ -9,8 +9,7 @@ template <bool GRAY, bool ALIGNED, int FORCE, int EWPB, bool DCG>
 __global__ __launch_bounds__(64 * EWPB, JPEZY_F32_WAVES) void fdct_quant_f32_kernel(EncParams p)
 {
     __shared__ __attribute__((aligned(16))) uint32_t lds_all[EWPB][WAVE_LDS_DWORDS];
-    [[maybe_unused]] constexpr int BPM = GRAY ? 4 : 6;
-    constexpr bool COOP = ALIGNED && EWPB == 4 && JPEZY_COOP_LOAD;     // (the cooperative load is written for 4 waves: 4 x 4 rows of 256 bytes)
+    constexpr bool COOP = ALIGNED && EWPB == 4;     // (the cooperative load is written for 4 waves: 4 x 4 rows of 256 bytes)
     static_assert(!COOP || 3 * 4096 <= EWPB * WAVE_LDS_DWORDS * 4, "the pixel staging area lies over the waves' slices");
 
     // WPB waves per workgroup; the wave index is made an SGPR so that everything derived from it (quad position, plane
@@ -112,33 +111,6 @@ __global__ __launch_bounds__(64 * EWPB, JPEZY_F32_WAVES) void fdct_quant_f32_ker
     const unsigned long long tr_t1 = __builtin_amdgcn_s_memrealtime();
 #endif
     PHASE_STAMP(1);
-#ifdef JPEZY_ABL_LIGHT_TAIL
-    // TIMING PROBE (wrong results; jpezy_experiment.h): the workgroups of the launch's last JPEZY_ABL_LIGHT_TAIL groups do their loads and their
-    // stores and nothing in between -- the shortest waves a tail of any finer-grained design (half quads) could have.
-    // What the launch gains from that is the upper bound of what such a design can gain.
-    if (blockIdx.x + (unsigned)JPEZY_ABL_LIGHT_TAIL >= gridDim.x) {
-        char* st0 = reinterpret_cast<char*>(lds) + CT_BYTES;
-        uint32_t* w = reinterpret_cast<uint32_t*>(st0) + lane * 12;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { w[k] = R[k]; w[4 + k] = G[k]; w[8 + k] = B[k]; }
-        wave_sync();
-        if (has_quad) {
-            const int valid_chunks = min(4, p.mcu_cols - quad_x * 4) * BPM * 8;
-            int16_t* gbase = p.coeffs + (size_t)frame * p.coeffs_per_frame + ((size_t)mcu_y * p.mcu_cols + (size_t)quad_x * 4) * (BPM * 64);
-            uint4* g4 = reinterpret_cast<uint4*>(gbase);
-#pragma unroll
-            for (int k = 0; k < BPM * 128 * 4 / 1024; ++k) {
-                const int c = k * 64 + lane;
-                if (c < valid_chunks) {
-                    const uint4 v = *reinterpret_cast<const uint4*>(st0 + (c >> 3) * STG_BLK + (c & 7) * 16);
-                    typedef unsigned v4u __attribute__((ext_vector_type(4)));
-                    __builtin_nontemporal_store(v4u{v.x, v.y, v.z, v.w}, reinterpret_cast<v4u*>(g4 + c));
-                }
-            }
-        }
-        return;
-    }
-#endif
     encode_quad<GRAY, FORCE, false, DCG>(p, R, G, B, lds, lane, mcu_y, quad_x, frame, qidx, nullptr, nullptr, nullptr QUAD_TRACE_ARG);
 #ifdef JPEZY_TRACE
     if (frame == 0 && qidx < 65536u) {
@@ -164,7 +136,6 @@ __global__ __launch_bounds__(64 * EWPB, JPEZY_F32_WAVES) void fdct_quant_f32_ker
 #endif
 }
 
-
 }  // namespace f32
 
 template <bool GRAY, bool ALIGNED, int EW, bool DCG>
@@ -185,7 +156,7 @@ static void enc_f32_launch2(const EncParams& p, int force, dim3 grid, hipStream_
 {
     // the DC through the generic quantiser where jpezy_ctx_create verified it for this build's constants (both tables), else on its
     // own path from the exact table -- a second instance of the kernel, so that the common one carries no trace of the DC path
-    if (JPEZY_DC_GENERIC && p.dc_rq[0] != 0.f && p.dc_rq[1] != 0.f) enc_f32_launch3<GRAY, ALIGNED, EW, true>(p, force, grid, s);
+    if (p.dc_rq[0] != 0.f && p.dc_rq[1] != 0.f) enc_f32_launch3<GRAY, ALIGNED, EW, true>(p, force, grid, s);
     else enc_f32_launch3<GRAY, ALIGNED, EW, false>(p, force, grid, s);
 }
 
@@ -195,7 +166,7 @@ hipError_t launch_fdct_quant_f32(const EncParams& p0, bool gray, int force, hipS
     const bool al = (p.W % 16 == 0) && (p.plane_stride % 16 == 0) &&
                     (((uintptr_t)p.r | (uintptr_t)p.g | (uintptr_t)p.b) % 16 == 0);
     // four quads per workgroup with the cooperative load where the rows divide evenly, two with direct loads elsewhere
-    const int ew = (al && JPEZY_COOP_LOAD && p.quads_per_row % 4 == 0) ? 4 : 2;
+    const int ew = (al && p.quads_per_row % 4 == 0) ? 4 : 2;
     p.groups_per_row = (p.quads_per_row + ew - 1) / ew;
     const long groups = (long)p.mcu_rows * p.groups_per_row;
     if (groups <= 0 || p.n_frames <= 0) return hipSuccess;

@@ -1,7 +1,7 @@
 // jpezy_kernels_generic.hip -- decode for ANY baseline layout the reference's decoder accepts (1 or 3 components,
 // sampling factors 1..4).  Blocks are independent 8x8 inverse transforms whatever the layout:
 //   generic_idct_kernel : one wavefront per EIGHT consecutive blocks, lane = (block, column).  Fast path as in the fused
-//                         kernel of jpezy_kernels.hip: FP64 separable butterflies (column pass, transpose through LDS, row
+//                         kernel of jpezy_kernels_decode.hip: FP64 separable butterflies (column pass, transpose through LDS, row
 //                         pass), sample = int(v) with a guard band of 2^-18 around every integer, DC-only blocks exact by
 //                         construction.  A block with a sample inside the band (5e-4 of the blocks), with a coefficient
 //                         above the magnitude guard, or under the force_exact test hook is recomputed by all 64 lanes in
@@ -12,7 +12,7 @@
 //                         :504-528), then make_rgb / revise_value in the reference's FP64 order (ref :531-578, 672-676)
 // The fused kernel covers jpezy_encode's own 2x2,1x1,1x1 layout in one pass; this pair exists so that every file the
 // reference decodes also decodes here, at about a third of the fused kernel's speed.
-#include "jpezy_device.h"
+#include "jpezy_wave.h"
 #include "../../include/jpezy_constants.h"
 
 namespace jpezy_dev {
@@ -22,13 +22,6 @@ __constant__ double c_cos[64] = JPEZY_COS_INIT;
 __constant__ unsigned char c_zzinv[64] = JPEZY_ZZ_INV_INIT;
 #define JPEZY_S JPEZY_INV_SQRT2
 #define GFMA(a, b, c) __builtin_fma((a), (b), (c))
-
-__device__ __forceinline__ void gsync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // x[y] = sum_v X[v] * cos((2y+1)v*pi/16)   (X[0] already carries its 1/sqrt2); an estimate: FMAs allowed
 __device__ __forceinline__ void idct8_est(const double* X, double* x)
@@ -69,7 +62,7 @@ __global__ __launch_bounds__(64) void generic_idct_kernel(GenericDecParams p, lo
         if (g0 + (lane >> 3) < nblk) v = src[lane];                              // lane: block lane>>3, 16-byte piece lane&7
         *reinterpret_cast<uint4*>(reinterpret_cast<char*>(lds) + (lane >> 3) * (G_STG * 2) + (lane & 7) * 16) = v;
     }
-    gsync();
+    wave_sync();
     const int k = live ? (int)(g % p.blocks_per_mcu) : 0;
     int comp = 0;
     if (k >= p.blk_start[1]) comp = 1;
@@ -96,12 +89,12 @@ __global__ __launch_bounds__(64) void generic_idct_kernel(GenericDecParams p, lo
     const unsigned long long ac_any = __ballot(acor != 0);
     const bool dc_only = ((ac_any >> (8 * b)) & 0xFFull) == 0;
     const unsigned long long big = __ballot(amax > p.coef_limit);
-    gsync();                                                                     // staging consumed: the tile overwrites it
+    wave_sync();                                                                 // staging consumed: the tile overwrites it
 
     // ---- transpose, row pass ----
 #pragma unroll
     for (int y = 0; y < 8; ++y) *reinterpret_cast<double*>(lds + b * G_TILE + y * G_PITCH + u * 2) = col[y];
-    gsync();
+    wave_sync();
     int smp[8];
     bool flagged = false;
     {
@@ -141,10 +134,10 @@ __global__ __launch_bounds__(64) void generic_idct_kernel(GenericDecParams p, lo
         int cq = 0;
         if (kq >= p.blk_start[1]) cq = 1;
         if (kq >= p.blk_start[2]) cq = 2;
-        gsync();
+        wave_sync();
         // natural index `lane`: coefficient at zig-zag position zzinv[lane], times its quantiser (ref :645-650)
         dct[lane] = (int)p.coeffs[gq * 64 + c_zzinv[lane]] * p.qt[cq * 64 + lane];
-        gsync();
+        wave_sync();
         const int y = lane >> 3, x = lane & 7;
         double sum = 0;
         for (int v = 0; v < 8; ++v) {
@@ -162,12 +155,6 @@ __global__ __launch_bounds__(64) void generic_idct_kernel(GenericDecParams p, lo
 
 __device__ __forceinline__ uint32_t revise(double v) { return (v < 0.0) ? 0u : (v > 255.0) ? 255u : (uint32_t)v; }
 
-__device__ __forceinline__ unsigned gdiv(unsigned n, unsigned magic, unsigned shift)      // fast_div_setup, jpezy_device.h
-{
-    const unsigned q = __umulhi(n, magic);
-    return magic ? (((n - q) >> 1) + q) >> shift : n;
-}
-
 // One thread: four consecutive pixels of a row (one 4-byte store per plane when the row allows it); a workgroup: 256 pixels
 // of four rows.  Everything that depends on the row only (MCU row, the component's block row, whether decode_mcu ever
 // writes that row of the component's plane) is computed once per thread.
@@ -182,7 +169,7 @@ __global__ __launch_bounds__(256) void generic_rgb_kernel(GenericDecParams p)
         p.r += f * p.plane_stride; p.g += f * p.plane_stride; p.b += f * p.plane_stride;
     }
     const unsigned mw = (unsigned)p.hmax * 8u, mh = (unsigned)p.vmax * 8u;
-    const unsigned uy = gdiv(y, p.mh_magic, p.mh_shift), iy = y - uy * mh;
+    const unsigned uy = fast_div(y, p.mh_magic, p.mh_shift), iy = y - uy * mh;
     // decode_mcu (ref :504-528) writes block (kx, ky) of a component at plane offset (kx*8, ky*8) -- not scaled by the
     // replication factor -- as a rectangle of 8*dupx x 8*dupy samples, ky outer, kx inner; the last write to a position
     // stays.  For H == hmax or H == 1 that is ordinary nearest-neighbour upsampling.  For the other legal factors
@@ -196,13 +183,13 @@ __global__ __launch_bounds__(256) void generic_rgb_kernel(GenericDecParams p)
         const unsigned ky = min(cvv - 1u, iy >> 3), yu = iy - ky * 8u;                   // last block row written over iy
         rowok[c] = c < p.ncomp && yu < 8u * dupy;
         rowblk[c] = (unsigned)p.blk_start[c] + ky * (unsigned)p.ch[c];
-        rowsmp[c] = gdiv(yu, p.dy_magic[c], p.dy_shift[c]) * 8u;
+        rowsmp[c] = fast_div(yu, p.dy_magic[c], p.dy_shift[c]) * 8u;
     }
     const unsigned npx = min(4u, (unsigned)p.W - x0);
     int smp[3][4];
     {
         // the four pixels sit in one MCU (x0 is a multiple of 4, MCUs are multiples of 8 wide)
-        const unsigned ux = gdiv(x0, p.mw_magic, p.mw_shift), ix0 = x0 - ux * mw;
+        const unsigned ux = fast_div(x0, p.mw_magic, p.mw_shift), ix0 = x0 - ux * mw;
         const size_t mcu_blk = ((size_t)uy * p.mcu_cols + ux) * (size_t)p.blocks_per_mcu;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
@@ -222,7 +209,7 @@ __global__ __launch_bounds__(256) void generic_rgb_kernel(GenericDecParams p)
                 for (unsigned j = 0; j < 4; ++j) {
                     const unsigned ix = ix0 + j;
                     const unsigned kx = min(chh - 1u, ix >> 3), xu = ix - kx * 8u;
-                    if (xu < 8u * dupx) smp[c][j] = p.samples[(mcu_blk + rowblk[c] + kx) * 64 + rowsmp[c] + gdiv(xu, p.dx_magic[c], p.dx_shift[c])];
+                    if (xu < 8u * dupx) smp[c][j] = p.samples[(mcu_blk + rowblk[c] + kx) * 64 + rowsmp[c] + fast_div(xu, p.dx_magic[c], p.dx_shift[c])];
                 }
             }
         }

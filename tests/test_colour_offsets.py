@@ -1,4 +1,4 @@
-"""The decode kernel's colour conversion without FP64 (jpezy_amd/csrc/jpezy_kernels.hip, step 5): proof by enumeration.
+"""The decode kernel's colour conversion without FP64 (jpezy_amd/csrc/jpezy_kernels_decode.hip, step 5): proof by enumeration.
 
 The reference converts in doubles and truncates (ref decoder/jpezy_decoder.hpp:567-578, revise_value :672-676):
     r = Y + V * 1.4020,  g = Y - U * 0.3441 - V * 0.7139,  b = Y + U * 1.7718      (U = Cb - 128, V = Cr - 128, integers)

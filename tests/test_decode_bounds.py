@@ -1,4 +1,4 @@
-"""The two numerical bounds the decode kernel's modes rest on (jpezy_amd/csrc/jpezy_kernels.hip, jpezy_capi.hip upload_dequant),
+"""The two numerical bounds the decode kernel's modes rest on (jpezy_amd/csrc/jpezy_kernels_decode.hip, jpezy_capi.hip upload_dequant),
 re-derived on the CPU with an emulation of the kernel's butterfly sequence:
 
 * exact mode trusts its FP64 fast path for every int16 coefficient as long as |c * Q| <= 2^23 (every 8-bit quantiser table):
@@ -68,7 +68,7 @@ def test_tolerance_mode_fp32_luma_error_is_below_one():
     got = samples(cq, np.float32)
     ref = samples(cq, np.longdouble)
     err = float(np.abs(got.astype(np.longdouble) - ref).max())
-    assert err < (13 + 2) * 2.0 ** -24 * 2.0 ** 19 < 1.0, err      # the bound quoted in jpezy_kernels.hip: 0.47
+    assert err < (13 + 2) * 2.0 ** -24 * 2.0 ** 19 < 1.0, err      # the bound quoted in jpezy_kernels_decode.hip: 0.47
     # and therefore truncated samples differ by at most one
     assert int(np.abs(np.trunc(got.astype(np.float64)) - np.trunc(ref.astype(np.float64))).max()) <= 1
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""LDS bank-conflict model of the decode kernel's accesses (dequant_idct_kernel, jpezy_kernels.hip), per the lane groups and
+"""LDS bank-conflict model of the decode kernel's accesses (dequant_idct_kernel, jpezy_kernels_decode.hip), per the lane groups and
 bank functions of /opt/skills/guides/MI355X_MICROARCH.md (section LDS): a wave64 access is served in fixed lane groups, one
 LDS cycle per group when conflict-free; every extra distinct address on a busy bank adds a cycle.  Prints LDS-array cycles
 per wave for each access class of the current geometry and of candidate geometries; the counters to compare with are

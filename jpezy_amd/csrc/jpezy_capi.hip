@@ -147,14 +147,14 @@ jpezy_ctx* jpezy_ctx_create(int device)
             for (int t = 0; t < 2; ++t) (hh ? h.f32col[t][j].zz_hi : h.f32col[t][j].zz_lo) = w;
         }
     bool ok = hipSetDevice(device) == hipSuccess;
-    ok = ok && hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) == hipSuccess;
-    ok = ok && hipMalloc((void**)&c->d_tab, sizeof(DeviceTables)) == hipSuccess;
-    ok = ok && hipMalloc((void**)&c->d_counter, sizeof(unsigned long long) * COUNTER_SHARDS) == hipSuccess;
-    ok = ok && hipMalloc((void**)&c->d_dqscale, sizeof(double) * 3 * 64) == hipSuccess;
-    ok = ok && hipMalloc((void**)&c->d_dqt, sizeof(int) * 3 * 64) == hipSuccess;
-    ok = ok && hipMalloc((void**)&c->d_dqscale_f, sizeof(float) * 64) == hipSuccess;
-    ok = ok && hipMemcpy(c->d_tab, &h, sizeof h, hipMemcpyHostToDevice) == hipSuccess;
-    ok = ok && hipMemset(c->d_counter, 0, sizeof(unsigned long long) * COUNTER_SHARDS) == hipSuccess;
+    ok = ok && c->stream.create() == hipSuccess;
+    ok = ok && c->d_tab.try_reserve(sizeof(DeviceTables)) == hipSuccess;
+    ok = ok && c->d_counter.try_reserve(sizeof(unsigned long long) * COUNTER_SHARDS) == hipSuccess;
+    ok = ok && c->d_dqscale.try_reserve(sizeof(double) * 3 * 64) == hipSuccess;
+    ok = ok && c->d_dqt.try_reserve(sizeof(int) * 3 * 64) == hipSuccess;
+    ok = ok && c->d_dqscale_f.try_reserve(sizeof(float) * 64) == hipSuccess;
+    ok = ok && hipMemcpy(c->d_tab.p, &h, sizeof h, hipMemcpyHostToDevice) == hipSuccess;
+    ok = ok && hipMemset(c->d_counter.p, 0, sizeof(unsigned long long) * COUNTER_SHARDS) == hipSuccess;
     if (!ok) {
         set_err(JPEZY_E_HIP, std::string("context creation failed: ") + hipGetErrorString(hipGetLastError()));
         jpezy_ctx_destroy(c);
@@ -165,31 +165,7 @@ jpezy_ctx* jpezy_ctx_create(int device)
 
 void jpezy_ctx_destroy(jpezy_ctx* c)
 {
-    if (!c) return;
-    for (jpezy_ctx* w : c->workers) jpezy_ctx_destroy(w);
-    c->workers.clear();
-    (void)hipSetDevice(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    c->pipe.release();
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    if (c->d_tab) (void)hipFree(c->d_tab);
-    if (c->d_counter) (void)hipFree(c->d_counter);
-    if (c->d_dqscale) (void)hipFree(c->d_dqscale);
-    if (c->d_dqt) (void)hipFree(c->d_dqt);
-    if (c->d_dqscale_f) (void)hipFree(c->d_dqscale_f);
-    for (auto& b : c->in) b.release();
-    c->out.release();
-    c->scratch.release();
-    if (c->d_codes) (void)hipFree(c->d_codes);
-    if (c->e_pinned) (void)hipHostFree(c->e_pinned);
-    if (c->b_pin) (void)hipHostFree(c->b_pin);
-    if (c->h_fb_pin) (void)hipHostFree(c->h_fb_pin);
-    for (uint8_t* q : c->b_stage) if (q) (void)hipHostFree(q);
-    for (DevBuf* b : { &c->b_scan, &c->b_U, &c->b_cnt, &c->b_rb, &c->b_state, &c->b_prop, &c->b_meta, &c->b_coef }) b->release();
-    for (DevBuf& b : c->b_planes) b.release();
-    for (DevBuf* b : { &c->e_tmp, &c->e_small, &c->e_U, &c->e_cnt, &c->e_out, &c->e_coef, &c->e_hdr, &c->e_status, &c->e_tt, &c->e_fft, &c->e_S, &c->e_base, &c->e_ft,
-                       &c->dump_t, &c->h_scan, &c->h_U, &c->h_cnt, &c->h_off, &c->h_state, &c->h_setup, &c->h_small, &c->h_dc, &c->h_dcbuf }) b->release();
-    delete c;
+    if (c) delete c;
 }
 
 int jpezy_ctx_sync(jpezy_ctx* c)
@@ -201,7 +177,7 @@ int jpezy_ctx_sync(jpezy_ctx* c)
 }
 
 int jpezy_ctx_device(const jpezy_ctx* c) { return c ? c->device : -1; }
-void* jpezy_ctx_stream(const jpezy_ctx* c) { return c ? (void*)c->stream : nullptr; }
+void* jpezy_ctx_stream(const jpezy_ctx* c) { return c ? (void*)(hipStream_t)c->stream : nullptr; }
 
 void jpezy_ctx_set_force_exact(jpezy_ctx* c, int on)
 {
@@ -235,8 +211,8 @@ long jpezy_ctx_last_fallback_count(jpezy_ctx* c)
     static thread_local unsigned long long shards[COUNTER_SHARDS];
     if (hipSetDevice(c->device) != hipSuccess) return -1;
     if (hipDeviceSynchronize() != hipSuccess) return -1;
-    if (hipMemcpy(shards, c->d_counter, sizeof shards, hipMemcpyDeviceToHost) != hipSuccess) return -1;
-    if (hipMemset(c->d_counter, 0, sizeof shards) != hipSuccess) return -1;
+    if (hipMemcpy(shards, c->d_counter.p, sizeof shards, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    if (hipMemset(c->d_counter.p, 0, sizeof shards) != hipSuccess) return -1;
     unsigned long long v = 0;
     for (unsigned long long s : shards) v += s;
 #ifdef JPEZY_WITH_LAB
@@ -253,7 +229,7 @@ long jpezy_ctx_last_fallback_count(jpezy_ctx* c)
 int jpezy_internal_check_dims(const jpezy_ctx* c, int W, int H, int n_frames)
 {
     if (!c) return set_err(JPEZY_E_BADARG, "null context");
-    if (W <= 0 || H <= 0 || W > 65535 || H > 65535) return set_err(JPEZY_E_BADARG, "width/height must be in 1..65535 (16-bit SOF0 fields)");
+    if (int rc = check_wh(W, H)) return rc;
     if (n_frames <= 0) return set_err(JPEZY_E_BADARG, "n_frames must be positive");
     return JPEZY_OK;
 }
@@ -272,13 +248,13 @@ int jpezy_fdct_quant_dev(jpezy_ctx* c, const uint8_t* d_r, const uint8_t* d_g, c
     p.plane_stride = plane_stride;
     p.coeffs = d_coeffs;
     p.coeffs_per_frame = jpezy_coeff_count(W, H, gray);
-    p.tab = c->d_tab;
-    p.dcq_luma = c->d_tab->dcq[0];       // address arithmetic only: d_tab is a device pointer
-    p.dcq_chroma = c->d_tab->dcq[1];
-    p.fallback_count = c->d_counter;
+    p.tab = c->d_tab.as<DeviceTables>();
+    p.dcq_luma = p.tab->dcq[0];          // address arithmetic only: d_tab is a device pointer
+    p.dcq_chroma = p.tab->dcq[1];
+    p.fallback_count = c->d_counter.as<unsigned long long>();
 #ifdef JPEZY_TRACE
-    if (!c->d_trace) HIP_TRY(hipMalloc((void**)&c->d_trace, sizeof(unsigned long long) * 13 * 65536));   // 4 words per wave + 9 phase stamps (JPEZY_TRACE=3)
-    p.trace = c->d_trace;
+    if (int rc = c->d_trace.reserve(sizeof(unsigned long long) * 13 * 65536)) return rc;
+    p.trace = c->d_trace.as<unsigned long long>();
 #endif
 #ifdef JPEZY_DUMP_T
     if (int rc = c->dump_t.reserve(p.coeffs_per_frame * (size_t)n_frames * sizeof(float))) return rc;
@@ -292,8 +268,7 @@ int jpezy_fdct_quant_dev(jpezy_ctx* c, const uint8_t* d_r, const uint8_t* d_g, c
     p.n_frames = n_frames;
     fast_div_setup((unsigned)p.quads_per_row, &p.qpr_magic, &p.qpr_shift);
     for (int t = 0; t < 2; ++t) { p.dc_rq[t] = c->dc_rq[t]; p.dc_bias[t] = c->dc_bias[t]; }
-    // the f32 kernel puts the frame index in grid.y (at most 65535): larger batches go out in chunks
-    constexpr int kMaxFramesPerLaunch = 65535;
+    // the f32 kernel puts the frame index in grid.y: larger batches go out in chunks
     for (int f0 = 0; f0 < n_frames; f0 += kMaxFramesPerLaunch) {
         EncParams q = p;
         q.n_frames = n_frames - f0 < kMaxFramesPerLaunch ? n_frames - f0 : kMaxFramesPerLaunch;
@@ -328,7 +303,7 @@ int jpezy_debug_read_t(jpezy_ctx* c, float* host, size_t n)
 int jpezy_debug_read_trace(jpezy_ctx* c, unsigned long long* host, size_t n)
 {
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(host, c->d_trace, n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(host, c->d_trace.p, n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     return JPEZY_OK;
 }
 #endif
@@ -345,32 +320,24 @@ try {
     if (!r || !g || !b || !coeffs) return set_err(JPEZY_E_BADARG, "null host pointer");
     HIP_TRY(hipSetDevice(c->device));
     const size_t plane = (size_t)W * H;
-    const int mcu_cols = jpezy_mcu_cols(W), B = gray ? 4 : 6;
-    const size_t ncoef = jpezy_coeff_count(W, H, gray);
+    const int B = gray ? 4 : 6;
     const std::vector<HostChunk> chunks = plan_host_chunks(W, H, n_frames, 3, c->host_chunk_bytes);
-    // a chunk's planes sit one behind the other in its slot, P bytes apart (a multiple of 16: the aligned kernel stays usable)
-    size_t P = 0, max_out = 0;
-    for (const HostChunk& k : chunks) {
-        const size_t rows = (size_t)std::min(H - k.y0 * 16, (k.y1 - k.y0) * 16);
-        P = std::max(P, k.nf > 1 || k.y1 - k.y0 == jpezy_mcu_rows(H) ? plane * k.nf : rows * W);
-        max_out = std::max(max_out, (size_t)k.nf * (k.y1 - k.y0) * mcu_cols * B * 128);
-    }
-    P = (P + 15) & ~(size_t)15;
+    const size_t P = plane_pitch(chunks, W, H);
+    size_t max_out = 0;
+    for (const HostChunk& k : chunks) max_out = std::max(max_out, k.coef_bytes(W, B));
     const uint8_t* src[3] = { r, g, b };
     int rc_kernel = JPEZY_OK;
     std::string err;
     auto plan = [&](int i) {
         const HostChunk& k = chunks[(size_t)i];
         jpezy_host::ChunkPlan p;
-        const size_t rows = (size_t)std::min(H - k.y0 * 16, (k.y1 - k.y0) * 16);
-        const size_t bytes = k.nf > 1 ? plane * k.nf : rows * W, off = (size_t)k.f0 * plane + (size_t)k.y0 * 16 * W;
-        for (int q = 0; q < 3; ++q) p.in.push_back({ const_cast<uint8_t*>(src[q]) + off, bytes, (size_t)q * P });
-        p.out.push_back({ coeffs + (size_t)k.f0 * ncoef + (size_t)k.y0 * mcu_cols * B * 64, (size_t)k.nf * (k.y1 - k.y0) * mcu_cols * B * 128, 0 });
+        for (int q = 0; q < 3; ++q) p.in.push_back({ const_cast<uint8_t*>(src[q]) + k.plane_off(W, H), k.plane_bytes(W, H), (size_t)q * P });
+        p.out.push_back({ coeffs + k.coef_off(W, H, B), k.coef_bytes(W, B), 0 });
         return p;
     };
     auto kernel = [&](int i, uint8_t* d_in, uint8_t* d_out, hipStream_t s) -> hipError_t {
         const HostChunk& k = chunks[(size_t)i];
-        const int Hc = std::min(H - k.y0 * 16, (k.y1 - k.y0) * 16);
+        const int Hc = k.rows(H);
         const int rc = jpezy_fdct_quant_dev(c, d_in, d_in + P, d_in + 2 * P, k.nf > 1 ? plane : (size_t)Hc * W, W, Hc, gray, k.nf, (int16_t*)d_out, s);
         if (rc != JPEZY_OK) { rc_kernel = rc; return hipErrorLaunchFailure; }
         return hipSuccess;
@@ -403,9 +370,9 @@ static int upload_dequant(jpezy_ctx* c, const uint16_t qt[4][64], const uint8_t 
     static thread_local float h_scale_f[8][8];
     for (int u = 0; u < 8; ++u)
         for (int v = 0; v < 8; ++v) h_scale_f[u][v] = (float)h_scale[0][u][v];
-    HIP_TRY(hipMemcpy(c->d_dqscale, h_scale, sizeof h_scale, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(c->d_dqscale_f, h_scale_f, sizeof h_scale_f, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(c->d_dqt, h_qt, sizeof h_qt, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->d_dqscale.p, h_scale, sizeof h_scale, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->d_dqscale_f.p, h_scale_f, sizeof h_scale_f, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->d_dqt.p, h_qt, sizeof h_qt, hipMemcpyHostToDevice));
     std::memcpy(c->dq_cache, sel, sizeof sel);
     int qmax = 1;
     for (int k = 0; k < 3; ++k)
@@ -439,17 +406,16 @@ int jpezy_dequant_idct_dev(jpezy_ctx* c, const int16_t* d_coeffs, const uint16_t
     p.coeffs_per_frame = jpezy_coeff_count(W, H, 0);
     p.r = d_r; p.g = d_g; p.b = d_b;
     p.plane_stride = plane_stride;
-    p.dqscale = c->d_dqscale;
-    p.dqscale_f = c->d_dqscale_f;
-    p.dqt = c->d_dqt;
+    p.dqscale = c->d_dqscale.as<double>();
+    p.dqscale_f = c->d_dqscale_f.as<float>();
+    p.dqt = c->d_dqt.as<int>();
     p.coef_limit = c->dec_tolerance ? c->coef_limit : c->coef_limit_exact;
-    p.fallback_count = c->d_counter;
+    p.fallback_count = c->d_counter.as<unsigned long long>();
     p.W = W; p.H = H;
     p.mcu_cols = jpezy_mcu_cols(W);
     p.mcu_rows = jpezy_mcu_rows(H);
     p.quads_per_row = (p.mcu_cols + 3) / 4;
     p.n_frames = n_frames;
-    constexpr int kMaxFramesPerLaunch = 65535;           // grid.y
     for (int f0 = 0; f0 < n_frames; f0 += kMaxFramesPerLaunch) {
         DecParams q = p;
         q.n_frames = n_frames - f0 < kMaxFramesPerLaunch ? n_frames - f0 : kMaxFramesPerLaunch;
@@ -468,32 +434,23 @@ try {
     HIP_TRY(hipSetDevice(c->device));
     if (int rc = upload_dequant(c, qt, comp_tq, c->stream)) return rc;      // tables first: never rewritten while chunks are in flight
     const size_t plane = (size_t)W * H;
-    const int mcu_cols = jpezy_mcu_cols(W);
-    const size_t ncoef = jpezy_coeff_count(W, H, 0);
     const std::vector<HostChunk> chunks = plan_host_chunks(W, H, n_frames, 3, c->host_chunk_bytes);
-    size_t P = 0, max_in = 0;
-    for (const HostChunk& k : chunks) {
-        const size_t rows = (size_t)std::min(H - k.y0 * 16, (k.y1 - k.y0) * 16);
-        P = std::max(P, k.nf > 1 || k.y1 - k.y0 == jpezy_mcu_rows(H) ? plane * k.nf : rows * W);
-        max_in = std::max(max_in, (size_t)k.nf * (k.y1 - k.y0) * mcu_cols * 6 * 128);
-    }
-    P = (P + 15) & ~(size_t)15;
+    const size_t P = plane_pitch(chunks, W, H);
+    size_t max_in = 0;
+    for (const HostChunk& k : chunks) max_in = std::max(max_in, k.coef_bytes(W, 6));
     uint8_t* dst[3] = { r, g, b };
     int rc_kernel = JPEZY_OK;
     std::string err;
     auto plan = [&](int i) {
         const HostChunk& k = chunks[(size_t)i];
         jpezy_host::ChunkPlan p;
-        const size_t rows = (size_t)std::min(H - k.y0 * 16, (k.y1 - k.y0) * 16);
-        const size_t bytes = k.nf > 1 ? plane * k.nf : rows * W, off = (size_t)k.f0 * plane + (size_t)k.y0 * 16 * W;
-        p.in.push_back({ const_cast<int16_t*>(coeffs) + (size_t)k.f0 * ncoef + (size_t)k.y0 * mcu_cols * 6 * 64,
-                         (size_t)k.nf * (k.y1 - k.y0) * mcu_cols * 6 * 128, 0 });
-        for (int q = 0; q < 3; ++q) p.out.push_back({ dst[q] + off, bytes, (size_t)q * P });
+        p.in.push_back({ const_cast<int16_t*>(coeffs) + k.coef_off(W, H, 6), k.coef_bytes(W, 6), 0 });
+        for (int q = 0; q < 3; ++q) p.out.push_back({ dst[q] + k.plane_off(W, H), k.plane_bytes(W, H), (size_t)q * P });
         return p;
     };
     auto kernel = [&](int i, uint8_t* d_in, uint8_t* d_out, hipStream_t s) -> hipError_t {
         const HostChunk& k = chunks[(size_t)i];
-        const int Hc = std::min(H - k.y0 * 16, (k.y1 - k.y0) * 16);
+        const int Hc = k.rows(H);
         const int rc = jpezy_dequant_idct_dev(c, (const int16_t*)d_in, qt, comp_tq, k.nf > 1 ? plane : (size_t)Hc * W, W, Hc, gray, k.nf, d_out,
                                               d_out + P, d_out + 2 * P, s);
         if (rc != JPEZY_OK) { rc_kernel = rc; return hipErrorLaunchFailure; }
@@ -545,12 +502,12 @@ int jpezy_internal_generic_dev_core(jpezy_ctx* c, const int16_t* d_coeffs, const
     const uint8_t tq3[3] = { comp_tq[0], (uint8_t)(ncomp > 1 ? comp_tq[1] : 0), (uint8_t)(ncomp > 2 ? comp_tq[2] : 0) };
     if (int rc = upload_dequant(c, qt, tq3, s)) return rc;
     p.coeffs = d_coeffs;
-    p.samples = (int*)c->scratch.p;
-    p.qt = c->d_dqt;
-    p.dqscale = c->d_dqscale;
+    p.samples = c->scratch.as<int>();
+    p.qt = c->d_dqt.as<int>();
+    p.dqscale = c->d_dqscale.as<double>();
     p.coef_limit = c->coef_limit;
     p.force_exact = c->force_exact != 0;
-    p.fallback_count = c->d_counter;
+    p.fallback_count = c->d_counter.as<unsigned long long>();
     p.r = d_r; p.g = d_g; p.b = d_b;
     HIP_TRY(launch_dequant_idct_generic(p, s));
     return JPEZY_OK;

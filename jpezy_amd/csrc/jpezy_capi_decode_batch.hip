@@ -144,24 +144,22 @@ try {
             const int nt = (int)std::max(1u, std::min<unsigned>(std::min<unsigned>(hwp ? hwp : 4u, 8u), (unsigned)(n + 15) / 16));
             std::atomic<int> next{ 0 };
             auto work = [&] { for (int i = next.fetch_add(1); i < n; i = next.fetch_add(1)) prep(i); };
-            std::vector<std::thread> pool;
-            for (int t = 1; t < nt; ++t) pool.emplace_back(work);
+            Joiner pool;
+            for (int t = 1; t < nt; ++t) pool.start(work);
             work();
-            for (auto& t : pool) t.join();
         }
         std::vector<const Cand*> cand;
         for (const Cand& cd : all)
             if (cd.good) cand.push_back(&cd);
         // the planes of slice k go down to the caller's buffers on a thread and a stream of their own while slice k + 1 is decoded
         // (two plane buffers): a 1080p file is 6.2 MB of planes, PCIe is what bounds a batch
-        hipStream_t s_down = nullptr;
-        HIP_TRY(hipStreamCreateWithFlags(&s_down, hipStreamNonBlocking));
+        Stream s_down;
+        HIP_TRY(s_down.create());
         // (three plane buffers: with two, slice k waits for the planes of slice k - 2 to be delivered, and a slice of 1080p noise -- 1.7 ms of
         // decoding, 2.8 ms of download and hand-out -- then takes (1.7 + 2.8) / 2 = 2.25 ms; with three the link's 1.8 ms is the bound)
-        std::thread drainer[jpezy_ctx::B_DEPTH];
         std::atomic<int> drain_err{ 0 };
         int slice_no = 0;
-        auto join_all = [&] { for (auto& t : drainer) if (t.joinable()) t.join(); };
+        Joiner drainer(jpezy_ctx::B_DEPTH);          // (after s_down: joined before the stream goes, on every way out)
         std::vector<char> taken(cand.size(), 0);
         for (size_t a = 0; a < cand.size(); ++a) {
             if (taken[a]) continue;
@@ -193,7 +191,7 @@ try {
                 std::vector<FastFile> slice(grp.begin() + s0, grp.begin() + std::min(grp.size(), s0 + per_slice));
                 std::vector<char> okv;
                 const int pb = slice_no % jpezy_ctx::B_DEPTH;
-                if (drainer[pb].joinable()) drainer[pb].join();             // the slice that used this plane buffer has been delivered
+                drainer.join((size_t)pb);                                   // the slice that used this plane buffer has been delivered
                 if (decode_slice_fast(c, slice, gi, gray, pb, okv) != JPEZY_OK) continue;      // (the per-file path reports what is wrong)
                 ++slice_no;
                 std::vector<int> idx;                                        // (k, caller index) of the files decoded here
@@ -217,14 +215,9 @@ try {
                 static const bool direct = std::getenv("JPEZY_BATCH_DIRECT") != nullptr;
                 if (!direct && 3 * pstride * nfs <= ((size_t)256 << 20)) {       // (slices of very large pictures: no quarter-GB of pinned memory each)
                     const size_t need = 3 * pstride * nfs;
-                    if (c->b_stage_cap[pb] < need) {
-                        if (c->b_stage[pb]) (void)hipHostFree(c->b_stage[pb]);
-                        c->b_stage[pb] = nullptr; c->b_stage_cap[pb] = 0;
-                        if (hipHostMalloc((void**)&c->b_stage[pb], need + (need >> 2), hipHostMallocDefault) == hipSuccess) c->b_stage_cap[pb] = need + (need >> 2);
-                    }
-                    stage = c->b_stage_cap[pb] >= need ? c->b_stage[pb] : nullptr;         // (no pinned memory: the per-plane copies)
+                    stage = c->b_stage[pb].reserve_soft(need, need + (need >> 2)) ? c->b_stage[pb].p : nullptr;   // (no pinned memory: the per-plane copies)
                 }
-                drainer[pb] = std::thread([=, &drain_err] {
+                drainer.ts[(size_t)pb] = std::thread([=, &drain_err, &s_down] {
                     if (hipSetDevice(device) != hipSuccess) { drain_err.store(1); return; }
                     if (stage) {
                         if (hipMemcpyAsync(stage, pl, 3 * pstride * nfs, hipMemcpyDeviceToHost, s_down) != hipSuccess ||
@@ -239,10 +232,9 @@ try {
                             }
                         };
                         const int nt = 3 * plane * (idx.size() / 2) > ((size_t)8 << 20) ? 4 : 1;
-                        std::vector<std::thread> helpers;
-                        for (int t = 1; t < nt; ++t) helpers.emplace_back(hand_out, (size_t)2 * t, (size_t)2 * nt);
+                        Joiner helpers;
+                        for (int t = 1; t < nt; ++t) helpers.start(hand_out, (size_t)2 * t, (size_t)2 * nt);
                         hand_out(0, (size_t)2 * nt);
-                        for (auto& h : helpers) h.join();
                         return;
                     }
                     for (size_t q = 0; q + 1 < idx.size(); q += 2) {
@@ -257,8 +249,7 @@ try {
                 });
             }
         }
-        join_all();
-        (void)hipStreamDestroy(s_down);
+        drainer.join();
         if (drain_err.load()) return set_err(JPEZY_E_HIP, "decode_jpeg_batch: copying the planes to the host failed");
     }
     unsigned hw = std::thread::hardware_concurrency();
@@ -285,10 +276,11 @@ try {
             if (status[i] < 0) msg[(size_t)i] = g_err;               // this thread's message
         }
     };
-    std::vector<std::thread> pool;
-    for (int k = 1; k < nw; ++k) pool.emplace_back(work, k);
-    work(0);
-    for (auto& t : pool) t.join();
+    {
+        Joiner pool;
+        for (int k = 1; k < nw; ++k) pool.start(work, k);
+        work(0);
+    }
     for (int i = 0; i < n; ++i)
         if (status[i] < 0) return set_err(status[i], "decode_jpeg_batch: file " + std::to_string(i) + ": " + msg[(size_t)i]);
     return JPEZY_OK;

@@ -23,10 +23,11 @@ try {
             if (sizes[f] < 0) failed.store(1);
         }
     };
-    std::vector<std::thread> pool;
-    for (unsigned t = 1; t < nt; ++t) pool.emplace_back(work);
-    work();
-    for (auto& t : pool) t.join();
+    {
+        Joiner pool;
+        for (unsigned t = 1; t < nt; ++t) pool.start(work);
+        work();
+    }
     return failed.load() ? set_err(JPEZY_E_FORMAT, "write_jpeg_batch: at least one frame failed (see sizes[])") : JPEZY_OK;
 }
 JPEZY_CATCH
@@ -36,7 +37,7 @@ namespace {
 
 int ensure_code_tables(jpezy_ctx* c)
 {
-    if (c->d_codes) return JPEZY_OK;
+    if (c->d_codes.p) return JPEZY_OK;
     uint16_t code[4][256];
     uint8_t len[4][256];
     jpezy_host::enc_code_tables(code, len);
@@ -57,8 +58,8 @@ int ensure_code_tables(jpezy_ctx* c)
                 h.fast[t][(run << 6) | (v + 32)] = (bits << 5) | (uint32_t)(len[2 + t][k] + sz);
             }
     }
-    HIP_TRY(hipMalloc((void**)&c->d_codes, sizeof h));
-    HIP_TRY(hipMemcpy(c->d_codes, &h, sizeof h, hipMemcpyHostToDevice));
+    if (int rc = c->d_codes.reserve(sizeof h)) return rc;
+    HIP_TRY(hipMemcpy(c->d_codes.p, &h, sizeof h, hipMemcpyHostToDevice));
     return JPEZY_OK;
 }
 
@@ -73,7 +74,7 @@ int entropy_chunk(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H, int gray,
     E::Job job;
     job.coeffs = d_coeffs;
     job.coeffs_per_frame = jpezy_coeff_count(W, H, gray);
-    job.tables = c->d_codes;
+    job.tables = c->d_codes.as<jpezy_dev::entropy::CodeTables>();
     job.blocks_per_frame = (unsigned)nblk;
     job.bpm = gray ? 4 : 6;
     job.n_frames = F;
@@ -127,14 +128,8 @@ int entropy_chunk(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H, int gray,
 
     // 4. header + entropy-coded segment + EOI into the caller's buffers.  One device-to-host copy of all streams into a
     //    pinned staging buffer (per-frame copies into pageable memory cost more than the kernels for small frames).
-    if (c->e_pinned_cap < o_stride * F) {
-        if (c->e_pinned) (void)hipHostFree(c->e_pinned);
-        c->e_pinned = nullptr;
-        c->e_pinned_cap = 0;
-        HIP_TRY(hipHostMalloc((void**)&c->e_pinned, o_stride * F, hipHostMallocDefault));
-        c->e_pinned_cap = o_stride * F;
-    }
-    HIP_TRY(hipMemcpyAsync(c->e_pinned, c->e_out.p, o_stride * F, hipMemcpyDeviceToHost, s));
+    if (int rc = c->e_pinned.reserve(o_stride * F)) return rc;
+    HIP_TRY(hipMemcpyAsync(c->e_pinned.p, c->e_out.p, o_stride * F, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     // (four threads when there is much to hand out: a core copies ~25 GB/s -- 256 frames of 1080p noise, 168 MB: 11.9 -> 7 ms per call)
     std::atomic<int> failed{ 0 };
@@ -145,17 +140,18 @@ int entropy_chunk(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H, int gray,
             const size_t hdr = jpezy_host::write_header(W, H, comment, dst, cap);
             const size_t body = (size_t)(nbytes[f] + fftot[f]);
             if (!hdr || hdr + body + 2 > cap) { sizes[f] = JPEZY_E_NOSPACE; failed.store(1); continue; }
-            std::memcpy(dst + hdr, c->e_pinned + (size_t)f * o_stride, body);
+            std::memcpy(dst + hdr, c->e_pinned.p + (size_t)f * o_stride, body);
             dst[hdr + body] = 0xFF;
             dst[hdr + body + 1] = 0xD9;
             sizes[f] = (long)(hdr + body + 2);
         }
     };
     const int n_copy = o_stride * (size_t)F > ((size_t)8 << 20) && F >= 4 ? 4 : 1;
-    std::vector<std::thread> helpers;
-    for (int t = 1; t < n_copy; ++t) helpers.emplace_back(hand_out, t, n_copy);
-    hand_out(0, n_copy);
-    for (auto& h : helpers) h.join();
+    {
+        Joiner helpers;
+        for (int t = 1; t < n_copy; ++t) helpers.start(hand_out, t, n_copy);
+        hand_out(0, n_copy);
+    }
     if (failed.load()) *any_failed = true;
     return JPEZY_OK;
 }
@@ -194,7 +190,7 @@ int jpezy_write_jpeg_gpu_dev(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H
     const size_t piece = E::assemble_piece_bytes();
     const size_t u_stride = (nblk * 208 + 8 + piece - 1) / piece * piece;
     // frames per pass: worst-case streams below ~1 GiB, and at most 65535 (the frame index is a grid dimension)
-    const int per = (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>((size_t)n_frames, 65535), ((size_t)1 << 30) / u_stride));
+    const int per = (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>((size_t)n_frames, kMaxFramesPerLaunch), ((size_t)1 << 30) / u_stride));
     const size_t cpf = jpezy_coeff_count(W, H, gray);
     const size_t tpf = E::tiles256(nblk);                           // tiles of one frame (a tile never straddles frames)
     const bool self = E::assemble_scans_tiles_itself(tpf);
@@ -204,7 +200,7 @@ int jpezy_write_jpeg_gpu_dev(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H
         E::Job job;
         job.coeffs = d_coeffs + (size_t)f0 * cpf;
         job.coeffs_per_frame = cpf;
-        job.tables = c->d_codes;
+        job.tables = c->d_codes.as<jpezy_dev::entropy::CodeTables>();
         job.blocks_per_frame = (unsigned)nblk;
         job.bpm = gray ? 4 : 6;
         job.n_frames = F;
@@ -264,7 +260,7 @@ try {
     const size_t nblk = (size_t)jpezy_mcu_cols(W) * jpezy_mcu_rows(H) * 6;
     // chunk the batch so that the worst-case unstuffed streams (208 bytes per block) stay below ~1 GiB
     const size_t worst = nblk * 208 + 4096;
-    int per = (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>((size_t)n_frames, 65535), ((size_t)1 << 30) / worst));   // 65535: grid dimension
+    int per = (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>((size_t)n_frames, kMaxFramesPerLaunch), ((size_t)1 << 30) / worst));   // 65535: grid dimension
     bool any_failed = false;
     const size_t cpf = jpezy_coeff_count(W, H, gray);
     for (int f0 = 0; f0 < n_frames; f0 += per) {
@@ -296,35 +292,30 @@ try {
     HIP_TRY(hipSetDevice(c->device));
     // the planes go up band by band (jpezy_hostpipe.h) while the bands before them are transformed into the frame's
     // coefficient buffer on the device; the Huffman stage then runs on the whole frame
-    const size_t plane = (size_t)W * H;
-    const int mcu_cols = jpezy_mcu_cols(W), B = gray ? 4 : 6;
+    const int B = gray ? 4 : 6;
     if (int rc = c->e_coef.reserve(jpezy_coeff_count(W, H, gray) * sizeof(int16_t))) return rc;
     const std::vector<HostChunk> chunks = plan_host_chunks(W, H, 1, 3, c->host_chunk_bytes);
-    size_t P = 0;
-    for (const HostChunk& k : chunks) P = std::max(P, (size_t)std::min(H - k.y0 * 16, (k.y1 - k.y0) * 16) * W);
-    P = (P + 15) & ~(size_t)15;
+    const size_t P = plane_pitch(chunks, W, H);
     const uint8_t* src[3] = { r, g, b };
     int rc_kernel = JPEZY_OK;
     std::string err;
     auto plan = [&](int i) {
         const HostChunk& k = chunks[(size_t)i];
         jpezy_host::ChunkPlan p;
-        const size_t rows = (size_t)std::min(H - k.y0 * 16, (k.y1 - k.y0) * 16);
-        for (int q = 0; q < 3; ++q) p.in.push_back({ const_cast<uint8_t*>(src[q]) + (size_t)k.y0 * 16 * W, rows * W, (size_t)q * P });
+        for (int q = 0; q < 3; ++q) p.in.push_back({ const_cast<uint8_t*>(src[q]) + k.plane_off(W, H), k.plane_bytes(W, H), (size_t)q * P });
         return p;
     };
     auto kernel = [&](int i, uint8_t* d_in, uint8_t*, hipStream_t s) -> hipError_t {
         const HostChunk& k = chunks[(size_t)i];
-        const int Hc = std::min(H - k.y0 * 16, (k.y1 - k.y0) * 16);
+        const int Hc = k.rows(H);
         const int rc = jpezy_fdct_quant_dev(c, d_in, d_in + P, d_in + 2 * P, (size_t)Hc * W, W, Hc, gray, 1,
-                                            (int16_t*)c->e_coef.p + (size_t)k.y0 * mcu_cols * B * 64, s);
+                                            c->e_coef.as<int16_t>() + k.coef_off(W, H, B), s);
         if (rc != JPEZY_OK) { rc_kernel = rc; return hipErrorLaunchFailure; }
         return hipSuccess;
     };
     const hipError_t e = c->pipe.run(c->device, c->stream, (int)chunks.size(), 3 * P, 0, plan, kernel, &err);
     if (rc_kernel != JPEZY_OK) return rc_kernel;
     if (e != hipSuccess) return set_err(JPEZY_E_HIP, err.empty() ? std::string("host pipeline: ") + hipGetErrorString(e) : err);
-    (void)plane;
     return jpezy_write_jpeg_gpu(c, (const int16_t*)c->e_coef.p, W, H, gray, comment, out, cap);
 }
 JPEZY_CATCH

@@ -18,19 +18,11 @@ int read_jpeg_host_to_device(jpezy_ctx* c, const uint8_t* data, size_t len, jpez
     // would otherwise hold gigabytes of page-locked memory for the life of their parent); a pinned allocation that fails is not an
     // error: the pageable path below does the same work.
     const size_t pin_limit = c->is_batch_child ? ((size_t)32 << 20) : ((size_t)256 << 20);
-    if (bytes <= pin_limit) {
-        if (c->h_fb_cap < bytes) {
-            if (c->h_fb_pin) (void)hipHostFree(c->h_fb_pin);
-            c->h_fb_pin = nullptr; c->h_fb_cap = 0;
-            if (hipHostMalloc((void**)&c->h_fb_pin, bytes, hipHostMallocDefault) == hipSuccess) c->h_fb_cap = bytes;
-            else { c->h_fb_pin = nullptr; (void)hipGetLastError(); }
-        }
-        if (c->h_fb_pin) {
-            const int rc = jpezy_host::read_jpeg(data, len, info, (int16_t*)c->h_fb_pin, total, &err);
-            if (rc < 0) { g_err = err; return rc; }
-            HIP_TRY(hipMemcpy(d_coeffs, c->h_fb_pin, bytes, hipMemcpyHostToDevice));
-            return JPEZY_OK;
-        }
+    if (bytes <= pin_limit && c->h_fb_pin.reserve_soft(bytes) && c->h_fb_pin.p) {
+        const int rc = jpezy_host::read_jpeg(data, len, info, c->h_fb_pin.as<int16_t>(), total, &err);
+        if (rc < 0) { g_err = err; return rc; }
+        HIP_TRY(hipMemcpy(d_coeffs, c->h_fb_pin.p, bytes, hipMemcpyHostToDevice));
+        return JPEZY_OK;
     }
     std::vector<int16_t> tmp(total);
     const int rc = jpezy_host::read_jpeg(data, len, info, tmp.data(), tmp.size(), &err);
@@ -142,12 +134,7 @@ int jpezy_internal_huffdec_streams(jpezy_ctx* c, const std::vector<DevStream>& s
 
     // buffers
     const size_t scan_bytes = total_chunks * chunk;
-    if (c->b_pin_cap < scan_bytes) {
-        if (c->b_pin) (void)hipHostFree(c->b_pin);
-        c->b_pin = nullptr; c->b_pin_cap = 0;
-        HIP_TRY(hipHostMalloc((void**)&c->b_pin, scan_bytes + (scan_bytes >> 2) + 4096, hipHostMallocDefault));
-        c->b_pin_cap = scan_bytes + (scan_bytes >> 2) + 4096;
-    }
+    if (int rc = c->b_pin.reserve(scan_bytes, scan_bytes + (scan_bytes >> 2) + 4096)) return rc;
     const size_t meta_F = (sizeof(HD::BatchFile) * nf + 255) & ~(size_t)255, meta_S = (sizeof(HD::Setup) * ns + 255) & ~(size_t)255;
     const size_t meta_wg = ((size_t)n_wg * 4 + 255) & ~(size_t)255, meta_act = ((size_t)nf * 4 + 255) & ~(size_t)255;
     if (int rc = c->b_scan.reserve(scan_bytes + 64)) return rc;
@@ -167,11 +154,11 @@ int jpezy_internal_huffdec_streams(jpezy_ctx* c, const std::vector<DevStream>& s
 
     // segments side by side (64-byte aligned, zero padded) in pinned memory: one upload
     for (unsigned k = 0; k < nf; ++k) {
-        uint8_t* dst = c->b_pin + (size_t)F[k].chunk0 * chunk;
+        uint8_t* dst = c->b_pin.p + (size_t)F[k].chunk0 * chunk;
         std::memcpy(dst, streams[k].scan, streams[k].n);
         std::memset(dst + streams[k].n, 0, (size_t)F[k].n_chunks * chunk - streams[k].n);
     }
-    HIP_TRY(hipMemcpyAsync(c->b_scan.p, c->b_pin, scan_bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(c->b_scan.p, c->b_pin.p, scan_bytes, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d_F, F.data(), sizeof(HD::BatchFile) * nf, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d_S, setups.data(), sizeof(HD::Setup) * ns, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d_wg_file, wg_file.data(), (size_t)n_wg * 4, hipMemcpyHostToDevice, s));

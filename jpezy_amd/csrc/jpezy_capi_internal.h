@@ -1,4 +1,4 @@
-// jpezy_capi_internal.h -- what the translation units of the C-ABI share (internal): error plumbing, device buffers, the context.
+// jpezy_capi_internal.h -- what the translation units of the C-ABI share (internal): error macros, the context (owners: jpezy_owners.h).
 // jpezy_capi.hip (context, the two transform stages), jpezy_capi_entropy.hip (Huffman coding, host and GPU),
 // jpezy_capi_huffdec.hip (GPU Huffman decoding of one file, decoder::decode end to end), jpezy_capi_decode_batch.hip (the batch form).
 #pragma once
@@ -23,28 +23,23 @@
 #include "jpezy_entropy.h"
 #include "jpezy_huffdec.h"
 #include "jpezy_host_codec.h"
+#include "jpezy_owners.h"
 #include "jpezy_hostpipe.h"
 
 using namespace jpezy_dev;
 
 namespace jpezy_capi {
 
-inline thread_local std::string g_err;
-
-inline int set_err(int code, const std::string& msg)
-{
-    g_err = msg;
-    return code;
-}
 // one comment limit for every writer (include/jpezy_hip.h, JPEZY_MAX_COMMENT)
 inline int check_comment(const char* comment, const char* who)
 {
     if (jpezy_host::comment_ok(comment)) return JPEZY_OK;
     return set_err(JPEZY_E_BADARG, std::string(who) + ": comment longer than JPEZY_MAX_COMMENT (" + std::to_string(JPEZY_MAX_COMMENT) + " bytes)");
 }
-inline int hip_err(hipError_t e, const char* what)
+inline int check_wh(int W, int H)
 {
-    return set_err(JPEZY_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
+    if (W <= 0 || H <= 0 || W > 65535 || H > 65535) return set_err(JPEZY_E_BADARG, "width/height must be in 1..65535 (16-bit SOF0 fields)");
+    return JPEZY_OK;
 }
 #define HIP_TRY(expr)                                     \
     do {                                                  \
@@ -82,31 +77,20 @@ inline int drain_before_table_rewrite(hipStream_t s, const char* what, bool own_
 inline const int kQt[2][64] = { JPEZY_QT_LUMA_INIT, JPEZY_QT_CHROMA_INIT };
 inline const unsigned char kZzInv[64] = JPEZY_ZZ_INV_INIT;   // natural index -> zig-zag position
 
-struct DevBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    int reserve(size_t n)
-    {
-        if (n <= cap) return 0;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        hipError_t e = hipMalloc(&p, n);
-        if (e != hipSuccess) return hip_err(e, "hipMalloc");
-        cap = n;
-        return 0;
-    }
-    void release()
-    {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
+constexpr int kMaxFramesPerLaunch = 65535;   // the frame index is a grid dimension: larger batches go out as several launches
 
 // Chunks of the streaming host-buffer entry points: MCU-row bands of a frame that is large against the chunk size, otherwise
 // several whole frames.  Chunk k covers frames [f0, f0 + nf) and, in band mode (nf == 1), MCU rows [y0, y1) of frame f0.
-struct HostChunk { int f0, nf, y0, y1; };
+// Its planes are rows(H) pixel rows of W (whole frames: nf planes of W x H), plane_bytes each, plane_off into the caller's plane;
+// its coefficients are coef_bytes (B blocks per MCU), coef_off int16 elements into the caller's.
+struct HostChunk {
+    int f0, nf, y0, y1;
+    int rows(int H) const { return std::min(H - y0 * 16, (y1 - y0) * 16); }
+    size_t plane_bytes(int W, int H) const { return nf > 1 ? (size_t)W * H * nf : (size_t)rows(H) * W; }
+    size_t plane_off(int W, int H) const { return (size_t)f0 * W * H + (size_t)y0 * 16 * W; }
+    size_t coef_bytes(int W, int B) const { return (size_t)nf * (y1 - y0) * jpezy_mcu_cols(W) * B * 128; }
+    size_t coef_off(int W, int H, int B) const { return ((size_t)f0 * jpezy_mcu_rows(H) + (size_t)y0) * jpezy_mcu_cols(W) * B * 64; }
+};
 
 inline std::vector<HostChunk> plan_host_chunks(int W, int H, int n_frames, size_t bytes_per_px, size_t target)
 {
@@ -125,17 +109,25 @@ inline std::vector<HostChunk> plan_host_chunks(int W, int H, int n_frames, size_
     return out;
 }
 
+// a chunk's planes sit one behind the other in its slot, this many bytes apart (a multiple of 16: the aligned kernel stays usable)
+inline size_t plane_pitch(const std::vector<HostChunk>& chunks, int W, int H)
+{
+    size_t P = 0;
+    for (const HostChunk& k : chunks) P = std::max(P, k.plane_bytes(W, H));
+    return (P + 15) & ~(size_t)15;
+}
+
 }  // namespace jpezy_capi
 using namespace jpezy_capi;
 
 struct jpezy_ctx {
     int device = 0;
-    hipStream_t stream = nullptr;
-    DeviceTables* d_tab = nullptr;
-    unsigned long long* d_counter = nullptr;
-    double* d_dqscale = nullptr;   // [3][8][8]
-    int* d_dqt = nullptr;          // [3][64]
-    float* d_dqscale_f = nullptr;  // [8][8] luma constants in FP32 (decode tolerance mode)
+    Stream stream;
+    DevBuf d_tab;                  // DeviceTables
+    DevBuf d_counter;              // unsigned long long [COUNTER_SHARDS]
+    DevBuf d_dqscale;              // double [3][8][8]
+    DevBuf d_dqt;                  // int [3][64]
+    DevBuf d_dqscale_f;            // float [8][8] luma constants in FP32 (decode tolerance mode)
     int dec_tolerance = 0;         // 0 = bit-exact decode (default), 1 = luma in FP32, output within one of the reference per channel
     uint16_t dq_cache[3][64];
     int coef_limit = 0;            // 2^15 / largest quantiser: the generic kernels and the tolerance mode of the fused kernel
@@ -149,24 +141,20 @@ struct jpezy_ctx {
     int variant = JPEZY_DEFAULT_VARIANT;   // encode kernel: 0 = FP64 butterflies, 1 = FP32 first level (default), 2 = variant 1's arithmetic in persistent workgroups
     int n_cus = 0;                 // compute units of the device (grid of the persistent kernel)
     float dc_rq[2] = { 0, 0 }, dc_bias[2] = { 0, 0 };   // f32::dc_formula's constants; 0: the table-free DC does not reproduce the DC table (jpezy_ctx_create)
-#ifdef JPEZY_TRACE
-    unsigned long long* d_trace = nullptr;
-#endif
+    DevBuf d_trace;                // JPEZY_TRACE builds: 4 words per wave + 9 phase stamps (JPEZY_TRACE=3)
     DevBuf dump_t;                 // JPEZY_DUMP_T builds: level-1 t values of the last jpezy_fdct_quant_dev call
     DevBuf in[3], out, scratch;    // staging for the host-buffer entry points; scratch: samples of the generic decoder
     // GPU entropy coder (jpezy_entropy.hip): code tables + scratch
-    jpezy_dev::entropy::CodeTables* d_codes = nullptr;
+    DevBuf d_codes;                // jpezy_dev::entropy::CodeTables (ensure_code_tables)
     DevBuf e_tmp, e_small, e_U, e_cnt, e_out, e_coef;
     DevBuf e_tt, e_fft;            // totals per tile (256 coded blocks: bits) and per piece (256 chunks of 64 bytes: 0xFF bytes)
     DevBuf e_S, e_base, e_ft;      // one-pass coder: tile streams, frame-relative tile bit offsets, first tile per 16 KB of output
     DevBuf e_status;               // per-frame error flags of the device-resident entropy path: zero between calls (cleared by their consumer)
-    uint8_t* e_pinned = nullptr;   // pinned host staging of the stuffed streams
-    size_t e_pinned_cap = 0;
+    PinBuf e_pinned;               // pinned host staging of the stuffed streams
     DevBuf h_scan, h_U, h_cnt, h_off, h_state, h_setup, h_small, h_dc, h_dcbuf;   // GPU Huffman decoder (jpezy_huffdec.hip)
     std::vector<uint8_t> h_setup_host;  // the device tables h_setup holds (jpezy_read_jpeg_gpu uploads them only when they change)
     const void* h_setup_dev = nullptr;  // ... and the allocation they were uploaded to
-    uint8_t* h_fb_pin = nullptr;        // pinned buffer for the host decoder's coefficients (read_jpeg_host_to_device)
-    size_t h_fb_cap = 0;
+    PinBuf h_fb_pin;                    // pinned buffer for the host decoder's coefficients (read_jpeg_host_to_device)
     int h_last_passes = 0;         // synchronisation passes of the last jpezy_read_jpeg_gpu (0: the host decoder was used)
     size_t h_min_bytes = 32 << 10;    // scans shorter than this are decoded on the host: the GPU path has ~0.32 ms of fixed cost, the host decoder
                                       // takes ~10.5 us per KiB of scan (tools/measure/huffdec_threshold.py, profiles/r04_huffdec_threshold.txt: they cross at
@@ -174,10 +162,8 @@ struct jpezy_ctx {
     static constexpr int B_DEPTH = 3;   // slices of jpezy_decode_jpeg_batch whose planes may be on their way to the host while the next one is decoded
     DevBuf b_scan, b_U, b_cnt, b_rb, b_state, b_prop, b_meta, b_coef, b_planes[B_DEPTH];   // jpezy_decode_jpeg_batch, batch form of the Huffman decoder
     int b_last_fast = 0;           // files of the last jpezy_decode_jpeg_batch call that took the batch form (diagnostic hook)
-    uint8_t* b_pin = nullptr;      // pinned staging of the concatenated scans
-    size_t b_pin_cap = 0;
-    uint8_t* b_stage[B_DEPTH] = {};               // pinned staging of a slice's planes (one download per slice)
-    size_t b_stage_cap[B_DEPTH] = {};
+    PinBuf b_pin;                  // pinned staging of the concatenated scans
+    PinBuf b_stage[B_DEPTH];       // pinned staging of a slice's planes (one download per slice)
     DevBuf e_hdr;                  // JFIF header bytes of the device-resident variant (cached per W, H, comment)
     jpezy_host::HostPipe pipe;     // staging ring of the streaming host-buffer entry points (jpezy_hostpipe.h)
     size_t host_chunk_bytes = 4u << 20;   // bytes of input per chunk of that pipeline (jpezy_ctx_set_host_chunk_bytes)
@@ -185,6 +171,14 @@ struct jpezy_ctx {
     std::vector<jpezy_ctx*> workers;   // jpezy_decode_jpeg_batch: one child context (stream, buffers, tables) per file in flight
     uint8_t e_hdr_host[1024];
     size_t e_hdr_len = 0;
+
+    // the children first, then nothing of this context in flight; after that the members free themselves
+    ~jpezy_ctx()
+    {
+        for (jpezy_ctx* w : workers) delete w;
+        (void)hipSetDevice(device);
+        if (stream) (void)hipStreamSynchronize(stream);
+    }
 };
 
 // ---- helpers shared by the translation units (C linkage, hidden: not part of the ABI) ----

@@ -9,7 +9,7 @@
 // lane streams its shard through its ring in chunks of chunk_frames:
 //
 //   feeder threads   memcpy caller planes -> pinned slot, hipMemcpyAsync H2D on the upload stream, event
-//                    (planes the caller has pinned itself -- hipHostMalloc / hipHostRegister -- go to the DMA engine as they are)
+//                    (planes the caller has pinned itself -- allocated or registered page-locked -- go to the DMA engine as they are)
 //   lane thread      waits (stream-side) for the upload, enqueues FDCT + Huffman stage + the chunk's file sizes on the context's stream
 //   drainer threads  wait for the chunk's kernels, then move its results at their REAL length: .jpg files and coefficients through the
 //                    pinned slot into the caller's host memory, or -- consumer on the root GPU -- by hipMemcpyPeerAsync into devices[0]'s
@@ -41,19 +41,18 @@ struct Job {                            // one jpezy_multi_encode call
 };
 
 struct Slot {
-    uint8_t* pin_in = nullptr;          // [3][chunk][plane]
+    PinBuf pin_in;                      // [3][chunk][plane]
     DevBuf dev_in, dev_coef, dev_jpg, dev_sizes;
-    long long* pin_sizes = nullptr;
-    uint8_t* pin_coef = nullptr;
-    uint8_t* pin_jpg = nullptr;         // files of a chunk, packed at their real lengths (grows on demand)
-    size_t pin_jpg_cap = 0;
-    hipEvent_t ev_up = nullptr, ev_k0 = nullptr, ev_k = nullptr;
+    PinBuf pin_sizes;                   // long long [chunk]
+    PinBuf pin_coef;
+    PinBuf pin_jpg;                     // files of a chunk, packed at their real lengths (grows on demand)
+    Event ev_up, ev_k0, ev_k;
 };
 
 struct Lane {
     int index = 0, dev = 0;
-    jpezy_ctx* ctx = nullptr;
-    hipStream_t s_up = nullptr, s_down[MAX_DRAIN] = {};
+    std::unique_ptr<jpezy_ctx> ctx;
+    Stream s_up, s_down[MAX_DRAIN];
     Slot slot[RING];
     int ring = RING;                    // slots in use (the one-shot form of a small batch builds no more than its chunks need)
     bool peer_enabled = false;
@@ -62,6 +61,15 @@ struct Lane {
     int rc = JPEZY_OK;
     std::string err;
     jpezy_multi_lane_stats stats = {};
+
+    // nothing of the lane in flight before its members free themselves; leaves the lane's device current
+    ~Lane()
+    {
+        if (hipSetDevice(dev) != hipSuccess) (void)hipGetLastError();
+        if (ctx) (void)jpezy_ctx_sync(ctx.get());
+        if (s_up) (void)hipStreamSynchronize(s_up);
+        for (hipStream_t s : s_down) if (s) (void)hipStreamSynchronize(s);
+    }
 };
 
 }  // namespace
@@ -83,65 +91,24 @@ struct DeviceRestore {
     ~DeviceRestore() { if (dev >= 0) (void)hipSetDevice(dev); }
 };
 
-// joined on every way out of a scope; an exception on the way raises the lanes' failure flag first (see jpezy_hostpipe.h)
-struct Joiner {
-    std::vector<std::thread>& ts;
-    std::function<void()> on_unwind;
-    ~Joiner()
-    {
-        bool running = false;
-        for (auto& t : ts) running = running || t.joinable();
-        if (running && std::uncaught_exceptions() > 0 && on_unwind) on_unwind();
-        for (auto& t : ts) if (t.joinable()) t.join();
-    }
-};
-
-void release_lane(Lane& L)
-{
-    if (hipSetDevice(L.dev) != hipSuccess) (void)hipGetLastError();
-    if (L.ctx) (void)jpezy_ctx_sync(L.ctx);
-    if (L.s_up) { (void)hipStreamSynchronize(L.s_up); (void)hipStreamDestroy(L.s_up); }
-    for (hipStream_t& s : L.s_down) if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); s = nullptr; }
-    L.s_up = nullptr;
-    for (Slot& sl : L.slot) {
-        if (sl.pin_in) (void)hipHostFree(sl.pin_in);
-        if (sl.pin_sizes) (void)hipHostFree(sl.pin_sizes);
-        if (sl.pin_coef) (void)hipHostFree(sl.pin_coef);
-        if (sl.pin_jpg) (void)hipHostFree(sl.pin_jpg);
-        sl.pin_in = sl.pin_coef = sl.pin_jpg = nullptr;
-        sl.pin_sizes = nullptr;
-        sl.pin_jpg_cap = 0;
-        for (DevBuf* b : { &sl.dev_in, &sl.dev_coef, &sl.dev_jpg, &sl.dev_sizes }) b->release();
-        for (hipEvent_t* e : { &sl.ev_up, &sl.ev_k0, &sl.ev_k }) if (*e) { (void)hipEventDestroy(*e); *e = nullptr; }
-    }
-    if (L.ctx) jpezy_ctx_destroy(L.ctx);
-    L.ctx = nullptr;
-}
-
-#define L_TRY(expr)                                                                  \
-    do {                                                                             \
-        hipError_t e__ = (expr);                                                     \
-        if (e__ != hipSuccess) return hip_err(e__, #expr);                           \
-    } while (0)
-
 // what every call needs whatever it asks for: context, streams, events, the input ring, the coefficient buffers
 int create_lane(const jpezy_multi& M, Lane& L)
 {
-    L_TRY(hipSetDevice(L.dev));
-    L.ctx = jpezy_ctx_create(L.dev);
+    HIP_TRY(hipSetDevice(L.dev));
+    L.ctx.reset(jpezy_ctx_create(L.dev));
     if (!L.ctx) return JPEZY_E_HIP;                     // (message set by jpezy_ctx_create)
-    L_TRY(hipStreamCreateWithFlags(&L.s_up, hipStreamNonBlocking));
-    for (hipStream_t& s : L.s_down) L_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    HIP_TRY(L.s_up.create());
+    for (Stream& s : L.s_down) HIP_TRY(s.create());
     const size_t in_bytes = 3 * M.plane * (size_t)M.chunk;
     for (int k = 0; k < L.ring; ++k) {
         Slot& sl = L.slot[k];
-        L_TRY(hipEventCreateWithFlags(&sl.ev_up, hipEventDisableTiming));
-        L_TRY(hipEventCreate(&sl.ev_k0));               // (timed: the lane's kernel time is the sum of its chunks' spans)
-        L_TRY(hipEventCreate(&sl.ev_k));
+        HIP_TRY(sl.ev_up.create());
+        HIP_TRY(sl.ev_k0.create(hipEventDefault));      // (timed: the lane's kernel time is the sum of its chunks' spans)
+        HIP_TRY(sl.ev_k.create(hipEventDefault));
         if (int rc = sl.dev_in.reserve(in_bytes)) return rc;
         if (int rc = sl.dev_coef.reserve(M.cpf * sizeof(int16_t) * (size_t)M.chunk)) return rc;
         if (int rc = sl.dev_sizes.reserve(sizeof(long long) * (size_t)M.chunk)) return rc;
-        L_TRY(hipHostMalloc((void**)&sl.pin_sizes, sizeof(long long) * (size_t)M.chunk, hipHostMallocDefault));
+        if (int rc = sl.pin_sizes.reserve(sizeof(long long) * (size_t)M.chunk)) return rc;
     }
     return JPEZY_OK;
 }
@@ -212,12 +179,11 @@ void run_lane(const jpezy_multi& M, Lane& L, const Job& J)
         for (int k = 0; k < L.ring; ++k) {
             Slot& sl = L.slot[k];
             if (rc || e != hipSuccess) break;
-            if (!J.src_pinned && !sl.pin_in) e = hipHostMalloc((void**)&sl.pin_in, 3 * M.plane * (size_t)chunk, hipHostMallocDefault);
+            if (!J.src_pinned) e = sl.pin_in.try_reserve(3 * M.plane * (size_t)chunk);
             if (e == hipSuccess && want_jpg && !in_place) rc = sl.dev_jpg.reserve(dstride * (size_t)chunk);
-            if (!rc && e == hipSuccess && want_coef && !to_root && !sl.pin_coef)
-                e = hipHostMalloc((void**)&sl.pin_coef, M.cpf * sizeof(int16_t) * (size_t)chunk, hipHostMallocDefault);
+            if (!rc && e == hipSuccess && want_coef && !to_root) e = sl.pin_coef.try_reserve(M.cpf * sizeof(int16_t) * (size_t)chunk);
         }
-        if (e != hipSuccess) { L.rc = JPEZY_E_HIP; L.err = std::string("hipHostMalloc (staging ring): ") + hipGetErrorString(e); return; }
+        if (e != hipSuccess) { L.rc = JPEZY_E_HIP; L.err = std::string("pinned allocation (staging ring): ") + hipGetErrorString(e); return; }
         if (rc) { L.rc = rc; L.err = jpezy_hip_last_error(); return; }
     }
 
@@ -240,11 +206,11 @@ void run_lane(const jpezy_multi& M, Lane& L, const Job& J)
             const size_t seg = M.plane * (size_t)n, qs = M.plane * (size_t)chunk;
             uint8_t* d_in = (uint8_t*)sl.dev_in.p;
             if (!J.src_pinned)
-                for (int q = 0; q < 3; ++q) std::memcpy(sl.pin_in + (size_t)q * qs, J.src[q] + (size_t)f * M.plane, seg);
+                for (int q = 0; q < 3; ++q) std::memcpy(sl.pin_in.p + (size_t)q * qs, J.src[q] + (size_t)f * M.plane, seg);
             {
                 std::lock_guard<std::mutex> lk(R.up_mu);                // one stream, several feeders: keep copies + event together
                 for (int q = 0; q < 3; ++q) {
-                    const uint8_t* from = J.src_pinned ? J.src[q] + (size_t)f * M.plane : sl.pin_in + (size_t)q * qs;
+                    const uint8_t* from = J.src_pinned ? J.src[q] + (size_t)f * M.plane : sl.pin_in.p + (size_t)q * qs;
                     R_TRY(hipMemcpyAsync(d_in + (size_t)q * qs, from, seg, hipMemcpyHostToDevice, L.s_up));
                 }
                 R_TRY(hipEventRecord(sl.ev_up, L.s_up));
@@ -273,7 +239,7 @@ void run_lane(const jpezy_multi& M, Lane& L, const Job& J)
                 const size_t bytes = M.cpf * sizeof(int16_t) * (size_t)n;
                 int16_t* dst = J.out.coeffs + (size_t)f * M.cpf;
                 if (to_root) R_TRY(hipMemcpyPeerAsync(dst, root_dev, sl.dev_coef.p, L.dev, bytes, sd));
-                else R_TRY(hipMemcpyAsync(sl.pin_coef, sl.dev_coef.p, bytes, hipMemcpyDeviceToHost, sd));
+                else R_TRY(hipMemcpyAsync(sl.pin_coef.p, sl.dev_coef.p, bytes, hipMemcpyDeviceToHost, sd));
                 moved += bytes;
             }
             std::vector<size_t> off;
@@ -281,37 +247,31 @@ void run_lane(const jpezy_multi& M, Lane& L, const Job& J)
                 size_t total = 0;
                 off.assign((size_t)n, 0);
                 for (int i = 0; i < n; ++i) {
-                    long long len = sl.pin_sizes[i];
+                    long long len = sl.pin_sizes.as<long long>()[i];
                     if (len > 0 && (size_t)len > J.out.jpg_stride) len = JPEZY_E_NOSPACE;
                     J.out.jpg_sizes[f + i] = len;                       // a refused frame keeps its negative status
                     off[(size_t)i] = total;
                     if (len > 0) total += ((size_t)len + 63) & ~(size_t)63;
                 }
-                if (!in_place && !to_root && total > sl.pin_jpg_cap) {  // (first chunks of a handle, or content that codes longer than any before)
-                    if (sl.pin_jpg) (void)hipHostFree(sl.pin_jpg);
-                    sl.pin_jpg = nullptr;
-                    sl.pin_jpg_cap = 0;
-                    const size_t cap = std::max(total + total / 4, M.plane * (size_t)chunk / 2);
-                    R_TRY(hipHostMalloc((void**)&sl.pin_jpg, cap, hipHostMallocDefault));
-                    sl.pin_jpg_cap = cap;
-                }
+                if (!in_place && !to_root)          // (grows with the first chunks of a handle, or content that codes longer than any before)
+                    R_TRY(sl.pin_jpg.try_reserve(total, std::max(total + total / 4, M.plane * (size_t)chunk / 2)));
                 if (!in_place)
                     for (int i = 0; i < n; ++i) {
                         const long long len = J.out.jpg_sizes[f + i];
                         if (len <= 0) continue;
                         const uint8_t* src = (const uint8_t*)sl.dev_jpg.p + (size_t)i * dstride;
                         if (to_root) R_TRY(hipMemcpyPeerAsync(J.out.jpg + (size_t)(f + i) * J.out.jpg_stride, root_dev, src, L.dev, (size_t)len, sd));
-                        else R_TRY(hipMemcpyAsync(sl.pin_jpg + off[(size_t)i], src, (size_t)len, hipMemcpyDeviceToHost, sd));
+                        else R_TRY(hipMemcpyAsync(sl.pin_jpg.p + off[(size_t)i], src, (size_t)len, hipMemcpyDeviceToHost, sd));
                         moved += (size_t)len;
                     }
             }
             if (!in_place) R_TRY(hipStreamSynchronize(sd));
             if (!to_root) {
-                if (want_coef) std::memcpy(J.out.coeffs + (size_t)f * M.cpf, sl.pin_coef, M.cpf * sizeof(int16_t) * (size_t)n);
+                if (want_coef) std::memcpy(J.out.coeffs + (size_t)f * M.cpf, sl.pin_coef.p, M.cpf * sizeof(int16_t) * (size_t)n);
                 if (want_jpg)
                     for (int i = 0; i < n; ++i) {
                         const long long len = J.out.jpg_sizes[f + i];
-                        if (len > 0) std::memcpy(J.out.jpg + (size_t)(f + i) * J.out.jpg_stride, sl.pin_jpg + off[(size_t)i], (size_t)len);
+                        if (len > 0) std::memcpy(J.out.jpg + (size_t)(f + i) * J.out.jpg_stride, sl.pin_jpg.p + off[(size_t)i], (size_t)len);
                     }
             }
             bytes_down += moved;
@@ -319,17 +279,16 @@ void run_lane(const jpezy_multi& M, Lane& L, const Job& J)
         }
     };
 
-    std::vector<std::thread> threads;
     {
-        Joiner joiner{ threads, [&] { R.fail(JPEZY_E_HIP, "unexpected exception in the lane thread"); } };
-        threads.reserve((size_t)(n_feed + n_drain));
+        Joiner threads{ 0, [&] { R.fail(JPEZY_E_HIP, "unexpected exception in the lane thread"); } };
+        threads.ts.reserve((size_t)(n_feed + n_drain));
         try {
-            for (int k = 0; k < std::min(n_feed, n_chunks); ++k) threads.emplace_back(feeder, k);
-            for (int k = 0; k < std::min(n_drain, n_chunks); ++k) threads.emplace_back(drainer, k);
+            for (int k = 0; k < std::min(n_feed, n_chunks); ++k) threads.start(feeder, k);
+            for (int k = 0; k < std::min(n_drain, n_chunks); ++k) threads.start(drainer, k);
         } catch (const std::exception&) {
             R.fail(JPEZY_E_HIP, "starting a copy thread failed");
         }
-        hipStream_t sc = (hipStream_t)jpezy_ctx_stream(L.ctx);
+        hipStream_t sc = L.ctx->stream;
         for (int c = 0; c < n_chunks && !R.failed.load(); ++c) {
             Slot& sl = L.slot[c % ring];
             if (!R.wait(c, 1)) break;
@@ -342,13 +301,13 @@ void run_lane(const jpezy_multi& M, Lane& L, const Job& J)
             hipError_t e = hipStreamWaitEvent(sc, sl.ev_up, 0);
             if (e == hipSuccess) e = hipEventRecord(sl.ev_k0, sc);
             if (e != hipSuccess) { R.hip(e, "hipStreamWaitEvent / hipEventRecord"); break; }
-            int rc = jpezy_fdct_quant_dev(L.ctx, d_in, d_in + qs, d_in + 2 * qs, M.plane, M.W, M.H, M.gray, n, d_coef, sc);
+            int rc = jpezy_fdct_quant_dev(L.ctx.get(), d_in, d_in + qs, d_in + 2 * qs, M.plane, M.W, M.H, M.gray, n, d_coef, sc);
             if (rc == JPEZY_OK && want_jpg) {
                 uint8_t* d_jpg = in_place ? J.out.jpg + (size_t)f * J.out.jpg_stride : (uint8_t*)sl.dev_jpg.p;
-                rc = jpezy_write_jpeg_gpu_dev(L.ctx, d_coef, M.W, M.H, M.gray, n, J.comment, d_jpg, in_place ? J.out.jpg_stride : dstride,
+                rc = jpezy_write_jpeg_gpu_dev(L.ctx.get(), d_coef, M.W, M.H, M.gray, n, J.comment, d_jpg, in_place ? J.out.jpg_stride : dstride,
                                               (long long*)sl.dev_sizes.p, sc);
                 if (rc == JPEZY_OK) {
-                    e = hipMemcpyAsync(sl.pin_sizes, sl.dev_sizes.p, sizeof(long long) * (size_t)n, hipMemcpyDeviceToHost, sc);
+                    e = hipMemcpyAsync(sl.pin_sizes.p, sl.dev_sizes.p, sizeof(long long) * (size_t)n, hipMemcpyDeviceToHost, sc);
                     if (e != hipSuccess) { R.hip(e, "hipMemcpyAsync (file sizes)"); break; }
                 }
             }
@@ -358,7 +317,7 @@ void run_lane(const jpezy_multi& M, Lane& L, const Job& J)
             R.set(c, 2);
         }
     }   // threads joined
-    (void)hipStreamSynchronize((hipStream_t)jpezy_ctx_stream(L.ctx));
+    (void)hipStreamSynchronize(L.ctx->stream);
     if (R.failed.load()) {
         (void)hipStreamSynchronize(L.s_up);
         for (hipStream_t s : L.s_down) (void)hipStreamSynchronize(s);
@@ -452,9 +411,9 @@ jpezy_multi* multi_create(const int* devices, int n_dev, int W, int H, int gray,
     for (auto& L : M->lanes) {
         const int rc = create_lane(*M, *L);
         if (rc != JPEZY_OK) {
-            const std::string why = jpezy_hip_last_error();
-            for (auto& K : M->lanes) release_lane(*K);
-            set_err(rc, "multi_create, device " + std::to_string(L->dev) + " (lane " + std::to_string(L->index) + "): " + why);
+            const std::string why = "multi_create, device " + std::to_string(L->dev) + " (lane " + std::to_string(L->index) + "): " + jpezy_hip_last_error();
+            M.reset();                                  // (the lanes release themselves)
+            set_err(rc, why);
             return nullptr;
         }
     }
@@ -480,7 +439,7 @@ void jpezy_shard_range(long n_units, int n_shards, int k, long* first, long* cou
 jpezy_multi* jpezy_multi_create(const int* devices, int n_dev, int W, int H, int gray, int chunk_frames)
 try {
     if (check_devices(devices, n_dev, "multi_create")) return nullptr;
-    if (W <= 0 || H <= 0 || W > 65535 || H > 65535) { set_err(JPEZY_E_BADARG, "width/height must be in 1..65535 (16-bit SOF0 fields)"); return nullptr; }
+    if (check_wh(W, H)) return nullptr;
     if (check_device_range(devices, n_dev, "multi_create")) return nullptr;
     DeviceRestore restore;
     return multi_create(devices, n_dev, W, H, gray, chunk_frames, 0);
@@ -493,7 +452,6 @@ void jpezy_multi_destroy(jpezy_multi* m)
 {
     if (!m) return;
     DeviceRestore restore;
-    for (auto& L : m->lanes) release_lane(*L);
     delete m;
 }
 
@@ -534,13 +492,12 @@ try {
         L.stats.device = L.dev;
     }
     {
-        std::vector<std::thread> pool;
-        Joiner joiner{ pool, nullptr };             // (lanes fail on their own; an exception here only has to wait for them)
+        Joiner pool;                                // (lanes fail on their own; an exception here only has to wait for them)
         try {
             for (int i = 1; i < n_dev; ++i)
-                if (m->lanes[(size_t)i]->nf > 0) pool.emplace_back(lane_main, std::cref(*m), std::ref(*m->lanes[(size_t)i]), std::cref(J));
+                if (m->lanes[(size_t)i]->nf > 0) pool.start(lane_main, std::cref(*m), std::ref(*m->lanes[(size_t)i]), std::cref(J));
         } catch (const std::exception&) {           // the lanes that did start run to their end; the call fails
-            for (auto& t : pool) if (t.joinable()) t.join();
+            pool.join();
             return set_err(JPEZY_E_HIP, "multi_encode: starting a lane thread failed");
         }
         if (m->lanes[0]->nf > 0) lane_main(*m, *m->lanes[0], J);    // the calling thread drives the root device
@@ -567,7 +524,7 @@ int jpezy_encode_batch_multi(const int* devices, int n_dev, const uint8_t* r, co
 try {
     if (int rc = check_devices(devices, n_dev, "encode_batch_multi")) return rc;
     if (!r || !g || !b || !out) return set_err(JPEZY_E_BADARG, "encode_batch_multi: null pointer");
-    if (W <= 0 || H <= 0 || W > 65535 || H > 65535) return set_err(JPEZY_E_BADARG, "width/height must be in 1..65535 (16-bit SOF0 fields)");
+    if (int rc = check_wh(W, H)) return rc;
     if (n_frames <= 0) return set_err(JPEZY_E_BADARG, "n_frames must be positive");
     if (int rc = check_out(out, "encode_batch_multi")) return rc;
     if (int rc = check_device_range(devices, n_dev, "encode_batch_multi")) return rc;

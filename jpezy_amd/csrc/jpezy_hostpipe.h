@@ -24,14 +24,20 @@
 #include <atomic>
 #include <condition_variable>
 #include <cstring>
-#include <exception>
 #include <functional>
 #include <mutex>
 #include <string>
-#include <thread>
 #include <vector>
 
+#include "jpezy_owners.h"
+
 namespace jpezy_host {
+
+using jpezy_capi::DevBuf;
+using jpezy_capi::PinBuf;
+using jpezy_capi::Stream;
+using jpezy_capi::Event;
+using jpezy_capi::Joiner;
 
 struct Segment {
     void* host;          // caller memory (source for uploads, destination for downloads)
@@ -46,28 +52,6 @@ struct ChunkPlan {
 class HostPipe {
 public:
     static constexpr int RING = 4;
-
-    ~HostPipe() { release(); }
-
-    void release()
-    {
-        for (int k = 0; k < RING; ++k) {
-            if (pin_in_[k]) (void)hipHostFree(pin_in_[k]);
-            if (pin_out_[k]) (void)hipHostFree(pin_out_[k]);
-            if (dev_in_[k]) (void)hipFree(dev_in_[k]);
-            if (dev_out_[k]) (void)hipFree(dev_out_[k]);
-            pin_in_[k] = pin_out_[k] = nullptr;
-            dev_in_[k] = dev_out_[k] = nullptr;
-            if (ev_up_[k]) (void)hipEventDestroy(ev_up_[k]);
-            if (ev_k_[k]) (void)hipEventDestroy(ev_k_[k]);
-            if (ev_down_[k]) (void)hipEventDestroy(ev_down_[k]);
-            ev_up_[k] = ev_k_[k] = ev_down_[k] = nullptr;
-        }
-        if (s_up_) (void)hipStreamDestroy(s_up_);
-        if (s_down_) (void)hipStreamDestroy(s_down_);
-        s_up_ = s_down_ = nullptr;
-        cap_in_ = cap_out_ = 0;
-    }
 
     // kernel(c, d_in, d_out, stream): enqueue chunk c's launches on `stream` (inputs at d_in + Segment::slot_off, outputs likewise);
     // returns a hipError_t.  plan(c): the chunk's segments.  Returns hipSuccess or the first error (message in *err).
@@ -84,20 +68,21 @@ public:
         if (n_chunks == 1) {
             // a call that fits one chunk (small frames): nothing to overlap -- the plain staged copy on the calling thread,
             // without six thread starts and their event round trips
-            for (const Segment& sg : plans[0].in) std::memcpy(pin_in_[0] + sg.slot_off, sg.host, sg.bytes);
+            uint8_t *d_in = dev_in_[0].as<uint8_t>(), *d_out = dev_out_[0].as<uint8_t>();
+            for (const Segment& sg : plans[0].in) std::memcpy(pin_in_[0].p + sg.slot_off, sg.host, sg.bytes);
             for (const Segment& sg : plans[0].in) {
-                e = hipMemcpyAsync(dev_in_[0] + sg.slot_off, pin_in_[0] + sg.slot_off, sg.bytes, hipMemcpyHostToDevice, compute);
+                e = hipMemcpyAsync(d_in + sg.slot_off, pin_in_[0].p + sg.slot_off, sg.bytes, hipMemcpyHostToDevice, compute);
                 if (e != hipSuccess) { if (err) *err = "host pipeline: hipMemcpyAsync (upload) failed"; return e; }
             }
-            e = kernel(0, dev_in_[0], dev_out_[0], compute);
+            e = kernel(0, d_in, d_out, compute);
             for (const Segment& sg : plans[0].out) {
                 if (e != hipSuccess) break;
-                e = hipMemcpyAsync(pin_out_[0] + sg.slot_off, dev_out_[0] + sg.slot_off, sg.bytes, hipMemcpyDeviceToHost, compute);
+                e = hipMemcpyAsync(pin_out_[0].p + sg.slot_off, d_out + sg.slot_off, sg.bytes, hipMemcpyDeviceToHost, compute);
             }
             const hipError_t es = hipStreamSynchronize(compute);
             if (e == hipSuccess) e = es;
             if (e != hipSuccess) { if (err) *err = std::string("host pipeline: ") + hipGetErrorString(e); return e; }
-            for (const Segment& sg : plans[0].out) std::memcpy(sg.host, pin_out_[0] + sg.slot_off, sg.bytes);
+            for (const Segment& sg : plans[0].out) std::memcpy(sg.host, pin_out_[0].p + sg.slot_off, sg.bytes);
             return hipSuccess;
         }
 
@@ -131,11 +116,11 @@ public:
                     hipError_t e2 = hipEventSynchronize(ev_k_[slot]);
                     if (e2 != hipSuccess) { fail(e2, "hipEventSynchronize"); return; }
                 }
-                for (const Segment& sg : plans[(size_t)c].in) std::memcpy(pin_in_[slot] + sg.slot_off, sg.host, sg.bytes);
+                for (const Segment& sg : plans[(size_t)c].in) std::memcpy(pin_in_[slot].p + sg.slot_off, sg.host, sg.bytes);
                 {
                     std::lock_guard<std::mutex> lk(up_mu_);               // one stream, several feeders: keep copy + event together
                     for (const Segment& sg : plans[(size_t)c].in) {
-                        hipError_t e2 = hipMemcpyAsync(dev_in_[slot] + sg.slot_off, pin_in_[slot] + sg.slot_off, sg.bytes, hipMemcpyHostToDevice, s_up_);
+                        hipError_t e2 = hipMemcpyAsync(dev_in_[slot].as<uint8_t>() + sg.slot_off, pin_in_[slot].p + sg.slot_off, sg.bytes, hipMemcpyHostToDevice, s_up_);
                         if (e2 != hipSuccess) { fail(e2, "hipMemcpyAsync (upload)"); return; }
                     }
                     hipError_t e2 = hipEventRecord(ev_up_[slot], s_up_);
@@ -151,34 +136,22 @@ public:
                 if (!wait_state(c, 2)) return;
                 hipError_t e2 = hipEventSynchronize(ev_down_[slot]);
                 if (e2 != hipSuccess) { fail(e2, "hipEventSynchronize"); return; }
-                for (const Segment& sg : plans[(size_t)c].out) std::memcpy(sg.host, pin_out_[slot] + sg.slot_off, sg.bytes);
+                for (const Segment& sg : plans[(size_t)c].out) std::memcpy(sg.host, pin_out_[slot].p + sg.slot_off, sg.bytes);
                 set_state(c, 3);
             }
         };
         // Joined on every way out of this scope: an exception below (a thread that cannot be started, an allocation, a
         // throwing kernel callback) first raises `failed` -- the workers' waits all watch it -- and then joins them, instead
         // of destroying joinable threads (std::terminate) before the C-ABI's catch can turn it into an error code.
-        std::vector<std::thread> threads;
-        struct Joiner {
-            std::vector<std::thread>& ts;
-            std::atomic<int>& failed;
-            std::condition_variable& cv;
-            ~Joiner()
-            {
-                bool running = false;
-                for (auto& t : ts) running = running || t.joinable();
-                if (running && std::uncaught_exceptions() > 0) {
-                    int expected = 0;
-                    failed.compare_exchange_strong(expected, (int)hipErrorUnknown);
-                    cv.notify_all();
-                }
-                for (auto& t : ts) if (t.joinable()) t.join();
-            }
-        } joiner{ threads, failed, cv };
-        threads.reserve((size_t)(n_feed + n_drain));
+        Joiner threads{ 0, [&] {
+            int expected = 0;
+            failed.compare_exchange_strong(expected, (int)hipErrorUnknown);
+            cv.notify_all();
+        } };
+        threads.ts.reserve((size_t)(n_feed + n_drain));
         try {
-            for (int k = 0; k < n_feed; ++k) threads.emplace_back(feeder, k);
-            for (int k = 0; k < n_drain; ++k) threads.emplace_back(drainer, k);
+            for (int k = 0; k < n_feed; ++k) threads.start(feeder, k);
+            for (int k = 0; k < n_drain; ++k) threads.start(drainer, k);
         } catch (const std::exception&) {
             fail(hipErrorOutOfMemory, "starting a copy thread");
         }
@@ -188,18 +161,18 @@ public:
             if (!wait_state(c, 1)) break;
             if (c >= RING && !wait_state(c - RING, 3)) break;             // the slot's output buffers have been delivered
             hipError_t e2 = hipStreamWaitEvent(compute, ev_up_[slot], 0);
-            if (e2 == hipSuccess) e2 = kernel(c, dev_in_[slot], dev_out_[slot], compute);
+            if (e2 == hipSuccess) e2 = kernel(c, dev_in_[slot].as<uint8_t>(), dev_out_[slot].as<uint8_t>(), compute);
             if (e2 == hipSuccess) e2 = hipEventRecord(ev_k_[slot], compute);
             if (e2 == hipSuccess) e2 = hipStreamWaitEvent(s_down_, ev_k_[slot], 0);
             for (const Segment& sg : plans[(size_t)c].out) {
                 if (e2 != hipSuccess) break;
-                e2 = hipMemcpyAsync(pin_out_[slot] + sg.slot_off, dev_out_[slot] + sg.slot_off, sg.bytes, hipMemcpyDeviceToHost, s_down_);
+                e2 = hipMemcpyAsync(pin_out_[slot].p + sg.slot_off, dev_out_[slot].as<uint8_t>() + sg.slot_off, sg.bytes, hipMemcpyDeviceToHost, s_down_);
             }
             if (e2 == hipSuccess) e2 = hipEventRecord(ev_down_[slot], s_down_);
             if (e2 != hipSuccess) { fail(e2, "launch / download"); break; }
             set_state(c, 2);
         }
-        for (auto& t : threads) t.join();
+        threads.join();
         if (failed.load()) {
             (void)hipStreamSynchronize(compute);
             (void)hipStreamSynchronize(s_up_);
@@ -210,53 +183,35 @@ public:
     }
 
 private:
-    hipError_t reserve(size_t in, size_t out)
+    // the slots of one direction are regrown together, to one capacity (the last slot is allocated last: it tells whether all were)
+    static hipError_t regrow(PinBuf (&pin)[RING], DevBuf (&dev)[RING], size_t n)
     {
+        if (n <= pin[RING - 1].cap && n <= dev[RING - 1].cap) return hipSuccess;
+        for (int k = 0; k < RING; ++k) { pin[k].release(); dev[k].release(); }
         hipError_t e = hipSuccess;
-        if (!s_up_) e = hipStreamCreateWithFlags(&s_up_, hipStreamNonBlocking);
-        if (e == hipSuccess && !s_down_) e = hipStreamCreateWithFlags(&s_down_, hipStreamNonBlocking);
-        for (int k = 0; k < RING && e == hipSuccess; ++k) {
-            if (!ev_up_[k]) e = hipEventCreateWithFlags(&ev_up_[k], hipEventDisableTiming);
-            if (e == hipSuccess && !ev_k_[k]) e = hipEventCreateWithFlags(&ev_k_[k], hipEventDisableTiming);
-            if (e == hipSuccess && !ev_down_[k]) e = hipEventCreateWithFlags(&ev_down_[k], hipEventDisableTiming);
-        }
-        if (e != hipSuccess) return e;
-        if (in > cap_in_) {
-            for (int k = 0; k < RING; ++k) {
-                if (pin_in_[k]) (void)hipHostFree(pin_in_[k]);
-                if (dev_in_[k]) (void)hipFree(dev_in_[k]);
-                pin_in_[k] = nullptr; dev_in_[k] = nullptr;
-            }
-            cap_in_ = 0;
-            for (int k = 0; k < RING; ++k) {
-                if ((e = hipHostMalloc((void**)&pin_in_[k], in, hipHostMallocDefault)) != hipSuccess) return e;
-                if ((e = hipMalloc((void**)&dev_in_[k], in)) != hipSuccess) return e;
-            }
-            cap_in_ = in;
-        }
-        if (out > cap_out_) {
-            for (int k = 0; k < RING; ++k) {
-                if (pin_out_[k]) (void)hipHostFree(pin_out_[k]);
-                if (dev_out_[k]) (void)hipFree(dev_out_[k]);
-                pin_out_[k] = nullptr; dev_out_[k] = nullptr;
-            }
-            cap_out_ = 0;
-            for (int k = 0; k < RING; ++k) {
-                if ((e = hipHostMalloc((void**)&pin_out_[k], out, hipHostMallocDefault)) != hipSuccess) return e;
-                if ((e = hipMalloc((void**)&dev_out_[k], out)) != hipSuccess) return e;
-            }
-            cap_out_ = out;
-        }
-        return hipSuccess;
+        for (int k = 0; k < RING && e == hipSuccess; ++k)
+            if ((e = pin[k].try_reserve(n)) == hipSuccess) e = dev[k].try_reserve(n);
+        return e;
     }
 
-    uint8_t* pin_in_[RING] = {};
-    uint8_t* pin_out_[RING] = {};
-    uint8_t* dev_in_[RING] = {};
-    uint8_t* dev_out_[RING] = {};
-    hipEvent_t ev_up_[RING] = {}, ev_k_[RING] = {}, ev_down_[RING] = {};
-    hipStream_t s_up_ = nullptr, s_down_ = nullptr;
-    size_t cap_in_ = 0, cap_out_ = 0;
+    hipError_t reserve(size_t in, size_t out)
+    {
+        hipError_t e = s_up_.create();
+        if (e == hipSuccess) e = s_down_.create();
+        for (int k = 0; k < RING && e == hipSuccess; ++k) {
+            e = ev_up_[k].create();
+            if (e == hipSuccess) e = ev_k_[k].create();
+            if (e == hipSuccess) e = ev_down_[k].create();
+        }
+        if (e == hipSuccess) e = regrow(pin_in_, dev_in_, in);
+        if (e == hipSuccess) e = regrow(pin_out_, dev_out_, out);
+        return e;
+    }
+
+    PinBuf pin_in_[RING], pin_out_[RING];
+    DevBuf dev_in_[RING], dev_out_[RING];
+    Event ev_up_[RING], ev_k_[RING], ev_down_[RING];
+    Stream s_up_, s_down_;
     std::mutex up_mu_;
 };
 

@@ -30,6 +30,8 @@
  * the chroma blocks (jpezy_encoder.hpp:61-64) so they are not materialised; inside a block the 64
  * quantised coefficients are in ZIG-ZAG order: coeffs[n] = q[ZZ[n]] (jpezy.hpp:36-45).
  * Pixel planes are planar 8-bit r, g, b with row stride W, W*H bytes each (jpezy_encoder.hpp:105,266).
+ * Packed pixels (the *_packed entry points at the end of this header): one interleaved buffer, 3 or 4 bytes per pixel, rows
+ * row_stride bytes apart.
  */
 #ifndef JPEZY_HIP_H
 #define JPEZY_HIP_H
@@ -386,6 +388,51 @@ int jpezy_ctx_last_batch_fast_count(jpezy_ctx* ctx);
  * sends every scan to the GPU decoder (tests). */
 void jpezy_ctx_set_huffdec_min_bytes(jpezy_ctx* ctx, size_t n);
 
+/*
+ * PACKED (INTERLEAVED) PIXELS.  The reference keeps three planes (jpezy_encoder.hpp:24-28; its CLI builds an interleaved image and
+ * splits it, encode_io.hpp:151); a caller with a decoded camera frame, an H x W x C array or a framebuffer has interleaved pixels.
+ * These entry points take and return them as they are: only the first step (pixel load) and the last step (pixel store) of the kernels
+ * differ, the arithmetic, the guard bands, the exact paths and the Huffman stages are the planar ones', and every coefficient and every
+ * pixel byte equals what the planar sibling gives for the same pixels.
+ *
+ *   Addressing    pixel (x, y) of frame f starts at pix + f*frame_stride + y*row_stride + x*bytes, bytes = jpezy_pixel_bytes(format)
+ *   row_stride    >= W*bytes; 0 = tight (W*bytes)
+ *   frame_stride  >= (H-1)*row_stride + W*bytes; 0 = H*row_stride
+ *   Size limit    row_stride * H must fit in 32 bits (JPEZY_E_BADARG otherwise): the kernels keep 32-bit row offsets as the planar ones do
+ *   Alignment     none required.  W % 16 == 0 with base, row_stride and frame_stride multiples of 16 takes the 16-byte load / store form
+ *                 (channels separated / merged in registers); everything else moves single bytes
+ *   Bytes touched only bytes [0, W*bytes) of each row are read or written: never row padding, never anything behind the last row's W*bytes
+ *                 (jpezy_encode_jpeg_packed alone may READ the padding between the rows of a band when it uploads it)
+ *   32-bit formats  encode ignores the fourth byte, decode writes 0xFF into it
+ *   gray          the planar meaning: encode computes luma from the three channels and emits the 4-block layout, decode writes r = g = b = clamp(Y)
+ *   Context settings  jpezy_ctx_set_force_exact, _set_variant, _set_decode_tolerance and _set_host_chunk_bytes act as on the planar entries.
+ *                 Encode variant 0 (FP64) reads packed pixels through its byte loop; the laboratory's variants 2 and 3 hand packed input to
+ *                 variant 1's launch, as they do every frame they do not cover
+ *   Batches       more than 65535 frames go out as several launches, as in jpezy_fdct_quant_dev
+ *
+ * NOT provided in packed form: the host-buffer jpezy_fdct_quant / jpezy_dequant_idct, jpezy_decode_jpeg_batch, the multi-GPU handle, the
+ * jpezy::encoder / decoder class surface and the CLIs (they mirror the reference's planar constructors and P3 files), formats with alpha
+ * first, 16-bit channels.
+ */
+enum jpezy_pixel_format { JPEZY_PIX_RGB24 = 0, JPEZY_PIX_BGR24 = 1, JPEZY_PIX_RGBA32 = 2, JPEZY_PIX_BGRA32 = 3 };
+int jpezy_pixel_bytes(int format);          /* 3, 3, 4, 4; JPEZY_E_BADARG otherwise (pure host function) */
+/* jpezy_fdct_quant_dev for packed pixels in device memory; replaces the same reference lines (encoder/jpezy_encoder.hpp:90-172, 195, 212,
+ * 244-256).  Asynchronous on `stream`. */
+int jpezy_fdct_quant_packed_dev(jpezy_ctx* ctx, const uint8_t* d_pix, int format, size_t row_stride, size_t frame_stride, int W, int H,
+                                int gray, int n_frames, int16_t* d_coeffs, void* stream);
+/* jpezy_dequant_idct_dev writing packed pixels (decoder/jpezy_decoder.hpp:519-524, 531-578, 645-676); jpezy's own 2x2,1x1,1x1 layout.
+ * Asynchronous on `stream`; the table rules of jpezy_dequant_idct_dev apply. */
+int jpezy_dequant_idct_packed_dev(jpezy_ctx* ctx, const int16_t* d_coeffs, const uint16_t qt[4][64], const uint8_t comp_tq[3], int format,
+                                  size_t row_stride, size_t frame_stride, int W, int H, int gray, int n_frames, uint8_t* d_pix, void* stream);
+/* jpezy_encode_jpeg from host packed pixels (encoder/jpezy_encoder.hpp:38-77): streamed in MCU-row bands like it, one input segment per
+ * band instead of three; the bytes are those of jpezy_encode_jpeg for the same pixels. */
+long jpezy_encode_jpeg_packed(jpezy_ctx* ctx, const uint8_t* pix, int format, size_t row_stride, int W, int H, int gray, const char* comment,
+                              uint8_t* out, size_t cap);
+/* jpezy_decode_jpeg into host packed pixels (decoder/jpezy_decoder.hpp:76-134), for every layout it accepts: jpezy's own through the fused
+ * kernel, everything else through the generic pair, files handed to the host Huffman decoder included.  pix NULL: header only;
+ * pix_cap < (H-1)*row_stride + W*bytes: JPEZY_E_NOSPACE. */
+int jpezy_decode_jpeg_packed(jpezy_ctx* ctx, const uint8_t* data, size_t len, int gray, jpezy_frame_info* info, int format, size_t row_stride,
+                             uint8_t* pix, size_t pix_cap);
 
 #ifdef __cplusplus
 }

@@ -15,6 +15,10 @@ from .api import (  # noqa: F401
     FrameInfo,
     JpezyError,
     MultiEncoder,
+    PIX_BGR24,
+    PIX_BGRA32,
+    PIX_RGB24,
+    PIX_RGBA32,
     coeff_count,
     encode_batch_multi,
     library_path,
@@ -27,6 +31,6 @@ from .api import (  # noqa: F401
 )
 
 __all__ = [
-    "Context", "Decoder", "Encoder", "FrameInfo", "JpezyError", "MultiEncoder", "coeff_count", "encode_batch_multi", "library_path",
+    "Context", "Decoder", "Encoder", "FrameInfo", "JpezyError", "MultiEncoder", "PIX_BGR24", "PIX_BGRA32", "PIX_RGB24", "PIX_RGBA32", "coeff_count", "encode_batch_multi", "library_path",
     "load_library", "mcu_grid", "read_jpeg", "shard_range", "write_jpeg", "write_jpeg_batch",
 ]

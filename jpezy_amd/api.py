@@ -97,7 +97,19 @@ ABI = [
     ("jpezy_ctx_last_huffdec_passes", C.c_int, [_vp]),
     ("jpezy_ctx_last_batch_fast_count", C.c_int, [_vp]),
     ("jpezy_ctx_set_huffdec_min_bytes", None, [_vp, C.c_size_t]),
+    ("jpezy_pixel_bytes", C.c_int, [C.c_int]),
+    ("jpezy_fdct_quant_packed_dev", C.c_int, [_vp, _vp, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]),
+    ("jpezy_dequant_idct_packed_dev", C.c_int, [_vp, _vp, _QT, _TQ, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]),
+    ("jpezy_encode_jpeg_packed", C.c_long, [_vp, _vp, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_char_p, _vp, C.c_size_t]),
+    ("jpezy_decode_jpeg_packed", C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.POINTER(FrameInfo), C.c_int, C.c_size_t, _vp, C.c_size_t]),
 ]
+
+# enum jpezy_pixel_format: packed (interleaved) pixels, 3 or 4 bytes each
+PIX_RGB24, PIX_BGR24, PIX_RGBA32, PIX_BGRA32 = 0, 1, 2, 3
+
+
+def pixel_bytes(fmt):
+    return _check(load_library().jpezy_pixel_bytes(int(fmt)))
 
 
 def library_path():
@@ -391,6 +403,71 @@ class Context:
         _check(load_library().jpezy_dequant_idct_dev(self._h, d_coeffs.data_ptr(), C.byref(qtab), C.byref(tq), stride, W, H,
                                                      int(gray), n_frames, d_r.data_ptr(), d_g.data_ptr(), d_b.data_ptr(),
                                                      stream))
+
+    # ---- packed (interleaved) pixels ----
+    def encode_jpeg_packed(self, img, format=PIX_RGB24, gray=False, comment=None):
+        """numpy uint8 (H, W, C) interleaved pixels -> .jpg bytes (the bytes encode_jpeg gives for the same pixels).  Taken as it is,
+        without a copy, whenever strides[2] == 1 and strides[1] == C: strides[0] becomes row_stride, so a cropped view encodes in place."""
+        lib = load_library()
+        nb = pixel_bytes(format)
+        img = np.asarray(img)
+        if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != nb:
+            raise JpezyError(f"encode_jpeg_packed: a uint8 array of shape (H, W, {nb}) is expected")
+        if not (img.strides[2] == 1 and img.strides[1] == nb and img.strides[0] >= img.shape[1] * nb):
+            img = np.ascontiguousarray(img)
+        H, W = img.shape[:2]
+        if comment is None:
+            comment = b"Encoded by JPEZY" if gray else b"Encoded by jpezy"
+        cap = lib.jpezy_jpeg_bound(W, H)
+        buf = np.empty(cap, dtype=np.uint8)
+        n = lib.jpezy_encode_jpeg_packed(self._h, _np_ptr(img), int(format), img.strides[0], W, H, int(gray), comment, _np_ptr(buf), cap)
+        _check(n)
+        return buf[:n].tobytes()
+
+    def decode_jpeg_packed(self, data, format=PIX_RGB24, gray=False):
+        """.jpg bytes -> (FrameInfo, uint8 array (H, W, C)) of interleaved pixels; the fourth byte of a 32-bit format is 0xFF."""
+        lib = load_library()
+        nb = pixel_bytes(format)
+        arr = np.frombuffer(bytes(data), dtype=np.uint8)
+        info = FrameInfo()
+        _check(lib.jpezy_decode_jpeg_packed(self._h, _np_ptr(arr), arr.size, int(gray), C.byref(info), int(format), 0, None, 0))
+        img = np.empty((info.height, info.width, nb), dtype=np.uint8)
+        _check(lib.jpezy_decode_jpeg_packed(self._h, _np_ptr(arr), arr.size, int(gray), C.byref(info), int(format), 0, _np_ptr(img), img.size))
+        return info, img
+
+    @staticmethod
+    def _packed_layout(d_img, nb, who):
+        """(n_frames, H, W, row_stride, frame_stride) of a torch uint8 tensor (H, W, C) or (N, H, W, C) whose pixels are interleaved"""
+        import torch
+        if d_img.dtype != torch.uint8 or d_img.dim() not in (3, 4) or d_img.shape[-1] != nb:
+            raise JpezyError(f"{who}: a uint8 tensor of shape (H, W, {nb}) or (N, H, W, {nb}) is expected")
+        if d_img.stride(-1) != 1 or d_img.stride(-2) != nb:
+            raise JpezyError(f"{who}: the pixels are not interleaved (stride(-1) must be 1 and stride(-2) {nb})")
+        H, W = int(d_img.shape[-3]), int(d_img.shape[-2])
+        n = int(d_img.shape[0]) if d_img.dim() == 4 else 1
+        row = int(d_img.stride(-3))
+        frame = int(d_img.stride(0)) if d_img.dim() == 4 and n > 1 else 0
+        return n, H, W, row, frame
+
+    def fdct_quant_packed_dev(self, d_img, d_coeffs, format=PIX_RGB24, gray=False, stream=None):
+        """device packed pixels (torch uint8 (H, W, C) or (N, H, W, C); row and frame strides are the tensor's) -> d_coeffs"""
+        import torch
+        n, H, W, row, frame = self._packed_layout(d_img, pixel_bytes(format), "fdct_quant_packed_dev")
+        if stream is None:
+            stream = torch.cuda.current_stream(d_img.device).cuda_stream
+        _check(load_library().jpezy_fdct_quant_packed_dev(self._h, d_img.data_ptr(), int(format), row, frame, W, H, int(gray), n,
+                                                          d_coeffs.data_ptr(), stream))
+
+    def dequant_idct_packed_dev(self, d_coeffs, d_img, format=PIX_RGB24, qt=None, comp_tq=(0, 1, 1), gray=False, stream=None):
+        """device coefficients (6-block layout) -> device packed pixels written into d_img (layout as for fdct_quant_packed_dev)"""
+        import torch
+        n, H, W, row, frame = self._packed_layout(d_img, pixel_bytes(format), "dequant_idct_packed_dev")
+        if stream is None:
+            stream = torch.cuda.current_stream(d_coeffs.device).cuda_stream
+        qtab = qt if qt is not None else annex_k_tables().qt
+        tq = (C.c_uint8 * 3)(*comp_tq)
+        _check(load_library().jpezy_dequant_idct_packed_dev(self._h, d_coeffs.data_ptr(), C.byref(qtab), C.byref(tq), int(format), row, frame,
+                                                            W, H, int(gray), n, d_img.data_ptr(), stream))
 
 
 # ---- host serial tail / head ----

@@ -234,18 +234,10 @@ int jpezy_internal_check_dims(const jpezy_ctx* c, int W, int H, int n_frames)
     return JPEZY_OK;
 }
 
-int jpezy_fdct_quant_dev(jpezy_ctx* c, const uint8_t* d_r, const uint8_t* d_g, const uint8_t* d_b,
-                         size_t plane_stride, int W, int H, int gray, int n_frames, int16_t* d_coeffs, void* stream)
+// Everything of EncParams that does not say where the pixels are; shared by the planar and the packed entry point.
+int jpezy_internal_enc_params(jpezy_ctx* c, int W, int H, int gray, int n_frames, int16_t* d_coeffs, hipStream_t s, EncParams* out)
 {
-    if (int rc = jpezy_internal_check_dims(c, W, H, n_frames)) return rc;
-    if (!d_r || !d_g || !d_b || !d_coeffs) return set_err(JPEZY_E_BADARG, "null device pointer");
-    if (!aligned16(d_coeffs)) return set_err(JPEZY_E_BADARG, "d_coeffs must be 16-byte aligned");
-    if (plane_stride < (size_t)W * H) return set_err(JPEZY_E_BADARG, "plane_stride smaller than W*H");
-    HIP_TRY(hipSetDevice(c->device));
-    hipStream_t s = (hipStream_t)stream;
-    EncParams p;
-    p.r = d_r; p.g = d_g; p.b = d_b;
-    p.plane_stride = plane_stride;
+    EncParams& p = *out;
     p.coeffs = d_coeffs;
     p.coeffs_per_frame = jpezy_coeff_count(W, H, gray);
     p.tab = c->d_tab.as<DeviceTables>();
@@ -261,6 +253,7 @@ int jpezy_fdct_quant_dev(jpezy_ctx* c, const uint8_t* d_r, const uint8_t* d_g, c
     HIP_TRY(hipMemsetAsync(c->dump_t.p, 0, p.coeffs_per_frame * (size_t)n_frames * sizeof(float), s));
     p.dump_t = (float*)c->dump_t.p;
 #endif
+    (void)s;
     p.W = W; p.H = H;
     p.mcu_cols = jpezy_mcu_cols(W);
     p.mcu_rows = jpezy_mcu_rows(H);
@@ -268,6 +261,22 @@ int jpezy_fdct_quant_dev(jpezy_ctx* c, const uint8_t* d_r, const uint8_t* d_g, c
     p.n_frames = n_frames;
     fast_div_setup((unsigned)p.quads_per_row, &p.qpr_magic, &p.qpr_shift);
     for (int t = 0; t < 2; ++t) { p.dc_rq[t] = c->dc_rq[t]; p.dc_bias[t] = c->dc_bias[t]; }
+    return JPEZY_OK;
+}
+
+int jpezy_fdct_quant_dev(jpezy_ctx* c, const uint8_t* d_r, const uint8_t* d_g, const uint8_t* d_b,
+                         size_t plane_stride, int W, int H, int gray, int n_frames, int16_t* d_coeffs, void* stream)
+{
+    if (int rc = jpezy_internal_check_dims(c, W, H, n_frames)) return rc;
+    if (!d_r || !d_g || !d_b || !d_coeffs) return set_err(JPEZY_E_BADARG, "null device pointer");
+    if (!aligned16(d_coeffs)) return set_err(JPEZY_E_BADARG, "d_coeffs must be 16-byte aligned");
+    if (plane_stride < (size_t)W * H) return set_err(JPEZY_E_BADARG, "plane_stride smaller than W*H");
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    EncParams p;
+    p.r = d_r; p.g = d_g; p.b = d_b;
+    p.plane_stride = plane_stride;
+    if (int rc = jpezy_internal_enc_params(c, W, H, gray, n_frames, d_coeffs, s, &p)) return rc;
     // the f32 kernel puts the frame index in grid.y: larger batches go out in chunks
     for (int f0 = 0; f0 < n_frames; f0 += kMaxFramesPerLaunch) {
         EncParams q = p;
@@ -349,7 +358,7 @@ try {
 }
 JPEZY_CATCH
 
-static int upload_dequant(jpezy_ctx* c, const uint16_t qt[4][64], const uint8_t comp_tq[3], hipStream_t s)
+int jpezy_internal_upload_dequant(jpezy_ctx* c, const uint16_t qt[4][64], const uint8_t comp_tq[3], hipStream_t s)
 {
     uint16_t sel[3][64];
     for (int k = 0; k < 3; ++k) std::memcpy(sel[k], qt[comp_tq[k] & 3], sizeof sel[k]);
@@ -390,22 +399,12 @@ static int upload_dequant(jpezy_ctx* c, const uint16_t qt[4][64], const uint8_t 
     return JPEZY_OK;
 }
 
-int jpezy_dequant_idct_dev(jpezy_ctx* c, const int16_t* d_coeffs, const uint16_t qt[4][64], const uint8_t comp_tq[3],
-                           size_t plane_stride, int W, int H, int gray, int n_frames, uint8_t* d_r, uint8_t* d_g,
-                           uint8_t* d_b, void* stream)
+// Everything of DecParams that does not say where the pixels go (after jpezy_internal_upload_dequant); planar and packed entry point.
+void jpezy_internal_dec_params(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H, int n_frames, DecParams* out)
 {
-    if (int rc = jpezy_internal_check_dims(c, W, H, n_frames)) return rc;
-    if (!d_coeffs || !qt || !comp_tq || !d_r || !d_g || !d_b) return set_err(JPEZY_E_BADARG, "null pointer");
-    if (!aligned16(d_coeffs)) return set_err(JPEZY_E_BADARG, "d_coeffs must be 16-byte aligned");
-    if (plane_stride < (size_t)W * H) return set_err(JPEZY_E_BADARG, "plane_stride smaller than W*H");
-    HIP_TRY(hipSetDevice(c->device));
-    hipStream_t s = (hipStream_t)stream;
-    if (int rc = upload_dequant(c, qt, comp_tq, s)) return rc;
-    DecParams p;
+    DecParams& p = *out;
     p.coeffs = d_coeffs;
     p.coeffs_per_frame = jpezy_coeff_count(W, H, 0);
-    p.r = d_r; p.g = d_g; p.b = d_b;
-    p.plane_stride = plane_stride;
     p.dqscale = c->d_dqscale.as<double>();
     p.dqscale_f = c->d_dqscale_f.as<float>();
     p.dqt = c->d_dqt.as<int>();
@@ -416,6 +415,23 @@ int jpezy_dequant_idct_dev(jpezy_ctx* c, const int16_t* d_coeffs, const uint16_t
     p.mcu_rows = jpezy_mcu_rows(H);
     p.quads_per_row = (p.mcu_cols + 3) / 4;
     p.n_frames = n_frames;
+}
+
+int jpezy_dequant_idct_dev(jpezy_ctx* c, const int16_t* d_coeffs, const uint16_t qt[4][64], const uint8_t comp_tq[3],
+                           size_t plane_stride, int W, int H, int gray, int n_frames, uint8_t* d_r, uint8_t* d_g,
+                           uint8_t* d_b, void* stream)
+{
+    if (int rc = jpezy_internal_check_dims(c, W, H, n_frames)) return rc;
+    if (!d_coeffs || !qt || !comp_tq || !d_r || !d_g || !d_b) return set_err(JPEZY_E_BADARG, "null pointer");
+    if (!aligned16(d_coeffs)) return set_err(JPEZY_E_BADARG, "d_coeffs must be 16-byte aligned");
+    if (plane_stride < (size_t)W * H) return set_err(JPEZY_E_BADARG, "plane_stride smaller than W*H");
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = jpezy_internal_upload_dequant(c, qt, comp_tq, s)) return rc;
+    DecParams p;
+    p.r = d_r; p.g = d_g; p.b = d_b;
+    p.plane_stride = plane_stride;
+    jpezy_internal_dec_params(c, d_coeffs, W, H, n_frames, &p);
     for (int f0 = 0; f0 < n_frames; f0 += kMaxFramesPerLaunch) {
         DecParams q = p;
         q.n_frames = n_frames - f0 < kMaxFramesPerLaunch ? n_frames - f0 : kMaxFramesPerLaunch;
@@ -432,7 +448,7 @@ try {
     if (int rc = jpezy_internal_check_dims(c, W, H, n_frames)) return rc;
     if (!coeffs || !qt || !comp_tq || !r || !g || !b) return set_err(JPEZY_E_BADARG, "null pointer");
     HIP_TRY(hipSetDevice(c->device));
-    if (int rc = upload_dequant(c, qt, comp_tq, c->stream)) return rc;      // tables first: never rewritten while chunks are in flight
+    if (int rc = jpezy_internal_upload_dequant(c, qt, comp_tq, c->stream)) return rc;      // tables first: never rewritten while chunks are in flight
     const size_t plane = (size_t)W * H;
     const std::vector<HostChunk> chunks = plan_host_chunks(W, H, n_frames, 3, c->host_chunk_bytes);
     const size_t P = plane_pitch(chunks, W, H);
@@ -467,7 +483,8 @@ JPEZY_CATCH
 // uploaded synchronously when they changed since the last call)
 int jpezy_internal_generic_dev_core(jpezy_ctx* c, const int16_t* d_coeffs, const uint16_t qt[4][64], int ncomp, const uint8_t comp_h[3],
                             const uint8_t comp_v[3], const uint8_t comp_tq[3], int W, int H, int gray, int precision, uint8_t* d_r,
-                            uint8_t* d_g, uint8_t* d_b, hipStream_t s, size_t* nblk_out, int n_frames, size_t plane_stride)
+                            uint8_t* d_g, uint8_t* d_b, hipStream_t s, size_t* nblk_out, int n_frames, size_t plane_stride, int pix_bytes,
+                            unsigned row_stride)
 {
     if (ncomp != 1 && ncomp != 3) return set_err(JPEZY_E_UNSUPPORTED, "dimension not supported (the reference accepts 1 or 3)");
     GenericDecParams p;
@@ -495,12 +512,14 @@ int jpezy_internal_generic_dev_core(jpezy_ctx* c, const int16_t* d_coeffs, const
         return set_err(JPEZY_E_BADARG, "generic decoder, batch form: plane stride must hold a plane and be a multiple of 4");
     p.n_frames = n_frames;
     p.plane_stride = plane_stride;
+    p.pix_bytes = pix_bytes;                                 // packed pixels: d_r, d_g, d_b are the channel bytes of pixel (0, 0)
+    p.row_stride = row_stride;
     const int per = generic_frames_per_launch(p);            // samples scratch: the frames of one launch (launches run in stream order)
     if (per < 1) return set_err(JPEZY_E_UNSUPPORTED, "generic decoder: frame of more than 2^31 blocks");
     if (int rc = c->scratch.reserve(nblk * 64 * sizeof(int) * (size_t)std::min(n_frames, per))) return rc;
     // per-component dequantiser constants (fast path) and integer quantisers (reference-order path), cached in the context
     const uint8_t tq3[3] = { comp_tq[0], (uint8_t)(ncomp > 1 ? comp_tq[1] : 0), (uint8_t)(ncomp > 2 ? comp_tq[2] : 0) };
-    if (int rc = upload_dequant(c, qt, tq3, s)) return rc;
+    if (int rc = jpezy_internal_upload_dequant(c, qt, tq3, s)) return rc;
     p.coeffs = d_coeffs;
     p.samples = c->scratch.as<int>();
     p.qt = c->d_dqt.as<int>();

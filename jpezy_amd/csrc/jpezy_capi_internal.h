@@ -1,6 +1,7 @@
 // jpezy_capi_internal.h -- what the translation units of the C-ABI share (internal): error macros, the context (owners: jpezy_owners.h).
 // jpezy_capi.hip (context, the two transform stages), jpezy_capi_entropy.hip (Huffman coding, host and GPU),
-// jpezy_capi_huffdec.hip (GPU Huffman decoding of one file, decoder::decode end to end), jpezy_capi_decode_batch.hip (the batch form).
+// jpezy_capi_huffdec.hip (GPU Huffman decoding of one file, decoder::decode end to end), jpezy_capi_decode_batch.hip (the batch form),
+// jpezy_capi_packed.hip (the entry points for packed, i.e. interleaved, pixels).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -203,7 +204,12 @@ JPEZY_INTERNAL int jpezy_internal_check_dims(const jpezy_ctx* c, int W, int H, i
 // geometry + tables + the two launches of the any-layout decoder on device memory (jpezy_capi.hip)
 JPEZY_INTERNAL int jpezy_internal_generic_dev_core(jpezy_ctx* c, const int16_t* d_coeffs, const uint16_t qt[4][64], int ncomp, const uint8_t comp_h[3],
                                                    const uint8_t comp_v[3], const uint8_t comp_tq[3], int W, int H, int gray, int precision, uint8_t* d_r,
-                                                   uint8_t* d_g, uint8_t* d_b, hipStream_t s, size_t* nblk_out, int n_frames = 1, size_t plane_stride = 0);
+                                                   uint8_t* d_g, uint8_t* d_b, hipStream_t s, size_t* nblk_out, int n_frames = 1, size_t plane_stride = 0,
+                                                   int pix_bytes = 0, unsigned row_stride = 0);
+// the parts of the two transform stages' kernel parameters that planar and packed entry points share, and the cached dequantiser tables
+JPEZY_INTERNAL int jpezy_internal_enc_params(jpezy_ctx* c, int W, int H, int gray, int n_frames, int16_t* d_coeffs, hipStream_t s, EncParams* out);
+JPEZY_INTERNAL void jpezy_internal_dec_params(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H, int n_frames, DecParams* out);
+JPEZY_INTERNAL int jpezy_internal_upload_dequant(jpezy_ctx* c, const uint16_t qt[4][64], const uint8_t comp_tq[3], hipStream_t s);
 JPEZY_INTERNAL int jpezy_internal_dequant_idct_generic_impl(jpezy_ctx* c, const int16_t* coeffs, const uint16_t qt[4][64], int ncomp, const uint8_t comp_h[3],
                                                             const uint8_t comp_v[3], const uint8_t comp_tq[3], int W, int H, int gray, int precision,
                                                             uint8_t* r, uint8_t* g, uint8_t* b, bool coeffs_on_device = false);

@@ -77,6 +77,13 @@ struct EncParams {
     // flagged sums): fl(1 / Q_t[0]) and 1 / (2 Q_t[0]); 0: one of the two did not reproduce DeviceTables::dcq for these constants (checked
     // for every sum at context creation) and neither may be used
     float dc_rq[2], dc_bias[2];
+    // Packed (interleaved) pixels, jpezy_fdct_quant_packed_dev: pix_bytes = 3 or 4 (0: planes).  r, g, b then point at the three channel
+    // bytes of pixel (0, 0) of frame 0, pixel (x, y) of a channel lies x * pix_bytes + y * row_stride behind it and plane_stride is the
+    // frame stride.  pix = the first byte of the buffer, swap_rb = blue comes first (the 16-byte load form de-interleaves whole words and
+    // picks its v_perm selectors by it).  Only the packed kernel instances read these four; the planar ones are compiled as before.
+    const uint8_t* pix = nullptr;
+    unsigned row_stride = 0;
+    int pix_bytes = 0, swap_rb = 0;
 #ifdef JPEZY_TRACE
     unsigned long long* trace;       // development builds only (tools/profile/wave_trace.py): 4 words per wave
 #endif
@@ -101,6 +108,11 @@ struct DecParams {
     unsigned long long* fallback_count;
     int W, H, mcu_cols, mcu_rows, quads_per_row, n_frames;
     unsigned qpr_magic, qpr_shift;   // fast_div by quads_per_row (set by the launcher)
+    // packed (interleaved) output, jpezy_dequant_idct_packed_dev: the same four fields as EncParams' (r, g, b = the channel bytes of pixel
+    // (0, 0), plane_stride = the frame stride); the fourth byte of a 32-bit pixel is written as 0xFF
+    uint8_t* pix = nullptr;
+    unsigned row_stride = 0;
+    int pix_bytes = 0, swap_rb = 0;
 };
 
 // (magic, shift) such that n / d == (((n - mulhi(n, magic)) >> 1) + mulhi(n, magic)) >> shift for all 32-bit n;
@@ -119,6 +131,11 @@ hipError_t launch_fdct_quant(const EncParams& p, bool gray, bool force_exact, hi
 // coefficient through the reference-order chain, 2 every coefficient through the FP64 second level, 3 every quad
 // through the per-lane evaluator of the queue-overflow case.
 hipError_t launch_fdct_quant_f32(const EncParams& p, bool gray, int force, hipStream_t stream);
+// the same two kernels for packed (interleaved) pixels (EncParams::pix_bytes != 0): the f32 one with a 16-byte load form that separates
+// the channels in registers, the FP64 one through its byte loop
+hipError_t launch_fdct_quant_f32_packed(const EncParams& p, bool gray, int force, hipStream_t stream);
+hipError_t launch_fdct_quant_packed(const EncParams& p, bool gray, bool force_exact, hipStream_t stream);
+bool packed_is_aligned16(const void* pix, int W, size_t row_stride, size_t frame_stride);
 // variant 2: the same arithmetic in persistent workgroups with LDS-DMA loader waves (jpezy_kernels_f32_ps.hip); frames whose rows do
 // not divide into groups of four quads, or unaligned planes, go to variant 1's launch.  n_cus: compute units of the device.
 hipError_t launch_fdct_quant_f32_ps(const EncParams& p, bool gray, int force, int n_cus, hipStream_t stream);
@@ -128,6 +145,8 @@ bool fdct_quant_f32_ps_applies(const EncParams& p);
 hipError_t launch_fdct_quant_f32_ps2(const EncParams& p, bool gray, int force, int n_cus, hipStream_t stream);
 // tolerant: luma in FP32 without guard band (samples within one of the reference's, jpezy_kernels_decode.hip); chroma stays exact
 hipError_t launch_dequant_idct(const DecParams& p, bool gray, bool force_exact, bool tolerant, hipStream_t stream);
+// the same kernel with the packed store stage (DecParams::pix_bytes != 0)
+hipError_t launch_dequant_idct_packed(const DecParams& p, bool gray, bool force_exact, bool tolerant, hipStream_t stream);
 
 // any-layout decode (jpezy_kernels_generic.hip)
 struct GenericDecParams {
@@ -151,6 +170,10 @@ struct GenericDecParams {
     // its samples at samples + f * blocks * 64, its planes at r/g/b + f * plane_stride (a multiple of 4)
     int n_frames = 1;
     size_t plane_stride = 0;
+    // packed (interleaved) output: pix_bytes = 3 or 4 (0: planes); r, g, b = the channel bytes of pixel (0, 0), rows row_stride apart,
+    // frames plane_stride apart (any value then); byte 3 of a 32-bit pixel = 0xFF
+    int pix_bytes = 0;
+    unsigned row_stride = 0;
 };
 hipError_t launch_dequant_idct_generic(const GenericDecParams& p, hipStream_t stream);
 // frames of p's layout one pair of launches takes (the launcher loops over larger batches); 0: a frame too large for one launch

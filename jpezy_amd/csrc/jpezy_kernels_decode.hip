@@ -221,7 +221,43 @@ constexpr float DEC_CHROMA_BAND = 5e-5f, DEC_CHROMA_GATE = 512.f;      // intege
 // rigorous figure is 0.7 ... 0.9 -- still below 1: the truncated samples differ by at most one.
 // MODE: 0 = exact, with the coefficient range test; 1 = exact, no range test (8-bit quantiser tables: see launch_dequant_idct);
 // 2 = tolerance mode (always with the range test: the FP32 bound above needs it)
-template <bool GRAY, bool ALIGNED, bool FORCE_EXACT, int MODE>
+// PIX: 0 = three planes; 3 / 4 = packed (interleaved) pixels of that many bytes (jpezy_dequant_idct_packed_dev) -- only the store stage
+// (the end of step 5) differs: a lane interleaves its 16 pixels into 12 or 16 words with v_perm_b32, two per word (24 or 32 per
+// lane; the fourth byte of a 32-bit pixel comes out of the selector as 0xFF), and stores 48 or 64 contiguous bytes.
+template <int PIX>
+__device__ __forceinline__ void store_packed16(uint8_t* dst, bool swap_rb, const uint32_t* Rw, const uint32_t* Gw, const uint32_t* Bw, bool nontemporal)
+{
+    uint32_t w[4 * PIX];
+    if (PIX == 3) {
+        // r0 g0 b0 r1 | g1 b1 r2 g2 | b2 r3 g3 b3, or with blue first b0 g0 r0 b1 | g1 r1 b2 g2 | r2 b3 g3 r3: the same operands
+        // (green over red, then blue over that), other selectors -- picked on the scalar unit
+        const uint32_t a0 = swap_rb ? 0x00000400u : 0x01000400u, b0 = swap_rb ? 0x05020104u : 0x03040100u;
+        const uint32_t a1 = swap_rb ? 0x06000105u : 0x06020005u, b1 = swap_rb ? 0x03060100u : 0x03020500u;
+        const uint32_t a2 = swap_rb ? 0x03070002u : 0x00070300u, b2 = swap_rb ? 0x03020700u : 0x07020106u;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            w[3 * q] = __builtin_amdgcn_perm(Bw[q], __builtin_amdgcn_perm(Gw[q], Rw[q], a0), b0);
+            w[3 * q + 1] = __builtin_amdgcn_perm(Bw[q], __builtin_amdgcn_perm(Gw[q], Rw[q], a1), b1);
+            w[3 * q + 2] = __builtin_amdgcn_perm(Bw[q], __builtin_amdgcn_perm(Gw[q], Rw[q], a2), b2);
+        }
+    } else {
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {                       // pixel k of the group: (r, g, b, 0xFF) or (b, g, r, 0xFF)
+                const uint32_t a = swap_rb ? ((uint32_t)k << 16) | ((4u + k) << 8) : ((4u + k) << 8) | (uint32_t)k;
+                const uint32_t b = swap_rb ? 0xFF020100u | (4u + k) : 0xFF000100u | ((4u + k) << 16);
+                w[4 * q + k] = __builtin_amdgcn_perm(Bw[q], __builtin_amdgcn_perm(Gw[q], Rw[q], a), b);
+            }
+    }
+#pragma unroll
+    for (int k = 0; k < PIX; ++k) {
+        const uint4 v = make_uint4(w[4 * k], w[4 * k + 1], w[4 * k + 2], w[4 * k + 3]);
+        if (nontemporal) nt_store16(reinterpret_cast<uint4*>(dst) + k, v); else reinterpret_cast<uint4*>(dst)[k] = v;
+    }
+}
+
+template <bool GRAY, bool ALIGNED, bool FORCE_EXACT, int MODE, int PIX = 0>
 __global__ __launch_bounds__(64 * WPB, GRAY ? JPEZY_DEC_WAVES_GRAY : JPEZY_DEC_WAVES) void dequant_idct_kernel(DecParams p)
 {
     constexpr bool TOL = MODE == 2, RANGE = MODE != 1;
@@ -632,6 +668,31 @@ __global__ __launch_bounds__(64 * WPB, GRAY ? JPEZY_DEC_WAVES_GRAY : JPEZY_DEC_W
     // LDS so that wave 0 stores rows 0..7 and wave 1 rows 8..15 of BOTH quads: eight lanes = one whole line.  The launch takes the
     // same time either way (34.2 us per 4096^2 frame, three interleaved rounds), but half-line non-temporal stores are counted --
     // and moved -- as 63.8 MB of writes for 50.3 MB of planes; whole lines bring WRITE_SIZE to 49.2 MB (profiles/r04_dec_traffic.txt).
+    if (PIX != 0) {
+        // Packed pixels: every lane stores its own row segment, 48 or 64 contiguous bytes (the four lanes of a pixel row 192 or 256);
+        // the two-wave whole-line swap below is the planar instances' -- these pass through no workgroup barrier at all.  Colour
+        // goes out non-temporal and gray plain, the planar kernel's measured choice; the packed form was not measured both ways.
+        const int py = mcu_y * 16 + row;
+        if (live && py < H) {
+            const size_t rowoff = (size_t)frame * p.plane_stride + (unsigned)py * p.row_stride;   // row_stride * H < 2^32 (entry point)
+            if (ALIGNED) {
+                store_packed16<PIX == 0 ? 3 : PIX>(p.pix + rowoff + (unsigned)mcu_x * (16u * PIX), p.swap_rb != 0, Rw, Gw, Bw, !GRAY);
+            } else {
+#pragma unroll
+                for (int k = 0; k < 16; ++k) {
+                    const int x = mcu_x * 16 + k;
+                    if (x < W) {                                   // ref :546-551
+                        const size_t o = rowoff + (unsigned)x * (unsigned)PIX;
+                        p.r[o] = (uint8_t)(Rw[k >> 2] >> ((k & 3) * 8));
+                        p.g[o] = (uint8_t)(Gw[k >> 2] >> ((k & 3) * 8));
+                        p.b[o] = (uint8_t)(Bw[k >> 2] >> ((k & 3) * 8));
+                        if (PIX == 4) p.pix[o + 3] = 0xFF;
+                    }
+                }
+            }
+        }
+        return;
+    }
     if (ALIGNED && !GRAY && WPB == 2) {
         const unsigned q0 = blockIdx.x * 2u;                                         // the workgroup's first quad
         const int qx0 = (int)q0 - (int)fast_div(q0, p.qpr_magic, p.qpr_shift) * p.quads_per_row;
@@ -694,6 +755,40 @@ __global__ __launch_bounds__(64 * WPB, GRAY ? JPEZY_DEC_WAVES_GRAY : JPEZY_DEC_W
 // ======================================================================================================
 // launchers
 // ======================================================================================================
+template <bool GRAY, bool ALIGNED, int PIX>
+static void dec_packed_launch2(const DecParams& p, bool force, bool tol, dim3 grid, hipStream_t s)
+{
+    if (force)           // the same choice of instance as dec_launch2
+        hipLaunchKernelGGL((dequant_idct_kernel<GRAY, ALIGNED, true, 0, PIX>), grid, dim3(64 * WPB), 0, s, p);
+    else if (tol)
+        hipLaunchKernelGGL((dequant_idct_kernel<GRAY, ALIGNED, false, 2, PIX>), grid, dim3(64 * WPB), 0, s, p);
+    else if (p.coef_limit >= 32768)
+        hipLaunchKernelGGL((dequant_idct_kernel<GRAY, ALIGNED, false, 1, PIX>), grid, dim3(64 * WPB), 0, s, p);
+    else
+        hipLaunchKernelGGL((dequant_idct_kernel<GRAY, ALIGNED, false, 0, PIX>), grid, dim3(64 * WPB), 0, s, p);
+}
+
+template <int PIX>
+static void dec_packed_launch(const DecParams& p, bool gray, bool al, bool force, bool tol, dim3 grid, hipStream_t s)
+{
+    if (gray) { if (al) dec_packed_launch2<true, true, PIX>(p, force, tol, grid, s); else dec_packed_launch2<true, false, PIX>(p, force, tol, grid, s); }
+    else      { if (al) dec_packed_launch2<false, true, PIX>(p, force, tol, grid, s); else dec_packed_launch2<false, false, PIX>(p, force, tol, grid, s); }
+}
+
+hipError_t launch_dequant_idct_packed(const DecParams& p0, bool gray, bool force_exact, bool tolerant, hipStream_t stream)
+{
+    const long quads = (long)p0.mcu_rows * p0.quads_per_row;
+    if (quads <= 0 || p0.n_frames <= 0) return hipSuccess;
+    if (p0.n_frames > 65535 || (p0.pix_bytes != 3 && p0.pix_bytes != 4)) return hipErrorInvalidValue;
+    DecParams p = p0;
+    fast_div_setup((unsigned)p.quads_per_row, &p.qpr_magic, &p.qpr_shift);
+    const dim3 grid((unsigned)((quads + WPB - 1) / WPB), (unsigned)p.n_frames);
+    const bool al = packed_is_aligned16(p.pix, p.W, p.row_stride, p.plane_stride);
+    if (p.pix_bytes == 3) dec_packed_launch<3>(p, gray, al, force_exact, tolerant, grid, stream);
+    else dec_packed_launch<4>(p, gray, al, force_exact, tolerant, grid, stream);
+    return hipGetLastError();
+}
+
 template <bool GRAY, bool ALIGNED>
 static void dec_launch2(const DecParams& p, bool force, bool tol, dim3 grid, hipStream_t s)
 {

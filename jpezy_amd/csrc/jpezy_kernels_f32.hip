@@ -136,6 +136,93 @@ __global__ __launch_bounds__(64 * EWPB, JPEZY_F32_WAVES) void fdct_quant_f32_ker
 #endif
 }
 
+// ---- packed (interleaved) pixels: jpezy_fdct_quant_packed_dev ------------------------------------------------------------------
+// The same quad, the same arithmetic (encode_quad takes R[4], G[4], B[4] as before); only step 1 differs.  PIX = bytes per pixel.
+// ALIGNED (W % 16 == 0; base, row stride and frame stride multiples of 16): a lane's 16-pixel row segment is 48 or 64 contiguous
+// bytes -- three or four 16-byte loads, the four lanes of a pixel row read 192 or 256 contiguous bytes, so there is no
+// 64-bytes-of-16-rows pattern to cure and no cooperative load for either workgroup shape -- and the channels are separated in
+// registers with v_perm_b32: 24 bits per pixel need 2 per output word (24 per lane), 32 bits per pixel 7 per four pixels (28 per
+// lane, two levels: the (c0, c2) pairs and the c1 pairs of two pixels, then one per output word).  Blue first (BGR, BGRA) only
+// exchanges the selectors of the first and the third channel, chosen on the scalar unit: it costs no vector instruction.
+// Anything else: the byte loop over the three channel pointers with the planar kernel's edge replication.
+template <int PIX>
+__device__ __forceinline__ void load_packed16(const uint8_t* src, bool swap_rb, uint32_t* R, uint32_t* G, uint32_t* B)
+{
+    const uint4* s4 = reinterpret_cast<const uint4*>(src);
+    if (PIX == 3) {
+        // bytes of three words = four pixels: c0 at 0, 3, 6, 9; c1 at 1, 4, 7, 10; c2 at 2, 5, 8, 11
+        const uint32_t a1 = swap_rb ? 0x00000502u : 0x00060300u, a2 = swap_rb ? 0x07040100u : 0x05020100u;   // red
+        const uint32_t c1 = swap_rb ? 0x00060300u : 0x00000502u, c2 = swap_rb ? 0x05020100u : 0x07040100u;   // blue
+        const uint4 v0 = s4[0], v1 = s4[1], v2 = s4[2];
+        const uint32_t w[12] = { v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w, v2.x, v2.y, v2.z, v2.w };
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const uint32_t w0 = w[3 * q], w1 = w[3 * q + 1], w2 = w[3 * q + 2];
+            R[q] = __builtin_amdgcn_perm(w2, __builtin_amdgcn_perm(w1, w0, a1), a2);
+            G[q] = __builtin_amdgcn_perm(w2, __builtin_amdgcn_perm(w1, w0, 0x00070401u), 0x06020100u);
+            B[q] = __builtin_amdgcn_perm(w2, __builtin_amdgcn_perm(w1, w0, c1), c2);
+        }
+    } else {
+        // one word per pixel (c0, c1, c2, unused): u = (c0, c0', c2, c2') and v = (c1, c1', ., .) of a pixel pair, then the words
+        const uint32_t a = swap_rb ? 0x07060302u : 0x05040100u, c = swap_rb ? 0x05040100u : 0x07060302u;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {                          // one 16-byte piece at a time: its four words die here
+            const uint4 v = s4[q];
+            const uint32_t u01 = __builtin_amdgcn_perm(v.y, v.x, 0x06020400u), u23 = __builtin_amdgcn_perm(v.w, v.z, 0x06020400u);
+            const uint32_t v01 = __builtin_amdgcn_perm(v.y, v.x, 0x00000501u), v23 = __builtin_amdgcn_perm(v.w, v.z, 0x00000501u);
+            R[q] = __builtin_amdgcn_perm(u23, u01, a);
+            G[q] = __builtin_amdgcn_perm(v23, v01, 0x05040100u);
+            B[q] = __builtin_amdgcn_perm(u23, u01, c);
+        }
+    }
+}
+
+template <bool GRAY, bool ALIGNED, int FORCE, int EWPB, bool DCG, int PIX>
+__global__ __launch_bounds__(64 * EWPB, JPEZY_F32_WAVES) void fdct_quant_f32_packed_kernel(EncParams p)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t lds_all[EWPB][WAVE_LDS_DWORDS];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int mcu_y = (int)fast_div(blockIdx.x, p.gpr_magic, p.gpr_shift);
+    const int gx = (int)blockIdx.x - mcu_y * p.groups_per_row;
+    const int quad_x = gx * EWPB + wave;
+    if (quad_x >= p.quads_per_row) return;                                // wave-uniform; the waves never meet at a barrier
+    const unsigned qidx = (unsigned)(mcu_y * p.quads_per_row + quad_x);
+    const int frame = (int)blockIdx.y;
+    uint32_t* lds = lds_all[wave];
+    const int row = lane >> 2, m = lane & 3;
+    const int mcu_x = min(quad_x * 4 + m, p.mcu_cols - 1);
+    const int W = p.W, H = p.H;
+    const int y = min(mcu_y * 16 + row, H - 1);                           // edge replication, ref :101
+    const unsigned rowoff = (unsigned)y * p.row_stride;                   // row_stride * H < 2^32 (the entry point refuses more)
+    uint32_t R[4], G[4], B[4];
+    if (ALIGNED) {
+        load_packed16<PIX>(p.pix + (size_t)frame * p.plane_stride + (rowoff + (unsigned)mcu_x * (16u * PIX)), p.swap_rb != 0, R, G, B);
+    } else {
+        const uint8_t* pr = p.r + (size_t)frame * p.plane_stride + rowoff;
+        const uint8_t* pg = p.g + (size_t)frame * p.plane_stride + rowoff;
+        const uint8_t* pb = p.b + (size_t)frame * p.plane_stride + rowoff;
+#pragma unroll
+        for (int w4 = 0; w4 < 4; ++w4) {
+            uint32_t ar = 0, ag = 0, ab = 0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const unsigned x = (unsigned)min(mcu_x * 16 + w4 * 4 + k, W - 1) * (unsigned)PIX;   // ref :104
+                ar |= (uint32_t)pr[x] << (8 * k);
+                ag |= (uint32_t)pg[x] << (8 * k);
+                ab |= (uint32_t)pb[x] << (8 * k);
+            }
+            R[w4] = ar; G[w4] = ag; B[w4] = ab;
+        }
+    }
+#ifdef JPEZY_TRACE
+    QuadTrace tr;                                                         // (the wave trace follows the planar kernel only)
+#if JPEZY_TRACE >= 3
+    unsigned long long* ph = tr.ph;
+#endif
+#endif
+    encode_quad<GRAY, FORCE, false, DCG>(p, R, G, B, lds, lane, mcu_y, quad_x, frame, qidx, nullptr, nullptr, nullptr QUAD_TRACE_ARG);
+}
+
 }  // namespace f32
 
 template <bool GRAY, bool ALIGNED, int EW, bool DCG>
@@ -183,5 +270,57 @@ hipError_t launch_fdct_quant_f32(const EncParams& p0, bool gray, int force, hipS
     return hipGetLastError();
 }
 
+
+template <bool GRAY, bool ALIGNED, int EW, int PIX>
+static void enc_f32_packed_launch(const EncParams& p, int force, dim3 grid, hipStream_t s)
+{
+    const bool dcg = p.dc_rq[0] != 0.f && p.dc_rq[1] != 0.f;            // as enc_f32_launch2
+#define JPEZY_PACKED_LAUNCH(F)                                                                                                   \
+    do {                                                                                                                         \
+        if (dcg) hipLaunchKernelGGL((f32::fdct_quant_f32_packed_kernel<GRAY, ALIGNED, F, EW, true, PIX>), grid, dim3(64 * EW), 0, s, p); \
+        else hipLaunchKernelGGL((f32::fdct_quant_f32_packed_kernel<GRAY, ALIGNED, F, EW, false, PIX>), grid, dim3(64 * EW), 0, s, p);    \
+    } while (0)
+    if constexpr (EW == 2) {
+        if (force == 1) { JPEZY_PACKED_LAUNCH(1); return; }
+        if (force == 2) { JPEZY_PACKED_LAUNCH(2); return; }
+        if (force == 3) { JPEZY_PACKED_LAUNCH(3); return; }
+    }
+    JPEZY_PACKED_LAUNCH(0);
+#undef JPEZY_PACKED_LAUNCH
+}
+
+template <int PIX>
+static void enc_f32_packed_launch_pix(const EncParams& p, bool gray, bool al, int ew, int force, dim3 grid, hipStream_t s)
+{
+    if (ew == 4) {
+        if (gray) enc_f32_packed_launch<true, true, 4, PIX>(p, force, grid, s); else enc_f32_packed_launch<false, true, 4, PIX>(p, force, grid, s);
+    } else if (gray) {
+        if (al) enc_f32_packed_launch<true, true, 2, PIX>(p, force, grid, s); else enc_f32_packed_launch<true, false, 2, PIX>(p, force, grid, s);
+    } else {
+        if (al) enc_f32_packed_launch<false, true, 2, PIX>(p, force, grid, s); else enc_f32_packed_launch<false, false, 2, PIX>(p, force, grid, s);
+    }
+}
+
+bool packed_is_aligned16(const void* pix, int W, size_t row_stride, size_t frame_stride)
+{
+    return W % 16 == 0 && row_stride % 16 == 0 && frame_stride % 16 == 0 && (uintptr_t)pix % 16 == 0;
+}
+
+hipError_t launch_fdct_quant_f32_packed(const EncParams& p0, bool gray, int force, hipStream_t stream)
+{
+    EncParams p = p0;
+    const bool al = packed_is_aligned16(p.pix, p.W, p.row_stride, p.plane_stride);
+    // the workgroup shapes of the planar launch (both with direct loads here); the test hooks' instances exist for two waves only
+    const int ew = (al && p.quads_per_row % 4 == 0 && force == 0) ? 4 : 2;
+    p.groups_per_row = (p.quads_per_row + ew - 1) / ew;
+    const long groups = (long)p.mcu_rows * p.groups_per_row;
+    if (groups <= 0 || p.n_frames <= 0) return hipSuccess;
+    if (p.n_frames > 65535 || (p.pix_bytes != 3 && p.pix_bytes != 4)) return hipErrorInvalidValue;
+    fast_div_setup((unsigned)p.groups_per_row, &p.gpr_magic, &p.gpr_shift);
+    const dim3 grid((unsigned)groups, (unsigned)p.n_frames);
+    if (p.pix_bytes == 3) enc_f32_packed_launch_pix<3>(p, gray, al, ew, force, grid, stream);
+    else enc_f32_packed_launch_pix<4>(p, gray, al, ew, force, grid, stream);
+    return hipGetLastError();
+}
 
 }  // namespace jpezy_dev

@@ -110,6 +110,7 @@ struct BlockRef {   // the frame's planes: what the exact path needs to find a b
     const uint8_t* g;
     const uint8_t* b;
     int W, H;
+    unsigned row_stride, pix_bytes;     // packed pixels only (PACKED instances): bytes between rows / between pixels of one channel
 };
 
 // ---- exact-order FDCT + quantise of ONE coefficient by the whole wave (ref jpezy_encoder.hpp:146-172) ----
@@ -117,6 +118,7 @@ struct BlockRef {   // the frame's planes: what the exact path needs to find a b
 // pixel, converts it, forms (pic*cos[j][x])*cos[i][y]; the 64 terms are then added in the reference's order.
 // comp 0: luma block with top-left pixel (px0,py0), step 1.  comp 1/2: Cb/Cr of the MCU at (px0,py0), step 2
 // (top-left sample of each 2x2, ref :134-142).  Coordinates clamp to the image (ref :101,104).
+template <bool PACKED = false>
 __device__ __forceinline__ int exact_fdct_coef_wave(const BlockRef& img, int px0, int py0, int comp, int i, int j,
                                                     int Q, int lane)
 {
@@ -124,7 +126,7 @@ __device__ __forceinline__ int exact_fdct_coef_wave(const BlockRef& img, int px0
     const int y = lane >> 3, x = lane & 7;
     const int yy = min(py0 + y * step, img.H - 1);
     const int xx = min(px0 + x * step, img.W - 1);
-    const size_t idx = (size_t)yy * img.W + xx;
+    const size_t idx = PACKED ? (size_t)yy * img.row_stride + (size_t)xx * img.pix_bytes : (size_t)yy * img.W + xx;
     const double rf = (double)img.r[idx], gf = (double)img.g[idx], bf = (double)img.b[idx];
     const double pic = comp == 0 ? ref_y(rf, gf, bf) : comp == 1 ? ref_cb(rf, gf, bf) : ref_cr(rf, gf, bf);
     const double sum = ordered_wave_sum(pic * c_cos[j * 8 + x] * c_cos[i * 8 + y]);
@@ -199,7 +201,9 @@ __device__ __forceinline__ double byte_of(const uint32_t* w, int k)
 // ======================================================================================================
 // ENCODE
 // ======================================================================================================
-template <bool GRAY, bool ALIGNED, bool FORCE_EXACT>
+// PACKED (jpezy_fdct_quant_packed_dev): r, g, b are the channel bytes of pixel (0, 0) of an interleaved buffer, p.pix_bytes between
+// pixels and p.row_stride between rows; such input takes the byte loop (ALIGNED is never set with it)
+template <bool GRAY, bool ALIGNED, bool FORCE_EXACT, bool PACKED = false>
 __global__ __launch_bounds__(64 * WPB, 4) void fdct_quant_kernel(EncParams p)
 {
     __shared__ __attribute__((aligned(16))) uint32_t lds_all[WPB][WAVE_LDS_DWORDS];
@@ -227,13 +231,13 @@ __global__ __launch_bounds__(64 * WPB, 4) void fdct_quant_kernel(EncParams p)
     const uint8_t* pr = p.r + (size_t)frame * p.plane_stride;
     const uint8_t* pg = p.g + (size_t)frame * p.plane_stride;
     const uint8_t* pb = p.b + (size_t)frame * p.plane_stride;
-    const BlockRef img = { pr, pg, pb, W, H };
+    const BlockRef img = { pr, pg, pb, W, H, PACKED ? p.row_stride : 0u, PACKED ? (unsigned)p.pix_bytes : 0u };
 
     // ---- 1. stream this lane's 16-pixel row segment of the three planes ----
     uint32_t R[4], G[4], B[4];
     {
         const int y = min(mcu_y * 16 + row, H - 1);             // edge replication, ref :101
-        const size_t rowoff = (size_t)y * W;
+        const size_t rowoff = PACKED ? (size_t)y * p.row_stride : (size_t)y * W;
         if (ALIGNED) {
             const size_t off = rowoff + (size_t)mcu_x * 16;
             const uint4 vr = *reinterpret_cast<const uint4*>(pr + off);
@@ -248,7 +252,7 @@ __global__ __launch_bounds__(64 * WPB, 4) void fdct_quant_kernel(EncParams p)
                 uint32_t ar = 0, ag = 0, ab = 0;
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
-                    const int x = min(mcu_x * 16 + w4 * 4 + k, W - 1);   // ref :104
+                    const int x = min(mcu_x * 16 + w4 * 4 + k, W - 1) * (PACKED ? p.pix_bytes : 1);   // ref :104
                     ar |= (uint32_t)pr[rowoff + x] << (8 * k);
                     ag |= (uint32_t)pg[rowoff + x] << (8 * k);
                     ab |= (uint32_t)pb[rowoff + x] << (8 * k);
@@ -365,7 +369,7 @@ __global__ __launch_bounds__(64 * WPB, 4) void fdct_quant_kernel(EncParams p)
                 int px0 = emx * 16, py0 = mcu_y * 16, comp = 0;
                 if (eb < 4) { px0 += (eb & 1) * 8; py0 += (eb >> 1) * 8; } else { comp = eb - 3; }
                 const int Q = tab->qt[comp ? 1 : 0][nat];
-                const int qv = exact_fdct_coef_wave(img, px0, py0, comp, ei, ej, Q, lane);
+                const int qv = exact_fdct_coef_wave<PACKED>(img, px0, py0, comp, ei, ej, Q, lane);
                 if (lane == 0) *reinterpret_cast<int16_t*>(stage + blk * STG_BLK + 2 * (int)c_zzinv[nat]) = (int16_t)qv;
                 ++done;
             }
@@ -409,6 +413,21 @@ hipError_t launch_fdct_quant(const EncParams& p, bool gray, bool force_exact, hi
     const bool al = is_aligned16(p, p.r, p.g, p.b);
     if (gray) { if (al) enc_launch2<true, true>(p, force_exact, grid, stream); else enc_launch2<true, false>(p, force_exact, grid, stream); }
     else      { if (al) enc_launch2<false, true>(p, force_exact, grid, stream); else enc_launch2<false, false>(p, force_exact, grid, stream); }
+    return hipGetLastError();
+}
+
+hipError_t launch_fdct_quant_packed(const EncParams& p, bool gray, bool force_exact, hipStream_t stream)
+{
+    const long quads = (long)p.n_frames * p.mcu_rows * p.quads_per_row;
+    if (quads <= 0) return hipSuccess;
+    const dim3 grid((unsigned)((quads + WPB - 1) / WPB));
+    if (gray) {
+        if (force_exact) hipLaunchKernelGGL((fdct_quant_kernel<true, false, true, true>), grid, dim3(64 * WPB), 0, stream, p);
+        else hipLaunchKernelGGL((fdct_quant_kernel<true, false, false, true>), grid, dim3(64 * WPB), 0, stream, p);
+    } else {
+        if (force_exact) hipLaunchKernelGGL((fdct_quant_kernel<false, false, true, true>), grid, dim3(64 * WPB), 0, stream, p);
+        else hipLaunchKernelGGL((fdct_quant_kernel<false, false, false, true>), grid, dim3(64 * WPB), 0, stream, p);
+    }
     return hipGetLastError();
 }
 

@@ -158,6 +158,9 @@ __device__ __forceinline__ uint32_t revise(double v) { return (v < 0.0) ? 0u : (
 // One thread: four consecutive pixels of a row (one 4-byte store per plane when the row allows it); a workgroup: 256 pixels
 // of four rows.  Everything that depends on the row only (MCU row, the component's block row, whether decode_mcu ever
 // writes that row of the component's plane) is computed once per thread.
+// PIX: 0 = planes; 3 / 4 = packed (interleaved) pixels of that many bytes -- the thread's four pixels are 12 or 16 contiguous bytes,
+// one 12- or 16-byte store when they start on a 4-byte boundary and all four exist, single bytes otherwise.
+template <int PIX = 0>
 __global__ __launch_bounds__(256) void generic_rgb_kernel(GenericDecParams p)
 {
     const unsigned x0 = (blockIdx.x * 64u + (threadIdx.x & 63u)) * 4u;
@@ -228,6 +231,38 @@ __global__ __launch_bounds__(256) void generic_rgb_kernel(GenericDecParams p)
         }
         rw |= r << (8 * j); gw |= g << (8 * j); bw |= b << (8 * j);
     }
+    if (PIX != 0) {
+        const bool blue_first = p.b < p.r;                       // r, g, b: the channel bytes of pixel (0, 0)
+        uint8_t* px = (blue_first ? p.b : p.r) + (size_t)y * p.row_stride + (size_t)x0 * PIX;
+        const uint32_t fw = blue_first ? bw : rw, tw = blue_first ? rw : bw;
+        auto byte = [](uint32_t w, unsigned j) { return (w >> (8 * j)) & 0xFFu; };
+        if (npx == 4 && ((uintptr_t)px & 3u) == 0) {
+            if (PIX == 3) {
+                typedef unsigned v3u __attribute__((ext_vector_type(3)));
+                typedef v3u v3u_a4 __attribute__((aligned(4)));
+                v3u v;
+                v.x = byte(fw, 0) | byte(gw, 0) << 8 | byte(tw, 0) << 16 | byte(fw, 1) << 24;
+                v.y = byte(gw, 1) | byte(tw, 1) << 8 | byte(fw, 2) << 16 | byte(gw, 2) << 24;
+                v.z = byte(tw, 2) | byte(fw, 3) << 8 | byte(gw, 3) << 16 | byte(tw, 3) << 24;
+                *reinterpret_cast<v3u_a4*>(px) = v;
+            } else {
+                typedef unsigned v4u __attribute__((ext_vector_type(4)));
+                typedef v4u v4u_a4 __attribute__((aligned(4)));
+                v4u v;
+                v.x = byte(fw, 0) | byte(gw, 0) << 8 | byte(tw, 0) << 16 | 0xFF000000u;
+                v.y = byte(fw, 1) | byte(gw, 1) << 8 | byte(tw, 1) << 16 | 0xFF000000u;
+                v.z = byte(fw, 2) | byte(gw, 2) << 8 | byte(tw, 2) << 16 | 0xFF000000u;
+                v.w = byte(fw, 3) | byte(gw, 3) << 8 | byte(tw, 3) << 16 | 0xFF000000u;
+                *reinterpret_cast<v4u_a4*>(px) = v;
+            }
+        } else {
+            for (unsigned j = 0; j < npx; ++j) {
+                px[j * PIX] = (uint8_t)byte(fw, j); px[j * PIX + 1] = (uint8_t)byte(gw, j); px[j * PIX + 2] = (uint8_t)byte(tw, j);
+                if (PIX == 4) px[j * PIX + 3] = 0xFF;
+            }
+        }
+        return;
+    }
     const size_t off = (size_t)y * p.W + x0;
     if (npx == 4 && (p.W & 3) == 0) {                           // rows start 4-byte aligned (the planes are device allocations)
         *reinterpret_cast<uint32_t*>(p.r + off) = rw;
@@ -273,7 +308,9 @@ hipError_t launch_dequant_idct_generic(const GenericDecParams& p_in, hipStream_t
         q.r += (size_t)f0 * p.plane_stride; q.g += (size_t)f0 * p.plane_stride; q.b += (size_t)f0 * p.plane_stride;
         const long nblk = fblk * q.n_frames;
         hipLaunchKernelGGL(generic::generic_idct_kernel, dim3((unsigned)((nblk + generic::G_BLOCKS - 1) / generic::G_BLOCKS)), dim3(64), 0, s, q, nblk);
-        hipLaunchKernelGGL(generic::generic_rgb_kernel, dim3(gx, gy, (unsigned)q.n_frames), dim3(256), 0, s, q);
+        if (q.pix_bytes == 3) hipLaunchKernelGGL(generic::generic_rgb_kernel<3>, dim3(gx, gy, (unsigned)q.n_frames), dim3(256), 0, s, q);
+        else if (q.pix_bytes == 4) hipLaunchKernelGGL(generic::generic_rgb_kernel<4>, dim3(gx, gy, (unsigned)q.n_frames), dim3(256), 0, s, q);
+        else hipLaunchKernelGGL(generic::generic_rgb_kernel<0>, dim3(gx, gy, (unsigned)q.n_frames), dim3(256), 0, s, q);
         if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
     }
     return hipSuccess;

@@ -200,6 +200,21 @@ long jpezy_ctx_last_fallback_count(jpezy_ctx* ctx);
 long jpezy_write_jpeg(const int16_t* coeffs, int W, int H, int gray, const char* comment, uint8_t* out,
                       size_t cap);
 /*
+ * Per-image optimised Huffman tables (what libjpeg calls `optimize`): the same coefficients and the same decoded pixels in a smaller
+ * file.  The four DHT segments then hold the frame's own tables, built from its symbol counts exactly as ITU-T T.81 Annex K.2
+ * states (Figures K.1 - K.4, a reserved symbol so that no code is all ones, every tie toward the larger symbol value, no code longer
+ * than 16 bits).  jpezy_write_jpeg_opt is jpezy_write_jpeg with such tables, on the host; the GPU coder writes the same bytes when
+ * jpezy_ctx_set_huffman_optimize is on.  A value outside the code tables is JPEZY_E_FORMAT, as for jpezy_write_jpeg.
+ */
+long jpezy_write_jpeg_opt(const int16_t* coeffs, int W, int H, int gray, const char* comment, uint8_t* out,
+                          size_t cap);
+/*
+ * The table construction alone (pure host function): freq[sym] = how often symbol sym occurs -> bits[l - 1] = codes of length l,
+ * vals = the symbols in order of code length, then ascending value (a DHT segment's two arrays).  Returns the number of symbols
+ * (those with a non-zero count) or JPEZY_E_BADARG.  A single used symbol gets the one-bit code 0.
+ */
+int jpezy_huffman_optimal_table(const unsigned long long freq[256], uint8_t bits[16], uint8_t vals[256]);
+/*
  * The longest comment (bytes before the terminating NUL) any writer accepts: jpezy_write_jpeg[_batch], jpezy_write_jpeg_gpu[_batch,
  * _dev], jpezy_encode_jpeg and jpezy_multi_encode / jpezy_encode_batch_multi all refuse a longer one with JPEZY_E_BADARG.  It is
  * what makes the header fit 1024 bytes: 623 bytes of markers and tables + a COM segment of n + 5 bytes (marker, length, text, NUL).
@@ -210,6 +225,10 @@ long jpezy_write_jpeg(const int16_t* coeffs, int W, int H, int gray, const char*
  * MCU codes 4 x 1658 + 2 x 1660 bits (every AC coefficient a 16-bit code + 10 value bits, the DC difference 9 or 11 + 11 bits), i.e.
  * 1244 bytes, 2488 if every byte were 0xFF and stuffed; the pad bits (one byte, two if stuffed) and the 2-byte EOI fit in the
  * 200 bytes per MCU left over (tests/test_jpeg_bound.py).
+ * With per-image tables (jpezy_write_jpeg_opt, jpezy_ctx_set_huffman_optimize) a DC code is at most 12 bits (12 categories + the
+ * reserved symbol: 13 leaves) and an AC code at most 16: a block is at most 12 + 11 + 63 x 26 = 1661 bits, an MCU 9966 bits = 1246
+ * bytes, 2492 stuffed -- still within 2688; and no table has more symbols than its Annex-K counterpart (12 / 162), so the header is
+ * never longer.  The same bound holds (tests/test_huffopt_host.py).
  */
 size_t jpezy_jpeg_bound(int W, int H);
 /*
@@ -247,6 +266,23 @@ int jpezy_write_jpeg_gpu_batch(jpezy_ctx* ctx, const int16_t* d_coeffs, int W, i
  */
 int jpezy_write_jpeg_gpu_dev(jpezy_ctx* ctx, const int16_t* d_coeffs, int W, int H, int gray, int n_frames,
                              const char* comment, uint8_t* d_out, size_t out_stride, long long* d_sizes, void* stream);
+/*
+ * Per-image optimised Huffman tables on the GPU path (opt-in; default 0).  With on = 1, jpezy_write_jpeg_gpu, jpezy_write_jpeg_gpu_batch,
+ * jpezy_encode_jpeg and jpezy_encode_jpeg_packed write the bytes of jpezy_write_jpeg_opt: a kernel counts every frame's symbols, the
+ * host builds the frame's four tables from the counts (one extra synchronisation and two small copies per call) and the coder runs
+ * with a table image per frame; every frame of a batch gets its own DHT segments.  With on = 0 every byte is what it was.
+ * Restrictions: jpezy_write_jpeg_gpu_dev returns JPEZY_E_UNSUPPORTED while the setting is on (the tables are built on the host and
+ * that call is asynchronous); the multi-GPU handle (jpezy_multi_*, jpezy_encode_batch_multi) owns its contexts and always writes
+ * Annex-K tables.  Returns 0 or JPEZY_E_BADARG.
+ */
+int jpezy_ctx_set_huffman_optimize(jpezy_ctx* ctx, int on);
+/*
+ * The symbol-counting kernel on its own, asynchronous on `stream`: d_hist[f][k][sym] (device memory, [n_frames][4][256], zeroed
+ * here) = how often the coder emits symbol sym from table k (DHT order: 0 YDc, 1 CDc, 2 YAc, 3 CAc) for frame f.  A value outside
+ * the code tables is counted as the clamped symbol the coder would emit (size 10, category 11).
+ */
+int jpezy_huffman_histogram_dev(jpezy_ctx* ctx, const int16_t* d_coeffs, int W, int H, int gray, int n_frames,
+                                unsigned long long* d_hist, void* stream);
 /*
  * encoder::encode end to end (encoder/jpezy_encoder.hpp:38-77) with both stages on the GPU: host planar r,g,b in,
  * host .jpg bytes out; returns the byte count (the value encoder::encode returns) or a negative status.

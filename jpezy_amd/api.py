@@ -79,6 +79,10 @@ ABI = [
     ("jpezy_write_jpeg_gpu", C.c_long, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_char_p, _vp, C.c_size_t]),
     ("jpezy_write_jpeg_gpu_batch", C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, _vp, C.c_size_t, C.POINTER(C.c_long)]),
     ("jpezy_write_jpeg_gpu_dev", C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, _vp, C.c_size_t, _vp, _vp]),
+    ("jpezy_ctx_set_huffman_optimize", C.c_int, [_vp, C.c_int]),
+    ("jpezy_huffman_histogram_dev", C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]),
+    ("jpezy_huffman_optimal_table", C.c_int, [_vp, _vp, _vp]),
+    ("jpezy_write_jpeg_opt", C.c_long, [_vp, C.c_int, C.c_int, C.c_int, C.c_char_p, _vp, C.c_size_t]),
     ("jpezy_encode_jpeg", C.c_long, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_char_p, _vp, C.c_size_t]),
     ("jpezy_shard_range", None, [C.c_long, C.c_int, C.c_int, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
     ("jpezy_encode_batch_multi", C.c_int, [C.POINTER(C.c_int), C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p,
@@ -208,6 +212,11 @@ class Context:
         """0: bit-exact decode (default); 1: luma in FP32, every output byte within one of the reference's."""
         _check(load_library().jpezy_ctx_set_decode_tolerance(self._h, int(on)))
 
+    def set_huffman_optimize(self, on):
+        """0: Annex-K tables (default); 1: write_jpeg_gpu, encode_jpeg and encode_jpeg_packed give every frame its own optimal
+        Huffman tables (the bytes of write_jpeg(..., optimize=True)); write_jpeg_gpu_dev is refused while it is on."""
+        _check(load_library().jpezy_ctx_set_huffman_optimize(self._h, int(on)))
+
     def set_host_chunk_bytes(self, n):
         """bytes of input per chunk of the streaming host-buffer entry points (default 4 MiB)"""
         load_library().jpezy_ctx_set_host_chunk_bytes(self._h, int(n))
@@ -305,6 +314,16 @@ class Context:
         stride = d_out.numel() // n_frames
         _check(load_library().jpezy_write_jpeg_gpu_dev(self._h, d_coeffs.data_ptr(), W, H, int(gray), n_frames, comment,
                                                        d_out.data_ptr(), stride, d_sizes.data_ptr(), stream))
+
+    def huffman_histogram_dev(self, d_coeffs, W, H, d_hist, gray=False, n_frames=1, stream=None):
+        """Asynchronous: d_hist (torch int64 tensor [n_frames, 4, 256] on the device) receives the frames' symbol counts, table k in
+        DHT order YDc, CDc, YAc, CAc."""
+        import torch
+        if stream is None:
+            stream = torch.cuda.current_stream(d_coeffs.device).cuda_stream
+        if d_hist.numel() != n_frames * 4 * 256 or d_hist.element_size() != 8 or not d_hist.is_contiguous():
+            raise JpezyError("huffman_histogram_dev: d_hist must be a contiguous 64-bit tensor of n_frames * 4 * 256 elements")
+        _check(load_library().jpezy_huffman_histogram_dev(self._h, d_coeffs.data_ptr(), W, H, int(gray), n_frames, d_hist.data_ptr(), stream))
 
     def read_jpeg_gpu(self, data):
         """.jpg bytes -> (FrameInfo, torch int16 tensor [mcu_rows, mcu_cols, blocks_per_mcu, 64] on the device): header
@@ -471,8 +490,19 @@ class Context:
 
 
 # ---- host serial tail / head ----
-def write_jpeg(coeffs, W, H, gray=False, comment=None):
-    """zig-zag int16 coefficients -> the .jpg bytes jpezy_encode writes (header + Huffman + EOI)."""
+def optimal_table(freq):
+    """256 symbol counts -> (bits[16], vals[nval]) of the optimal Huffman table (Annex K.2; jpezy_huffman_optimal_table)"""
+    f = np.ascontiguousarray(freq, dtype=np.uint64)
+    if f.size != 256:
+        raise JpezyError("optimal_table: 256 counts are expected")
+    bits, vals = np.zeros(16, dtype=np.uint8), np.zeros(256, dtype=np.uint8)
+    n = _check(load_library().jpezy_huffman_optimal_table(_np_ptr(f), _np_ptr(bits), _np_ptr(vals)))
+    return bits, vals[:n].copy()
+
+
+def write_jpeg(coeffs, W, H, gray=False, comment=None, optimize=False):
+    """zig-zag int16 coefficients -> the .jpg bytes jpezy_encode writes (header + Huffman + EOI); optimize: with the frame's own
+    optimal Huffman tables instead of Annex K (same coefficients, smaller file)."""
     lib = load_library()
     coeffs = np.ascontiguousarray(coeffs, dtype=np.int16)
     if coeffs.size != lib.jpezy_coeff_count(W, H, int(gray)):
@@ -481,7 +511,8 @@ def write_jpeg(coeffs, W, H, gray=False, comment=None):
         comment = b"Encoded by JPEZY" if gray else b"Encoded by jpezy"   # ref encode_io.hpp:149,181
     cap = lib.jpezy_jpeg_bound(W, H)
     buf = np.empty(cap, dtype=np.uint8)
-    n = _check(lib.jpezy_write_jpeg(_np_ptr(coeffs), W, H, int(gray), comment, _np_ptr(buf), cap))
+    fn = lib.jpezy_write_jpeg_opt if optimize else lib.jpezy_write_jpeg
+    n = _check(fn(_np_ptr(coeffs), W, H, int(gray), comment, _np_ptr(buf), cap))
     return buf[:n].tobytes()
 
 

@@ -1,6 +1,8 @@
-// jpezy_encode <input.ppm> ( <output.(jpeg | jpg) [OPT: --gray]> | <output.ppm> | --debug )
+// jpezy_encode <input.ppm> ( <output.(jpeg | jpg) [OPT: --gray] [OPT: --optimize]> | <output.ppm> | --debug )
 // Same argv rules, transcript and exit codes as the reference's src/encoder/main.cpp; the codec underneath is
 // the MI355X path (jpezy_encoder.hpp).
+// Extension (not in the reference):  --optimize (single-file mode only, either side of --gray) writes the file with its own optimal
+// Huffman tables (jpezy_ctx_set_huffman_optimize): same pixels, fewer bytes.
 // Extension (not in the reference):  jpezy_encode --gpus N [--gray] <in1.ppm> <out1.jpg> [<in2.ppm> <out2.jpg> ...]
 // encodes a list of files on up to N GPUs of this node through jpezy_encode_batch_multi: runs of consecutive inputs of one size
 // form a batch, a batch is sharded over the GPUs frame by frame.
@@ -99,12 +101,16 @@ int main(const int argc, const char* argv[])
     if (argc < 3) return disp_error();
 
     Mode m1 = Mode::UD, m2 = Mode::UD;
+    bool optimize = false;
     const std::string_view sv1 = argv[2];
     const std::string_view sv2 = argc > 3 ? std::string_view(argv[3]) : std::string_view();   // the reference reads argv[3] unguarded
 
     if (has_ext(sv1, "jpeg") || has_ext(sv1, "jpg")) {
         m1 = Mode::JPEG;
         if (sv2.find("--gray") != std::string_view::npos) m2 = Mode::GRAY;
+        const std::string_view sv3 = argc > 4 ? std::string_view(argv[4]) : std::string_view();
+        optimize = sv2 == "--optimize" || sv3 == "--optimize";
+        if (sv2 == "--optimize" && sv3 == "--gray") m2 = Mode::GRAY;
     } else if (has_ext(sv1, "ppm")) {
         m1 = Mode::PPM;
     } else if (sv1 == "--debug") {
@@ -126,6 +132,8 @@ int main(const int argc, const char* argv[])
 
     try {
         if (m1 == Mode::JPEG) {
+            if (optimize && jpezy_ctx_set_huffman_optimize(jpezy::detail::device_context(), 1) != JPEZY_OK)
+                throw std::runtime_error(std::string("jpezy_ctx_set_huffman_optimize: ") + jpezy_hip_last_error());
             std::ofstream ofs(argv[2], std::ios::binary);
             if (m2 == Mode::GRAY) ofs << (pnm | jpezy::to_jpeg(argv[2]) | jpezy::gray_scale);
             else ofs << (pnm | jpezy::to_jpeg(argv[2]));

@@ -35,14 +35,13 @@ JPEZY_CATCH
 // ---- GPU entropy coding: same bytes as jpezy_write_jpeg, coefficients already on the device ----
 namespace {
 
-int ensure_code_tables(jpezy_ctx* c)
+// the device image of four tables (DHT order YDc, CDc, YAc, CAc; nullptr: Annex K): canonical codes per symbol, and the AC codes
+// of small values with their value bits appended (CodeTables::fast)
+void fill_code_image(jpezy_dev::entropy::CodeTables& h, const jpezy_host::HuffTable* tabs)
 {
-    if (c->d_codes.p) return JPEZY_OK;
     uint16_t code[4][256];
     uint8_t len[4][256];
-    jpezy_host::enc_code_tables(code, len);
-    std::vector<jpezy_dev::entropy::CodeTables> hv(1);       // 10 KB: off the stack
-    jpezy_dev::entropy::CodeTables& h = hv[0];
+    jpezy_host::enc_code_tables(code, len, tabs);
     std::memset(&h, 0, sizeof h);
     for (int t = 0; t < 2; ++t) {      // DHT order: YDc, CDc, YAc, CAc
         for (int k = 0; k < 12; ++k) h.dc[t][k] = ((uint32_t)code[t][k] << 8) | len[t][k];
@@ -58,10 +57,31 @@ int ensure_code_tables(jpezy_ctx* c)
                 h.fast[t][(run << 6) | (v + 32)] = (bits << 5) | (uint32_t)(len[2 + t][k] + sz);
             }
     }
-    if (int rc = c->d_codes.reserve(sizeof h)) return rc;
-    HIP_TRY(hipMemcpy(c->d_codes.p, &h, sizeof h, hipMemcpyHostToDevice));
+}
+
+int ensure_code_tables(jpezy_ctx* c)
+{
+    if (c->d_codes.p) return JPEZY_OK;
+    std::vector<jpezy_dev::entropy::CodeTables> hv(1);       // 10 KB: off the stack
+    fill_code_image(hv[0], nullptr);
+    if (int rc = c->d_codes.reserve(sizeof hv[0])) return rc;
+    HIP_TRY(hipMemcpy(c->d_codes.p, &hv[0], sizeof hv[0], hipMemcpyHostToDevice));
     return JPEZY_OK;
 }
+
+void make_job(jpezy_dev::entropy::Job& job, const int16_t* d_coeffs, int W, int H, int gray, int F, const jpezy_dev::entropy::CodeTables* tables)
+{
+    job.coeffs = d_coeffs;
+    job.coeffs_per_frame = jpezy_coeff_count(W, H, gray);
+    job.tables = tables;
+    job.blocks_per_frame = (unsigned)((size_t)jpezy_mcu_cols(W) * jpezy_mcu_rows(H) * 6);
+    job.bpm = gray ? 4 : 6;
+    job.n_frames = F;
+    job.tables_stride = 0;
+}
+
+// frames per pass with per-image tables: a frame's table image is 10 KB
+constexpr int kMaxOptFramesPerPass = 1024;
 
 // one chunk of frames, all resident in the scratch buffers
 int entropy_chunk(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H, int gray, int F, const char* comment, uint8_t* out,
@@ -72,12 +92,8 @@ int entropy_chunk(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H, int gray,
     const size_t nmcu = (size_t)jpezy_mcu_cols(W) * jpezy_mcu_rows(H);
     const size_t nblk = nmcu * 6;
     E::Job job;
-    job.coeffs = d_coeffs;
-    job.coeffs_per_frame = jpezy_coeff_count(W, H, gray);
-    job.tables = c->d_codes.as<jpezy_dev::entropy::CodeTables>();
-    job.blocks_per_frame = (unsigned)nblk;
-    job.bpm = gray ? 4 : 6;
-    job.n_frames = F;
+    make_job(job, d_coeffs, W, H, gray, F, c->d_codes.as<E::CodeTables>());
+    const bool optimize = c->huff_optimize != 0;
 
     // every block is coded once, into the stream of its tile (256 coded blocks of a frame); worst case 208 bytes per block
     const size_t tpf = E::tiles256(nblk), nt = tpf * (size_t)F, piece = E::assemble_piece_bytes(), chunk = E::chunk_bytes();
@@ -102,13 +118,39 @@ int entropy_chunk(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H, int gray,
 
     // 1. codes; 2. unstuffed streams, one per frame, with their 0xFF bytes counted; stream lengths
     HIP_TRY(hipMemsetAsync(d_status, 0, sizeof(unsigned) * F, s));
+    // 0. per-image tables: the frames' symbol counts come to the host, which builds every frame's four tables (Annex K.2) and
+    //    sends their code images back; the coder then takes frame f's image.  One extra synchronisation and two small copies.
+    std::vector<jpezy_host::HuffTable> tabs;
+    if (optimize) {
+        const size_t hist_bytes = (size_t)F * 4 * 256 * sizeof(unsigned long long), img_bytes = (size_t)F * sizeof(E::CodeTables);
+        if (int rc = c->e_hist.reserve(hist_bytes)) return rc;
+        if (int rc = c->e_hist_pin.reserve(hist_bytes)) return rc;
+        if (int rc = c->e_codes_opt.reserve(img_bytes)) return rc;
+        if (int rc = c->e_codes_pin.reserve(img_bytes)) return rc;
+        HIP_TRY(hipMemsetAsync(c->e_hist.p, 0, hist_bytes, s));
+        HIP_TRY(E::launch_symbol_histogram(job, (unsigned long long*)c->e_hist.p, d_status, s));
+        HIP_TRY(hipMemcpyAsync(c->e_hist_pin.p, c->e_hist.p, hist_bytes, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        tabs.resize((size_t)F * 4);
+        const unsigned long long* hist = c->e_hist_pin.as<unsigned long long>();
+        for (int f = 0; f < F; ++f) {
+            for (int k = 0; k < 4; ++k) {
+                jpezy_host::HuffTable& t = tabs[(size_t)f * 4 + k];
+                t.nval = jpezy_host::optimal_table(hist + ((size_t)f * 4 + k) * 256, t.bits, t.vals);
+            }
+            fill_code_image(c->e_codes_pin.as<E::CodeTables>()[f], &tabs[(size_t)f * 4]);
+        }
+        HIP_TRY(hipMemcpyAsync(c->e_codes_opt.p, c->e_codes_pin.p, img_bytes, hipMemcpyHostToDevice, s));
+        job.tables = c->e_codes_opt.as<E::CodeTables>();
+        job.tables_stride = 1;
+    }
     HIP_TRY(E::launch_code_tiles(job, (uint32_t*)c->e_S.p, (uint32_t*)c->e_tt.p, d_status, s));
     if (!self)
         HIP_TRY(E::launch_tile_bases((const uint32_t*)c->e_tt.p, (unsigned)tpf, F, (unsigned long long*)c->e_base.p, d_bytes,
                                      (uint32_t*)c->e_ft.p, (unsigned)ft_stride, d_status, nullptr, s));
     HIP_TRY(E::launch_assemble((const uint32_t*)c->e_S.p, (const uint32_t*)c->e_tt.p, (const unsigned long long*)c->e_base.p, d_bytes,
                                (const uint32_t*)c->e_ft.p, (unsigned)ft_stride, (unsigned)tpf, F, (uint32_t*)c->e_U.p, u_stride / 4,
-                               (uint32_t*)c->e_cnt.p, (uint32_t*)c->e_fft.p, d_status, nullptr, s));
+                               (uint32_t*)c->e_cnt.p, (uint32_t*)c->e_fft.p, d_status, nullptr, s, optimize));
     HIP_TRY(E::launch_ff_frame_totals((const uint32_t*)c->e_fft.p, d_bytes, u_stride / 4, F, d_fftot, s));
     std::vector<unsigned long long> nbytes(F), fftot(F);
     std::vector<unsigned> status(F);
@@ -137,7 +179,7 @@ int entropy_chunk(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H, int gray,
         for (int f = f0; f < F; f += step) {
             uint8_t* dst = out + (size_t)f * cap;
             if (status[f]) { sizes[f] = JPEZY_E_FORMAT; failed.store(1); continue; }
-            const size_t hdr = jpezy_host::write_header(W, H, comment, dst, cap);
+            const size_t hdr = jpezy_host::write_header(W, H, comment, dst, cap, optimize ? &tabs[(size_t)f * 4] : nullptr);
             const size_t body = (size_t)(nbytes[f] + fftot[f]);
             if (!hdr || hdr + body + 2 > cap) { sizes[f] = JPEZY_E_NOSPACE; failed.store(1); continue; }
             std::memcpy(dst + hdr, c->e_pinned.p + (size_t)f * o_stride, body);
@@ -167,6 +209,9 @@ int jpezy_write_jpeg_gpu_dev(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H
     if (!d_coeffs || !d_out || !d_sizes) return set_err(JPEZY_E_BADARG, "write_jpeg_gpu_dev: null pointer");
     if (!aligned16(d_coeffs)) return set_err(JPEZY_E_BADARG, "write_jpeg_gpu_dev: d_coeffs must be 16-byte aligned");
     if (int rc = check_comment(comment, "write_jpeg_gpu_dev")) return rc;
+    if (c->huff_optimize)      // (before anything is enqueued or cached: the context is left as it was)
+        return set_err(JPEZY_E_UNSUPPORTED, "write_jpeg_gpu_dev: per-image Huffman tables are built on the host and this call is asynchronous; "
+                                            "use jpezy_write_jpeg_gpu[_batch] or jpezy_ctx_set_huffman_optimize(ctx, 0)");
     HIP_TRY(hipSetDevice(c->device));
     if (int rc = ensure_code_tables(c)) return rc;
     hipStream_t s = (hipStream_t)stream;
@@ -198,12 +243,7 @@ int jpezy_write_jpeg_gpu_dev(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H
         const int F = std::min(per, n_frames - f0);
         const size_t nchunks = u_stride / chunk * F, nt = tpf * F, nct = E::tiles256(nchunks);
         E::Job job;
-        job.coeffs = d_coeffs + (size_t)f0 * cpf;
-        job.coeffs_per_frame = cpf;
-        job.tables = c->d_codes.as<jpezy_dev::entropy::CodeTables>();
-        job.blocks_per_frame = (unsigned)nblk;
-        job.bpm = gray ? 4 : 6;
-        job.n_frames = F;
+        make_job(job, d_coeffs + (size_t)f0 * cpf, W, H, gray, F, c->d_codes.as<E::CodeTables>());
         if (int rc = c->e_tt.reserve(nt * sizeof(uint32_t))) return rc;
         if (int rc = c->e_S.reserve(nt * E::tile_stream_bytes())) return rc;
         if (!self) {
@@ -261,6 +301,7 @@ try {
     // chunk the batch so that the worst-case unstuffed streams (208 bytes per block) stay below ~1 GiB
     const size_t worst = nblk * 208 + 4096;
     int per = (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>((size_t)n_frames, kMaxFramesPerLaunch), ((size_t)1 << 30) / worst));   // 65535: grid dimension
+    if (c->huff_optimize) per = std::min(per, kMaxOptFramesPerPass);
     bool any_failed = false;
     const size_t cpf = jpezy_coeff_count(W, H, gray);
     for (int f0 = 0; f0 < n_frames; f0 += per) {
@@ -281,6 +322,51 @@ long jpezy_write_jpeg_gpu(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H, i
     if (size == JPEZY_E_NOSPACE) set_err(JPEZY_E_NOSPACE, "write_jpeg_gpu: output buffer too small");
     return size;
 }
+
+int jpezy_ctx_set_huffman_optimize(jpezy_ctx* c, int on)
+{
+    if (!c) return set_err(JPEZY_E_BADARG, "null context");
+    if (on != 0 && on != 1) return set_err(JPEZY_E_BADARG, "huffman optimize: 0 (Annex-K tables) or 1 (per-image tables)");
+    c->huff_optimize = on;
+    return JPEZY_OK;
+}
+
+int jpezy_huffman_histogram_dev(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H, int gray, int n_frames, unsigned long long* d_hist,
+                                void* stream)
+{
+    namespace E = jpezy_dev::entropy;
+    if (int rc = jpezy_internal_check_dims(c, W, H, n_frames)) return rc;
+    if (!d_coeffs || !d_hist) return set_err(JPEZY_E_BADARG, "huffman_histogram_dev: null pointer");
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    const size_t cpf = jpezy_coeff_count(W, H, gray);
+    for (int f0 = 0; f0 < n_frames; f0 += kMaxFramesPerLaunch) {
+        const int F = std::min(kMaxFramesPerLaunch, n_frames - f0);
+        if (c->e_hstat.cap < sizeof(unsigned) * (size_t)F)
+            if (int rc = c->e_hstat.reserve(sizeof(unsigned) * (size_t)F)) return rc;
+        unsigned long long* h = d_hist + (size_t)f0 * 4 * 256;
+        HIP_TRY(hipMemsetAsync(h, 0, (size_t)F * 4 * 256 * sizeof(unsigned long long), s));
+        E::Job job;
+        make_job(job, d_coeffs + (size_t)f0 * cpf, W, H, gray, F, nullptr);
+        HIP_TRY(E::launch_symbol_histogram(job, h, (unsigned*)c->e_hstat.p, s));
+    }
+    return JPEZY_OK;
+}
+
+int jpezy_huffman_optimal_table(const unsigned long long freq[256], uint8_t bits[16], uint8_t vals[256])
+{
+    if (!freq || !bits || !vals) return set_err(JPEZY_E_BADARG, "huffman_optimal_table: null pointer");
+    return jpezy_host::optimal_table(freq, bits, vals);
+}
+
+long jpezy_write_jpeg_opt(const int16_t* coeffs, int W, int H, int gray, const char* comment, uint8_t* out, size_t cap)
+try {
+    std::string err;
+    const long n = jpezy_host::write_jpeg_opt(coeffs, W, H, gray != 0, comment, out, cap, &err);
+    if (n < 0) g_err = err;
+    return n;
+}
+JPEZY_CATCH
 
 // planar RGB on the host -> .jpg bytes on the host, both stages on the GPU (what encoder::encode does end to end)
 long jpezy_encode_jpeg(jpezy_ctx* c, const uint8_t* r, const uint8_t* g, const uint8_t* b, int W, int H, int gray, const char* comment,

@@ -152,6 +152,10 @@ struct jpezy_ctx {
     DevBuf e_S, e_base, e_ft;      // one-pass coder: tile streams, frame-relative tile bit offsets, first tile per 16 KB of output
     DevBuf e_status;               // per-frame error flags of the device-resident entropy path: zero between calls (cleared by their consumer)
     PinBuf e_pinned;               // pinned host staging of the stuffed streams
+    int huff_optimize = 0;         // 1: the host-delivered entropy entry points build every frame's own Huffman tables (jpezy_ctx_set_huffman_optimize)
+    DevBuf e_hist, e_hstat;        // per-image tables: symbol counts [frames][4][256] uint64; error flags of jpezy_huffman_histogram_dev (never read)
+    DevBuf e_codes_opt;            // ... and the frames' CodeTables images [frames]
+    PinBuf e_hist_pin, e_codes_pin;    // pinned host twins of the two
     DevBuf h_scan, h_U, h_cnt, h_off, h_state, h_setup, h_small, h_dc, h_dcbuf;   // GPU Huffman decoder (jpezy_huffdec.hip)
     std::vector<uint8_t> h_setup_host;  // the device tables h_setup holds (jpezy_read_jpeg_gpu uploads them only when they change)
     const void* h_setup_dev = nullptr;  // ... and the allocation they were uploaded to

@@ -22,6 +22,7 @@ struct Job {
     const int16_t* coeffs;        // device, [frame][mcu][bpm][64] zig-zag
     size_t coeffs_per_frame;      // int16 elements
     const CodeTables* tables;     // device
+    size_t tables_stride = 0;     // frame f codes with tables[f * tables_stride]; 0: every frame with tables[0] (the Annex-K image)
     unsigned blocks_per_frame;    // coded blocks: 6 per MCU (gray: the two chroma blocks are coded as zero blocks)
     int bpm;                      // stored blocks per MCU: 6 colour, 4 gray
     int n_frames;
@@ -63,12 +64,18 @@ hipError_t launch_tile_bases(const uint32_t* tile_total, unsigned tiles_per_fram
 bool assemble_scans_tiles_itself(size_t tiles_per_frame);
 hipError_t launch_assemble(const uint32_t* S, const uint32_t* tile_total, const unsigned long long* base, unsigned long long* bytes,
                            const uint32_t* first_tile, unsigned ft_stride, unsigned tiles_per_frame, int n_frames, uint32_t* U,
-                           size_t u_stride_words, uint32_t* loc, uint32_t* ff_tile_total, unsigned* status, unsigned* latched, hipStream_t s);
+                           size_t u_stride_words, uint32_t* loc, uint32_t* ff_tile_total, unsigned* status, unsigned* latched, hipStream_t s,
+                           bool any_tables = false);    // any_tables: per-image tables (codes as short as one bit): a wider tile window for large frames
 hipError_t launch_stuff(const uint32_t* U, size_t u_stride_words, const unsigned long long* frame_bytes, int n_frames,
                         const uint32_t* ff_loc, const uint32_t* ff_tile_total, uint8_t* out, size_t out_stride, FilePlan plan, hipStream_t s);
 // dst[f] = 0xFF bytes of frame f (the host-delivered form sizes its output buffer from it)
 hipError_t launch_ff_frame_totals(const uint32_t* ff_tile_total, const unsigned long long* bytes, size_t u_stride_words, int n_frames,
                                   unsigned long long* dst, hipStream_t s);
+
+// Symbol statistics for per-image optimised tables (jpezy_huffstat.hip): hist[frame][k][sym] += the number of times the coder
+// emits symbol sym from table k (DHT order: 0 YDc, 1 CDc, 2 YAc, 3 CAc) for the frame -- what code_block sees, out-of-range values
+// counted as the clamped symbol with status[frame] |= 1.  hist must be zero before the launch (job.tables is not read).
+hipError_t launch_symbol_histogram(const Job& job, unsigned long long* hist, unsigned* status, hipStream_t s);
 
 }  // namespace entropy
 }  // namespace jpezy_dev

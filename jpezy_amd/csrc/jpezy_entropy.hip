@@ -261,8 +261,8 @@ __global__ __launch_bounds__(WG) void code_tiles_kernel(Job job, uint32_t* S, ui
 {
     __shared__ LdsTables L;
     __shared__ __attribute__((aligned(16))) char tile[WG * ROW];
-    load_tables(L, job.tables);
     const unsigned tid = threadIdx.x, frame = blockIdx.y;
+    load_tables(L, job.tables + (size_t)frame * job.tables_stride);
     const unsigned nblk = job.blocks_per_frame, g0 = blockIdx.x * (unsigned)WG;
     const unsigned nb = nblk - g0 < (unsigned)WG ? nblk - g0 : (unsigned)WG;          // coded blocks of this tile
     const int16_t* fc = job.coeffs + (size_t)frame * job.coeffs_per_frame;
@@ -413,6 +413,11 @@ __global__ __launch_bounds__(256) void tile_bases_kernel(const uint32_t* tile_to
 constexpr unsigned MIN_TILE_BITS = 42u * 32u + 20u;
 constexpr int ASM_WIN = 128;
 static_assert((unsigned)(ASM_WIN - 2) * MIN_TILE_BITS >= ASM_BITS, "assemble window too small for flat content");
+// Per-image tables (Job::tables_stride != 0) can be shorter than Annex K: a table with one used symbol codes it in ONE bit, so a flat
+// block is at least 1 (DC) + 1 (EOB) = 2 bits and a full tile at least 512: the window is ASM_BITS / 512 + 2 = 258 tiles.
+constexpr unsigned MIN_TILE_BITS_ANY = 256u * 2u;
+constexpr int ASM_WIN_ANY = 264;
+static_assert((unsigned)(ASM_WIN_ANY - 2) * MIN_TILE_BITS_ANY >= ASM_BITS, "assemble window too small for one-bit codes");
 constexpr unsigned ASM_SELF_TILES = 2048;   // frames of up to this many tiles: every assembling workgroup scans the totals itself
 
 // the 64 bytes of U that start at frame bit p: tile A (bits [bA, eA) of the frame, stream srcA) holds p; tile B (LB bits,
@@ -471,13 +476,13 @@ __device__ __forceinline__ unsigned assemble_chunk(unsigned long long p, unsigne
 // (what tile_bases_kernel does for larger frames).
 // !SELF: tile offsets, stream length and the first tile of every piece come from tile_bases_kernel; a workgroup loads the
 // window of at most ASM_WIN tile offsets its piece can touch.
-template <bool SELF>
+template <bool SELF, int WIN = ASM_WIN>
 __global__ __launch_bounds__(256) void assemble_kernel(const uint32_t* S, const uint32_t* tile_total, const unsigned long long* base,
                                                       unsigned long long* bytes, const uint32_t* first_tile, unsigned tpf,
                                                       unsigned ft_stride, uint32_t* U, size_t u_stride_words, uint32_t* loc,
                                                       uint32_t* ff_tile_total, unsigned* status, unsigned* latched)
 {
-    __shared__ unsigned long long wb[SELF ? 1 : ASM_WIN + 2];
+    __shared__ unsigned long long wb[SELF ? 1 : WIN + 2];
     __shared__ uint32_t pre[SELF ? ASM_SELF_TILES + 2 : 1];
     const unsigned frame = blockIdx.y, tid = threadIdx.x;
     const size_t chunks_per_frame = u_stride_words * 4 / CHUNK, pieces = chunks_per_frame / 256;   // a multiple of 256 (launcher)
@@ -540,10 +545,10 @@ __global__ __launch_bounds__(256) void assemble_kernel(const uint32_t* S, const 
             const unsigned t0 = first_tile[(size_t)frame * ft_stride + x];     // (garbage past the stream's end: clamped, unused)
             const unsigned long long* B = base + (size_t)frame * (tpf + 1);
             __syncthreads();                                                    // the previous piece's window is no longer read
-            for (unsigned i = tid; i < (unsigned)ASM_WIN + 2u; i += 256u) wb[i] = B[t0 + i < tpf ? t0 + i : tpf];
+            for (unsigned i = tid; i < (unsigned)WIN + 2u; i += 256u) wb[i] = B[t0 + i < tpf ? t0 + i : tpf];
             __syncthreads();
             if (c * CHUNK < nbytes) {
-                int lo = 0, hi = ASM_WIN;                               // wb[lo] <= p; first wb[hi] > p or the window's end
+                int lo = 0, hi = WIN;                               // wb[lo] <= p; first wb[hi] > p or the window's end
                 while (hi - lo > 1) {
                     const int mid = (lo + hi) >> 1;
                     if (wb[mid] <= p) lo = mid; else hi = mid;
@@ -909,7 +914,8 @@ bool assemble_scans_tiles_itself(size_t tiles_per_frame) { return tiles_per_fram
 
 hipError_t launch_assemble(const uint32_t* S, const uint32_t* tile_total, const unsigned long long* base, unsigned long long* bytes,
                            const uint32_t* first_tile, unsigned ft_stride, unsigned tiles_per_frame, int n_frames, uint32_t* U,
-                           size_t u_stride_words, uint32_t* loc, uint32_t* ff_tile_total, unsigned* status, unsigned* latched, hipStream_t s)
+                           size_t u_stride_words, uint32_t* loc, uint32_t* ff_tile_total, unsigned* status, unsigned* latched, hipStream_t s,
+                           bool any_tables)
 {
     const size_t pieces = u_stride_words * 4 / assemble_piece_bytes();
     if (!pieces || n_frames <= 0) return hipSuccess;
@@ -922,6 +928,10 @@ hipError_t launch_assemble(const uint32_t* S, const uint32_t* tile_total, const 
                            tiles_per_frame, ft_stride, U, u_stride_words, loc, ff_tile_total, status, latched);
     } else {
         if (pieces > ft_stride) return hipErrorInvalidValue;
+        if (any_tables)
+            hipLaunchKernelGGL((assemble_kernel<false, ASM_WIN_ANY>), dim3((unsigned)gx, (unsigned)n_frames), dim3(256), 0, s, S, tile_total, base,
+                               bytes, first_tile, tiles_per_frame, ft_stride, U, u_stride_words, loc, ff_tile_total, status, latched);
+        else
         hipLaunchKernelGGL(assemble_kernel<false>, dim3((unsigned)gx, (unsigned)n_frames), dim3(256), 0, s, S, tile_total, base, bytes,
                            first_tile, tiles_per_frame, ft_stride, U, u_stride_words, loc, ff_tile_total, status, latched);
     }

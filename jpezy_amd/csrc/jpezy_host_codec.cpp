@@ -44,19 +44,19 @@ struct EncLut {
 };
 struct EncTables {
     EncLut t[4];
-    EncTables()
+    EncTables() { for (int k = 0; k < 4; ++k) set(k, kSpec[k].bits, kSpec[k].vals); }
+    explicit EncTables(const HuffTable* tabs) { for (int k = 0; k < 4; ++k) set(k, tabs[k].bits, tabs[k].vals); }
+    void set(int k, const uint8_t* bits, const uint8_t* vals)
     {
-        for (int k = 0; k < 4; ++k) {
-            std::memset(&t[k], 0, sizeof t[k]);
-            unsigned code = 0;
-            int p = 0;
-            for (int l = 1; l <= 16; ++l) {
-                for (int c = 0; c < kSpec[k].bits[l - 1]; ++c, ++p) {
-                    t[k].code[kSpec[k].vals[p]] = (uint16_t)code++;
-                    t[k].len[kSpec[k].vals[p]] = (uint8_t)l;
-                }
-                code <<= 1;
+        std::memset(&t[k], 0, sizeof t[k]);
+        unsigned code = 0;
+        int p = 0;
+        for (int l = 1; l <= 16; ++l) {
+            for (int c = 0; c < bits[l - 1]; ++c, ++p) {
+                t[k].code[vals[p]] = (uint16_t)code++;
+                t[k].len[vals[p]] = (uint8_t)l;
             }
+            code <<= 1;
         }
     }
 };
@@ -158,7 +158,7 @@ inline bool put_block(BitSink& o, const int16_t* z, int& pred, const EncLut& dc,
     return true;
 }
 
-void put_header(BitSink& o, int W, int H, const char* comment)
+void put_header(BitSink& o, int W, int H, const char* comment, const HuffTable* tabs = nullptr)
 {
     static const uint8_t soi_app0[] = { 0xFF, 0xD8, 0xFF, 0xE0, 0x00, 0x10, 'J', 'F', 'I', 'F', 0x00,
                                         0x01, 0x02, 0x01, 0x00, 0x60, 0x00, 0x60, 0x00, 0x00 };
@@ -176,10 +176,13 @@ void put_header(BitSink& o, int W, int H, const char* comment)
     }
     for (int k = 0; k < 4; ++k) {
         o.raw(0xFF); o.raw(0xC4);
-        o.raw16((unsigned)(19 + kSpec[k].nval));
+        const uint8_t* bits = tabs ? tabs[k].bits : kSpec[k].bits;
+        const uint8_t* vals = tabs ? tabs[k].vals : kSpec[k].vals;
+        const int nval = tabs ? tabs[k].nval : kSpec[k].nval;
+        o.raw16((unsigned)(19 + nval));
         o.raw(kSpecId[k]);
-        o.raw_n(kSpec[k].bits, 16);
-        o.raw_n(kSpec[k].vals, (size_t)kSpec[k].nval);
+        o.raw_n(bits, 16);
+        o.raw_n(vals, (size_t)nval);
     }
     const uint8_t sof_sos[] = { 0xFF, 0xC0, 0x00, 0x11, 0x08, (uint8_t)(H >> 8), (uint8_t)H, (uint8_t)(W >> 8), (uint8_t)W,
                                 0x03, 0x00, 0x22, 0x00, 0x01, 0x11, 0x01, 0x02, 0x11, 0x01,
@@ -194,17 +197,18 @@ bool comment_ok(const char* comment)
     return !comment || std::strlen(comment) <= JPEZY_MAX_COMMENT;      // the COM length field (n + 3) can then never wrap
 }
 
-size_t write_header(int W, int H, const char* comment, uint8_t* out, size_t cap)
+size_t write_header(int W, int H, const char* comment, uint8_t* out, size_t cap, const HuffTable* tabs)
 {
     if (!comment_ok(comment)) return 0;
     BitSink o(out, cap);
-    put_header(o, W, H, comment);
+    put_header(o, W, H, comment, tabs);
     return o.ok() ? o.size() : 0;
 }
 
-void enc_code_tables(uint16_t code[4][256], uint8_t len[4][256])
+void enc_code_tables(uint16_t code[4][256], uint8_t len[4][256], const HuffTable* tabs)
 {
-    const EncTables& T = enc_tables();
+    const EncTables own = tabs ? EncTables(tabs) : EncTables();
+    const EncTables& T = tabs ? own : enc_tables();
     for (int k = 0; k < 4; ++k) {
         std::memcpy(code[k], T.t[k].code, sizeof T.t[k].code);
         std::memcpy(len[k], T.t[k].len, sizeof T.t[k].len);
@@ -214,12 +218,17 @@ void enc_code_tables(uint16_t code[4][256], uint8_t len[4][256])
 size_t jpeg_bound(int W, int H)
 {
     const size_t nmcu = (size_t)((W + 15) / 16) * (size_t)((H + 15) / 16);
-    // worst case per coefficient: 16-bit code + 10 value bits, doubled by byte stuffing
+    // Worst case with ANY tables optimal_table can return (Annex K included): a DC code of at most kMaxDcCodeBits = 12 bits (13
+    // leaves with the reserved symbol) + 11 value bits, 63 AC codes of at most 16 bits (Figure K.3) + 10 value bits:
+    // kMaxBlockBits = 1661 bits per block (207.6 bytes: the 208 bytes per block of the GPU coder's scratch hold it),
+    // kMaxMcuBits = 9966 bits = 1246 bytes per MCU, 2492 if every byte were 0xFF and stuffed; pad byte (two if stuffed) and EOI
+    // fit in the 196 bytes left of 2688 = 6 * 64 * 7.  A table never has more symbols than its Annex-K counterpart (12 / 162),
+    // so no header is longer than the Annex-K one: the 1024 bytes and JPEZY_MAX_COMMENT stand.  (static_asserts: jpezy_host_codec.h)
     return 1024 + nmcu * 6 * 64 * 7;
 }
 
-long write_jpeg(const int16_t* coeffs, int W, int H, bool gray, const char* comment, uint8_t* out, size_t cap,
-                std::string* err)
+namespace {
+int check_write_args(const int16_t* coeffs, int W, int H, const char* comment, const uint8_t* out, std::string* err)
 {
     if (!coeffs || !out || W <= 0 || H <= 0 || W > 65535 || H > 65535) {
         if (err) *err = "write_jpeg: bad argument";
@@ -229,9 +238,136 @@ long write_jpeg(const int16_t* coeffs, int W, int H, bool gray, const char* comm
         if (err) *err = "write_jpeg: comment longer than JPEZY_MAX_COMMENT (" + std::to_string(JPEZY_MAX_COMMENT) + " bytes)";
         return JPEZY_E_BADARG;
     }
-    const EncTables& T = enc_tables();
+    return JPEZY_OK;
+}
+
+long write_jpeg_with(const EncTables& T, const HuffTable* tabs, const int16_t* coeffs, int W, int H, bool gray, const char* comment,
+                     uint8_t* out, size_t cap, std::string* err);
+}  // namespace
+
+long write_jpeg(const int16_t* coeffs, int W, int H, bool gray, const char* comment, uint8_t* out, size_t cap,
+                std::string* err)
+{
+    if (int rc = check_write_args(coeffs, W, H, comment, out, err)) return rc;
+    return write_jpeg_with(enc_tables(), nullptr, coeffs, W, H, gray, comment, out, cap, err);
+}
+
+// ---- per-image optimised tables ----
+// The symbols of one block, as put_block emits them (out-of-range values: the clamped symbol, and false).
+namespace {
+inline bool count_block(const int16_t* z, int& pred, unsigned long long* dc, unsigned long long* ac)
+{
+    bool ok = true;
+    const int diff = z[0] - pred;
+    pred = z[0];
+    int di = bit_length((unsigned)(diff < 0 ? -diff : diff));
+    if (di > 11) { ok = false; di = 11; }
+    ++dc[di];
+    int run = 0;
+    for (int n = 1; n < 64; ++n) {
+        const int v = z[n];
+        if (v == 0) { ++run; continue; }
+        ac[0xF0] += (unsigned)(run >> 4);
+        int s = bit_length((unsigned)(v < 0 ? -v : v));
+        if (s > 10) { ok = false; s = 10; }
+        ++ac[((run & 15) << 4) | s];
+        run = 0;
+    }
+    if (run) ++ac[0x00];
+    return ok;
+}
+}  // namespace
+
+bool symbol_histogram(const int16_t* coeffs, int W, int H, bool gray, unsigned long long hist[4][256])
+{
+    static const int16_t kZeroBlock[64] = { 0 };
+    std::memset(hist, 0, sizeof(unsigned long long) * 4 * 256);
+    const size_t nmcu = (size_t)((W + 15) / 16) * (size_t)((H + 15) / 16);
+    const int bpm = gray ? 4 : 6;
+    int pred[3] = { 0, 0, 0 };
+    bool ok = true;
+    for (size_t mcu = 0; mcu < nmcu; ++mcu) {
+        const int16_t* z = coeffs + mcu * (size_t)bpm * 64;
+        for (int i = 0; i < 4; ++i) ok &= count_block(z + i * 64, pred[0], hist[0], hist[2]);
+        ok &= count_block(gray ? kZeroBlock : z + 256, pred[1], hist[1], hist[3]);
+        ok &= count_block(gray ? kZeroBlock : z + 320, pred[2], hist[1], hist[3]);
+    }
+    return ok;
+}
+
+int optimal_table(const unsigned long long freq_in[256], uint8_t bits_out[16], uint8_t vals[256])
+{
+    // a code tree over 257 leaves is at most 256 deep (libjpeg stops at 32, which ~25 million symbols can exceed: depth d takes
+    // only about Fibonacci(d + 2) of them)
+    constexpr int MAXLEN = 256;
+    unsigned long long freq[257];
+    int codesize[257], others[257], bits[MAXLEN + 1];
+    std::memset(bits_out, 0, 16);
+    int nval = 0;
+    for (int i = 0; i < 256; ++i) { freq[i] = freq_in[i]; nval += freq[i] != 0; }
+    if (nval == 0) return 0;
+    freq[256] = 1;                                        // the reserved symbol: no code of all ones (K.2)
+    for (int i = 0; i < 257; ++i) { codesize[i] = 0; others[i] = -1; }
+    for (;;) {                                            // Figure K.1
+        int c1 = -1, c2 = -1;
+        unsigned long long v = ~0ull;
+        for (int i = 0; i <= 256; ++i)                    // least non-zero count; ties: the larger symbol
+            if (freq[i] && freq[i] <= v) { v = freq[i]; c1 = i; }
+        v = ~0ull;
+        for (int i = 0; i <= 256; ++i)                    // the next one
+            if (freq[i] && freq[i] <= v && i != c1) { v = freq[i]; c2 = i; }
+        if (c2 < 0) break;
+        freq[c1] += freq[c2];
+        freq[c2] = 0;
+        for (++codesize[c1]; others[c1] >= 0;) { c1 = others[c1]; ++codesize[c1]; }
+        others[c1] = c2;
+        for (++codesize[c2]; others[c2] >= 0;) { c2 = others[c2]; ++codesize[c2]; }
+    }
+    for (int i = 0; i <= MAXLEN; ++i) bits[i] = 0;        // Figure K.2
+    for (int i = 0; i <= 256; ++i)
+        if (codesize[i]) ++bits[codesize[i]];
+    for (int i = MAXLEN; i > 16; --i)                     // Figure K.3
+        while (bits[i] > 0) {
+            int j = i - 2;
+            while (bits[j] == 0) --j;
+            bits[i] -= 2;
+            ++bits[i - 1];
+            bits[j + 1] += 2;
+            --bits[j];
+        }
+    {
+        int i = 16;
+        while (bits[i] == 0) --i;
+        --bits[i];                                        // the reserved symbol leaves the longest length
+    }
+    for (int l = 1; l <= 16; ++l) bits_out[l - 1] = (uint8_t)bits[l];
+    int p = 0;                                            // Figure K.4: by code size, then ascending value
+    for (int l = 1; l <= MAXLEN; ++l)
+        for (int j = 0; j < 256; ++j)
+            if (codesize[j] == l) vals[p++] = (uint8_t)j;
+    return nval;
+}
+
+long write_jpeg_opt(const int16_t* coeffs, int W, int H, bool gray, const char* comment, uint8_t* out, size_t cap, std::string* err)
+{
+    if (int rc = check_write_args(coeffs, W, H, comment, out, err)) return rc;
+    unsigned long long hist[4][256];
+    if (!symbol_histogram(coeffs, W, H, gray, hist)) {
+        if (err) *err = "write_jpeg: coefficient outside the code tables";
+        return JPEZY_E_FORMAT;
+    }
+    HuffTable tabs[4];
+    for (int k = 0; k < 4; ++k) tabs[k].nval = optimal_table(hist[k], tabs[k].bits, tabs[k].vals);
+    const EncTables T(tabs);
+    return write_jpeg_with(T, tabs, coeffs, W, H, gray, comment, out, cap, err);
+}
+
+namespace {
+long write_jpeg_with(const EncTables& T, const HuffTable* tabs, const int16_t* coeffs, int W, int H, bool gray, const char* comment,
+                     uint8_t* out, size_t cap, std::string* err)
+{
     BitSink o(out, cap);
-    put_header(o, W, H, comment);
+    put_header(o, W, H, comment, tabs);
 
     static const int16_t kZeroBlock[64] = { 0 };
     const size_t nmcu = (size_t)((W + 15) / 16) * (size_t)((H + 15) / 16);
@@ -256,6 +392,7 @@ long write_jpeg(const int16_t* coeffs, int W, int H, bool gray, const char* comm
     }
     return (long)o.size();
 }
+}  // namespace
 
 // ======================================================================================================
 // reader

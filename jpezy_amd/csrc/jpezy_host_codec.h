@@ -17,11 +17,36 @@ long write_jpeg(const int16_t* coeffs, int W, int H, bool gray, const char* comm
 size_t jpeg_bound(int W, int H);
 // false for a comment longer than JPEZY_MAX_COMMENT: every writer refuses it (JPEZY_E_BADARG)
 bool comment_ok(const char* comment);
+// One Huffman table as a DHT segment states it: bits[l - 1] codes of length l, their symbols in vals[0..nval).
+struct HuffTable {
+    uint8_t bits[16];
+    uint8_t vals[256];
+    int nval;
+};
 // the bytes before the entropy-coded segment (SOI .. SOS, 644 with the default comment); 0 if cap is too small or the
-// comment too long
-size_t write_header(int W, int H, const char* comment, uint8_t* out, size_t cap);
-// canonical (code, length) per symbol of the four Annex-K tables in DHT order YDc, CDc, YAc, CAc (for the GPU coder)
-void enc_code_tables(uint16_t code[4][256], uint8_t len[4][256]);
+// comment too long.  tabs: the four tables of the DHT segments in file order YDc, CDc, YAc, CAc (nullptr: Annex K)
+size_t write_header(int W, int H, const char* comment, uint8_t* out, size_t cap, const HuffTable* tabs = nullptr);
+// canonical (code, length) per symbol of four tables in DHT order YDc, CDc, YAc, CAc (for the GPU coder); nullptr: Annex K
+void enc_code_tables(uint16_t code[4][256], uint8_t len[4][256], const HuffTable* tabs = nullptr);
+
+// ---- per-image optimised tables (ITU-T T.81 Annex K.2) ----
+// Code lengths the coder and its scratch sizes rest on, for ANY table optimal_table can return (derivation: jpeg_bound):
+constexpr int kMaxDcCodeBits = 12;      // 12 categories + the reserved symbol = 13 leaves: no leaf deeper than 12
+constexpr int kMaxAcCodeBits = 16;      // Figure K.3
+constexpr int kMaxBlockBits = kMaxDcCodeBits + 11 + 63 * (kMaxAcCodeBits + 10);      // 1661
+constexpr int kMaxMcuBits = 6 * kMaxBlockBits;                                        // 9966
+static_assert(kMaxBlockBits == 1661 && (kMaxBlockBits + 7) / 8 <= 208, "a coded block must fit the 208 bytes the GPU coder's scratch gives it");
+static_assert(kMaxMcuBits == 9966 && 2 * ((kMaxMcuBits + 7) / 8) + 2 + 2 <= 2688, "jpeg_bound: a stuffed MCU, pad byte and EOI within 2688 bytes");
+static_assert(kMaxDcCodeBits + 11 <= 31 && kMaxAcCodeBits + 10 <= 31, "one append of the GPU coder (code + value bits) is at most 31 bits");
+// freq[sym] -> (bits, vals) of the optimal prefix code with no code longer than 16 bits and none of all ones; returns the
+// number of symbols (those with freq != 0).  Exactly Figures K.1 - K.4, every tie in K.1 resolved toward the larger symbol
+// value, working arrays for trees of any depth (256 symbols): a second implementation reproduces it bit for bit.
+int optimal_table(const unsigned long long freq[256], uint8_t bits[16], uint8_t vals[256]);
+// hist[k][sym]: how often the writer emits symbol sym from table k (DHT order) for this frame.  Returns false when a value lies
+// outside the code tables (DC category over 11, |AC| > 1023): counted as the largest size.
+bool symbol_histogram(const int16_t* coeffs, int W, int H, bool gray, unsigned long long hist[4][256]);
+// write_jpeg with the frame's own optimal tables: same coefficients, same decoded pixels, a smaller file
+long write_jpeg_opt(const int16_t* coeffs, int W, int H, bool gray, const char* comment, uint8_t* out, size_t cap, std::string* err);
 
 // What the entropy decoder needs besides jpezy_frame_info: where the scan data start, the raw DHT specifications
 // (slot = tc*4 + th: 0..3 DC, 4..7 AC) and the table selector of each scan component (the reference uses Td for both

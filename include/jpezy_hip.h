@@ -215,11 +215,31 @@ long jpezy_write_jpeg_opt(const int16_t* coeffs, int W, int H, int gray, const c
  */
 int jpezy_huffman_optimal_table(const unsigned long long freq[256], uint8_t bits[16], uint8_t vals[256]);
 /*
+ * jpezy_write_jpeg with restart intervals (ITU-T T.81 B.2.4.4, E.1.4): restart_interval = MCUs per interval, 0..65535, anything
+ * else is JPEZY_E_BADARG.  0: no DRI segment and no RSTn marker -- the bytes of jpezy_write_jpeg (optimize = 0) or
+ * jpezy_write_jpeg_opt (optimize != 0).  Otherwise a DRI segment FF DD 00 04 hi lo stands directly in front of SOS; behind every
+ * interval but the last the bits are padded to a byte with JPEZY_PAD_BIT (the fill the frame's last byte gets: with the default 0 a
+ * padded byte cannot be 0xFF, in a JPEZY_PAD_BIT 1 build a padded 0xFF is stuffed like any other) and the marker FF D0+(k mod 8)
+ * follows interval k, never stuffed; the three DC predictors are zero at the start of every interval.  Nothing follows the last
+ * interval but the usual pad and EOI, so restart_interval >= the MCU count writes the DRI segment and no marker.
+ * optimize != 0: the frame's own tables (Annex K.2) from the symbols THIS scan emits -- the DC difference at an interval's start
+ * is taken against 0, so the counts differ from those of the file without restarts.
+ * The comment may be at most JPEZY_MAX_COMMENT_RESTART bytes when restart_interval > 0.  The GPU coder writes the same bytes with
+ * jpezy_ctx_set_restart_interval.
+ */
+long jpezy_write_jpeg_rst(const int16_t* coeffs, int W, int H, int gray, const char* comment, int restart_interval,
+                          int optimize, uint8_t* out, size_t cap);
+/*
  * The longest comment (bytes before the terminating NUL) any writer accepts: jpezy_write_jpeg[_batch], jpezy_write_jpeg_gpu[_batch,
  * _dev], jpezy_encode_jpeg and jpezy_multi_encode / jpezy_encode_batch_multi all refuse a longer one with JPEZY_E_BADARG.  It is
  * what makes the header fit 1024 bytes: 623 bytes of markers and tables + a COM segment of n + 5 bytes (marker, length, text, NUL).
  */
 #define JPEZY_MAX_COMMENT 396
+/*
+ * With a restart interval (jpezy_ctx_set_restart_interval, jpezy_write_jpeg_rst) the header also holds the six bytes of the DRI
+ * segment, which come out of the comment's room: a longer comment is then JPEZY_E_BADARG.  JPEZY_MAX_COMMENT itself does not change.
+ */
+#define JPEZY_MAX_COMMENT_RESTART 390
 /*
  * A cap that always suffices for a comment of up to JPEZY_MAX_COMMENT bytes: 1024 bytes of header + 2688 bytes per MCU.  The worst
  * MCU codes 4 x 1658 + 2 x 1660 bits (every AC coefficient a 16-bit code + 10 value bits, the DC difference 9 or 11 + 11 bits), i.e.
@@ -229,6 +249,10 @@ int jpezy_huffman_optimal_table(const unsigned long long freq[256], uint8_t bits
  * reserved symbol: 13 leaves) and an AC code at most 16: a block is at most 12 + 11 + 63 x 26 = 1661 bits, an MCU 9966 bits = 1246
  * bytes, 2492 stuffed -- still within 2688; and no table has more symbols than its Annex-K counterpart (12 / 162), so the header is
  * never longer.  The same bound holds (tests/test_huffopt_host.py).
+ * With restart intervals every interval but the last adds at most a pad byte (two if it is 0xFF and stuffed) and the 2-byte RSTn
+ * marker: at the shortest interval of one MCU that is at most 4 bytes per MCU, which together with the frame's own pad and EOI
+ * (4 bytes, once) still fit in the 196 bytes per MCU that 2492 leaves of 2688; the six DRI bytes come out of the comment's room
+ * (JPEZY_MAX_COMMENT_RESTART).  The same bound holds (tests/test_restart_host.py).
  */
 size_t jpezy_jpeg_bound(int W, int H);
 /*
@@ -276,6 +300,22 @@ int jpezy_write_jpeg_gpu_dev(jpezy_ctx* ctx, const int16_t* d_coeffs, int W, int
  * Annex-K tables.  Returns 0 or JPEZY_E_BADARG.
  */
 int jpezy_ctx_set_huffman_optimize(jpezy_ctx* ctx, int on);
+/*
+ * Restart intervals on the GPU path (opt-in; default 0 = none).  With mcus > 0, jpezy_write_jpeg_gpu, jpezy_write_jpeg_gpu_batch,
+ * jpezy_write_jpeg_gpu_dev, jpezy_encode_jpeg and jpezy_encode_jpeg_packed write the bytes of jpezy_write_jpeg_rst(..., mcus,
+ * optimize, ...) with optimize = the context's jpezy_ctx_set_huffman_optimize setting, and jpezy_huffman_histogram_dev counts with
+ * the predictors reset at every interval's start.  Every value 1..65535 is coded on the GPU at every frame size.  The coder's
+ * workgroups never straddle an interval (an interval takes ceil(6 * mcus / 256) of them), so an interval of an MCU row or longer
+ * costs one more launch than no interval (about 10 us on a 4096 x 4096 frame), while short intervals leave most lanes of a workgroup
+ * idle (one MCU per interval: 10 to 15 times the time; DESIGN.md 4.6 has the figures).
+ * jpezy_write_jpeg_gpu_dev stays asynchronous and capturable.  With 0 every byte is what it was.  A comment longer than
+ * JPEZY_MAX_COMMENT_RESTART is refused with JPEZY_E_BADARG while the setting is non-zero.
+ * The multi-GPU handle (jpezy_multi_*, jpezy_encode_batch_multi) owns its contexts and always writes files without restart
+ * intervals.  jpezy_ctx_set_restart_interval returns 0, or JPEZY_E_BADARG for a value outside 0..65535;
+ * jpezy_ctx_restart_interval returns the setting (JPEZY_E_BADARG for a null context).
+ */
+int jpezy_ctx_set_restart_interval(jpezy_ctx* ctx, int mcus);
+int jpezy_ctx_restart_interval(const jpezy_ctx* ctx);
 /*
  * The symbol-counting kernel on its own, asynchronous on `stream`: d_hist[f][k][sym] (device memory, [n_frames][4][256], zeroed
  * here) = how often the coder emits symbol sym from table k (DHT order: 0 YDc, 1 CDc, 2 YAc, 3 CAc) for frame f.  A value outside

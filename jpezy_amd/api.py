@@ -83,6 +83,9 @@ ABI = [
     ("jpezy_huffman_histogram_dev", C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     ("jpezy_huffman_optimal_table", C.c_int, [_vp, _vp, _vp]),
     ("jpezy_write_jpeg_opt", C.c_long, [_vp, C.c_int, C.c_int, C.c_int, C.c_char_p, _vp, C.c_size_t]),
+    ("jpezy_write_jpeg_rst", C.c_long, [_vp, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int, C.c_int, _vp, C.c_size_t]),
+    ("jpezy_ctx_set_restart_interval", C.c_int, [_vp, C.c_int]),
+    ("jpezy_ctx_restart_interval", C.c_int, [_vp]),
     ("jpezy_encode_jpeg", C.c_long, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_char_p, _vp, C.c_size_t]),
     ("jpezy_shard_range", None, [C.c_long, C.c_int, C.c_int, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
     ("jpezy_encode_batch_multi", C.c_int, [C.POINTER(C.c_int), C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p,
@@ -216,6 +219,14 @@ class Context:
         """0: Annex-K tables (default); 1: write_jpeg_gpu, encode_jpeg and encode_jpeg_packed give every frame its own optimal
         Huffman tables (the bytes of write_jpeg(..., optimize=True)); write_jpeg_gpu_dev is refused while it is on."""
         _check(load_library().jpezy_ctx_set_huffman_optimize(self._h, int(on)))
+
+    def set_restart_interval(self, n):
+        """MCUs per restart interval (0..65535; default 0: none) that write_jpeg_gpu[_dev], encode_jpeg and encode_jpeg_packed write:
+        a DRI segment and RSTn markers, the bytes of write_jpeg(..., restart_interval=n); huffman_histogram_dev counts accordingly."""
+        _check(load_library().jpezy_ctx_set_restart_interval(self._h, int(n)))
+
+    def restart_interval(self):
+        return _check(load_library().jpezy_ctx_restart_interval(self._h))
 
     def set_host_chunk_bytes(self, n):
         """bytes of input per chunk of the streaming host-buffer entry points (default 4 MiB)"""
@@ -500,9 +511,10 @@ def optimal_table(freq):
     return bits, vals[:n].copy()
 
 
-def write_jpeg(coeffs, W, H, gray=False, comment=None, optimize=False):
+def write_jpeg(coeffs, W, H, gray=False, comment=None, optimize=False, restart_interval=0):
     """zig-zag int16 coefficients -> the .jpg bytes jpezy_encode writes (header + Huffman + EOI); optimize: with the frame's own
-    optimal Huffman tables instead of Annex K (same coefficients, smaller file)."""
+    optimal Huffman tables instead of Annex K (same coefficients, smaller file); restart_interval: MCUs per restart interval
+    (DRI segment, RSTn markers, predictors reset), 0 for none."""
     lib = load_library()
     coeffs = np.ascontiguousarray(coeffs, dtype=np.int16)
     if coeffs.size != lib.jpezy_coeff_count(W, H, int(gray)):
@@ -511,6 +523,10 @@ def write_jpeg(coeffs, W, H, gray=False, comment=None, optimize=False):
         comment = b"Encoded by JPEZY" if gray else b"Encoded by jpezy"   # ref encode_io.hpp:149,181
     cap = lib.jpezy_jpeg_bound(W, H)
     buf = np.empty(cap, dtype=np.uint8)
+    if restart_interval != 0:
+        n = _check(lib.jpezy_write_jpeg_rst(_np_ptr(coeffs), W, H, int(gray), comment, int(restart_interval), int(bool(optimize)),
+                                            _np_ptr(buf), cap))
+        return buf[:n].tobytes()
     fn = lib.jpezy_write_jpeg_opt if optimize else lib.jpezy_write_jpeg
     n = _check(fn(_np_ptr(coeffs), W, H, int(gray), comment, _np_ptr(buf), cap))
     return buf[:n].tobytes()

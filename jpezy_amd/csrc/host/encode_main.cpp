@@ -1,8 +1,10 @@
-// jpezy_encode <input.ppm> ( <output.(jpeg | jpg) [OPT: --gray] [OPT: --optimize]> | <output.ppm> | --debug )
+// jpezy_encode <input.ppm> ( <output.(jpeg | jpg) [OPT: --gray] [OPT: --optimize] [OPT: --restart=N]> | <output.ppm> | --debug )
 // Same argv rules, transcript and exit codes as the reference's src/encoder/main.cpp; the codec underneath is
 // the MI355X path (jpezy_encoder.hpp).
 // Extension (not in the reference):  --optimize (single-file mode only, either side of --gray) writes the file with its own optimal
 // Huffman tables (jpezy_ctx_set_huffman_optimize): same pixels, fewer bytes.
+// Extension (not in the reference):  --restart=N (single-file mode only, one token, anywhere behind the output name) writes restart
+// intervals of N MCUs, 0..65535 (jpezy_ctx_set_restart_interval); a malformed N is a usage error.
 // Extension (not in the reference):  jpezy_encode --gpus N [--gray] <in1.ppm> <out1.jpg> [<in2.ppm> <out2.jpg> ...]
 // encodes a list of files on up to N GPUs of this node through jpezy_encode_batch_multi: runs of consecutive inputs of one size
 // form a batch, a batch is sharded over the GPUs frame by frame.
@@ -93,12 +95,37 @@ int batch_main(const int argc, const char* argv[])
     return EXIT_SUCCESS;
 }
 
+// "--restart=N" with N a decimal number in 0..65535: N; anything else that starts like it: -1
+int parse_restart(std::string_view tok)
+{
+    tok.remove_prefix(std::string_view("--restart=").size());
+    if (tok.empty() || tok.size() > 5) return -1;
+    int n = 0;
+    for (const char ch : tok) {
+        if (ch < '0' || ch > '9') return -1;
+        n = n * 10 + (ch - '0');
+    }
+    return n <= 65535 ? n : -1;
+}
+
 }  // namespace
 
-int main(const int argc, const char* argv[])
+int main(const int argc_in, const char* argv_in[])
 {
-    if (argc >= 3 && std::string_view(argv[1]) == "--gpus") return batch_main(argc, argv);
-    if (argc < 3) return disp_error();
+    if (argc_in >= 3 && std::string_view(argv_in[1]) == "--gpus") return batch_main(argc_in, argv_in);
+    if (argc_in < 3) return disp_error();
+    // the one --restart=N token is taken out; what is left is read as before
+    std::vector<const char*> args(argv_in, argv_in + argc_in);
+    int restart = 0;
+    for (std::size_t i = 3; i < args.size(); ++i)
+        if (std::string_view(args[i]).rfind("--restart=", 0) == 0) {
+            restart = parse_restart(args[i]);
+            if (restart < 0) return disp_error();
+            args.erase(args.begin() + static_cast<std::ptrdiff_t>(i));
+            break;
+        }
+    const int argc = static_cast<int>(args.size());
+    const char* const* argv = args.data();
 
     Mode m1 = Mode::UD, m2 = Mode::UD;
     bool optimize = false;
@@ -134,6 +161,8 @@ int main(const int argc, const char* argv[])
         if (m1 == Mode::JPEG) {
             if (optimize && jpezy_ctx_set_huffman_optimize(jpezy::detail::device_context(), 1) != JPEZY_OK)
                 throw std::runtime_error(std::string("jpezy_ctx_set_huffman_optimize: ") + jpezy_hip_last_error());
+            if (restart && jpezy_ctx_set_restart_interval(jpezy::detail::device_context(), restart) != JPEZY_OK)
+                throw std::runtime_error(std::string("jpezy_ctx_set_restart_interval: ") + jpezy_hip_last_error());
             std::ofstream ofs(argv[2], std::ios::binary);
             if (m2 == Mode::GRAY) ofs << (pnm | jpezy::to_jpeg(argv[2]) | jpezy::gray_scale);
             else ofs << (pnm | jpezy::to_jpeg(argv[2]));

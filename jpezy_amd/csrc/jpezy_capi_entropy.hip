@@ -69,8 +69,12 @@ int ensure_code_tables(jpezy_ctx* c)
     return JPEZY_OK;
 }
 
-void make_job(jpezy_dev::entropy::Job& job, const int16_t* d_coeffs, int W, int H, int gray, int F, const jpezy_dev::entropy::CodeTables* tables)
+// restart: the context's setting; an interval that holds the whole frame changes the header alone, so the device is told of none
+void make_job(jpezy_dev::entropy::Job& job, const int16_t* d_coeffs, int W, int H, int gray, int F, const jpezy_dev::entropy::CodeTables* tables,
+              int restart)
 {
+    const size_t n_mcu = (size_t)jpezy_mcu_cols(W) * jpezy_mcu_rows(H);
+    job.restart = restart > 0 && (size_t)restart < n_mcu ? (unsigned)restart : 0u;
     job.coeffs = d_coeffs;
     job.coeffs_per_frame = jpezy_coeff_count(W, H, gray);
     job.tables = tables;
@@ -78,6 +82,20 @@ void make_job(jpezy_dev::entropy::Job& job, const int16_t* d_coeffs, int W, int 
     job.bpm = gray ? 4 : 6;
     job.n_frames = F;
     job.tables_stride = 0;
+}
+
+// with a restart interval the six DRI bytes come out of the comment's room (JPEZY_MAX_COMMENT_RESTART)
+int check_restart_comment(const jpezy_ctx* c, const char* comment, const char* who)
+{
+    if (jpezy_host::restart_ok(c->restart_interval, comment)) return JPEZY_OK;
+    return set_err(JPEZY_E_BADARG, std::string(who) + ": with a restart interval the comment may be at most JPEZY_MAX_COMMENT_RESTART (" +
+                                       std::to_string(JPEZY_MAX_COMMENT_RESTART) + " bytes)");
+}
+
+// worst-case bytes of a frame's unstuffed stream: 208 per block, and a pad byte behind every restart interval
+size_t worst_stream_bytes(size_t nblk, unsigned restart)
+{
+    return nblk * 208 + (restart ? jpezy_dev::entropy::restart_intervals(nblk, restart) : 0);
 }
 
 // frames per pass with per-image tables: a frame's table image is 10 KB
@@ -92,16 +110,22 @@ int entropy_chunk(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H, int gray,
     const size_t nmcu = (size_t)jpezy_mcu_cols(W) * jpezy_mcu_rows(H);
     const size_t nblk = nmcu * 6;
     E::Job job;
-    make_job(job, d_coeffs, W, H, gray, F, c->d_codes.as<E::CodeTables>());
+    make_job(job, d_coeffs, W, H, gray, F, c->d_codes.as<E::CodeTables>(), c->restart_interval);
     const bool optimize = c->huff_optimize != 0;
+    const unsigned rst = job.restart;
 
     // every block is coded once, into the stream of its tile (256 coded blocks of a frame); worst case 208 bytes per block
-    const size_t tpf = E::tiles256(nblk), nt = tpf * (size_t)F, piece = E::assemble_piece_bytes(), chunk = E::chunk_bytes();
-    const size_t u_stride = (nblk * 208 + 8 + piece - 1) / piece * piece, ft_stride = u_stride / piece;
+    // (restart intervals: a tile never straddles an interval, so there are more of them; their streams lie where the blocks' would)
+    const size_t tpf = E::job_tiles(nblk, rst), nt = tpf * (size_t)F, piece = E::assemble_piece_bytes(), chunk = E::chunk_bytes();
+    const size_t u_stride = (worst_stream_bytes(nblk, rst) + 8 + piece - 1) / piece * piece, ft_stride = u_stride / piece;
     const size_t nchunks = u_stride / chunk * F;
-    const bool self = E::assemble_scans_tiles_itself(tpf);
+    const bool self = !rst && E::assemble_scans_tiles_itself(tpf);
     if (int rc = c->e_tt.reserve(nt * sizeof(uint32_t))) return rc;                          // tile totals (bits)
-    if (int rc = c->e_S.reserve(nt * E::tile_stream_bytes())) return rc;                     // tile streams
+    if (int rc = c->e_S.reserve(E::tiles256(nblk) * (size_t)F * E::tile_stream_bytes())) return rc;   // tile streams
+    if (rst) {
+        if (int rc = c->e_rpad.reserve(E::restart_intervals(nblk, rst) * F * sizeof(unsigned long long))) return rc;   // pads in front of an interval
+        if (int rc = c->e_mk.reserve(nchunks * sizeof(unsigned long long))) return rc;       // markers behind a chunk's bytes
+    }
     if (int rc = c->e_U.reserve(u_stride * F)) return rc;                                    // unstuffed streams
     if (int rc = c->e_cnt.reserve(nchunks * sizeof(uint32_t))) return rc;                    // 0xFF bytes: per chunk inside its piece,
     if (int rc = c->e_fft.reserve(ft_stride * F * sizeof(uint32_t))) return rc;              //             per piece
@@ -145,12 +169,20 @@ int entropy_chunk(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H, int gray,
         job.tables_stride = 1;
     }
     HIP_TRY(E::launch_code_tiles(job, (uint32_t*)c->e_S.p, (uint32_t*)c->e_tt.p, d_status, s));
+    if (rst) {
+        HIP_TRY(E::launch_restart_bases(job, (const uint32_t*)c->e_tt.p, (unsigned long long*)c->e_base.p, (unsigned long long*)c->e_rpad.p,
+                                        d_bytes, (uint32_t*)c->e_ft.p, (unsigned)ft_stride, d_status, nullptr, s));
+        HIP_TRY(E::launch_assemble_restart(job, (const uint32_t*)c->e_S.p, (const uint32_t*)c->e_tt.p, (const unsigned long long*)c->e_base.p,
+                                           d_bytes, (const uint32_t*)c->e_ft.p, (unsigned)ft_stride, (uint32_t*)c->e_U.p, u_stride / 4,
+                                           (uint32_t*)c->e_cnt.p, (uint32_t*)c->e_fft.p, (unsigned long long*)c->e_mk.p, s));
+    } else {
     if (!self)
         HIP_TRY(E::launch_tile_bases((const uint32_t*)c->e_tt.p, (unsigned)tpf, F, (unsigned long long*)c->e_base.p, d_bytes,
                                      (uint32_t*)c->e_ft.p, (unsigned)ft_stride, d_status, nullptr, s));
     HIP_TRY(E::launch_assemble((const uint32_t*)c->e_S.p, (const uint32_t*)c->e_tt.p, (const unsigned long long*)c->e_base.p, d_bytes,
                                (const uint32_t*)c->e_ft.p, (unsigned)ft_stride, (unsigned)tpf, F, (uint32_t*)c->e_U.p, u_stride / 4,
                                (uint32_t*)c->e_cnt.p, (uint32_t*)c->e_fft.p, d_status, nullptr, s, optimize));
+    }
     HIP_TRY(E::launch_ff_frame_totals((const uint32_t*)c->e_fft.p, d_bytes, u_stride / 4, F, d_fftot, s));
     std::vector<unsigned long long> nbytes(F), fftot(F);
     std::vector<unsigned> status(F);
@@ -159,14 +191,16 @@ int entropy_chunk(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H, int gray,
     HIP_TRY(hipMemcpyAsync(fftot.data(), d_fftot, sizeof(unsigned long long) * F, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
 
-    // 3. byte stuffing into a buffer sized from the actual lengths
+    // 3. byte stuffing into a buffer sized from the actual lengths (fftot: the bytes stuffing adds -- with restart intervals the markers too)
     unsigned long long max_out = 0;
     for (int f = 0; f < F; ++f)
         if (nbytes[f] + fftot[f] > max_out) max_out = nbytes[f] + fftot[f];
     const size_t o_stride = ((size_t)max_out + 2 + 63) / 64 * 64;
     if (int rc = c->e_out.reserve(o_stride * F)) return rc;
+    E::FilePlan stuff_plan;
+    if (rst) stuff_plan.markers = (const unsigned long long*)c->e_mk.p;
     HIP_TRY(E::launch_stuff((const uint32_t*)c->e_U.p, u_stride / 4, d_bytes, F, (const uint32_t*)c->e_cnt.p, (const uint32_t*)c->e_fft.p,
-                            (uint8_t*)c->e_out.p, o_stride, E::FilePlan{}, s));
+                            (uint8_t*)c->e_out.p, o_stride, stuff_plan, s));
 
     // 4. header + entropy-coded segment + EOI into the caller's buffers.  One device-to-host copy of all streams into a
     //    pinned staging buffer (per-frame copies into pageable memory cost more than the kernels for small frames).
@@ -179,7 +213,7 @@ int entropy_chunk(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H, int gray,
         for (int f = f0; f < F; f += step) {
             uint8_t* dst = out + (size_t)f * cap;
             if (status[f]) { sizes[f] = JPEZY_E_FORMAT; failed.store(1); continue; }
-            const size_t hdr = jpezy_host::write_header(W, H, comment, dst, cap, optimize ? &tabs[(size_t)f * 4] : nullptr);
+            const size_t hdr = jpezy_host::write_header(W, H, comment, dst, cap, optimize ? &tabs[(size_t)f * 4] : nullptr, c->restart_interval);
             const size_t body = (size_t)(nbytes[f] + fftot[f]);
             if (!hdr || hdr + body + 2 > cap) { sizes[f] = JPEZY_E_NOSPACE; failed.store(1); continue; }
             std::memcpy(dst + hdr, c->e_pinned.p + (size_t)f * o_stride, body);
@@ -209,6 +243,7 @@ int jpezy_write_jpeg_gpu_dev(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H
     if (!d_coeffs || !d_out || !d_sizes) return set_err(JPEZY_E_BADARG, "write_jpeg_gpu_dev: null pointer");
     if (!aligned16(d_coeffs)) return set_err(JPEZY_E_BADARG, "write_jpeg_gpu_dev: d_coeffs must be 16-byte aligned");
     if (int rc = check_comment(comment, "write_jpeg_gpu_dev")) return rc;
+    if (int rc = check_restart_comment(c, comment, "write_jpeg_gpu_dev")) return rc;
     if (c->huff_optimize)      // (before anything is enqueued or cached: the context is left as it was)
         return set_err(JPEZY_E_UNSUPPORTED, "write_jpeg_gpu_dev: per-image Huffman tables are built on the host and this call is asynchronous; "
                                             "use jpezy_write_jpeg_gpu[_batch] or jpezy_ctx_set_huffman_optimize(ctx, 0)");
@@ -216,9 +251,9 @@ int jpezy_write_jpeg_gpu_dev(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H
     if (int rc = ensure_code_tables(c)) return rc;
     hipStream_t s = (hipStream_t)stream;
     // header bytes: cached on the device per (W, H, comment) -- uploaded outside any capture on first use; 1024 bytes hold the
-    // header with the longest comment allowed (JPEZY_MAX_COMMENT)
+    // header with the longest comment allowed (JPEZY_MAX_COMMENT; with a DRI segment JPEZY_MAX_COMMENT_RESTART)
     uint8_t hdr[1024];
-    const size_t hdr_len = jpezy_host::write_header(W, H, comment, hdr, sizeof hdr);
+    const size_t hdr_len = jpezy_host::write_header(W, H, comment, hdr, sizeof hdr, nullptr, c->restart_interval);
     if (!hdr_len) return set_err(JPEZY_E_BADARG, "write_jpeg_gpu_dev: comment too long");
     if (c->e_hdr_len != hdr_len || std::memcmp(c->e_hdr_host, hdr, hdr_len)) {
         if (int rc = c->e_hdr.reserve(sizeof hdr)) return rc;
@@ -233,19 +268,24 @@ int jpezy_write_jpeg_gpu_dev(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H
     // worst case per block: 64 x (16-bit code + 10 value bits) = 208 bytes; whole 16 KB pieces (one workgroup of the
     // assembling / stuffing kernels each)
     const size_t piece = E::assemble_piece_bytes();
-    const size_t u_stride = (nblk * 208 + 8 + piece - 1) / piece * piece;
+    const unsigned rst = c->restart_interval > 0 && (size_t)c->restart_interval < nmcu ? (unsigned)c->restart_interval : 0u;   // (make_job)
+    const size_t u_stride = (worst_stream_bytes(nblk, rst) + 8 + piece - 1) / piece * piece;
     // frames per pass: worst-case streams below ~1 GiB, and at most 65535 (the frame index is a grid dimension)
     const int per = (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>((size_t)n_frames, kMaxFramesPerLaunch), ((size_t)1 << 30) / u_stride));
     const size_t cpf = jpezy_coeff_count(W, H, gray);
-    const size_t tpf = E::tiles256(nblk);                           // tiles of one frame (a tile never straddles frames)
-    const bool self = E::assemble_scans_tiles_itself(tpf);
+    const size_t tpf = E::job_tiles(nblk, rst);                     // tiles of one frame (a tile never straddles frames, nor restart intervals)
+    const bool self = !rst && E::assemble_scans_tiles_itself(tpf);
     for (int f0 = 0; f0 < n_frames; f0 += per) {
         const int F = std::min(per, n_frames - f0);
         const size_t nchunks = u_stride / chunk * F, nt = tpf * F, nct = E::tiles256(nchunks);
         E::Job job;
-        make_job(job, d_coeffs + (size_t)f0 * cpf, W, H, gray, F, c->d_codes.as<E::CodeTables>());
+        make_job(job, d_coeffs + (size_t)f0 * cpf, W, H, gray, F, c->d_codes.as<E::CodeTables>(), c->restart_interval);
         if (int rc = c->e_tt.reserve(nt * sizeof(uint32_t))) return rc;
-        if (int rc = c->e_S.reserve(nt * E::tile_stream_bytes())) return rc;
+        if (int rc = c->e_S.reserve(E::tiles256(nblk) * (size_t)F * E::tile_stream_bytes())) return rc;
+        if (rst) {
+            if (int rc = c->e_rpad.reserve(E::restart_intervals(nblk, rst) * F * sizeof(unsigned long long))) return rc;
+            if (int rc = c->e_mk.reserve(nchunks * sizeof(unsigned long long))) return rc;
+        }
         if (!self) {
             if (int rc = c->e_base.reserve((tpf + 1) * F * sizeof(unsigned long long))) return rc;
             if (int rc = c->e_ft.reserve(u_stride / piece * F * sizeof(uint32_t))) return rc;
@@ -267,6 +307,14 @@ int jpezy_write_jpeg_gpu_dev(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H
         // the coder may have raised per-frame error flags that only their consumer (tile_bases / assemble) clears: if the call ends
         // between the two, the flags are cleared here so that they do not leak into the context's next call
         hipError_t e_mid = hipSuccess;
+        if (rst) {      // one launch more than a frame without intervals that scans its tiles itself: the offsets need the pads
+            e_mid = E::launch_restart_bases(job, (const uint32_t*)c->e_tt.p, (unsigned long long*)c->e_base.p, (unsigned long long*)c->e_rpad.p,
+                                            d_bytes, (uint32_t*)c->e_ft.p, (unsigned)(u_stride / piece), d_status, d_latched, s);
+            if (e_mid == hipSuccess)
+                e_mid = E::launch_assemble_restart(job, (const uint32_t*)c->e_S.p, (const uint32_t*)c->e_tt.p, (const unsigned long long*)c->e_base.p,
+                                                   d_bytes, (const uint32_t*)c->e_ft.p, (unsigned)(u_stride / piece), (uint32_t*)c->e_U.p,
+                                                   u_stride / 4, (uint32_t*)c->e_cnt.p, (uint32_t*)c->e_fft.p, (unsigned long long*)c->e_mk.p, s);
+        } else {
         if (!self)
             e_mid = E::launch_tile_bases((const uint32_t*)c->e_tt.p, (unsigned)tpf, F, (unsigned long long*)c->e_base.p, d_bytes,
                                          (uint32_t*)c->e_ft.p, (unsigned)(u_stride / piece), d_status, d_latched, s);
@@ -274,6 +322,7 @@ int jpezy_write_jpeg_gpu_dev(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H
             e_mid = E::launch_assemble((const uint32_t*)c->e_S.p, (const uint32_t*)c->e_tt.p, (const unsigned long long*)c->e_base.p, d_bytes,
                                        (const uint32_t*)c->e_ft.p, (unsigned)(u_stride / piece), (unsigned)tpf, F, (uint32_t*)c->e_U.p,
                                        u_stride / 4, (uint32_t*)c->e_cnt.p, (uint32_t*)c->e_fft.p, d_status, d_latched, s);
+        }
         if (e_mid != hipSuccess) {
             (void)hipMemsetAsync(d_status, 0, sizeof(unsigned) * (size_t)F, s);
             return hip_err(e_mid, "entropy stage (tile offsets / assembly)");
@@ -283,6 +332,7 @@ int jpezy_write_jpeg_gpu_dev(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H
         plan.hdr_len = hdr_len;
         plan.latched = d_latched;
         plan.sizes = d_sizes + f0;
+        if (rst) plan.markers = (const unsigned long long*)c->e_mk.p;
         HIP_TRY(E::launch_stuff((const uint32_t*)c->e_U.p, u_stride / 4, d_bytes, F, (const uint32_t*)c->e_cnt.p, (const uint32_t*)c->e_fft.p,
                                 d_out + (size_t)f0 * out_stride, out_stride, plan, s));
     }
@@ -295,11 +345,12 @@ try {
     if (int rc = jpezy_internal_check_dims(c, W, H, n_frames)) return rc;
     if (!d_coeffs || !out || !sizes) return set_err(JPEZY_E_BADARG, "write_jpeg_gpu: null pointer");
     if (int rc = check_comment(comment, "write_jpeg_gpu")) return rc;
+    if (int rc = check_restart_comment(c, comment, "write_jpeg_gpu")) return rc;
     HIP_TRY(hipSetDevice(c->device));
     if (int rc = ensure_code_tables(c)) return rc;
     const size_t nblk = (size_t)jpezy_mcu_cols(W) * jpezy_mcu_rows(H) * 6;
     // chunk the batch so that the worst-case unstuffed streams (208 bytes per block) stay below ~1 GiB
-    const size_t worst = nblk * 208 + 4096;
+    const size_t worst = nblk * 208 + nblk / 6 + 4096;             // (a pad byte behind every restart interval, at the most one per MCU)
     int per = (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>((size_t)n_frames, kMaxFramesPerLaunch), ((size_t)1 << 30) / worst));   // 65535: grid dimension
     if (c->huff_optimize) per = std::min(per, kMaxOptFramesPerPass);
     bool any_failed = false;
@@ -331,6 +382,20 @@ int jpezy_ctx_set_huffman_optimize(jpezy_ctx* c, int on)
     return JPEZY_OK;
 }
 
+int jpezy_ctx_set_restart_interval(jpezy_ctx* c, int mcus)
+{
+    if (!c) return set_err(JPEZY_E_BADARG, "null context");
+    if (mcus < 0 || mcus > 65535) return set_err(JPEZY_E_BADARG, "restart interval: 0 (none) or 1..65535 MCUs (16-bit DRI field)");
+    c->restart_interval = mcus;
+    return JPEZY_OK;
+}
+
+int jpezy_ctx_restart_interval(const jpezy_ctx* c)
+{
+    if (!c) return set_err(JPEZY_E_BADARG, "null context");
+    return c->restart_interval;
+}
+
 int jpezy_huffman_histogram_dev(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H, int gray, int n_frames, unsigned long long* d_hist,
                                 void* stream)
 {
@@ -347,7 +412,7 @@ int jpezy_huffman_histogram_dev(jpezy_ctx* c, const int16_t* d_coeffs, int W, in
         unsigned long long* h = d_hist + (size_t)f0 * 4 * 256;
         HIP_TRY(hipMemsetAsync(h, 0, (size_t)F * 4 * 256 * sizeof(unsigned long long), s));
         E::Job job;
-        make_job(job, d_coeffs + (size_t)f0 * cpf, W, H, gray, F, nullptr);
+        make_job(job, d_coeffs + (size_t)f0 * cpf, W, H, gray, F, nullptr, c->restart_interval);
         HIP_TRY(E::launch_symbol_histogram(job, h, (unsigned*)c->e_hstat.p, s));
     }
     return JPEZY_OK;
@@ -363,6 +428,16 @@ long jpezy_write_jpeg_opt(const int16_t* coeffs, int W, int H, int gray, const c
 try {
     std::string err;
     const long n = jpezy_host::write_jpeg_opt(coeffs, W, H, gray != 0, comment, out, cap, &err);
+    if (n < 0) g_err = err;
+    return n;
+}
+JPEZY_CATCH
+
+long jpezy_write_jpeg_rst(const int16_t* coeffs, int W, int H, int gray, const char* comment, int restart_interval, int optimize,
+                          uint8_t* out, size_t cap)
+try {
+    std::string err;
+    const long n = jpezy_host::write_jpeg_rst(coeffs, W, H, gray != 0, comment, restart_interval, optimize != 0, out, cap, &err);
     if (n < 0) g_err = err;
     return n;
 }

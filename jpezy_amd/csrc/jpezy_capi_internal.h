@@ -155,6 +155,8 @@ struct jpezy_ctx {
     int huff_optimize = 0;         // 1: the host-delivered entropy entry points build every frame's own Huffman tables (jpezy_ctx_set_huffman_optimize)
     DevBuf e_hist, e_hstat;        // per-image tables: symbol counts [frames][4][256] uint64; error flags of jpezy_huffman_histogram_dev (never read)
     DevBuf e_codes_opt;            // ... and the frames' CodeTables images [frames]
+    int restart_interval = 0;      // MCUs per restart interval the entropy entry points write (jpezy_ctx_set_restart_interval); 0: none
+    DevBuf e_rpad, e_mk;           // restart intervals: pad bits in front of every interval (uint64), RSTn markers behind a chunk's bytes (uint64 mask)
     PinBuf e_hist_pin, e_codes_pin;    // pinned host twins of the two
     DevBuf h_scan, h_U, h_cnt, h_off, h_state, h_setup, h_small, h_dc, h_dcbuf;   // GPU Huffman decoder (jpezy_huffdec.hip)
     std::vector<uint8_t> h_setup_host;  // the device tables h_setup holds (jpezy_read_jpeg_gpu uploads them only when they change)

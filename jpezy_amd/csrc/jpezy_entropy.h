@@ -26,9 +26,32 @@ struct Job {
     unsigned blocks_per_frame;    // coded blocks: 6 per MCU (gray: the two chroma blocks are coded as zero blocks)
     int bpm;                      // stored blocks per MCU: 6 colour, 4 gray
     int n_frames;
+    unsigned restart = 0;         // MCUs per restart interval that the DEVICE acts on: 0 for none, and 0 too for an interval that holds
+                                  // the whole frame (no marker, no reset: only the header differs, and the host writes that)
 };
 
 inline size_t tiles256(size_t n) { return (n + 255) / 256; }
+
+// Tiles of a frame with restart intervals (Job::restart != 0): a tile never straddles an interval.  Every interval starts a tile of
+// its own and takes restart_tpi() tiles, all of 256 blocks but its last; the frame's last interval may hold fewer MCUs and so fewer
+// tiles.  Tile t: interval t / tpi, blocks [first, first + count) of the frame with first = (t / tpi) * 6 * restart + (t % tpi) * 256.
+__host__ __device__ inline unsigned restart_tpi(unsigned restart) { return (restart * 6u + 255u) / 256u; }
+__host__ __device__ inline unsigned restart_tile_first(unsigned t, unsigned restart)
+{
+    const unsigned tpi = restart_tpi(restart);
+    return (t / tpi) * (restart * 6u) + (t % tpi) * 256u;
+}
+inline size_t restart_intervals(size_t blocks_per_frame, unsigned restart) { return (blocks_per_frame / 6 + restart - 1) / restart; }
+inline size_t restart_tiles(size_t blocks_per_frame, unsigned restart)
+{
+    const size_t ni = restart_intervals(blocks_per_frame, restart);
+    return (ni - 1) * restart_tpi(restart) + tiles256(blocks_per_frame - (ni - 1) * restart * 6u);
+}
+// tiles of a frame, either way
+inline size_t job_tiles(size_t blocks_per_frame, unsigned restart)
+{
+    return restart ? restart_tiles(blocks_per_frame, restart) : tiles256(blocks_per_frame);
+}
 
 // device-resident form of launch_stuff: whole files (header, stuffed stream, EOI), sizes and per-frame verdicts on the device
 struct FilePlan {
@@ -36,6 +59,8 @@ struct FilePlan {
     size_t hdr_len = 0;
     const unsigned* latched = nullptr;  // [frames] error flags as latched by launch_tile_bases
     long long* sizes = nullptr;         // [frames] file size, or JPEZY_E_FORMAT (-5) / JPEZY_E_NOSPACE (-6)
+    const unsigned long long* markers = nullptr;   // restart intervals: launch_assemble_restart's marker masks [frame][chunk]; selects the
+                                                   // stuffing kernel that places RSTn markers
 };
 
 size_t scan_tmp_elems(size_t n);  // uint64 scratch elements launch_scan_u32 needs for n inputs
@@ -72,9 +97,24 @@ hipError_t launch_stuff(const uint32_t* U, size_t u_stride_words, const unsigned
 hipError_t launch_ff_frame_totals(const uint32_t* ff_tile_total, const unsigned long long* bytes, size_t u_stride_words, int n_frames,
                                   unsigned long long* dst, hipStream_t s);
 
+// Restart intervals (Job::restart != 0; tiles as restart_tiles() lays them out, S and tile_total from launch_code_tiles with the same job).
+// launch_restart_bases: frame-relative bit offsets base[frame][tiles + 1] in which every interval but the last ends on a byte
+// (pad[frame][intervals] is its scratch), bytes[frame], first_tile as launch_tile_bases; latches and clears status likewise.
+// launch_assemble_restart: U and the two-level prefix sums as launch_assemble, where the counts are the bytes the stuffing pass
+// ADDS: one per 0xFF byte and two per RSTn marker (a marker belongs to the chunk that holds the last byte of its interval);
+// markers[frame][chunk]: bit j = a marker follows byte j of the chunk; the top three bits of ff_loc hold the number (mod 8) of the
+// chunk's first marker.  launch_stuff places the markers when FilePlan::markers is set.
+hipError_t launch_restart_bases(const Job& job, const uint32_t* tile_total, unsigned long long* base, unsigned long long* pad,
+                                unsigned long long* bytes, uint32_t* first_tile, unsigned ft_stride, unsigned* status, unsigned* latched,
+                                hipStream_t s);
+hipError_t launch_assemble_restart(const Job& job, const uint32_t* S, const uint32_t* tile_total, const unsigned long long* base,
+                                   const unsigned long long* bytes, const uint32_t* first_tile, unsigned ft_stride, uint32_t* U,
+                                   size_t u_stride_words, uint32_t* loc, uint32_t* ff_tile_total, unsigned long long* markers, hipStream_t s);
+
 // Symbol statistics for per-image optimised tables (jpezy_huffstat.hip): hist[frame][k][sym] += the number of times the coder
 // emits symbol sym from table k (DHT order: 0 YDc, 1 CDc, 2 YAc, 3 CAc) for the frame -- what code_block sees, out-of-range values
 // counted as the clamped symbol with status[frame] |= 1.  hist must be zero before the launch (job.tables is not read).
+// job.restart: the DC predictors are zero at every interval's start, as the coder has them.
 hipError_t launch_symbol_histogram(const Job& job, unsigned long long* hist, unsigned* status, hipStream_t s);
 
 }  // namespace entropy

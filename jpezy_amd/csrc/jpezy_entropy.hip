@@ -2,6 +2,8 @@
 // zig-zagged coefficients, bit packing, 0xFF00 byte stuffing.  Same bytes as jpezy_host::write_jpeg / the reference's
 // encoder::encode_huffman + bofstream (ref encoder/jpezy_encoder.hpp:174-242): MSB-first bits, DC predictors per
 // component never reset, EOB only when a block ends in zeros, ZRL for runs over 15, zero pad bits before EOI.
+// With restart intervals (Job::restart, not in the reference; jpezy_host::write_jpeg_rst is the host twin) the predictors are zero at
+// every interval's start, every interval but the last is padded to a byte and an RSTn marker follows it: "restart intervals" below.
 //
 // What is serial in the reference is the bit cursor and pre_DC[3].  Neither is a true dependency:
 //   * pre_DC of a block is the DC of the previous block of the same component, which is simply read;
@@ -16,6 +18,10 @@
 //   4. scan                of the 0xFF tile totals (one workgroup for a few thousand)
 //   5. stuff_kernel        copies U to the output inserting 0x00 after every 0xFF; in the device-resident form it also
 //                          decides fit / size, writes EOI and copies the JFIF header (workgroup 0 of each frame)
+// Restart intervals: 1. the RST instance of code_tiles_kernel (tiles that never straddle an interval), 2. restart_bases_kernel (offsets
+// with every interval ending on a byte) at every frame size, 3. assemble_restart_kernel (any number of tiles per chunk; the counts
+// include two bytes per marker; the markers behind a chunk's bytes as a 64-bit mask), 5. the RST instance of stuff_kernel (inserts
+// them).  One launch more than a frame that scans its tiles itself; without intervals no kernel and no launch is another.
 // (Round 1 and the first half of round 2 coded every block twice -- lengths, scan, then bits at the scanned offset with
 // atomicOr into a zeroed buffer -- in 22, then 9 launches: 174 / 100 us per 4096x4096 frame; see DESIGN.md.)
 #include <hip/hip_runtime.h>
@@ -257,14 +263,29 @@ struct DirectWriter {
     }
 };
 
+// RST (Job::restart != 0): the tiles are those of restart_tiles() -- a tile never straddles a restart interval, so an interval's bits
+// are the bits of whole tiles, and the predictors of an interval's first MCU (lanes 0..5 of its first tile) are zero.  A tile's
+// stream starts at 52 words per block in front of it in the frame, which is where the plain layout has it too.
+template <bool RST>
 __global__ __launch_bounds__(WG) void code_tiles_kernel(Job job, uint32_t* S, uint32_t* tile_total, unsigned* status)
 {
     __shared__ LdsTables L;
     __shared__ __attribute__((aligned(16))) char tile[WG * ROW];
     const unsigned tid = threadIdx.x, frame = blockIdx.y;
     load_tables(L, job.tables + (size_t)frame * job.tables_stride);
-    const unsigned nblk = job.blocks_per_frame, g0 = blockIdx.x * (unsigned)WG;
-    const unsigned nb = nblk - g0 < (unsigned)WG ? nblk - g0 : (unsigned)WG;          // coded blocks of this tile
+    const unsigned nblk = job.blocks_per_frame;
+    unsigned g0, nb;                                                                  // first coded block of this tile, and how many
+    bool interval_start = false;
+    if constexpr (RST) {
+        const unsigned bpi = job.restart * 6u, tpi = restart_tpi(job.restart), iv = blockIdx.x / tpi, j = blockIdx.x - iv * tpi;
+        const unsigned i0 = iv * bpi, ilen = nblk - i0 < bpi ? nblk - i0 : bpi;       // the interval's blocks: [i0, i0 + ilen)
+        g0 = i0 + j * (unsigned)WG;
+        nb = ilen - j * (unsigned)WG < (unsigned)WG ? ilen - j * (unsigned)WG : (unsigned)WG;
+        interval_start = j == 0;
+    } else {
+        g0 = blockIdx.x * (unsigned)WG;
+        nb = nblk - g0 < (unsigned)WG ? nblk - g0 : (unsigned)WG;
+    }
     const int16_t* fc = job.coeffs + (size_t)frame * job.coeffs_per_frame;
     // this lane's block: its place in global memory (nullptr: a zero chroma block of gray mode) and its DC predictor -- the
     // previous block of the same component in scan order, read from global memory (it may be another tile's), requested
@@ -278,7 +299,7 @@ __global__ __launch_bounds__(WG) void code_tiles_kernel(Job job, uint32_t* S, ui
         if (!(i >= 4 && job.bpm == 4)) {
             zg = fc + ((size_t)mcu * job.bpm + i) * 64;
             if (i >= 1 && i <= 3) pred = zg[-64];
-            else if (mcu != 0) pred = i == 0 ? zg[-(job.bpm - 3) * 64] : zg[-job.bpm * 64];
+            else if (RST ? !(interval_start && tid < 6u) : mcu != 0) pred = i == 0 ? zg[-(job.bpm - 3) * 64] : zg[-job.bpm * 64];
         }
     }
     // the tile's stored blocks are contiguous in memory; row = the lane that codes the block
@@ -318,7 +339,8 @@ __global__ __launch_bounds__(WG) void code_tiles_kernel(Job job, uint32_t* S, ui
     if (tid == 0) tile_total[t_index] = total;
     if (!valid) return;
 
-    uint32_t* const Sg = S + t_index * TILE_STREAM_WORDS;
+    uint32_t* const Sg = RST ? S + (size_t)frame * ((size_t)((nblk + 255u) / 256u) * TILE_STREAM_WORDS) + (size_t)g0 * (TILE_STREAM_WORDS / 256u)
+                             : S + t_index * TILE_STREAM_WORDS;
     const unsigned sh = o & 31u, w0 = o >> 5, end = o + n;
     uint32_t tail = 0;
     unsigned tail_word = 0, tail_fill = 0;                   // tail_fill != 0: this lane owns a partial last word
@@ -568,6 +590,201 @@ __global__ __launch_bounds__(256) void assemble_kernel(const uint32_t* S, const 
     }
 }
 
+// ---- restart intervals: tile offsets with every interval ending on a byte, and the assembling kernel that knows the markers ----
+// One workgroup per frame, as tile_bases_kernel.  Every interval starts on a byte, so the pad behind interval k depends on its own raw
+// length alone: (1) raw exclusive sums of the tile totals, (2) pad_k = (-raw length of interval k) mod 8 for every interval but
+// the last and the exclusive sums of those, (3) a tile's offset = its raw offset + the pads of the intervals in front of it.
+// Then stream length, first tile per piece and the error latch as tile_bases_kernel has them.  The markers themselves take no room
+// in U: they are inserted by the stuffing pass, which may not look at them.
+__global__ __launch_bounds__(256) void restart_bases_kernel(const uint32_t* tile_total, unsigned tpf, unsigned tpi, unsigned ni,
+                                                           unsigned long long* base, unsigned long long* padsum, unsigned long long* bytes,
+                                                           uint32_t* first_tile, unsigned ft_stride, unsigned* status, unsigned* latched)
+{
+    const unsigned f = blockIdx.x, tid = threadIdx.x;
+    const uint32_t* tt = tile_total + (size_t)f * tpf;
+    unsigned long long* B = base + (size_t)f * (tpf + 1);
+    unsigned long long* P = padsum + (size_t)f * ni;
+    uint32_t* ft = first_tile + (size_t)f * ft_stride;
+    unsigned long long carry = 0;
+    for (unsigned b0 = 0; b0 < tpf; b0 += 2048u) {
+        uint32_t v[8], s = 0;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const unsigned t = b0 + tid * 8u + k;
+            v[k] = t < tpf ? tt[t] : 0u;
+            s += v[k];
+        }
+        uint32_t total;
+        unsigned long long run = carry + wg256_exclusive_scan(s, &total);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const unsigned t = b0 + tid * 8u + k;
+            if (t < tpf) B[t] = run;
+            run += v[k];
+        }
+        carry += total;
+        __syncthreads();                 // the scan's LDS is reused by the next batch
+    }
+    if (tid == 0) B[tpf] = carry;
+    __syncthreads();                     // the raw offsets are complete (one workgroup: its own stores are visible behind the barrier)
+    carry = 0;
+    for (unsigned k0 = 0; k0 < ni; k0 += 2048u) {
+        uint32_t v[8], s = 0;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const unsigned k = k0 + tid * 8u + e;
+            v[e] = k + 1 < ni ? (uint32_t)((0ull - (B[(size_t)(k + 1) * tpi] - B[(size_t)k * tpi])) & 7ull) : 0u;
+            s += v[e];
+        }
+        uint32_t total;
+        unsigned long long run = carry + wg256_exclusive_scan(s, &total);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const unsigned k = k0 + tid * 8u + e;
+            if (k < ni) P[k] = run;
+            run += v[e];
+        }
+        carry += total;
+        __syncthreads();
+    }
+    for (unsigned t = tid; t <= tpf; t += 256u) {
+        const unsigned k = t / tpi;
+        B[t] += P[k < ni ? k : ni - 1];          // (the end of the stream: the last interval has no pad of its own)
+    }
+    __syncthreads();
+    for (unsigned t = tid; t < tpf; t += 256u) {
+        const unsigned long long b = B[t], e = B[t + 1];
+        // pieces whose first bit lies in [b, e): a piece starts on a byte, so never among the pad bits behind a tile
+        for (unsigned long long w = (b + ASM_BITS - 1) / ASM_BITS; w * ASM_BITS < e && w < ft_stride; ++w) ft[w] = t;
+    }
+    if (tid == 0) {
+        bytes[f] = (B[tpf] + 7) >> 3;
+        if (latched) {
+            latched[f] = status[f];
+            status[f] = 0;
+        }
+    }
+}
+
+// assemble_chunk for tiles that may be short (an interval's last tile can hold a single block): the chunk takes bits from the
+// tile that holds p and from EVERY tile that starts inside it, one after the other.  A tile that ends an interval (every tpi-th,
+// except the frame's last) ends on a byte in B; if that byte lies in the chunk, a marker follows it: bit j of `marks` = behind byte
+// j, k7 = the number (mod 8) of the chunk's first marker.  Returns the bytes the stuffing pass adds: 0xFF bytes + 2 per marker.
+__device__ __forceinline__ unsigned assemble_chunk_restart(unsigned long long p, const unsigned long long* B, const uint32_t* tt, unsigned t,
+                                                           unsigned tpf, unsigned tpi, unsigned restart, const uint32_t* Sf,
+                                                           unsigned long long T, uint4* dst, unsigned long long& marks, unsigned& k7)
+{
+    uint32_t out[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) out[k] = 0u;
+    marks = 0;
+    k7 = 0;
+    unsigned long long b = B[t];
+    for (unsigned u = t; u < tpf && b < p + CHUNK * 8; ++u) {
+        const unsigned long long e = B[u + 1];
+        const uint32_t* src = Sf + (size_t)restart_tile_first(u, restart) * (TILE_STREAM_WORDS / 256u);
+        // the tile's own bits: its total, not e - b -- a tile starts at any bit of U, so the pad up to a byte of U may reach into the
+        // tile stream's next word, which nobody wrote
+        const unsigned L = tt[u];
+        if (u == t) {                        // the tile that holds p: from its bit p - b on (or, behind its last bit, pad bits only)
+            const unsigned long long q = p - b;
+            const unsigned a = (unsigned)(q >> 5), sa = (unsigned)(q & 31u);
+            uint32_t wa[17];
+#pragma unroll
+            for (int k = 0; k < 17; ++k) wa[k] = ((a + k) << 5) < L ? src[a + k] : 0u;
+#pragma unroll
+            for (int k = 0; k < 16; ++k) out[k] = sa ? __builtin_amdgcn_alignbit(wa[k], wa[k + 1], 32u - sa) : wa[k];
+        } else {                             // a tile that starts inside the chunk, at chunk bit d = 32 * kb + rb
+            const unsigned d = (unsigned)(b - p), kb = d >> 5, rb = d & 31u;
+            uint32_t wn[16];
+#pragma unroll
+            for (int k = 0; k < 16; ++k) wn[k] = (unsigned)k >= kb && (((unsigned)k - kb) << 5) < L ? src[(unsigned)k - kb] : 0u;
+#pragma unroll
+            for (int k = 0; k < 16; ++k) out[k] |= __builtin_amdgcn_alignbit(k > 0 ? wn[k - 1] : 0u, wn[k], rb);
+        }
+        const bool ends = (u + 1) % tpi == 0 && u + 1 < tpf;
+        if (ends && e <= p + CHUNK * 8) {    // e > p, and both are whole bytes
+            if (!marks) k7 = (u / tpi) & 7u;
+            marks |= 1ull << (unsigned)(((e - p) >> 3) - 1);
+        }
+#if JPEZY_PAD_BIT   // one pad bits behind the interval's last bit (raw end: the tile's own total), as the frame's last byte below
+        if (ends) {
+            const unsigned long long raw = b + L;
+            const unsigned pad = (unsigned)(e - raw);
+            if (pad && raw < p + CHUNK * 8) {
+                const unsigned kk = (unsigned)((raw - p) >> 5), keep = (unsigned)((raw - p) & 31u);
+#pragma unroll
+                for (int k = 0; k < 16; ++k)
+                    if ((unsigned)k == kk) out[k] |= ((1u << pad) - 1u) << (32u - keep - pad);
+            }
+        }
+#endif
+        b = e;
+    }
+#if JPEZY_PAD_BIT
+    {
+        const unsigned pad = (unsigned)((8 - (T & 7)) & 7);
+        if (pad && T > p && T < p + CHUNK * 8) {
+            const unsigned kk = (unsigned)((T - p) >> 5), keep = (unsigned)((T - p) & 31u);
+#pragma unroll
+            for (int k = 0; k < 16; ++k)
+                if ((unsigned)k == kk) out[k] |= ((1u << pad) - 1u) << (32u - keep - pad);
+        }
+    }
+#else
+    (void)T;
+#endif
+    unsigned n_ff = 0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) n_ff += count_ff(out[k]);
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        dst[k] = make_uint4(__builtin_bswap32(out[4 * k]), __builtin_bswap32(out[4 * k + 1]), __builtin_bswap32(out[4 * k + 2]),
+                            __builtin_bswap32(out[4 * k + 3]));
+    return n_ff + 2u * (unsigned)__builtin_popcountll(marks);
+}
+
+// assemble_kernel for frames with restart intervals: offsets, stream length and the first tile of every piece come from
+// restart_bases_kernel at every frame size.  A thread finds its chunk's tile by binary search in the offsets themselves, between
+// the first tile of its piece and the first tile of the next -- a handful of tiles, so two or three dependent loads, and no bound
+// on how many tiles a piece can touch is needed (there is none worth having: an interval's last tile may hold a single block).
+__global__ __launch_bounds__(256) void assemble_restart_kernel(const uint32_t* S, size_t s_frame_words, const uint32_t* tile_total,
+                                                              const unsigned long long* base, const unsigned long long* bytes,
+                                                              const uint32_t* first_tile, unsigned tpf, unsigned restart, unsigned ft_stride,
+                                                              uint32_t* U, size_t u_stride_words, uint32_t* loc, uint32_t* ff_tile_total,
+                                                              unsigned long long* markers)
+{
+    const unsigned frame = blockIdx.y, tid = threadIdx.x;
+    const size_t chunks_per_frame = u_stride_words * 4 / CHUNK, pieces = chunks_per_frame / 256;   // a multiple of 256 (launcher)
+    const unsigned long long* B = base + (size_t)frame * (tpf + 1);
+    const uint32_t* ft = first_tile + (size_t)frame * ft_stride;
+    const unsigned long long nbytes = bytes[frame], T = B[tpf];
+    const unsigned tpi = restart_tpi(restart);
+    for (size_t x = blockIdx.x; x < pieces; x += gridDim.x) {
+        const unsigned long long c0 = (unsigned long long)x * 256u, c = c0 + tid;
+        if (x != 0 && c0 * CHUNK > nbytes) break;                       // (as assemble_kernel: the one-past-the-end chunk is written)
+        unsigned extra = 0, k7 = 0;
+        unsigned long long marks = 0;
+        const unsigned long long p = c * (CHUNK * 8ull);
+        if (c * CHUNK < nbytes) {                                       // p < T, and the piece's first bit lies in the stream
+            unsigned lo = ft[x], hi = (unsigned long long)(x + 1) * ASM_BITS < T ? ft[x + 1] + 1u : tpf;      // B[lo] <= p < B[hi]
+            while (hi - lo > 1) {
+                const unsigned mid = (lo + hi) >> 1;
+                if (B[mid] <= p) lo = mid; else hi = mid;
+            }
+            uint4* dst = reinterpret_cast<uint4*>(U + (size_t)frame * u_stride_words) + c * (CHUNK / 16);
+            extra = assemble_chunk_restart(p, B, tile_total + (size_t)frame * tpf, lo, tpf, tpi, restart, S + (size_t)frame * s_frame_words, T,
+                                           dst, marks, k7);
+        }
+        uint32_t total;
+        const uint32_t off = wg256_exclusive_scan(extra, &total);       // at most 256 x 128: the top three bits are free
+        loc[(size_t)frame * chunks_per_frame + c] = off | (k7 << 29);
+        markers[(size_t)frame * chunks_per_frame + c] = marks;
+        if (tid == 0) ff_tile_total[(size_t)frame * pieces + x] = total;
+        __syncthreads();                                                // the scan's LDS is reused by the next piece
+    }
+}
+
 // ---- exclusive prefix sums: 2048 elements per workgroup, recursive over the workgroup totals ----
 constexpr int SCAN_T = 256, SCAN_E = 8, SCAN_N = SCAN_T * SCAN_E;
 
@@ -732,11 +949,15 @@ constexpr int STUFF_WG = 256;
 // plan.hdr != nullptr (device-resident form): the frame's file is header + stuffed stream + EOI at out + frame * out_stride;
 // every workgroup works out whether the frame failed (a coefficient outside the tables: JPEZY_E_FORMAT = -5) or does not fit
 // (JPEZY_E_NOSPACE = -6) and leaves at once if so; workgroup 0 of the frame reports the size, writes EOI and copies the header.
+// RST (plan.markers != nullptr): restart intervals.  The counts in ff_loc / ff_tile_total then include two bytes per RSTn marker, a
+// thread places its chunk's markers behind the bytes plan.markers names (an interval is at least two bytes long, so a chunk holds at
+// most 32 of them: 192 bytes of staging per chunk), and a marker's 0xFF is never stuffed.
+template <bool RST>
 __global__ __launch_bounds__(STUFF_WG) void stuff_kernel(const uint32_t* U, size_t u_stride_words, const unsigned long long* frame_bytes,
                                                         const uint32_t* ff_loc, const uint32_t* ff_tile_total, uint8_t* out, size_t out_stride,
                                                         FilePlan plan)
 {
-    __shared__ uint32_t buf[STUFF_WG * CHUNK * 2 / 4 + 4];
+    __shared__ uint32_t buf[STUFF_WG * CHUNK * (RST ? 3 : 2) / 4 + 4];
     __shared__ unsigned long long red[2][STUFF_WG / 64];
     uint8_t* const lb = reinterpret_cast<uint8_t*>(buf);
     const size_t chunks_per_frame = u_stride_words * 4 / CHUNK, pieces = chunks_per_frame / STUFF_WG;
@@ -751,11 +972,18 @@ __global__ __launch_bounds__(STUFF_WG) void stuff_kernel(const uint32_t* U, size
         const bool has_data = (unsigned long long)c * CHUNK < nbytes;
         uint4 data[CHUNK / 16];
         uint32_t my_loc = 0;
+        unsigned long long marks = 0;
+        unsigned k7 = 0;
         if (has_data) {
             const uint4* src = reinterpret_cast<const uint4*>(reinterpret_cast<const uint8_t*>(U + frame * u_stride_words) + c * CHUNK);
 #pragma unroll
             for (int k = 0; k < CHUNK / 16; ++k) data[k] = src[k];
             my_loc = loc[c];
+            if constexpr (RST) {
+                marks = plan.markers[frame * chunks_per_frame + c];
+                k7 = my_loc >> 29;
+                my_loc &= 0x1FFFFFFFu;
+            }
         }
         // 0xFF bytes of the frame before this workgroup's chunks, and in the whole frame: the workgroup adds up the tile totals
         // itself (a few hundred 4-byte values out of the L2) -- a scan launched in between costs more than all of these sums
@@ -810,6 +1038,13 @@ __global__ __launch_bounds__(STUFF_WG) void stuff_kernel(const uint32_t* U, size
                         const uint8_t b = (uint8_t)(wd[j >> 2] >> ((j & 3) * 8));
                         *dst++ = b;
                         if (b == 0xFF) *dst++ = 0x00;
+                        if constexpr (RST) {
+                            if ((marks >> (k * 16 + j)) & 1ull) {
+                                *dst++ = 0xFF;
+                                *dst++ = (uint8_t)(0xD0u + k7);
+                                k7 = (k7 + 1u) & 7u;
+                            }
+                        }
                     }
                 }
             }
@@ -819,7 +1054,7 @@ __global__ __launch_bounds__(STUFF_WG) void stuff_kernel(const uint32_t* U, size
         const unsigned long long last_chunk = (nbytes + CHUNK - 1) / CHUNK;          // chunks of the frame that hold data
         const size_t ce = c0 + STUFF_WG < last_chunk ? c0 + STUFF_WG : (size_t)last_chunk;
         const unsigned long long src_end = (unsigned long long)ce * CHUNK < nbytes ? (unsigned long long)ce * CHUNK : nbytes;
-        const unsigned total = (unsigned)(src_end - (unsigned long long)c0 * CHUNK) + (ce < c0 + STUFF_WG ? loc[ce] : ft[px]);
+        const unsigned total = (unsigned)(src_end - (unsigned long long)c0 * CHUNK) + (ce < c0 + STUFF_WG ? (RST ? loc[ce] & 0x1FFFFFFFu : loc[ce]) : ft[px]);
         uint32_t* const A = reinterpret_cast<uint32_t*>(P - shift);                  // 4-byte aligned
         const unsigned end = shift + total, nwords = (end + 3) / 4;
         for (unsigned w = threadIdx.x; w < nwords; w += STUFF_WG) {
@@ -855,8 +1090,12 @@ hipError_t launch_stuff(const uint32_t* U, size_t u_stride_words, const unsigned
     if (n_frames > 65535 || chunks % STUFF_WG) return hipErrorInvalidValue;      // the frame index is a grid dimension
     size_t gx = chunks / STUFF_WG < 1024 ? chunks / STUFF_WG : 1024;
     if (n_frames > 1 && gx > 128) gx = 128;
-    hipLaunchKernelGGL(stuff_kernel, dim3((unsigned)gx, (unsigned)n_frames), dim3(STUFF_WG), 0, s, U, u_stride_words,
-                       frame_bytes, ff_loc, ff_tile_total, out, out_stride, plan);
+    if (plan.markers)
+        hipLaunchKernelGGL(stuff_kernel<true>, dim3((unsigned)gx, (unsigned)n_frames), dim3(STUFF_WG), 0, s, U, u_stride_words,
+                           frame_bytes, ff_loc, ff_tile_total, out, out_stride, plan);
+    else
+        hipLaunchKernelGGL(stuff_kernel<false>, dim3((unsigned)gx, (unsigned)n_frames), dim3(STUFF_WG), 0, s, U, u_stride_words,
+                           frame_bytes, ff_loc, ff_tile_total, out, out_stride, plan);
     return hipGetLastError();
 }
 
@@ -895,8 +1134,41 @@ hipError_t launch_code_tiles(const Job& job, uint32_t* S, uint32_t* tile_total, 
 {
     if (!job.blocks_per_frame || job.n_frames <= 0) return hipSuccess;
     if (job.n_frames > 65535) return hipErrorInvalidValue;                       // the frame index is a grid dimension
-    hipLaunchKernelGGL(code_tiles_kernel, dim3((unsigned)tiles256(job.blocks_per_frame), (unsigned)job.n_frames), dim3(WG), 0, s, job, S,
+    if (job.restart) {
+        if (job.restart > 65535u || job.blocks_per_frame % 6u || job.restart >= job.blocks_per_frame / 6u) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(code_tiles_kernel<true>, dim3((unsigned)restart_tiles(job.blocks_per_frame, job.restart), (unsigned)job.n_frames),
+                           dim3(WG), 0, s, job, S, tile_total, status);
+    } else
+    hipLaunchKernelGGL(code_tiles_kernel<false>, dim3((unsigned)tiles256(job.blocks_per_frame), (unsigned)job.n_frames), dim3(WG), 0, s, job, S,
                        tile_total, status);
+    return hipGetLastError();
+}
+
+hipError_t launch_restart_bases(const Job& job, const uint32_t* tile_total, unsigned long long* base, unsigned long long* pad,
+                                unsigned long long* bytes, uint32_t* first_tile, unsigned ft_stride, unsigned* status, unsigned* latched,
+                                hipStream_t s)
+{
+    if (!job.blocks_per_frame || job.n_frames <= 0) return hipSuccess;
+    if (!job.restart || job.restart >= job.blocks_per_frame / 6u) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(restart_bases_kernel, dim3((unsigned)job.n_frames), dim3(256), 0, s, tile_total,
+                       (unsigned)restart_tiles(job.blocks_per_frame, job.restart), restart_tpi(job.restart),
+                       (unsigned)restart_intervals(job.blocks_per_frame, job.restart), base, pad, bytes, first_tile, ft_stride, status, latched);
+    return hipGetLastError();
+}
+
+hipError_t launch_assemble_restart(const Job& job, const uint32_t* S, const uint32_t* tile_total, const unsigned long long* base,
+                                   const unsigned long long* bytes, const uint32_t* first_tile, unsigned ft_stride, uint32_t* U,
+                                   size_t u_stride_words, uint32_t* loc, uint32_t* ff_tile_total, unsigned long long* markers, hipStream_t s)
+{
+    const size_t pieces = u_stride_words * 4 / assemble_piece_bytes();
+    if (!pieces || job.n_frames <= 0) return hipSuccess;
+    if (u_stride_words * 4 % assemble_piece_bytes() || job.n_frames > 65535 || pieces > ft_stride || !job.restart) return hipErrorInvalidValue;
+    size_t gx = pieces < 1024 ? pieces : 1024;                   // (the grid of launch_assemble)
+    if (job.n_frames > 1 && gx > 128) gx = 128;
+    hipLaunchKernelGGL(assemble_restart_kernel, dim3((unsigned)gx, (unsigned)job.n_frames), dim3(256), 0, s, S,
+                       tiles256(job.blocks_per_frame) * (size_t)TILE_STREAM_WORDS, tile_total, base, bytes, first_tile,
+                       (unsigned)restart_tiles(job.blocks_per_frame, job.restart), job.restart, ft_stride, U, u_stride_words, loc,
+                       ff_tile_total, markers);
     return hipGetLastError();
 }
 

@@ -158,7 +158,7 @@ inline bool put_block(BitSink& o, const int16_t* z, int& pred, const EncLut& dc,
     return true;
 }
 
-void put_header(BitSink& o, int W, int H, const char* comment, const HuffTable* tabs = nullptr)
+void put_header(BitSink& o, int W, int H, const char* comment, const HuffTable* tabs = nullptr, int restart = 0)
 {
     static const uint8_t soi_app0[] = { 0xFF, 0xD8, 0xFF, 0xE0, 0x00, 0x10, 'J', 'F', 'I', 'F', 0x00,
                                         0x01, 0x02, 0x01, 0x00, 0x60, 0x00, 0x60, 0x00, 0x00 };
@@ -184,10 +184,14 @@ void put_header(BitSink& o, int W, int H, const char* comment, const HuffTable* 
         o.raw_n(bits, 16);
         o.raw_n(vals, (size_t)nval);
     }
-    const uint8_t sof_sos[] = { 0xFF, 0xC0, 0x00, 0x11, 0x08, (uint8_t)(H >> 8), (uint8_t)H, (uint8_t)(W >> 8), (uint8_t)W,
-                                0x03, 0x00, 0x22, 0x00, 0x01, 0x11, 0x01, 0x02, 0x11, 0x01,
-                                0xFF, 0xDA, 0x00, 0x0C, 0x03, 0x00, 0x00, 0x01, 0x11, 0x02, 0x11, 0x00, 0x3F, 0x00 };
-    o.raw_n(sof_sos, sizeof sof_sos);
+    const uint8_t sof[] = { 0xFF, 0xC0, 0x00, 0x11, 0x08, (uint8_t)(H >> 8), (uint8_t)H, (uint8_t)(W >> 8), (uint8_t)W,
+                            0x03, 0x00, 0x22, 0x00, 0x01, 0x11, 0x01, 0x02, 0x11, 0x01 };
+    o.raw_n(sof, sizeof sof);
+    if (restart > 0) {                                            // DRI: MCUs per restart interval, directly in front of SOS
+        o.raw(0xFF); o.raw(0xDD); o.raw16(4); o.raw16((unsigned)restart);
+    }
+    static const uint8_t sos[] = { 0xFF, 0xDA, 0x00, 0x0C, 0x03, 0x00, 0x00, 0x01, 0x11, 0x02, 0x11, 0x00, 0x3F, 0x00 };
+    o.raw_n(sos, sizeof sos);
 }
 
 }  // namespace
@@ -197,11 +201,17 @@ bool comment_ok(const char* comment)
     return !comment || std::strlen(comment) <= JPEZY_MAX_COMMENT;      // the COM length field (n + 3) can then never wrap
 }
 
-size_t write_header(int W, int H, const char* comment, uint8_t* out, size_t cap, const HuffTable* tabs)
+bool restart_ok(int restart, const char* comment)
 {
-    if (!comment_ok(comment)) return 0;
+    if (restart < 0 || restart > 65535) return false;
+    return restart == 0 || !comment || std::strlen(comment) <= JPEZY_MAX_COMMENT_RESTART;   // the six DRI bytes come out of the comment's room
+}
+
+size_t write_header(int W, int H, const char* comment, uint8_t* out, size_t cap, const HuffTable* tabs, int restart)
+{
+    if (!comment_ok(comment) || !restart_ok(restart, comment)) return 0;
     BitSink o(out, cap);
-    put_header(o, W, H, comment, tabs);
+    put_header(o, W, H, comment, tabs, restart);
     return o.ok() ? o.size() : 0;
 }
 
@@ -224,6 +234,9 @@ size_t jpeg_bound(int W, int H)
     // kMaxMcuBits = 9966 bits = 1246 bytes per MCU, 2492 if every byte were 0xFF and stuffed; pad byte (two if stuffed) and EOI
     // fit in the 196 bytes left of 2688 = 6 * 64 * 7.  A table never has more symbols than its Annex-K counterpart (12 / 162),
     // so no header is longer than the Annex-K one: the 1024 bytes and JPEZY_MAX_COMMENT stand.  (static_asserts: jpezy_host_codec.h)
+    // Restart intervals: every interval but the last adds a pad byte at the most (two if it is 0xFF and stuffed) and a 2-byte marker,
+    // so at one MCU per interval 4 bytes per MCU; with the frame's own pad and EOI (4 bytes, once) that is still inside the 196 bytes
+    // 2492 leaves of 2688.  The six DRI bytes come out of the comment's room (JPEZY_MAX_COMMENT_RESTART).  (tests/test_restart_host.py)
     return 1024 + nmcu * 6 * 64 * 7;
 }
 
@@ -242,7 +255,7 @@ int check_write_args(const int16_t* coeffs, int W, int H, const char* comment, c
 }
 
 long write_jpeg_with(const EncTables& T, const HuffTable* tabs, const int16_t* coeffs, int W, int H, bool gray, const char* comment,
-                     uint8_t* out, size_t cap, std::string* err);
+                     uint8_t* out, size_t cap, std::string* err, int restart = 0);
 }  // namespace
 
 long write_jpeg(const int16_t* coeffs, int W, int H, bool gray, const char* comment, uint8_t* out, size_t cap,
@@ -278,7 +291,7 @@ inline bool count_block(const int16_t* z, int& pred, unsigned long long* dc, uns
 }
 }  // namespace
 
-bool symbol_histogram(const int16_t* coeffs, int W, int H, bool gray, unsigned long long hist[4][256])
+bool symbol_histogram(const int16_t* coeffs, int W, int H, bool gray, unsigned long long hist[4][256], int restart)
 {
     static const int16_t kZeroBlock[64] = { 0 };
     std::memset(hist, 0, sizeof(unsigned long long) * 4 * 256);
@@ -288,6 +301,7 @@ bool symbol_histogram(const int16_t* coeffs, int W, int H, bool gray, unsigned l
     bool ok = true;
     for (size_t mcu = 0; mcu < nmcu; ++mcu) {
         const int16_t* z = coeffs + mcu * (size_t)bpm * 64;
+        if (restart > 0 && mcu % (size_t)restart == 0) pred[0] = pred[1] = pred[2] = 0;     // as the writer resets them
         for (int i = 0; i < 4; ++i) ok &= count_block(z + i * 64, pred[0], hist[0], hist[2]);
         ok &= count_block(gray ? kZeroBlock : z + 256, pred[1], hist[1], hist[3]);
         ok &= count_block(gray ? kZeroBlock : z + 320, pred[2], hist[1], hist[3]);
@@ -362,19 +376,50 @@ long write_jpeg_opt(const int16_t* coeffs, int W, int H, bool gray, const char* 
     return write_jpeg_with(T, tabs, coeffs, W, H, gray, comment, out, cap, err);
 }
 
+long write_jpeg_rst(const int16_t* coeffs, int W, int H, bool gray, const char* comment, int restart, bool optimize, uint8_t* out,
+                    size_t cap, std::string* err)
+{
+    if (int rc = check_write_args(coeffs, W, H, comment, out, err)) return rc;
+    if (restart < 0 || restart > 65535) {
+        if (err) *err = "write_jpeg: restart interval must be in 0..65535 MCUs";
+        return JPEZY_E_BADARG;
+    }
+    if (!restart_ok(restart, comment)) {
+        if (err) *err = "write_jpeg: with a restart interval the comment may be at most JPEZY_MAX_COMMENT_RESTART (" +
+                        std::to_string(JPEZY_MAX_COMMENT_RESTART) + " bytes)";
+        return JPEZY_E_BADARG;
+    }
+    if (!optimize) return write_jpeg_with(enc_tables(), nullptr, coeffs, W, H, gray, comment, out, cap, err, restart);
+    // the symbols THIS scan emits: the DC difference at an interval start is taken against 0
+    unsigned long long hist[4][256];
+    if (!symbol_histogram(coeffs, W, H, gray, hist, restart)) {
+        if (err) *err = "write_jpeg: coefficient outside the code tables";
+        return JPEZY_E_FORMAT;
+    }
+    HuffTable tabs[4];
+    for (int k = 0; k < 4; ++k) tabs[k].nval = optimal_table(hist[k], tabs[k].bits, tabs[k].vals);
+    const EncTables T(tabs);
+    return write_jpeg_with(T, tabs, coeffs, W, H, gray, comment, out, cap, err, restart);
+}
+
 namespace {
 long write_jpeg_with(const EncTables& T, const HuffTable* tabs, const int16_t* coeffs, int W, int H, bool gray, const char* comment,
-                     uint8_t* out, size_t cap, std::string* err)
+                     uint8_t* out, size_t cap, std::string* err, int restart)
 {
     BitSink o(out, cap);
-    put_header(o, W, H, comment, tabs);
+    put_header(o, W, H, comment, tabs, restart);
 
     static const int16_t kZeroBlock[64] = { 0 };
     const size_t nmcu = (size_t)((W + 15) / 16) * (size_t)((H + 15) / 16);
     const int bpm = gray ? 4 : 6;
-    int pred[3] = { 0, 0, 0 };                                     // pre_DC, never reset (no RSTn)
+    int pred[3] = { 0, 0, 0 };                                     // pre_DC: reset only at a restart interval's start
     for (size_t mcu = 0; mcu < nmcu; ++mcu) {
         const int16_t* z = coeffs + mcu * (size_t)bpm * 64;
+        if (restart > 0 && mcu != 0 && mcu % (size_t)restart == 0) {
+            // behind every interval but the last: pad to a byte (JPEZY_PAD_BIT, a padded 0xFF stuffed), then RSTn, never stuffed
+            o.raw(0xFF); o.raw(0xD0 + (unsigned)((mcu / (size_t)restart - 1) & 7));
+            pred[0] = pred[1] = pred[2] = 0;
+        }
         bool good = true;
         for (int i = 0; i < 4; ++i) good &= put_block(o, z + i * 64, pred[0], T.t[0], T.t[2]);
         good &= put_block(o, gray ? kZeroBlock : z + 256, pred[1], T.t[1], T.t[3]);

@@ -25,7 +25,10 @@ struct HuffTable {
 };
 // the bytes before the entropy-coded segment (SOI .. SOS, 644 with the default comment); 0 if cap is too small or the
 // comment too long.  tabs: the four tables of the DHT segments in file order YDc, CDc, YAc, CAc (nullptr: Annex K)
-size_t write_header(int W, int H, const char* comment, uint8_t* out, size_t cap, const HuffTable* tabs = nullptr);
+// restart: MCUs per restart interval (0: none) -- a DRI segment in front of SOS; 0 is returned too for a restart interval outside
+// 0..65535 or, with one, a comment longer than JPEZY_MAX_COMMENT_RESTART
+size_t write_header(int W, int H, const char* comment, uint8_t* out, size_t cap, const HuffTable* tabs = nullptr, int restart = 0);
+bool restart_ok(int restart, const char* comment);
 // canonical (code, length) per symbol of four tables in DHT order YDc, CDc, YAc, CAc (for the GPU coder); nullptr: Annex K
 void enc_code_tables(uint16_t code[4][256], uint8_t len[4][256], const HuffTable* tabs = nullptr);
 
@@ -44,9 +47,15 @@ static_assert(kMaxDcCodeBits + 11 <= 31 && kMaxAcCodeBits + 10 <= 31, "one appen
 int optimal_table(const unsigned long long freq[256], uint8_t bits[16], uint8_t vals[256]);
 // hist[k][sym]: how often the writer emits symbol sym from table k (DHT order) for this frame.  Returns false when a value lies
 // outside the code tables (DC category over 11, |AC| > 1023): counted as the largest size.
-bool symbol_histogram(const int16_t* coeffs, int W, int H, bool gray, unsigned long long hist[4][256]);
+// restart: MCUs per restart interval (0: none); the DC predictors are zero at every interval's start
+bool symbol_histogram(const int16_t* coeffs, int W, int H, bool gray, unsigned long long hist[4][256], int restart = 0);
 // write_jpeg with the frame's own optimal tables: same coefficients, same decoded pixels, a smaller file
 long write_jpeg_opt(const int16_t* coeffs, int W, int H, bool gray, const char* comment, uint8_t* out, size_t cap, std::string* err);
+// write_jpeg with restart intervals of `restart` MCUs (0: none): DRI in the header; behind every interval but the last the bits are
+// padded to a byte (JPEZY_PAD_BIT) and RSTn (n = interval index mod 8) follows; predictors zero at every interval's start.
+// optimize: the frame's own tables, built from the symbols this scan emits.
+long write_jpeg_rst(const int16_t* coeffs, int W, int H, bool gray, const char* comment, int restart, bool optimize, uint8_t* out,
+                    size_t cap, std::string* err);
 
 // What the entropy decoder needs besides jpezy_frame_info: where the scan data start, the raw DHT specifications
 // (slot = tc*4 + th: 0..3 DC, 4..7 AC) and the table selector of each scan component (the reference uses Td for both

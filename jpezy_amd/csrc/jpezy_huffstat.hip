@@ -9,6 +9,7 @@
 // with one 64-bit global atomic each; integer sums do not depend on the order of arrival.
 // Gray frames code two zero chroma blocks per MCU (DC category 0 and EOB each, predictor 0): they are not walked, workgroup 0 of the
 // frame adds 2 * MCUs to those two bins.
+// Restart intervals (Job::restart != 0, the RST instance): the predictors of an interval's first MCU are zero, as the coder has them.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -27,6 +28,7 @@ struct LdsHist {
 };
 static_assert((unsigned long long)HB * 64ull < (1ull << 32), "a workgroup's bin cannot overflow 32 bits");
 
+template <bool RST>
 __global__ __launch_bounds__(HWG) void symbol_histogram_kernel(Job job, unsigned long long* hist, unsigned* status)
 {
     __shared__ LdsHist L;
@@ -56,7 +58,7 @@ __global__ __launch_bounds__(HWG) void symbol_histogram_kernel(Job job, unsigned
                 const unsigned mcu = sb / bpm, i = sb - mcu * bpm;
                 if (lane == 0) {
                     if (i >= 1 && i <= 3) pred[j] = z[-64];
-                    else if (mcu != 0) pred[j] = i == 0 ? z[-(int)(bpm - 3) * 64] : z[-(int)bpm * 64];
+                    else if (mcu != 0 && !(RST && mcu % job.restart == 0u)) pred[j] = i == 0 ? z[-(int)(bpm - 3) * 64] : z[-(int)bpm * 64];
                 }
             }
         }
@@ -104,7 +106,10 @@ hipError_t launch_symbol_histogram(const Job& job, unsigned long long* hist, uns
     if (!job.blocks_per_frame || job.n_frames <= 0) return hipSuccess;
     if (job.n_frames > 65535 || (job.bpm != 4 && job.bpm != 6) || job.blocks_per_frame % 6u) return hipErrorInvalidValue;
     const unsigned nstored = job.blocks_per_frame / 6u * (unsigned)job.bpm;
-    hipLaunchKernelGGL(symbol_histogram_kernel, dim3((nstored + HB - 1) / HB, (unsigned)job.n_frames), dim3(HWG), 0, s, job, hist, status);
+    if (job.restart)
+        hipLaunchKernelGGL(symbol_histogram_kernel<true>, dim3((nstored + HB - 1) / HB, (unsigned)job.n_frames), dim3(HWG), 0, s, job, hist, status);
+    else
+        hipLaunchKernelGGL(symbol_histogram_kernel<false>, dim3((nstored + HB - 1) / HB, (unsigned)job.n_frames), dim3(HWG), 0, s, job, hist, status);
     return hipGetLastError();
 }
 

@@ -593,13 +593,4 @@ int jpezy_dequant_idct_generic(jpezy_ctx* c, const int16_t* coeffs, const uint16
     return jpezy_internal_dequant_idct_generic_impl(c, coeffs, qt, ncomp, comp_h, comp_v, comp_tq, W, H, gray, 8, r, g, b);
 }
 
-long jpezy_write_jpeg(const int16_t* coeffs, int W, int H, int gray, const char* comment, uint8_t* out, size_t cap)
-try {
-    std::string err;
-    const long n = jpezy_host::write_jpeg(coeffs, W, H, gray != 0, comment, out, cap, &err);
-    if (n < 0) g_err = err;
-    return n;
-}
-JPEZY_CATCH
-
 }  // extern "C"

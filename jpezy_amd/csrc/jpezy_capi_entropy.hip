@@ -1,5 +1,6 @@
-// jpezy_capi_entropy.hip -- the C-ABI, part 2: the Huffman tail of encoder::encode (ref encoder/jpezy_encoder.hpp:174-225): host writer,
-// GPU entropy coder, encoder::encode end to end.
+// jpezy_capi_entropy.hip -- the C-ABI, part 2: the Huffman tail of encoder::encode (ref encoder/jpezy_encoder.hpp:174-225): the host
+// writer's entry points, the GPU entropy coder in its host-delivered and its device-resident form -- one Pass (plan,
+// launch chain) for both --, encoder::encode end to end.
 #include "jpezy_capi_internal.h"
 
 extern "C" {
@@ -19,7 +20,7 @@ try {
     std::atomic<int> failed{ 0 };
     auto work = [&]() {
         for (int f = next.fetch_add(1); f < n_frames; f = next.fetch_add(1)) {
-            sizes[f] = jpezy_host::write_jpeg(coeffs + (size_t)f * cpf, W, H, gray != 0, comment, out + (size_t)f * cap, cap, nullptr);
+            sizes[f] = jpezy_host::write_jpeg(coeffs + (size_t)f * cpf, W, H, gray != 0, comment, 0, false, out + (size_t)f * cap, cap, nullptr);
             if (sizes[f] < 0) failed.store(1);
         }
     };
@@ -92,56 +93,115 @@ int check_restart_comment(const jpezy_ctx* c, const char* comment, const char* w
                                        std::to_string(JPEZY_MAX_COMMENT_RESTART) + " bytes)");
 }
 
-// worst-case bytes of a frame's unstuffed stream: 208 per block, and a pad byte behind every restart interval
-size_t worst_stream_bytes(size_t nblk, unsigned restart)
-{
-    return nblk * 208 + (restart ? jpezy_dev::entropy::restart_intervals(nblk, restart) : 0);
-}
-
 // frames per pass with per-image tables: a frame's table image is 10 KB
 constexpr int kMaxOptFramesPerPass = 1024;
 
-// one chunk of frames, all resident in the scratch buffers
+// frames of one pass of either form: worst-case streams of 1 GiB, and the frame index is a grid dimension
+int frames_per_pass(const jpezy_ctx* c, int W, int H, int gray, int n_frames)
+{
+    jpezy_dev::entropy::Job job;
+    make_job(job, nullptr, W, H, gray, 1, nullptr, c->restart_interval);
+    const size_t per = std::min<size_t>(std::min<size_t>((size_t)n_frames, kMaxFramesPerLaunch), jpezy_dev::entropy::max_pass_frames(job));
+    return c->huff_optimize ? std::min((int)per, kMaxOptFramesPerPass) : (int)per;
+}
+
+// One pass: F frames, all resident in the context's scratch buffers.
+struct Pass {
+    jpezy_dev::entropy::Job job;
+    jpezy_dev::entropy::Scratch sc;
+    unsigned long long* added = nullptr;   // [F] bytes stuffing adds to a frame (host-delivered form)
+    hipStream_t s = nullptr;
+
+    // Builds the job and reserves the scratch.  The per-frame error flags come in two protocols:
+    //   resident = false (host-delivered form): status is cleared here, set by the coder and read by the host after the pass;
+    //   resident = true (device-resident form, capturable): status is the context's e_status, zero between calls -- zeroed once when it
+    //     grows (first call, never inside a capture); the consumer of the tile totals latches and clears it, the stuffing kernel reads
+    //     the latched copy.  Nothing is reserved and nothing synchronised on a call whose arguments the context has seen.
+    int plan(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H, int gray, int F, bool resident, hipStream_t stream)
+    {
+        namespace E = jpezy_dev::entropy;
+        s = stream;
+        make_job(job, d_coeffs, W, H, gray, F, c->d_codes.as<E::CodeTables>(), c->restart_interval);
+        const E::ScratchSizes z = E::scratch_sizes(job, c->huff_optimize != 0);
+        if (int rc = c->e_S.reserve(z.tile_stream)) return rc;
+        if (int rc = c->e_tt.reserve(z.tile_total)) return rc;
+        if (int rc = c->e_base.reserve(z.tile_base)) return rc;
+        if (int rc = c->e_ft.reserve(z.first_tile)) return rc;
+        if (int rc = c->e_rpad.reserve(z.restart_pad)) return rc;
+        if (int rc = c->e_U.reserve(z.U)) return rc;
+        if (int rc = c->e_cnt.reserve(z.ff_loc)) return rc;
+        if (int rc = c->e_fft.reserve(z.ff_piece)) return rc;
+        if (int rc = c->e_mk.reserve(z.markers)) return rc;
+        if (int rc = c->e_small.reserve(2 * z.bytes + z.flags)) return rc;      // [F] stream bytes | [F] added bytes | [F] flags
+        sc.tile_stream = c->e_S.as<uint32_t>();
+        sc.tile_total = c->e_tt.as<uint32_t>();
+        sc.tile_base = c->e_base.as<unsigned long long>();
+        sc.first_tile = c->e_ft.as<uint32_t>();
+        sc.restart_pad = c->e_rpad.as<unsigned long long>();
+        sc.U = c->e_U.as<uint32_t>();
+        sc.u_stride = E::stream_stride(job);
+        sc.ft_stride = (unsigned)(sc.u_stride / E::assemble_piece_bytes());
+        sc.ff_loc = c->e_cnt.as<uint32_t>();
+        sc.ff_piece = c->e_fft.as<uint32_t>();
+        sc.markers = c->e_mk.as<unsigned long long>();
+        sc.bytes = c->e_small.as<unsigned long long>();
+        added = sc.bytes + F;
+        unsigned* flags = reinterpret_cast<unsigned*>(added + F);
+        if (!resident) {
+            sc.status = flags;
+            sc.latched = nullptr;
+            HIP_TRY(hipMemsetAsync(sc.status, 0, z.flags, s));
+        } else {
+            if (c->e_status.cap < z.flags) {
+                if (int rc = c->e_status.reserve(z.flags)) return rc;
+                HIP_TRY(hipMemsetAsync(c->e_status.p, 0, c->e_status.cap, s));
+            }
+            sc.status = c->e_status.as<unsigned>();
+            sc.latched = flags;
+        }
+        return JPEZY_OK;
+    }
+
+    // every block coded once into its tile's stream; tile offsets; streams assembled, and the bytes stuffing adds counted
+    int code(bool any_tables) const
+    {
+        namespace E = jpezy_dev::entropy;
+        HIP_TRY(E::launch_code_tiles(job, sc, s));
+        // the coder may have raised error flags that only their consumer (tile offsets / assembly) clears: if the call ends between
+        // the two, the flags are cleared here so that they do not leak into the context's next call
+        hipError_t e = E::launch_tile_bases(job, sc, s);
+        if (e == hipSuccess) e = E::launch_assemble(job, sc, any_tables, s);
+        if (e == hipSuccess) return JPEZY_OK;
+        (void)hipMemsetAsync(sc.status, 0, sizeof(unsigned) * (size_t)job.n_frames, s);
+        return hip_err(e, "entropy stage (tile offsets / assembly)");
+    }
+
+    // byte stuffing (restart intervals: and the markers): streams out_stride apart, or with plan.hdr whole files and their verdicts
+    int stuff(uint8_t* out, size_t out_stride, const jpezy_dev::entropy::FilePlan& plan) const
+    {
+        HIP_TRY(jpezy_dev::entropy::launch_stuff(job, sc, out, out_stride, plan, s));
+        return JPEZY_OK;
+    }
+};
+
+// symbol counts of the job's frames (job.tables is not read)
+int enqueue_histogram(const jpezy_dev::entropy::Job& job, unsigned long long* d_hist, unsigned* d_status, hipStream_t s)
+{
+    HIP_TRY(hipMemsetAsync(d_hist, 0, (size_t)job.n_frames * 4 * 256 * sizeof(unsigned long long), s));
+    HIP_TRY(jpezy_dev::entropy::launch_symbol_histogram(job, d_hist, d_status, s));
+    return JPEZY_OK;
+}
+
+// one pass of the host-delivered form
 int entropy_chunk(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H, int gray, int F, const char* comment, uint8_t* out,
                   size_t cap, long* sizes, bool* any_failed)
 {
     namespace E = jpezy_dev::entropy;
     hipStream_t s = c->stream;
-    const size_t nmcu = (size_t)jpezy_mcu_cols(W) * jpezy_mcu_rows(H);
-    const size_t nblk = nmcu * 6;
-    E::Job job;
-    make_job(job, d_coeffs, W, H, gray, F, c->d_codes.as<E::CodeTables>(), c->restart_interval);
     const bool optimize = c->huff_optimize != 0;
-    const unsigned rst = job.restart;
+    Pass p;
+    if (int rc = p.plan(c, d_coeffs, W, H, gray, F, false, s)) return rc;
 
-    // every block is coded once, into the stream of its tile (256 coded blocks of a frame); worst case 208 bytes per block
-    // (restart intervals: a tile never straddles an interval, so there are more of them; their streams lie where the blocks' would)
-    const size_t tpf = E::job_tiles(nblk, rst), nt = tpf * (size_t)F, piece = E::assemble_piece_bytes(), chunk = E::chunk_bytes();
-    const size_t u_stride = (worst_stream_bytes(nblk, rst) + 8 + piece - 1) / piece * piece, ft_stride = u_stride / piece;
-    const size_t nchunks = u_stride / chunk * F;
-    const bool self = !rst && E::assemble_scans_tiles_itself(tpf);
-    if (int rc = c->e_tt.reserve(nt * sizeof(uint32_t))) return rc;                          // tile totals (bits)
-    if (int rc = c->e_S.reserve(E::tiles256(nblk) * (size_t)F * E::tile_stream_bytes())) return rc;   // tile streams
-    if (rst) {
-        if (int rc = c->e_rpad.reserve(E::restart_intervals(nblk, rst) * F * sizeof(unsigned long long))) return rc;   // pads in front of an interval
-        if (int rc = c->e_mk.reserve(nchunks * sizeof(unsigned long long))) return rc;       // markers behind a chunk's bytes
-    }
-    if (int rc = c->e_U.reserve(u_stride * F)) return rc;                                    // unstuffed streams
-    if (int rc = c->e_cnt.reserve(nchunks * sizeof(uint32_t))) return rc;                    // 0xFF bytes: per chunk inside its piece,
-    if (int rc = c->e_fft.reserve(ft_stride * F * sizeof(uint32_t))) return rc;              //             per piece
-    if (!self) {
-        if (int rc = c->e_base.reserve((tpf + 1) * F * sizeof(unsigned long long))) return rc;   // frame-relative tile offsets
-        if (int rc = c->e_ft.reserve(ft_stride * F * sizeof(uint32_t))) return rc;
-    }
-    // small arrays: [F] status u32 | [F] (unused) | [F] stream bytes | [F] 0xFF totals
-    const size_t small_words = (size_t)F * 8;
-    if (int rc = c->e_small.reserve(small_words * sizeof(unsigned long long))) return rc;
-    unsigned* d_status = (unsigned*)c->e_small.p;
-    unsigned long long* d_bytes = (unsigned long long*)c->e_small.p + 2 * F;
-    unsigned long long* d_fftot = d_bytes + F;
-
-    // 1. codes; 2. unstuffed streams, one per frame, with their 0xFF bytes counted; stream lengths
-    HIP_TRY(hipMemsetAsync(d_status, 0, sizeof(unsigned) * F, s));
     // 0. per-image tables: the frames' symbol counts come to the host, which builds every frame's four tables (Annex K.2) and
     //    sends their code images back; the coder then takes frame f's image.  One extra synchronisation and two small copies.
     std::vector<jpezy_host::HuffTable> tabs;
@@ -151,8 +211,7 @@ int entropy_chunk(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H, int gray,
         if (int rc = c->e_hist_pin.reserve(hist_bytes)) return rc;
         if (int rc = c->e_codes_opt.reserve(img_bytes)) return rc;
         if (int rc = c->e_codes_pin.reserve(img_bytes)) return rc;
-        HIP_TRY(hipMemsetAsync(c->e_hist.p, 0, hist_bytes, s));
-        HIP_TRY(E::launch_symbol_histogram(job, (unsigned long long*)c->e_hist.p, d_status, s));
+        if (int rc = enqueue_histogram(p.job, c->e_hist.as<unsigned long long>(), p.sc.status, s)) return rc;
         HIP_TRY(hipMemcpyAsync(c->e_hist_pin.p, c->e_hist.p, hist_bytes, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         tabs.resize((size_t)F * 4);
@@ -165,30 +224,17 @@ int entropy_chunk(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H, int gray,
             fill_code_image(c->e_codes_pin.as<E::CodeTables>()[f], &tabs[(size_t)f * 4]);
         }
         HIP_TRY(hipMemcpyAsync(c->e_codes_opt.p, c->e_codes_pin.p, img_bytes, hipMemcpyHostToDevice, s));
-        job.tables = c->e_codes_opt.as<E::CodeTables>();
-        job.tables_stride = 1;
+        p.job.tables = c->e_codes_opt.as<E::CodeTables>();
+        p.job.tables_stride = 1;
     }
-    HIP_TRY(E::launch_code_tiles(job, (uint32_t*)c->e_S.p, (uint32_t*)c->e_tt.p, d_status, s));
-    if (rst) {
-        HIP_TRY(E::launch_restart_bases(job, (const uint32_t*)c->e_tt.p, (unsigned long long*)c->e_base.p, (unsigned long long*)c->e_rpad.p,
-                                        d_bytes, (uint32_t*)c->e_ft.p, (unsigned)ft_stride, d_status, nullptr, s));
-        HIP_TRY(E::launch_assemble_restart(job, (const uint32_t*)c->e_S.p, (const uint32_t*)c->e_tt.p, (const unsigned long long*)c->e_base.p,
-                                           d_bytes, (const uint32_t*)c->e_ft.p, (unsigned)ft_stride, (uint32_t*)c->e_U.p, u_stride / 4,
-                                           (uint32_t*)c->e_cnt.p, (uint32_t*)c->e_fft.p, (unsigned long long*)c->e_mk.p, s));
-    } else {
-    if (!self)
-        HIP_TRY(E::launch_tile_bases((const uint32_t*)c->e_tt.p, (unsigned)tpf, F, (unsigned long long*)c->e_base.p, d_bytes,
-                                     (uint32_t*)c->e_ft.p, (unsigned)ft_stride, d_status, nullptr, s));
-    HIP_TRY(E::launch_assemble((const uint32_t*)c->e_S.p, (const uint32_t*)c->e_tt.p, (const unsigned long long*)c->e_base.p, d_bytes,
-                               (const uint32_t*)c->e_ft.p, (unsigned)ft_stride, (unsigned)tpf, F, (uint32_t*)c->e_U.p, u_stride / 4,
-                               (uint32_t*)c->e_cnt.p, (uint32_t*)c->e_fft.p, d_status, nullptr, s, optimize));
-    }
-    HIP_TRY(E::launch_ff_frame_totals((const uint32_t*)c->e_fft.p, d_bytes, u_stride / 4, F, d_fftot, s));
+    // 1. codes; 2. unstuffed streams, one per frame; their lengths and the bytes stuffing adds to them
+    if (int rc = p.code(optimize)) return rc;
+    HIP_TRY(E::launch_ff_frame_totals(p.job, p.sc, p.added, s));
     std::vector<unsigned long long> nbytes(F), fftot(F);
     std::vector<unsigned> status(F);
-    HIP_TRY(hipMemcpyAsync(nbytes.data(), d_bytes, sizeof(unsigned long long) * F, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(status.data(), d_status, sizeof(unsigned) * F, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(fftot.data(), d_fftot, sizeof(unsigned long long) * F, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(nbytes.data(), p.sc.bytes, sizeof(unsigned long long) * F, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(status.data(), p.sc.status, sizeof(unsigned) * F, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(fftot.data(), p.added, sizeof(unsigned long long) * F, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
 
     // 3. byte stuffing into a buffer sized from the actual lengths (fftot: the bytes stuffing adds -- with restart intervals the markers too)
@@ -197,10 +243,7 @@ int entropy_chunk(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H, int gray,
         if (nbytes[f] + fftot[f] > max_out) max_out = nbytes[f] + fftot[f];
     const size_t o_stride = ((size_t)max_out + 2 + 63) / 64 * 64;
     if (int rc = c->e_out.reserve(o_stride * F)) return rc;
-    E::FilePlan stuff_plan;
-    if (rst) stuff_plan.markers = (const unsigned long long*)c->e_mk.p;
-    HIP_TRY(E::launch_stuff((const uint32_t*)c->e_U.p, u_stride / 4, d_bytes, F, (const uint32_t*)c->e_cnt.p, (const uint32_t*)c->e_fft.p,
-                            (uint8_t*)c->e_out.p, o_stride, stuff_plan, s));
+    if (int rc = p.stuff(c->e_out.as<uint8_t>(), o_stride, E::FilePlan())) return rc;
 
     // 4. header + entropy-coded segment + EOI into the caller's buffers.  One device-to-host copy of all streams into a
     //    pinned staging buffer (per-frame copies into pageable memory cost more than the kernels for small frames).
@@ -262,79 +305,18 @@ int jpezy_write_jpeg_gpu_dev(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H
         std::memcpy(c->e_hdr_host, hdr, hdr_len);
         c->e_hdr_len = hdr_len;
     }
-    const size_t nmcu = (size_t)jpezy_mcu_cols(W) * jpezy_mcu_rows(H);
-    const size_t nblk = nmcu * 6;
-    const size_t chunk = E::chunk_bytes();
-    // worst case per block: 64 x (16-bit code + 10 value bits) = 208 bytes; whole 16 KB pieces (one workgroup of the
-    // assembling / stuffing kernels each)
-    const size_t piece = E::assemble_piece_bytes();
-    const unsigned rst = c->restart_interval > 0 && (size_t)c->restart_interval < nmcu ? (unsigned)c->restart_interval : 0u;   // (make_job)
-    const size_t u_stride = (worst_stream_bytes(nblk, rst) + 8 + piece - 1) / piece * piece;
-    // frames per pass: worst-case streams below ~1 GiB, and at most 65535 (the frame index is a grid dimension)
-    const int per = (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>((size_t)n_frames, kMaxFramesPerLaunch), ((size_t)1 << 30) / u_stride));
+    const int per = frames_per_pass(c, W, H, gray, n_frames);
     const size_t cpf = jpezy_coeff_count(W, H, gray);
-    const size_t tpf = E::job_tiles(nblk, rst);                     // tiles of one frame (a tile never straddles frames, nor restart intervals)
-    const bool self = !rst && E::assemble_scans_tiles_itself(tpf);
     for (int f0 = 0; f0 < n_frames; f0 += per) {
-        const int F = std::min(per, n_frames - f0);
-        const size_t nchunks = u_stride / chunk * F, nt = tpf * F, nct = E::tiles256(nchunks);
-        E::Job job;
-        make_job(job, d_coeffs + (size_t)f0 * cpf, W, H, gray, F, c->d_codes.as<E::CodeTables>(), c->restart_interval);
-        if (int rc = c->e_tt.reserve(nt * sizeof(uint32_t))) return rc;
-        if (int rc = c->e_S.reserve(E::tiles256(nblk) * (size_t)F * E::tile_stream_bytes())) return rc;
-        if (rst) {
-            if (int rc = c->e_rpad.reserve(E::restart_intervals(nblk, rst) * F * sizeof(unsigned long long))) return rc;
-            if (int rc = c->e_mk.reserve(nchunks * sizeof(unsigned long long))) return rc;
-        }
-        if (!self) {
-            if (int rc = c->e_base.reserve((tpf + 1) * F * sizeof(unsigned long long))) return rc;
-            if (int rc = c->e_ft.reserve(u_stride / piece * F * sizeof(uint32_t))) return rc;
-        }
-        if (int rc = c->e_small.reserve((size_t)F * 8 * sizeof(unsigned long long))) return rc;
-        if (int rc = c->e_U.reserve(u_stride * F)) return rc;
-        if (int rc = c->e_cnt.reserve(nchunks * sizeof(uint32_t))) return rc;
-        if (int rc = c->e_fft.reserve(nct * sizeof(uint32_t))) return rc;
-        if (c->e_status.cap < sizeof(unsigned) * (size_t)F) {      // grown (first call, never inside a capture): zero it once;
-            if (int rc = c->e_status.reserve(sizeof(unsigned) * (size_t)F)) return rc;   // from then on tile_bases_kernel clears what it latches
-            HIP_TRY(hipMemsetAsync(c->e_status.p, 0, c->e_status.cap, s));
-        }
-        unsigned* d_status = (unsigned*)c->e_status.p;
-        unsigned* d_latched = (unsigned*)c->e_small.p;
-        unsigned long long* d_bytes = (unsigned long long*)c->e_small.p + F;
-        // every block coded once into its tile's stream; tile offsets; streams assembled and their 0xFF bytes counted; the
-        // 0xFF offsets; files written (header, stuffed stream, EOI, size or verdict)
-        HIP_TRY(E::launch_code_tiles(job, (uint32_t*)c->e_S.p, (uint32_t*)c->e_tt.p, d_status, s));
-        // the coder may have raised per-frame error flags that only their consumer (tile_bases / assemble) clears: if the call ends
-        // between the two, the flags are cleared here so that they do not leak into the context's next call
-        hipError_t e_mid = hipSuccess;
-        if (rst) {      // one launch more than a frame without intervals that scans its tiles itself: the offsets need the pads
-            e_mid = E::launch_restart_bases(job, (const uint32_t*)c->e_tt.p, (unsigned long long*)c->e_base.p, (unsigned long long*)c->e_rpad.p,
-                                            d_bytes, (uint32_t*)c->e_ft.p, (unsigned)(u_stride / piece), d_status, d_latched, s);
-            if (e_mid == hipSuccess)
-                e_mid = E::launch_assemble_restart(job, (const uint32_t*)c->e_S.p, (const uint32_t*)c->e_tt.p, (const unsigned long long*)c->e_base.p,
-                                                   d_bytes, (const uint32_t*)c->e_ft.p, (unsigned)(u_stride / piece), (uint32_t*)c->e_U.p,
-                                                   u_stride / 4, (uint32_t*)c->e_cnt.p, (uint32_t*)c->e_fft.p, (unsigned long long*)c->e_mk.p, s);
-        } else {
-        if (!self)
-            e_mid = E::launch_tile_bases((const uint32_t*)c->e_tt.p, (unsigned)tpf, F, (unsigned long long*)c->e_base.p, d_bytes,
-                                         (uint32_t*)c->e_ft.p, (unsigned)(u_stride / piece), d_status, d_latched, s);
-        if (e_mid == hipSuccess)
-            e_mid = E::launch_assemble((const uint32_t*)c->e_S.p, (const uint32_t*)c->e_tt.p, (const unsigned long long*)c->e_base.p, d_bytes,
-                                       (const uint32_t*)c->e_ft.p, (unsigned)(u_stride / piece), (unsigned)tpf, F, (uint32_t*)c->e_U.p,
-                                       u_stride / 4, (uint32_t*)c->e_cnt.p, (uint32_t*)c->e_fft.p, d_status, d_latched, s);
-        }
-        if (e_mid != hipSuccess) {
-            (void)hipMemsetAsync(d_status, 0, sizeof(unsigned) * (size_t)F, s);
-            return hip_err(e_mid, "entropy stage (tile offsets / assembly)");
-        }
-        E::FilePlan plan;
-        plan.hdr = (const uint8_t*)c->e_hdr.p;
-        plan.hdr_len = hdr_len;
-        plan.latched = d_latched;
-        plan.sizes = d_sizes + f0;
-        if (rst) plan.markers = (const unsigned long long*)c->e_mk.p;
-        HIP_TRY(E::launch_stuff((const uint32_t*)c->e_U.p, u_stride / 4, d_bytes, F, (const uint32_t*)c->e_cnt.p, (const uint32_t*)c->e_fft.p,
-                                d_out + (size_t)f0 * out_stride, out_stride, plan, s));
+        Pass p;
+        if (int rc = p.plan(c, d_coeffs + (size_t)f0 * cpf, W, H, gray, std::min(per, n_frames - f0), true, s)) return rc;
+        if (int rc = p.code(false)) return rc;
+        // files written (header, stuffed stream, EOI, size or verdict)
+        E::FilePlan files;
+        files.hdr = c->e_hdr.as<uint8_t>();
+        files.hdr_len = hdr_len;
+        files.sizes = d_sizes + f0;
+        if (int rc = p.stuff(d_out + (size_t)f0 * out_stride, out_stride, files)) return rc;
     }
     return JPEZY_OK;
 }
@@ -348,11 +330,7 @@ try {
     if (int rc = check_restart_comment(c, comment, "write_jpeg_gpu")) return rc;
     HIP_TRY(hipSetDevice(c->device));
     if (int rc = ensure_code_tables(c)) return rc;
-    const size_t nblk = (size_t)jpezy_mcu_cols(W) * jpezy_mcu_rows(H) * 6;
-    // chunk the batch so that the worst-case unstuffed streams (208 bytes per block) stay below ~1 GiB
-    const size_t worst = nblk * 208 + nblk / 6 + 4096;             // (a pad byte behind every restart interval, at the most one per MCU)
-    int per = (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>((size_t)n_frames, kMaxFramesPerLaunch), ((size_t)1 << 30) / worst));   // 65535: grid dimension
-    if (c->huff_optimize) per = std::min(per, kMaxOptFramesPerPass);
+    const int per = frames_per_pass(c, W, H, gray, n_frames);
     bool any_failed = false;
     const size_t cpf = jpezy_coeff_count(W, H, gray);
     for (int f0 = 0; f0 < n_frames; f0 += per) {
@@ -409,11 +387,9 @@ int jpezy_huffman_histogram_dev(jpezy_ctx* c, const int16_t* d_coeffs, int W, in
         const int F = std::min(kMaxFramesPerLaunch, n_frames - f0);
         if (c->e_hstat.cap < sizeof(unsigned) * (size_t)F)
             if (int rc = c->e_hstat.reserve(sizeof(unsigned) * (size_t)F)) return rc;
-        unsigned long long* h = d_hist + (size_t)f0 * 4 * 256;
-        HIP_TRY(hipMemsetAsync(h, 0, (size_t)F * 4 * 256 * sizeof(unsigned long long), s));
         E::Job job;
         make_job(job, d_coeffs + (size_t)f0 * cpf, W, H, gray, F, nullptr, c->restart_interval);
-        HIP_TRY(E::launch_symbol_histogram(job, h, (unsigned*)c->e_hstat.p, s));
+        if (int rc = enqueue_histogram(job, d_hist + (size_t)f0 * 4 * 256, c->e_hstat.as<unsigned>(), s)) return rc;
     }
     return JPEZY_OK;
 }
@@ -424,24 +400,31 @@ int jpezy_huffman_optimal_table(const unsigned long long freq[256], uint8_t bits
     return jpezy_host::optimal_table(freq, bits, vals);
 }
 
-long jpezy_write_jpeg_opt(const int16_t* coeffs, int W, int H, int gray, const char* comment, uint8_t* out, size_t cap)
+// the three forms of the host writer (jpezy_host::write_jpeg)
+static long host_write(const int16_t* coeffs, int W, int H, int gray, const char* comment, int restart, int optimize, uint8_t* out, size_t cap)
 try {
     std::string err;
-    const long n = jpezy_host::write_jpeg_opt(coeffs, W, H, gray != 0, comment, out, cap, &err);
+    const long n = jpezy_host::write_jpeg(coeffs, W, H, gray != 0, comment, restart, optimize != 0, out, cap, &err);
     if (n < 0) g_err = err;
     return n;
 }
 JPEZY_CATCH
 
+long jpezy_write_jpeg(const int16_t* coeffs, int W, int H, int gray, const char* comment, uint8_t* out, size_t cap)
+{
+    return host_write(coeffs, W, H, gray, comment, 0, 0, out, cap);
+}
+
+long jpezy_write_jpeg_opt(const int16_t* coeffs, int W, int H, int gray, const char* comment, uint8_t* out, size_t cap)
+{
+    return host_write(coeffs, W, H, gray, comment, 0, 1, out, cap);
+}
+
 long jpezy_write_jpeg_rst(const int16_t* coeffs, int W, int H, int gray, const char* comment, int restart_interval, int optimize,
                           uint8_t* out, size_t cap)
-try {
-    std::string err;
-    const long n = jpezy_host::write_jpeg_rst(coeffs, W, H, gray != 0, comment, restart_interval, optimize != 0, out, cap, &err);
-    if (n < 0) g_err = err;
-    return n;
+{
+    return host_write(coeffs, W, H, gray, comment, restart_interval, optimize, out, cap);
 }
-JPEZY_CATCH
 
 // planar RGB on the host -> .jpg bytes on the host, both stages on the GPU (what encoder::encode does end to end)
 long jpezy_encode_jpeg(jpezy_ctx* c, const uint8_t* r, const uint8_t* g, const uint8_t* b, int W, int H, int gray, const char* comment,

@@ -1,7 +1,8 @@
 // jpezy_capi_internal.h -- what the translation units of the C-ABI share (internal): error macros, the context (owners: jpezy_owners.h).
-// jpezy_capi.hip (context, the two transform stages), jpezy_capi_entropy.hip (Huffman coding, host and GPU),
-// jpezy_capi_huffdec.hip (GPU Huffman decoding of one file, decoder::decode end to end), jpezy_capi_decode_batch.hip (the batch form),
-// jpezy_capi_packed.hip (the entry points for packed, i.e. interleaved, pixels).
+// jpezy_capi.hip (context, the two transform stages), jpezy_capi_entropy.hip (Huffman coding: the host writer's entry points, the GPU
+// coder's two forms, encoder::encode end to end), jpezy_capi_huffdec.hip (GPU Huffman decoding of one file, decoder::decode end to end),
+// jpezy_capi_decode_batch.hip (the batch form), jpezy_capi_packed.hip (the entry points for packed, i.e. interleaved, pixels),
+// jpezy_capi_multi.hip (the multi-GPU handle).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -145,12 +146,18 @@ struct jpezy_ctx {
     DevBuf d_trace;                // JPEZY_TRACE builds: 4 words per wave + 9 phase stamps (JPEZY_TRACE=3)
     DevBuf dump_t;                 // JPEZY_DUMP_T builds: level-1 t values of the last jpezy_fdct_quant_dev call
     DevBuf in[3], out, scratch;    // staging for the host-buffer entry points; scratch: samples of the generic decoder
-    // GPU entropy coder (jpezy_entropy.hip): code tables + scratch
-    DevBuf d_codes;                // jpezy_dev::entropy::CodeTables (ensure_code_tables)
-    DevBuf e_tmp, e_small, e_U, e_cnt, e_out, e_coef;
-    DevBuf e_tt, e_fft;            // totals per tile (256 coded blocks: bits) and per piece (256 chunks of 64 bytes: 0xFF bytes)
-    DevBuf e_S, e_base, e_ft;      // one-pass coder: tile streams, frame-relative tile bit offsets, first tile per 16 KB of output
+    // GPU entropy coder (jpezy_entropy.hip): code tables + the scratch of a pass (entropy::Scratch; jpezy_capi_entropy.hip's Pass::plan
+    // sizes them by entropy::scratch_sizes)
+    DevBuf d_codes;                // jpezy_dev::entropy::CodeTables, the Annex-K image (ensure_code_tables)
+    DevBuf e_S, e_tt;              // tile streams; tile totals (bits)
+    DevBuf e_base, e_ft;           // frame-relative tile bit offsets, first tile per 16 KB piece of output: frames whose assembling kernel does not scan the totals itself
+    DevBuf e_U;                    // unstuffed streams
+    DevBuf e_cnt, e_fft;           // bytes stuffing adds: in front of a chunk (64 bytes) inside its piece (256 chunks), and per piece
+    DevBuf e_small;                // [F] stream bytes (uint64) | [F] bytes stuffing adds (uint64, host-delivered form) | [F] flags (uint32): the
+                                   // host-delivered form's error flags, the device-resident form's latched copy of e_status
     DevBuf e_status;               // per-frame error flags of the device-resident entropy path: zero between calls (cleared by their consumer)
+    DevBuf e_out, e_coef;          // host-delivered form: stuffed streams; jpezy_encode_jpeg[_packed]: the frame's coefficients
+    DevBuf e_tmp;                  // scratch of entropy::launch_scan_u32 (GPU Huffman decoder)
     PinBuf e_pinned;               // pinned host staging of the stuffed streams
     int huff_optimize = 0;         // 1: the host-delivered entropy entry points build every frame's own Huffman tables (jpezy_ctx_set_huffman_optimize)
     DevBuf e_hist, e_hstat;        // per-image tables: symbol counts [frames][4][256] uint64; error flags of jpezy_huffman_histogram_dev (never read)

@@ -1,6 +1,7 @@
 // jpezy_entropy.h -- GPU Huffman coder + bit packer + byte stuffer (internal; see jpezy_entropy.hip)
 #pragma once
 #include "jpezy_experiment.h"
+#include "jpezy_host_codec.h"   // kMaxBlockBits
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
@@ -30,6 +31,11 @@ struct Job {
                                   // the whole frame (no marker, no reset: only the header differs, and the host writes that)
 };
 
+// Worst-case bytes of a coded block, 64 x (16-bit code + 10 value bits): the stride of a block in a tile's stream and the unit of
+// the worst-case stream size (stream_stride) that the scratch and the frames of a pass are sized by
+constexpr unsigned kMaxBlockBytes = 208;
+static_assert((jpezy_host::kMaxBlockBits + 7) / 8 <= kMaxBlockBytes, "a coded block must fit the bytes the coder's scratch gives it");
+
 inline size_t tiles256(size_t n) { return (n + 255) / 256; }
 
 // Tiles of a frame with restart intervals (Job::restart != 0): a tile never straddles an interval.  Every interval starts a tile of
@@ -48,68 +54,70 @@ inline size_t restart_tiles(size_t blocks_per_frame, unsigned restart)
     return (ni - 1) * restart_tpi(restart) + tiles256(blocks_per_frame - (ni - 1) * restart * 6u);
 }
 // tiles of a frame, either way
-inline size_t job_tiles(size_t blocks_per_frame, unsigned restart)
-{
-    return restart ? restart_tiles(blocks_per_frame, restart) : tiles256(blocks_per_frame);
-}
+inline size_t job_tiles(const Job& job) { return job.restart ? restart_tiles(job.blocks_per_frame, job.restart) : tiles256(job.blocks_per_frame); }
 
 // device-resident form of launch_stuff: whole files (header, stuffed stream, EOI), sizes and per-frame verdicts on the device
 struct FilePlan {
     const uint8_t* hdr = nullptr;       // nullptr: streams only (the host adds header and EOI)
     size_t hdr_len = 0;
-    const unsigned* latched = nullptr;  // [frames] error flags as latched by launch_tile_bases
+    const unsigned* latched = nullptr;  // [frames] Scratch::latched (launch_stuff sets it)
     long long* sizes = nullptr;         // [frames] file size, or JPEZY_E_FORMAT (-5) / JPEZY_E_NOSPACE (-6)
-    const unsigned long long* markers = nullptr;   // restart intervals: launch_assemble_restart's marker masks [frame][chunk]; selects the
-                                                   // stuffing kernel that places RSTn markers
+    const unsigned long long* markers = nullptr;   // restart intervals: Scratch::markers (launch_stuff sets it); selects the stuffing
+                                                   // kernel that places RSTn markers
 };
+
+// The device arrays of one pass (job.n_frames frames), scratch_sizes() bytes each.  "tile": the blocks of one coding workgroup, 256 of a
+// frame or, with restart intervals, of an interval (restart_tiles); "chunk": 64 bytes of a frame's unstuffed stream, "piece": 256 chunks.
+struct Scratch {
+    uint32_t* tile_stream;            // [frame][tile] the tile's blocks coded back to back (MSB-first words), room for 256 x kMaxBlockBytes
+    uint32_t* tile_total;             // [frame][tile] bits
+    unsigned long long* tile_base;    // [frame][tiles + 1] frame-relative bit offsets           } not read when the assembling kernel
+    uint32_t* first_tile;             // [frame][ft_stride] the tile a piece's first bit lies in } scans the tile totals itself
+    unsigned ft_stride;               // pieces of a stream: u_stride / assemble_piece_bytes()
+    unsigned long long* restart_pad;  // [frame][interval] restart intervals: launch_tile_bases' scratch
+    unsigned long long* bytes;        // [frame] length of the unstuffed stream
+    uint32_t* U;                      // [frame] unstuffed streams, u_stride bytes apart (stream_stride)
+    size_t u_stride;
+    uint32_t* ff_loc;                 // [frame][chunk] bytes the stuffing pass adds in front of the chunk inside its piece (restart intervals:
+                                      //                the top three bits hold the number mod 8 of the chunk's first marker)
+    uint32_t* ff_piece;               // [frame][piece] ... and in the whole piece: a prefix sum in two levels whose upper level every
+                                      //                stuffing workgroup adds up for itself
+    unsigned long long* markers;      // [frame][chunk] restart intervals: bit j = an RSTn marker follows byte j of the chunk
+    unsigned* status;                 // [frame] |= 1 for a coefficient outside the code tables; zero before launch_code_tiles
+    unsigned* latched;                // [frame] nullptr: status stays as the coder left it, for the host to read.  Otherwise the consumer
+                                      //         of the tile totals moves it here (latched[f] = status[f], status[f] = 0) for launch_stuff
+};
+struct ScratchSizes {
+    size_t tile_stream, tile_total, tile_base, first_tile, restart_pad, bytes, U, ff_loc, ff_piece, markers, flags;   // (flags: status, latched)
+};
+// bytes of every array of Scratch for job (job.n_frames frames); 0 for an array the pass does not use: no offsets and no first-tile
+// table when the assembling kernel scans the tile totals itself (frames of at most ASM_SELF_TILES tiles without restart intervals),
+// no pads and no markers without restart intervals.  any_tables: as launch_assemble takes it.
+ScratchSizes scratch_sizes(const Job& job, bool any_tables);
+size_t stream_stride(const Job& job);       // Scratch::u_stride: the worst-case stream of a frame (a pad byte behind every restart interval), in whole pieces
+size_t max_pass_frames(const Job& job);     // frames of a pass: worst-case streams of 1 GiB together (at least one frame)
 
 size_t scan_tmp_elems(size_t n);  // uint64 scratch elements launch_scan_u32 needs for n inputs
 size_t chunk_bytes();             // granularity of the stuffing pass (64)
-size_t tile_stream_bytes();       // stride of a tile's stream in the scratch S (worst case: 256 blocks x 208 bytes)
-size_t assemble_piece_bytes();    // bytes of U one assembling / stuffing workgroup handles (16 KB): U strides are multiples of it
+size_t assemble_piece_bytes();    // bytes of U one assembling / stuffing workgroup handles (16 KB)
 
 // out[0..n) exclusive prefix sums, out[n] the total
 hipError_t launch_scan_u32(const uint32_t* in, unsigned long long* out, size_t n, unsigned long long* tmp, hipStream_t s);
-hipError_t launch_scan_u64(const unsigned long long* in, unsigned long long* out, size_t n, unsigned long long* tmp, hipStream_t s);
 
-// One coding pass (see jpezy_entropy.hip): every block is coded once, workgroup by workgroup ("tile" = 256 coded blocks of
-// one frame), into tile streams S[frame][tile][tile_stream_bytes()], tile_total[frame][tile] bits each; status[frame] |= 1
-// for a coefficient outside the Annex-K tables.
-hipError_t launch_code_tiles(const Job& job, uint32_t* S, uint32_t* tile_total, unsigned* status, hipStream_t s);
-// frame-relative bit offsets base[frame][tiles + 1], bytes[frame] = ceil(bits / 8), first_tile[frame][ft_stride] = the tile
-// the first bit of every assemble_piece_bytes() of output lies in; latched != nullptr: latched[f] = status[f], status[f] = 0
-hipError_t launch_tile_bases(const uint32_t* tile_total, unsigned tiles_per_frame, int n_frames, unsigned long long* base,
-                             unsigned long long* bytes, uint32_t* first_tile, unsigned ft_stride, unsigned* status, unsigned* latched,
-                             hipStream_t s);
-// unstuffed streams U (stride a multiple of assemble_piece_bytes()) and the 0xFF bytes in front of every 64-byte chunk inside
-// its piece (ff_loc[frame][chunk]) + per piece (ff_tile_total[frame][piece]): a prefix sum in two levels whose upper level
-// every stuffing workgroup adds up for itself.  Frames with assemble_scans_tiles_itself(tiles): launch_tile_bases is NOT
-// needed -- the kernel scans tile_total itself, publishes bytes[frame] and (latched != nullptr) latches + clears status;
-// base / first_tile are then unused.  Larger frames: launch_tile_bases first (at most ft_stride pieces).
-bool assemble_scans_tiles_itself(size_t tiles_per_frame);
-hipError_t launch_assemble(const uint32_t* S, const uint32_t* tile_total, const unsigned long long* base, unsigned long long* bytes,
-                           const uint32_t* first_tile, unsigned ft_stride, unsigned tiles_per_frame, int n_frames, uint32_t* U,
-                           size_t u_stride_words, uint32_t* loc, uint32_t* ff_tile_total, unsigned* status, unsigned* latched, hipStream_t s,
-                           bool any_tables = false);    // any_tables: per-image tables (codes as short as one bit): a wider tile window for large frames
-hipError_t launch_stuff(const uint32_t* U, size_t u_stride_words, const unsigned long long* frame_bytes, int n_frames,
-                        const uint32_t* ff_loc, const uint32_t* ff_tile_total, uint8_t* out, size_t out_stride, FilePlan plan, hipStream_t s);
-// dst[f] = 0xFF bytes of frame f (the host-delivered form sizes its output buffer from it)
-hipError_t launch_ff_frame_totals(const uint32_t* ff_tile_total, const unsigned long long* bytes, size_t u_stride_words, int n_frames,
-                                  unsigned long long* dst, hipStream_t s);
-
-// Restart intervals (Job::restart != 0; tiles as restart_tiles() lays them out, S and tile_total from launch_code_tiles with the same job).
-// launch_restart_bases: frame-relative bit offsets base[frame][tiles + 1] in which every interval but the last ends on a byte
-// (pad[frame][intervals] is its scratch), bytes[frame], first_tile as launch_tile_bases; latches and clears status likewise.
-// launch_assemble_restart: U and the two-level prefix sums as launch_assemble, where the counts are the bytes the stuffing pass
-// ADDS: one per 0xFF byte and two per RSTn marker (a marker belongs to the chunk that holds the last byte of its interval);
-// markers[frame][chunk]: bit j = a marker follows byte j of the chunk; the top three bits of ff_loc hold the number (mod 8) of the
-// chunk's first marker.  launch_stuff places the markers when FilePlan::markers is set.
-hipError_t launch_restart_bases(const Job& job, const uint32_t* tile_total, unsigned long long* base, unsigned long long* pad,
-                                unsigned long long* bytes, uint32_t* first_tile, unsigned ft_stride, unsigned* status, unsigned* latched,
-                                hipStream_t s);
-hipError_t launch_assemble_restart(const Job& job, const uint32_t* S, const uint32_t* tile_total, const unsigned long long* base,
-                                   const unsigned long long* bytes, const uint32_t* first_tile, unsigned ft_stride, uint32_t* U,
-                                   size_t u_stride_words, uint32_t* loc, uint32_t* ff_tile_total, unsigned long long* markers, hipStream_t s);
+// One pass, all launches on one stream (see jpezy_entropy.hip), each choosing its kernel by job.restart and the self-scan rule:
+// 1. every block is coded once into its tile's stream; tile_total; status
+hipError_t launch_code_tiles(const Job& job, const Scratch& sc, hipStream_t s);
+// 2. tile_base, bytes, first_tile; latches status.  With restart intervals every interval but the last ends on a byte.  Nothing to
+//    launch when the assembling kernel scans the tile totals itself: it then publishes bytes and latches status.
+hipError_t launch_tile_bases(const Job& job, const Scratch& sc, hipStream_t s);
+// 3. U, ff_loc, ff_piece, markers.  With restart intervals the counts are the bytes the stuffing pass ADDS: one per 0xFF byte and two
+//    per RSTn marker (a marker belongs to the chunk that holds the last byte of its interval).
+//    any_tables: tables other than Annex K's (codes as short as one bit): a wider tile window for large frames
+hipError_t launch_assemble(const Job& job, const Scratch& sc, bool any_tables, hipStream_t s);
+// 4. the stuffed streams, out_stride apart, or (plan.hdr) whole files with their sizes
+hipError_t launch_stuff(const Job& job, const Scratch& sc, uint8_t* out, size_t out_stride, FilePlan plan, hipStream_t s);
+// dst[f] = bytes stuffing adds to frame f (the host-delivered form sizes its output buffer from it)
+hipError_t launch_ff_frame_totals(const Job& job, const Scratch& sc, unsigned long long* dst, hipStream_t s);
 
 // Symbol statistics for per-image optimised tables (jpezy_huffstat.hip): hist[frame][k][sym] += the number of times the coder
 // emits symbol sym from table k (DHT order: 0 YDc, 1 CDc, 2 YAc, 3 CAc) for the frame -- what code_block sees, out-of-range values

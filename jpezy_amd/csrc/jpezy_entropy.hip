@@ -2,7 +2,7 @@
 // zig-zagged coefficients, bit packing, 0xFF00 byte stuffing.  Same bytes as jpezy_host::write_jpeg / the reference's
 // encoder::encode_huffman + bofstream (ref encoder/jpezy_encoder.hpp:174-242): MSB-first bits, DC predictors per
 // component never reset, EOB only when a block ends in zeros, ZRL for runs over 15, zero pad bits before EOI.
-// With restart intervals (Job::restart, not in the reference; jpezy_host::write_jpeg_rst is the host twin) the predictors are zero at
+// With restart intervals (Job::restart, not in the reference; jpezy_host::write_jpeg's `restart` is the host twin) the predictors are zero at
 // every interval's start, every interval but the last is padded to a byte and an RSTn marker follows it: "restart intervals" below.
 //
 // What is serial in the reference is the bit cursor and pre_DC[3].  Neither is a true dependency:
@@ -198,7 +198,7 @@ __device__ __forceinline__ unsigned count_ff(uint32_t x)
 // counts the 0xFF bytes of its chunk while it has them.
 constexpr int WG = 256;                                          // coded blocks per workgroup ("tile")
 constexpr int ROW = 144, ROW_DATA = 16, ROW_LAST_WORD = 34;      // private stream: words 0..34; word 35 (bytes 140..143): its length
-constexpr unsigned TILE_STREAM_WORDS = 256 * 208 / 4;            // worst case of 208 bytes per block
+constexpr unsigned TILE_STREAM_WORDS = 256 * kMaxBlockBytes / 4;  // a tile's stream in the scratch: every block at its worst
 
 struct RowWriter {
     unsigned long long acc;         // the youngest bit is bit 0; nacc < 32 valid bits between two appends
@@ -1076,26 +1076,115 @@ hipError_t launch_scan_u32(const uint32_t* in, unsigned long long* out, size_t n
     return e != hipSuccess ? e : hipGetLastError();
 }
 
-hipError_t launch_scan_u64(const unsigned long long* in, unsigned long long* out, size_t n, unsigned long long* tmp, hipStream_t s)
+size_t chunk_bytes() { return CHUNK; }
+size_t assemble_piece_bytes() { return (size_t)256 * CHUNK; }
+
+// frames of at most ASM_SELF_TILES tiles without restart intervals: no launch between the coder and the assembling kernel
+static bool assemble_scans_tiles_itself(const Job& job) { return !job.restart && job_tiles(job) <= ASM_SELF_TILES; }
+
+size_t stream_stride(const Job& job)
 {
-    hipError_t e = scan_exclusive<unsigned long long>(in, out, n, tmp, s);
-    return e != hipSuccess ? e : hipGetLastError();
+    const size_t worst = (size_t)job.blocks_per_frame * kMaxBlockBytes + (job.restart ? restart_intervals(job.blocks_per_frame, job.restart) : 0);
+    return (worst + 8 + assemble_piece_bytes() - 1) / assemble_piece_bytes() * assemble_piece_bytes();
 }
 
-hipError_t launch_stuff(const uint32_t* U, size_t u_stride_words, const unsigned long long* frame_bytes, int n_frames,
-                        const uint32_t* ff_loc, const uint32_t* ff_tile_total, uint8_t* out, size_t out_stride, FilePlan plan, hipStream_t s)
+size_t max_pass_frames(const Job& job)
 {
-    const size_t chunks = u_stride_words * 4 / CHUNK;
-    if (!chunks || n_frames <= 0) return hipSuccess;
-    if (n_frames > 65535 || chunks % STUFF_WG) return hipErrorInvalidValue;      // the frame index is a grid dimension
-    size_t gx = chunks / STUFF_WG < 1024 ? chunks / STUFF_WG : 1024;
-    if (n_frames > 1 && gx > 128) gx = 128;
-    if (plan.markers)
-        hipLaunchKernelGGL(stuff_kernel<true>, dim3((unsigned)gx, (unsigned)n_frames), dim3(STUFF_WG), 0, s, U, u_stride_words,
-                           frame_bytes, ff_loc, ff_tile_total, out, out_stride, plan);
+    const size_t n = ((size_t)1 << 30) / stream_stride(job);
+    return n ? n : 1;
+}
+
+ScratchSizes scratch_sizes(const Job& job, bool)
+{
+    const size_t F = (size_t)job.n_frames, u_stride = stream_stride(job), pieces = u_stride / assemble_piece_bytes(), chunks = u_stride / CHUNK;
+    const bool self = assemble_scans_tiles_itself(job);
+    ScratchSizes z;
+    z.tile_stream = tiles256(job.blocks_per_frame) * F * TILE_STREAM_WORDS * sizeof(uint32_t);   // (restart intervals: more tiles, their
+    z.tile_total = job_tiles(job) * F * sizeof(uint32_t);                                        //  streams where the blocks' would lie)
+    z.tile_base = self ? 0 : (job_tiles(job) + 1) * F * sizeof(unsigned long long);
+    z.first_tile = self ? 0 : pieces * F * sizeof(uint32_t);
+    z.restart_pad = job.restart ? restart_intervals(job.blocks_per_frame, job.restart) * F * sizeof(unsigned long long) : 0;
+    z.bytes = F * sizeof(unsigned long long);
+    z.U = u_stride * F;
+    z.ff_loc = chunks * F * sizeof(uint32_t);
+    z.ff_piece = pieces * F * sizeof(uint32_t);
+    z.markers = job.restart ? chunks * F * sizeof(unsigned long long) : 0;
+    z.flags = F * sizeof(unsigned);
+    return z;
+}
+
+hipError_t launch_code_tiles(const Job& job, const Scratch& sc, hipStream_t s)
+{
+    if (!job.blocks_per_frame || job.n_frames <= 0) return hipSuccess;
+    if (job.n_frames > 65535) return hipErrorInvalidValue;                       // the frame index is a grid dimension
+    if (job.restart) {
+        if (job.restart > 65535u || job.blocks_per_frame % 6u || job.restart >= job.blocks_per_frame / 6u) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(code_tiles_kernel<true>, dim3((unsigned)job_tiles(job), (unsigned)job.n_frames), dim3(WG), 0, s, job, sc.tile_stream,
+                           sc.tile_total, sc.status);
+    } else
+        hipLaunchKernelGGL(code_tiles_kernel<false>, dim3((unsigned)job_tiles(job), (unsigned)job.n_frames), dim3(WG), 0, s, job, sc.tile_stream,
+                           sc.tile_total, sc.status);
+    return hipGetLastError();
+}
+
+hipError_t launch_tile_bases(const Job& job, const Scratch& sc, hipStream_t s)
+{
+    if (!job.blocks_per_frame || job.n_frames <= 0 || assemble_scans_tiles_itself(job)) return hipSuccess;
+    if (job.restart) {
+        if (job.restart >= job.blocks_per_frame / 6u) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(restart_bases_kernel, dim3((unsigned)job.n_frames), dim3(256), 0, s, sc.tile_total, (unsigned)job_tiles(job),
+                           restart_tpi(job.restart), (unsigned)restart_intervals(job.blocks_per_frame, job.restart), sc.tile_base, sc.restart_pad,
+                           sc.bytes, sc.first_tile, sc.ft_stride, sc.status, sc.latched);
+    } else
+        hipLaunchKernelGGL(tile_bases_kernel, dim3((unsigned)job.n_frames), dim3(256), 0, s, sc.tile_total, (unsigned)job_tiles(job), sc.tile_base,
+                           sc.bytes, sc.first_tile, sc.ft_stride, sc.status, sc.latched);
+    return hipGetLastError();
+}
+
+hipError_t launch_assemble(const Job& job, const Scratch& sc, bool any_tables, hipStream_t s)
+{
+    const size_t pieces = sc.u_stride / assemble_piece_bytes(), u_stride_words = sc.u_stride / 4;
+    const unsigned tpf = (unsigned)job_tiles(job);
+    if (!pieces || job.n_frames <= 0) return hipSuccess;
+    if (sc.u_stride % assemble_piece_bytes() || job.n_frames > 65535) return hipErrorInvalidValue;
+    // a grid for a typical stream (1024 pieces = 16 MB per frame), fewer per frame when the frames fill the chip
+    size_t gx = pieces < 1024 ? pieces : 1024;
+    if (job.n_frames > 1 && gx > 128) gx = 128;
+    const dim3 grid((unsigned)gx, (unsigned)job.n_frames);
+    if (assemble_scans_tiles_itself(job)) {
+        hipLaunchKernelGGL(assemble_kernel<true>, grid, dim3(256), 0, s, sc.tile_stream, sc.tile_total, sc.tile_base, sc.bytes, sc.first_tile, tpf,
+                           sc.ft_stride, sc.U, u_stride_words, sc.ff_loc, sc.ff_piece, sc.status, sc.latched);
+        return hipGetLastError();
+    }
+    if (pieces > sc.ft_stride) return hipErrorInvalidValue;
+    if (job.restart)
+        hipLaunchKernelGGL(assemble_restart_kernel, grid, dim3(256), 0, s, sc.tile_stream, tiles256(job.blocks_per_frame) * (size_t)TILE_STREAM_WORDS,
+                           sc.tile_total, sc.tile_base, sc.bytes, sc.first_tile, tpf, job.restart, sc.ft_stride, sc.U, u_stride_words, sc.ff_loc,
+                           sc.ff_piece, sc.markers);
+    else if (any_tables)
+        hipLaunchKernelGGL((assemble_kernel<false, ASM_WIN_ANY>), grid, dim3(256), 0, s, sc.tile_stream, sc.tile_total, sc.tile_base, sc.bytes,
+                           sc.first_tile, tpf, sc.ft_stride, sc.U, u_stride_words, sc.ff_loc, sc.ff_piece, sc.status, sc.latched);
     else
-        hipLaunchKernelGGL(stuff_kernel<false>, dim3((unsigned)gx, (unsigned)n_frames), dim3(STUFF_WG), 0, s, U, u_stride_words,
-                           frame_bytes, ff_loc, ff_tile_total, out, out_stride, plan);
+        hipLaunchKernelGGL(assemble_kernel<false>, grid, dim3(256), 0, s, sc.tile_stream, sc.tile_total, sc.tile_base, sc.bytes, sc.first_tile, tpf,
+                           sc.ft_stride, sc.U, u_stride_words, sc.ff_loc, sc.ff_piece, sc.status, sc.latched);
+    return hipGetLastError();
+}
+
+hipError_t launch_stuff(const Job& job, const Scratch& sc, uint8_t* out, size_t out_stride, FilePlan plan, hipStream_t s)
+{
+    const size_t chunks = sc.u_stride / CHUNK;
+    if (!chunks || job.n_frames <= 0) return hipSuccess;
+    if (job.n_frames > 65535 || chunks % STUFF_WG) return hipErrorInvalidValue;      // the frame index is a grid dimension
+    size_t gx = chunks / STUFF_WG < 1024 ? chunks / STUFF_WG : 1024;
+    if (job.n_frames > 1 && gx > 128) gx = 128;
+    plan.latched = sc.latched;
+    plan.markers = job.restart ? sc.markers : nullptr;
+    if (plan.markers)
+        hipLaunchKernelGGL(stuff_kernel<true>, dim3((unsigned)gx, (unsigned)job.n_frames), dim3(STUFF_WG), 0, s, sc.U, sc.u_stride / 4, sc.bytes,
+                           sc.ff_loc, sc.ff_piece, out, out_stride, plan);
+    else
+        hipLaunchKernelGGL(stuff_kernel<false>, dim3((unsigned)gx, (unsigned)job.n_frames), dim3(STUFF_WG), 0, s, sc.U, sc.u_stride / 4, sc.bytes,
+                           sc.ff_loc, sc.ff_piece, out, out_stride, plan);
     return hipGetLastError();
 }
 
@@ -1116,97 +1205,11 @@ __global__ __launch_bounds__(256) void ff_frame_totals_kernel(const uint32_t* ff
     if (threadIdx.x == 0) dst[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
 }
 
-hipError_t launch_ff_frame_totals(const uint32_t* ff_tile_total, const unsigned long long* bytes, size_t u_stride_words, int n_frames,
-                                  unsigned long long* dst, hipStream_t s)
+hipError_t launch_ff_frame_totals(const Job& job, const Scratch& sc, unsigned long long* dst, hipStream_t s)
 {
-    if (n_frames <= 0) return hipSuccess;
-    hipLaunchKernelGGL(ff_frame_totals_kernel, dim3((unsigned)n_frames), dim3(256), 0, s, ff_tile_total, bytes,
-                       u_stride_words * 4 / assemble_piece_bytes(), dst);
-    return hipGetLastError();
-}
-
-size_t chunk_bytes() { return CHUNK; }
-
-size_t tile_stream_bytes() { return (size_t)TILE_STREAM_WORDS * 4; }
-size_t assemble_piece_bytes() { return (size_t)256 * CHUNK; }
-
-hipError_t launch_code_tiles(const Job& job, uint32_t* S, uint32_t* tile_total, unsigned* status, hipStream_t s)
-{
-    if (!job.blocks_per_frame || job.n_frames <= 0) return hipSuccess;
-    if (job.n_frames > 65535) return hipErrorInvalidValue;                       // the frame index is a grid dimension
-    if (job.restart) {
-        if (job.restart > 65535u || job.blocks_per_frame % 6u || job.restart >= job.blocks_per_frame / 6u) return hipErrorInvalidValue;
-        hipLaunchKernelGGL(code_tiles_kernel<true>, dim3((unsigned)restart_tiles(job.blocks_per_frame, job.restart), (unsigned)job.n_frames),
-                           dim3(WG), 0, s, job, S, tile_total, status);
-    } else
-    hipLaunchKernelGGL(code_tiles_kernel<false>, dim3((unsigned)tiles256(job.blocks_per_frame), (unsigned)job.n_frames), dim3(WG), 0, s, job, S,
-                       tile_total, status);
-    return hipGetLastError();
-}
-
-hipError_t launch_restart_bases(const Job& job, const uint32_t* tile_total, unsigned long long* base, unsigned long long* pad,
-                                unsigned long long* bytes, uint32_t* first_tile, unsigned ft_stride, unsigned* status, unsigned* latched,
-                                hipStream_t s)
-{
-    if (!job.blocks_per_frame || job.n_frames <= 0) return hipSuccess;
-    if (!job.restart || job.restart >= job.blocks_per_frame / 6u) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(restart_bases_kernel, dim3((unsigned)job.n_frames), dim3(256), 0, s, tile_total,
-                       (unsigned)restart_tiles(job.blocks_per_frame, job.restart), restart_tpi(job.restart),
-                       (unsigned)restart_intervals(job.blocks_per_frame, job.restart), base, pad, bytes, first_tile, ft_stride, status, latched);
-    return hipGetLastError();
-}
-
-hipError_t launch_assemble_restart(const Job& job, const uint32_t* S, const uint32_t* tile_total, const unsigned long long* base,
-                                   const unsigned long long* bytes, const uint32_t* first_tile, unsigned ft_stride, uint32_t* U,
-                                   size_t u_stride_words, uint32_t* loc, uint32_t* ff_tile_total, unsigned long long* markers, hipStream_t s)
-{
-    const size_t pieces = u_stride_words * 4 / assemble_piece_bytes();
-    if (!pieces || job.n_frames <= 0) return hipSuccess;
-    if (u_stride_words * 4 % assemble_piece_bytes() || job.n_frames > 65535 || pieces > ft_stride || !job.restart) return hipErrorInvalidValue;
-    size_t gx = pieces < 1024 ? pieces : 1024;                   // (the grid of launch_assemble)
-    if (job.n_frames > 1 && gx > 128) gx = 128;
-    hipLaunchKernelGGL(assemble_restart_kernel, dim3((unsigned)gx, (unsigned)job.n_frames), dim3(256), 0, s, S,
-                       tiles256(job.blocks_per_frame) * (size_t)TILE_STREAM_WORDS, tile_total, base, bytes, first_tile,
-                       (unsigned)restart_tiles(job.blocks_per_frame, job.restart), job.restart, ft_stride, U, u_stride_words, loc,
-                       ff_tile_total, markers);
-    return hipGetLastError();
-}
-
-hipError_t launch_tile_bases(const uint32_t* tile_total, unsigned tiles_per_frame, int n_frames, unsigned long long* base,
-                             unsigned long long* bytes, uint32_t* first_tile, unsigned ft_stride, unsigned* status, unsigned* latched,
-                             hipStream_t s)
-{
-    if (!tiles_per_frame || n_frames <= 0) return hipSuccess;
-    hipLaunchKernelGGL(tile_bases_kernel, dim3((unsigned)n_frames), dim3(256), 0, s, tile_total, tiles_per_frame, base, bytes, first_tile,
-                       ft_stride, status, latched);
-    return hipGetLastError();
-}
-
-bool assemble_scans_tiles_itself(size_t tiles_per_frame) { return tiles_per_frame <= ASM_SELF_TILES; }
-
-hipError_t launch_assemble(const uint32_t* S, const uint32_t* tile_total, const unsigned long long* base, unsigned long long* bytes,
-                           const uint32_t* first_tile, unsigned ft_stride, unsigned tiles_per_frame, int n_frames, uint32_t* U,
-                           size_t u_stride_words, uint32_t* loc, uint32_t* ff_tile_total, unsigned* status, unsigned* latched, hipStream_t s,
-                           bool any_tables)
-{
-    const size_t pieces = u_stride_words * 4 / assemble_piece_bytes();
-    if (!pieces || n_frames <= 0) return hipSuccess;
-    if (u_stride_words * 4 % assemble_piece_bytes() || n_frames > 65535) return hipErrorInvalidValue;
-    // a grid for a typical stream (1024 pieces = 16 MB per frame), fewer per frame when the frames fill the chip
-    size_t gx = pieces < 1024 ? pieces : 1024;
-    if (n_frames > 1 && gx > 128) gx = 128;
-    if (assemble_scans_tiles_itself(tiles_per_frame)) {
-        hipLaunchKernelGGL(assemble_kernel<true>, dim3((unsigned)gx, (unsigned)n_frames), dim3(256), 0, s, S, tile_total, base, bytes, first_tile,
-                           tiles_per_frame, ft_stride, U, u_stride_words, loc, ff_tile_total, status, latched);
-    } else {
-        if (pieces > ft_stride) return hipErrorInvalidValue;
-        if (any_tables)
-            hipLaunchKernelGGL((assemble_kernel<false, ASM_WIN_ANY>), dim3((unsigned)gx, (unsigned)n_frames), dim3(256), 0, s, S, tile_total, base,
-                               bytes, first_tile, tiles_per_frame, ft_stride, U, u_stride_words, loc, ff_tile_total, status, latched);
-        else
-        hipLaunchKernelGGL(assemble_kernel<false>, dim3((unsigned)gx, (unsigned)n_frames), dim3(256), 0, s, S, tile_total, base, bytes,
-                           first_tile, tiles_per_frame, ft_stride, U, u_stride_words, loc, ff_tile_total, status, latched);
-    }
+    if (job.n_frames <= 0) return hipSuccess;
+    hipLaunchKernelGGL(ff_frame_totals_kernel, dim3((unsigned)job.n_frames), dim3(256), 0, s, sc.ff_piece, sc.bytes,
+                       sc.u_stride / assemble_piece_bytes(), dst);
     return hipGetLastError();
 }
 

@@ -9,6 +9,7 @@
 #include "jpezy_host_codec.h"
 
 #include <cstring>
+#include <optional>
 #if defined(__SSE2__)
 #include <emmintrin.h>
 #endif
@@ -230,7 +231,7 @@ size_t jpeg_bound(int W, int H)
     const size_t nmcu = (size_t)((W + 15) / 16) * (size_t)((H + 15) / 16);
     // Worst case with ANY tables optimal_table can return (Annex K included): a DC code of at most kMaxDcCodeBits = 12 bits (13
     // leaves with the reserved symbol) + 11 value bits, 63 AC codes of at most 16 bits (Figure K.3) + 10 value bits:
-    // kMaxBlockBits = 1661 bits per block (207.6 bytes: the 208 bytes per block of the GPU coder's scratch hold it),
+    // kMaxBlockBits = 1661 bits per block (207.6 bytes: the GPU coder's scratch gives a block entropy::kMaxBlockBytes),
     // kMaxMcuBits = 9966 bits = 1246 bytes per MCU, 2492 if every byte were 0xFF and stuffed; pad byte (two if stuffed) and EOI
     // fit in the 196 bytes left of 2688 = 6 * 64 * 7.  A table never has more symbols than its Annex-K counterpart (12 / 162),
     // so no header is longer than the Annex-K one: the 1024 bytes and JPEZY_MAX_COMMENT stand.  (static_asserts: jpezy_host_codec.h)
@@ -238,31 +239,6 @@ size_t jpeg_bound(int W, int H)
     // so at one MCU per interval 4 bytes per MCU; with the frame's own pad and EOI (4 bytes, once) that is still inside the 196 bytes
     // 2492 leaves of 2688.  The six DRI bytes come out of the comment's room (JPEZY_MAX_COMMENT_RESTART).  (tests/test_restart_host.py)
     return 1024 + nmcu * 6 * 64 * 7;
-}
-
-namespace {
-int check_write_args(const int16_t* coeffs, int W, int H, const char* comment, const uint8_t* out, std::string* err)
-{
-    if (!coeffs || !out || W <= 0 || H <= 0 || W > 65535 || H > 65535) {
-        if (err) *err = "write_jpeg: bad argument";
-        return JPEZY_E_BADARG;
-    }
-    if (!comment_ok(comment)) {
-        if (err) *err = "write_jpeg: comment longer than JPEZY_MAX_COMMENT (" + std::to_string(JPEZY_MAX_COMMENT) + " bytes)";
-        return JPEZY_E_BADARG;
-    }
-    return JPEZY_OK;
-}
-
-long write_jpeg_with(const EncTables& T, const HuffTable* tabs, const int16_t* coeffs, int W, int H, bool gray, const char* comment,
-                     uint8_t* out, size_t cap, std::string* err, int restart = 0);
-}  // namespace
-
-long write_jpeg(const int16_t* coeffs, int W, int H, bool gray, const char* comment, uint8_t* out, size_t cap,
-                std::string* err)
-{
-    if (int rc = check_write_args(coeffs, W, H, comment, out, err)) return rc;
-    return write_jpeg_with(enc_tables(), nullptr, coeffs, W, H, gray, comment, out, cap, err);
 }
 
 // ---- per-image optimised tables ----
@@ -362,24 +338,17 @@ int optimal_table(const unsigned long long freq_in[256], uint8_t bits_out[16], u
     return nval;
 }
 
-long write_jpeg_opt(const int16_t* coeffs, int W, int H, bool gray, const char* comment, uint8_t* out, size_t cap, std::string* err)
+long write_jpeg(const int16_t* coeffs, int W, int H, bool gray, const char* comment, int restart, bool optimize, uint8_t* out, size_t cap,
+                std::string* err)
 {
-    if (int rc = check_write_args(coeffs, W, H, comment, out, err)) return rc;
-    unsigned long long hist[4][256];
-    if (!symbol_histogram(coeffs, W, H, gray, hist)) {
-        if (err) *err = "write_jpeg: coefficient outside the code tables";
-        return JPEZY_E_FORMAT;
+    if (!coeffs || !out || W <= 0 || H <= 0 || W > 65535 || H > 65535) {
+        if (err) *err = "write_jpeg: bad argument";
+        return JPEZY_E_BADARG;
     }
-    HuffTable tabs[4];
-    for (int k = 0; k < 4; ++k) tabs[k].nval = optimal_table(hist[k], tabs[k].bits, tabs[k].vals);
-    const EncTables T(tabs);
-    return write_jpeg_with(T, tabs, coeffs, W, H, gray, comment, out, cap, err);
-}
-
-long write_jpeg_rst(const int16_t* coeffs, int W, int H, bool gray, const char* comment, int restart, bool optimize, uint8_t* out,
-                    size_t cap, std::string* err)
-{
-    if (int rc = check_write_args(coeffs, W, H, comment, out, err)) return rc;
+    if (!comment_ok(comment)) {
+        if (err) *err = "write_jpeg: comment longer than JPEZY_MAX_COMMENT (" + std::to_string(JPEZY_MAX_COMMENT) + " bytes)";
+        return JPEZY_E_BADARG;
+    }
     if (restart < 0 || restart > 65535) {
         if (err) *err = "write_jpeg: restart interval must be in 0..65535 MCUs";
         return JPEZY_E_BADARG;
@@ -389,25 +358,21 @@ long write_jpeg_rst(const int16_t* coeffs, int W, int H, bool gray, const char* 
                         std::to_string(JPEZY_MAX_COMMENT_RESTART) + " bytes)";
         return JPEZY_E_BADARG;
     }
-    if (!optimize) return write_jpeg_with(enc_tables(), nullptr, coeffs, W, H, gray, comment, out, cap, err, restart);
-    // the symbols THIS scan emits: the DC difference at an interval start is taken against 0
-    unsigned long long hist[4][256];
-    if (!symbol_histogram(coeffs, W, H, gray, hist, restart)) {
-        if (err) *err = "write_jpeg: coefficient outside the code tables";
-        return JPEZY_E_FORMAT;
-    }
     HuffTable tabs[4];
-    for (int k = 0; k < 4; ++k) tabs[k].nval = optimal_table(hist[k], tabs[k].bits, tabs[k].vals);
-    const EncTables T(tabs);
-    return write_jpeg_with(T, tabs, coeffs, W, H, gray, comment, out, cap, err, restart);
-}
+    std::optional<EncTables> own;
+    if (optimize) {      // the frame's own tables, from the symbols THIS scan emits: the DC difference at an interval start is taken against 0
+        unsigned long long hist[4][256];
+        if (!symbol_histogram(coeffs, W, H, gray, hist, restart)) {
+            if (err) *err = "write_jpeg: coefficient outside the code tables";
+            return JPEZY_E_FORMAT;
+        }
+        for (int k = 0; k < 4; ++k) tabs[k].nval = optimal_table(hist[k], tabs[k].bits, tabs[k].vals);
+        own.emplace(tabs);
+    }
+    const EncTables& T = own ? *own : enc_tables();
 
-namespace {
-long write_jpeg_with(const EncTables& T, const HuffTable* tabs, const int16_t* coeffs, int W, int H, bool gray, const char* comment,
-                     uint8_t* out, size_t cap, std::string* err, int restart)
-{
     BitSink o(out, cap);
-    put_header(o, W, H, comment, tabs, restart);
+    put_header(o, W, H, comment, optimize ? tabs : nullptr, restart);
 
     static const int16_t kZeroBlock[64] = { 0 };
     const size_t nmcu = (size_t)((W + 15) / 16) * (size_t)((H + 15) / 16);
@@ -437,7 +402,6 @@ long write_jpeg_with(const EncTables& T, const HuffTable* tabs, const int16_t* c
     }
     return (long)o.size();
 }
-}  // namespace
 
 // ======================================================================================================
 // reader

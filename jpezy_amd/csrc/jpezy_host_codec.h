@@ -11,8 +11,12 @@
 
 namespace jpezy_host {
 
-// ref encoder/jpezy_writer.hpp:20-105 + encoder/jpezy_encoder.hpp:174-242
-long write_jpeg(const int16_t* coeffs, int W, int H, bool gray, const char* comment, uint8_t* out, size_t cap,
+// ref encoder/jpezy_writer.hpp:20-105 + encoder/jpezy_encoder.hpp:174-242: header, entropy-coded segment, EOI; the size or a JPEZY_E_* status.
+// restart: MCUs per restart interval (0: none, as the reference): DRI in the header; behind every interval but the last the bits are
+// padded to a byte (JPEZY_PAD_BIT) and RSTn (n = interval index mod 8) follows; predictors zero at every interval's start.
+// optimize: the frame's own optimal tables (below), built from the symbols this scan emits, for Annex K's: same coefficients, same decoded
+// pixels, a smaller file.
+long write_jpeg(const int16_t* coeffs, int W, int H, bool gray, const char* comment, int restart, bool optimize, uint8_t* out, size_t cap,
                 std::string* err);
 size_t jpeg_bound(int W, int H);
 // false for a comment longer than JPEZY_MAX_COMMENT: every writer refuses it (JPEZY_E_BADARG)
@@ -38,7 +42,7 @@ constexpr int kMaxDcCodeBits = 12;      // 12 categories + the reserved symbol =
 constexpr int kMaxAcCodeBits = 16;      // Figure K.3
 constexpr int kMaxBlockBits = kMaxDcCodeBits + 11 + 63 * (kMaxAcCodeBits + 10);      // 1661
 constexpr int kMaxMcuBits = 6 * kMaxBlockBits;                                        // 9966
-static_assert(kMaxBlockBits == 1661 && (kMaxBlockBits + 7) / 8 <= 208, "a coded block must fit the 208 bytes the GPU coder's scratch gives it");
+static_assert(kMaxBlockBits == 1661, "the GPU coder's scratch gives a coded block entropy::kMaxBlockBytes (jpezy_entropy.h ties the two)");
 static_assert(kMaxMcuBits == 9966 && 2 * ((kMaxMcuBits + 7) / 8) + 2 + 2 <= 2688, "jpeg_bound: a stuffed MCU, pad byte and EOI within 2688 bytes");
 static_assert(kMaxDcCodeBits + 11 <= 31 && kMaxAcCodeBits + 10 <= 31, "one append of the GPU coder (code + value bits) is at most 31 bits");
 // freq[sym] -> (bits, vals) of the optimal prefix code with no code longer than 16 bits and none of all ones; returns the
@@ -49,13 +53,6 @@ int optimal_table(const unsigned long long freq[256], uint8_t bits[16], uint8_t 
 // outside the code tables (DC category over 11, |AC| > 1023): counted as the largest size.
 // restart: MCUs per restart interval (0: none); the DC predictors are zero at every interval's start
 bool symbol_histogram(const int16_t* coeffs, int W, int H, bool gray, unsigned long long hist[4][256], int restart = 0);
-// write_jpeg with the frame's own optimal tables: same coefficients, same decoded pixels, a smaller file
-long write_jpeg_opt(const int16_t* coeffs, int W, int H, bool gray, const char* comment, uint8_t* out, size_t cap, std::string* err);
-// write_jpeg with restart intervals of `restart` MCUs (0: none): DRI in the header; behind every interval but the last the bits are
-// padded to a byte (JPEZY_PAD_BIT) and RSTn (n = interval index mod 8) follows; predictors zero at every interval's start.
-// optimize: the frame's own tables, built from the symbols this scan emits.
-long write_jpeg_rst(const int16_t* coeffs, int W, int H, bool gray, const char* comment, int restart, bool optimize, uint8_t* out,
-                    size_t cap, std::string* err);
 
 // What the entropy decoder needs besides jpezy_frame_info: where the scan data start, the raw DHT specifications
 // (slot = tc*4 + th: 0..3 DC, 4..7 AC) and the table selector of each scan component (the reference uses Td for both

@@ -44,9 +44,9 @@ int main(int argc, char** argv)
         const bool own = info.ncomp == 3 && info.H[0] == 2 && info.V[0] == 2 && info.H[1] == 1 && info.V[1] == 1 && info.H[2] == 1 && info.V[2] == 1;
         if (own && info.width > 0 && info.height > 0) {
             std::vector<unsigned char> out(jpezy_host::jpeg_bound(info.width, info.height));
-            (void)jpezy_host::write_jpeg(co.data(), info.width, info.height, false, nullptr, out.data(), out.size(), &err);
+            (void)jpezy_host::write_jpeg(co.data(), info.width, info.height, false, nullptr, 0, false, out.data(), out.size(), &err);
             // a deliberately short buffer must be refused, not overrun
-            (void)jpezy_host::write_jpeg(co.data(), info.width, info.height, false, nullptr, out.data(), out.size() / 16, &err);
+            (void)jpezy_host::write_jpeg(co.data(), info.width, info.height, false, nullptr, 0, false, out.data(), out.size() / 16, &err);
             ++rewritten;
         }
     }

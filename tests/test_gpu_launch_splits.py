@@ -299,22 +299,21 @@ def test_gpu_writer_across_the_65535_frame_split(J, ctx, oracle):
 
 
 def _frames_per_pass(J, W, H):
-    """the writer's pass rule (jpezy_capi_entropy.hip): worst-case streams of 208 bytes per block, at most 1 GiB per pass"""
+    """the pass rule of both forms of the writer (jpezy_entropy.hip): worst-case streams of 208 bytes per block in whole 16 KB pieces,
+    at most 1 GiB of them per pass"""
     mc, mr = J.mcu_grid(W, H)
     nblk = mc * mr * 6
     piece = 16384
     u_stride = (nblk * 208 + 8 + piece - 1) // piece * piece
-    per_dev = min(65535, (1 << 30) // u_stride)
-    per_host = min(65535, (1 << 30) // (nblk * 208 + 4096))
-    return per_dev, per_host
+    return min(65535, (1 << 30) // u_stride)
 
 
 def test_gpu_writer_across_the_worst_case_pass_split(J, ctx, oracle):
     """1080p: passes of `per` frames; per + 2 frames of mixed dense and sparse content, two of them refused at the seam"""
     import torch
     W, H = 1920, 1080
-    per, per_host = _frames_per_pass(J, W, H)
-    assert per == per_host == 105
+    per = _frames_per_pass(J, W, H)
+    assert per == 105
     n = per + 2
     assert per < n
     mc, mr = J.mcu_grid(W, H)

@@ -437,8 +437,47 @@ def test_out_of_range_coefficient(J, ctx):
             ctx.write_jpeg_gpu(_dev(co), 272, 48)
         good = _frames(272, 48, False)[0]
         assert ctx.write_jpeg_gpu(_dev(good), 272, 48)[0] == J.write_jpeg(good, 272, 48, restart_interval=3)
+        _flags_do_not_leak_between_the_two_forms(J, ctx)
     finally:
         ctx.set_restart_interval(0)
+
+
+def _flags_do_not_leak_between_the_two_forms(J, ctx):
+    """Both forms keep their per-frame error flags in one scratch layout of the context.  272 x 48 (51 MCUs, two tiles), Ri = 3, three
+    frames, the middle one with a coefficient of 1024: the host-delivered form, then the device-resident form, refuse frame 1 alone;
+    the three good frames through the device-resident and then the host-delivered form: nothing is left of the refusals."""
+    import ctypes as C
+    import torch
+    W, H, n = 272, 48, 3
+    lib = J.load_library()
+    cap = ctx_bound(W, H)
+    good = np.array(_frames(W, H, False))
+    bad = good.copy()
+    bad[1, 20, 2, 7] = 1024
+    want = [J.write_jpeg(good[f], W, H, restart_interval=3) for f in range(n)]
+
+    def batch(co):
+        buf = np.zeros(cap * n, np.uint8)
+        sizes = (C.c_long * n)()
+        rc = lib.jpezy_write_jpeg_gpu_batch(ctx._h, _dev(co).data_ptr(), W, H, 0, n, b"Encoded by jpezy", buf.ctypes.data_as(C.c_void_p), cap, sizes)
+        return rc, [sizes[f] if sizes[f] < 0 else buf[f * cap: f * cap + sizes[f]].tobytes() for f in range(n)]
+
+    def dev(co):
+        out = torch.zeros((n, cap), dtype=torch.uint8, device="cuda")
+        sizes = torch.zeros(n, dtype=torch.int64, device="cuda")
+        ctx.write_jpeg_gpu_dev(_dev(co), W, H, out, sizes, n_frames=n)
+        torch.cuda.synchronize()
+        sz, host = sizes.cpu().numpy(), out.cpu().numpy()
+        return [int(sz[f]) if sz[f] < 0 else host[f, :sz[f]].tobytes() for f in range(n)]
+
+    FORMAT = -5
+    rc, got = batch(bad)
+    assert rc == FORMAT and got == [want[0], FORMAT, want[2]], (rc, [g if isinstance(g, int) else len(g) for g in got])
+    got = dev(bad)
+    assert got == [want[0], FORMAT, want[2]], [g if isinstance(g, int) else len(g) for g in got]
+    assert dev(good) == want
+    rc, got = batch(good)
+    assert rc == 0 and got == want
 
 
 # ---- round trips ----

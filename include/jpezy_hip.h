@@ -510,6 +510,58 @@ long jpezy_encode_jpeg_packed(jpezy_ctx* ctx, const uint8_t* pix, int format, si
 int jpezy_decode_jpeg_packed(jpezy_ctx* ctx, const uint8_t* data, size_t len, int gray, jpezy_frame_info* info, int format, size_t row_stride,
                              uint8_t* pix, size_t pix_cap);
 
+/*
+ * REDUCED-SIZE DECODE (1/2, 1/4, 1/8).  scale_denom is 1, 2, 4 or 8 and N = 8 / scale_denom is the edge of a block in output samples;
+ * the output is Ws x Hs = ceil(W*N/8) x ceil(H*N/8).  The reference has no such mode: the definition is this project's own
+ * and says that the result is what the reference's decode loop would give if its block were N x N instead of 8 x 8:
+ *
+ *   dequantise    as always (decoder/jpezy_decoder.hpp:645-650): dct[nat] = (int)coef * qt[Tq][nat], 32-bit int
+ *   transform     inverse_dct (:652-670) over the N x N low-frequency corner, for y, x < N: sum = 0.0; v = 0..N-1 outer, u = 0..N-1 inner:
+ *                 sum += cu * cv * dct[v*8+u] * COS[(u*8/N)*8 + x] * COS[(v*8/N)*8 + y], left to right in binary64 without contraction, COS the
+ *                 8-point table (cos((2x+1)u*pi/2N) is its entry (u*8/N, x)); sample = int(sum / 4 + level) with the reference's conversion
+ *                 (INT_MIN outside int32), level = 128 or 2048.  The 1/4 holds for every N: an N-point inverse fed 8-point-scaled
+ *                 coefficients has that normalisation; for N = 1 the sample is int(DC*Q/8 + level), the block mean
+ *   placement     decode_mcu (:504-528) with N for 8: the MCU is hmax*N x vmax*N, block (kx, ky) is written at (kx*N, ky*N) as a rectangle of
+ *                 N*dupx x N*dupy, the last writer stays, unwritten positions keep 0 / 0x80, rows >= Hs and columns >= Ws are dropped.  A
+ *                 subsampled component is replicated as the reference replicates it, not given a larger transform
+ *   colour        make_rgb / revise_value and gray (:531-578, 672-676) unchanged
+ *
+ * Every layout jpezy_decode_jpeg accepts is accepted, jpezy's own included: all of them take the two kernels of jpezy_kernels_scaled.hip
+ * (every sample evaluated directly in the order above: no fast path, no guard band).  jpezy_ctx_set_force_exact and
+ * jpezy_ctx_set_decode_tolerance therefore have nothing to act on here, and the fallback counter is not advanced.
+ * scale_denom = 1 is handed to the full-size entry point named with each function, under that entry's own rules: byte for byte the existing decode.
+ * JPEZY_E_BADARG for any other denominator.
+ */
+/* Ws, Hs (either may be NULL) for a W x H file; JPEZY_E_BADARG for a denominator outside {1, 2, 4, 8} or a non-positive size.  Pure host
+ * function. */
+int jpezy_scaled_size(int W, int H, int scale_denom, int* Ws, int* Hs);
+/* jpezy_dequant_idct_generic_batch_dev at reduced size (stands in for decoder/jpezy_decoder.hpp:504-578, 645-676 with an N x N block; the
+ * reference has no such mode, the definition above is this project's own): d_r, d_g, d_b planes of Ws*Hs bytes, frame f's at
+ * + f * plane_stride (>= Ws*Hs, no alignment asked).  The generic entry's table, scratch (one call in flight per context) and capture rules
+ * apply; more than 65535 frames go out as several pairs of launches.  scale_denom 1: jpezy_dequant_idct_generic_dev for one frame,
+ * jpezy_dequant_idct_generic_batch_dev (plane_stride a multiple of 4) for more. */
+int jpezy_dequant_idct_scaled_dev(jpezy_ctx* ctx, const int16_t* d_coeffs, const uint16_t qt[4][64], int ncomp, const uint8_t comp_h[3],
+                                  const uint8_t comp_v[3], const uint8_t comp_tq[3], int precision, int W, int H, int gray, int scale_denom,
+                                  int n_frames, size_t plane_stride, uint8_t* d_r, uint8_t* d_g, uint8_t* d_b, void* stream);
+/* The same writing packed pixels (same reference lines, same remark: no such mode in the reference, the definition is this project's own).
+ * The addressing rules of the packed section apply with Ws, Hs for W, H: pixel (x, y) of frame f at d_pix + f*frame_stride + y*row_stride +
+ * x*bytes, row_stride 0 = Ws*bytes, frame_stride 0 = Hs*row_stride, only bytes [0, Ws*bytes) of a row are written, byte 3 of a 32-bit pixel
+ * is 0xFF.  scale_denom 1: the generic kernels' packed store stage (n_frames > 1 then asks for a frame_stride that is a multiple of 4). */
+int jpezy_dequant_idct_scaled_packed_dev(jpezy_ctx* ctx, const int16_t* d_coeffs, const uint16_t qt[4][64], int ncomp,
+                                         const uint8_t comp_h[3], const uint8_t comp_v[3], const uint8_t comp_tq[3], int precision, int W,
+                                         int H, int gray, int scale_denom, int format, size_t row_stride, size_t frame_stride, int n_frames,
+                                         uint8_t* d_pix, void* stream);
+/* jpezy_decode_jpeg at reduced size (decoder/jpezy_decoder.hpp:76-134 with the transform stage above; the reference has no such mode, the
+ * definition is this project's own): header parse and Huffman decoding exactly as jpezy_decode_jpeg does them (GPU decoder, host decoder
+ * for what it declines), then the scaled stage and a download of Ws*Hs bytes per plane.  info keeps the FILE's width and height.  r, g, b
+ * NULL: header only; plane_cap < Ws*Hs: JPEZY_E_NOSPACE.  scale_denom 1: jpezy_decode_jpeg. */
+int jpezy_decode_jpeg_scaled(jpezy_ctx* ctx, const uint8_t* data, size_t len, int gray, int scale_denom, jpezy_frame_info* info, uint8_t* r,
+                             uint8_t* g, uint8_t* b, size_t plane_cap);
+/* The same into host packed pixels (jpezy_decode_jpeg_packed at reduced size; same reference lines and remark): pix NULL: header only;
+ * pix_cap < (Hs-1)*row_stride + Ws*bytes: JPEZY_E_NOSPACE.  scale_denom 1: jpezy_decode_jpeg_packed. */
+int jpezy_decode_jpeg_scaled_packed(jpezy_ctx* ctx, const uint8_t* data, size_t len, int gray, int scale_denom, jpezy_frame_info* info,
+                                    int format, size_t row_stride, uint8_t* pix, size_t pix_cap);
+
 #ifdef __cplusplus
 }
 #endif

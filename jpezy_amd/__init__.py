@@ -26,6 +26,7 @@ from .api import (  # noqa: F401
     mcu_grid,
     optimal_table,
     read_jpeg,
+    scaled_size,
     shard_range,
     write_jpeg,
     write_jpeg_batch,
@@ -33,5 +34,5 @@ from .api import (  # noqa: F401
 
 __all__ = [
     "Context", "Decoder", "Encoder", "FrameInfo", "JpezyError", "MultiEncoder", "PIX_BGR24", "PIX_BGRA32", "PIX_RGB24", "PIX_RGBA32", "coeff_count", "encode_batch_multi", "library_path",
-    "load_library", "mcu_grid", "optimal_table", "read_jpeg", "shard_range", "write_jpeg", "write_jpeg_batch",
+    "load_library", "mcu_grid", "optimal_table", "read_jpeg", "scaled_size", "shard_range", "write_jpeg", "write_jpeg_batch",
 ]

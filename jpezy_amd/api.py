@@ -109,6 +109,13 @@ ABI = [
     ("jpezy_dequant_idct_packed_dev", C.c_int, [_vp, _vp, _QT, _TQ, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     ("jpezy_encode_jpeg_packed", C.c_long, [_vp, _vp, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_char_p, _vp, C.c_size_t]),
     ("jpezy_decode_jpeg_packed", C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.POINTER(FrameInfo), C.c_int, C.c_size_t, _vp, C.c_size_t]),
+    ("jpezy_scaled_size", C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    ("jpezy_dequant_idct_scaled_dev", C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t,
+                                                _vp, _vp, _vp, _vp]),
+    ("jpezy_dequant_idct_scaled_packed_dev", C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                       C.c_size_t, C.c_size_t, C.c_int, _vp, _vp]),
+    ("jpezy_decode_jpeg_scaled", C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.c_int, C.POINTER(FrameInfo), _vp, _vp, _vp, C.c_size_t]),
+    ("jpezy_decode_jpeg_scaled_packed", C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.c_int, C.POINTER(FrameInfo), C.c_int, C.c_size_t, _vp, C.c_size_t]),
 ]
 
 # enum jpezy_pixel_format: packed (interleaved) pixels, 3 or 4 bytes each
@@ -162,6 +169,13 @@ def mcu_grid(W, H):
 
 def coeff_count(W, H, gray=False):
     return load_library().jpezy_coeff_count(W, H, int(gray))
+
+
+def scaled_size(W, H, scale):
+    """(Ws, Hs) of a W x H file decoded at 1/scale (scale 1, 2, 4 or 8): ceil(W * n / 8), ceil(H * n / 8) with n = 8 / scale"""
+    ws, hs = C.c_int(), C.c_int()
+    _check(load_library().jpezy_scaled_size(int(W), int(H), int(scale), C.byref(ws), C.byref(hs)))
+    return ws.value, hs.value
 
 
 def _np_ptr(a):
@@ -499,6 +513,57 @@ class Context:
         _check(load_library().jpezy_dequant_idct_packed_dev(self._h, d_coeffs.data_ptr(), C.byref(qtab), C.byref(tq), int(format), row, frame,
                                                             W, H, int(gray), n, d_img.data_ptr(), stream))
 
+    # ---- reduced-size decode (scale 1, 2, 4, 8: an N x N inverse transform per block, N = 8 / scale; include/jpezy_hip.h) ----
+    def decode_jpeg_scaled(self, data, scale, gray=False):
+        """.jpg bytes -> (FrameInfo, r, g, b) planes of Ws*Hs bytes, (Ws, Hs) = scaled_size(width, height, scale); the FrameInfo keeps
+        the file's own width and height.  scale 1 is decode_jpeg."""
+        lib = load_library()
+        arr = np.frombuffer(bytes(data), dtype=np.uint8)
+        info = FrameInfo()
+        _check(lib.jpezy_decode_jpeg_scaled(self._h, _np_ptr(arr), arr.size, int(gray), int(scale), C.byref(info), None, None, None, 0))
+        ws, hs = scaled_size(info.width, info.height, scale)
+        n = ws * hs
+        r, g, b = (np.empty(n, dtype=np.uint8) for _ in range(3))
+        _check(lib.jpezy_decode_jpeg_scaled(self._h, _np_ptr(arr), arr.size, int(gray), int(scale), C.byref(info), _np_ptr(r), _np_ptr(g),
+                                            _np_ptr(b), n))
+        return info, r, g, b
+
+    def decode_jpeg_scaled_packed(self, data, scale, format=PIX_RGB24, gray=False):
+        """.jpg bytes -> (FrameInfo, uint8 array (Hs, Ws, C)) of interleaved pixels at 1/scale; the fourth byte of a 32-bit format is 0xFF."""
+        lib = load_library()
+        nb = pixel_bytes(format)
+        arr = np.frombuffer(bytes(data), dtype=np.uint8)
+        info = FrameInfo()
+        _check(lib.jpezy_decode_jpeg_scaled_packed(self._h, _np_ptr(arr), arr.size, int(gray), int(scale), C.byref(info), int(format), 0, None, 0))
+        ws, hs = scaled_size(info.width, info.height, scale)
+        img = np.empty((hs, ws, nb), dtype=np.uint8)
+        _check(lib.jpezy_decode_jpeg_scaled_packed(self._h, _np_ptr(arr), arr.size, int(gray), int(scale), C.byref(info), int(format), 0,
+                                                   _np_ptr(img), img.size))
+        return info, img
+
+    def dequant_idct_scaled_dev(self, d_coeffs, info, scale, d_r=None, d_g=None, d_b=None, gray=False, stream=None, n_frames=1,
+                                plane_stride=None, d_img=None, format=PIX_RGB24):
+        """any-layout decode at 1/scale on device memory (torch tensors): coefficients as read_jpeg_gpu leaves them -> planes of Ws*Hs
+        bytes (n_frames frames plane_stride apart, default Ws*Hs), or, with d_img, packed pixels written into a uint8 tensor (Hs, Ws, C) or
+        (N, Hs, Ws, C) whose strides give the row and frame strides, as dequant_idct_packed_dev takes it"""
+        import torch
+        if stream is None:
+            stream = torch.cuda.current_stream(d_coeffs.device).cuda_stream
+        hs = (C.c_uint8 * 3)(*[max(1, info.H[i]) for i in range(3)])
+        vs = (C.c_uint8 * 3)(*[max(1, info.V[i]) for i in range(3)])
+        tq = (C.c_uint8 * 3)(*[info.Tq[i] for i in range(3)])
+        Ws, Hs = scaled_size(info.width, info.height, scale)
+        head = (self._h, d_coeffs.data_ptr(), C.byref(info.qt), info.ncomp, C.byref(hs), C.byref(vs), C.byref(tq), info.precision or 8,
+                info.width, info.height, int(gray), int(scale))
+        if d_img is not None:
+            n, H, W, row, frame = self._packed_layout(d_img, pixel_bytes(format), "dequant_idct_scaled_dev")
+            if (W, H) != (Ws, Hs):
+                raise JpezyError(f"dequant_idct_scaled_dev: d_img is {W} x {H}, the scaled size is {Ws} x {Hs}")
+            _check(load_library().jpezy_dequant_idct_scaled_packed_dev(*head, int(format), row, frame, n, d_img.data_ptr(), stream))
+            return
+        stride = plane_stride if plane_stride is not None else Ws * Hs
+        _check(load_library().jpezy_dequant_idct_scaled_dev(*head, n_frames, stride, d_r.data_ptr(), d_g.data_ptr(), d_b.data_ptr(), stream))
+
 
 # ---- host serial tail / head ----
 def optimal_table(freq):
@@ -730,12 +795,14 @@ class Decoder:
         self.ctx = ctx
         self.pr = None
 
-    def decode(self, gray=False):
+    def decode(self, gray=False, scale=1):
+        """scale 2, 4 or 8: planes of scaled_size(width, height, scale) (Context.decode_jpeg_scaled); self.pr keeps the file's size"""
         try:
             with open(self.filename, "rb") as f:
                 data = f.read()
             ctx = self.ctx or default_context()
-            info, r, g, b = ctx.decode_jpeg(data, gray=gray)       # Huffman head, IDCT and colour conversion on the GPU
+            # Huffman head, IDCT and colour conversion on the GPU
+            info, r, g, b = ctx.decode_jpeg(data, gray=gray) if scale == 1 else ctx.decode_jpeg_scaled(data, scale, gray=gray)
         except (OSError, JpezyError):
             return None
         self.pr = info

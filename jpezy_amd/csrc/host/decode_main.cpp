@@ -1,5 +1,6 @@
-// jpezy_decode <input.(jpg | jpeg)> ( <output.ppm | [OPT: --gray]> | -v )
-// Same argv rules, transcript and exit codes as the reference's src/decoder/main.cpp.
+// jpezy_decode <input.(jpg | jpeg)> ( <output.ppm | [OPT: --gray]> | -v ) [--scale=N]
+// Same argv rules, transcript and exit codes as the reference's src/decoder/main.cpp.  --scale=N (N = 1, 2, 4, 8; this project's own
+// option, looked for in argv[3] / argv[4] the way --gray is) writes the picture at 1/N; any other N is the usage error.
 #include <cstdlib>
 #include <fstream>
 #include <iostream>
@@ -12,7 +13,7 @@ namespace {
 
 int disp_error()
 {
-    std::cerr << "Usage: jpezy_decode <input.(jpg | jpeg)> ( <output.ppm | [OPT: --gray]> | -v )" << std::endl;
+    std::cerr << "Usage: jpezy_decode <input.(jpg | jpeg)> ( <output.ppm | [OPT: --gray]> | -v ) [OPT: --scale=(1 | 2 | 4 | 8)]" << std::endl;
     return EXIT_FAILURE;
 }
 
@@ -22,30 +23,39 @@ bool has_ext(std::string_view s, std::string_view ext)
 }
 
 template <class CL, class T>
-int output(jpezy::decoder<T>& dec, const char* out)
+int output(jpezy::decoder<T>& dec, const char* out, int scale)
 {
-    auto raw_op = dec.template decode<CL>();
+    auto raw_op = dec.template decode<CL>(scale);
     if (!raw_op) {
         std::cerr << "decode failed" << std::endl;
         return EXIT_FAILURE;
     }
     const auto raw = std::move(raw_op.value());
     const auto& [r, g, b] = raw;
-    using At = jpezy::property::At;
-    jpezy::decode_io dec_io(dec.pr.template get<At::HSize>(), dec.pr.template get<At::VSize>(), r, g, b);
+    jpezy::decode_io dec_io(dec.out_width, dec.out_height, r, g, b);
     std::ofstream ofs(out, std::ios_base::out | std::ios_base::trunc);
     ofs << dec_io;
-    std::cout << "Decoded image: Netpbm image data, size = " << dec.pr.template get<At::HSize>() << " x "
-              << dec.pr.template get<At::VSize>() << ", pixmap, ASCII text" << std::endl;
+    std::cout << "Decoded image: Netpbm image data, size = " << dec.out_width << " x " << dec.out_height << ", pixmap, ASCII text"
+              << std::endl;
     return EXIT_SUCCESS;
 }
 
 template <class T>
-int run(const char* in, const char* out, bool gray)
+int run(const char* in, const char* out, bool gray, int scale)
 {
     jpezy::disp_logo();
     jpezy::decoder<T> dec(in);
-    return gray ? output<jpezy::GRAY_MODE>(dec, out) : output<jpezy::COLOR_MODE>(dec, out);
+    return gray ? output<jpezy::GRAY_MODE>(dec, out, scale) : output<jpezy::COLOR_MODE>(dec, out, scale);
+}
+
+// --scale=N inside an option: N when it is 1, 2, 4 or 8, 0 for anything else, 1 when the option is not there
+int scale_of(std::string_view opt)
+{
+    constexpr std::string_view key = "--scale=";
+    const auto at = opt.find(key);
+    if (at == std::string_view::npos) return 1;
+    const std::string_view n = opt.substr(at + key.size());
+    return n == "1" ? 1 : n == "2" ? 2 : n == "4" ? 4 : n == "8" ? 8 : 0;
 }
 
 }  // namespace
@@ -62,8 +72,11 @@ int main(const int argc, const char* argv[])
 
     const bool gray = sv2.find("--gray") != std::string_view::npos || sv3.find("--gray") != std::string_view::npos;
     const bool verbose = sv2.find("-v") != std::string_view::npos || sv3.find("-v") != std::string_view::npos;
+    const int scale2 = scale_of(sv2), scale3 = scale_of(sv3);
+    if (!scale2 || !scale3) return disp_error();
+    const int scale = scale2 != 1 ? scale2 : scale3;
     try {
-        return verbose ? run<jpezy::Debug>(argv[1], argv[2], gray) : run<jpezy::Release>(argv[1], argv[2], gray);
+        return verbose ? run<jpezy::Debug>(argv[1], argv[2], gray, scale) : run<jpezy::Release>(argv[1], argv[2], gray, scale);
     } catch (const std::runtime_error& e) {
         std::cerr << e.what() << std::endl;
         return EXIT_FAILURE;

@@ -36,8 +36,10 @@ struct decoder {
     static constexpr bool is_release_mode = std::is_same_v<Release, BuildMode>;
     static constexpr std::size_t rgb_size = 3, block_size = 8, blocks_size = 64, mcu_size = 4;
 
+    // scale_denom 2, 4, 8: the picture at 1/2, 1/4, 1/8 (jpezy_decode_jpeg_scaled; the reference has no such mode, the definition is
+    // include/jpezy_hip.h's) -- out_width x out_height is then the size of the planes' image, pr keeps the file's
     template <class MODE_TAG = COLOR_MODE>
-    std::optional<std::array<std::vector<byte>, 3>> decode()
+    std::optional<std::array<std::vector<byte>, 3>> decode(int scale_denom = 1)
     {
         constexpr bool gray = std::is_same_v<MODE_TAG, GRAY_MODE>;
         raii_messenger mes("process started...");
@@ -66,12 +68,16 @@ struct decoder {
         const std::size_t rgb_s = static_cast<std::size_t>(info.mcu_rows) * info.vmax * 8 * static_cast<std::size_t>(info.mcu_cols) * info.hmax * 8;
         std::array<std::vector<byte>, 3> rgb;
         for (auto& v : rgb) v.resize(rgb_s);
+        int ws = info.width, hs = info.height;
+        if (jpezy_scaled_size(info.width, info.height, scale_denom, &ws, &hs) != JPEZY_OK) return {};
+        out_width = static_cast<std::size_t>(ws);
+        out_height = static_cast<std::size_t>(hs);
         jpezy_ctx* ctx = detail::device_context();
         // decode_huffman + inverse_quantization + inverse_dct + upsampling + make_rgb (:504-578, 583-670) for all MCUs: one
         // C-ABI call; for jpezy_encode's own layout every stage runs on the device
-        const int rc = jpezy_decode_jpeg(ctx, reinterpret_cast<const std::uint8_t*>(file.data()), file.size(), gray, &info,
-                                         reinterpret_cast<std::uint8_t*>(rgb[0].data()), reinterpret_cast<std::uint8_t*>(rgb[1].data()),
-                                         reinterpret_cast<std::uint8_t*>(rgb[2].data()), rgb_s);
+        const int rc = jpezy_decode_jpeg_scaled(ctx, reinterpret_cast<const std::uint8_t*>(file.data()), file.size(), gray, scale_denom, &info,
+                                                reinterpret_cast<std::uint8_t*>(rgb[0].data()), reinterpret_cast<std::uint8_t*>(rgb[1].data()),
+                                                reinterpret_cast<std::uint8_t*>(rgb[2].data()), rgb_s);
         if (rc == JPEZY_E_FORMAT || rc == JPEZY_E_NOSPACE) {
             std::cerr << "decode_mcu(): throw exception from " << jpezy_hip_last_error() << std::endl;   // :109-114
             return {};
@@ -84,6 +90,7 @@ struct decoder {
     }
 
     property pr;
+    std::size_t out_width = 0, out_height = 0;   // size of the decoded picture: the file's, or the scaled size
 
 private:
     void disp_info(const char* indent = "")   // ref :139-150 (spelling as in the reference)

@@ -2,7 +2,7 @@
 // jpezy_capi.hip (context, the two transform stages), jpezy_capi_entropy.hip (Huffman coding: the host writer's entry points, the GPU
 // coder's two forms, encoder::encode end to end), jpezy_capi_huffdec.hip (GPU Huffman decoding of one file, decoder::decode end to end),
 // jpezy_capi_decode_batch.hip (the batch form), jpezy_capi_packed.hip (the entry points for packed, i.e. interleaved, pixels),
-// jpezy_capi_multi.hip (the multi-GPU handle).
+// jpezy_capi_scaled.hip (reduced-size decode), jpezy_capi_multi.hip (the multi-GPU handle).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -117,6 +117,30 @@ inline size_t plane_pitch(const std::vector<HostChunk>& chunks, int W, int H)
     size_t P = 0;
     for (const HostChunk& k : chunks) P = std::max(P, k.plane_bytes(W, H));
     return (P + 15) & ~(size_t)15;
+}
+
+// packed (interleaved) pixels: jpezy_capi_packed.hip, jpezy_capi_scaled.hip
+struct PackedLayout {
+    int bytes;                 // per pixel
+    int off[3];                // byte of r, g, b inside a pixel
+    size_t row_stride, frame_stride;
+};
+
+// format, strides and the 32-bit row-offset limit; before anything is touched
+inline int packed_layout(const char* who, int format, size_t row_stride, size_t frame_stride, int W, int H, PackedLayout* L)
+{
+    const int bytes = jpezy_pixel_bytes(format);
+    if (bytes < 0) return set_err(JPEZY_E_BADARG, std::string(who) + ": unknown pixel format");
+    const size_t tight = (size_t)W * bytes;
+    const size_t rs = row_stride ? row_stride : tight;
+    if (rs < tight) return set_err(JPEZY_E_BADARG, std::string(who) + ": row_stride smaller than W * bytes per pixel");
+    if (rs > 0xFFFFFFFFull / (size_t)H) return set_err(JPEZY_E_BADARG, std::string(who) + ": row_stride * H must fit in 32 bits");
+    const size_t need = (size_t)(H - 1) * rs + tight;
+    const size_t fs = frame_stride ? frame_stride : (size_t)H * rs;
+    if (fs < need) return set_err(JPEZY_E_BADARG, std::string(who) + ": frame_stride smaller than (H-1) * row_stride + W * bytes per pixel");
+    const bool blue_first = format == JPEZY_PIX_BGR24 || format == JPEZY_PIX_BGRA32;
+    *L = { bytes, { blue_first ? 2 : 0, 1, blue_first ? 0 : 2 }, rs, fs };
+    return JPEZY_OK;
 }
 
 }  // namespace jpezy_capi

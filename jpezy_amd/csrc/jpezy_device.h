@@ -179,6 +179,34 @@ hipError_t launch_dequant_idct_generic(const GenericDecParams& p, hipStream_t st
 // frames of p's layout one pair of launches takes (the launcher loops over larger batches); 0: a frame too large for one launch
 int generic_frames_per_launch(const GenericDecParams& p);
 
+// reduced-size decode of any layout (jpezy_kernels_scaled.hip): an N x N inverse transform per block, N = 1 << log2n = 4, 2, 1
+struct ScaledDecParams {
+    const int16_t* coeffs;
+    int* samples;             // [block][N*N], scratch
+    const int* qt;            // [3 comps][64] natural order
+    uint8_t* r;
+    uint8_t* g;
+    uint8_t* b;
+    int Ws, Hs;               // the output: ceil(W * N / 8) x ceil(H * N / 8)
+    int log2n, ncomp, gray;
+    int ch[3], cv[3], hmax, vmax, mcu_cols, mcu_rows, blocks_per_mcu;
+    int blk_start[3];         // first block of each component inside an MCU
+    int level;                // 128, or 2048 when SOF0 says precision != 8 (ref :654)
+    unsigned mw_magic, mw_shift, mh_magic, mh_shift;        // fast_div by hmax*N, vmax*N (set by the launcher)
+    unsigned dx_magic[3], dx_shift[3], dy_magic[3], dy_shift[3];   // fast_div by hmax/H, vmax/V of each component
+    // n_frames frames of ONE layout, size and set of quantiser tables: frame f's coefficients at coeffs + f * blocks * 64, its samples at
+    // samples + f * blocks * N*N, its planes at r/g/b + f * plane_stride (any value that holds a plane)
+    int n_frames = 1;
+    size_t plane_stride = 0;
+    // packed (interleaved) output as in GenericDecParams: pix_bytes = 3 or 4 (0: planes); r, g, b = the channel bytes of pixel (0, 0),
+    // rows row_stride apart, frames plane_stride apart; byte 3 of a 32-bit pixel = 0xFF
+    int pix_bytes = 0;
+    unsigned row_stride = 0;
+};
+hipError_t launch_dequant_idct_scaled(const ScaledDecParams& p, hipStream_t stream);
+// frames of p's layout one pair of launches takes (the launcher loops over larger batches); 0: a frame too large for one launch
+int scaled_frames_per_launch(const ScaledDecParams& p);
+
 #if defined(__HIPCC__)
 // The reference's sample int(sum / 4 + sl) (ref decoder/jpezy_decoder.hpp:667) as its x86-64 build executes it: cvttsd2si truncates
 // toward zero and gives INT_MIN for every value outside [-2^31, 2^31) and for NaN, where v_cvt_i32_f64 saturates (INT_MAX above the

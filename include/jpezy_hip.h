@@ -562,6 +562,77 @@ int jpezy_decode_jpeg_scaled(jpezy_ctx* ctx, const uint8_t* data, size_t len, in
 int jpezy_decode_jpeg_scaled_packed(jpezy_ctx* ctx, const uint8_t* data, size_t len, int gray, int scale_denom, jpezy_frame_info* info,
                                     int format, size_t row_stride, uint8_t* pix, size_t pix_cap);
 
+/*
+ * PLANAR YCbCr 4:2:0 SAMPLES (I420 / YV12 / NV12 / NV21) IN AND OUT.  The file format is full-range BT.601 YCbCr sampled 2x2, 1x1, 1x1: a
+ * caller that already holds such planes (a video decoder, a camera, an ISP) holds the file's own sample domain.  The reference only takes
+ * RGB (encoder/jpezy_encoder.hpp:24-28) and only gives RGB (decoder/jpezy_decoder.hpp:531-578), so the definition is this project's own
+ * (restated in tests/ycc_model.py):
+ *
+ *   Sizes         CW = ceil(W/2), CH = ceil(H/2) (jpezy_ycc_chroma_size)
+ *   Encode        the result of the reference's MCU loop (encoder/jpezy_encoder.hpp:58-67) if make_YCC (:90-144) handed over, instead of
+ *                 converted pixels, for luma block i of MCU (ux, uy), sample (x, y):
+ *                     (int)Y[min(uy*16 + 8*(i>>1) + y, H-1)][min(ux*16 + 8*(i&1) + x, W-1)] - 128
+ *                 and for the Cb / Cr block, sample (x, y):
+ *                     (int)C[min(uy*8 + y, CH-1)][min(ux*8 + x, CW-1)] - 128
+ *                 DCT (:146-166), quantization (:168-172) and the zig-zag order are unchanged.  gray != 0: luma only, the 4-block layout;
+ *                 the chroma pointers are not read and may be NULL.
+ *   Anchor        with Y = Y_ref + 128 and Cb / Cr = the reference's chroma of the top-left pixel of every 2x2 + 128 (they fit a byte), the
+ *                 coefficients equal jpezy_fdct_quant's for the RGB pixels whenever each of W and H is a multiple of 16 or odd, and for
+ *                 gray at every size.  (Behind an even edge that is no multiple of 16 the RGB path replicates pixel W-1, whose chroma
+ *                 sample no 4:2:0 plane holds: the plane's last sample belongs to pixel W-2.)
+ *   Range         samples span [-128, 127] in all three components (the RGB path's chroma stops at -127): block sums span [-8192, 8128],
+ *                 the range the exact DC table and its create-time check cover; flat planes of 0 give DCs -63 / -60, of 255 +63 / +59
+ *   Decode        component c at its native sampling, ceil(W*H_c/hmax) x ceil(H*V_c/vmax) samples (jpezy_ycc_component_size): for this
+ *                 project's own layout W x H, CW x CH, CW x CH.  inverse_quantization and inverse_dct (decoder/jpezy_decoder.hpp:645-670)
+ *                 unchanged; block (kx, ky) of MCU (ux, uy) of component c is placed at ((ux*H_c + kx)*8, (uy*V_c + ky)*8); no replication
+ *                 and no make_rgb; every byte is revise_value (:672-676) of the integer sample, so a sample of INT_MIN gives 0.  The Y plane
+ *                 equals the r plane of jpezy_decode_jpeg(..., gray = 1).  jpezy_ctx_set_decode_tolerance(1): Y within one, chroma exact.
+ *   Addressing    sample (x, y) of Y of frame f: y_ptr + f*y_frame_stride + y*y_stride + x; of Cb: cb_ptr + f*c_frame_stride + y*c_stride +
+ *                 x*c_step, Cr the same from cr_ptr.  c_step 1: planes (I420; YV12 by exchanging the pointers); 2: one interleaved plane
+ *                 (NV12: cr = cb + 1; NV21: cb = cr + 1).  Any other c_step: JPEZY_E_BADARG.  Strides of 0 mean tight (W; CW*c_step; H*y_stride;
+ *                 CH*c_stride); a c_stride may be as small as (CW-1)*c_step + 1.  y_stride*H and c_stride*CH must fit in 32 bits.
+ *   Alignment     none required.  W % 16 == 0 with 16-byte aligned Y base and strides and 8-byte aligned chroma planes (c_step 1) or a
+ *                 16-byte aligned interleaved plane whose Cb and Cr are neighbours (c_step 2) takes the 16 / 8-byte form
+ *   Bytes touched only sample bytes are read or written: never padding, never the other channel's bytes of an interleaved plane when only
+ *                 one chroma pointer is given (decode), never anything behind the last row (jpezy_encode_jpeg_ycc alone may READ the
+ *                 padding between the rows of a band when it uploads it)
+ *   Context settings  jpezy_ctx_set_force_exact (levels 1-3), _set_variant, _set_decode_tolerance, _set_host_chunk_bytes, _set_huffman_optimize
+ *                 and _set_restart_interval act as on the RGB entries.  Encode variant 0 (FP64) reads the planes through its byte loop; the
+ *                 laboratory's variants 2 and 3 hand YCC input to variant 1's launch
+ *
+ * NOT provided in YCC form: jpezy_decode_jpeg_batch, the multi-GPU handle, reduced-size decode, the host-buffer jpezy_fdct_quant /
+ * jpezy_dequant_idct, the jpezy::encoder / decoder class surface, 4:2:2 / 4:4:4 INPUT, limited-range (16-235) video levels: the caller's
+ * planes are taken as the file's full-range samples.
+ */
+/* CW, CH (either may be NULL) of a W x H picture; JPEZY_E_BADARG for a size outside 1..65535.  Pure host function (stands in for the
+ * decimation of encoder/jpezy_encoder.hpp:134-142). */
+int jpezy_ycc_chroma_size(int W, int H, int* CW, int* CH);
+/* Width and height (either may be NULL) of component comp of a parsed file at its native sampling (decoder/jpezy_decoder.hpp:166-169,
+ * 504-528 without the replication); JPEZY_E_BADARG for a component the file does not have.  Pure host function. */
+int jpezy_ycc_component_size(const jpezy_frame_info* info, int comp, int* w, int* h);
+/* jpezy_fdct_quant_dev from Y, Cb, Cr samples in device memory: stands in for encoder/jpezy_encoder.hpp:90-172 with make_YCC's conversion
+ * (:244-256) taken out.  Asynchronous on `stream`; more than 65535 frames go out as several launches. */
+int jpezy_fdct_quant_ycc_dev(jpezy_ctx* ctx, const uint8_t* d_y, size_t y_stride, const uint8_t* d_cb, const uint8_t* d_cr, size_t c_stride,
+                             int c_step, size_t y_frame_stride, size_t c_frame_stride, int W, int H, int gray, int n_frames,
+                             int16_t* d_coeffs, void* stream);
+/* jpezy_dequant_idct_dev writing the components at their native sampling (decoder/jpezy_decoder.hpp:645-676 without decode_mcu's
+ * replication :504-528 and make_rgb :531-578); jpezy's own 2x2,1x1,1x1 layout, the fused kernel.  d_cb == d_cr == NULL: luma only.
+ * Asynchronous on `stream`; the table and capture rules of jpezy_dequant_idct_dev apply. */
+int jpezy_dequant_idct_ycc_dev(jpezy_ctx* ctx, const int16_t* d_coeffs, const uint16_t qt[4][64], const uint8_t comp_tq[3], uint8_t* d_y,
+                               size_t y_stride, uint8_t* d_cb, uint8_t* d_cr, size_t c_stride, int c_step, size_t y_frame_stride,
+                               size_t c_frame_stride, int W, int H, int n_frames, void* stream);
+/* jpezy_encode_jpeg from host Y, Cb, Cr planes (encoder/jpezy_encoder.hpp:38-77 without the conversion): streamed in MCU-row bands, up to
+ * three input segments per band (16*k luma rows, ceil(rows/2) chroma rows; an interleaved plane travels as one segment); the Huffman
+ * stage is jpezy_write_jpeg_gpu, so the optimise and restart settings act. */
+long jpezy_encode_jpeg_ycc(jpezy_ctx* ctx, const uint8_t* y, size_t y_stride, const uint8_t* cb, const uint8_t* cr, size_t c_stride, int c_step,
+                           int W, int H, int gray, const char* comment, uint8_t* out, size_t cap);
+/* jpezy_decode_jpeg into host component planes (decoder/jpezy_decoder.hpp:76-134 without :504-578's replication and conversion), for every
+ * layout it accepts: jpezy's own through the fused kernel, everything else through the generic pair, files handed to the host Huffman
+ * decoder included.  y, cb, cr all NULL: header only.  A one-component file writes y only.  JPEZY_E_NOSPACE when y_cap <
+ * (h0-1)*y_stride + w0 or c_cap < (hc-1)*c_stride + (wc-1)*c_step + 1 (w, h: jpezy_ycc_component_size). */
+int jpezy_decode_jpeg_ycc(jpezy_ctx* ctx, const uint8_t* data, size_t len, jpezy_frame_info* info, uint8_t* y, size_t y_stride, size_t y_cap,
+                          uint8_t* cb, uint8_t* cr, size_t c_stride, int c_step, size_t c_cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -116,6 +116,15 @@ ABI = [
                                                        C.c_size_t, C.c_size_t, C.c_int, _vp, _vp]),
     ("jpezy_decode_jpeg_scaled", C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.c_int, C.POINTER(FrameInfo), _vp, _vp, _vp, C.c_size_t]),
     ("jpezy_decode_jpeg_scaled_packed", C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.c_int, C.POINTER(FrameInfo), C.c_int, C.c_size_t, _vp, C.c_size_t]),
+    ("jpezy_ycc_chroma_size", C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    ("jpezy_ycc_component_size", C.c_int, [C.POINTER(FrameInfo), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    ("jpezy_fdct_quant_ycc_dev", C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int,
+                                           C.c_int, _vp, _vp]),
+    ("jpezy_dequant_idct_ycc_dev", C.c_int, [_vp, _vp, _QT, _TQ, _vp, C.c_size_t, _vp, _vp, C.c_size_t, C.c_int, C.c_size_t, C.c_size_t, C.c_int,
+                                             C.c_int, C.c_int, _vp]),
+    ("jpezy_encode_jpeg_ycc", C.c_long, [_vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, _vp, C.c_size_t]),
+    ("jpezy_decode_jpeg_ycc", C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(FrameInfo), _vp, C.c_size_t, C.c_size_t, _vp, _vp, C.c_size_t, C.c_int,
+                                        C.c_size_t]),
 ]
 
 # enum jpezy_pixel_format: packed (interleaved) pixels, 3 or 4 bytes each
@@ -176,6 +185,20 @@ def scaled_size(W, H, scale):
     ws, hs = C.c_int(), C.c_int()
     _check(load_library().jpezy_scaled_size(int(W), int(H), int(scale), C.byref(ws), C.byref(hs)))
     return ws.value, hs.value
+
+
+def ycc_chroma_size(W, H):
+    """(CW, CH) = (ceil(W/2), ceil(H/2)): the chroma planes of a W x H picture in planar YCbCr 4:2:0 (I420 / NV12)"""
+    cw, ch = C.c_int(), C.c_int()
+    _check(load_library().jpezy_ycc_chroma_size(int(W), int(H), C.byref(cw), C.byref(ch)))
+    return cw.value, ch.value
+
+
+def ycc_component_size(info, comp):
+    """(w, h) of component comp of a parsed file at its native sampling: ceil(W * H_c / hmax), ceil(H * V_c / vmax)"""
+    w, h = C.c_int(), C.c_int()
+    _check(load_library().jpezy_ycc_component_size(C.byref(info), int(comp), C.byref(w), C.byref(h)))
+    return w.value, h.value
 
 
 def _np_ptr(a):
@@ -512,6 +535,116 @@ class Context:
         tq = (C.c_uint8 * 3)(*comp_tq)
         _check(load_library().jpezy_dequant_idct_packed_dev(self._h, d_coeffs.data_ptr(), C.byref(qtab), C.byref(tq), int(format), row, frame,
                                                             W, H, int(gray), n, d_img.data_ptr(), stream))
+
+    # ---- planar YCbCr 4:2:0 samples (I420 / YV12 / NV12 / NV21): the file's own sample domain, no colour conversion ----
+    def encode_jpeg_ycc(self, y, cb=None, cr=None, gray=False, comment=None):
+        """2-D numpy uint8 planes -> .jpg bytes: y (H, W), cb and cr (ceil(H/2), ceil(W/2)).  Strides and c_step are read from the arrays,
+        so uv[..., 0], uv[..., 1] of an NV12 plane (H/2, W/2, 2) encode in place.  gray: luma only, cb and cr are not read."""
+        lib = load_library()
+        y = np.asarray(y)
+        if y.dtype != np.uint8 or y.ndim != 2:
+            raise JpezyError("encode_jpeg_ycc: y must be a 2-D uint8 array")
+        H, W = y.shape
+        if y.strides[1] != 1 or y.strides[0] < W:
+            y = np.ascontiguousarray(y)
+        c_stride, c_step, pcb, pcr = 0, 1, None, None
+        if not gray:
+            cw, ch = ycc_chroma_size(W, H)
+            cb, cr = np.asarray(cb), np.asarray(cr)
+            for c in (cb, cr):
+                if c.dtype != np.uint8 or c.shape != (ch, cw):
+                    raise JpezyError(f"encode_jpeg_ycc: cb and cr must be uint8 arrays of shape ({ch}, {cw})")
+            ok = cb.strides == cr.strides and cb.strides[1] in (1, 2) and cb.strides[0] >= (cw - 1) * cb.strides[1] + 1
+            if not ok:
+                cb, cr = np.ascontiguousarray(cb), np.ascontiguousarray(cr)
+            c_stride, c_step = (cb.strides[0] if ch > 1 else 0), (cb.strides[1] if cw > 1 else 1)
+            pcb, pcr = _np_ptr(cb), _np_ptr(cr)
+        if comment is None:
+            comment = b"Encoded by JPEZY" if gray else b"Encoded by jpezy"
+        cap = lib.jpezy_jpeg_bound(W, H)
+        buf = np.empty(cap, dtype=np.uint8)
+        n = lib.jpezy_encode_jpeg_ycc(self._h, _np_ptr(y), y.strides[0] if H > 1 else 0, pcb, pcr, c_stride, c_step, W, H, int(gray), comment,
+                                      _np_ptr(buf), cap)
+        _check(n)
+        return buf[:n].tobytes()
+
+    def decode_jpeg_ycc(self, data, interleaved=False):
+        """.jpg bytes -> (FrameInfo, y, cb, cr): the components at their native sampling as 2-D uint8 arrays (no upsampling, no colour
+        conversion; cb = cr = None for a one-component file).  interleaved: cb and cr are the two views uv[..., 0], uv[..., 1] of one
+        (h, w, 2) array (NV12)."""
+        lib = load_library()
+        arr = np.frombuffer(bytes(data), dtype=np.uint8)
+        info = FrameInfo()
+        _check(lib.jpezy_decode_jpeg_ycc(self._h, _np_ptr(arr), arr.size, C.byref(info), None, 0, 0, None, None, 0, 1, 0))
+        w0, h0 = ycc_component_size(info, 0)
+        y = np.empty((h0, w0), dtype=np.uint8)
+        cb = cr = pcb = pcr = None
+        c_stride, c_step, c_cap = 0, 1, 0
+        if info.ncomp == 3:
+            (w1, h1), (w2, h2) = ycc_component_size(info, 1), ycc_component_size(info, 2)
+            if interleaved and (w1, h1) == (w2, h2):
+                uv = np.empty((h1, w1, 2), dtype=np.uint8)
+                cb, cr = uv[..., 0], uv[..., 1]
+                c_stride, c_step, c_cap = 2 * w1, 2, uv.size - 1
+            else:
+                wm = max(w1, w2)
+                cb, cr = np.empty((h1, wm), dtype=np.uint8)[:, :w1], np.empty((h2, wm), dtype=np.uint8)[:, :w2]
+                c_stride, c_cap = wm, min((h1 - 1) * wm + w1, (h2 - 1) * wm + w2)
+                if interleaved:
+                    raise JpezyError("decode_jpeg_ycc: the chroma components of this file differ in size and cannot share one interleaved plane")
+            pcb, pcr = cb.ctypes.data, cr.ctypes.data
+        _check(lib.jpezy_decode_jpeg_ycc(self._h, _np_ptr(arr), arr.size, C.byref(info), _np_ptr(y), w0, y.size, pcb, pcr, c_stride, c_step, c_cap))
+        return info, y, cb, cr
+
+    @staticmethod
+    def _ycc_layout(d_y, d_cb, d_cr, who):
+        """(n_frames, H, W, y_stride, y_frame_stride, c_stride, c_step, c_frame_stride) of torch uint8 tensors (H, W) / (CH, CW) or with a
+        leading frame dimension; d_cb / d_cr None: luma only"""
+        import torch
+        if d_y.dtype != torch.uint8 or d_y.dim() not in (2, 3) or (d_y.shape[-1] > 1 and d_y.stride(-1) != 1):
+            raise JpezyError(f"{who}: d_y must be a uint8 tensor (H, W) or (N, H, W) whose rows are contiguous")
+        H, W = int(d_y.shape[-2]), int(d_y.shape[-1])
+        n = int(d_y.shape[0]) if d_y.dim() == 3 else 1
+        ys = int(d_y.stride(-2)) if H > 1 else 0
+        yfs = int(d_y.stride(0)) if d_y.dim() == 3 and n > 1 else 0
+        cs, step, cfs = 0, 1, 0
+        chroma = [c for c in (d_cb, d_cr) if c is not None]
+        if chroma:
+            cw, ch = ycc_chroma_size(W, H)
+            c0 = chroma[0]
+            for c in chroma:
+                if c.dtype != torch.uint8 or c.dim() != d_y.dim() or tuple(c.shape[-2:]) != (ch, cw) or (c.dim() == 3 and int(c.shape[0]) != n):
+                    raise JpezyError(f"{who}: chroma tensors must be uint8 of shape ({ch}, {cw}) with d_y's frame dimension")
+                if c.stride() != c0.stride():
+                    raise JpezyError(f"{who}: d_cb and d_cr must have the same strides")
+            step = int(c0.stride(-1)) if cw > 1 else 1
+            cs = int(c0.stride(-2)) if ch > 1 else 0
+            cfs = int(c0.stride(0)) if c0.dim() == 3 and n > 1 else 0
+        return n, H, W, ys, yfs, cs, step, cfs
+
+    def fdct_quant_ycc_dev(self, d_y, d_cb, d_cr, d_coeffs, gray=False, stream=None):
+        """device Y, Cb, Cr samples (torch uint8 (H, W) and (CH, CW), or with a leading frame dimension; strides are the tensors', so the two
+        views of an interleaved NV12 plane work) -> d_coeffs.  gray: luma only, d_cb and d_cr may be None."""
+        import torch
+        n, H, W, ys, yfs, cs, step, cfs = self._ycc_layout(d_y, None if gray else d_cb, None if gray else d_cr, "fdct_quant_ycc_dev")
+        if stream is None:
+            stream = torch.cuda.current_stream(d_y.device).cuda_stream
+        pcb, pcr = (None, None) if gray else (d_cb.data_ptr(), d_cr.data_ptr())
+        _check(load_library().jpezy_fdct_quant_ycc_dev(self._h, d_y.data_ptr(), ys, pcb, pcr, cs, step, yfs, cfs, W, H, int(gray), n,
+                                                       d_coeffs.data_ptr(), stream))
+
+    def dequant_idct_ycc_dev(self, d_coeffs, d_y, d_cb=None, d_cr=None, qt=None, comp_tq=(0, 1, 1), stream=None):
+        """device coefficients (6-block layout) -> the components at their native sampling, written into d_y (H, W) and d_cb, d_cr (CH, CW)
+        (layout as for fdct_quant_ycc_dev); d_cb = d_cr = None: luma only"""
+        import torch
+        n, H, W, ys, yfs, cs, step, cfs = self._ycc_layout(d_y, d_cb, d_cr, "dequant_idct_ycc_dev")
+        if stream is None:
+            stream = torch.cuda.current_stream(d_coeffs.device).cuda_stream
+        qtab = qt if qt is not None else annex_k_tables().qt
+        tq = (C.c_uint8 * 3)(*comp_tq)
+        _check(load_library().jpezy_dequant_idct_ycc_dev(self._h, d_coeffs.data_ptr(), C.byref(qtab), C.byref(tq), d_y.data_ptr(), ys,
+                                                         d_cb.data_ptr() if d_cb is not None else None, d_cr.data_ptr() if d_cr is not None else None,
+                                                         cs, step, yfs, cfs, W, H, n, stream))
 
     # ---- reduced-size decode (scale 1, 2, 4, 8: an N x N inverse transform per block, N = 8 / scale; include/jpezy_hip.h) ----
     def decode_jpeg_scaled(self, data, scale, gray=False):

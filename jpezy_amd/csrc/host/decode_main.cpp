@@ -1,10 +1,16 @@
 // jpezy_decode <input.(jpg | jpeg)> ( <output.ppm | [OPT: --gray]> | -v ) [--scale=N]
 // Same argv rules, transcript and exit codes as the reference's src/decoder/main.cpp.  --scale=N (N = 1, 2, 4, 8; this project's own
 // option, looked for in argv[3] / argv[4] the way --gray is) writes the picture at 1/N; any other N is the usage error.
+// jpezy_decode --i420 <input.(jpg | jpeg)> <output.yuv>   (this project's own option) writes the file's own samples, without upsampling
+// or colour conversion, as raw planes: Y, then Cb, then Cr (full range: ffmpeg's yuvj420p) through jpezy_decode_jpeg_ycc.  Only a
+// 4:2:0 file (sampling 2x2, 1x1, 1x1) is such a picture: any other layout is refused with a message.
 #include <cstdlib>
 #include <fstream>
 #include <iostream>
+#include <cstdint>
+#include <iterator>
 #include <string_view>
+#include <vector>
 
 #include "decode_io.hpp"
 #include "jpezy_decoder.hpp"
@@ -58,10 +64,53 @@ int scale_of(std::string_view opt)
     return n == "1" ? 1 : n == "2" ? 2 : n == "4" ? 4 : n == "8" ? 8 : 0;
 }
 
+int i420_main(const int argc, const char* argv[])
+{
+    if (argc != 4) {
+        std::cerr << "Usage: jpezy_decode --i420 <input.(jpg | jpeg)> <output.yuv>" << std::endl;
+        return EXIT_FAILURE;
+    }
+    jpezy::disp_logo();
+    std::ifstream ifs(argv[2], std::ios::binary);
+    const std::vector<std::uint8_t> data((std::istreambuf_iterator<char>(ifs)), std::istreambuf_iterator<char>());
+    jpezy_ctx* ctx = jpezy::detail::device_context();
+    jpezy_frame_info info;
+    if (!ifs.is_open() || jpezy_decode_jpeg_ycc(ctx, data.data(), data.size(), &info, nullptr, 0, 0, nullptr, nullptr, 0, 1, 0) != JPEZY_OK) {
+        std::cerr << "decode failed" << std::endl;
+        return EXIT_FAILURE;
+    }
+    const bool is420 = info.ncomp == 3 && info.H[0] == 2 && info.V[0] == 2 && info.H[1] == 1 && info.V[1] == 1 && info.H[2] == 1 && info.V[2] == 1;
+    if (!is420) {
+        std::cerr << "jpezy_decode --i420: " << argv[2] << " is not a 4:2:0 file (its sampling is not 2x2, 1x1, 1x1)" << std::endl;
+        return EXIT_FAILURE;
+    }
+    int CW = 0, CH = 0;
+    jpezy_ycc_chroma_size(info.width, info.height, &CW, &CH);
+    const std::size_t ny = static_cast<std::size_t>(info.width) * info.height, nc = static_cast<std::size_t>(CW) * CH;
+    std::vector<std::uint8_t> out(ny + 2 * nc);
+    if (jpezy_decode_jpeg_ycc(ctx, data.data(), data.size(), &info, out.data(), 0, ny, out.data() + ny, out.data() + ny + nc, 0, 1, nc) != JPEZY_OK) {
+        std::cerr << "decode failed: " << jpezy_hip_last_error() << std::endl;
+        return EXIT_FAILURE;
+    }
+    std::ofstream ofs(argv[3], std::ios::binary | std::ios::trunc);
+    ofs.write(reinterpret_cast<const char*>(out.data()), static_cast<std::streamsize>(out.size()));
+    if (!ofs) { std::cerr << "output_file" << std::endl; return EXIT_FAILURE; }
+    std::cout << "Decoded image: raw planar YCbCr 4:2:0 (Y, Cb, Cr), size = " << info.width << " x " << info.height << std::endl;
+    return EXIT_SUCCESS;
+}
+
 }  // namespace
 
 int main(const int argc, const char* argv[])
 {
+    if (argc >= 2 && std::string_view(argv[1]) == "--i420") {
+        try {
+            return i420_main(argc, argv);
+        } catch (const std::runtime_error& e) {
+            std::cerr << e.what() << std::endl;
+            return EXIT_FAILURE;
+        }
+    }
     if (argc > 5 || argc < 3) return disp_error();
 
     const std::string_view sv0 = argv[1], sv1 = argv[2];

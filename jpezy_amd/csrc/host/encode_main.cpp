@@ -8,9 +8,13 @@
 // Extension (not in the reference):  jpezy_encode --gpus N [--gray] <in1.ppm> <out1.jpg> [<in2.ppm> <out2.jpg> ...]
 // encodes a list of files on up to N GPUs of this node through jpezy_encode_batch_multi: runs of consecutive inputs of one size
 // form a batch, a batch is sharded over the GPUs frame by frame.
+// Extension (not in the reference):  jpezy_encode --i420=WxH <in.yuv> <out.jpg> [--gray] [--optimize] [--restart=N]
+// encodes a raw planar YCbCr 4:2:0 file -- the W x H Y plane, then the ceil(W/2) x ceil(H/2) Cb and Cr planes, full range (ffmpeg's
+// yuvj420p) -- through jpezy_encode_jpeg_ycc: the samples go into the file as they are, without a colour conversion.
 #include <cstdlib>
 #include <fstream>
 #include <iostream>
+#include <iterator>
 #include <string_view>
 
 #include "encode_io.hpp"
@@ -95,10 +99,9 @@ int batch_main(const int argc, const char* argv[])
     return EXIT_SUCCESS;
 }
 
-// "--restart=N" with N a decimal number in 0..65535: N; anything else that starts like it: -1
-int parse_restart(std::string_view tok)
+// a decimal number in 0..65535, or -1
+int parse_u16(std::string_view tok)
 {
-    tok.remove_prefix(std::string_view("--restart=").size());
     if (tok.empty() || tok.size() > 5) return -1;
     int n = 0;
     for (const char ch : tok) {
@@ -108,11 +111,71 @@ int parse_restart(std::string_view tok)
     return n <= 65535 ? n : -1;
 }
 
+// "--restart=N" with N a decimal number in 0..65535: N; anything else that starts like it: -1
+int parse_restart(std::string_view tok)
+{
+    tok.remove_prefix(std::string_view("--restart=").size());
+    return parse_u16(tok);
+}
+
+// jpezy_encode --i420=WxH in.yuv out.jpg [--gray] [--optimize] [--restart=N]
+int i420_main(const int argc, const char* argv[])
+{
+    const auto usage = [] {
+        std::cerr << "Usage: jpezy_encode --i420=WxH <input.yuv> <output.(jpeg | jpg)> [OPT: --gray] [OPT: --optimize] [OPT: --restart=N]" << std::endl;
+        return EXIT_FAILURE;
+    };
+    std::string_view dims = argv[1];
+    dims.remove_prefix(std::string_view("--i420=").size());
+    const auto x = dims.find('x');
+    if (x == std::string_view::npos || argc < 4) return usage();
+    const int W = parse_u16(dims.substr(0, x)), H = parse_u16(dims.substr(x + 1));
+    if (W <= 0 || H <= 0) return usage();
+    bool gray = false, optimize = false;
+    int restart = 0;
+    for (int i = 4; i < argc; ++i) {
+        const std::string_view o = argv[i];
+        if (o == "--gray") gray = true;
+        else if (o == "--optimize") optimize = true;
+        else if (o.rfind("--restart=", 0) == 0 && (restart = parse_restart(o)) >= 0) continue;
+        else return usage();
+    }
+    jpezy::disp_logo();
+    int CW = 0, CH = 0;
+    jpezy_ycc_chroma_size(W, H, &CW, &CH);
+    const std::size_t ny = static_cast<std::size_t>(W) * H, nc = static_cast<std::size_t>(CW) * CH;
+    std::ifstream ifs(argv[2], std::ios::binary);
+    std::vector<std::uint8_t> buf((std::istreambuf_iterator<char>(ifs)), std::istreambuf_iterator<char>());
+    if (!ifs.is_open() || buf.size() != ny + 2 * nc) {
+        std::cerr << "jpezy_encode: " << argv[2] << " must hold " << ny + 2 * nc << " bytes (Y, Cb, Cr planes of a " << W << " x " << H
+                  << " picture), it holds " << buf.size() << std::endl;
+        return EXIT_FAILURE;
+    }
+    try {
+        jpezy_ctx* ctx = jpezy::detail::device_context();
+        if (optimize && jpezy_ctx_set_huffman_optimize(ctx, 1) != JPEZY_OK) throw std::runtime_error(std::string("jpezy_ctx_set_huffman_optimize: ") + jpezy_hip_last_error());
+        if (restart && jpezy_ctx_set_restart_interval(ctx, restart) != JPEZY_OK) throw std::runtime_error(std::string("jpezy_ctx_set_restart_interval: ") + jpezy_hip_last_error());
+        std::vector<std::uint8_t> jpg(jpezy_jpeg_bound(W, H));
+        const long n = jpezy_encode_jpeg_ycc(ctx, buf.data(), 0, buf.data() + ny, buf.data() + ny + nc, 0, 1, W, H, gray ? 1 : 0,
+                                             gray ? "Encoded by JPEZY" : "Encoded by jpezy", jpg.data(), jpg.size());
+        if (n < 0) throw std::runtime_error(std::string("jpezy_encode_jpeg_ycc: ") + jpezy_hip_last_error());
+        std::ofstream ofs(argv[3], std::ios::binary);
+        ofs.write(reinterpret_cast<const char*>(jpg.data()), static_cast<std::streamsize>(n));
+        if (!ofs) throw std::runtime_error("output_file");
+        std::cout << argv[3] << ": Output size: " << n << " byte" << std::endl;
+    } catch (const std::runtime_error& e) {
+        std::cerr << e.what() << std::endl;
+        return EXIT_FAILURE;
+    }
+    return EXIT_SUCCESS;
+}
+
 }  // namespace
 
 int main(const int argc_in, const char* argv_in[])
 {
     if (argc_in >= 3 && std::string_view(argv_in[1]) == "--gpus") return batch_main(argc_in, argv_in);
+    if (argc_in >= 2 && std::string_view(argv_in[1]).rfind("--i420=", 0) == 0) return i420_main(argc_in, argv_in);
     if (argc_in < 3) return disp_error();
     // the one --restart=N token is taken out; what is left is read as before
     std::vector<const char*> args(argv_in, argv_in + argc_in);

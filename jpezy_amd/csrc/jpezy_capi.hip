@@ -484,7 +484,7 @@ JPEZY_CATCH
 int jpezy_internal_generic_dev_core(jpezy_ctx* c, const int16_t* d_coeffs, const uint16_t qt[4][64], int ncomp, const uint8_t comp_h[3],
                             const uint8_t comp_v[3], const uint8_t comp_tq[3], int W, int H, int gray, int precision, uint8_t* d_r,
                             uint8_t* d_g, uint8_t* d_b, hipStream_t s, size_t* nblk_out, int n_frames, size_t plane_stride, int pix_bytes,
-                            unsigned row_stride)
+                            unsigned row_stride, int ycc_c_step, unsigned ycc_c_row_stride)
 {
     if (ncomp != 1 && ncomp != 3) return set_err(JPEZY_E_UNSUPPORTED, "dimension not supported (the reference accepts 1 or 3)");
     GenericDecParams p;
@@ -514,6 +514,10 @@ int jpezy_internal_generic_dev_core(jpezy_ctx* c, const int16_t* d_coeffs, const
     p.plane_stride = plane_stride;
     p.pix_bytes = pix_bytes;                                 // packed pixels: d_r, d_g, d_b are the channel bytes of pixel (0, 0)
     p.row_stride = row_stride;
+    // native component planes (jpezy_decode_jpeg_ycc): d_r, d_g, d_b are sample (0, 0) of the components, null = not wanted
+    p.ycc = ycc_c_step != 0;
+    p.c_step = ycc_c_step ? ycc_c_step : 1;
+    p.c_row_stride = ycc_c_row_stride;
     const int per = generic_frames_per_launch(p);            // samples scratch: the frames of one launch (launches run in stream order)
     if (per < 1) return set_err(JPEZY_E_UNSUPPORTED, "generic decoder: frame of more than 2^31 blocks");
     if (int rc = c->scratch.reserve(nblk * 64 * sizeof(int) * (size_t)std::min(n_frames, per))) return rc;

@@ -1,0 +1,287 @@
+// jpezy_capi_ycc.hip -- the C-ABI of include/jpezy_hip.h, part 7: planar YCbCr 4:2:0 samples (I420 / YV12 / NV12 / NV21) in and out.  The
+// caller's planes are the file's own sample domain: the encode kernels skip the colour conversion (first step and sample stage differ),
+// the decode kernels skip replication and make_rgb (last step differs); coefficients keep their layout, so the Huffman stages, optimised
+// tables, restart intervals and the file header are the RGB entries'.
+#include "jpezy_capi_internal.h"
+
+namespace {
+
+struct YccLayout {
+    int CW, CH;
+    size_t ys, cs, yfs, cfs;      // resolved strides
+};
+
+// c_step, strides and the 32-bit row-offset limit (W, H already checked); before the context or a device is touched
+int ycc_layout(const char* who, int W, int H, size_t y_stride, size_t c_stride, int c_step, size_t y_frame_stride, size_t c_frame_stride,
+               YccLayout* L)
+{
+    if (c_step != 1 && c_step != 2) return set_err(JPEZY_E_BADARG, std::string(who) + ": c_step must be 1 (planes) or 2 (one interleaved plane)");
+    const int CW = (W + 1) / 2, CH = (H + 1) / 2;
+    const size_t ys = y_stride ? y_stride : (size_t)W;
+    const size_t c_min = (size_t)(CW - 1) * c_step + 1;
+    const size_t cs = c_stride ? c_stride : (size_t)CW * c_step;
+    if (ys < (size_t)W) return set_err(JPEZY_E_BADARG, std::string(who) + ": y_stride smaller than W");
+    if (cs < c_min) return set_err(JPEZY_E_BADARG, std::string(who) + ": c_stride smaller than (CW-1) * c_step + 1");
+    if (ys > 0xFFFFFFFFull / (size_t)H || cs > 0xFFFFFFFFull / (size_t)CH)
+        return set_err(JPEZY_E_BADARG, std::string(who) + ": y_stride * H and c_stride * CH must fit in 32 bits");
+    const size_t yfs = y_frame_stride ? y_frame_stride : (size_t)H * ys;
+    const size_t cfs = c_frame_stride ? c_frame_stride : (size_t)CH * cs;
+    if (yfs < (size_t)(H - 1) * ys + (size_t)W) return set_err(JPEZY_E_BADARG, std::string(who) + ": y_frame_stride smaller than (H-1) * y_stride + W");
+    if (cfs < (size_t)(CH - 1) * cs + c_min) return set_err(JPEZY_E_BADARG, std::string(who) + ": c_frame_stride smaller than a chroma plane");
+    *L = { CW, CH, ys, cs, yfs, cfs };
+    return JPEZY_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int jpezy_ycc_chroma_size(int W, int H, int* CW, int* CH)
+{
+    if (int rc = check_wh(W, H)) return rc;
+    if (CW) *CW = (W + 1) / 2;
+    if (CH) *CH = (H + 1) / 2;
+    return JPEZY_OK;
+}
+
+int jpezy_ycc_component_size(const jpezy_frame_info* info, int comp, int* w, int* h)
+{
+    if (!info) return set_err(JPEZY_E_BADARG, "ycc_component_size: null argument");
+    if (info->ncomp < 1 || info->ncomp > 3 || comp < 0 || comp >= info->ncomp)
+        return set_err(JPEZY_E_BADARG, "ycc_component_size: the file has no such component");
+    const int hc = info->H[comp], vc = info->V[comp];
+    if (info->width <= 0 || info->height <= 0 || hc < 1 || vc < 1 || info->hmax < hc || info->vmax < vc)
+        return set_err(JPEZY_E_BADARG, "ycc_component_size: not a parsed frame header");
+    if (w) *w = (int)(((long)info->width * hc + info->hmax - 1) / info->hmax);
+    if (h) *h = (int)(((long)info->height * vc + info->vmax - 1) / info->vmax);
+    return JPEZY_OK;
+}
+
+int jpezy_fdct_quant_ycc_dev(jpezy_ctx* c, const uint8_t* d_y, size_t y_stride, const uint8_t* d_cb, const uint8_t* d_cr, size_t c_stride,
+                             int c_step, size_t y_frame_stride, size_t c_frame_stride, int W, int H, int gray, int n_frames,
+                             int16_t* d_coeffs, void* stream)
+{
+    if (int rc = check_wh(W, H)) return rc;
+    YccLayout L;
+    if (int rc = ycc_layout("fdct_quant_ycc_dev", W, H, y_stride, c_stride, c_step, y_frame_stride, c_frame_stride, &L)) return rc;
+    if (!d_y || !d_coeffs || (!gray && (!d_cb || !d_cr))) return set_err(JPEZY_E_BADARG, "fdct_quant_ycc_dev: null device pointer");
+    if (int rc = jpezy_internal_check_dims(c, W, H, n_frames)) return rc;
+    if (!aligned16(d_coeffs)) return set_err(JPEZY_E_BADARG, "d_coeffs must be 16-byte aligned");
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    EncParams p;
+    p.r = d_y;
+    p.g = gray ? nullptr : d_cb; p.b = gray ? nullptr : d_cr;            // gray: the chroma pointers are not read
+    p.plane_stride = L.yfs;
+    p.row_stride = (unsigned)L.ys;
+    p.c_row_stride = (unsigned)L.cs;
+    p.c_step = c_step;
+    p.c_frame_stride = L.cfs;
+    if (int rc = jpezy_internal_enc_params(c, W, H, gray, n_frames, d_coeffs, s, &p)) return rc;
+    for (int f0 = 0; f0 < n_frames; f0 += kMaxFramesPerLaunch) {
+        EncParams q = p;
+        q.n_frames = n_frames - f0 < kMaxFramesPerLaunch ? n_frames - f0 : kMaxFramesPerLaunch;
+        q.r += (size_t)f0 * L.yfs;
+        if (!gray) { q.g += (size_t)f0 * L.cfs; q.b += (size_t)f0 * L.cfs; }
+        q.coeffs += (size_t)f0 * p.coeffs_per_frame;
+        // variant 0: the FP64 kernel's byte loop; every other variant: the f32 kernel's YCC launch (the laboratory's persistent variants
+        // 2 and 3 hand YCC input to it as they do every frame they do not cover)
+        if (c->variant == 0)
+            HIP_TRY(launch_fdct_quant_ycc(q, gray != 0, c->force_exact != 0, s));
+        else
+            HIP_TRY(launch_fdct_quant_f32_ycc(q, gray != 0, c->force_exact, s));
+    }
+    return JPEZY_OK;
+}
+
+int jpezy_dequant_idct_ycc_dev(jpezy_ctx* c, const int16_t* d_coeffs, const uint16_t qt[4][64], const uint8_t comp_tq[3], uint8_t* d_y,
+                               size_t y_stride, uint8_t* d_cb, uint8_t* d_cr, size_t c_stride, int c_step, size_t y_frame_stride,
+                               size_t c_frame_stride, int W, int H, int n_frames, void* stream)
+{
+    if (int rc = check_wh(W, H)) return rc;
+    YccLayout L;
+    if (int rc = ycc_layout("dequant_idct_ycc_dev", W, H, y_stride, c_stride, c_step, y_frame_stride, c_frame_stride, &L)) return rc;
+    if (!d_coeffs || !qt || !comp_tq || !d_y) return set_err(JPEZY_E_BADARG, "dequant_idct_ycc_dev: null pointer");
+    if (int rc = jpezy_internal_check_dims(c, W, H, n_frames)) return rc;
+    if (!aligned16(d_coeffs)) return set_err(JPEZY_E_BADARG, "d_coeffs must be 16-byte aligned");
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = jpezy_internal_upload_dequant(c, qt, comp_tq, s)) return rc;
+    const bool luma_only = !d_cb && !d_cr;
+    DecParams p;
+    p.r = d_y; p.g = d_cb; p.b = d_cr;
+    p.plane_stride = L.yfs;
+    p.row_stride = (unsigned)L.ys;
+    p.c_row_stride = (unsigned)L.cs;
+    p.c_step = c_step;
+    p.c_frame_stride = L.cfs;
+    jpezy_internal_dec_params(c, d_coeffs, W, H, n_frames, &p);
+    for (int f0 = 0; f0 < n_frames; f0 += kMaxFramesPerLaunch) {
+        DecParams q = p;
+        q.n_frames = n_frames - f0 < kMaxFramesPerLaunch ? n_frames - f0 : kMaxFramesPerLaunch;
+        q.coeffs += (size_t)f0 * p.coeffs_per_frame;
+        q.r += (size_t)f0 * L.yfs;
+        if (q.g) q.g += (size_t)f0 * L.cfs;
+        if (q.b) q.b += (size_t)f0 * L.cfs;
+        HIP_TRY(launch_dequant_idct_ycc(q, luma_only, c->force_exact != 0, c->dec_tolerance != 0, s));
+    }
+    return JPEZY_OK;
+}
+
+// host planes -> .jpg bytes on the host: jpezy_encode_jpeg with up to three input segments per band (the Y rows, and the chroma rows as
+// two planes or as one interleaved plane)
+long jpezy_encode_jpeg_ycc(jpezy_ctx* c, const uint8_t* y, size_t y_stride, const uint8_t* cb, const uint8_t* cr, size_t c_stride, int c_step,
+                           int W, int H, int gray, const char* comment, uint8_t* out, size_t cap)
+try {
+    if (int rc = check_wh(W, H)) return rc;
+    YccLayout L;
+    if (int rc = ycc_layout("encode_jpeg_ycc", W, H, y_stride, c_stride, c_step, 0, 0, &L)) return rc;
+    if (!y || !out || (!gray && (!cb || !cr))) return set_err(JPEZY_E_BADARG, "encode_jpeg_ycc: null pointer");
+    if (int rc = jpezy_internal_check_dims(c, W, H, 1)) return rc;
+    if (int rc = check_comment(comment, "encode_jpeg_ycc")) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const int B = gray ? 4 : 6;
+    if (int rc = c->e_coef.reserve(jpezy_coeff_count(W, H, gray) * sizeof(int16_t))) return rc;
+    const std::vector<HostChunk> chunks = plan_host_chunks(W, H, 1, gray ? 1 : 2, c->host_chunk_bytes);
+    // one interleaved plane (Cb and Cr neighbours) travels as one segment: its rows hold 2 * CW sample bytes from the lower pointer
+    const bool inter = !gray && c_step == 2 && (cb + 1 == cr || cr + 1 == cb);
+    const uint8_t* c_lo = inter ? std::min(cb, cr) : nullptr;
+    const size_t c_row_bytes = inter ? (size_t)2 * L.CW : (size_t)(L.CW - 1) * c_step + 1;
+    // a band goes up as it lies in the caller's buffers, row padding included, up to the last sample byte of its last row
+    auto y_bytes = [&](const HostChunk& k) { return (size_t)(k.rows(H) - 1) * L.ys + (size_t)W; };
+    auto c_rows = [&](const HostChunk& k) { return (k.rows(H) + 1) / 2; };
+    auto c_bytes = [&](const HostChunk& k) { return (size_t)(c_rows(k) - 1) * L.cs + c_row_bytes; };
+    auto pad16 = [](size_t n) { return (n + 15) & ~(size_t)15; };
+    size_t max_in = 0;
+    for (const HostChunk& k : chunks) max_in = std::max(max_in, pad16(y_bytes(k)) + (gray ? 0 : (inter ? 1 : 2) * pad16(c_bytes(k))));
+    int rc_kernel = JPEZY_OK;
+    std::string err;
+    auto plan = [&](int i) {
+        const HostChunk& k = chunks[(size_t)i];
+        jpezy_host::ChunkPlan p;
+        p.in.push_back({ const_cast<uint8_t*>(y) + (size_t)k.y0 * 16 * L.ys, y_bytes(k), 0 });
+        if (!gray) {
+            const size_t coff = (size_t)k.y0 * 8 * L.cs, o1 = pad16(y_bytes(k)), o2 = o1 + pad16(c_bytes(k));
+            if (inter) {
+                p.in.push_back({ const_cast<uint8_t*>(c_lo) + coff, c_bytes(k), o1 });
+            } else {
+                p.in.push_back({ const_cast<uint8_t*>(cb) + coff, c_bytes(k), o1 });
+                p.in.push_back({ const_cast<uint8_t*>(cr) + coff, c_bytes(k), o2 });
+            }
+        }
+        return p;
+    };
+    auto kernel = [&](int i, uint8_t* d_in, uint8_t*, hipStream_t s) -> hipError_t {
+        const HostChunk& k = chunks[(size_t)i];
+        const size_t o1 = pad16(y_bytes(k)), o2 = o1 + pad16(c_bytes(k));
+        const uint8_t* d_cb = gray ? nullptr : inter ? d_in + o1 + (cb > cr ? 1 : 0) : d_in + o1;
+        const uint8_t* d_cr = gray ? nullptr : inter ? d_in + o1 + (cr > cb ? 1 : 0) : d_in + o2;
+        const int rc = jpezy_fdct_quant_ycc_dev(c, d_in, L.ys, d_cb, d_cr, L.cs, c_step, 0, 0, W, k.rows(H), gray, 1,
+                                                c->e_coef.as<int16_t>() + k.coef_off(W, H, B), s);
+        if (rc != JPEZY_OK) { rc_kernel = rc; return hipErrorLaunchFailure; }
+        return hipSuccess;
+    };
+    const hipError_t e = c->pipe.run(c->device, c->stream, (int)chunks.size(), max_in, 0, plan, kernel, &err);
+    if (rc_kernel != JPEZY_OK) return rc_kernel;
+    if (e != hipSuccess) return set_err(JPEZY_E_HIP, err.empty() ? std::string("host pipeline: ") + hipGetErrorString(e) : err);
+    return jpezy_write_jpeg_gpu(c, (const int16_t*)c->e_coef.p, W, H, gray, comment, out, cap);
+}
+JPEZY_CATCH
+
+// .jpg bytes -> component planes on the host: jpezy_decode_jpeg with the native-sample store stage of the fused kernel (jpezy's own layout)
+// or of the generic pair (every other layout).  The device planes are tight; an interleaved chroma plane whose Cb and Cr are neighbours
+// is written interleaved on the device and comes down as one plane, any other c_step == 2 request is scattered on the host so that
+// only the caller's sample bytes are written.
+int jpezy_decode_jpeg_ycc(jpezy_ctx* c, const uint8_t* data, size_t len, jpezy_frame_info* info, uint8_t* y, size_t y_stride, size_t y_cap,
+                          uint8_t* cb, uint8_t* cr, size_t c_stride, int c_step, size_t c_cap)
+try {
+    if (c_step != 1 && c_step != 2) return set_err(JPEZY_E_BADARG, "decode_jpeg_ycc: c_step must be 1 (planes) or 2 (one interleaved plane)");
+    if (!data || !info) return set_err(JPEZY_E_BADARG, "decode_jpeg_ycc: null pointer");
+    if (!y && (cb || cr)) return set_err(JPEZY_E_BADARG, "decode_jpeg_ycc: null pointer: a chroma plane without the Y plane");
+    if (!c) return set_err(JPEZY_E_BADARG, "decode_jpeg_ycc: null context");
+    int rc = jpezy_read_jpeg_gpu(c, data, len, info, nullptr, 0);           // header only
+    if (rc < 0) return rc;
+    if (!y && !cb && !cr) return JPEZY_OK;
+    const int W = info->width, H = info->height;
+    if (int rc2 = jpezy_internal_check_dims(c, W, H, 1)) return rc2;
+    if (info->ncomp != 1 && info->ncomp != 3) return set_err(JPEZY_E_UNSUPPORTED, "dimension not supported (the reference accepts 1 or 3)");
+    int cw[3] = { 0, 0, 0 }, ch[3] = { 0, 0, 0 };
+    for (int k = 0; k < info->ncomp; ++k)
+        if (int rc2 = jpezy_ycc_component_size(info, k, &cw[k], &ch[k])) return rc2;
+    uint8_t* host[3] = { y, info->ncomp == 3 ? cb : nullptr, info->ncomp == 3 ? cr : nullptr };     // a one-component file writes Y only
+    const size_t ys = y_stride ? y_stride : (size_t)cw[0];
+    if (ys < (size_t)cw[0]) return set_err(JPEZY_E_BADARG, "decode_jpeg_ycc: y_stride smaller than the Y plane's width");
+    if (y_cap < (size_t)(ch[0] - 1) * ys + (size_t)cw[0]) return set_err(JPEZY_E_NOSPACE, "decode_jpeg_ycc: Y buffer too small");
+    const int cwm = std::max(cw[1], cw[2]);
+    const size_t cs = c_stride ? c_stride : (size_t)cwm * c_step;
+    for (int k = 1; k < 3; ++k) {
+        if (!host[k]) continue;
+        if (cs < (size_t)(cw[k] - 1) * c_step + 1) return set_err(JPEZY_E_BADARG, "decode_jpeg_ycc: c_stride smaller than (wc-1) * c_step + 1");
+        if (c_cap < (size_t)(ch[k] - 1) * cs + (size_t)(cw[k] - 1) * c_step + 1) return set_err(JPEZY_E_NOSPACE, "decode_jpeg_ycc: chroma buffer too small");
+    }
+    const size_t ncoef = (size_t)info->mcu_cols * info->mcu_rows * info->blocks_per_mcu * 64;
+    // sized from untrusted SOF0 fields: a block costs at least 2 bits of scan (1-bit DC code + 1-bit EOB code)
+    if (ncoef / 64 > 4 * len) return set_err(JPEZY_E_FORMAT, "decode_jpeg_ycc: scan too short for the declared dimensions");
+    const uint8_t tq[3] = { (uint8_t)info->Tq[0], (uint8_t)info->Tq[1], (uint8_t)info->Tq[2] };
+    const bool own_layout = info->ncomp == 3 && info->precision == 8 && info->H[0] == 2 && info->V[0] == 2 && info->H[1] == 1 &&
+                            info->V[1] == 1 && info->H[2] == 1 && info->V[2] == 1;
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc2 = c->out.reserve(ncoef * sizeof(int16_t))) return rc2;
+    rc = jpezy_read_jpeg_gpu(c, data, len, info, (int16_t*)c->out.p, ncoef);
+    if (rc < 0) return rc;
+    // device planes: Y tight in in[0]; chroma tight planes in in[1] / in[2], or one tight interleaved plane in in[1]
+    const bool inter = c_step == 2 && host[1] && host[2] && (host[1] + 1 == host[2] || host[2] + 1 == host[1]) && cw[1] == cw[2] && ch[1] == ch[2] &&
+                       cs >= (size_t)2 * cw[1];
+    if (int rc2 = c->in[0].reserve((size_t)cw[0] * ch[0])) return rc2;
+    uint8_t* d[3] = { (uint8_t*)c->in[0].p, nullptr, nullptr };
+    if (inter) {
+        if (int rc2 = c->in[1].reserve((size_t)2 * cw[1] * ch[1])) return rc2;
+        d[1] = (uint8_t*)c->in[1].p + (host[1] > host[2] ? 1 : 0);
+        d[2] = (uint8_t*)c->in[1].p + (host[2] > host[1] ? 1 : 0);
+    } else {
+        for (int k = 1; k < 3; ++k) {
+            if (!host[k]) continue;
+            if (int rc2 = c->in[k].reserve((size_t)cwm * ch[k])) return rc2;
+            d[k] = (uint8_t*)c->in[k].p;
+        }
+    }
+    const int d_step = inter ? 2 : 1;
+    const size_t d_cs = inter ? (size_t)2 * cw[1] : (size_t)cwm;       // (the generic pair: one chroma row stride for both components)
+    if (own_layout) {
+        if (int rc2 = jpezy_dequant_idct_ycc_dev(c, (const int16_t*)c->out.p, info->qt, tq, d[0], (size_t)cw[0], d[1], d[2], d_cs, d_step, 0, 0, W, H, 1,
+                                                 c->stream))
+            return rc2;
+    } else {
+        const uint8_t hs[3] = { (uint8_t)info->H[0], (uint8_t)info->H[1], (uint8_t)info->H[2] };
+        const uint8_t vs[3] = { (uint8_t)info->V[0], (uint8_t)info->V[1], (uint8_t)info->V[2] };
+        if ((size_t)W * (size_t)H > 0xFFFFFFFFull) return set_err(JPEZY_E_BADARG, "decode_jpeg_ycc: image of more than 2^32 bytes");
+        if (int rc2 = jpezy_internal_generic_dev_core(c, (const int16_t*)c->out.p, info->qt, info->ncomp, hs, vs, tq, W, H, 0, info->precision,
+                                                      d[0], d[1], d[2], c->stream, nullptr, 1, 0, 0, (unsigned)cw[0], d_step, (unsigned)d_cs))
+            return rc2;
+    }
+    // only sample bytes of the caller's rows are written
+    HIP_TRY(hipMemcpy2DAsync(y, ys, d[0], (size_t)cw[0], (size_t)cw[0], (size_t)ch[0], hipMemcpyDeviceToHost, c->stream));
+    std::vector<uint8_t> tmp[3];
+    if (inter) {
+        HIP_TRY(hipMemcpy2DAsync(std::min(host[1], host[2]), cs, c->in[1].p, d_cs, d_cs, (size_t)ch[1], hipMemcpyDeviceToHost, c->stream));
+    } else {
+        for (int k = 1; k < 3; ++k) {
+            if (!host[k]) continue;
+            if (c_step == 1) {
+                HIP_TRY(hipMemcpy2DAsync(host[k], cs, d[k], d_cs, (size_t)cw[k], (size_t)ch[k], hipMemcpyDeviceToHost, c->stream));
+            } else {
+                tmp[k].resize((size_t)d_cs * ch[k]);
+                HIP_TRY(hipMemcpyAsync(tmp[k].data(), d[k], tmp[k].size(), hipMemcpyDeviceToHost, c->stream));
+            }
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (int k = 1; k < 3; ++k)
+        if (!tmp[k].empty())
+            for (int yy = 0; yy < ch[k]; ++yy)
+                for (int xx = 0; xx < cw[k]; ++xx) host[k][(size_t)yy * cs + (size_t)xx * 2] = tmp[k][(size_t)yy * d_cs + xx];
+    return JPEZY_OK;
+}
+JPEZY_CATCH
+
+}  // extern "C"

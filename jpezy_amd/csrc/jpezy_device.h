@@ -84,6 +84,12 @@ struct EncParams {
     const uint8_t* pix = nullptr;
     unsigned row_stride = 0;
     int pix_bytes = 0, swap_rb = 0;
+    // Planar YCbCr 4:2:0 input, jpezy_fdct_quant_ycc_dev (the YCC kernel instances only): r = the Y plane (rows row_stride apart, frames
+    // plane_stride), g / b = the Cb / Cr samples (0, 0) -- rows c_row_stride apart, samples c_step (1: planes, 2: one interleaved plane),
+    // frames c_frame_stride.  Appended behind every field the other instances read: their argument offsets are what they were.
+    unsigned c_row_stride = 0;
+    int c_step = 0;
+    size_t c_frame_stride = 0;
 #ifdef JPEZY_TRACE
     unsigned long long* trace;       // development builds only (tools/profile/wave_trace.py): 4 words per wave
 #endif
@@ -113,6 +119,11 @@ struct DecParams {
     uint8_t* pix = nullptr;
     unsigned row_stride = 0;
     int pix_bytes = 0, swap_rb = 0;
+    // native planar YCbCr 4:2:0 output, jpezy_dequant_idct_ycc_dev: the same fields as EncParams' (r = Y, g = Cb, b = Cr; g == b == null:
+    // luma only)
+    unsigned c_row_stride = 0;
+    int c_step = 0;
+    size_t c_frame_stride = 0;
 };
 
 // (magic, shift) such that n / d == (((n - mulhi(n, magic)) >> 1) + mulhi(n, magic)) >> shift for all 32-bit n;
@@ -136,6 +147,9 @@ hipError_t launch_fdct_quant_f32(const EncParams& p, bool gray, int force, hipSt
 hipError_t launch_fdct_quant_f32_packed(const EncParams& p, bool gray, int force, hipStream_t stream);
 hipError_t launch_fdct_quant_packed(const EncParams& p, bool gray, bool force_exact, hipStream_t stream);
 bool packed_is_aligned16(const void* pix, int W, size_t row_stride, size_t frame_stride);
+// ... and for planar YCbCr 4:2:0 samples (EncParams::c_step != 0): no colour conversion, the planes are the file's own sample domain
+hipError_t launch_fdct_quant_f32_ycc(const EncParams& p, bool gray, int force, hipStream_t stream);
+hipError_t launch_fdct_quant_ycc(const EncParams& p, bool gray, bool force_exact, hipStream_t stream);
 // variant 2: the same arithmetic in persistent workgroups with LDS-DMA loader waves (jpezy_kernels_f32_ps.hip); frames whose rows do
 // not divide into groups of four quads, or unaligned planes, go to variant 1's launch.  n_cus: compute units of the device.
 hipError_t launch_fdct_quant_f32_ps(const EncParams& p, bool gray, int force, int n_cus, hipStream_t stream);
@@ -147,6 +161,8 @@ hipError_t launch_fdct_quant_f32_ps2(const EncParams& p, bool gray, int force, i
 hipError_t launch_dequant_idct(const DecParams& p, bool gray, bool force_exact, bool tolerant, hipStream_t stream);
 // the same kernel with the packed store stage (DecParams::pix_bytes != 0)
 hipError_t launch_dequant_idct_packed(const DecParams& p, bool gray, bool force_exact, bool tolerant, hipStream_t stream);
+// the same kernel with the native-sample store stage (DecParams::c_step != 0); gray: luma only
+hipError_t launch_dequant_idct_ycc(const DecParams& p, bool gray, bool force_exact, bool tolerant, hipStream_t stream);
 
 // any-layout decode (jpezy_kernels_generic.hip)
 struct GenericDecParams {
@@ -174,6 +190,11 @@ struct GenericDecParams {
     // frames plane_stride apart (any value then); byte 3 of a 32-bit pixel = 0xFF
     int pix_bytes = 0;
     unsigned row_stride = 0;
+    // native component planes (jpezy_decode_jpeg_ycc on a layout that is not this project's own): ycc != 0 -- r, g, b = sample (0, 0) of
+    // component 0, 1, 2 (null: not written); rows row_stride (component 0) / c_row_stride apart, chroma samples c_step apart; no colour
+    // conversion, no replication
+    int ycc = 0, c_step = 1;
+    unsigned c_row_stride = 0;
 };
 hipError_t launch_dequant_idct_generic(const GenericDecParams& p, hipStream_t stream);
 // frames of p's layout one pair of launches takes (the launcher loops over larger batches); 0: a frame too large for one launch

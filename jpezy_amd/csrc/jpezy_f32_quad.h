@@ -227,6 +227,17 @@ __device__ __forceinline__ void luma8(const uint32_t* wr, const uint32_t* wg, co
     }
 }
 
+// Planar YCbCr input (jpezy_fdct_quant_ycc_dev): the caller's bytes ARE the samples, so the sample stage is byte - 128, exact in FP32
+// (a conversion and a subtraction of small integers), with nothing to guard and no FP64 formula behind it.  w[0..1]: eight samples
+// -> A[k] = (s[k], s[7-k]), the input form of fdct8p, as luma8 delivers it.
+__device__ __forceinline__ void ycc8(const uint32_t* w, f2* A)
+{
+    A[0] = f2{ ubyte<0>(w[0]) - 128.f, ubyte<3>(w[1]) - 128.f };
+    A[1] = f2{ ubyte<1>(w[0]) - 128.f, ubyte<2>(w[1]) - 128.f };
+    A[2] = f2{ ubyte<2>(w[0]) - 128.f, ubyte<1>(w[1]) - 128.f };
+    A[3] = f2{ ubyte<3>(w[0]) - 128.f, ubyte<0>(w[1]) - 128.f };
+}
+
 // two chroma samples (Cb on even-row lanes, Cr on odd-row lanes); k1..k3: this lane's three coefficients
 template <int B0, int B1>
 __device__ __forceinline__ void chroma_px2(uint32_t r0, uint32_t g0, uint32_t b0, uint32_t r1, uint32_t g1, uint32_t b1, float k1,
@@ -489,7 +500,11 @@ struct QuadTrace { unsigned long long t2; unsigned long long ph[8]; };
 struct NoHook { __device__ __forceinline__ void operator()() const {} };
 // after_pixels(): called once the raw pixel registers R, G, B are dead (behind step 2b) -- variant 3 requests the next quad's there
 // DCG: the DC through the generic quantiser (quant_block_column); the one-quad kernel's launcher decides
-template <bool GRAY, int FORCE, bool PS, bool DCG = false, class AFTER_PIXELS>
+// YCC: R[0..3] = the lane's 16 Y bytes, G[0..1] = the 8 bytes of chroma row mcu_y * 8 + (row >> 1), Cb on even-row lanes and Cr on
+// odd-row lanes (where the chroma row pass expects them); B is not read.  Only the sample stage differs: everything from step 3 on
+// sees YL / YR / CS as before.  Samples reach -128 in chroma as they always did in luma (block sums down to -8192, the first entry of
+// the DC table; the per-lane evaluator's bytes are signed: -128 fits).
+template <bool GRAY, int FORCE, bool PS, bool DCG = false, bool YCC = false, class AFTER_PIXELS>
 __device__ __forceinline__ void encode_quad_compute(const EncParams& p, const uint32_t* R, const uint32_t* G, const uint32_t* B, uint32_t* lds,
                                             int lane, int mcu_y, int quad_x, int frame, unsigned qidx, const LaneConsts* pre,
                                             const signed char* dcq_lds, const PsTables* pst, AFTER_PIXELS after_pixels QUAD_TRACE_PARAM)
@@ -522,10 +537,10 @@ __device__ __forceinline__ void encode_quad_compute(const EncParams& p, const ui
     {
         f2* dst = reinterpret_cast<f2*>(ldsf + m * Y_MCU + row * Y_PITCH);
         f2 X[4];
-        luma8(R, G, B, YL);
+        if constexpr (YCC) ycc8(R, YL); else luma8(R, G, B, YL);
         fdct8p(YL, X, kc);
         dst[0] = X[0]; dst[1] = X[1]; dst[2] = X[2]; dst[3] = X[3];
-        luma8(R + 2, G + 2, B + 2, YR);
+        if constexpr (YCC) ycc8(R + 2, YR); else luma8(R + 2, G + 2, B + 2, YR);
         fdct8p(YR, X, kc);
         dst[4] = X[0]; dst[5] = X[1]; dst[6] = X[2]; dst[7] = X[3];
     }
@@ -534,7 +549,8 @@ __device__ __forceinline__ void encode_quad_compute(const EncParams& p, const ui
     // ---- 2b. chroma samples (top-left pixel of every 2x2, ref :134-142): the odd-row lane takes its even neighbour's
     //         pixels (DPP row_shr:4) and computes Cr, the even-row lane Cb.  Only the samples survive, so the raw
     //         pixel registers die here.  Sample s is pixel 2s: byte 2(s & 1) of word s >> 1. ----
-    if (!GRAY) {
+    if constexpr (!GRAY && YCC) ycc8(G, CS);
+    if constexpr (!GRAY && !YCC) {
         const bool odd = (row & 1) != 0;
         uint32_t R2[4], G2[4], B2[4];
 #pragma unroll
@@ -783,12 +799,12 @@ __device__ __forceinline__ void encode_quad_store(const EncParams& p, uint32_t* 
     }
 }
 
-template <bool GRAY, int FORCE, bool PS, bool DCG = false>
+template <bool GRAY, int FORCE, bool PS, bool DCG = false, bool YCC = false>
 __device__ __forceinline__ void encode_quad(const EncParams& p, const uint32_t* R, const uint32_t* G, const uint32_t* B, uint32_t* lds,
                                             int lane, int mcu_y, int quad_x, int frame, unsigned qidx, const LaneConsts* pre,
                                             const signed char* dcq_lds, const PsTables* pst QUAD_TRACE_PARAM)
 {
-    encode_quad_compute<GRAY, FORCE, PS, DCG>(p, R, G, B, lds, lane, mcu_y, quad_x, frame, qidx, pre, dcq_lds, pst, NoHook()
+    encode_quad_compute<GRAY, FORCE, PS, DCG, YCC>(p, R, G, B, lds, lane, mcu_y, quad_x, frame, qidx, pre, dcq_lds, pst, NoHook()
 #ifdef JPEZY_TRACE
                                          , tr
 #endif

@@ -224,6 +224,10 @@ constexpr float DEC_CHROMA_BAND = 5e-5f, DEC_CHROMA_GATE = 512.f;      // intege
 // PIX: 0 = three planes; 3 / 4 = packed (interleaved) pixels of that many bytes (jpezy_dequant_idct_packed_dev) -- only the store stage
 // (the end of step 5) differs: a lane interleaves its 16 pixels into 12 or 16 words with v_perm_b32, two per word (24 or 32 per
 // lane; the fourth byte of a 32-bit pixel comes out of the selector as 0xFF), and stores 48 or 64 contiguous bytes.
+// PIX == 1 (PIX_YCC, jpezy_dequant_idct_ycc_dev): the components at their native sampling -- step 5 is replaced by a store of the
+// clamped samples, no replication and no colour arithmetic (GRAY: luma only).  It is a value of PIX that is no pixel size: the packed
+// store stage is compiled for PIX >= 3 only, the YCC one for PIX == PIX_YCC only.
+constexpr int PIX_YCC = 1;
 template <int PIX>
 __device__ __forceinline__ void store_packed16(uint8_t* dst, bool swap_rb, const uint32_t* Rw, const uint32_t* Gw, const uint32_t* Bw, bool nontemporal)
 {
@@ -587,6 +591,66 @@ __global__ __launch_bounds__(64 * WPB, GRAY ? JPEZY_DEC_WAVES_GRAY : JPEZY_DEC_W
         }
     }
 
+    // ---- 5 (PIX_YCC). revise_value of the samples themselves: 16 Y bytes per lane; the even-row lane holds the Cb row
+    //         mcu_y * 8 + (row >> 1) of its MCU, the odd-row lane the Cr row (Cb[] / Cr[] carry sample - 128 modulo 2^32: restored
+    //         before the clamp, so a forced sample of INT_MIN comes out as 0).  ALIGNED (the launcher): one 16-byte store of Y and one
+    //         8-byte store of a chroma plane, or -- one interleaved plane, Cb and Cr neighbours -- the even-row lane takes the odd
+    //         one's row (DPP) and stores 16 interleaved bytes.  Otherwise single bytes under x < W / CW, y < H / CH. ----
+    if constexpr (PIX == PIX_YCC) {
+        const int py = mcu_y * 16 + row;
+        uint32_t Yw[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) Yw[q] = clamp_pack4(Y + 4 * q);
+        if (live && py < H) {
+            uint8_t* oy = p.r + (size_t)frame * p.plane_stride + (unsigned)py * p.row_stride;   // row_stride * H < 2^32 (entry point)
+            if (ALIGNED) {
+                uint4* d = reinterpret_cast<uint4*>(oy + (unsigned)mcu_x * 16u);
+                if (!GRAY) nt_store16(d, make_uint4(Yw[0], Yw[1], Yw[2], Yw[3])); else *d = make_uint4(Yw[0], Yw[1], Yw[2], Yw[3]);
+            } else {
+#pragma unroll
+                for (int k = 0; k < 16; ++k) {
+                    const int x = mcu_x * 16 + k;
+                    if (x < W) oy[x] = (uint8_t)(Yw[k >> 2] >> ((k & 3) * 8));
+                }
+            }
+        }
+        if (!GRAY) {
+            const bool odd = (row & 1) != 0;
+            int cs[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) cs[k] = (int)((unsigned)(odd ? Cr[k] : Cb[k]) + 128u);
+            const uint32_t c0 = clamp_pack4(cs), c1 = clamp_pack4(cs + 4);
+            // the odd-row neighbour's words, for the interleaved form (outside every lane-dependent branch)
+            const uint32_t n0 = (uint32_t)__builtin_amdgcn_update_dpp((int)c0, (int)c0, 0x104, 0xF, 0x5, false);
+            const uint32_t n1 = (uint32_t)__builtin_amdgcn_update_dpp((int)c1, (int)c1, 0x104, 0xF, 0x5, false);
+            const int cy = mcu_y * 8 + (row >> 1), CW = (W + 1) >> 1, CH = (H + 1) >> 1;
+            if (live && cy < CH) {
+                const size_t coff = (size_t)frame * p.c_frame_stride + (unsigned)cy * p.c_row_stride;   // c_row_stride * CH < 2^32
+                uint8_t* const plane = odd ? p.b : p.g;                                    // null: that component is not wanted
+                uint8_t* oc = plane + coff;
+                if (ALIGNED && p.c_step == 1) {
+                    *reinterpret_cast<uint2*>(oc + (unsigned)mcu_x * 8u) = make_uint2(c0, c1);
+                } else if (ALIGNED) {
+                    if (!odd) {
+                        const bool cb_first = p.g < p.b;                                   // NV12; else NV21
+                        const uint32_t lo0 = cb_first ? c0 : n0, hi0 = cb_first ? n0 : c0, lo1 = cb_first ? c1 : n1, hi1 = cb_first ? n1 : c1;
+                        const uint4 v = make_uint4(__builtin_amdgcn_perm(hi0, lo0, 0x05010400u), __builtin_amdgcn_perm(hi0, lo0, 0x07030602u),
+                                                   __builtin_amdgcn_perm(hi1, lo1, 0x05010400u), __builtin_amdgcn_perm(hi1, lo1, 0x07030602u));
+                        nt_store16(reinterpret_cast<uint4*>((cb_first ? p.g : p.b) + coff + (unsigned)mcu_x * 16u), v);
+                    }
+                } else if (plane != nullptr) {
+                    const unsigned step = (unsigned)p.c_step;
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) {
+                        const int x = mcu_x * 8 + k;
+                        if (x < CW) oc[(unsigned)x * step] = (uint8_t)((k < 4 ? c0 : c1) >> ((k & 3) * 8));
+                    }
+                }
+            }
+        }
+        return;
+    }
+
     // ---- 5. YCbCr -> RGB (ref :567-578), clamp, pack, store ----
     // Y, U = Cb - 128, V = Cr - 128 are integers, so each of r = Y + 1.402 V, g = Y - 0.3441 U - 0.7139 V, b = Y + 1.7718 U is Y plus a
     // term of the chroma sample alone, and revise_value(trunc(Y + t)) == clamp(Y + floor(t)) unless t is an integer whose double
@@ -668,7 +732,7 @@ __global__ __launch_bounds__(64 * WPB, GRAY ? JPEZY_DEC_WAVES_GRAY : JPEZY_DEC_W
     // LDS so that wave 0 stores rows 0..7 and wave 1 rows 8..15 of BOTH quads: eight lanes = one whole line.  The launch takes the
     // same time either way (34.2 us per 4096^2 frame, three interleaved rounds), but half-line non-temporal stores are counted --
     // and moved -- as 63.8 MB of writes for 50.3 MB of planes; whole lines bring WRITE_SIZE to 49.2 MB (profiles/r04_dec_traffic.txt).
-    if (PIX != 0) {
+    if constexpr (PIX >= 3) {
         // Packed pixels: every lane stores its own row segment, 48 or 64 contiguous bytes (the four lanes of a pixel row 192 or 256);
         // the two-wave whole-line swap below is the planar instances' -- these pass through no workgroup barrier at all.  Colour
         // goes out non-temporal and gray plain, the planar kernel's measured choice; the packed form was not measured both ways.
@@ -676,7 +740,7 @@ __global__ __launch_bounds__(64 * WPB, GRAY ? JPEZY_DEC_WAVES_GRAY : JPEZY_DEC_W
         if (live && py < H) {
             const size_t rowoff = (size_t)frame * p.plane_stride + (unsigned)py * p.row_stride;   // row_stride * H < 2^32 (entry point)
             if (ALIGNED) {
-                store_packed16<PIX == 0 ? 3 : PIX>(p.pix + rowoff + (unsigned)mcu_x * (16u * PIX), p.swap_rb != 0, Rw, Gw, Bw, !GRAY);
+                store_packed16<PIX>(p.pix + rowoff + (unsigned)mcu_x * (16u * PIX), p.swap_rb != 0, Rw, Gw, Bw, !GRAY);
             } else {
 #pragma unroll
                 for (int k = 0; k < 16; ++k) {
@@ -786,6 +850,27 @@ hipError_t launch_dequant_idct_packed(const DecParams& p0, bool gray, bool force
     const bool al = packed_is_aligned16(p.pix, p.W, p.row_stride, p.plane_stride);
     if (p.pix_bytes == 3) dec_packed_launch<3>(p, gray, al, force_exact, tolerant, grid, stream);
     else dec_packed_launch<4>(p, gray, al, force_exact, tolerant, grid, stream);
+    return hipGetLastError();
+}
+
+// native planar YCbCr 4:2:0 output: the PIX_YCC instances (gray: luma only).  ALIGNED: W % 16 == 0 and every base and stride a multiple
+// of its access -- 16 bytes of Y; 8 bytes of a chroma plane, or 16 of an interleaved one whose Cb and Cr are neighbours.
+hipError_t launch_dequant_idct_ycc(const DecParams& p0, bool gray, bool force_exact, bool tolerant, hipStream_t stream)
+{
+    const long quads = (long)p0.mcu_rows * p0.quads_per_row;
+    if (quads <= 0 || p0.n_frames <= 0) return hipSuccess;
+    if (p0.n_frames > 65535 || (!gray && p0.c_step != 1 && p0.c_step != 2)) return hipErrorInvalidValue;
+    DecParams p = p0;
+    fast_div_setup((unsigned)p.quads_per_row, &p.qpr_magic, &p.qpr_shift);
+    const dim3 grid((unsigned)((quads + WPB - 1) / WPB), (unsigned)p.n_frames);
+    bool al = p.W % 16 == 0 && p.row_stride % 16 == 0 && p.plane_stride % 16 == 0 && (uintptr_t)p.r % 16 == 0;
+    if (al && !gray) {
+        const uintptr_t g = (uintptr_t)p.g, b = (uintptr_t)p.b;
+        if (!g || !b) al = false;                                       // one chroma plane only: the byte form
+        else if (p.c_step == 1) al = (g | b | p.c_row_stride | p.c_frame_stride) % 8 == 0;
+        else al = (g > b ? g - b : b - g) == 1 && ((g < b ? g : b) | p.c_row_stride | p.c_frame_stride) % 16 == 0;
+    }
+    dec_packed_launch<PIX_YCC>(p, gray, al, force_exact, tolerant, grid, stream);
     return hipGetLastError();
 }
 

@@ -111,24 +111,38 @@ struct BlockRef {   // the frame's planes: what the exact path needs to find a b
     const uint8_t* b;
     int W, H;
     unsigned row_stride, pix_bytes;     // packed pixels only (PACKED instances): bytes between rows / between pixels of one channel
-};
+    unsigned c_row_stride, c_step;      // YCC instances: r, g, b = the Y, Cb, Cr samples (0, 0) of the frame; Y rows row_stride apart,
+};                                      // chroma rows c_row_stride and chroma samples c_step apart
 
 // ---- exact-order FDCT + quantise of ONE coefficient by the whole wave (ref jpezy_encoder.hpp:146-172) ----
 // All arguments are wave-uniform.  Lane k owns term k = y*8+x of the reference's double loop: it re-reads its
 // pixel, converts it, forms (pic*cos[j][x])*cos[i][y]; the 64 terms are then added in the reference's order.
 // comp 0: luma block with top-left pixel (px0,py0), step 1.  comp 1/2: Cb/Cr of the MCU at (px0,py0), step 2
 // (top-left sample of each 2x2, ref :134-142).  Coordinates clamp to the image (ref :101,104).
-template <bool PACKED = false>
+// YCC: the planes hold the samples themselves (jpezy_fdct_quant_ycc_dev): pic = byte - 128 of luma sample (px0 + x, py0 + y) or of
+// chroma sample (px0 / 2 + x, py0 / 2 + y), clamped to the plane (W x H, ceil(W/2) x ceil(H/2)).
+template <bool PACKED = false, bool YCC = false>
 __device__ __forceinline__ int exact_fdct_coef_wave(const BlockRef& img, int px0, int py0, int comp, int i, int j,
                                                     int Q, int lane)
 {
     const int step = comp ? 2 : 1;
     const int y = lane >> 3, x = lane & 7;
-    const int yy = min(py0 + y * step, img.H - 1);
-    const int xx = min(px0 + x * step, img.W - 1);
-    const size_t idx = PACKED ? (size_t)yy * img.row_stride + (size_t)xx * img.pix_bytes : (size_t)yy * img.W + xx;
-    const double rf = (double)img.r[idx], gf = (double)img.g[idx], bf = (double)img.b[idx];
-    const double pic = comp == 0 ? ref_y(rf, gf, bf) : comp == 1 ? ref_cb(rf, gf, bf) : ref_cr(rf, gf, bf);
+    double pic;
+    if constexpr (YCC) {
+        if (comp == 0) {
+            const int yy = min(py0 + y, img.H - 1), xx = min(px0 + x, img.W - 1);
+            pic = (double)((int)img.r[(size_t)yy * img.row_stride + xx] - 128);
+        } else {
+            const int yy = min((py0 >> 1) + y, ((img.H + 1) >> 1) - 1), xx = min((px0 >> 1) + x, ((img.W + 1) >> 1) - 1);
+            pic = (double)((int)(comp == 1 ? img.g : img.b)[(size_t)yy * img.c_row_stride + (size_t)xx * img.c_step] - 128);
+        }
+    } else {
+        const int yy = min(py0 + y * step, img.H - 1);
+        const int xx = min(px0 + x * step, img.W - 1);
+        const size_t idx = PACKED ? (size_t)yy * img.row_stride + (size_t)xx * img.pix_bytes : (size_t)yy * img.W + xx;
+        const double rf = (double)img.r[idx], gf = (double)img.g[idx], bf = (double)img.b[idx];
+        pic = comp == 0 ? ref_y(rf, gf, bf) : comp == 1 ? ref_cb(rf, gf, bf) : ref_cr(rf, gf, bf);
+    }
     const double sum = ordered_wave_sum(pic * c_cos[j * 8 + x] * c_cos[i * 8 + y]);
     const double cu = j ? 1.0 : JPEZY_S, cv = i ? 1.0 : JPEZY_S;
     const int dct = (int)(sum * cu * cv / 4);
@@ -203,7 +217,9 @@ __device__ __forceinline__ double byte_of(const uint32_t* w, int k)
 // ======================================================================================================
 // PACKED (jpezy_fdct_quant_packed_dev): r, g, b are the channel bytes of pixel (0, 0) of an interleaved buffer, p.pix_bytes between
 // pixels and p.row_stride between rows; such input takes the byte loop (ALIGNED is never set with it)
-template <bool GRAY, bool ALIGNED, bool FORCE_EXACT, bool PACKED = false>
+// YCC (jpezy_fdct_quant_ycc_dev): r = the Y plane, g / b = the Cb / Cr samples; the byte loop fetches the lane's 16 Y samples and the 8
+// samples of its chroma row (Cb on even-row lanes, Cr on odd-row lanes), and the two conversions become byte - 128
+template <bool GRAY, bool ALIGNED, bool FORCE_EXACT, bool PACKED = false, bool YCC = false>
 __global__ __launch_bounds__(64 * WPB, 4) void fdct_quant_kernel(EncParams p)
 {
     __shared__ __attribute__((aligned(16))) uint32_t lds_all[WPB][WAVE_LDS_DWORDS];
@@ -229,13 +245,28 @@ __global__ __launch_bounds__(64 * WPB, 4) void fdct_quant_kernel(EncParams p)
     const int mcu_x = live ? mcu_x_raw : p.mcu_cols - 1;
     const int W = p.W, H = p.H;
     const uint8_t* pr = p.r + (size_t)frame * p.plane_stride;
-    const uint8_t* pg = p.g + (size_t)frame * p.plane_stride;
-    const uint8_t* pb = p.b + (size_t)frame * p.plane_stride;
-    const BlockRef img = { pr, pg, pb, W, H, PACKED ? p.row_stride : 0u, PACKED ? (unsigned)p.pix_bytes : 0u };
+    const uint8_t* pg = p.g + (size_t)frame * (YCC ? p.c_frame_stride : p.plane_stride);
+    const uint8_t* pb = p.b + (size_t)frame * (YCC ? p.c_frame_stride : p.plane_stride);
+    const BlockRef img = { pr, pg, pb, W, H, PACKED || YCC ? p.row_stride : 0u, PACKED ? (unsigned)p.pix_bytes : 0u,
+                           YCC ? p.c_row_stride : 0u, YCC ? (unsigned)p.c_step : 0u };
 
     // ---- 1. stream this lane's 16-pixel row segment of the three planes ----
     uint32_t R[4], G[4], B[4];
-    {
+    if constexpr (YCC) {
+        const int y = min(mcu_y * 16 + row, H - 1), cy = min(mcu_y * 8 + (row >> 1), ((H + 1) >> 1) - 1), CW = (W + 1) >> 1;
+        const uint8_t* py = pr + (size_t)y * p.row_stride;
+        const uint8_t* pc = ((row & 1) ? pb : pg) + (size_t)cy * p.c_row_stride;
+#pragma unroll
+        for (int w4 = 0; w4 < 4; ++w4) {
+            uint32_t ay = 0, ac = 0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                ay |= (uint32_t)py[min(mcu_x * 16 + w4 * 4 + k, W - 1)] << (8 * k);
+                if (!GRAY && w4 < 2) ac |= (uint32_t)pc[(size_t)min(mcu_x * 8 + w4 * 4 + k, CW - 1) * (size_t)p.c_step] << (8 * k);
+            }
+            R[w4] = ay; G[w4] = ac; B[w4] = 0;
+        }
+    } else {
         const int y = min(mcu_y * 16 + row, H - 1);             // edge replication, ref :101
         const size_t rowoff = PACKED ? (size_t)y * p.row_stride : (size_t)y * W;
         if (ALIGNED) {
@@ -266,7 +297,7 @@ __global__ __launch_bounds__(64 * WPB, 4) void fdct_quant_kernel(EncParams p)
     {
         double yv[16], X[16];
 #pragma unroll
-        for (int k = 0; k < 16; ++k) yv[k] = ref_y(byte_of(R, k), byte_of(G, k), byte_of(B, k));
+        for (int k = 0; k < 16; ++k) yv[k] = YCC ? byte_of(R, k) - 128.0 : ref_y(byte_of(R, k), byte_of(G, k), byte_of(B, k));
         fdct8(yv, X);
         fdct8(yv + 8, X + 8);
         double2* dst = reinterpret_cast<double2*>(lds + m * Y_MCU + row * Y_PITCH);
@@ -324,7 +355,7 @@ __global__ __launch_bounds__(64 * WPB, 4) void fdct_quant_kernel(EncParams p)
         double cv[8], cX[8];
 #pragma unroll
         for (int k = 0; k < 8; ++k)
-            cv[k] = __builtin_trunc((k1 * byte_of(R2, 2 * k) - k2 * byte_of(G2, 2 * k)) + k3 * byte_of(B2, 2 * k));
+            cv[k] = YCC ? byte_of(G, k) - 128.0 : __builtin_trunc((k1 * byte_of(R2, 2 * k) - k2 * byte_of(G2, 2 * k)) + k3 * byte_of(B2, 2 * k));
         fdct8(cv, cX);
         double2* dst = reinterpret_cast<double2*>(lds + m * C_MCU + (odd ? C_COMP : 0) + (row >> 1) * C_PITCH);
 #pragma unroll
@@ -369,7 +400,7 @@ __global__ __launch_bounds__(64 * WPB, 4) void fdct_quant_kernel(EncParams p)
                 int px0 = emx * 16, py0 = mcu_y * 16, comp = 0;
                 if (eb < 4) { px0 += (eb & 1) * 8; py0 += (eb >> 1) * 8; } else { comp = eb - 3; }
                 const int Q = tab->qt[comp ? 1 : 0][nat];
-                const int qv = exact_fdct_coef_wave<PACKED>(img, px0, py0, comp, ei, ej, Q, lane);
+                const int qv = exact_fdct_coef_wave<PACKED, YCC>(img, px0, py0, comp, ei, ej, Q, lane);
                 if (lane == 0) *reinterpret_cast<int16_t*>(stage + blk * STG_BLK + 2 * (int)c_zzinv[nat]) = (int16_t)qv;
                 ++done;
             }
@@ -427,6 +458,21 @@ hipError_t launch_fdct_quant_packed(const EncParams& p, bool gray, bool force_ex
     } else {
         if (force_exact) hipLaunchKernelGGL((fdct_quant_kernel<false, false, true, true>), grid, dim3(64 * WPB), 0, stream, p);
         else hipLaunchKernelGGL((fdct_quant_kernel<false, false, false, true>), grid, dim3(64 * WPB), 0, stream, p);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_fdct_quant_ycc(const EncParams& p, bool gray, bool force_exact, hipStream_t stream)
+{
+    const long quads = (long)p.n_frames * p.mcu_rows * p.quads_per_row;
+    if (quads <= 0) return hipSuccess;
+    const dim3 grid((unsigned)((quads + WPB - 1) / WPB));
+    if (gray) {
+        if (force_exact) hipLaunchKernelGGL((fdct_quant_kernel<true, false, true, false, true>), grid, dim3(64 * WPB), 0, stream, p);
+        else hipLaunchKernelGGL((fdct_quant_kernel<true, false, false, false, true>), grid, dim3(64 * WPB), 0, stream, p);
+    } else {
+        if (force_exact) hipLaunchKernelGGL((fdct_quant_kernel<false, false, true, false, true>), grid, dim3(64 * WPB), 0, stream, p);
+        else hipLaunchKernelGGL((fdct_quant_kernel<false, false, false, false, true>), grid, dim3(64 * WPB), 0, stream, p);
     }
     return hipGetLastError();
 }

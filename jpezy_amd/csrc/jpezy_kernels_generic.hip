@@ -275,6 +275,32 @@ __global__ __launch_bounds__(256) void generic_rgb_kernel(GenericDecParams p)
     }
 }
 
+// Native component planes (GenericDecParams::ycc, jpezy_decode_jpeg_ycc on a layout that is not this project's own): component c comes
+// out at its own sampling, ceil(W * H_c / hmax) x ceil(H * V_c / vmax) samples, block (kx, ky) of MCU (ux, uy) at ((ux * H_c + kx) * 8,
+// (uy * V_c + ky) * 8); every byte is revise_value of the integer sample (INT_MIN from ref_int: 0).  No replication, no make_rgb.
+// One thread: four samples of a component row (they lie in one block row of one block); blockIdx.z: the component.
+__global__ __launch_bounds__(256) void generic_ycc_kernel(GenericDecParams p)
+{
+    const int c = (int)blockIdx.z;
+    uint8_t* const plane = c == 0 ? p.r : c == 1 ? p.g : p.b;
+    if (c >= p.ncomp || plane == nullptr) return;
+    const unsigned chh = (unsigned)p.ch[c], cvv = (unsigned)p.cv[c];
+    const unsigned wc = ((unsigned)p.W * chh + (unsigned)p.hmax - 1u) / (unsigned)p.hmax;
+    const unsigned hc = ((unsigned)p.H * cvv + (unsigned)p.vmax - 1u) / (unsigned)p.vmax;
+    const unsigned x0 = (blockIdx.x * 64u + (threadIdx.x & 63u)) * 4u;
+    const unsigned y = blockIdx.y * 4u + (threadIdx.x >> 6);
+    if (y >= hc || x0 >= wc) return;
+    const unsigned bxq = x0 >> 3, byq = y >> 3;
+    const unsigned ux = bxq / chh, kx = bxq - ux * chh, uy = byq / cvv, ky = byq - uy * cvv;
+    const size_t blk = ((size_t)uy * p.mcu_cols + ux) * (size_t)p.blocks_per_mcu + (unsigned)p.blk_start[c] + ky * chh + kx;
+    const int4 v = *reinterpret_cast<const int4*>(p.samples + blk * 64 + (y & 7u) * 8u + (x0 & 7u));
+    const int smp[4] = { v.x, v.y, v.z, v.w };
+    const unsigned npx = min(4u, wc - x0);
+    const unsigned step = c ? (unsigned)p.c_step : 1u;
+    uint8_t* dst = plane + (size_t)y * (c ? p.c_row_stride : p.row_stride) + (size_t)x0 * step;
+    for (unsigned j = 0; j < npx; ++j) dst[j * step] = (uint8_t)min(max(smp[j], 0), 255);
+}
+
 }  // namespace generic
 
 int generic_frames_per_launch(const GenericDecParams& p)
@@ -308,6 +334,11 @@ hipError_t launch_dequant_idct_generic(const GenericDecParams& p_in, hipStream_t
         q.r += (size_t)f0 * p.plane_stride; q.g += (size_t)f0 * p.plane_stride; q.b += (size_t)f0 * p.plane_stride;
         const long nblk = fblk * q.n_frames;
         hipLaunchKernelGGL(generic::generic_idct_kernel, dim3((unsigned)((nblk + generic::G_BLOCKS - 1) / generic::G_BLOCKS)), dim3(64), 0, s, q, nblk);
+        if (q.ycc) {                                            // native component planes (one frame): no plane is larger than W x H
+            hipLaunchKernelGGL(generic::generic_ycc_kernel, dim3(gx, gy, (unsigned)q.ncomp), dim3(256), 0, s, q);
+            if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+            continue;
+        }
         if (q.pix_bytes == 3) hipLaunchKernelGGL(generic::generic_rgb_kernel<3>, dim3(gx, gy, (unsigned)q.n_frames), dim3(256), 0, s, q);
         else if (q.pix_bytes == 4) hipLaunchKernelGGL(generic::generic_rgb_kernel<4>, dim3(gx, gy, (unsigned)q.n_frames), dim3(256), 0, s, q);
         else hipLaunchKernelGGL(generic::generic_rgb_kernel<0>, dim3(gx, gy, (unsigned)q.n_frames), dim3(256), 0, s, q);

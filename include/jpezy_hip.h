@@ -563,6 +563,67 @@ int jpezy_decode_jpeg_scaled_packed(jpezy_ctx* ctx, const uint8_t* data, size_t 
                                     int format, size_t row_stride, uint8_t* pix, size_t pix_cap);
 
 /*
+ * REGION DECODE (a crop window of the picture, full size or reduced).  The reference decodes whole pictures only; a loader that feeds
+ * crops, a viewer that tiles a large scan or a detector that re-reads a box wants a part.  The definition is this project's own
+ *  and adds no arithmetic:
+ *
+ *   Coordinates   a region {x, y, w, h} lives in the picture at the requested scale, Ws x Hs = jpezy_scaled_size(W, H, scale_denom),
+ *                 scale_denom one of 1, 2, 4, 8
+ *   Result        output byte (i, j) of every plane, 0 <= i < w, 0 <= j < h, is byte (x + i, y + j) of what jpezy_decode_jpeg_scaled gives
+ *                 for the same file, gray and scale_denom -- at scale_denom 1 that is jpezy_decode_jpeg in its exact mode.  Packed pixels:
+ *                 the same against jpezy_decode_jpeg_scaled_packed.  Chroma is replicated, not interpolated, and make_rgb is per pixel, so
+ *                 a pixel depends only on the MCU that covers it and the slice of the decode is the decode of the MCUs the window touches
+ *   Inside        w, h >= 1, x, y >= 0, x + w <= Ws, y + h <= Hs; anything else is JPEZY_E_BADARG with a message that names the region and
+ *                 Ws x Hs.  There is no silent clipping
+ *   Arithmetic    every sample is evaluated in the definition's order (the scaled section's sum with N = 8 / scale_denom, N = 8 included:
+ *                 dequantise in 32-bit int, v outer, u inner, left to right in binary64, int(sum / 4 + level)): no fast path, no guard band.
+ *                 jpezy_ctx_set_force_exact and jpezy_ctx_set_decode_tolerance have nothing to act on and the fallback counter is not
+ *                 advanced
+ *   Whole picture a region that is the whole picture is handed to the reduced-size entry point of the same shape (and by it, at
+ *                 scale_denom 1, to the full-size one) under that entry's own rules: it costs what it costs today.  One exception: a
+ *                 device batch at scale_denom 1 whose plane or frame stride is no multiple of 4, which the full-size batch entry refuses,
+ *                 stays with the region kernel
+ *   What is saved the inverse transform, the colour stage and the stores run over the MCUs that intersect the window only, only their
+ *                 coefficient blocks are read, and only w * h bytes per plane (h rows of w * bytes) travel back to the host
+ *   What is not   the WHOLE scan is still Huffman-decoded and the coefficient buffer stays full size: jpezy_decode_jpeg_region pays the
+ *                 upload and the entropy decoding of the whole file
+ *   Bytes touched no byte outside the w x h output is written: never row padding, never anything between the frames of a batch
+ *
+ * NOT provided: several regions per call, regions in jpezy_decode_jpeg_batch, YCC-plane output of a region, skipping the Huffman decoding
+ * of restart intervals outside the window.
+ */
+typedef struct jpezy_rect { int x, y, w, h; } jpezy_rect;
+/* JPEZY_OK when region lies inside a W x H file decoded at 1 / scale_denom, else JPEZY_E_BADARG and the message.  Pure host function. */
+int jpezy_region_check(int W, int H, int scale_denom, const jpezy_rect* region);
+/* jpezy_dequant_idct_scaled_dev for a window (stands in for decoder/jpezy_decoder.hpp:504-578, 645-676 over the MCUs the window touches; the
+ * reference has no such mode, the definition above is this project's own): d_coeffs the WHOLE frames' coefficients as jpezy_read_jpeg_gpu
+ * leaves them, d_r, d_g, d_b planes of w*h bytes, frame f's at + f * plane_stride (>= w*h, no alignment asked).  Null pointers, scale,
+ * region and strides are refused before the context is looked at.  One launch per 65535 frames, no scratch; the generic entry's table and
+ * capture rules apply.  Asynchronous on `stream`. */
+int jpezy_dequant_idct_region_dev(jpezy_ctx* ctx, const int16_t* d_coeffs, const uint16_t qt[4][64], int ncomp, const uint8_t comp_h[3],
+                                  const uint8_t comp_v[3], const uint8_t comp_tq[3], int precision, int W, int H, int gray, int scale_denom,
+                                  const jpezy_rect* region, int n_frames, size_t plane_stride, uint8_t* d_r, uint8_t* d_g, uint8_t* d_b,
+                                  void* stream);
+/* The same writing packed pixels (same reference lines, same remark).  The addressing rules of the packed section apply with w, h for W, H:
+ * pixel (i, j) of the window of frame f at d_pix + f*frame_stride + j*row_stride + i*bytes, row_stride 0 = w*bytes, frame_stride 0 =
+ * h*row_stride, only bytes [0, w*bytes) of a row are written, byte 3 of a 32-bit pixel is 0xFF. */
+int jpezy_dequant_idct_region_packed_dev(jpezy_ctx* ctx, const int16_t* d_coeffs, const uint16_t qt[4][64], int ncomp,
+                                         const uint8_t comp_h[3], const uint8_t comp_v[3], const uint8_t comp_tq[3], int precision, int W,
+                                         int H, int gray, int scale_denom, const jpezy_rect* region, int format, size_t row_stride,
+                                         size_t frame_stride, int n_frames, uint8_t* d_pix, void* stream);
+/* jpezy_decode_jpeg_scaled for a window (decoder/jpezy_decoder.hpp:76-134 with the region stage; the reference has no such mode, the
+ * definition is this project's own): header parse and Huffman decoding of the whole file exactly as jpezy_decode_jpeg does them (GPU
+ * decoder, host decoder for what it declines), then the region stage and a download of w*h bytes per plane.  info keeps the FILE's width
+ * and height.  r, g, b NULL: header only, and the region is then checked for w, h >= 1 and x, y >= 0 alone; plane_cap < w*h:
+ * JPEZY_E_NOSPACE. */
+int jpezy_decode_jpeg_region(jpezy_ctx* ctx, const uint8_t* data, size_t len, int gray, int scale_denom, const jpezy_rect* region,
+                             jpezy_frame_info* info, uint8_t* r, uint8_t* g, uint8_t* b, size_t plane_cap);
+/* The same into host packed pixels (jpezy_decode_jpeg_scaled_packed for a window; same reference lines and remark): pix NULL: header only;
+ * pix_cap < (h-1)*row_stride + w*bytes: JPEZY_E_NOSPACE. */
+int jpezy_decode_jpeg_region_packed(jpezy_ctx* ctx, const uint8_t* data, size_t len, int gray, int scale_denom, const jpezy_rect* region,
+                                    jpezy_frame_info* info, int format, size_t row_stride, uint8_t* pix, size_t pix_cap);
+
+/*
  * PLANAR YCbCr 4:2:0 SAMPLES (I420 / YV12 / NV12 / NV21) IN AND OUT.  The file format is full-range BT.601 YCbCr sampled 2x2, 1x1, 1x1: a
  * caller that already holds such planes (a video decoder, a camera, an ISP) holds the file's own sample domain.  The reference only takes
  * RGB (encoder/jpezy_encoder.hpp:24-28) and only gives RGB (decoder/jpezy_decoder.hpp:531-578), so the definition is this project's own
@@ -600,7 +661,7 @@ int jpezy_decode_jpeg_scaled_packed(jpezy_ctx* ctx, const uint8_t* data, size_t 
  *                 and _set_restart_interval act as on the RGB entries.  Encode variant 0 (FP64) reads the planes through its byte loop; the
  *                 laboratory's variants 2 and 3 hand YCC input to variant 1's launch
  *
- * NOT provided in YCC form: jpezy_decode_jpeg_batch, the multi-GPU handle, reduced-size decode, the host-buffer jpezy_fdct_quant /
+ * NOT provided in YCC form: jpezy_decode_jpeg_batch, the multi-GPU handle, reduced-size decode, region decode, the host-buffer jpezy_fdct_quant /
  * jpezy_dequant_idct, the jpezy::encoder / decoder class surface, 4:2:2 / 4:4:4 INPUT, limited-range (16-235) video levels: the caller's
  * planes are taken as the file's full-range samples.
  */

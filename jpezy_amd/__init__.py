@@ -19,6 +19,7 @@ from .api import (  # noqa: F401
     PIX_BGRA32,
     PIX_RGB24,
     PIX_RGBA32,
+    Rect,
     coeff_count,
     encode_batch_multi,
     library_path,
@@ -26,6 +27,7 @@ from .api import (  # noqa: F401
     mcu_grid,
     optimal_table,
     read_jpeg,
+    region_check,
     scaled_size,
     shard_range,
     write_jpeg,
@@ -35,6 +37,6 @@ from .api import (  # noqa: F401
 )
 
 __all__ = [
-    "Context", "Decoder", "Encoder", "FrameInfo", "JpezyError", "MultiEncoder", "PIX_BGR24", "PIX_BGRA32", "PIX_RGB24", "PIX_RGBA32", "coeff_count", "encode_batch_multi", "library_path",
-    "load_library", "mcu_grid", "optimal_table", "read_jpeg", "scaled_size", "shard_range", "write_jpeg", "write_jpeg_batch", "ycc_chroma_size", "ycc_component_size",
+    "Context", "Decoder", "Encoder", "FrameInfo", "JpezyError", "MultiEncoder", "PIX_BGR24", "PIX_BGRA32", "PIX_RGB24", "PIX_RGBA32", "Rect", "coeff_count", "encode_batch_multi", "library_path",
+    "load_library", "mcu_grid", "optimal_table", "read_jpeg", "region_check", "scaled_size", "shard_range", "write_jpeg", "write_jpeg_batch", "ycc_chroma_size", "ycc_component_size",
 ]

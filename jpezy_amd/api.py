@@ -34,6 +34,11 @@ class FrameInfo(C.Structure):
     ]
 
 
+class Rect(C.Structure):
+    """jpezy_rect: a window of the picture at the requested scale"""
+    _fields_ = [("x", C.c_int), ("y", C.c_int), ("w", C.c_int), ("h", C.c_int)]
+
+
 class MultiOut(C.Structure):
     _fields_ = [("coeffs", C.c_void_p), ("jpg", C.c_void_p), ("jpg_stride", C.c_size_t), ("jpg_sizes", C.POINTER(C.c_longlong)),
                 ("on_root_device", C.c_int)]
@@ -116,6 +121,14 @@ ABI = [
                                                        C.c_size_t, C.c_size_t, C.c_int, _vp, _vp]),
     ("jpezy_decode_jpeg_scaled", C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.c_int, C.POINTER(FrameInfo), _vp, _vp, _vp, C.c_size_t]),
     ("jpezy_decode_jpeg_scaled_packed", C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.c_int, C.POINTER(FrameInfo), C.c_int, C.c_size_t, _vp, C.c_size_t]),
+    ("jpezy_region_check", C.c_int, [C.c_int, C.c_int, C.c_int, _vp]),
+    ("jpezy_dequant_idct_region_dev", C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int,
+                                                C.c_size_t, _vp, _vp, _vp, _vp]),
+    ("jpezy_dequant_idct_region_packed_dev", C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp,
+                                                       C.c_int, C.c_size_t, C.c_size_t, C.c_int, _vp, _vp]),
+    ("jpezy_decode_jpeg_region", C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.c_int, _vp, C.POINTER(FrameInfo), _vp, _vp, _vp, C.c_size_t]),
+    ("jpezy_decode_jpeg_region_packed", C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.c_int, _vp, C.POINTER(FrameInfo), C.c_int, C.c_size_t, _vp,
+                                                  C.c_size_t]),
     ("jpezy_ycc_chroma_size", C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("jpezy_ycc_component_size", C.c_int, [C.POINTER(FrameInfo), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("jpezy_fdct_quant_ycc_dev", C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int,
@@ -185,6 +198,16 @@ def scaled_size(W, H, scale):
     ws, hs = C.c_int(), C.c_int()
     _check(load_library().jpezy_scaled_size(int(W), int(H), int(scale), C.byref(ws), C.byref(hs)))
     return ws.value, hs.value
+
+
+def _rect(region):
+    x, y, w, h = (int(v) for v in region)
+    return Rect(x, y, w, h)
+
+
+def region_check(W, H, scale, region):
+    """raises JpezyError unless region = (x, y, w, h) lies inside a W x H file decoded at 1/scale, i.e. inside scaled_size(W, H, scale)"""
+    _check(load_library().jpezy_region_check(int(W), int(H), int(scale), C.byref(_rect(region))))
 
 
 def ycc_chroma_size(W, H):
@@ -697,6 +720,53 @@ class Context:
         stride = plane_stride if plane_stride is not None else Ws * Hs
         _check(load_library().jpezy_dequant_idct_scaled_dev(*head, n_frames, stride, d_r.data_ptr(), d_g.data_ptr(), d_b.data_ptr(), stream))
 
+    # ---- region decode (a window (x, y, w, h) of the picture at 1/scale: the scaled decode, sliced; include/jpezy_hip.h) ----
+    def decode_jpeg_region(self, data, region, scale=1, gray=False):
+        """.jpg bytes -> (FrameInfo, r, g, b) planes of w*h bytes: the window region = (x, y, w, h) of the picture at 1/scale.  The
+        FrameInfo keeps the file's own width and height."""
+        lib = load_library()
+        arr = np.frombuffer(bytes(data), dtype=np.uint8)
+        info, rect = FrameInfo(), _rect(region)
+        n = max(rect.w, 0) * max(rect.h, 0)
+        r, g, b = (np.empty(max(n, 1), dtype=np.uint8) for _ in range(3))
+        _check(lib.jpezy_decode_jpeg_region(self._h, _np_ptr(arr), arr.size, int(gray), int(scale), C.byref(rect), C.byref(info), _np_ptr(r),
+                                            _np_ptr(g), _np_ptr(b), n))
+        return info, r, g, b
+
+    def decode_jpeg_region_packed(self, data, region, scale=1, format=PIX_RGB24, gray=False):
+        """.jpg bytes -> (FrameInfo, uint8 array (h, w, C)) of interleaved pixels of the window; the fourth byte of a 32-bit format is 0xFF."""
+        lib = load_library()
+        nb = pixel_bytes(format)
+        arr = np.frombuffer(bytes(data), dtype=np.uint8)
+        info, rect = FrameInfo(), _rect(region)
+        img = np.empty((max(rect.h, 1), max(rect.w, 1), nb), dtype=np.uint8)
+        _check(lib.jpezy_decode_jpeg_region_packed(self._h, _np_ptr(arr), arr.size, int(gray), int(scale), C.byref(rect), C.byref(info),
+                                                   int(format), 0, _np_ptr(img), img.size))
+        return info, img
+
+    def dequant_idct_region_dev(self, d_coeffs, info, region, scale=1, d_r=None, d_g=None, d_b=None, gray=False, stream=None, n_frames=1,
+                                plane_stride=None, d_img=None, format=PIX_RGB24):
+        """the window region = (x, y, w, h) of the picture at 1/scale on device memory (torch tensors): the WHOLE frames' coefficients as
+        read_jpeg_gpu leaves them -> planes of w*h bytes (n_frames frames plane_stride apart, default w*h), or, with d_img, packed pixels
+        written into a uint8 tensor (h, w, C) or (N, h, w, C) whose strides give the row and frame strides"""
+        import torch
+        if stream is None:
+            stream = torch.cuda.current_stream(d_coeffs.device).cuda_stream
+        hs = (C.c_uint8 * 3)(*[max(1, info.H[i]) for i in range(3)])
+        vs = (C.c_uint8 * 3)(*[max(1, info.V[i]) for i in range(3)])
+        tq = (C.c_uint8 * 3)(*[info.Tq[i] for i in range(3)])
+        rect = _rect(region)
+        head = (self._h, d_coeffs.data_ptr(), C.byref(info.qt), info.ncomp, C.byref(hs), C.byref(vs), C.byref(tq), info.precision or 8,
+                info.width, info.height, int(gray), int(scale), C.byref(rect))
+        if d_img is not None:
+            n, H, W, row, frame = self._packed_layout(d_img, pixel_bytes(format), "dequant_idct_region_dev")
+            if (W, H) != (rect.w, rect.h):
+                raise JpezyError(f"dequant_idct_region_dev: d_img is {W} x {H}, the region is {rect.w} x {rect.h}")
+            _check(load_library().jpezy_dequant_idct_region_packed_dev(*head, int(format), row, frame, n, d_img.data_ptr(), stream))
+            return
+        stride = plane_stride if plane_stride is not None else rect.w * rect.h
+        _check(load_library().jpezy_dequant_idct_region_dev(*head, n_frames, stride, d_r.data_ptr(), d_g.data_ptr(), d_b.data_ptr(), stream))
+
 
 # ---- host serial tail / head ----
 def optimal_table(freq):
@@ -928,14 +998,18 @@ class Decoder:
         self.ctx = ctx
         self.pr = None
 
-    def decode(self, gray=False, scale=1):
-        """scale 2, 4 or 8: planes of scaled_size(width, height, scale) (Context.decode_jpeg_scaled); self.pr keeps the file's size"""
+    def decode(self, gray=False, scale=1, region=None):
+        """scale 2, 4 or 8: planes of scaled_size(width, height, scale) (Context.decode_jpeg_scaled); region = (x, y, w, h): planes of
+        w*h bytes, that window of the picture at 1/scale (Context.decode_jpeg_region); self.pr keeps the file's size"""
         try:
             with open(self.filename, "rb") as f:
                 data = f.read()
             ctx = self.ctx or default_context()
             # Huffman head, IDCT and colour conversion on the GPU
-            info, r, g, b = ctx.decode_jpeg(data, gray=gray) if scale == 1 else ctx.decode_jpeg_scaled(data, scale, gray=gray)
+            if region is not None:
+                info, r, g, b = ctx.decode_jpeg_region(data, region, scale=scale, gray=gray)
+            else:
+                info, r, g, b = ctx.decode_jpeg(data, gray=gray) if scale == 1 else ctx.decode_jpeg_scaled(data, scale, gray=gray)
         except (OSError, JpezyError):
             return None
         self.pr = info

@@ -1,6 +1,9 @@
-// jpezy_decode <input.(jpg | jpeg)> ( <output.ppm | [OPT: --gray]> | -v ) [--scale=N]
+// jpezy_decode <input.(jpg | jpeg)> ( <output.ppm | [OPT: --gray]> | -v ) [--scale=N] [--region=WxH+X+Y]
 // Same argv rules, transcript and exit codes as the reference's src/decoder/main.cpp.  --scale=N (N = 1, 2, 4, 8; this project's own
-// option, looked for in argv[3] / argv[4] the way --gray is) writes the picture at 1/N; any other N is the usage error.
+// option, looked for in argv[3] .. argv[5] the way --gray is) writes the picture at 1/N; any other N is the usage error.
+// --region=WxH+X+Y (this project's own option, X11 geometry order, looked for in the same places) writes the W x H window whose top-left
+// pixel is (X, Y) of the picture at 1/N (jpezy_decode_jpeg_region); a malformed geometry is the usage error, a well-formed one that does
+// not lie inside the picture prints the library's message and writes no file.
 // jpezy_decode --i420 <input.(jpg | jpeg)> <output.yuv>   (this project's own option) writes the file's own samples, without upsampling
 // or colour conversion, as raw planes: Y, then Cb, then Cr (full range: ffmpeg's yuvj420p) through jpezy_decode_jpeg_ycc.  Only a
 // 4:2:0 file (sampling 2x2, 1x1, 1x1) is such a picture: any other layout is refused with a message.
@@ -19,7 +22,8 @@ namespace {
 
 int disp_error()
 {
-    std::cerr << "Usage: jpezy_decode <input.(jpg | jpeg)> ( <output.ppm | [OPT: --gray]> | -v ) [OPT: --scale=(1 | 2 | 4 | 8)]" << std::endl;
+    std::cerr << "Usage: jpezy_decode <input.(jpg | jpeg)> ( <output.ppm | [OPT: --gray]> | -v ) [OPT: --scale=(1 | 2 | 4 | 8)] [OPT: --region=WxH+X+Y]"
+              << std::endl;
     return EXIT_FAILURE;
 }
 
@@ -29,9 +33,9 @@ bool has_ext(std::string_view s, std::string_view ext)
 }
 
 template <class CL, class T>
-int output(jpezy::decoder<T>& dec, const char* out, int scale)
+int output(jpezy::decoder<T>& dec, const char* out, int scale, const jpezy_rect* region)
 {
-    auto raw_op = dec.template decode<CL>(scale);
+    auto raw_op = region ? dec.template decode<CL>(scale, *region) : dec.template decode<CL>(scale);
     if (!raw_op) {
         std::cerr << "decode failed" << std::endl;
         return EXIT_FAILURE;
@@ -47,11 +51,11 @@ int output(jpezy::decoder<T>& dec, const char* out, int scale)
 }
 
 template <class T>
-int run(const char* in, const char* out, bool gray, int scale)
+int run(const char* in, const char* out, bool gray, int scale, const jpezy_rect* region)
 {
     jpezy::disp_logo();
     jpezy::decoder<T> dec(in);
-    return gray ? output<jpezy::GRAY_MODE>(dec, out, scale) : output<jpezy::COLOR_MODE>(dec, out, scale);
+    return gray ? output<jpezy::GRAY_MODE>(dec, out, scale, region) : output<jpezy::COLOR_MODE>(dec, out, scale, region);
 }
 
 // --scale=N inside an option: N when it is 1, 2, 4 or 8, 0 for anything else, 1 when the option is not there
@@ -62,6 +66,31 @@ int scale_of(std::string_view opt)
     if (at == std::string_view::npos) return 1;
     const std::string_view n = opt.substr(at + key.size());
     return n == "1" ? 1 : n == "2" ? 2 : n == "4" ? 4 : n == "8" ? 8 : 0;
+}
+
+// --region=WxH+X+Y inside an option: 1 and *r when it is well formed (decimal numbers, W, H >= 1), 0 when it is not, -1 when the option
+// is not there
+int region_of(std::string_view opt, jpezy_rect* r)
+{
+    constexpr std::string_view key = "--region=";
+    const auto at = opt.find(key);
+    if (at == std::string_view::npos) return -1;
+    std::string_view g = opt.substr(at + key.size());
+    int val[4];                                        // W, H, X, Y
+    constexpr char sep[4] = { 'x', '+', '+', '\0' };   // what follows each number
+    for (int k = 0; k < 4; ++k) {
+        std::size_t n = 0;
+        long v = 0;
+        while (n < g.size() && g[n] >= '0' && g[n] <= '9' && n < 9) v = v * 10 + (g[n++] - '0');
+        if (!n) return 0;
+        val[k] = static_cast<int>(v);
+        g.remove_prefix(n);
+        if (sep[k] ? (g.empty() || g[0] != sep[k]) : !g.empty()) return 0;
+        if (sep[k]) g.remove_prefix(1);
+    }
+    if (val[0] < 1 || val[1] < 1) return 0;
+    *r = jpezy_rect{ val[2], val[3], val[0], val[1] };
+    return 1;
 }
 
 int i420_main(const int argc, const char* argv[])
@@ -111,21 +140,31 @@ int main(const int argc, const char* argv[])
             return EXIT_FAILURE;
         }
     }
-    if (argc > 5 || argc < 3) return disp_error();
+    if (argc > 6 || argc < 3) return disp_error();
 
     const std::string_view sv0 = argv[1], sv1 = argv[2];
-    const std::string_view sv2 = argc > 3 ? std::string_view(argv[3]) : std::string_view();
-    const std::string_view sv3 = argc > 4 ? std::string_view(argv[4]) : std::string_view();
+    const std::string_view opt[3] = { argc > 3 ? std::string_view(argv[3]) : std::string_view(), argc > 4 ? std::string_view(argv[4]) : std::string_view(),
+                                      argc > 5 ? std::string_view(argv[5]) : std::string_view() };
 
     if (!((has_ext(sv0, "jpeg") || has_ext(sv0, "jpg")) && has_ext(sv1, "ppm"))) return disp_error();
 
-    const bool gray = sv2.find("--gray") != std::string_view::npos || sv3.find("--gray") != std::string_view::npos;
-    const bool verbose = sv2.find("-v") != std::string_view::npos || sv3.find("-v") != std::string_view::npos;
-    const int scale2 = scale_of(sv2), scale3 = scale_of(sv3);
-    if (!scale2 || !scale3) return disp_error();
-    const int scale = scale2 != 1 ? scale2 : scale3;
+    bool gray = false, verbose = false, has_region = false;
+    int scale = 1;
+    jpezy_rect region{};
+    for (const std::string_view sv : opt) {
+        gray = gray || sv.find("--gray") != std::string_view::npos;
+        verbose = verbose || sv.find("-v") != std::string_view::npos;
+        const int sc = scale_of(sv);
+        if (!sc) return disp_error();
+        if (scale == 1) scale = sc;
+        jpezy_rect r;
+        const int rg = region_of(sv, &r);
+        if (!rg) return disp_error();
+        if (rg > 0 && !has_region) { region = r; has_region = true; }
+    }
+    const jpezy_rect* rp = has_region ? &region : nullptr;
     try {
-        return verbose ? run<jpezy::Debug>(argv[1], argv[2], gray, scale) : run<jpezy::Release>(argv[1], argv[2], gray, scale);
+        return verbose ? run<jpezy::Debug>(argv[1], argv[2], gray, scale, rp) : run<jpezy::Release>(argv[1], argv[2], gray, scale, rp);
     } catch (const std::runtime_error& e) {
         std::cerr << e.what() << std::endl;
         return EXIT_FAILURE;

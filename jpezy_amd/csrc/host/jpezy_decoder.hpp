@@ -41,6 +41,24 @@ struct decoder {
     template <class MODE_TAG = COLOR_MODE>
     std::optional<std::array<std::vector<byte>, 3>> decode(int scale_denom = 1)
     {
+        return decode_impl<MODE_TAG>(scale_denom, nullptr);
+    }
+
+    // the window `region` of the picture at 1 / scale_denom (jpezy_decode_jpeg_region; include/jpezy_hip.h, REGION DECODE): planes of
+    // w * h, out_width x out_height = w x h; a region that does not lie inside the picture is refused with the library's message
+    template <class MODE_TAG = COLOR_MODE>
+    std::optional<std::array<std::vector<byte>, 3>> decode(int scale_denom, const jpezy_rect& region)
+    {
+        return decode_impl<MODE_TAG>(scale_denom, &region);
+    }
+
+    property pr;
+    std::size_t out_width = 0, out_height = 0;   // size of the decoded picture: the file's, the scaled size, or the region's
+
+private:
+    template <class MODE_TAG>
+    std::optional<std::array<std::vector<byte>, 3>> decode_impl(int scale_denom, const jpezy_rect* region)
+    {
         constexpr bool gray = std::is_same_v<MODE_TAG, GRAY_MODE>;
         raii_messenger mes("process started...");
         std::cout << '\n';
@@ -70,14 +88,24 @@ struct decoder {
         for (auto& v : rgb) v.resize(rgb_s);
         int ws = info.width, hs = info.height;
         if (jpezy_scaled_size(info.width, info.height, scale_denom, &ws, &hs) != JPEZY_OK) return {};
+        if (region) {
+            if (jpezy_region_check(info.width, info.height, scale_denom, region) != JPEZY_OK) {
+                std::cerr << jpezy_hip_last_error() << std::endl;
+                return {};
+            }
+            ws = region->w;
+            hs = region->h;
+        }
         out_width = static_cast<std::size_t>(ws);
         out_height = static_cast<std::size_t>(hs);
         jpezy_ctx* ctx = detail::device_context();
+        const auto plane = [&](int k) { return reinterpret_cast<std::uint8_t*>(rgb[static_cast<std::size_t>(k)].data()); };
         // decode_huffman + inverse_quantization + inverse_dct + upsampling + make_rgb (:504-578, 583-670) for all MCUs: one
         // C-ABI call; for jpezy_encode's own layout every stage runs on the device
-        const int rc = jpezy_decode_jpeg_scaled(ctx, reinterpret_cast<const std::uint8_t*>(file.data()), file.size(), gray, scale_denom, &info,
-                                                reinterpret_cast<std::uint8_t*>(rgb[0].data()), reinterpret_cast<std::uint8_t*>(rgb[1].data()),
-                                                reinterpret_cast<std::uint8_t*>(rgb[2].data()), rgb_s);
+        const int rc = region ? jpezy_decode_jpeg_region(ctx, reinterpret_cast<const std::uint8_t*>(file.data()), file.size(), gray, scale_denom,
+                                                         region, &info, plane(0), plane(1), plane(2), rgb_s)
+                              : jpezy_decode_jpeg_scaled(ctx, reinterpret_cast<const std::uint8_t*>(file.data()), file.size(), gray, scale_denom,
+                                                         &info, plane(0), plane(1), plane(2), rgb_s);
         if (rc == JPEZY_E_FORMAT || rc == JPEZY_E_NOSPACE) {
             std::cerr << "decode_mcu(): throw exception from " << jpezy_hip_last_error() << std::endl;   // :109-114
             return {};
@@ -89,10 +117,6 @@ struct decoder {
         return { std::move(rgb) };
     }
 
-    property pr;
-    std::size_t out_width = 0, out_height = 0;   // size of the decoded picture: the file's, or the scaled size
-
-private:
     void disp_info(const char* indent = "")   // ref :139-150 (spelling as in the reference)
     {
         using At = property::At;

@@ -55,26 +55,6 @@ int scaled_dev_core(jpezy_ctx* c, const int16_t* d_coeffs, const uint16_t qt[4][
     return JPEZY_OK;
 }
 
-struct Layout {
-    uint8_t hs[3], vs[3], tq[3];
-    explicit Layout(const jpezy_frame_info& info)
-    {
-        for (int k = 0; k < 3; ++k) { hs[k] = (uint8_t)info.H[k]; vs[k] = (uint8_t)info.V[k]; tq[k] = (uint8_t)info.Tq[k]; }
-    }
-};
-
-// the head of jpezy_decode_jpeg: the file's coefficients into c->out (GPU Huffman decoder, or the host's for what it declines)
-int read_coeffs(jpezy_ctx* c, const uint8_t* data, size_t len, jpezy_frame_info* info, const char* who)
-{
-    const size_t ncoef = (size_t)info->mcu_cols * info->mcu_rows * info->blocks_per_mcu * 64;
-    // sized from untrusted SOF0 fields: a block costs at least 2 bits of scan (1-bit DC code + 1-bit EOB code)
-    if (ncoef / 64 > 4 * len) return set_err(JPEZY_E_FORMAT, std::string(who) + ": scan too short for the declared dimensions");
-    HIP_TRY(hipSetDevice(c->device));
-    if (int rc = c->out.reserve(ncoef * sizeof(int16_t))) return rc;
-    const int rc = jpezy_read_jpeg_gpu(c, data, len, info, (int16_t*)c->out.p, ncoef);
-    return rc < 0 ? rc : JPEZY_OK;
-}
-
 }  // namespace
 
 extern "C" {

@@ -228,6 +228,31 @@ hipError_t launch_dequant_idct_scaled(const ScaledDecParams& p, hipStream_t stre
 // frames of p's layout one pair of launches takes (the launcher loops over larger batches); 0: a frame too large for one launch
 int scaled_frames_per_launch(const ScaledDecParams& p);
 
+// region-of-interest decode of any layout (jpezy_kernels_region.hip): a window of the picture at scale 8 / N, N = 1 << log2n = 8, 4, 2, 1,
+// from the MCUs that intersect it -- one launch, no intermediate in device memory
+struct RegionDecParams {
+    const int16_t* coeffs;    // the WHOLE frame's coefficients; only the blocks of MCUs that intersect the window are read
+    const int* qt;            // [3 comps][64] natural order
+    uint8_t* r;               // byte (0, 0) of the window's output: planes w * h, or with pix_bytes != 0 the channel bytes of its first pixel
+    uint8_t* g;
+    uint8_t* b;
+    int x, y, w, h;           // the window, in the coordinates of the picture at the requested scale
+    int ux0, uy0, ucols, urows;   // the MCUs that intersect it: columns [ux0, ux0 + ucols), rows [uy0, uy0 + urows)
+    int log2n, ncomp, gray;
+    int ch[3], cv[3], hmax, vmax, mcu_cols, mcu_rows, blocks_per_mcu;
+    int blk_start[3];         // first block of each component inside an MCU
+    int level;                // 128, or 2048 when SOF0 says precision != 8 (ref :654)
+    // n_frames frames of ONE layout, size and set of quantiser tables: frame f's coefficients at coeffs + f * blocks * 64, its output at
+    // r/g/b + f * plane_stride (any value that holds a window)
+    int n_frames = 1;
+    size_t plane_stride = 0;
+    // packed (interleaved) output as in ScaledDecParams: pix_bytes = 3 or 4 (0: planes, rows w apart); rows row_stride apart, frames
+    // plane_stride apart; byte 3 of a 32-bit pixel = 0xFF
+    int pix_bytes = 0;
+    unsigned row_stride = 0;
+};
+hipError_t launch_dequant_idct_region(const RegionDecParams& p, hipStream_t stream);
+
 #if defined(__HIPCC__)
 // The reference's sample int(sum / 4 + sl) (ref decoder/jpezy_decoder.hpp:667) as its x86-64 build executes it: cvttsd2si truncates
 // toward zero and gives INT_MIN for every value outside [-2^31, 2^31) and for NaN, where v_cvt_i32_f64 saturates (INT_MAX above the

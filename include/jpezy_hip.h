@@ -317,6 +317,57 @@ int jpezy_ctx_set_huffman_optimize(jpezy_ctx* ctx, int on);
 int jpezy_ctx_set_restart_interval(jpezy_ctx* ctx, int mcus);
 int jpezy_ctx_restart_interval(const jpezy_ctx* ctx);
 /*
+ * Quality and caller-supplied quantisation tables (opt-in; default: the Annex-K tables of jpezy.hpp:131-152, libjpeg's quality 50).
+ * The reference has no such setting, so the definition is this project's own: two tables of 64 entries in NATURAL order, luma and
+ * chroma, every entry in 1..255 (the file stays baseline, Pq = 0).  The coefficients are those of the reference's MCU loop
+ * (encoder/jpezy_encoder.hpp:58-67, :90-172) with quantization(cs) (:168-172) dividing by the caller's table instead of
+ * YQuantumTb / CQuantumTb: blk[i] /= qt[cs][i], C's truncating int division, every coefficient bit for bit -- both encode variants,
+ * every force_exact level, planar, packed and YCbCr input.  The file is the writer's for those coefficients with the caller's tables
+ * in the two DQT segments (jpezy_writer.hpp:46-58: luma as table 0, chroma as table 1, zig-zag order); optimised Huffman tables and
+ * restart intervals compose with it unchanged.
+ *
+ * jpezy_quality_tables (pure host function): libjpeg's mapping for an integer quality 1..100 -- s = q < 50 ? 5000 / q : 200 - 2 q,
+ * entry = clamp((base * s + 50) / 100, 1, 255) in integer arithmetic, base = the Annex-K tables.  Quality 50 is Annex K itself, 1 is
+ * 255 everywhere, 100 is 1 everywhere.  JPEZY_E_BADARG for a quality outside 1..100 or a null pointer.
+ *
+ * jpezy_ctx_set_quant_tables: the setting of every encode entry of the context -- jpezy_fdct_quant[_dev], jpezy_fdct_quant_packed_dev,
+ * jpezy_fdct_quant_ycc_dev, jpezy_encode_jpeg[_packed, _ycc], and the DQT segments of the header jpezy_write_jpeg_gpu[_batch, _dev]
+ * write (those three code the coefficients they are given, whatever tables produced them).  Both pointers null: back to Annex K.
+ * JPEZY_E_BADARG for one null pointer of two or a zero entry.  A context that never calls it, or that sets quality 50 or the Annex-K
+ * tables, writes every byte it wrote before and launches the same kernels.  The device constants are rewritten only when the
+ * setting changes, and then under the rule of the dequantiser tables: the call waits for the whole device (launches on any stream may
+ * still read them) and is refused with JPEZY_E_BADARG, the context unchanged, while the context's stream is being captured.
+ * jpezy_write_jpeg_gpu_dev stays asynchronous and capturable once the tables are in place (its first call with a new header uploads it).
+ * jpezy_ctx_set_quality is jpezy_quality_tables + jpezy_ctx_set_quant_tables; jpezy_ctx_quant_tables reads the setting back.
+ *
+ * jpezy_write_jpeg_qt: the host writer (jpezy_write_jpeg_rst) with the tables of the DQT segments; null tables give the bytes of
+ * jpezy_write_jpeg_rst.  The coefficients are written as they are.
+ *
+ * Value range: at Q = 1 an AC coefficient reaches 1020 (size 10) and a DC difference 2038 (category 11): inside the code tables, so no
+ * table makes 8-bit input JPEZY_E_FORMAT, and jpezy_jpeg_bound does not depend on the tables.  Small quantisers cost time: more
+ * coefficients are non-zero and more fall into the kernels' guard bands (DESIGN.md 4.10 has the figures).
+ * Out of scope: the multi-GPU handle (jpezy_multi_*, jpezy_encode_batch_multi) owns its contexts and always writes Annex-K tables;
+ * jpezy_write_jpeg[_opt, _rst, _batch] keep their signatures and bytes; no per-frame tables inside one batch call; no 16-bit tables;
+ * no chroma sampling other than 4:2:0.
+ */
+int jpezy_quality_tables(int quality, uint8_t luma[64], uint8_t chroma[64]);
+int jpezy_ctx_set_quant_tables(jpezy_ctx* ctx, const uint8_t luma[64], const uint8_t chroma[64]);
+int jpezy_ctx_set_quality(jpezy_ctx* ctx, int quality);
+int jpezy_ctx_quant_tables(const jpezy_ctx* ctx, uint8_t luma[64], uint8_t chroma[64]);
+long jpezy_write_jpeg_qt(const int16_t* coeffs, int W, int H, int gray, const char* comment, const uint8_t luma[64],
+                         const uint8_t chroma[64], int restart_interval, int optimize, uint8_t* out, size_t cap);
+/*
+ * Diagnostic (pure host function): what jpezy_ctx_set_quant_tables would build for these tables (null, null: Annex K), in place of
+ * quantization(cs) (encoder/jpezy_encoder.hpp:168-172) -- delta1[t][j] = the level-1 guard band of block column j of table t,
+ * dc_generic[t] = 1 when both create-time checks allow the DC of table t through the level-1 quantiser (0: the kernels read the
+ * DC from the exact table; one 0 sends both tables there), *qfrac_bits = the fraction width of encode variant 0's fixed point.
+ * Any output pointer may be null.  JPEZY_E_BADARG as for the setter, and for tables whose guard band would reach 0.25 (none can).
+ * Test hook beside jpezy_ctx_set_force_exact: jpezy_ctx_set_dc_table_lookup(ctx, 1) makes the context's encode kernels read the DC
+ * from that table even where the checks pass, so that the lookup has parity tests at every table.
+ */
+int jpezy_quant_tables_probe(const uint8_t luma[64], const uint8_t chroma[64], float delta1[2][8], int dc_generic[2], int* qfrac_bits);
+void jpezy_ctx_set_dc_table_lookup(jpezy_ctx* ctx, int on);
+/*
  * The symbol-counting kernel on its own, asynchronous on `stream`: d_hist[f][k][sym] (device memory, [n_frames][4][256], zeroed
  * here) = how often the coder emits symbol sym from table k (DHT order: 0 YDc, 1 CDc, 2 YAc, 3 CAc) for frame f.  A value outside
  * the code tables is counted as the clamped symbol the coder would emit (size 10, category 11).

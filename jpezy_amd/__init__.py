@@ -26,6 +26,8 @@ from .api import (  # noqa: F401
     load_library,
     mcu_grid,
     optimal_table,
+    quality_tables,
+    quant_tables_probe,
     read_jpeg,
     region_check,
     scaled_size,
@@ -38,5 +40,5 @@ from .api import (  # noqa: F401
 
 __all__ = [
     "Context", "Decoder", "Encoder", "FrameInfo", "JpezyError", "MultiEncoder", "PIX_BGR24", "PIX_BGRA32", "PIX_RGB24", "PIX_RGBA32", "Rect", "coeff_count", "encode_batch_multi", "library_path",
-    "load_library", "mcu_grid", "optimal_table", "read_jpeg", "region_check", "scaled_size", "shard_range", "write_jpeg", "write_jpeg_batch", "ycc_chroma_size", "ycc_component_size",
+    "load_library", "mcu_grid", "optimal_table", "quality_tables", "quant_tables_probe", "read_jpeg", "region_check", "scaled_size", "shard_range", "write_jpeg", "write_jpeg_batch", "ycc_chroma_size", "ycc_component_size",
 ]

@@ -91,6 +91,13 @@ ABI = [
     ("jpezy_write_jpeg_rst", C.c_long, [_vp, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int, C.c_int, _vp, C.c_size_t]),
     ("jpezy_ctx_set_restart_interval", C.c_int, [_vp, C.c_int]),
     ("jpezy_ctx_restart_interval", C.c_int, [_vp]),
+    ("jpezy_quality_tables", C.c_int, [C.c_int, _vp, _vp]),
+    ("jpezy_ctx_set_quant_tables", C.c_int, [_vp, _vp, _vp]),
+    ("jpezy_ctx_set_quality", C.c_int, [_vp, C.c_int]),
+    ("jpezy_ctx_quant_tables", C.c_int, [_vp, _vp, _vp]),
+    ("jpezy_write_jpeg_qt", C.c_long, [_vp, C.c_int, C.c_int, C.c_int, C.c_char_p, _vp, _vp, C.c_int, C.c_int, _vp, C.c_size_t]),
+    ("jpezy_quant_tables_probe", C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(C.c_int)]),
+    ("jpezy_ctx_set_dc_table_lookup", None, [_vp, C.c_int]),
     ("jpezy_encode_jpeg", C.c_long, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_char_p, _vp, C.c_size_t]),
     ("jpezy_shard_range", None, [C.c_long, C.c_int, C.c_int, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
     ("jpezy_encode_batch_multi", C.c_int, [C.POINTER(C.c_int), C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p,
@@ -228,6 +235,31 @@ def _np_ptr(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def _table(t, who):
+    """one quantisation table: 64 entries, natural order, as a contiguous uint8 array (values outside 0..255 are refused here)"""
+    a = np.asarray(t)
+    if a.size != 64 or a.min() < 0 or a.max() > 255:
+        raise JpezyError(f"{who}: a quantisation table is 64 entries in 0..255")
+    return np.ascontiguousarray(a.reshape(64), dtype=np.uint8)
+
+
+def quality_tables(quality):
+    """(luma, chroma): the 64-entry tables (natural order, uint8) of libjpeg's quality 1..100 over the Annex-K tables; 50 is Annex K"""
+    luma, chroma = np.zeros(64, np.uint8), np.zeros(64, np.uint8)
+    _check(load_library().jpezy_quality_tables(int(quality), _np_ptr(luma), _np_ptr(chroma)))
+    return luma, chroma
+
+
+def quant_tables_probe(luma=None, chroma=None):
+    """diagnostic, no GPU: (delta1 float32 [2, 8], dc_generic [2], qfrac_bits) -- what Context.set_quant_tables would build"""
+    pl = None if luma is None else _table(luma, "quant_tables_probe")
+    pc = None if chroma is None else _table(chroma, "quant_tables_probe")
+    d1, dcg, bits = np.zeros((2, 8), np.float32), (C.c_int * 2)(), C.c_int()
+    _check(load_library().jpezy_quant_tables_probe(None if pl is None else _np_ptr(pl), None if pc is None else _np_ptr(pc), _np_ptr(d1), dcg,
+                                                   C.byref(bits)))
+    return d1, [dcg[0], dcg[1]], bits.value
+
+
 ANNEX_K_INFO = None
 
 
@@ -287,6 +319,32 @@ class Context:
 
     def restart_interval(self):
         return _check(load_library().jpezy_ctx_restart_interval(self._h))
+
+    def set_quant_tables(self, luma, chroma):
+        """the quantisation tables (64 entries each, natural order, 1..255) of every encode entry point of this context and of the DQT
+        segments write_jpeg_gpu[_dev] write; (None, None): back to Annex K.  Waits for the device when the setting changes; refused
+        while the context's stream is being captured."""
+        pl = None if luma is None else _table(luma, "set_quant_tables")
+        pc = None if chroma is None else _table(chroma, "set_quant_tables")
+        _check(load_library().jpezy_ctx_set_quant_tables(self._h, None if pl is None else _np_ptr(pl), None if pc is None else _np_ptr(pc)))
+
+    def set_quality(self, quality):
+        """set_quant_tables(*quality_tables(quality)): libjpeg's quality 1..100; 50 is the default"""
+        _check(load_library().jpezy_ctx_set_quality(self._h, int(quality)))
+
+    def quant_tables(self):
+        """(luma, chroma) the context encodes with"""
+        luma, chroma = np.zeros(64, np.uint8), np.zeros(64, np.uint8)
+        _check(load_library().jpezy_ctx_quant_tables(self._h, _np_ptr(luma), _np_ptr(chroma)))
+        return luma, chroma
+
+    def set_dc_table_lookup(self, on):
+        """test hook: the encode kernels read the quantised DC from the exact table even where the level-1 quantiser may take it"""
+        load_library().jpezy_ctx_set_dc_table_lookup(self._h, int(on))
+
+    def stream(self):
+        """the context's own hipStream_t as an integer"""
+        return load_library().jpezy_ctx_stream(self._h)
 
     def set_host_chunk_bytes(self, n):
         """bytes of input per chunk of the streaming host-buffer entry points (default 4 MiB)"""
@@ -779,10 +837,11 @@ def optimal_table(freq):
     return bits, vals[:n].copy()
 
 
-def write_jpeg(coeffs, W, H, gray=False, comment=None, optimize=False, restart_interval=0):
+def write_jpeg(coeffs, W, H, gray=False, comment=None, optimize=False, restart_interval=0, quant_tables=None):
     """zig-zag int16 coefficients -> the .jpg bytes jpezy_encode writes (header + Huffman + EOI); optimize: with the frame's own
     optimal Huffman tables instead of Annex K (same coefficients, smaller file); restart_interval: MCUs per restart interval
-    (DRI segment, RSTn markers, predictors reset), 0 for none."""
+    (DRI segment, RSTn markers, predictors reset), 0 for none; quant_tables = (luma, chroma): the tables the DQT segments state
+    (64 entries each, natural order, 1..255) instead of Annex K -- the coefficients are written as they are."""
     lib = load_library()
     coeffs = np.ascontiguousarray(coeffs, dtype=np.int16)
     if coeffs.size != lib.jpezy_coeff_count(W, H, int(gray)):
@@ -791,6 +850,11 @@ def write_jpeg(coeffs, W, H, gray=False, comment=None, optimize=False, restart_i
         comment = b"Encoded by JPEZY" if gray else b"Encoded by jpezy"   # ref encode_io.hpp:149,181
     cap = lib.jpezy_jpeg_bound(W, H)
     buf = np.empty(cap, dtype=np.uint8)
+    if quant_tables is not None:
+        luma, chroma = (_table(t, "write_jpeg") for t in quant_tables)
+        n = _check(lib.jpezy_write_jpeg_qt(_np_ptr(coeffs), W, H, int(gray), comment, _np_ptr(luma), _np_ptr(chroma), int(restart_interval),
+                                           int(bool(optimize)), _np_ptr(buf), cap))
+        return buf[:n].tobytes()
     if restart_interval != 0:
         n = _check(lib.jpezy_write_jpeg_rst(_np_ptr(coeffs), W, H, int(gray), comment, int(restart_interval), int(bool(optimize)),
                                             _np_ptr(buf), cap))

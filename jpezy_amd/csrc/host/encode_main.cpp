@@ -1,14 +1,16 @@
-// jpezy_encode <input.ppm> ( <output.(jpeg | jpg) [OPT: --gray] [OPT: --optimize] [OPT: --restart=N]> | <output.ppm> | --debug )
+// jpezy_encode <input.ppm> ( <output.(jpeg | jpg) [OPT: --gray] [OPT: --optimize] [OPT: --restart=N] [OPT: --quality=N]> | <output.ppm> | --debug )
 // Same argv rules, transcript and exit codes as the reference's src/encoder/main.cpp; the codec underneath is
 // the MI355X path (jpezy_encoder.hpp).
 // Extension (not in the reference):  --optimize (single-file mode only, either side of --gray) writes the file with its own optimal
 // Huffman tables (jpezy_ctx_set_huffman_optimize): same pixels, fewer bytes.
 // Extension (not in the reference):  --restart=N (single-file mode only, one token, anywhere behind the output name) writes restart
 // intervals of N MCUs, 0..65535 (jpezy_ctx_set_restart_interval); a malformed N is a usage error.
+// Extension (not in the reference):  --quality=N (single-file mode and --i420, one token, anywhere behind the output name) encodes with
+// libjpeg's quality N, 1..100 (jpezy_ctx_set_quality; 50 is the default); a malformed or out-of-range N is a usage error.
 // Extension (not in the reference):  jpezy_encode --gpus N [--gray] <in1.ppm> <out1.jpg> [<in2.ppm> <out2.jpg> ...]
 // encodes a list of files on up to N GPUs of this node through jpezy_encode_batch_multi: runs of consecutive inputs of one size
 // form a batch, a batch is sharded over the GPUs frame by frame.
-// Extension (not in the reference):  jpezy_encode --i420=WxH <in.yuv> <out.jpg> [--gray] [--optimize] [--restart=N]
+// Extension (not in the reference):  jpezy_encode --i420=WxH <in.yuv> <out.jpg> [--gray] [--optimize] [--restart=N] [--quality=N]
 // encodes a raw planar YCbCr 4:2:0 file -- the W x H Y plane, then the ceil(W/2) x ceil(H/2) Cb and Cr planes, full range (ffmpeg's
 // yuvj420p) -- through jpezy_encode_jpeg_ycc: the samples go into the file as they are, without a colour conversion.
 #include <cstdlib>
@@ -118,11 +120,19 @@ int parse_restart(std::string_view tok)
     return parse_u16(tok);
 }
 
-// jpezy_encode --i420=WxH in.yuv out.jpg [--gray] [--optimize] [--restart=N]
+// "--quality=N" with N a decimal number in 1..100: N; anything else that starts like it: -1
+int parse_quality(std::string_view tok)
+{
+    tok.remove_prefix(std::string_view("--quality=").size());
+    const int n = parse_u16(tok);
+    return n >= 1 && n <= 100 ? n : -1;
+}
+
+// jpezy_encode --i420=WxH in.yuv out.jpg [--gray] [--optimize] [--restart=N] [--quality=N]
 int i420_main(const int argc, const char* argv[])
 {
     const auto usage = [] {
-        std::cerr << "Usage: jpezy_encode --i420=WxH <input.yuv> <output.(jpeg | jpg)> [OPT: --gray] [OPT: --optimize] [OPT: --restart=N]" << std::endl;
+        std::cerr << "Usage: jpezy_encode --i420=WxH <input.yuv> <output.(jpeg | jpg)> [OPT: --gray] [OPT: --optimize] [OPT: --restart=N] [OPT: --quality=N]" << std::endl;
         return EXIT_FAILURE;
     };
     std::string_view dims = argv[1];
@@ -132,12 +142,13 @@ int i420_main(const int argc, const char* argv[])
     const int W = parse_u16(dims.substr(0, x)), H = parse_u16(dims.substr(x + 1));
     if (W <= 0 || H <= 0) return usage();
     bool gray = false, optimize = false;
-    int restart = 0;
+    int restart = 0, quality = 0;
     for (int i = 4; i < argc; ++i) {
         const std::string_view o = argv[i];
         if (o == "--gray") gray = true;
         else if (o == "--optimize") optimize = true;
         else if (o.rfind("--restart=", 0) == 0 && (restart = parse_restart(o)) >= 0) continue;
+        else if (o.rfind("--quality=", 0) == 0 && (quality = parse_quality(o)) >= 1) continue;
         else return usage();
     }
     jpezy::disp_logo();
@@ -155,6 +166,7 @@ int i420_main(const int argc, const char* argv[])
         jpezy_ctx* ctx = jpezy::detail::device_context();
         if (optimize && jpezy_ctx_set_huffman_optimize(ctx, 1) != JPEZY_OK) throw std::runtime_error(std::string("jpezy_ctx_set_huffman_optimize: ") + jpezy_hip_last_error());
         if (restart && jpezy_ctx_set_restart_interval(ctx, restart) != JPEZY_OK) throw std::runtime_error(std::string("jpezy_ctx_set_restart_interval: ") + jpezy_hip_last_error());
+        if (quality && jpezy_ctx_set_quality(ctx, quality) != JPEZY_OK) throw std::runtime_error(std::string("jpezy_ctx_set_quality: ") + jpezy_hip_last_error());
         std::vector<std::uint8_t> jpg(jpezy_jpeg_bound(W, H));
         const long n = jpezy_encode_jpeg_ycc(ctx, buf.data(), 0, buf.data() + ny, buf.data() + ny + nc, 0, 1, W, H, gray ? 1 : 0,
                                              gray ? "Encoded by JPEZY" : "Encoded by jpezy", jpg.data(), jpg.size());
@@ -177,13 +189,20 @@ int main(const int argc_in, const char* argv_in[])
     if (argc_in >= 3 && std::string_view(argv_in[1]) == "--gpus") return batch_main(argc_in, argv_in);
     if (argc_in >= 2 && std::string_view(argv_in[1]).rfind("--i420=", 0) == 0) return i420_main(argc_in, argv_in);
     if (argc_in < 3) return disp_error();
-    // the one --restart=N token is taken out; what is left is read as before
+    // the one --restart=N and the one --quality=N token are taken out; what is left is read as before
     std::vector<const char*> args(argv_in, argv_in + argc_in);
-    int restart = 0;
+    int restart = 0, quality = 0;
     for (std::size_t i = 3; i < args.size(); ++i)
         if (std::string_view(args[i]).rfind("--restart=", 0) == 0) {
             restart = parse_restart(args[i]);
             if (restart < 0) return disp_error();
+            args.erase(args.begin() + static_cast<std::ptrdiff_t>(i));
+            break;
+        }
+    for (std::size_t i = 3; i < args.size(); ++i)
+        if (std::string_view(args[i]).rfind("--quality=", 0) == 0) {
+            quality = parse_quality(args[i]);
+            if (quality < 0) return disp_error();
             args.erase(args.begin() + static_cast<std::ptrdiff_t>(i));
             break;
         }
@@ -226,6 +245,8 @@ int main(const int argc_in, const char* argv_in[])
                 throw std::runtime_error(std::string("jpezy_ctx_set_huffman_optimize: ") + jpezy_hip_last_error());
             if (restart && jpezy_ctx_set_restart_interval(jpezy::detail::device_context(), restart) != JPEZY_OK)
                 throw std::runtime_error(std::string("jpezy_ctx_set_restart_interval: ") + jpezy_hip_last_error());
+            if (quality && jpezy_ctx_set_quality(jpezy::detail::device_context(), quality) != JPEZY_OK)
+                throw std::runtime_error(std::string("jpezy_ctx_set_quality: ") + jpezy_hip_last_error());
             std::ofstream ofs(argv[2], std::ios::binary);
             if (m2 == Mode::GRAY) ofs << (pnm | jpezy::to_jpeg(argv[2]) | jpezy::gray_scale);
             else ofs << (pnm | jpezy::to_jpeg(argv[2]));

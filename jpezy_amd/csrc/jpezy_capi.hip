@@ -30,6 +30,114 @@ size_t jpezy_coeff_count(int W, int H, int gray)
     return (size_t)jpezy_mcu_cols(W) * (size_t)jpezy_mcu_rows(H) * (gray ? 4 : 6) * 64;
 }
 
+// Every quantiser-dependent device constant of the encode kernels as a function of the two tables (natural order, entries 1..255):
+// F32Column::ks / delta1 / th, DeviceTables::qt / qinv / qscale / qfrac_bits / rq_dc / dcq, and dc_formula's constants dc_rq / dc_bias --
+// zero when one of the two checks against dcq fails for these tables, which makes the launcher take the !DCG instance and the table.
+// jpezy_ctx_create calls it with the Annex-K tables, jpezy_ctx_set_quant_tables with the caller's.  false (and *why): a level-1 guard
+// band that would reach 0.25.
+static bool build_encode_tables(const int qt[2][64], DeviceTables& h, float dc_rq[2], float dc_bias[2], std::string* why)
+{
+    std::memset(&h, 0, sizeof h);
+    const double S = JPEZY_INV_SQRT2;
+    int pos_of_row[8];                 // inverse of kPairRow: where the f32 kernel keeps coefficient row i of a block column
+    for (int pp = 0; pp < 8; ++pp) pos_of_row[kPairRow[pp]] = pp;
+    int qmin = 255;
+    for (int t = 0; t < 2; ++t)
+        for (int k = 0; k < 64; ++k) qmin = std::min(qmin, qt[t][k]);
+    h.qfrac_bits = qfrac_bits(qmin);   // encode variant 0: the widest fixed point whose quotients stay inside int32 (jpezy_device.h)
+    for (int t = 0; t < 2; ++t) {
+        for (int j = 0; j < 8; ++j)
+            for (int i = 0; i < 8; ++i) {
+                const double cu = j ? 1.0 : S, cv = i ? 1.0 : S;
+                h.qscale[t][j][i] = cu * cv / (4.0 * qt[t][i * 8 + j]) * (double)(1 << h.qfrac_bits);
+            }
+        h.rq_dc[t] = 1.0 / qt[t][0];
+        for (int k = 0; k < 64; ++k) {
+            h.qt[t][k] = qt[t][k];
+            h.qinv[t][k] = 1.0 / qt[t][k];
+        }
+        for (int j = 0; j < 8; ++j)
+            for (int i = 0; i < 8; ++i) {
+                const double cu = j ? 1.0 : S, cv = i ? 1.0 : S;
+                // the f32 kernel's 8-point transform leaves output 4 without its factor cos(pi/4); it is applied here
+                const double k4 = 0x1.6a09e667f3bcdp-1;      // cos(pi/4), correctly rounded
+                h.f32col[t][j].ks[pos_of_row[i]] = (float)(cu * cv / (4.0 * qt[t][i * 8 + j]) * (i == 4 ? k4 : 1.0) * (j == 4 ? k4 : 1.0));
+            }
+    }
+    for (int t = 0; t < 2; ++t)
+        for (int sum = -8192; sum <= 8192; ++sum) {
+            const double cu = S, cv = S;
+            const int dct = (int)((double)sum * cu * cv / 4);          // int(sum * cu * cv / 4), no contraction (build flag)
+            h.dcq[t][sum + 8192] = (int16_t)(dct / qt[t][0]);      // |.| <= 1024 / Q_t[0]
+        }
+    // the table-free form of the same value (f32::dc_formula, persistent encode kernels): usable only if it reproduces the table for
+    // every sum with these constants -- evaluated here with the kernel's own FP32 operations
+    for (int t = 0; t < 2; ++t) {
+        const float rq = 1.0f / (float)qt[t][0], bias = 0.5f / (float)qt[t][0];
+        bool ok = true;
+        for (int sum = -8192; sum <= 8192 && ok; ++sum) {
+            const float d = std::trunc(std::fmaf(std::fabs((float)sum), 0.125f, -0.125f));
+            const float q = std::trunc(std::fmaf(d, rq, bias));
+            ok = (int)std::copysign(q, (float)sum) == (int)h.dcq[t][sum + 8192];
+        }
+        dc_rq[t] = ok ? rq : 0.f;
+        dc_bias[t] = ok ? bias : 0.f;
+    }
+    {
+        // f32 kernel, level 1: |t_fp32 - t| <= gamma_13 * S_i * S_j * 128 * ks + 2^-23 * |t|max, S_u = sum_x |cos_u(x)|
+        // (13 roundings at most on any input->output path of the two butterfly passes; ks rounded to FP32 and the
+        // fused product-and-bias fma(F, ks, delta1) rounded once: 2 * 2^-24 relative to |t| + delta1 <= 128 * S_i * S_j * ks
+        // -- the few 1e-12 that delta1 adds to that rounding disappear in the 25 % margin).  tests/test_f32_error_bound.py re-derives it.
+        static const double kCos[64] = JPEZY_COS_INIT;
+        double S1[8];
+        for (int u = 0; u < 8; ++u) {
+            S1[u] = 0;
+            for (int x = 0; x < 8; ++x) S1[u] += std::fabs(kCos[u * 8 + x]);
+        }
+        for (int t = 0; t < 2; ++t)
+            for (int j = 0; j < 8; ++j) {
+                double worst = 0;
+                for (int i = 0; i < 8; ++i) {
+                    if (i == 0 && j == 0) continue;            // DC: an exact integer sum, no transform error (checked for every sum below)
+                    const double cu = j ? 1.0 : S, cv = i ? 1.0 : S;
+                    const double ks = cu * cv / (4.0 * qt[t][i * 8 + j]);
+                    const double amp = 128.0 * S1[i] * S1[j] * ks;
+                    const double bound = 13.0 * 0x1p-24 * amp + 0x1p-23 * amp;
+                    if (bound > worst) worst = bound;
+                }
+                const float d1 = (float)(1.25 * worst);
+                // The kernel tells "near an integer other than zero" from "in the band around zero" by |t'| > 0.5: that needs
+                // 2 delta1 well below 0.5.  delta1 peaks at Q = 1, at 1.15e-3 (column 1); no table of entries >= 1 comes near 0.25.
+                if (!(d1 < 0.25f)) {
+                    if (why) *why = "quantisation tables: level-1 guard band of " + std::to_string(d1) + " reaches 0.25";
+                    return false;
+                }
+                h.f32col[t][j].delta1[0] = h.f32col[t][j].delta1[1] = d1;
+                h.f32col[t][j].th = d1 + d1;               // exact: a doubling
+            }
+        // The one-quad kernel sends the DC through that quantiser too (f32::quant_block_column, DCG): t' = fma(sum, ks, delta1), flagged
+        // <=> fract(t') < 2 delta1 -> dc_formula (verified above), else (int)t'.  The same FP32 operations for every sum against the table;
+        // a set of constants for which they do not reproduce it keeps the table lookup (dc_rq = 0).
+        for (int t = 0; t < 2; ++t) {
+            const F32Column& col = h.f32col[t][0];
+            bool ok = true;
+            for (int sum = -8192; sum <= 8192 && ok; ++sum) {
+                const float tp = std::fmaf((float)sum, col.ks[0], col.delta1[0]);
+                const bool flagged = tp - std::floor(tp) < col.th;         // v_fract_f32
+                ok = flagged || (int)tp == (int)h.dcq[t][sum + 8192];
+            }
+            if (!ok) dc_rq[t] = dc_bias[t] = 0.f;
+        }
+    }
+    for (int j = 0; j < 8; ++j)
+        for (int hh = 0; hh < 2; ++hh) {
+            uint32_t w = 0;
+            for (int k = 0; k < 4; ++k) w |= (uint32_t)(2 * kZzInv[kPairRow[4 * hh + k] * 8 + j]) << (8 * k);
+            for (int t = 0; t < 2; ++t) (hh ? h.f32col[t][j].zz_hi : h.f32col[t][j].zz_lo) = w;
+        }
+    return true;
+}
+
 jpezy_ctx* jpezy_ctx_create(int device)
 {
     int n = 0;
@@ -57,95 +165,16 @@ jpezy_ctx* jpezy_ctx_create(int device)
         if (k >= 0 && k <= 3) c->variant = k;
     }
 #endif
-    std::vector<DeviceTables> hbuf(1); // 33 KB: off the stack, and private to this call (contexts may be created concurrently)
+    std::vector<DeviceTables> hbuf(1); // 66 KB: off the stack, and private to this call (contexts may be created concurrently)
     DeviceTables& h = hbuf[0];
-    const double S = JPEZY_INV_SQRT2;
-    int pos_of_row[8];                 // inverse of kPairRow: where the f32 kernel keeps coefficient row i of a block column
-    for (int pp = 0; pp < 8; ++pp) pos_of_row[kPairRow[pp]] = pp;
-    for (int t = 0; t < 2; ++t) {
-        for (int j = 0; j < 8; ++j)
-            for (int i = 0; i < 8; ++i) {
-                const double cu = j ? 1.0 : S, cv = i ? 1.0 : S;
-                h.qscale[t][j][i] = cu * cv / (4.0 * kQt[t][i * 8 + j]) * (double)(1 << QFRAC_BITS);
-            }
-        h.rq_dc[t] = 1.0 / kQt[t][0];
-        for (int k = 0; k < 64; ++k) {
-            h.qt[t][k] = kQt[t][k];
-            h.qinv[t][k] = 1.0 / kQt[t][k];
-        }
-        for (int j = 0; j < 8; ++j)
-            for (int i = 0; i < 8; ++i) {
-                const double cu = j ? 1.0 : S, cv = i ? 1.0 : S;
-                // the f32 kernel's 8-point transform leaves output 4 without its factor cos(pi/4); it is applied here
-                const double k4 = 0x1.6a09e667f3bcdp-1;      // cos(pi/4), correctly rounded
-                h.f32col[t][j].ks[pos_of_row[i]] = (float)(cu * cv / (4.0 * kQt[t][i * 8 + j]) * (i == 4 ? k4 : 1.0) * (j == 4 ? k4 : 1.0));
-            }
+    std::string why;
+    if (!build_encode_tables(kQt, h, c->dc_rq, c->dc_bias, &why)) {     // (cannot happen: the Annex-K tables pass every check)
+        set_err(JPEZY_E_BADARG, why);
+        delete c;
+        return nullptr;
     }
     for (int t = 0; t < 2; ++t)
-        for (int sum = -8192; sum <= 8192; ++sum) {
-            const double cu = S, cv = S;
-            const int dct = (int)((double)sum * cu * cv / 4);          // int(sum * cu * cv / 4), no contraction (build flag)
-            h.dcq[t][sum + 8192] = (signed char)(dct / kQt[t][0]);
-        }
-    // the table-free form of the same value (f32::dc_formula, persistent encode kernels): usable only if it reproduces the table for
-    // every sum with these constants -- evaluated here with the kernel's own FP32 operations
-    for (int t = 0; t < 2; ++t) {
-        const float rq = 1.0f / (float)kQt[t][0], bias = 0.5f / (float)kQt[t][0];
-        bool ok = true;
-        for (int sum = -8192; sum <= 8192 && ok; ++sum) {
-            const float d = std::trunc(std::fmaf(std::fabs((float)sum), 0.125f, -0.125f));
-            const float q = std::trunc(std::fmaf(d, rq, bias));
-            ok = (int)std::copysign(q, (float)sum) == (int)h.dcq[t][sum + 8192];
-        }
-        c->dc_rq[t] = ok ? rq : 0.f;
-        c->dc_bias[t] = ok ? bias : 0.f;
-    }
-    {
-        // f32 kernel, level 1: |t_fp32 - t| <= gamma_13 * S_i * S_j * 128 * ks + 2^-23 * |t|max, S_u = sum_x |cos_u(x)|
-        // (13 roundings at most on any input->output path of the two butterfly passes; ks rounded to FP32 and the
-        // fused product-and-bias fma(F, ks, delta1) rounded once: 2 * 2^-24 relative to |t| + delta1 <= 128 * S_i * S_j * ks
-        // -- the few 1e-12 that delta1 adds to that rounding disappear in the 25 % margin).  tests/test_f32_error_bound.py re-derives it.
-        static const double kCos[64] = JPEZY_COS_INIT;
-        double S1[8];
-        for (int u = 0; u < 8; ++u) {
-            S1[u] = 0;
-            for (int x = 0; x < 8; ++x) S1[u] += std::fabs(kCos[u * 8 + x]);
-        }
-        for (int t = 0; t < 2; ++t)
-            for (int j = 0; j < 8; ++j) {
-                double worst = 0;
-                for (int i = 0; i < 8; ++i) {
-                    if (i == 0 && j == 0) continue;            // DC: an exact integer sum, no transform error (checked for every sum below)
-                    const double cu = j ? 1.0 : S, cv = i ? 1.0 : S;
-                    const double ks = cu * cv / (4.0 * kQt[t][i * 8 + j]);
-                    const double amp = 128.0 * S1[i] * S1[j] * ks;
-                    const double bound = 13.0 * 0x1p-24 * amp + 0x1p-23 * amp;
-                    if (bound > worst) worst = bound;
-                }
-                const float d1 = (float)(1.25 * worst);
-                h.f32col[t][j].delta1[0] = h.f32col[t][j].delta1[1] = d1;
-                h.f32col[t][j].th = d1 + d1;               // exact: a doubling
-            }
-        // The one-quad kernel sends the DC through that quantiser too (f32::quant_block_column, DCG): t' = fma(sum, ks, delta1), flagged
-        // <=> fract(t') < 2 delta1 -> dc_formula (verified above), else (int)t'.  The same FP32 operations for every sum against the table;
-        // a set of constants for which they do not reproduce it keeps the table lookup (dc_rq = 0).
-        for (int t = 0; t < 2; ++t) {
-            const F32Column& col = h.f32col[t][0];
-            bool ok = true;
-            for (int sum = -8192; sum <= 8192 && ok; ++sum) {
-                const float tp = std::fmaf((float)sum, col.ks[0], col.delta1[0]);
-                const bool flagged = tp - std::floor(tp) < col.th;         // v_fract_f32
-                ok = flagged || (int)tp == (int)h.dcq[t][sum + 8192];
-            }
-            if (!ok) c->dc_rq[t] = c->dc_bias[t] = 0.f;
-        }
-    }
-    for (int j = 0; j < 8; ++j)
-        for (int hh = 0; hh < 2; ++hh) {
-            uint32_t w = 0;
-            for (int k = 0; k < 4; ++k) w |= (uint32_t)(2 * kZzInv[kPairRow[4 * hh + k] * 8 + j]) << (8 * k);
-            for (int t = 0; t < 2; ++t) (hh ? h.f32col[t][j].zz_hi : h.f32col[t][j].zz_lo) = w;
-        }
+        for (int k = 0; k < 64; ++k) c->qt[t][k] = (uint8_t)kQt[t][k];
     bool ok = hipSetDevice(device) == hipSuccess;
     ok = ok && c->stream.create() == hipSuccess;
     ok = ok && c->d_tab.try_reserve(sizeof(DeviceTables)) == hipSuccess;
@@ -182,6 +211,98 @@ void* jpezy_ctx_stream(const jpezy_ctx* c) { return c ? (void*)(hipStream_t)c->s
 void jpezy_ctx_set_force_exact(jpezy_ctx* c, int on)
 {
     if (c) c->force_exact = on < 0 ? 0 : on > 3 ? 3 : on;
+}
+
+void jpezy_ctx_set_dc_table_lookup(jpezy_ctx* c, int on)
+{
+    if (c) c->dc_table_lookup = on != 0;
+}
+
+int jpezy_quality_tables(int quality, uint8_t luma[64], uint8_t chroma[64])
+{
+    if (!luma || !chroma) return set_err(JPEZY_E_BADARG, "quality_tables: null pointer");
+    if (quality < 1 || quality > 100) return set_err(JPEZY_E_BADARG, "quality must be in 1..100");
+    const int s = quality < 50 ? 5000 / quality : 200 - 2 * quality;        // libjpeg's jpeg_quality_scaling
+    for (int t = 0; t < 2; ++t)
+        for (int k = 0; k < 64; ++k) {
+            const int v = (kQt[t][k] * s + 50) / 100;                        // jpeg_add_quant_table, baseline: clamped to 1..255
+            (t ? chroma : luma)[k] = (uint8_t)(v < 1 ? 1 : v > 255 ? 255 : v);
+        }
+    return JPEZY_OK;
+}
+
+// both null: Annex K; one null or a zero entry: JPEZY_E_BADARG
+static int tables_from_args(const char* who, const uint8_t* luma, const uint8_t* chroma, int qt[2][64])
+{
+    if ((luma == nullptr) != (chroma == nullptr)) return set_err(JPEZY_E_BADARG, std::string(who) + ": one of the two tables is null (both null: Annex K)");
+    for (int t = 0; t < 2; ++t)
+        for (int k = 0; k < 64; ++k) {
+            qt[t][k] = luma ? (t ? chroma : luma)[k] : kQt[t][k];
+            if (qt[t][k] < 1) return set_err(JPEZY_E_BADARG, std::string(who) + ": a quantisation table entry is zero (1..255)");
+        }
+    return JPEZY_OK;
+}
+
+int jpezy_quant_tables_probe(const uint8_t luma[64], const uint8_t chroma[64], float delta1[2][8], int dc_generic[2], int* qfrac)
+try {
+    int qt[2][64];
+    if (int rc = tables_from_args("quant_tables_probe", luma, chroma, qt)) return rc;
+    std::vector<DeviceTables> hbuf(1);
+    float rq[2], bias[2];
+    std::string why;
+    if (!build_encode_tables(qt, hbuf[0], rq, bias, &why)) return set_err(JPEZY_E_BADARG, why);
+    for (int t = 0; t < 2; ++t) {
+        if (delta1)
+            for (int j = 0; j < 8; ++j) delta1[t][j] = hbuf[0].f32col[t][j].delta1[0];
+        if (dc_generic) dc_generic[t] = rq[t] != 0.f;
+    }
+    if (qfrac) *qfrac = hbuf[0].qfrac_bits;
+    return JPEZY_OK;
+}
+JPEZY_CATCH
+
+int jpezy_ctx_set_quant_tables(jpezy_ctx* c, const uint8_t luma[64], const uint8_t chroma[64])
+try {
+    if (!c) return set_err(JPEZY_E_BADARG, "null context");
+    int qt[2][64];
+    if (int rc = tables_from_args("set_quant_tables", luma, chroma, qt)) return rc;
+    bool same = true;
+    for (int t = 0; t < 2; ++t)
+        for (int k = 0; k < 64; ++k) same = same && qt[t][k] == c->qt[t][k];
+    if (same) return JPEZY_OK;                                   // the device tables are rewritten only when the setting changes
+    std::vector<DeviceTables> hbuf(1);
+    float rq[2], bias[2];
+    std::string why;
+    if (!build_encode_tables(qt, hbuf[0], rq, bias, &why)) return set_err(JPEZY_E_BADARG, why);
+    HIP_TRY(hipSetDevice(c->device));
+    // a launch on ANY stream may still read the tables: the rule of the dequantiser tables (wait for the device; never inside a capture).
+    // Nothing of the context has changed when this refuses.
+    if (int rc = drain_before_table_rewrite(c->stream, "set_quant_tables")) return rc;
+    HIP_TRY(hipMemcpy(c->d_tab.p, &hbuf[0], sizeof hbuf[0], hipMemcpyHostToDevice));
+    for (int t = 0; t < 2; ++t) {
+        for (int k = 0; k < 64; ++k) c->qt[t][k] = (uint8_t)qt[t][k];
+        c->dc_rq[t] = rq[t];
+        c->dc_bias[t] = bias[t];
+    }
+    c->qt_default = !std::memcmp(qt, kQt, sizeof qt);
+    return JPEZY_OK;
+}
+JPEZY_CATCH
+
+int jpezy_ctx_set_quality(jpezy_ctx* c, int quality)
+{
+    if (!c) return set_err(JPEZY_E_BADARG, "null context");
+    uint8_t luma[64], chroma[64];
+    if (int rc = jpezy_quality_tables(quality, luma, chroma)) return rc;
+    return jpezy_ctx_set_quant_tables(c, luma, chroma);
+}
+
+int jpezy_ctx_quant_tables(const jpezy_ctx* c, uint8_t luma[64], uint8_t chroma[64])
+{
+    if (!c || !luma || !chroma) return set_err(JPEZY_E_BADARG, "quant_tables: null pointer");
+    std::memcpy(luma, c->qt[0], 64);
+    std::memcpy(chroma, c->qt[1], 64);
+    return JPEZY_OK;
 }
 
 int jpezy_ctx_set_decode_tolerance(jpezy_ctx* c, int on)
@@ -260,7 +381,8 @@ int jpezy_internal_enc_params(jpezy_ctx* c, int W, int H, int gray, int n_frames
     p.quads_per_row = (p.mcu_cols + 3) / 4;
     p.n_frames = n_frames;
     fast_div_setup((unsigned)p.quads_per_row, &p.qpr_magic, &p.qpr_shift);
-    for (int t = 0; t < 2; ++t) { p.dc_rq[t] = c->dc_rq[t]; p.dc_bias[t] = c->dc_bias[t]; }
+    // dc_table_lookup (test hook): the launchers then take the !DCG instance and DeviceTables::dcq, as when a create-time check fails
+    for (int t = 0; t < 2; ++t) { p.dc_rq[t] = c->dc_table_lookup ? 0.f : c->dc_rq[t]; p.dc_bias[t] = c->dc_table_lookup ? 0.f : c->dc_bias[t]; }
     return JPEZY_OK;
 }
 
@@ -284,7 +406,11 @@ int jpezy_fdct_quant_dev(jpezy_ctx* c, const uint8_t* d_r, const uint8_t* d_g, c
         q.r += (size_t)f0 * plane_stride; q.g += (size_t)f0 * plane_stride; q.b += (size_t)f0 * plane_stride;
         q.coeffs += (size_t)f0 * p.coeffs_per_frame;
 #ifdef JPEZY_WITH_LAB
-        if (c->variant == 3)
+        // the persistent kernels were measured and archived with the Annex-K tables: a context with other tables hands its frames to
+        // variant 1's launch, as those variants do for the frames they do not cover
+        if (c->variant >= 2 && !c->qt_default)
+            HIP_TRY(launch_fdct_quant_f32(q, gray != 0, c->force_exact, s));
+        else if (c->variant == 3)
             HIP_TRY(launch_fdct_quant_f32_ps2(q, gray != 0, c->force_exact, c->n_cus, s));
         else if (c->variant == 2)
             HIP_TRY(launch_fdct_quant_f32_ps(q, gray != 0, c->force_exact, c->n_cus, s));

@@ -256,7 +256,7 @@ int entropy_chunk(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H, int gray,
         for (int f = f0; f < F; f += step) {
             uint8_t* dst = out + (size_t)f * cap;
             if (status[f]) { sizes[f] = JPEZY_E_FORMAT; failed.store(1); continue; }
-            const size_t hdr = jpezy_host::write_header(W, H, comment, dst, cap, optimize ? &tabs[(size_t)f * 4] : nullptr, c->restart_interval);
+            const size_t hdr = jpezy_host::write_header(W, H, comment, dst, cap, optimize ? &tabs[(size_t)f * 4] : nullptr, c->restart_interval, c->qt[0], c->qt[1]);
             const size_t body = (size_t)(nbytes[f] + fftot[f]);
             if (!hdr || hdr + body + 2 > cap) { sizes[f] = JPEZY_E_NOSPACE; failed.store(1); continue; }
             std::memcpy(dst + hdr, c->e_pinned.p + (size_t)f * o_stride, body);
@@ -293,10 +293,10 @@ int jpezy_write_jpeg_gpu_dev(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H
     HIP_TRY(hipSetDevice(c->device));
     if (int rc = ensure_code_tables(c)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    // header bytes: cached on the device per (W, H, comment) -- uploaded outside any capture on first use; 1024 bytes hold the
+    // header bytes: cached on the device per (W, H, comment, restart interval, quantisation tables: the bytes are compared) -- uploaded outside any capture on first use; 1024 bytes hold the
     // header with the longest comment allowed (JPEZY_MAX_COMMENT; with a DRI segment JPEZY_MAX_COMMENT_RESTART)
     uint8_t hdr[1024];
-    const size_t hdr_len = jpezy_host::write_header(W, H, comment, hdr, sizeof hdr, nullptr, c->restart_interval);
+    const size_t hdr_len = jpezy_host::write_header(W, H, comment, hdr, sizeof hdr, nullptr, c->restart_interval, c->qt[0], c->qt[1]);
     if (!hdr_len) return set_err(JPEZY_E_BADARG, "write_jpeg_gpu_dev: comment too long");
     if (c->e_hdr_len != hdr_len || std::memcmp(c->e_hdr_host, hdr, hdr_len)) {
         if (int rc = c->e_hdr.reserve(sizeof hdr)) return rc;
@@ -401,10 +401,11 @@ int jpezy_huffman_optimal_table(const unsigned long long freq[256], uint8_t bits
 }
 
 // the three forms of the host writer (jpezy_host::write_jpeg)
-static long host_write(const int16_t* coeffs, int W, int H, int gray, const char* comment, int restart, int optimize, uint8_t* out, size_t cap)
+static long host_write(const int16_t* coeffs, int W, int H, int gray, const char* comment, int restart, int optimize, uint8_t* out, size_t cap,
+                       const uint8_t* luma = nullptr, const uint8_t* chroma = nullptr)
 try {
     std::string err;
-    const long n = jpezy_host::write_jpeg(coeffs, W, H, gray != 0, comment, restart, optimize != 0, out, cap, &err);
+    const long n = jpezy_host::write_jpeg(coeffs, W, H, gray != 0, comment, restart, optimize != 0, out, cap, &err, luma, chroma);
     if (n < 0) g_err = err;
     return n;
 }
@@ -424,6 +425,15 @@ long jpezy_write_jpeg_rst(const int16_t* coeffs, int W, int H, int gray, const c
                           uint8_t* out, size_t cap)
 {
     return host_write(coeffs, W, H, gray, comment, restart_interval, optimize, out, cap);
+}
+
+long jpezy_write_jpeg_qt(const int16_t* coeffs, int W, int H, int gray, const char* comment, const uint8_t luma[64], const uint8_t chroma[64],
+                         int restart_interval, int optimize, uint8_t* out, size_t cap)
+{
+    if ((luma == nullptr) != (chroma == nullptr)) return set_err(JPEZY_E_BADARG, "write_jpeg_qt: one of the two tables is null (both null: Annex K)");
+    for (int k = 0; luma && k < 64; ++k)
+        if (!luma[k] || !chroma[k]) return set_err(JPEZY_E_BADARG, "write_jpeg_qt: a quantisation table entry is zero (1..255)");
+    return host_write(coeffs, W, H, gray, comment, restart_interval, optimize, out, cap, luma, chroma);
 }
 
 // planar RGB on the host -> .jpg bytes on the host, both stages on the GPU (what encoder::encode does end to end)

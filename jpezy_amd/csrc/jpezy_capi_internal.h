@@ -167,7 +167,10 @@ struct jpezy_ctx {
 #endif
     int variant = JPEZY_DEFAULT_VARIANT;   // encode kernel: 0 = FP64 butterflies, 1 = FP32 first level (default), 2 = variant 1's arithmetic in persistent workgroups
     int n_cus = 0;                 // compute units of the device (grid of the persistent kernel)
-    float dc_rq[2] = { 0, 0 }, dc_bias[2] = { 0, 0 };   // f32::dc_formula's constants; 0: the table-free DC does not reproduce the DC table (jpezy_ctx_create)
+    float dc_rq[2] = { 0, 0 }, dc_bias[2] = { 0, 0 };   // f32::dc_formula's constants; 0: the table-free DC does not reproduce the DC table (build_encode_tables)
+    uint8_t qt[2][64];             // the quantisation tables d_tab was built from (natural order): the header's DQT segments, jpezy_ctx_quant_tables
+    bool qt_default = true;        // ... are the Annex-K tables
+    bool dc_table_lookup = false;  // test hook (jpezy_ctx_set_dc_table_lookup): the DC from DeviceTables::dcq even where the checks allow the quantiser
     DevBuf d_trace;                // JPEZY_TRACE builds: 4 words per wave + 9 phase stamps (JPEZY_TRACE=3)
     DevBuf dump_t;                 // JPEZY_DUMP_T builds: level-1 t values of the last jpezy_fdct_quant_dev call
     DevBuf in[3], out, scratch;    // staging for the host-buffer entry points; scratch: samples of the generic decoder

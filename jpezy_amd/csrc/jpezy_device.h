@@ -7,9 +7,17 @@
 
 namespace jpezy_dev {
 
-// Fixed-point scale of the quantiser guard band: a coefficient is v/Q * 2^QFRAC_BITS truncated to int32.
-// |v/Q| <= 1024/10 with the Annex-K tables, so 2^24 keeps |n| < 2^31.
-constexpr int QFRAC_BITS = 24;
+// Fixed-point scale of encode variant 0's quantiser guard band: a coefficient is v/Q * 2^bits truncated to int32.  |v| <= 1024 (the DC of
+// a block of -128s; every other coefficient stays below 128 * 5.13^2 / 4 = 842), so |v/Q| <= 1024 / Qmin with Qmin the smallest entry of
+// the two tables, and bits = qfrac_bits(Qmin) is the largest width, at most QFRAC_BITS_MAX, with 1024 / Qmin * 2^bits < 2^31: 24 with the
+// Annex-K tables (Qmin = 10, the width this kernel has always had), 20 at Qmin = 1.  DeviceTables::qfrac_bits carries it.
+constexpr int QFRAC_BITS_MAX = 24;
+inline int qfrac_bits(int qmin)
+{
+    int bits = QFRAC_BITS_MAX;
+    while (bits > 0 && (1024ll << bits) >= (long long)qmin << 31) --bits;
+    return bits;
+}
 
 // Per (table, block column j) record of the f32 encode kernel: one 64-byte line per lane, three loads off one address.
 // The kernel's packed 8-point transform delivers its outputs as the pairs (0,4) (2,6) (1,3) (5,7): everything indexed by
@@ -33,13 +41,14 @@ struct DeviceTables {
     F32Column f32col[2][8];   // first: every field at an immediate offset from the table pointer
     // quantised DC as a function of the block's integer sample sum S in [-8192, 8192] (index S + 8192):
     // dcq[t][.] = int(((S * s) * s) / 4) / Q_t[0] with s = 1/sqrt(2), evaluated on the host in the reference's
-    // exact FP64 order (ref encoder/jpezy_encoder.hpp:163,171)
-    signed char dcq[2][16385];
-    // encode variant 0: qscale[t][j][i] = cu(j) * cv(i) / (4 * Q_t[i*8+j]) * 2^QFRAC_BITS   (t: 0 luma, 1 chroma)
+    // exact FP64 order (ref encoder/jpezy_encoder.hpp:163,171).  16-bit entries: |dcq| reaches 1024 at Q_t[0] = 1
+    int16_t dcq[2][16385];
+    // encode variant 0: qscale[t][j][i] = cu(j) * cv(i) / (4 * Q_t[i*8+j]) * 2^qfrac_bits   (t: 0 luma, 1 chroma)
     double qscale[2][8][8];
     double rq_dc[2];          // 1 / Q_t[0]
     int qt[2][64];            // natural order
     double qinv[2][64];       // 1.0 / Q_t[k] (levels 2/3 of the f32 kernel)
+    int qfrac_bits;           // encode variant 0: fraction width of its fixed-point quotients (qfrac_bits() above), one for both tables
 };
 
 // The exact-path counter is sharded over COUNTER_SHARDS words: thousands of waves adding to ONE word serialise
@@ -62,8 +71,8 @@ struct EncParams {
     int16_t* coeffs;
     size_t coeffs_per_frame;  // int16 elements
     const DeviceTables* tab;
-    const signed char* dcq_luma;     // &tab->dcq[0][0], &tab->dcq[1][0]: separate kernel arguments so that the f32 kernel's
-    const signed char* dcq_chroma;   // DC lookups are scalar-base + 32-bit-offset loads
+    const int16_t* dcq_luma;         // &tab->dcq[0][0], &tab->dcq[1][0]: separate kernel arguments so that the f32 kernel's
+    const int16_t* dcq_chroma;       // DC lookups are scalar-base + 32-bit-offset loads
     unsigned long long* fallback_count;
     int W, H, mcu_cols, mcu_rows, quads_per_row, n_frames;
     unsigned qpr_magic, qpr_shift;   // fast_div by quads_per_row

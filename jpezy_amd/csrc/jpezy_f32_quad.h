@@ -322,7 +322,7 @@ __device__ __forceinline__ int resolve_coef(const float* w, bool part, int y, in
 // Quantised DC of a block from the exact table (DeviceTables::dcq): sum = the lane's X0 of the column pass -- on the
 // j == 0 lane that is the block's integer sample sum (exact in FP32).  Issued right after the first adds of the column
 // pass, long before the value is needed, so the L2 latency never sits on a wave's critical path.
-__device__ __forceinline__ int dc_lookup(float sum, const signed char* dcq)
+__device__ __forceinline__ int dc_lookup(float sum, const int16_t* dcq)
 {
     // index = sum + 8192, formed in FP32 (exact) and clamped there (non-DC lanes carry arbitrary values); an
     // unsigned index keeps the lookup a scalar-base + 32-bit-offset load
@@ -338,7 +338,7 @@ __device__ __forceinline__ int dc_lookup(float sum, const signed char* dcq)
 // DeviceTables::dcq at context creation and only then lets the kernel use them (EncParams::dc_rq[t] != 0).
 // Only the j == 0 lane's result is used (quant_block_column); the other lanes feed it their X0 of some other
 // column -- an arbitrary float -- and throw the result away: no clamp is needed for them (an out-of-range v_cvt_i32_f32 saturates).
-__device__ __forceinline__ float dc_formula_f(float sum, float rq, float bias)    // the value as a float (an integer, |q| <= 64)
+__device__ __forceinline__ float dc_formula_f(float sum, float rq, float bias)    // the value as a float (an integer, |q| <= 1023)
 {
     const float d = __builtin_truncf(FMAF(__builtin_fabsf(sum), 0.125f, -0.125f));
     const float q = __builtin_truncf(FMAF(d, rq, bias));
@@ -351,6 +351,9 @@ __device__ __forceinline__ int dc_formula(float sum, float rq, float bias) { ret
 // error of fma(sum, ks, delta1) below 1e-5: the guard test flags the DC exactly when sum is a multiple of 8 Q (zero included), and
 // everywhere else (int)t' is the table's value.  A flagged DC evaluates dc_formula inside the candidate branch (0.6 % of blocks on
 // random pixels) and is never queued.  jpezy_ctx_create checks all of this for every sum with the same FP32 operations.
+// (The figures are the Annex-K tables'.  With caller-supplied tables the host repeats the check for them: a wide band beside a large DC
+// quantiser flags more sums than the multiples of 8 Q, which only sends more of them to dc_formula; DC quantisers for which dc_formula
+// itself misses the table -- the divisors of 369 and 738 -- get the !DCG instance and the lookup.  DESIGN.md 4.10.)
 // (Against the DC on a path of its own in every lane -- the !DCG instance: profiles/r07_dc_generic_ab.txt.)
 
 // Quantise one block column and stage it in zig-zag order.  F: the column pass' four output pairs (order pair_row);
@@ -493,7 +496,7 @@ struct QuadTrace { unsigned long long t2; unsigned long long ph[8]; };
 #define QUAD_TRACE_ARG
 #endif
 // pre / dcq_lds / cos_lds (persistent kernel): the lane's records already in registers, the two quantised-DC tables
-// ([2][16385] bytes) and the cosine table in LDS; null in the one-quad kernel, which reads all three from global memory.
+// ([2][16385] 16-bit entries) and the cosine table in LDS; null in the one-quad kernel, which reads all three from global memory.
 // The scheduler fences between the phases of a quad keep the one-quad kernel at 79 VGPRs (6 waves per SIMD); the persistent kernel has
 // 128 registers per lane anyway (16 waves per CU) and may let the scheduler overlap the phases (JPEZY_PS_FENCES=0).
 #define PHASE_FENCE() do { if (!PS || JPEZY_PS_FENCES) __builtin_amdgcn_sched_barrier(0); } while (0)
@@ -507,7 +510,7 @@ struct NoHook { __device__ __forceinline__ void operator()() const {} };
 template <bool GRAY, int FORCE, bool PS, bool DCG = false, bool YCC = false, class AFTER_PIXELS>
 __device__ __forceinline__ void encode_quad_compute(const EncParams& p, const uint32_t* R, const uint32_t* G, const uint32_t* B, uint32_t* lds,
                                             int lane, int mcu_y, int quad_x, int frame, unsigned qidx, const LaneConsts* pre,
-                                            const signed char* dcq_lds, const PsTables* pst, AFTER_PIXELS after_pixels QUAD_TRACE_PARAM)
+                                            const int16_t* dcq_lds, const PsTables* pst, AFTER_PIXELS after_pixels QUAD_TRACE_PARAM)
 {
 #if defined(JPEZY_TRACE) && JPEZY_TRACE >= 3
     unsigned long long* ph = tr->ph;
@@ -605,8 +608,8 @@ __device__ __forceinline__ void encode_quad_compute(const EncParams& p, const ui
     // (dc_rq == 0: the formula does not hold for this build's constants -- the table lookup, three byte loads per quad, stays).
     // Formula against table: 26.45 against 26.79 us (five rounds, profiles/r05_persistent_ab.txt)
     const bool DCF = PS ? (bool)JPEZY_PS_DC_FORMULA : (p.dc_rq[0] != 0.f && p.dc_rq[1] != 0.f);
-    const signed char* dcq_l = PS && JPEZY_PS_DCQ_LDS ? dcq_lds : p.dcq_luma;
-    const signed char* dcq_c = PS && JPEZY_PS_DCQ_LDS ? dcq_lds + 16385 : p.dcq_chroma;
+    const int16_t* dcq_l = PS && JPEZY_PS_DCQ_LDS ? dcq_lds : p.dcq_luma;
+    const int16_t* dcq_c = PS && JPEZY_PS_DCQ_LDS ? dcq_lds + 16385 : p.dcq_chroma;
     {
         f2 ks[4];
 #pragma unroll
@@ -802,7 +805,7 @@ __device__ __forceinline__ void encode_quad_store(const EncParams& p, uint32_t* 
 template <bool GRAY, int FORCE, bool PS, bool DCG = false, bool YCC = false>
 __device__ __forceinline__ void encode_quad(const EncParams& p, const uint32_t* R, const uint32_t* G, const uint32_t* B, uint32_t* lds,
                                             int lane, int mcu_y, int quad_x, int frame, unsigned qidx, const LaneConsts* pre,
-                                            const signed char* dcq_lds, const PsTables* pst QUAD_TRACE_PARAM)
+                                            const int16_t* dcq_lds, const PsTables* pst QUAD_TRACE_PARAM)
 {
     encode_quad_compute<GRAY, FORCE, PS, DCG, YCC>(p, R, G, B, lds, lane, mcu_y, quad_x, frame, qidx, pre, dcq_lds, pst, NoHook()
 #ifdef JPEZY_TRACE

@@ -159,7 +159,7 @@ inline bool put_block(BitSink& o, const int16_t* z, int& pred, const EncLut& dc,
     return true;
 }
 
-void put_header(BitSink& o, int W, int H, const char* comment, const HuffTable* tabs = nullptr, int restart = 0)
+void put_header(BitSink& o, int W, int H, const char* comment, const HuffTable* tabs, int restart, const uint8_t* luma, const uint8_t* chroma)
 {
     static const uint8_t soi_app0[] = { 0xFF, 0xD8, 0xFF, 0xE0, 0x00, 0x10, 'J', 'F', 'I', 'F', 0x00,
                                         0x01, 0x02, 0x01, 0x00, 0x60, 0x00, 0x60, 0x00, 0x00 };
@@ -171,7 +171,7 @@ void put_header(BitSink& o, int W, int H, const char* comment, const HuffTable* 
         o.raw_n(comment, n + 1);
     }
     for (int t = 0; t < 2; ++t) {
-        const uint8_t* q = t ? kQtChroma : kQtLuma;
+        const uint8_t* q = t ? (chroma ? chroma : kQtChroma) : (luma ? luma : kQtLuma);   // Pq = 0: 8-bit entries, zig-zag order
         o.raw(0xFF); o.raw(0xDB); o.raw16(67); o.raw((unsigned)t);
         for (int i = 0; i < 64; ++i) o.raw(q[kZZ[i]]);
     }
@@ -208,11 +208,12 @@ bool restart_ok(int restart, const char* comment)
     return restart == 0 || !comment || std::strlen(comment) <= JPEZY_MAX_COMMENT_RESTART;   // the six DRI bytes come out of the comment's room
 }
 
-size_t write_header(int W, int H, const char* comment, uint8_t* out, size_t cap, const HuffTable* tabs, int restart)
+size_t write_header(int W, int H, const char* comment, uint8_t* out, size_t cap, const HuffTable* tabs, int restart, const uint8_t* luma,
+                    const uint8_t* chroma)
 {
     if (!comment_ok(comment) || !restart_ok(restart, comment)) return 0;
     BitSink o(out, cap);
-    put_header(o, W, H, comment, tabs, restart);
+    put_header(o, W, H, comment, tabs, restart, luma, chroma);
     return o.ok() ? o.size() : 0;
 }
 
@@ -238,6 +239,10 @@ size_t jpeg_bound(int W, int H)
     // Restart intervals: every interval but the last adds a pad byte at the most (two if it is 0xFF and stuffed) and a 2-byte marker,
     // so at one MCU per interval 4 bytes per MCU; with the frame's own pad and EOI (4 bytes, once) that is still inside the 196 bytes
     // 2492 leaves of 2688.  The six DRI bytes come out of the comment's room (JPEZY_MAX_COMMENT_RESTART).  (tests/test_restart_host.py)
+    // Quantisation tables (jpezy_write_jpeg_qt, jpezy_ctx_set_quant_tables): the bound does not depend on them.  The two DQT segments
+    // have a fixed length, and the worst-case scan above is the worst case of the CODE (every value of the largest size the tables hold),
+    // whatever quantiser produced the values; on 8-bit input no table makes a value leave the code tables (|AC| <= 1020, DC difference
+    // <= 2038 at Q = 1).  (tests/test_quant_host.py)
     return 1024 + nmcu * 6 * 64 * 7;
 }
 
@@ -339,7 +344,7 @@ int optimal_table(const unsigned long long freq_in[256], uint8_t bits_out[16], u
 }
 
 long write_jpeg(const int16_t* coeffs, int W, int H, bool gray, const char* comment, int restart, bool optimize, uint8_t* out, size_t cap,
-                std::string* err)
+                std::string* err, const uint8_t* luma, const uint8_t* chroma)
 {
     if (!coeffs || !out || W <= 0 || H <= 0 || W > 65535 || H > 65535) {
         if (err) *err = "write_jpeg: bad argument";
@@ -372,7 +377,7 @@ long write_jpeg(const int16_t* coeffs, int W, int H, bool gray, const char* comm
     const EncTables& T = own ? *own : enc_tables();
 
     BitSink o(out, cap);
-    put_header(o, W, H, comment, optimize ? tabs : nullptr, restart);
+    put_header(o, W, H, comment, optimize ? tabs : nullptr, restart, luma, chroma);
 
     static const int16_t kZeroBlock[64] = { 0 };
     const size_t nmcu = (size_t)((W + 15) / 16) * (size_t)((H + 15) / 16);

@@ -16,8 +16,10 @@ namespace jpezy_host {
 // padded to a byte (JPEZY_PAD_BIT) and RSTn (n = interval index mod 8) follows; predictors zero at every interval's start.
 // optimize: the frame's own optimal tables (below), built from the symbols this scan emits, for Annex K's: same coefficients, same decoded
 // pixels, a smaller file.
+// luma, chroma: the quantisation tables the two DQT segments state (natural order, 8-bit entries; nullptr: Annex K) -- the header's only;
+// the coefficients are written as they are.
 long write_jpeg(const int16_t* coeffs, int W, int H, bool gray, const char* comment, int restart, bool optimize, uint8_t* out, size_t cap,
-                std::string* err);
+                std::string* err, const uint8_t* luma = nullptr, const uint8_t* chroma = nullptr);
 size_t jpeg_bound(int W, int H);
 // false for a comment longer than JPEZY_MAX_COMMENT: every writer refuses it (JPEZY_E_BADARG)
 bool comment_ok(const char* comment);
@@ -31,7 +33,9 @@ struct HuffTable {
 // comment too long.  tabs: the four tables of the DHT segments in file order YDc, CDc, YAc, CAc (nullptr: Annex K)
 // restart: MCUs per restart interval (0: none) -- a DRI segment in front of SOS; 0 is returned too for a restart interval outside
 // 0..65535 or, with one, a comment longer than JPEZY_MAX_COMMENT_RESTART
-size_t write_header(int W, int H, const char* comment, uint8_t* out, size_t cap, const HuffTable* tabs = nullptr, int restart = 0);
+// luma, chroma: the tables of the two DQT segments (natural order; nullptr: Annex K); the segments' length does not depend on them
+size_t write_header(int W, int H, const char* comment, uint8_t* out, size_t cap, const HuffTable* tabs = nullptr, int restart = 0,
+                    const uint8_t* luma = nullptr, const uint8_t* chroma = nullptr);
 bool restart_ok(int restart, const char* comment);
 // canonical (code, length) per symbol of four tables in DHT order YDc, CDc, YAc, CAc (for the GPU coder); nullptr: Annex K
 void enc_code_tables(uint16_t code[4][256], uint8_t len[4][256], const HuffTable* tabs = nullptr);

@@ -46,7 +46,7 @@ static_assert(PS_NL * (PS_LAG + 1) <= PS_NSLOT && 12 * PS_LAG <= 63, "every grou
 #endif                         // always spread evenly over a CU's four SIMDs (the register budget is per SIMD)
 constexpr int PS_WAVES = PS_NC + PS_NL + JPEZY_PS_PAD_WAVES;
 constexpr int PS_SLOT_BYTES = 3 * 4096;
-constexpr int PS_DCQ_BYTES = JPEZY_PS_DCQ_LDS ? (2 * 16385 + 15) / 16 * 16 : 16;      // LDS copy of DeviceTables::dcq (the tail of the last 16 bytes is never indexed)
+constexpr int PS_DCQ_BYTES = JPEZY_PS_DCQ_LDS ? (2 * 16385 * 2 + 15) / 16 * 16 : 16;      // LDS copy of DeviceTables::dcq (the tail of the last 16 bytes is never indexed)
 constexpr unsigned PS_SPIN_CAP = 1u << 20;     // x ~300 cycles per poll: > 100 ms
 struct PsControl {
     unsigned full[4];
@@ -87,7 +87,7 @@ __global__ __launch_bounds__(64 * PS_WAVES, (JPEZY_PS_WG_PER_CU * PS_WAVES + 3) 
     // the loop of a compute wave holds no vector-memory LOAD: a wait for one (vmcnt counts in issue order) would also wait for
     // the previous quad's coefficient stores.  So the workgroup keeps its own copy of the two quantised-DC tables and of the
     // cosine table in LDS, and every compute lane its quantiser records in registers.
-    __shared__ __attribute__((aligned(16))) signed char dcq_s[PS_DCQ_BYTES];
+    __shared__ __attribute__((aligned(16))) int16_t dcq_s[PS_DCQ_BYTES / 2];
     __shared__ PsTables pst;
     const int lane0 = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const unsigned nwg = gridDim.x, w = blockIdx.x;
@@ -277,14 +277,14 @@ constexpr int PS2_WAVES = JPEZY_PS2_WAVES;      // waves per workgroup = quads p
 // workgroups per CU: two when they are small enough (12 waves: six always-computing waves per SIMD -- which takes the DC formula instead of
 // the 32 KB table, the quantiser records read from LDS instead of kept in 22 registers, and a kernel within 80 VGPRs)
 constexpr int PS2_WG_PER_CU = PS2_WAVES <= 12 ? 2 : 1;
-static_assert(PS2_WG_PER_CU * (PS2_WAVES * WAVE_LDS_DWORDS * 4 + (JPEZY_PS_DC_FORMULA ? 16 : (2 * 16385 + 15) / 16 * 16) + (int)sizeof(PsTables) + 16) <= 160 * 1024, "LDS per CU");
+static_assert(PS2_WG_PER_CU * (PS2_WAVES * WAVE_LDS_DWORDS * 4 + (JPEZY_PS_DC_FORMULA ? 16 : (2 * 16385 * 2 + 15) / 16 * 16) + (int)sizeof(PsTables) + 16) <= 160 * 1024, "LDS per CU");
 
 template <bool GRAY, int FORCE>
 __global__ __launch_bounds__(64 * PS2_WAVES, (PS2_WG_PER_CU * PS2_WAVES + 3) / 4) void fdct_quant_f32_ps2_kernel(EncParams p)
 {
-    constexpr int DCQ_BYTES = JPEZY_PS_DC_FORMULA ? 16 : (2 * 16385 + 15) / 16 * 16;
+    constexpr int DCQ_BYTES = JPEZY_PS_DC_FORMULA ? 16 : (2 * 16385 * 2 + 15) / 16 * 16;
     __shared__ __attribute__((aligned(16))) uint32_t slices[PS2_WAVES][WAVE_LDS_DWORDS];
-    __shared__ __attribute__((aligned(16))) signed char dcq_s[DCQ_BYTES];
+    __shared__ __attribute__((aligned(16))) int16_t dcq_s[DCQ_BYTES / 2];
     __shared__ PsTables pst;
     const int lane0 = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     // The workgroup owns the runs of 16 consecutive quads number w, w + gridDim.x, ... (w = blockIdx.x) and its waves DRAW quads from

@@ -150,16 +150,21 @@ __device__ __forceinline__ int exact_fdct_coef_wave(const BlockRef& img, int px0
 }
 
 // Quantise the 8 coefficients F[i] (vertical frequency i, this lane's horizontal frequency j).
-// ks[i] = cu*cv/(4Q) * 2^24.  n[i] = trunc(v/Q * 2^24); q[i] = trunc-toward-zero(n / 2^24).
-// Returns true when some coefficient lies within 1 unit of a multiple of 2^24 (candidate for the exact path).
-__device__ __forceinline__ bool quant8(const double* F, const double* ks, bool dc_lane, double rq_dc, int* n, int* q)
+// ks[i] = cu*cv/(4Q) * 2^bits.  n[i] = trunc(v/Q * 2^bits); q[i] = trunc-toward-zero(n / 2^bits).
+// bits = DeviceTables::qfrac_bits, chosen by the host from the tables so that |n| <= 2^30 (jpezy_device.h): 24 with the Annex-K tables,
+// 20 when a table holds a 1.  Returns true when some coefficient lies within 1 unit of a multiple of 2^bits (candidate for the exact
+// path).  Why one unit is enough at every width: n is off from trunc(t * 2^bits) of the reference's own t = v/Q by at most one unit as
+// long as the two values of t differ by less than 2^-bits.  They differ by the rounding of the FP64 butterflies against the reference's
+// 64-term FP64 sum and of ks -- below 200 roundings of 2^-53 on |v| <= 1024, i.e. 3e-11 in v and no more in t (Q >= 1) -- against a
+// unit of 2^-24 = 6e-8 at the widest width (a factor of 2000) and of 2^-20 = 9.5e-7 at the narrowest (a factor of 30000).
+__device__ __forceinline__ bool quant8(const double* F, const double* ks, bool dc_lane, double rq_dc, int bits, int* n, int* q)
 {
-    constexpr int MASK = (1 << QFRAC_BITS) - 1;
+    const int MASK = (1 << bits) - 1;
     unsigned m[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
         n[i] = (int)(F[i] * ks[i]);                          // v_cvt_i32_f64 truncates toward zero
-        q[i] = (n[i] + ((n[i] >> 31) & MASK)) >> QFRAC_BITS;  // trunc-toward-zero division by 2^24
+        q[i] = (n[i] + ((n[i] >> 31) & MASK)) >> bits;       // trunc-toward-zero division by 2^bits
         m[i] = (unsigned)(n[i] + 1) & MASK;                  // 0,1,2 <=> within one unit of a boundary
     }
     // DC: F[0] of the j == 0 lane is the exact integer sum of the block, so the reference value
@@ -183,17 +188,17 @@ constexpr int STG_BLK = 144;
 
 // Quantise one block column, write it (zig-zag) to the staging area and queue the guard-band hits.
 // blk = index of the block inside the quad (m*BPM + b).  Queue entry = blk << 6 | natural index.
-__device__ __forceinline__ void quant_block_column(const double* F, const double* ks, int j, double rq_dc,
+__device__ __forceinline__ void quant_block_column(const double* F, const double* ks, int j, double rq_dc, int bits,
                                                    bool live, const int* zoff, char* stage_blk, int blk,
                                                    unsigned* queue)
 {
-    constexpr int MASK = (1 << QFRAC_BITS) - 1;
+    const int MASK = (1 << bits) - 1;
     int n[8], q[8];
-    const bool cand = quant8(F, ks, j == 0, rq_dc, n, q);
+    const bool cand = quant8(F, ks, j == 0, rq_dc, bits, n, q);
     if (cand && live) {   // rare.  Fully unrolled: a runtime index into n[] would send the array to scratch
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-            // within one unit of a multiple of 2^24 -- except around 0, which is not a truncation boundary;
+            // within one unit of a multiple of 2^bits -- except around 0, which is not a truncation boundary;
             // the DC term of the j == 0 lane is already exact
             const bool f = ((unsigned)(n[i] + 1) & MASK) <= 2u && (unsigned)(n[i] + 1) > 2u && !(i == 0 && j == 0);
             if (f) {
@@ -310,6 +315,7 @@ __global__ __launch_bounds__(64 * WPB, 4) void fdct_quant_kernel(EncParams p)
     const int cq = row;                 // 0..15
     const int j = cq & 7;
     const DeviceTables* tab = p.tab;
+    const int qbits = tab->qfrac_bits;  // wave-uniform: one scalar load
     char* stage = reinterpret_cast<char*>(lds) + STG_BASE;
     int zoff[8];                        // byte offset of natural coefficient (i, j) inside a staged block
 #pragma unroll
@@ -332,8 +338,8 @@ __global__ __launch_bounds__(64 * WPB, 4) void fdct_quant_kernel(EncParams p)
         for (int i = 0; i < 8; ++i) ks[i] = tab->qscale[0][j][i];
         const double rq = tab->rq_dc[0];
         const int bx = cq >> 3;   // 0: left blocks (Y0,Y2), 1: right blocks (Y1,Y3)
-        quant_block_column(Ftop, ks, j, rq, live, zoff, stage + (m * BPM + bx) * STG_BLK, m * BPM + bx, queue);
-        quant_block_column(Fbot, ks, j, rq, live, zoff, stage + (m * BPM + 2 + bx) * STG_BLK, m * BPM + 2 + bx, queue);
+        quant_block_column(Ftop, ks, j, rq, qbits, live, zoff, stage + (m * BPM + bx) * STG_BLK, m * BPM + bx, queue);
+        quant_block_column(Fbot, ks, j, rq, qbits, live, zoff, stage + (m * BPM + 2 + bx) * STG_BLK, m * BPM + 2 + bx, queue);
     }
 
     // ---- 5. chroma: top-left pixel of every 2x2 (ref :134-142) = even pixel rows, even columns.  The odd-row
@@ -374,7 +380,7 @@ __global__ __launch_bounds__(64 * WPB, 4) void fdct_quant_kernel(EncParams p)
 #pragma unroll
         for (int i = 0; i < 8; ++i) ks[i] = tab->qscale[1][j][i];
         const int comp = 1 + (cq >> 3);
-        quant_block_column(Fc, ks, j, tab->rq_dc[1], live, zoff, stage + (m * BPM + 3 + comp) * STG_BLK,
+        quant_block_column(Fc, ks, j, tab->rq_dc[1], qbits, live, zoff, stage + (m * BPM + 3 + comp) * STG_BLK,
                            m * BPM + 3 + comp, queue);
     }
     wave_sync();

@@ -348,7 +348,7 @@ int jpezy_ctx_restart_interval(const jpezy_ctx* ctx);
  * coefficients are non-zero and more fall into the kernels' guard bands (DESIGN.md 4.10 has the figures).
  * Out of scope: the multi-GPU handle (jpezy_multi_*, jpezy_encode_batch_multi) owns its contexts and always writes Annex-K tables;
  * jpezy_write_jpeg[_opt, _rst, _batch] keep their signatures and bytes; no per-frame tables inside one batch call; no 16-bit tables;
- * no chroma sampling other than 4:2:0.
+ * chroma sampling is an argument of the *_sampling entry points (end of this header), not a context setting.
  */
 int jpezy_quality_tables(int quality, uint8_t luma[64], uint8_t chroma[64]);
 int jpezy_ctx_set_quant_tables(jpezy_ctx* ctx, const uint8_t luma[64], const uint8_t chroma[64]);
@@ -744,6 +744,80 @@ long jpezy_encode_jpeg_ycc(jpezy_ctx* ctx, const uint8_t* y, size_t y_stride, co
  * (h0-1)*y_stride + w0 or c_cap < (hc-1)*c_stride + (wc-1)*c_step + 1 (w, h: jpezy_ycc_component_size). */
 int jpezy_decode_jpeg_ycc(jpezy_ctx* ctx, const uint8_t* data, size_t len, jpezy_frame_info* info, uint8_t* y, size_t y_stride, size_t y_cap,
                           uint8_t* cb, uint8_t* cr, size_t c_stride, int c_step, size_t c_cap);
+
+/*
+ * CHROMA SAMPLING as an argument of the encoder's entry points (opt-in; every entry above keeps its signature, kernels and bytes).
+ * The reference writes 2x2 / 1x1 / 1x1 only, so the definition of 4:4:4 is this project's own: the reference's per-sample arithmetic
+ * with the decimation step left out.
+ *
+ *   sampling      JPEZY_SAMPLING_420 = 0: the entry of the same name without _sampling, gray passed on -- the same kernels, the same bytes.
+ *                 JPEZY_SAMPLING_444 = 1: below.  Any other value: JPEZY_E_BADARG.
+ *   MCU           8 x 8 pixels; mcu_cols = ceil(W / 8), mcu_rows = ceil(H / 8); three blocks in the order Y, Cb, Cr.  The picture is
+ *                 extended to whole MCUs by clamping pixel coordinates (min(x, W-1), min(y, H-1)) as make_YCC does
+ *                 (encoder/jpezy_encoder.hpp:101,104).
+ *   Samples       Y, Cb and Cr of EVERY pixel from RGB::Y / Cb / Cr in the reference's FP64 order (:244-256), truncating.  Nothing of
+ *                 make_YCC:116-143 (the pick of every second sample) applies.
+ *   Transform     every block through DCT (:146-166) and quantization(cs) (:168-172) with the context's tables (Annex K, or
+ *                 jpezy_ctx_set_quality / _set_quant_tables): Y by the luma table, Cb and Cr by the chroma table; zig-zag order.
+ *   Coefficients  int16 [frame][mcu_y][mcu_x][3][64]: 192 * mcu_cols * mcu_rows elements per frame (jpezy_coeff_count_sampling), twice
+ *                 the 4:2:0 count per pixel.
+ *   File          the reference's writer (encoder/jpezy_writer.hpp:20-105, encoder/jpezy_encoder.hpp:174-242) except: SOF0 states H, V =
+ *                 1,1 / 1,1 / 1,1; the scan's MCUs hold three blocks; DC prediction runs per component; Y is coded with the luma
+ *                 Huffman tables, Cb and Cr with the chroma ones.  Optimised tables, restart intervals (counted in 8 x 8 MCUs) and DQT
+ *                 tables compose as they do for 4:2:0.  jpezy_read_jpeg[_gpu] and jpezy_decode_jpeg* read such files (H = V = 1,1,1,
+ *                 blocks_per_mcu = 3).
+ *   Bound         jpezy_jpeg_bound_sampling: 1024 + 1344 per 8 x 8 MCU (three blocks of at most 1661 bits = 623 bytes, 1246 stuffed,
+ *                 plus restart / pad / EOI); jpezy_jpeg_bound is per 16 x 16 MCU of six blocks and too small for 4:4:4.
+ *   Refused       gray != 0 with JPEZY_SAMPLING_444 (JPEZY_E_BADARG: a gray 4:4:4 file has no use that the gray 4:2:0 file lacks);
+ *                 encode variant 0, the FP64 kernel, with JPEZY_SAMPLING_444 (JPEZY_E_UNSUPPORTED; the context stays usable).
+ *   Context settings  jpezy_ctx_set_force_exact (levels 0-3), _set_dc_table_lookup, _set_quality / _set_quant_tables act on the 4:4:4
+ *                 transform as on the 4:2:0 one; jpezy_encode_jpeg_sampling[_packed] honour _set_huffman_optimize and
+ *                 _set_restart_interval.
+ *   Alignment     none required.  W % 8 == 0 with 8-byte aligned planes and plane stride (packed: 16-byte aligned base and strides)
+ *                 takes the 8-byte (24 / 32-byte) load form.
+ *
+ * jpezy_encode_jpeg_sampling[_packed] run both stages on the GPU: the transform kernel, then jpezy_write_jpeg_gpu_sampling (the 4:2:0
+ * entries' streaming upload in MCU-row bands is not built for 4:4:4: the picture goes up in one piece).
+ * NOT provided for 4:4:4: the multi-GPU handle; planar YCbCr 4:4:4 INPUT; 4:2:2 / 4:4:0; gray; encode variant 0.
+ */
+#define JPEZY_SAMPLING_420 0
+#define JPEZY_SAMPLING_444 1
+/* mcu_cols, mcu_rows, blocks_per_mcu (any may be NULL) of a W x H frame; pure host functions.  The counts are 0 for a bad argument. */
+int jpezy_sampling_geometry(int sampling, int W, int H, int* mcu_cols, int* mcu_rows, int* blocks_per_mcu);
+size_t jpezy_coeff_count_sampling(int W, int H, int sampling);   /* int16 elements per frame */
+size_t jpezy_jpeg_bound_sampling(int W, int H, int sampling);
+/* jpezy_fdct_quant_dev / jpezy_fdct_quant_packed_dev for the sampling: stand in for encoder/jpezy_encoder.hpp:90-172 (4:4:4: without
+ * :116-143).  d_coeffs holds jpezy_coeff_count_sampling elements per frame.  Asynchronous on `stream`. */
+int jpezy_fdct_quant_sampling_dev(jpezy_ctx* ctx, const uint8_t* d_r, const uint8_t* d_g, const uint8_t* d_b, size_t plane_stride, int W,
+                                  int H, int sampling, int gray, int n_frames, int16_t* d_coeffs, void* stream);
+int jpezy_fdct_quant_sampling_packed_dev(jpezy_ctx* ctx, const uint8_t* d_pix, int format, size_t row_stride, size_t frame_stride, int W,
+                                         int H, int sampling, int gray, int n_frames, int16_t* d_coeffs, void* stream);
+/* jpezy_write_jpeg_qt for the sampling (host writer; stands in for encoder/jpezy_writer.hpp:20-105 + encoder/jpezy_encoder.hpp:174-242);
+ * out must hold jpezy_jpeg_bound_sampling bytes to be safe for any coefficients */
+long jpezy_write_jpeg_sampling(const int16_t* coeffs, int W, int H, int sampling, int gray, const char* comment, const uint8_t luma[64],
+                               const uint8_t chroma[64], int restart_interval, int optimize, uint8_t* out, size_t cap);
+/* jpezy_write_jpeg_gpu / _batch / _dev for the sampling: the GPU entropy coder on the sampling's MCUs; the bytes of jpezy_write_jpeg_sampling
+ * with the context's DQT tables, restart interval (counted in the sampling's MCUs) and optimise setting.  out / d_out hold
+ * jpezy_jpeg_bound_sampling bytes per frame to be safe.  _dev: asynchronous and capturable, JPEZY_E_UNSUPPORTED while
+ * jpezy_ctx_set_huffman_optimize is on; a frame with a value outside the code tables gets JPEZY_E_FORMAT in its size slot, the others
+ * are written. */
+long jpezy_write_jpeg_gpu_sampling(jpezy_ctx* ctx, const int16_t* d_coeffs, int W, int H, int sampling, int gray, const char* comment,
+                                   uint8_t* out, size_t cap);
+int jpezy_write_jpeg_gpu_sampling_batch(jpezy_ctx* ctx, const int16_t* d_coeffs, int W, int H, int sampling, int gray, int n_frames,
+                                        const char* comment, uint8_t* out, size_t cap, long* sizes);
+int jpezy_write_jpeg_gpu_sampling_dev(jpezy_ctx* ctx, const int16_t* d_coeffs, int W, int H, int sampling, int gray, int n_frames,
+                                      const char* comment, uint8_t* d_out, size_t out_stride, long long* d_sizes, void* stream);
+/* jpezy_huffman_histogram_dev for the sampling (the context's restart interval acts, as there) */
+int jpezy_huffman_histogram_sampling_dev(jpezy_ctx* ctx, const int16_t* d_coeffs, int W, int H, int sampling, int gray, int n_frames,
+                                         unsigned long long* d_hist, void* stream);
+/* the symbols that writer emits for the frame (host function): hist[k][sym], k in DHT order YDc, CDc, YAc, CAc; JPEZY_E_FORMAT (counts
+ * of the clamped symbols) when a value lies outside the code tables */
+int jpezy_huffman_histogram_sampling(const int16_t* coeffs, int W, int H, int sampling, int restart_interval, unsigned long long hist[4][256]);
+/* jpezy_encode_jpeg / jpezy_encode_jpeg_packed for the sampling (encoder/jpezy_encoder.hpp:38-77) */
+long jpezy_encode_jpeg_sampling(jpezy_ctx* ctx, const uint8_t* r, const uint8_t* g, const uint8_t* b, int W, int H, int sampling, int gray,
+                                const char* comment, uint8_t* out, size_t cap);
+long jpezy_encode_jpeg_sampling_packed(jpezy_ctx* ctx, const uint8_t* pix, int format, size_t row_stride, int W, int H, int sampling,
+                                       int gray, const char* comment, uint8_t* out, size_t cap);
 
 #ifdef __cplusplus
 }

@@ -20,8 +20,12 @@ from .api import (  # noqa: F401
     PIX_RGB24,
     PIX_RGBA32,
     Rect,
+    SAMPLING_420,
+    SAMPLING_444,
     coeff_count,
     encode_batch_multi,
+    huffman_histogram,
+    jpeg_bound,
     library_path,
     load_library,
     mcu_grid,
@@ -30,6 +34,7 @@ from .api import (  # noqa: F401
     quant_tables_probe,
     read_jpeg,
     region_check,
+    sampling_geometry,
     scaled_size,
     shard_range,
     write_jpeg,
@@ -39,6 +44,6 @@ from .api import (  # noqa: F401
 )
 
 __all__ = [
-    "Context", "Decoder", "Encoder", "FrameInfo", "JpezyError", "MultiEncoder", "PIX_BGR24", "PIX_BGRA32", "PIX_RGB24", "PIX_RGBA32", "Rect", "coeff_count", "encode_batch_multi", "library_path",
-    "load_library", "mcu_grid", "optimal_table", "quality_tables", "quant_tables_probe", "read_jpeg", "region_check", "scaled_size", "shard_range", "write_jpeg", "write_jpeg_batch", "ycc_chroma_size", "ycc_component_size",
+    "Context", "Decoder", "Encoder", "FrameInfo", "JpezyError", "MultiEncoder", "PIX_BGR24", "PIX_BGRA32", "PIX_RGB24", "PIX_RGBA32", "Rect", "SAMPLING_420", "SAMPLING_444", "coeff_count", "encode_batch_multi", "huffman_histogram", "jpeg_bound", "library_path",
+    "load_library", "mcu_grid", "optimal_table", "quality_tables", "quant_tables_probe", "read_jpeg", "region_check", "sampling_geometry", "scaled_size", "shard_range", "write_jpeg", "write_jpeg_batch", "ycc_chroma_size", "ycc_component_size",
 ]

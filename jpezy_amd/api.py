@@ -145,7 +145,26 @@ ABI = [
     ("jpezy_encode_jpeg_ycc", C.c_long, [_vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, _vp, C.c_size_t]),
     ("jpezy_decode_jpeg_ycc", C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(FrameInfo), _vp, C.c_size_t, C.c_size_t, _vp, _vp, C.c_size_t, C.c_int,
                                         C.c_size_t]),
+    ("jpezy_sampling_geometry", C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    ("jpezy_coeff_count_sampling", C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    ("jpezy_jpeg_bound_sampling", C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    ("jpezy_fdct_quant_sampling_dev", C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]),
+    ("jpezy_fdct_quant_sampling_packed_dev", C.c_int, [_vp, _vp, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp,
+                                                       _vp]),
+    ("jpezy_write_jpeg_sampling", C.c_long, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, _vp, _vp, C.c_int, C.c_int, _vp, C.c_size_t]),
+    ("jpezy_write_jpeg_gpu_sampling", C.c_long, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, _vp, C.c_size_t]),
+    ("jpezy_write_jpeg_gpu_sampling_batch", C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, _vp, C.c_size_t, _vp]),
+    ("jpezy_write_jpeg_gpu_sampling_dev", C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, _vp, C.c_size_t, _vp, _vp]),
+    ("jpezy_huffman_histogram_sampling_dev", C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]),
+    ("jpezy_huffman_histogram_sampling", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
+    ("jpezy_encode_jpeg_sampling", C.c_long, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, _vp, C.c_size_t]),
+    ("jpezy_encode_jpeg_sampling_packed", C.c_long, [_vp, _vp, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, _vp,
+                                                     C.c_size_t]),
 ]
+
+# chroma sampling of the encoder's *_sampling entry points: 4:2:0 (the reference's 2x2 / 1x1 / 1x1, everything as without the keyword)
+# or 4:4:4 (8 x 8 MCUs of Y, Cb, Cr, no decimation; include/jpezy_hip.h has the definition)
+SAMPLING_420, SAMPLING_444 = 0, 1
 
 # enum jpezy_pixel_format: packed (interleaved) pixels, 3 or 4 bytes each
 PIX_RGB24, PIX_BGR24, PIX_RGBA32, PIX_BGRA32 = 0, 1, 2, 3
@@ -196,8 +215,38 @@ def mcu_grid(W, H):
     return lib.jpezy_mcu_cols(W), lib.jpezy_mcu_rows(H)
 
 
-def coeff_count(W, H, gray=False):
+def coeff_count(W, H, gray=False, sampling=SAMPLING_420):
+    if sampling != SAMPLING_420:
+        if gray:
+            raise JpezyError("coeff_count: gray is not available with SAMPLING_444")
+        sampling_geometry(sampling, W, H)
+        return load_library().jpezy_coeff_count_sampling(W, H, int(sampling))
     return load_library().jpezy_coeff_count(W, H, int(gray))
+
+
+def sampling_geometry(sampling, W, H):
+    """(mcu_cols, mcu_rows, blocks_per_mcu) of a W x H frame: 16 x 16 MCUs of 6 blocks (SAMPLING_420) or 8 x 8 MCUs of 3 (SAMPLING_444)"""
+    mc, mr, bpm = C.c_int(), C.c_int(), C.c_int()
+    _check(load_library().jpezy_sampling_geometry(int(sampling), W, H, C.byref(mc), C.byref(mr), C.byref(bpm)))
+    return mc.value, mr.value, bpm.value
+
+
+def jpeg_bound(W, H, sampling=SAMPLING_420):
+    """bytes that hold the .jpg of any W x H coefficient field of the sampling"""
+    if sampling != SAMPLING_420:
+        sampling_geometry(sampling, W, H)
+        return load_library().jpezy_jpeg_bound_sampling(W, H, int(sampling))
+    return load_library().jpezy_jpeg_bound(W, H)
+
+
+def huffman_histogram(coeffs, W, H, sampling=SAMPLING_420, restart_interval=0):
+    """uint64 [4, 256]: the symbols write_jpeg(..., sampling=) emits for the frame, table k in DHT order YDc, CDc, YAc, CAc (host)"""
+    coeffs = np.ascontiguousarray(coeffs, dtype=np.int16)
+    if coeffs.size != coeff_count(W, H, sampling=sampling):
+        raise JpezyError("coefficient buffer size does not match W, H, sampling")
+    hist = np.zeros((4, 256), dtype=np.uint64)
+    _check(load_library().jpezy_huffman_histogram_sampling(_np_ptr(coeffs), W, H, int(sampling), int(restart_interval), _np_ptr(hist)))
+    return hist
 
 
 def scaled_size(W, H, scale):
@@ -410,21 +459,36 @@ class Context:
                                                                        d_b.data_ptr(), stream))
 
     # ---- device-pointer entry points (torch tensors on this context's device) ----
-    def fdct_quant_dev(self, d_r, d_g, d_b, W, H, d_coeffs, gray=False, n_frames=1, plane_stride=None, stream=None):
+    def fdct_quant_dev(self, d_r, d_g, d_b, W, H, d_coeffs, gray=False, n_frames=1, plane_stride=None, stream=None, sampling=SAMPLING_420):
         import torch
         if stream is None:
             stream = torch.cuda.current_stream(d_r.device).cuda_stream
         stride = plane_stride if plane_stride is not None else W * H
+        if sampling != SAMPLING_420:      # d_coeffs: coeff_count(W, H, sampling=sampling) elements per frame
+            _check(load_library().jpezy_fdct_quant_sampling_dev(self._h, d_r.data_ptr(), d_g.data_ptr(), d_b.data_ptr(), stride, W, H,
+                                                                int(sampling), int(gray), n_frames, d_coeffs.data_ptr(), stream))
+            return
         _check(load_library().jpezy_fdct_quant_dev(self._h, d_r.data_ptr(), d_g.data_ptr(), d_b.data_ptr(), stride, W, H,
                                                    int(gray), n_frames, d_coeffs.data_ptr(), stream))
 
     # ---- entropy coding on the GPU: same bytes as write_jpeg ----
-    def write_jpeg_gpu(self, d_coeffs, W, H, gray=False, comment=None, n_frames=1):
+    def write_jpeg_gpu(self, d_coeffs, W, H, gray=False, comment=None, n_frames=1, sampling=SAMPLING_420, raise_on_error=True):
         """Device coefficients (torch int16 tensor, the output of fdct_quant_dev; its producing stream must be
-        synchronised) -> list of .jpg bytes, Huffman coding + bit packing + byte stuffing on the GPU."""
+        synchronised) -> list of .jpg bytes, Huffman coding + bit packing + byte stuffing on the GPU.
+        sampling=SAMPLING_444: coefficients of 3-block MCUs; raise_on_error=False (that form only): a frame that failed is its negative
+        status in the list instead of an exception for the whole call."""
         lib = load_library()
         if comment is None:
             comment = b"Encoded by JPEZY" if gray else b"Encoded by jpezy"
+        if sampling != SAMPLING_420:
+            cap = jpeg_bound(W, H, sampling)
+            buf = np.empty(cap * n_frames, dtype=np.uint8)
+            sizes = (C.c_long * n_frames)()
+            rc = lib.jpezy_write_jpeg_gpu_sampling_batch(self._h, d_coeffs.data_ptr(), W, H, int(sampling), int(gray), n_frames, comment,
+                                                         _np_ptr(buf), cap, sizes)
+            if raise_on_error or (rc < 0 and all(n >= 0 for n in sizes)):
+                _check(rc)
+            return [buf[f * cap: f * cap + sizes[f]].tobytes() if sizes[f] >= 0 else int(sizes[f]) for f in range(n_frames)]
         cap = lib.jpezy_jpeg_bound(W, H)
         buf = np.empty(cap * n_frames, dtype=np.uint8)
         sizes = (C.c_long * n_frames)()
@@ -432,7 +496,7 @@ class Context:
         _check(rc)
         return [buf[f * cap: f * cap + sizes[f]].tobytes() for f in range(n_frames)]
 
-    def write_jpeg_gpu_dev(self, d_coeffs, W, H, d_out, d_sizes, gray=False, comment=None, n_frames=1, stream=None):
+    def write_jpeg_gpu_dev(self, d_coeffs, W, H, d_out, d_sizes, gray=False, comment=None, n_frames=1, stream=None, sampling=SAMPLING_420):
         """Asynchronous, device-resident: d_out is a torch uint8 tensor [n_frames, out_stride], d_sizes int64 [n_frames];
         every frame's complete .jpg is left in d_out[f, :d_sizes[f]]."""
         import torch
@@ -441,10 +505,14 @@ class Context:
         if comment is None:
             comment = b"Encoded by JPEZY" if gray else b"Encoded by jpezy"
         stride = d_out.numel() // n_frames
+        if sampling != SAMPLING_420:
+            _check(load_library().jpezy_write_jpeg_gpu_sampling_dev(self._h, d_coeffs.data_ptr(), W, H, int(sampling), int(gray), n_frames, comment,
+                                                                    d_out.data_ptr(), stride, d_sizes.data_ptr(), stream))
+            return
         _check(load_library().jpezy_write_jpeg_gpu_dev(self._h, d_coeffs.data_ptr(), W, H, int(gray), n_frames, comment,
                                                        d_out.data_ptr(), stride, d_sizes.data_ptr(), stream))
 
-    def huffman_histogram_dev(self, d_coeffs, W, H, d_hist, gray=False, n_frames=1, stream=None):
+    def huffman_histogram_dev(self, d_coeffs, W, H, d_hist, gray=False, n_frames=1, stream=None, sampling=SAMPLING_420):
         """Asynchronous: d_hist (torch int64 tensor [n_frames, 4, 256] on the device) receives the frames' symbol counts, table k in
         DHT order YDc, CDc, YAc, CAc."""
         import torch
@@ -452,6 +520,10 @@ class Context:
             stream = torch.cuda.current_stream(d_coeffs.device).cuda_stream
         if d_hist.numel() != n_frames * 4 * 256 or d_hist.element_size() != 8 or not d_hist.is_contiguous():
             raise JpezyError("huffman_histogram_dev: d_hist must be a contiguous 64-bit tensor of n_frames * 4 * 256 elements")
+        if sampling != SAMPLING_420:
+            _check(load_library().jpezy_huffman_histogram_sampling_dev(self._h, d_coeffs.data_ptr(), W, H, int(sampling), int(gray), n_frames,
+                                                                       d_hist.data_ptr(), stream))
+            return
         _check(load_library().jpezy_huffman_histogram_dev(self._h, d_coeffs.data_ptr(), W, H, int(gray), n_frames, d_hist.data_ptr(), stream))
 
     def read_jpeg_gpu(self, data):
@@ -526,14 +598,20 @@ class Context:
         """synchronisation passes of the last read_jpeg_gpu call; 0 = the host decoder was used"""
         return load_library().jpezy_ctx_last_huffdec_passes(self._h)
 
-    def encode_jpeg(self, r, g, b, W, H, gray=False, comment=None):
-        """Host planes -> .jpg bytes, both stages on the GPU (encoder::encode end to end)."""
+    def encode_jpeg(self, r, g, b, W, H, gray=False, comment=None, sampling=SAMPLING_420):
+        """Host planes -> .jpg bytes, both stages on the GPU (encoder::encode end to end).  sampling=SAMPLING_444: a 4:4:4 file."""
         lib = load_library()
         r, g, b = (np.ascontiguousarray(p, dtype=np.uint8).reshape(-1) for p in (r, g, b))
         if not (r.size == g.size == b.size == W * H):
             raise JpezyError("plane size does not match W*H")
         if comment is None:
             comment = b"Encoded by JPEZY" if gray else b"Encoded by jpezy"
+        if sampling != SAMPLING_420:
+            cap = jpeg_bound(W, H, sampling)
+            buf = np.empty(cap, dtype=np.uint8)
+            n = _check(lib.jpezy_encode_jpeg_sampling(self._h, _np_ptr(r), _np_ptr(g), _np_ptr(b), W, H, int(sampling), int(gray), comment,
+                                                      _np_ptr(buf), cap))
+            return buf[:n].tobytes()
         cap = lib.jpezy_jpeg_bound(W, H)
         buf = np.empty(cap, dtype=np.uint8)
         n = lib.jpezy_encode_jpeg(self._h, _np_ptr(r), _np_ptr(g), _np_ptr(b), W, H, int(gray), comment, _np_ptr(buf), cap)
@@ -553,7 +631,7 @@ class Context:
                                                      stream))
 
     # ---- packed (interleaved) pixels ----
-    def encode_jpeg_packed(self, img, format=PIX_RGB24, gray=False, comment=None):
+    def encode_jpeg_packed(self, img, format=PIX_RGB24, gray=False, comment=None, sampling=SAMPLING_420):
         """numpy uint8 (H, W, C) interleaved pixels -> .jpg bytes (the bytes encode_jpeg gives for the same pixels).  Taken as it is,
         without a copy, whenever strides[2] == 1 and strides[1] == C: strides[0] becomes row_stride, so a cropped view encodes in place."""
         lib = load_library()
@@ -566,6 +644,12 @@ class Context:
         H, W = img.shape[:2]
         if comment is None:
             comment = b"Encoded by JPEZY" if gray else b"Encoded by jpezy"
+        if sampling != SAMPLING_420:
+            cap = jpeg_bound(W, H, sampling)
+            buf = np.empty(cap, dtype=np.uint8)
+            n = _check(lib.jpezy_encode_jpeg_sampling_packed(self._h, _np_ptr(img), int(format), img.strides[0], W, H, int(sampling), int(gray),
+                                                             comment, _np_ptr(buf), cap))
+            return buf[:n].tobytes()
         cap = lib.jpezy_jpeg_bound(W, H)
         buf = np.empty(cap, dtype=np.uint8)
         n = lib.jpezy_encode_jpeg_packed(self._h, _np_ptr(img), int(format), img.strides[0], W, H, int(gray), comment, _np_ptr(buf), cap)
@@ -597,12 +681,16 @@ class Context:
         frame = int(d_img.stride(0)) if d_img.dim() == 4 and n > 1 else 0
         return n, H, W, row, frame
 
-    def fdct_quant_packed_dev(self, d_img, d_coeffs, format=PIX_RGB24, gray=False, stream=None):
+    def fdct_quant_packed_dev(self, d_img, d_coeffs, format=PIX_RGB24, gray=False, stream=None, sampling=SAMPLING_420):
         """device packed pixels (torch uint8 (H, W, C) or (N, H, W, C); row and frame strides are the tensor's) -> d_coeffs"""
         import torch
         n, H, W, row, frame = self._packed_layout(d_img, pixel_bytes(format), "fdct_quant_packed_dev")
         if stream is None:
             stream = torch.cuda.current_stream(d_img.device).cuda_stream
+        if sampling != SAMPLING_420:
+            _check(load_library().jpezy_fdct_quant_sampling_packed_dev(self._h, d_img.data_ptr(), int(format), row, frame, W, H, int(sampling),
+                                                                       int(gray), n, d_coeffs.data_ptr(), stream))
+            return
         _check(load_library().jpezy_fdct_quant_packed_dev(self._h, d_img.data_ptr(), int(format), row, frame, W, H, int(gray), n,
                                                           d_coeffs.data_ptr(), stream))
 
@@ -837,13 +925,26 @@ def optimal_table(freq):
     return bits, vals[:n].copy()
 
 
-def write_jpeg(coeffs, W, H, gray=False, comment=None, optimize=False, restart_interval=0, quant_tables=None):
+def write_jpeg(coeffs, W, H, gray=False, comment=None, optimize=False, restart_interval=0, quant_tables=None, sampling=SAMPLING_420):
     """zig-zag int16 coefficients -> the .jpg bytes jpezy_encode writes (header + Huffman + EOI); optimize: with the frame's own
     optimal Huffman tables instead of Annex K (same coefficients, smaller file); restart_interval: MCUs per restart interval
     (DRI segment, RSTn markers, predictors reset), 0 for none; quant_tables = (luma, chroma): the tables the DQT segments state
-    (64 entries each, natural order, 1..255) instead of Annex K -- the coefficients are written as they are."""
+    (64 entries each, natural order, 1..255) instead of Annex K -- the coefficients are written as they are.
+    sampling=SAMPLING_444: coefficients of 8 x 8 MCUs of Y, Cb, Cr (coeff_count(W, H, sampling=SAMPLING_444)), a 4:4:4 file."""
     lib = load_library()
     coeffs = np.ascontiguousarray(coeffs, dtype=np.int16)
+    if sampling != SAMPLING_420:
+        if not gray and coeffs.size != coeff_count(W, H, sampling=sampling):
+            raise JpezyError("coefficient buffer size does not match W, H, sampling")
+        if comment is None:
+            comment = b"Encoded by jpezy"
+        luma, chroma = (_table(t, "write_jpeg") for t in quant_tables) if quant_tables is not None else (None, None)
+        cap = jpeg_bound(W, H, sampling)
+        buf = np.empty(cap, dtype=np.uint8)
+        n = _check(lib.jpezy_write_jpeg_sampling(_np_ptr(coeffs), W, H, int(sampling), int(gray), comment,
+                                                 _np_ptr(luma) if luma is not None else None, _np_ptr(chroma) if chroma is not None else None,
+                                                 int(restart_interval), int(bool(optimize)), _np_ptr(buf), cap))
+        return buf[:n].tobytes()
     if coeffs.size != lib.jpezy_coeff_count(W, H, int(gray)):
         raise JpezyError("coefficient buffer size does not match W, H, gray")
     if comment is None:

@@ -27,8 +27,9 @@
 namespace jpezy {
 
 struct to_jpeg {
-    explicit constexpr to_jpeg(const char* file_) : file(file_) {}
+    explicit constexpr to_jpeg(const char* file_, int sampling_ = JPEZY_SAMPLING_420) : file(file_), sampling(sampling_) {}
     const char* file;
+    int sampling;      // JPEZY_SAMPLING_420 (the reference's only layout) or JPEZY_SAMPLING_444: encoder::encode's second argument
 };
 
 struct gray_scale_t {};
@@ -186,21 +187,21 @@ private:
     }
 
     template <class MODE_TAG>
-    std::size_t run_encoder(const char* file, const char* comment) const
+    std::size_t run_encoder(const char* file, const char* comment, int sampling = JPEZY_SAMPLING_420) const
     {
         const property pr = make_property({ width, height, 3, 8, comment, property::Format::JFIF, byte(1), byte(2),
                                             property::Units::dots_inch, 96, 96, 0, 0, property::ExtensionCodes::undefined,
                                             property::AnalyzedResult::Yet });
         auto [r, g, b] = split_rgb();
         encoder enc(pr, r, g, b);
-        return enc.template encode<MODE_TAG>(file);
+        return enc.template encode<MODE_TAG>(file, sampling);
     }
 
     friend std::ofstream& operator<<(std::ofstream& ofs, const std::pair<const to_jpeg, const encode_io&>& pnm)   // :135-169
     {
         ofs.close();
         pnm.second.report_error(__func__);
-        const std::size_t size = pnm.second.run_encoder<COLOR_MODE>(pnm.first.file, "Encoded by jpezy");
+        const std::size_t size = pnm.second.run_encoder<COLOR_MODE>(pnm.first.file, "Encoded by jpezy", pnm.first.sampling);
         std::cout << "Output size: " << size << " byte" << std::endl;
         return ofs;
     }

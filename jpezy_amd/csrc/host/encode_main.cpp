@@ -7,6 +7,9 @@
 // intervals of N MCUs, 0..65535 (jpezy_ctx_set_restart_interval); a malformed N is a usage error.
 // Extension (not in the reference):  --quality=N (single-file mode and --i420, one token, anywhere behind the output name) encodes with
 // libjpeg's quality N, 1..100 (jpezy_ctx_set_quality; 50 is the default); a malformed or out-of-range N is a usage error.
+// Extension (not in the reference):  --sampling=444|420 (single-file mode, one token, anywhere behind the output name) writes the file with
+// 4:4:4 chroma sampling (jpezy_encode_jpeg_sampling: 8 x 8 MCUs, no chroma decimation) or, the default, 4:2:0; composes with --optimize,
+// --restart, --quality and --gpus 1.  Together with --gray, --i420 or --gpus N > 1, 444 prints the rule and exits 1.
 // Extension (not in the reference):  jpezy_encode --gpus N [--gray] <in1.ppm> <out1.jpg> [<in2.ppm> <out2.jpg> ...]
 // encodes a list of files on up to N GPUs of this node through jpezy_encode_batch_multi: runs of consecutive inputs of one size
 // form a batch, a batch is sharded over the GPUs frame by frame.
@@ -41,16 +44,25 @@ bool has_ext(std::string_view s, std::string_view ext)
 }
 
 // jpezy_encode --gpus N [--gray] in out [in out ...]
-int batch_main(const int argc, const char* argv[])
+int parse_sampling(std::string_view tok);
+int sampling_rule();
+int take_sampling(std::vector<const char*>& args, std::size_t from);
+
+int batch_main(const int argc_in, const char* argv_in[])
 {
+    std::vector<const char*> args(argv_in, argv_in + argc_in);
+    const int sampling = take_sampling(args, 3);
+    const int argc = static_cast<int>(args.size());
+    const char* const* argv = args.data();
     const int want = std::atoi(argv[2]);
     int a = 3;
     bool gray = false;
     if (a < argc && std::string_view(argv[a]) == "--gray") { gray = true; ++a; }
-    if (want <= 0 || a >= argc || (argc - a) % 2 != 0) {
+    if (want <= 0 || a >= argc || (argc - a) % 2 != 0 || sampling < 0) {
         std::cerr << "Usage: jpezy_encode --gpus N [--gray] <in1.ppm> <out1.jpg> [<in2.ppm> <out2.jpg> ...]" << std::endl;
         return EXIT_FAILURE;
     }
+    if (sampling == JPEZY_SAMPLING_444 && (gray || want > 1)) return sampling_rule();
     const int have = jpezy_hip_device_count();
     if (have <= 0) { std::cerr << "jpezy_encode: no HIP device (the jpezy hot path has no CPU fallback)" << std::endl; return EXIT_FAILURE; }
     std::vector<int> devices;
@@ -70,11 +82,21 @@ int batch_main(const int argc, const char* argv[])
             else if (pnm.image_width() != W || pnm.image_height() != H) break;
             pnm.append_planes(r, g, b);
         }
-        const std::size_t stride = jpezy_jpeg_bound(static_cast<int>(W), static_cast<int>(H));
+        const std::size_t stride = jpezy_jpeg_bound_sampling(static_cast<int>(W), static_cast<int>(H), sampling);
         std::vector<std::uint8_t> jpg(stride * static_cast<std::size_t>(n));
         std::vector<long long> sizes(static_cast<std::size_t>(n));
         const char* comment = gray ? "Encoded by JPEZY" : "Encoded by jpezy";
-        if (n == 1) {
+        if (sampling == JPEZY_SAMPLING_444) {      // one GPU (checked above): frame by frame through the single-file entry
+            if (!single) single = jpezy_ctx_create(devices[0]);
+            if (!single) { std::cerr << "jpezy_ctx_create: " << jpezy_hip_last_error() << std::endl; return EXIT_FAILURE; }
+            const std::size_t px = W * H;
+            for (int i = 0; i < n; ++i) {
+                const std::size_t o = px * static_cast<std::size_t>(i);
+                sizes[static_cast<std::size_t>(i)] = jpezy_encode_jpeg_sampling(single, r.data() + o, g.data() + o, b.data() + o, static_cast<int>(W), static_cast<int>(H),
+                                                                                sampling, 0, comment, jpg.data() + stride * static_cast<std::size_t>(i), stride);
+                if (sizes[static_cast<std::size_t>(i)] < 0) { std::cerr << "jpezy_encode_jpeg_sampling: " << jpezy_hip_last_error() << std::endl; jpezy_ctx_destroy(single); return EXIT_FAILURE; }
+            }
+        } else if (n == 1) {
             // a run of one frame has nothing to shard: the ordinary single-file path (streams the frame band by band, no ring of
             // whole-frame slots: a 16K x 16K file would otherwise reserve several GB of pinned memory for nothing)
             if (!single) single = jpezy_ctx_create(devices[0]);
@@ -128,6 +150,32 @@ int parse_quality(std::string_view tok)
     return n >= 1 && n <= 100 ? n : -1;
 }
 
+// "--sampling=444" / "--sampling=420": JPEZY_SAMPLING_*; anything else that starts like it: -1
+int parse_sampling(std::string_view tok)
+{
+    tok.remove_prefix(std::string_view("--sampling=").size());
+    return tok == "444" ? JPEZY_SAMPLING_444 : tok == "420" ? JPEZY_SAMPLING_420 : -1;
+}
+
+int sampling_rule()
+{
+    std::cerr << "jpezy_encode: --sampling=444 writes colour files from RGB input on one GPU; it cannot be combined with --gray, --i420 or --gpus N > 1"
+              << std::endl;
+    return EXIT_FAILURE;
+}
+
+// takes the one "--sampling=..." token at or behind position `from` out of args: its value, JPEZY_SAMPLING_420 when there is none, -1 malformed
+int take_sampling(std::vector<const char*>& args, std::size_t from)
+{
+    for (std::size_t i = from; i < args.size(); ++i)
+        if (std::string_view(args[i]).rfind("--sampling=", 0) == 0) {
+            const int s = parse_sampling(args[i]);
+            args.erase(args.begin() + static_cast<std::ptrdiff_t>(i));
+            return s;
+        }
+    return JPEZY_SAMPLING_420;
+}
+
 // jpezy_encode --i420=WxH in.yuv out.jpg [--gray] [--optimize] [--restart=N] [--quality=N]
 int i420_main(const int argc, const char* argv[])
 {
@@ -149,6 +197,8 @@ int i420_main(const int argc, const char* argv[])
         else if (o == "--optimize") optimize = true;
         else if (o.rfind("--restart=", 0) == 0 && (restart = parse_restart(o)) >= 0) continue;
         else if (o.rfind("--quality=", 0) == 0 && (quality = parse_quality(o)) >= 1) continue;
+        else if (o.rfind("--sampling=", 0) == 0 && parse_sampling(o) == JPEZY_SAMPLING_420) continue;
+        else if (o.rfind("--sampling=", 0) == 0 && parse_sampling(o) == JPEZY_SAMPLING_444) return sampling_rule();
         else return usage();
     }
     jpezy::disp_logo();
@@ -206,6 +256,8 @@ int main(const int argc_in, const char* argv_in[])
             args.erase(args.begin() + static_cast<std::ptrdiff_t>(i));
             break;
         }
+    const int sampling = take_sampling(args, 3);
+    if (sampling < 0) return disp_error();
     const int argc = static_cast<int>(args.size());
     const char* const* argv = args.data();
 
@@ -227,6 +279,7 @@ int main(const int argc_in, const char* argv_in[])
     } else {
         return disp_error();
     }
+    if (sampling == JPEZY_SAMPLING_444 && (m1 != Mode::JPEG || m2 == Mode::GRAY)) return m1 == Mode::JPEG ? sampling_rule() : disp_error();
 
     jpezy::disp_logo();
 
@@ -249,7 +302,7 @@ int main(const int argc_in, const char* argv_in[])
                 throw std::runtime_error(std::string("jpezy_ctx_set_quality: ") + jpezy_hip_last_error());
             std::ofstream ofs(argv[2], std::ios::binary);
             if (m2 == Mode::GRAY) ofs << (pnm | jpezy::to_jpeg(argv[2]) | jpezy::gray_scale);
-            else ofs << (pnm | jpezy::to_jpeg(argv[2]));
+            else ofs << (pnm | jpezy::to_jpeg(argv[2], sampling));
         } else if (m1 == Mode::PPM) {
             std::ofstream ofs(argv[2]);
             static_cast<std::ostream&>(ofs) << pnm;

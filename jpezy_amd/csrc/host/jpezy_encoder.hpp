@@ -25,8 +25,11 @@ struct encoder {
 
     static constexpr int block_size = 8;
 
+    // sampling (not in the reference, which writes 2x2 / 1x1 / 1x1 only): JPEZY_SAMPLING_420, or JPEZY_SAMPLING_444 -- a colour file of
+    // 8 x 8 MCUs without chroma decimation (jpezy_encode_jpeg_sampling; include/jpezy_hip.h has the definition); 4:4:4 with GRAY_MODE is
+    // refused with the library's message
     template <class MODE_TAG = COLOR_MODE>
-    std::size_t encode(const char* output_file)
+    std::size_t encode(const char* output_file, int sampling = JPEZY_SAMPLING_420)
     {
         constexpr bool gray = std::is_same_v<MODE_TAG, GRAY_MODE>;
         const int W = static_cast<int>(pr.template get<property::At::HSize>());
@@ -35,7 +38,9 @@ struct encoder {
             throw std::runtime_error("encode");
         std::FILE* fp = std::fopen(output_file, "wb");
         if (!fp) throw std::runtime_error("write_header");          // jpezy_writer::write_header (:22-23)
-        std::vector<std::uint8_t> out(jpezy_jpeg_bound(W, H));
+        if (sampling != JPEZY_SAMPLING_420 && (gray || sampling != JPEZY_SAMPLING_444))
+            throw std::runtime_error(gray ? "encode: gray is not available with 4:4:4 sampling" : "encode: unknown sampling");
+        std::vector<std::uint8_t> out(jpezy_jpeg_bound_sampling(W, H, sampling));
         long n = 0;
         {
             raii_messenger mes("Write JPEG Header ...");          // the header is produced with the entropy data below
@@ -43,6 +48,12 @@ struct encoder {
         try {
             raii_messenger mes("Encoding ...");
             jpezy_ctx* ctx = detail::device_context();
+            if (sampling == JPEZY_SAMPLING_444) {
+                n = jpezy_encode_jpeg_sampling(ctx, reinterpret_cast<const std::uint8_t*>(r.data()), reinterpret_cast<const std::uint8_t*>(g.data()),
+                                               reinterpret_cast<const std::uint8_t*>(b.data()), W, H, sampling, 0,
+                                               pr.template get<property::At::Comment>().c_str(), out.data(), out.size());
+                if (n < 0 && n != JPEZY_E_FORMAT) throw std::runtime_error(std::string("jpezy_encode_jpeg_sampling: ") + jpezy_hip_last_error());
+            } else {
 #ifdef JPEZY_HOST_ENTROPY
             std::vector<std::int16_t> coeffs(jpezy_coeff_count(W, H, gray));
             if (jpezy_fdct_quant(ctx, reinterpret_cast<const std::uint8_t*>(r.data()), reinterpret_cast<const std::uint8_t*>(g.data()),
@@ -55,6 +66,7 @@ struct encoder {
                                   pr.template get<property::At::Comment>().c_str(), out.data(), out.size());
             if (n < 0 && n != JPEZY_E_FORMAT) throw std::runtime_error(std::string("jpezy_encode_jpeg: ") + jpezy_hip_last_error());
 #endif
+            }
             if (n < 0) throw std::runtime_error("encode_huffman");   // ref :186-187, 207-208
         } catch (...) {
             std::fclose(fp);

@@ -71,16 +71,20 @@ int ensure_code_tables(jpezy_ctx* c)
 }
 
 // restart: the context's setting; an interval that holds the whole frame changes the header alone, so the device is told of none
+// sampling: JPEZY_SAMPLING_420 (gray or colour) or JPEZY_SAMPLING_444 (colour; the callers have refused gray) -- the job's MCU layout
 void make_job(jpezy_dev::entropy::Job& job, const int16_t* d_coeffs, int W, int H, int gray, int F, const jpezy_dev::entropy::CodeTables* tables,
-              int restart)
+              int restart, int sampling = JPEZY_SAMPLING_420)
 {
-    const size_t n_mcu = (size_t)jpezy_mcu_cols(W) * jpezy_mcu_rows(H);
+    const jpezy_host::McuLayout L = jpezy_host::mcu_layout(sampling, gray != 0);
+    const size_t n_mcu = (size_t)((W + L.mcu_px - 1) / L.mcu_px) * (size_t)((H + L.mcu_px - 1) / L.mcu_px);
     job.restart = restart > 0 && (size_t)restart < n_mcu ? (unsigned)restart : 0u;
     job.coeffs = d_coeffs;
-    job.coeffs_per_frame = jpezy_coeff_count(W, H, gray);
+    job.coeffs_per_frame = n_mcu * (size_t)L.stored * 64;
     job.tables = tables;
-    job.blocks_per_frame = (unsigned)((size_t)jpezy_mcu_cols(W) * jpezy_mcu_rows(H) * 6);
-    job.bpm = gray ? 4 : 6;
+    job.blocks_per_frame = (unsigned)(n_mcu * (size_t)L.coded);
+    job.bpm = L.stored;
+    job.coded = L.coded;
+    job.luma = L.luma;
     job.n_frames = F;
     job.tables_stride = 0;
 }
@@ -97,10 +101,10 @@ int check_restart_comment(const jpezy_ctx* c, const char* comment, const char* w
 constexpr int kMaxOptFramesPerPass = 1024;
 
 // frames of one pass of either form: worst-case streams of 1 GiB, and the frame index is a grid dimension
-int frames_per_pass(const jpezy_ctx* c, int W, int H, int gray, int n_frames)
+int frames_per_pass(const jpezy_ctx* c, int W, int H, int gray, int n_frames, int sampling)
 {
     jpezy_dev::entropy::Job job;
-    make_job(job, nullptr, W, H, gray, 1, nullptr, c->restart_interval);
+    make_job(job, nullptr, W, H, gray, 1, nullptr, c->restart_interval, sampling);
     const size_t per = std::min<size_t>(std::min<size_t>((size_t)n_frames, kMaxFramesPerLaunch), jpezy_dev::entropy::max_pass_frames(job));
     return c->huff_optimize ? std::min((int)per, kMaxOptFramesPerPass) : (int)per;
 }
@@ -117,11 +121,11 @@ struct Pass {
     //   resident = true (device-resident form, capturable): status is the context's e_status, zero between calls -- zeroed once when it
     //     grows (first call, never inside a capture); the consumer of the tile totals latches and clears it, the stuffing kernel reads
     //     the latched copy.  Nothing is reserved and nothing synchronised on a call whose arguments the context has seen.
-    int plan(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H, int gray, int F, bool resident, hipStream_t stream)
+    int plan(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H, int gray, int F, bool resident, hipStream_t stream, int sampling)
     {
         namespace E = jpezy_dev::entropy;
         s = stream;
-        make_job(job, d_coeffs, W, H, gray, F, c->d_codes.as<E::CodeTables>(), c->restart_interval);
+        make_job(job, d_coeffs, W, H, gray, F, c->d_codes.as<E::CodeTables>(), c->restart_interval, sampling);
         const E::ScratchSizes z = E::scratch_sizes(job, c->huff_optimize != 0);
         if (int rc = c->e_S.reserve(z.tile_stream)) return rc;
         if (int rc = c->e_tt.reserve(z.tile_total)) return rc;
@@ -194,13 +198,13 @@ int enqueue_histogram(const jpezy_dev::entropy::Job& job, unsigned long long* d_
 
 // one pass of the host-delivered form
 int entropy_chunk(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H, int gray, int F, const char* comment, uint8_t* out,
-                  size_t cap, long* sizes, bool* any_failed)
+                  size_t cap, long* sizes, bool* any_failed, int sampling)
 {
     namespace E = jpezy_dev::entropy;
     hipStream_t s = c->stream;
     const bool optimize = c->huff_optimize != 0;
     Pass p;
-    if (int rc = p.plan(c, d_coeffs, W, H, gray, F, false, s)) return rc;
+    if (int rc = p.plan(c, d_coeffs, W, H, gray, F, false, s, sampling)) return rc;
 
     // 0. per-image tables: the frames' symbol counts come to the host, which builds every frame's four tables (Annex K.2) and
     //    sends their code images back; the coder then takes frame f's image.  One extra synchronisation and two small copies.
@@ -256,7 +260,7 @@ int entropy_chunk(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H, int gray,
         for (int f = f0; f < F; f += step) {
             uint8_t* dst = out + (size_t)f * cap;
             if (status[f]) { sizes[f] = JPEZY_E_FORMAT; failed.store(1); continue; }
-            const size_t hdr = jpezy_host::write_header(W, H, comment, dst, cap, optimize ? &tabs[(size_t)f * 4] : nullptr, c->restart_interval, c->qt[0], c->qt[1]);
+            const size_t hdr = jpezy_host::write_header(W, H, comment, dst, cap, optimize ? &tabs[(size_t)f * 4] : nullptr, c->restart_interval, c->qt[0], c->qt[1], sampling);
             const size_t body = (size_t)(nbytes[f] + fftot[f]);
             if (!hdr || hdr + body + 2 > cap) { sizes[f] = JPEZY_E_NOSPACE; failed.store(1); continue; }
             std::memcpy(dst + hdr, c->e_pinned.p + (size_t)f * o_stride, body);
@@ -277,9 +281,10 @@ int entropy_chunk(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H, int gray,
 
 }  // namespace
 
+// The three GPU writers and the histogram for a sampling (jpezy_capi_sampling.hip; JPEZY_SAMPLING_420: the public entries below).
 // Device-resident, asynchronous variant: everything is enqueued on `stream`, nothing is copied to the host.
-int jpezy_write_jpeg_gpu_dev(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H, int gray, int n_frames, const char* comment,
-                             uint8_t* d_out, size_t out_stride, long long* d_sizes, void* stream)
+int jpezy_internal_write_jpeg_gpu_dev(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H, int gray, int sampling, int n_frames, const char* comment,
+                                      uint8_t* d_out, size_t out_stride, long long* d_sizes, void* stream)
 {
     namespace E = jpezy_dev::entropy;
     if (int rc = jpezy_internal_check_dims(c, W, H, n_frames)) return rc;
@@ -296,7 +301,7 @@ int jpezy_write_jpeg_gpu_dev(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H
     // header bytes: cached on the device per (W, H, comment, restart interval, quantisation tables: the bytes are compared) -- uploaded outside any capture on first use; 1024 bytes hold the
     // header with the longest comment allowed (JPEZY_MAX_COMMENT; with a DRI segment JPEZY_MAX_COMMENT_RESTART)
     uint8_t hdr[1024];
-    const size_t hdr_len = jpezy_host::write_header(W, H, comment, hdr, sizeof hdr, nullptr, c->restart_interval, c->qt[0], c->qt[1]);
+    const size_t hdr_len = jpezy_host::write_header(W, H, comment, hdr, sizeof hdr, nullptr, c->restart_interval, c->qt[0], c->qt[1], sampling);
     if (!hdr_len) return set_err(JPEZY_E_BADARG, "write_jpeg_gpu_dev: comment too long");
     if (c->e_hdr_len != hdr_len || std::memcmp(c->e_hdr_host, hdr, hdr_len)) {
         if (int rc = c->e_hdr.reserve(sizeof hdr)) return rc;
@@ -305,11 +310,11 @@ int jpezy_write_jpeg_gpu_dev(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H
         std::memcpy(c->e_hdr_host, hdr, hdr_len);
         c->e_hdr_len = hdr_len;
     }
-    const int per = frames_per_pass(c, W, H, gray, n_frames);
-    const size_t cpf = jpezy_coeff_count(W, H, gray);
+    const int per = frames_per_pass(c, W, H, gray, n_frames, sampling);
+    const size_t cpf = sampling == JPEZY_SAMPLING_420 ? jpezy_coeff_count(W, H, gray) : jpezy_coeff_count_sampling(W, H, sampling);
     for (int f0 = 0; f0 < n_frames; f0 += per) {
         Pass p;
-        if (int rc = p.plan(c, d_coeffs + (size_t)f0 * cpf, W, H, gray, std::min(per, n_frames - f0), true, s)) return rc;
+        if (int rc = p.plan(c, d_coeffs + (size_t)f0 * cpf, W, H, gray, std::min(per, n_frames - f0), true, s, sampling)) return rc;
         if (int rc = p.code(false)) return rc;
         // files written (header, stuffed stream, EOI, size or verdict)
         E::FilePlan files;
@@ -321,8 +326,14 @@ int jpezy_write_jpeg_gpu_dev(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H
     return JPEZY_OK;
 }
 
-int jpezy_write_jpeg_gpu_batch(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H, int gray, int n_frames, const char* comment,
-                               uint8_t* out, size_t cap, long* sizes)
+int jpezy_write_jpeg_gpu_dev(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H, int gray, int n_frames, const char* comment,
+                             uint8_t* d_out, size_t out_stride, long long* d_sizes, void* stream)
+{
+    return jpezy_internal_write_jpeg_gpu_dev(c, d_coeffs, W, H, gray, JPEZY_SAMPLING_420, n_frames, comment, d_out, out_stride, d_sizes, stream);
+}
+
+int jpezy_internal_write_jpeg_gpu_batch(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H, int gray, int sampling, int n_frames, const char* comment,
+                                        uint8_t* out, size_t cap, long* sizes)
 try {
     if (int rc = jpezy_internal_check_dims(c, W, H, n_frames)) return rc;
     if (!d_coeffs || !out || !sizes) return set_err(JPEZY_E_BADARG, "write_jpeg_gpu: null pointer");
@@ -330,17 +341,23 @@ try {
     if (int rc = check_restart_comment(c, comment, "write_jpeg_gpu")) return rc;
     HIP_TRY(hipSetDevice(c->device));
     if (int rc = ensure_code_tables(c)) return rc;
-    const int per = frames_per_pass(c, W, H, gray, n_frames);
+    const int per = frames_per_pass(c, W, H, gray, n_frames, sampling);
     bool any_failed = false;
-    const size_t cpf = jpezy_coeff_count(W, H, gray);
+    const size_t cpf = sampling == JPEZY_SAMPLING_420 ? jpezy_coeff_count(W, H, gray) : jpezy_coeff_count_sampling(W, H, sampling);
     for (int f0 = 0; f0 < n_frames; f0 += per) {
         const int F = std::min(per, n_frames - f0);
-        if (int rc = entropy_chunk(c, d_coeffs + (size_t)f0 * cpf, W, H, gray, F, comment, out + (size_t)f0 * cap, cap, sizes + f0, &any_failed))
+        if (int rc = entropy_chunk(c, d_coeffs + (size_t)f0 * cpf, W, H, gray, F, comment, out + (size_t)f0 * cap, cap, sizes + f0, &any_failed, sampling))
             return rc;
     }
     return any_failed ? set_err(JPEZY_E_FORMAT, "write_jpeg_gpu: at least one frame failed (see sizes[])") : JPEZY_OK;
 }
 JPEZY_CATCH
+
+int jpezy_write_jpeg_gpu_batch(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H, int gray, int n_frames, const char* comment,
+                               uint8_t* out, size_t cap, long* sizes)
+{
+    return jpezy_internal_write_jpeg_gpu_batch(c, d_coeffs, W, H, gray, JPEZY_SAMPLING_420, n_frames, comment, out, cap, sizes);
+}
 
 long jpezy_write_jpeg_gpu(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H, int gray, const char* comment, uint8_t* out, size_t cap)
 {
@@ -374,24 +391,30 @@ int jpezy_ctx_restart_interval(const jpezy_ctx* c)
     return c->restart_interval;
 }
 
-int jpezy_huffman_histogram_dev(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H, int gray, int n_frames, unsigned long long* d_hist,
-                                void* stream)
+int jpezy_internal_huffman_histogram_dev(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H, int gray, int sampling, int n_frames,
+                                         unsigned long long* d_hist, void* stream)
 {
     namespace E = jpezy_dev::entropy;
     if (int rc = jpezy_internal_check_dims(c, W, H, n_frames)) return rc;
     if (!d_coeffs || !d_hist) return set_err(JPEZY_E_BADARG, "huffman_histogram_dev: null pointer");
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
-    const size_t cpf = jpezy_coeff_count(W, H, gray);
+    const size_t cpf = sampling == JPEZY_SAMPLING_420 ? jpezy_coeff_count(W, H, gray) : jpezy_coeff_count_sampling(W, H, sampling);
     for (int f0 = 0; f0 < n_frames; f0 += kMaxFramesPerLaunch) {
         const int F = std::min(kMaxFramesPerLaunch, n_frames - f0);
         if (c->e_hstat.cap < sizeof(unsigned) * (size_t)F)
             if (int rc = c->e_hstat.reserve(sizeof(unsigned) * (size_t)F)) return rc;
         E::Job job;
-        make_job(job, d_coeffs + (size_t)f0 * cpf, W, H, gray, F, nullptr, c->restart_interval);
+        make_job(job, d_coeffs + (size_t)f0 * cpf, W, H, gray, F, nullptr, c->restart_interval, sampling);
         if (int rc = enqueue_histogram(job, d_hist + (size_t)f0 * 4 * 256, c->e_hstat.as<unsigned>(), s)) return rc;
     }
     return JPEZY_OK;
+}
+
+int jpezy_huffman_histogram_dev(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H, int gray, int n_frames, unsigned long long* d_hist,
+                                void* stream)
+{
+    return jpezy_internal_huffman_histogram_dev(c, d_coeffs, W, H, gray, JPEZY_SAMPLING_420, n_frames, d_hist, stream);
 }
 
 int jpezy_huffman_optimal_table(const unsigned long long freq[256], uint8_t bits[16], uint8_t vals[256])

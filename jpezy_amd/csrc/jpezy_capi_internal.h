@@ -2,8 +2,8 @@
 // jpezy_capi.hip (context, the two transform stages), jpezy_capi_entropy.hip (Huffman coding: the host writer's entry points, the GPU
 // coder's two forms, encoder::encode end to end), jpezy_capi_huffdec.hip (GPU Huffman decoding of one file, decoder::decode end to end),
 // jpezy_capi_decode_batch.hip (the batch form), jpezy_capi_packed.hip (the entry points for packed, i.e. interleaved, pixels),
-// jpezy_capi_scaled.hip (reduced-size decode), jpezy_capi_ycc.hip (planar YCbCr 4:2:0 samples in and out), jpezy_capi_multi.hip (the
-// multi-GPU handle).
+// jpezy_capi_scaled.hip (reduced-size decode), jpezy_capi_ycc.hip (planar YCbCr 4:2:0 samples in and out), jpezy_capi_sampling.hip (chroma
+// sampling as an argument of the encoder's entries), jpezy_capi_multi.hip (the multi-GPU handle).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -260,6 +260,14 @@ JPEZY_INTERNAL int jpezy_internal_huffdec_streams(jpezy_ctx* c, const std::vecto
                                                   std::vector<char>& ok, const std::function<void(const char*)>& lap, bool per_lane = false);
 JPEZY_INTERNAL bool jpezy_internal_build_dev_setup(jpezy_dev::huffdec::Setup& S, const jpezy_host::ScanSetup& setup, const jpezy_frame_info& info, unsigned total_blocks);
 JPEZY_INTERNAL StreamGeom jpezy_internal_stream_geom(const jpezy_frame_info& info);
+// the GPU entropy coder's entries for a sampling (jpezy_capi_entropy.hip): jpezy_write_jpeg_gpu_dev / _batch and jpezy_huffman_histogram_dev
+// are these at JPEZY_SAMPLING_420; with JPEZY_SAMPLING_444 gray is 0 (the callers refuse it) and d_coeffs holds 3-block MCUs
+JPEZY_INTERNAL int jpezy_internal_write_jpeg_gpu_dev(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H, int gray, int sampling, int n_frames,
+                                                     const char* comment, uint8_t* d_out, size_t out_stride, long long* d_sizes, void* stream);
+JPEZY_INTERNAL int jpezy_internal_write_jpeg_gpu_batch(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H, int gray, int sampling, int n_frames,
+                                                       const char* comment, uint8_t* out, size_t cap, long* sizes);
+JPEZY_INTERNAL int jpezy_internal_huffman_histogram_dev(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H, int gray, int sampling, int n_frames,
+                                                        unsigned long long* d_hist, void* stream);
 }
 
 // ---- what the reduced-size and the region decode share (jpezy_capi_scaled.hip, jpezy_capi_region.hip) ----

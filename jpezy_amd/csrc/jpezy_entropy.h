@@ -24,11 +24,17 @@ struct Job {
     size_t coeffs_per_frame;      // int16 elements
     const CodeTables* tables;     // device
     size_t tables_stride = 0;     // frame f codes with tables[f * tables_stride]; 0: every frame with tables[0] (the Annex-K image)
-    unsigned blocks_per_frame;    // coded blocks: 6 per MCU (gray: the two chroma blocks are coded as zero blocks)
-    int bpm;                      // stored blocks per MCU: 6 colour, 4 gray
+    unsigned blocks_per_frame;    // coded blocks: `coded` per MCU (gray: the two chroma blocks are coded as zero blocks)
+    int bpm;                      // stored blocks per MCU: 6 colour, 4 gray; 3 for 4:4:4
     int n_frames;
     unsigned restart = 0;         // MCUs per restart interval that the DEVICE acts on: 0 for none, and 0 too for an interval that holds
                                   // the whole frame (no marker, no reset: only the header differs, and the host writes that)
+    // The MCU as a layout: `coded` blocks per MCU of which the first `luma` are luma blocks, then one block each of Cb and Cr; `bpm` of
+    // them are stored.  6 / 4 (bpm 6; gray: bpm 4) is 4:2:0, 3 / 1 (bpm 3) is 4:4:4.  DC predictors: the first luma block of an MCU predicts
+    // from the previous MCU's last luma block, a later luma block from the block before, a chroma block from the same index one MCU back.
+    // The kernels take the pair as TEMPLATE parameters (the launchers pick the instance): the 4:2:0 instances divide by constants as
+    // they always did.  (4:2:2 would be 4 / 2; not instantiated.)
+    int coded = 6, luma = 4;
 };
 
 // Worst-case bytes of a coded block, 64 x (16-bit code + 10 value bits): the stride of a block in a tile's stream and the unit of
@@ -41,20 +47,29 @@ inline size_t tiles256(size_t n) { return (n + 255) / 256; }
 // Tiles of a frame with restart intervals (Job::restart != 0): a tile never straddles an interval.  Every interval starts a tile of
 // its own and takes restart_tpi() tiles, all of 256 blocks but its last; the frame's last interval may hold fewer MCUs and so fewer
 // tiles.  Tile t: interval t / tpi, blocks [first, first + count) of the frame with first = (t / tpi) * 6 * restart + (t % tpi) * 256.
-__host__ __device__ inline unsigned restart_tpi(unsigned restart) { return (restart * 6u + 255u) / 256u; }
+// (CODED: coded blocks per MCU, Job::coded -- a template parameter where kernels call these)
+template <unsigned CODED = 6u>
+__host__ __device__ inline unsigned restart_tpi(unsigned restart) { return (restart * CODED + 255u) / 256u; }
+template <unsigned CODED = 6u>
 __host__ __device__ inline unsigned restart_tile_first(unsigned t, unsigned restart)
 {
-    const unsigned tpi = restart_tpi(restart);
-    return (t / tpi) * (restart * 6u) + (t % tpi) * 256u;
+    const unsigned tpi = restart_tpi<CODED>(restart);
+    return (t / tpi) * (restart * CODED) + (t % tpi) * 256u;
 }
-inline size_t restart_intervals(size_t blocks_per_frame, unsigned restart) { return (blocks_per_frame / 6 + restart - 1) / restart; }
-inline size_t restart_tiles(size_t blocks_per_frame, unsigned restart)
+inline unsigned restart_tpi_of(unsigned restart, unsigned coded) { return coded == 3u ? restart_tpi<3u>(restart) : restart_tpi<6u>(restart); }
+inline size_t restart_intervals(size_t blocks_per_frame, unsigned restart, unsigned coded = 6u) { return (blocks_per_frame / coded + restart - 1) / restart; }
+inline size_t restart_tiles(size_t blocks_per_frame, unsigned restart, unsigned coded = 6u)
 {
-    const size_t ni = restart_intervals(blocks_per_frame, restart);
-    return (ni - 1) * restart_tpi(restart) + tiles256(blocks_per_frame - (ni - 1) * restart * 6u);
+    const size_t ni = restart_intervals(blocks_per_frame, restart, coded);
+    return (ni - 1) * restart_tpi_of(restart, coded) + tiles256(blocks_per_frame - (ni - 1) * restart * coded);
 }
+// the layouts the kernels are instantiated for
+inline bool layout_ok(const Job& job) { return (job.coded == 6 && job.luma == 4 && (job.bpm == 6 || job.bpm == 4)) || (job.coded == 3 && job.luma == 1 && job.bpm == 3); }
 // tiles of a frame, either way
-inline size_t job_tiles(const Job& job) { return job.restart ? restart_tiles(job.blocks_per_frame, job.restart) : tiles256(job.blocks_per_frame); }
+inline size_t job_tiles(const Job& job)
+{
+    return job.restart ? restart_tiles(job.blocks_per_frame, job.restart, (unsigned)job.coded) : tiles256(job.blocks_per_frame);
+}
 
 // device-resident form of launch_stuff: whole files (header, stuffed stream, EOI), sizes and per-frame verdicts on the device
 struct FilePlan {

@@ -266,7 +266,10 @@ struct DirectWriter {
 // RST (Job::restart != 0): the tiles are those of restart_tiles() -- a tile never straddles a restart interval, so an interval's bits
 // are the bits of whole tiles, and the predictors of an interval's first MCU (lanes 0..5 of its first tile) are zero.  A tile's
 // stream starts at 52 words per block in front of it in the frame, which is where the plain layout has it too.
-template <bool RST>
+// CODED / LUMA: the MCU as a layout (Job::coded, Job::luma) -- 6 / 4 for 4:2:0 (gray included), 3 / 1 for 4:4:4.  With 3 blocks per MCU a
+// 256-block tile boundary falls inside an MCU (256 = 85 * 3 + 1): nothing special happens there, because a lane's predictor is read
+// from global memory wherever the block it names lies.
+template <bool RST, unsigned CODED = 6u, unsigned LUMA = 4u>
 __global__ __launch_bounds__(WG) void code_tiles_kernel(Job job, uint32_t* S, uint32_t* tile_total, unsigned* status)
 {
     __shared__ LdsTables L;
@@ -277,7 +280,7 @@ __global__ __launch_bounds__(WG) void code_tiles_kernel(Job job, uint32_t* S, ui
     unsigned g0, nb;                                                                  // first coded block of this tile, and how many
     bool interval_start = false;
     if constexpr (RST) {
-        const unsigned bpi = job.restart * 6u, tpi = restart_tpi(job.restart), iv = blockIdx.x / tpi, j = blockIdx.x - iv * tpi;
+        const unsigned bpi = job.restart * CODED, tpi = restart_tpi<CODED>(job.restart), iv = blockIdx.x / tpi, j = blockIdx.x - iv * tpi;
         const unsigned i0 = iv * bpi, ilen = nblk - i0 < bpi ? nblk - i0 : bpi;       // the interval's blocks: [i0, i0 + ilen)
         g0 = i0 + j * (unsigned)WG;
         nb = ilen - j * (unsigned)WG < (unsigned)WG ? ilen - j * (unsigned)WG : (unsigned)WG;
@@ -294,16 +297,16 @@ __global__ __launch_bounds__(WG) void code_tiles_kernel(Job job, uint32_t* S, ui
     int pred = 0, table = 0;
     const int16_t* zg = nullptr;
     if (valid) {
-        const unsigned g = g0 + tid, mcu = g / 6u, i = g - mcu * 6u;
-        table = i < 4 ? 0 : 1;
-        if (!(i >= 4 && job.bpm == 4)) {
+        const unsigned g = g0 + tid, mcu = g / CODED, i = g - mcu * CODED;
+        table = i < LUMA ? 0 : 1;
+        if (!(CODED == 6u && i >= 4 && job.bpm == 4)) {
             zg = fc + ((size_t)mcu * job.bpm + i) * 64;
-            if (i >= 1 && i <= 3) pred = zg[-64];
-            else if (RST ? !(interval_start && tid < 6u) : mcu != 0) pred = i == 0 ? zg[-(job.bpm - 3) * 64] : zg[-job.bpm * 64];
+            if (i >= 1 && i < LUMA) pred = zg[-64];
+            else if (RST ? !(interval_start && tid < CODED) : mcu != 0) pred = i == 0 ? zg[-(job.bpm - (int)(LUMA - 1u)) * 64] : zg[-job.bpm * 64];
         }
     }
     // the tile's stored blocks are contiguous in memory; row = the lane that codes the block
-    if (job.bpm == 6) {
+    if (CODED != 6u || job.bpm == 6) {
         const uint4* src = reinterpret_cast<const uint4*>(fc + (size_t)g0 * 64);
         for (unsigned c = tid; c < nb * 8u; c += WG)
             *reinterpret_cast<uint4*>(tile + (c >> 3) * ROW + ROW_DATA + (c & 7u) * 16u) = src[c];
@@ -435,6 +438,9 @@ __global__ __launch_bounds__(256) void tile_bases_kernel(const uint32_t* tile_to
 constexpr unsigned MIN_TILE_BITS = 42u * 32u + 20u;
 constexpr int ASM_WIN = 128;
 static_assert((unsigned)(ASM_WIN - 2) * MIN_TILE_BITS >= ASM_BITS, "assemble window too small for flat content");
+// 4:4:4 (Job::coded = 3): a flat MCU is 6 + 4 + 4 = 14 bits, 256 consecutive blocks hold at least 85 MCUs + the cheapest block: 1194 bits
+constexpr unsigned MIN_TILE_BITS_444 = 85u * 14u + 4u;
+static_assert((unsigned)(ASM_WIN - 2) * MIN_TILE_BITS_444 >= ASM_BITS, "assemble window too small for flat 4:4:4 content");
 // Per-image tables (Job::tables_stride != 0) can be shorter than Annex K: a table with one used symbol codes it in ONE bit, so a flat
 // block is at least 1 (DC) + 1 (EOB) = 2 bits and a full tile at least 512: the window is ASM_BITS / 512 + 2 = 258 tiles.
 constexpr unsigned MIN_TILE_BITS_ANY = 256u * 2u;
@@ -670,6 +676,7 @@ __global__ __launch_bounds__(256) void restart_bases_kernel(const uint32_t* tile
 // tile that holds p and from EVERY tile that starts inside it, one after the other.  A tile that ends an interval (every tpi-th,
 // except the frame's last) ends on a byte in B; if that byte lies in the chunk, a marker follows it: bit j of `marks` = behind byte
 // j, k7 = the number (mod 8) of the chunk's first marker.  Returns the bytes the stuffing pass adds: 0xFF bytes + 2 per marker.
+template <unsigned CODED>
 __device__ __forceinline__ unsigned assemble_chunk_restart(unsigned long long p, const unsigned long long* B, const uint32_t* tt, unsigned t,
                                                            unsigned tpf, unsigned tpi, unsigned restart, const uint32_t* Sf,
                                                            unsigned long long T, uint4* dst, unsigned long long& marks, unsigned& k7)
@@ -682,7 +689,7 @@ __device__ __forceinline__ unsigned assemble_chunk_restart(unsigned long long p,
     unsigned long long b = B[t];
     for (unsigned u = t; u < tpf && b < p + CHUNK * 8; ++u) {
         const unsigned long long e = B[u + 1];
-        const uint32_t* src = Sf + (size_t)restart_tile_first(u, restart) * (TILE_STREAM_WORDS / 256u);
+        const uint32_t* src = Sf + (size_t)restart_tile_first<CODED>(u, restart) * (TILE_STREAM_WORDS / 256u);
         // the tile's own bits: its total, not e - b -- a tile starts at any bit of U, so the pad up to a byte of U may reach into the
         // tile stream's next word, which nobody wrote
         const unsigned L = tt[u];
@@ -748,6 +755,7 @@ __device__ __forceinline__ unsigned assemble_chunk_restart(unsigned long long p,
 // restart_bases_kernel at every frame size.  A thread finds its chunk's tile by binary search in the offsets themselves, between
 // the first tile of its piece and the first tile of the next -- a handful of tiles, so two or three dependent loads, and no bound
 // on how many tiles a piece can touch is needed (there is none worth having: an interval's last tile may hold a single block).
+template <unsigned CODED>
 __global__ __launch_bounds__(256) void assemble_restart_kernel(const uint32_t* S, size_t s_frame_words, const uint32_t* tile_total,
                                                               const unsigned long long* base, const unsigned long long* bytes,
                                                               const uint32_t* first_tile, unsigned tpf, unsigned restart, unsigned ft_stride,
@@ -759,7 +767,7 @@ __global__ __launch_bounds__(256) void assemble_restart_kernel(const uint32_t* S
     const unsigned long long* B = base + (size_t)frame * (tpf + 1);
     const uint32_t* ft = first_tile + (size_t)frame * ft_stride;
     const unsigned long long nbytes = bytes[frame], T = B[tpf];
-    const unsigned tpi = restart_tpi(restart);
+    const unsigned tpi = restart_tpi<CODED>(restart);
     for (size_t x = blockIdx.x; x < pieces; x += gridDim.x) {
         const unsigned long long c0 = (unsigned long long)x * 256u, c = c0 + tid;
         if (x != 0 && c0 * CHUNK > nbytes) break;                       // (as assemble_kernel: the one-past-the-end chunk is written)
@@ -773,7 +781,7 @@ __global__ __launch_bounds__(256) void assemble_restart_kernel(const uint32_t* S
                 if (B[mid] <= p) lo = mid; else hi = mid;
             }
             uint4* dst = reinterpret_cast<uint4*>(U + (size_t)frame * u_stride_words) + c * (CHUNK / 16);
-            extra = assemble_chunk_restart(p, B, tile_total + (size_t)frame * tpf, lo, tpf, tpi, restart, S + (size_t)frame * s_frame_words, T,
+            extra = assemble_chunk_restart<CODED>(p, B, tile_total + (size_t)frame * tpf, lo, tpf, tpi, restart, S + (size_t)frame * s_frame_words, T,
                                            dst, marks, k7);
         }
         uint32_t total;
@@ -1084,7 +1092,7 @@ static bool assemble_scans_tiles_itself(const Job& job) { return !job.restart &&
 
 size_t stream_stride(const Job& job)
 {
-    const size_t worst = (size_t)job.blocks_per_frame * kMaxBlockBytes + (job.restart ? restart_intervals(job.blocks_per_frame, job.restart) : 0);
+    const size_t worst = (size_t)job.blocks_per_frame * kMaxBlockBytes + (job.restart ? restart_intervals(job.blocks_per_frame, job.restart, (unsigned)job.coded) : 0);
     return (worst + 8 + assemble_piece_bytes() - 1) / assemble_piece_bytes() * assemble_piece_bytes();
 }
 
@@ -1103,7 +1111,7 @@ ScratchSizes scratch_sizes(const Job& job, bool)
     z.tile_total = job_tiles(job) * F * sizeof(uint32_t);                                        //  streams where the blocks' would lie)
     z.tile_base = self ? 0 : (job_tiles(job) + 1) * F * sizeof(unsigned long long);
     z.first_tile = self ? 0 : pieces * F * sizeof(uint32_t);
-    z.restart_pad = job.restart ? restart_intervals(job.blocks_per_frame, job.restart) * F * sizeof(unsigned long long) : 0;
+    z.restart_pad = job.restart ? restart_intervals(job.blocks_per_frame, job.restart, (unsigned)job.coded) * F * sizeof(unsigned long long) : 0;
     z.bytes = F * sizeof(unsigned long long);
     z.U = u_stride * F;
     z.ff_loc = chunks * F * sizeof(uint32_t);
@@ -1116,14 +1124,17 @@ ScratchSizes scratch_sizes(const Job& job, bool)
 hipError_t launch_code_tiles(const Job& job, const Scratch& sc, hipStream_t s)
 {
     if (!job.blocks_per_frame || job.n_frames <= 0) return hipSuccess;
-    if (job.n_frames > 65535) return hipErrorInvalidValue;                       // the frame index is a grid dimension
+    if (job.n_frames > 65535 || !layout_ok(job)) return hipErrorInvalidValue;    // the frame index is a grid dimension
+    const unsigned coded = (unsigned)job.coded;
+    const dim3 grid((unsigned)job_tiles(job), (unsigned)job.n_frames);
     if (job.restart) {
-        if (job.restart > 65535u || job.blocks_per_frame % 6u || job.restart >= job.blocks_per_frame / 6u) return hipErrorInvalidValue;
-        hipLaunchKernelGGL(code_tiles_kernel<true>, dim3((unsigned)job_tiles(job), (unsigned)job.n_frames), dim3(WG), 0, s, job, sc.tile_stream,
-                           sc.tile_total, sc.status);
-    } else
-        hipLaunchKernelGGL(code_tiles_kernel<false>, dim3((unsigned)job_tiles(job), (unsigned)job.n_frames), dim3(WG), 0, s, job, sc.tile_stream,
-                           sc.tile_total, sc.status);
+        if (job.restart > 65535u || job.blocks_per_frame % coded || job.restart >= job.blocks_per_frame / coded) return hipErrorInvalidValue;
+        if (coded == 3u) hipLaunchKernelGGL((code_tiles_kernel<true, 3u, 1u>), grid, dim3(WG), 0, s, job, sc.tile_stream, sc.tile_total, sc.status);
+        else hipLaunchKernelGGL(code_tiles_kernel<true>, grid, dim3(WG), 0, s, job, sc.tile_stream, sc.tile_total, sc.status);
+    } else if (coded == 3u)
+        hipLaunchKernelGGL((code_tiles_kernel<false, 3u, 1u>), grid, dim3(WG), 0, s, job, sc.tile_stream, sc.tile_total, sc.status);
+    else
+        hipLaunchKernelGGL(code_tiles_kernel<false>, grid, dim3(WG), 0, s, job, sc.tile_stream, sc.tile_total, sc.status);
     return hipGetLastError();
 }
 
@@ -1131,9 +1142,10 @@ hipError_t launch_tile_bases(const Job& job, const Scratch& sc, hipStream_t s)
 {
     if (!job.blocks_per_frame || job.n_frames <= 0 || assemble_scans_tiles_itself(job)) return hipSuccess;
     if (job.restart) {
-        if (job.restart >= job.blocks_per_frame / 6u) return hipErrorInvalidValue;
+        if (!layout_ok(job) || job.restart >= job.blocks_per_frame / (unsigned)job.coded) return hipErrorInvalidValue;
         hipLaunchKernelGGL(restart_bases_kernel, dim3((unsigned)job.n_frames), dim3(256), 0, s, sc.tile_total, (unsigned)job_tiles(job),
-                           restart_tpi(job.restart), (unsigned)restart_intervals(job.blocks_per_frame, job.restart), sc.tile_base, sc.restart_pad,
+                           restart_tpi_of(job.restart, (unsigned)job.coded),
+                           (unsigned)restart_intervals(job.blocks_per_frame, job.restart, (unsigned)job.coded), sc.tile_base, sc.restart_pad,
                            sc.bytes, sc.first_tile, sc.ft_stride, sc.status, sc.latched);
     } else
         hipLaunchKernelGGL(tile_bases_kernel, dim3((unsigned)job.n_frames), dim3(256), 0, s, sc.tile_total, (unsigned)job_tiles(job), sc.tile_base,
@@ -1157,8 +1169,12 @@ hipError_t launch_assemble(const Job& job, const Scratch& sc, bool any_tables, h
         return hipGetLastError();
     }
     if (pieces > sc.ft_stride) return hipErrorInvalidValue;
-    if (job.restart)
-        hipLaunchKernelGGL(assemble_restart_kernel, grid, dim3(256), 0, s, sc.tile_stream, tiles256(job.blocks_per_frame) * (size_t)TILE_STREAM_WORDS,
+    if (job.restart && job.coded == 3)
+        hipLaunchKernelGGL(assemble_restart_kernel<3u>, grid, dim3(256), 0, s, sc.tile_stream, tiles256(job.blocks_per_frame) * (size_t)TILE_STREAM_WORDS,
+                           sc.tile_total, sc.tile_base, sc.bytes, sc.first_tile, tpf, job.restart, sc.ft_stride, sc.U, u_stride_words, sc.ff_loc,
+                           sc.ff_piece, sc.markers);
+    else if (job.restart)
+        hipLaunchKernelGGL(assemble_restart_kernel<6u>, grid, dim3(256), 0, s, sc.tile_stream, tiles256(job.blocks_per_frame) * (size_t)TILE_STREAM_WORDS,
                            sc.tile_total, sc.tile_base, sc.bytes, sc.first_tile, tpf, job.restart, sc.ft_stride, sc.U, u_stride_words, sc.ff_loc,
                            sc.ff_piece, sc.markers);
     else if (any_tables)

@@ -1,6 +1,7 @@
 // jpezy_f32_quad.h -- device code of ONE quad (64 x 16 pixels, 24 blocks) of the f32 encode path, shared by the one-quad-per-wave kernel
 // (jpezy_kernels_f32.hip, encode variant 1) and the persistent kernels (jpezy_kernels_f32_ps.hip, variants 2 and 3): the packed 8-point
 // transform, the colour estimates with their guard tests, the quantiser, levels 2 and 3, and encode_quad_compute / encode_quad_store.
+// The 4:4:4 kernel (jpezy_kernels_f32_444.hip: an octet of 8 x 8 MCUs per wave) calls the same pieces below encode_quad_compute.
 //
 // Level 1 (every coefficient): colour conversion as an FP32 estimate with a guard band (below), separable 8-point
 //   butterflies in FP32, written as PACKED FP32 instructions (v_pk_add/mul/fma_f32 with op_sel / neg modifiers: one

@@ -159,7 +159,8 @@ inline bool put_block(BitSink& o, const int16_t* z, int& pred, const EncLut& dc,
     return true;
 }
 
-void put_header(BitSink& o, int W, int H, const char* comment, const HuffTable* tabs, int restart, const uint8_t* luma, const uint8_t* chroma)
+void put_header(BitSink& o, int W, int H, const char* comment, const HuffTable* tabs, int restart, const uint8_t* luma, const uint8_t* chroma,
+                bool s444 = false)
 {
     static const uint8_t soi_app0[] = { 0xFF, 0xD8, 0xFF, 0xE0, 0x00, 0x10, 'J', 'F', 'I', 'F', 0x00,
                                         0x01, 0x02, 0x01, 0x00, 0x60, 0x00, 0x60, 0x00, 0x00 };
@@ -186,7 +187,7 @@ void put_header(BitSink& o, int W, int H, const char* comment, const HuffTable* 
         o.raw_n(vals, (size_t)nval);
     }
     const uint8_t sof[] = { 0xFF, 0xC0, 0x00, 0x11, 0x08, (uint8_t)(H >> 8), (uint8_t)H, (uint8_t)(W >> 8), (uint8_t)W,
-                            0x03, 0x00, 0x22, 0x00, 0x01, 0x11, 0x01, 0x02, 0x11, 0x01 };
+                            0x03, 0x00, (uint8_t)(s444 ? 0x11 : 0x22), 0x00, 0x01, 0x11, 0x01, 0x02, 0x11, 0x01 };   // 4:4:4: H, V = 1, 1 three times
     o.raw_n(sof, sizeof sof);
     if (restart > 0) {                                            // DRI: MCUs per restart interval, directly in front of SOS
         o.raw(0xFF); o.raw(0xDD); o.raw16(4); o.raw16((unsigned)restart);
@@ -209,11 +210,12 @@ bool restart_ok(int restart, const char* comment)
 }
 
 size_t write_header(int W, int H, const char* comment, uint8_t* out, size_t cap, const HuffTable* tabs, int restart, const uint8_t* luma,
-                    const uint8_t* chroma)
+                    const uint8_t* chroma, int sampling)
 {
     if (!comment_ok(comment) || !restart_ok(restart, comment)) return 0;
+    if (sampling != JPEZY_SAMPLING_420 && sampling != JPEZY_SAMPLING_444) return 0;
     BitSink o(out, cap);
-    put_header(o, W, H, comment, tabs, restart, luma, chroma);
+    put_header(o, W, H, comment, tabs, restart, luma, chroma, sampling == JPEZY_SAMPLING_444);
     return o.ok() ? o.size() : 0;
 }
 
@@ -246,6 +248,16 @@ size_t jpeg_bound(int W, int H)
     return 1024 + nmcu * 6 * 64 * 7;
 }
 
+size_t jpeg_bound_sampling(int W, int H, int sampling)
+{
+    if (sampling != JPEZY_SAMPLING_444) return jpeg_bound(W, H);
+    // The same derivation per 8 x 8 MCU of three blocks: kMaxMcuBits444 = 3 * 1661 = 4983 bits = 623 bytes, 1246 if every byte were
+    // 0xFF and stuffed; a restart interval per MCU adds at most 4 bytes (pad, stuffed pad, marker), the frame's own pad and EOI 4 once:
+    // inside the 98 bytes 1246 leaves of 1344 = 3 * 64 * 7.  The header is the 4:2:0 one with other sampling bytes: 1024 stands.
+    const size_t nmcu = (size_t)((W + 7) / 8) * (size_t)((H + 7) / 8);
+    return 1024 + nmcu * 3 * 64 * 7;
+}
+
 // ---- per-image optimised tables ----
 // The symbols of one block, as put_block emits them (out-of-range values: the clamped symbol, and false).
 namespace {
@@ -272,22 +284,39 @@ inline bool count_block(const int16_t* z, int& pred, unsigned long long* dc, uns
 }
 }  // namespace
 
-bool symbol_histogram(const int16_t* coeffs, int W, int H, bool gray, unsigned long long hist[4][256], int restart)
+// The scan as a layout (jpezy_host_codec.h, McuLayout): luma blocks share one predictor (the first luma block of an MCU predicts from the
+// previous MCU's last one, the later ones from the block before), chroma block i predicts from the same index one MCU back; blocks
+// that are coded but not stored are zero blocks.
+namespace {
+inline size_t layout_mcus(int W, int H, const McuLayout& L)
+{
+    return (size_t)((W + L.mcu_px - 1) / L.mcu_px) * (size_t)((H + L.mcu_px - 1) / L.mcu_px);
+}
+bool symbol_histogram_layout(const int16_t* coeffs, int W, int H, const McuLayout& L, unsigned long long hist[4][256], int restart)
 {
     static const int16_t kZeroBlock[64] = { 0 };
     std::memset(hist, 0, sizeof(unsigned long long) * 4 * 256);
-    const size_t nmcu = (size_t)((W + 15) / 16) * (size_t)((H + 15) / 16);
-    const int bpm = gray ? 4 : 6;
+    const size_t nmcu = layout_mcus(W, H, L);
     int pred[3] = { 0, 0, 0 };
     bool ok = true;
     for (size_t mcu = 0; mcu < nmcu; ++mcu) {
-        const int16_t* z = coeffs + mcu * (size_t)bpm * 64;
+        const int16_t* z = coeffs + mcu * (size_t)L.stored * 64;
         if (restart > 0 && mcu % (size_t)restart == 0) pred[0] = pred[1] = pred[2] = 0;     // as the writer resets them
-        for (int i = 0; i < 4; ++i) ok &= count_block(z + i * 64, pred[0], hist[0], hist[2]);
-        ok &= count_block(gray ? kZeroBlock : z + 256, pred[1], hist[1], hist[3]);
-        ok &= count_block(gray ? kZeroBlock : z + 320, pred[2], hist[1], hist[3]);
+        for (int i = 0; i < L.luma; ++i) ok &= count_block(z + i * 64, pred[0], hist[0], hist[2]);
+        for (int i = L.luma; i < L.coded; ++i) ok &= count_block(i < L.stored ? z + i * 64 : kZeroBlock, pred[1 + i - L.luma], hist[1], hist[3]);
     }
     return ok;
+}
+}  // namespace
+
+bool symbol_histogram(const int16_t* coeffs, int W, int H, bool gray, unsigned long long hist[4][256], int restart)
+{
+    return symbol_histogram_layout(coeffs, W, H, mcu_layout(JPEZY_SAMPLING_420, gray), hist, restart);
+}
+
+bool symbol_histogram_sampling(const int16_t* coeffs, int W, int H, int sampling, unsigned long long hist[4][256], int restart)
+{
+    return symbol_histogram_layout(coeffs, W, H, mcu_layout(sampling, false), hist, restart);
 }
 
 int optimal_table(const unsigned long long freq_in[256], uint8_t bits_out[16], uint8_t vals[256])
@@ -343,8 +372,9 @@ int optimal_table(const unsigned long long freq_in[256], uint8_t bits_out[16], u
     return nval;
 }
 
-long write_jpeg(const int16_t* coeffs, int W, int H, bool gray, const char* comment, int restart, bool optimize, uint8_t* out, size_t cap,
-                std::string* err, const uint8_t* luma, const uint8_t* chroma)
+namespace {
+long write_jpeg_layout(const int16_t* coeffs, int W, int H, const McuLayout& L, const char* comment, int restart, bool optimize, uint8_t* out,
+                       size_t cap, std::string* err, const uint8_t* luma, const uint8_t* chroma)
 {
     if (!coeffs || !out || W <= 0 || H <= 0 || W > 65535 || H > 65535) {
         if (err) *err = "write_jpeg: bad argument";
@@ -367,7 +397,7 @@ long write_jpeg(const int16_t* coeffs, int W, int H, bool gray, const char* comm
     std::optional<EncTables> own;
     if (optimize) {      // the frame's own tables, from the symbols THIS scan emits: the DC difference at an interval start is taken against 0
         unsigned long long hist[4][256];
-        if (!symbol_histogram(coeffs, W, H, gray, hist, restart)) {
+        if (!symbol_histogram_layout(coeffs, W, H, L, hist, restart)) {
             if (err) *err = "write_jpeg: coefficient outside the code tables";
             return JPEZY_E_FORMAT;
         }
@@ -377,23 +407,21 @@ long write_jpeg(const int16_t* coeffs, int W, int H, bool gray, const char* comm
     const EncTables& T = own ? *own : enc_tables();
 
     BitSink o(out, cap);
-    put_header(o, W, H, comment, optimize ? tabs : nullptr, restart, luma, chroma);
+    put_header(o, W, H, comment, optimize ? tabs : nullptr, restart, luma, chroma, L.mcu_px == 8);
 
     static const int16_t kZeroBlock[64] = { 0 };
-    const size_t nmcu = (size_t)((W + 15) / 16) * (size_t)((H + 15) / 16);
-    const int bpm = gray ? 4 : 6;
+    const size_t nmcu = layout_mcus(W, H, L);
     int pred[3] = { 0, 0, 0 };                                     // pre_DC: reset only at a restart interval's start
     for (size_t mcu = 0; mcu < nmcu; ++mcu) {
-        const int16_t* z = coeffs + mcu * (size_t)bpm * 64;
+        const int16_t* z = coeffs + mcu * (size_t)L.stored * 64;
         if (restart > 0 && mcu != 0 && mcu % (size_t)restart == 0) {
             // behind every interval but the last: pad to a byte (JPEZY_PAD_BIT, a padded 0xFF stuffed), then RSTn, never stuffed
             o.raw(0xFF); o.raw(0xD0 + (unsigned)((mcu / (size_t)restart - 1) & 7));
             pred[0] = pred[1] = pred[2] = 0;
         }
         bool good = true;
-        for (int i = 0; i < 4; ++i) good &= put_block(o, z + i * 64, pred[0], T.t[0], T.t[2]);
-        good &= put_block(o, gray ? kZeroBlock : z + 256, pred[1], T.t[1], T.t[3]);
-        good &= put_block(o, gray ? kZeroBlock : z + 320, pred[2], T.t[1], T.t[3]);
+        for (int i = 0; i < L.luma; ++i) good &= put_block(o, z + i * 64, pred[0], T.t[0], T.t[2]);
+        for (int i = L.luma; i < L.coded; ++i) good &= put_block(o, i < L.stored ? z + i * 64 : kZeroBlock, pred[1 + i - L.luma], T.t[1], T.t[3]);
         if (!good) {
             if (err) *err = "write_jpeg: coefficient outside the Annex-K code tables";
             return JPEZY_E_FORMAT;
@@ -406,6 +434,23 @@ long write_jpeg(const int16_t* coeffs, int W, int H, bool gray, const char* comm
         return JPEZY_E_NOSPACE;
     }
     return (long)o.size();
+}
+}  // namespace
+
+long write_jpeg(const int16_t* coeffs, int W, int H, bool gray, const char* comment, int restart, bool optimize, uint8_t* out, size_t cap,
+                std::string* err, const uint8_t* luma, const uint8_t* chroma)
+{
+    return write_jpeg_layout(coeffs, W, H, mcu_layout(JPEZY_SAMPLING_420, gray), comment, restart, optimize, out, cap, err, luma, chroma);
+}
+
+long write_jpeg_sampling(const int16_t* coeffs, int W, int H, int sampling, const char* comment, int restart, bool optimize, uint8_t* out,
+                         size_t cap, std::string* err, const uint8_t* luma, const uint8_t* chroma)
+{
+    if (sampling != JPEZY_SAMPLING_420 && sampling != JPEZY_SAMPLING_444) {
+        if (err) *err = "write_jpeg: unknown sampling";
+        return JPEZY_E_BADARG;
+    }
+    return write_jpeg_layout(coeffs, W, H, mcu_layout(sampling, false), comment, restart, optimize, out, cap, err, luma, chroma);
 }
 
 // ======================================================================================================

@@ -28,7 +28,8 @@ struct LdsHist {
 };
 static_assert((unsigned long long)HB * 64ull < (1ull << 32), "a workgroup's bin cannot overflow 32 bits");
 
-template <bool RST>
+// CODED / LUMA: the MCU as a layout (Job::coded, Job::luma; jpezy_entropy.h) -- 6 / 4 for 4:2:0 (gray: 4 of the 6 stored), 3 / 1 for 4:4:4
+template <bool RST, unsigned CODED = 6u, unsigned LUMA = 4u>
 __global__ __launch_bounds__(HWG) void symbol_histogram_kernel(Job job, unsigned long long* hist, unsigned* status)
 {
     __shared__ LdsHist L;
@@ -39,7 +40,7 @@ __global__ __launch_bounds__(HWG) void symbol_histogram_kernel(Job job, unsigned
     __syncthreads();
 
     const unsigned bpm = (unsigned)job.bpm;
-    const unsigned nstored = job.blocks_per_frame / 6u * bpm;                      // blocks the frame holds in memory
+    const unsigned nstored = job.blocks_per_frame / CODED * bpm;                   // blocks the frame holds in memory
     const int16_t* fc = job.coeffs + (size_t)frame * job.coeffs_per_frame;
     const unsigned w0 = blockIdx.x * HB + wave * (HB / 4);                         // this wave's blocks: [w0, w1)
     const unsigned w1 = w0 + HB / 4 < nstored ? w0 + HB / 4 : nstored;
@@ -57,8 +58,8 @@ __global__ __launch_bounds__(HWG) void symbol_histogram_kernel(Job job, unsigned
                 // lane 0: the DC predictor as code_tiles_kernel reads it -- the previous block of the component, 0 for the frame's first
                 const unsigned mcu = sb / bpm, i = sb - mcu * bpm;
                 if (lane == 0) {
-                    if (i >= 1 && i <= 3) pred[j] = z[-64];
-                    else if (mcu != 0 && !(RST && mcu % job.restart == 0u)) pred[j] = i == 0 ? z[-(int)(bpm - 3) * 64] : z[-(int)bpm * 64];
+                    if (i >= 1 && i < LUMA) pred[j] = z[-64];
+                    else if (mcu != 0 && !(RST && mcu % job.restart == 0u)) pred[j] = i == 0 ? z[-(int)(bpm - (LUMA - 1u)) * 64] : z[-(int)bpm * 64];
                 }
             }
         }
@@ -66,7 +67,7 @@ __global__ __launch_bounds__(HWG) void symbol_histogram_kernel(Job job, unsigned
         for (int j = 0; j < HBATCH; ++j) {
             const unsigned sb = b0 + j;
             if (sb >= w1) break;
-            const unsigned i = sb % bpm, t = i < 4 ? 0u : 1u;
+            const unsigned i = sb % bpm, t = i < LUMA ? 0u : 1u;
             const unsigned long long nz = __builtin_amdgcn_ballot_w64(v[j] != 0) & ~1ull;      // bit n: AC position n is non-zero
             if (lane == 0) {
                 const int diff = v[j] - pred[j];
@@ -96,7 +97,7 @@ __global__ __launch_bounds__(HWG) void symbol_histogram_kernel(Job job, unsigned
         unsigned long long c = bins[i];
         // bins[0..32): dc[t][cat] -> table t; bins[32..544): ac[t][sym] -> table 2 + t
         const unsigned k = i < 32u ? i >> 4 : 2u + ((i - 32u) >> 8), sym = i < 32u ? i & 15u : (i - 32u) & 255u;
-        if (bpm == 4u && blockIdx.x == 0 && sym == 0u && (k == 1u || k == 3u)) c += 2ull * (job.blocks_per_frame / 6u);
+        if (CODED == 6u && bpm == 4u && blockIdx.x == 0 && sym == 0u && (k == 1u || k == 3u)) c += 2ull * (job.blocks_per_frame / 6u);
         if (c) atomicAdd(H + k * 256u + sym, c);
     }
 }
@@ -104,12 +105,16 @@ __global__ __launch_bounds__(HWG) void symbol_histogram_kernel(Job job, unsigned
 hipError_t launch_symbol_histogram(const Job& job, unsigned long long* hist, unsigned* status, hipStream_t s)
 {
     if (!job.blocks_per_frame || job.n_frames <= 0) return hipSuccess;
-    if (job.n_frames > 65535 || (job.bpm != 4 && job.bpm != 6) || job.blocks_per_frame % 6u) return hipErrorInvalidValue;
-    const unsigned nstored = job.blocks_per_frame / 6u * (unsigned)job.bpm;
-    if (job.restart)
-        hipLaunchKernelGGL(symbol_histogram_kernel<true>, dim3((nstored + HB - 1) / HB, (unsigned)job.n_frames), dim3(HWG), 0, s, job, hist, status);
+    if (job.n_frames > 65535 || !layout_ok(job) || job.blocks_per_frame % (unsigned)job.coded) return hipErrorInvalidValue;
+    const unsigned nstored = job.blocks_per_frame / (unsigned)job.coded * (unsigned)job.bpm;
+    const dim3 grid((nstored + HB - 1) / HB, (unsigned)job.n_frames);
+    if (job.coded == 3) {
+        if (job.restart) hipLaunchKernelGGL((symbol_histogram_kernel<true, 3u, 1u>), grid, dim3(HWG), 0, s, job, hist, status);
+        else hipLaunchKernelGGL((symbol_histogram_kernel<false, 3u, 1u>), grid, dim3(HWG), 0, s, job, hist, status);
+    } else if (job.restart)
+        hipLaunchKernelGGL(symbol_histogram_kernel<true>, grid, dim3(HWG), 0, s, job, hist, status);
     else
-        hipLaunchKernelGGL(symbol_histogram_kernel<false>, dim3((nstored + HB - 1) / HB, (unsigned)job.n_frames), dim3(HWG), 0, s, job, hist, status);
+        hipLaunchKernelGGL(symbol_histogram_kernel<false>, grid, dim3(HWG), 0, s, job, hist, status);
     return hipGetLastError();
 }
 

@@ -819,6 +819,83 @@ long jpezy_encode_jpeg_sampling(jpezy_ctx* ctx, const uint8_t* r, const uint8_t*
 long jpezy_encode_jpeg_sampling_packed(jpezy_ctx* ctx, const uint8_t* pix, int format, size_t row_stride, int W, int H, int sampling,
                                        int gray, const char* comment, uint8_t* out, size_t cap);
 
+/*
+ * LOSSLESS TRANSFORMS: flip, rotate, transpose of a picture in the COEFFICIENT domain (what jpegtran -rotate / -flip / -transpose and
+ * tjTransform do).  A caller with a .jpg that is to stand upright, mirrored or transposed needs no pixel: every output coefficient is an
+ * input coefficient, possibly negated, so nothing is decoded to samples, nothing is quantised again and no generation of quality is lost.
+ * The reference has no such mode; the definition is this project's own (restated in tests/transform_model.py).
+ *
+ *   Operations    libjpeg's JXFORM order; (x', y') an output pixel, W x H the (trimmed) source size:
+ *                     op                        source pixel        out size  swap  mirror_x  mirror_y
+ *                     0 JPEZY_XFORM_NONE        (x', y')            W x H     0     0         0
+ *                     1 JPEZY_XFORM_HFLIP       (W-1-x', y')        W x H     0     1         0
+ *                     2 JPEZY_XFORM_VFLIP       (x', H-1-y')        W x H     0     0         1
+ *                     3 JPEZY_XFORM_TRANSPOSE   (y', x')            H x W     1     0         0
+ *                     4 JPEZY_XFORM_TRANSVERSE  (W-1-y', H-1-x')    H x W     1     1         1
+ *                     5 JPEZY_XFORM_ROT90       (y', H-1-x')        H x W     1     0         1      (clockwise)
+ *                     6 JPEZY_XFORM_ROT180      (W-1-x', H-1-y')    W x H     0     1         1
+ *                     7 JPEZY_XFORM_ROT270      (W-1-y', x')        H x W     1     1         0      (clockwise)
+ *                 mirror_x / mirror_y: the SOURCE axis that is mirrored; swap: the axes change places.
+ *   Blocks        per component plane, block grid Gc x Gr over the used source MCUs C x R (4:2:0 luma: 2C x 2R; 4:2:0 chroma and every
+ *                 4:4:4 plane: C x R): output block (bx', by') is source block (sx, sy) = swap ? (by', bx') : (bx', by'), then
+ *                 sx = Gc-1-sx if mirror_x, then sy = Gr-1-sy if mirror_y.  The output's MCU grid is C x R (R x C with swap) and its MCUs
+ *                 hold their blocks in the writer's order: 4:2:0 Y00 Y01 Y10 Y11 Cb Cr, luma block (bx, by) being block 2*(by&1) + (bx&1) of
+ *                 MCU (bx>>1, by>>1); 4:4:4 Y Cb Cr.
+ *   Coefficients  natural order, v the vertical and u the horizontal frequency: out[v][u] = s * in[vs][us], (vs, us) = swap ? (u, v) : (v, u),
+ *                 s = -1 when mirror_x * us + mirror_y * vs is odd.  In the buffers' zig-zag order that is one fixed permutation and a
+ *                 64-bit sign mask per operation.  The DC never changes sign.  Negation is int16 two's complement: -32768 stays -32768 (no
+ *                 decoded file has such an AC value; the device entry takes any int16).
+ *   Tables        the quantiser tables travel with the coefficients: with swap the output's are the transposes, Q'[v][u] = Q[u][v]
+ *                 (jpezy_quant_tables_transform; the Annex-K tables are not symmetric).
+ *   Edges         m = 16 (4:2:0) or 8 (4:4:4).  A MIRRORED source axis whose length is no multiple of m would put the padding on the
+ *                 leading edge: with flags = 0 that is JPEZY_E_UNSUPPORTED (the message names the axis and the multiple); with
+ *                 JPEZY_XFORM_TRIM the partial MCU column / row is dropped, the length becomes floor(len / m) * m, and if nothing is left
+ *                 the call is JPEZY_E_BADARG.  An axis that is not mirrored keeps its length and its partial MCU (TRANSPOSE never trims).
+ *                 C, R are the MCU counts of the trimmed size; the source buffer keeps its own row pitch of mcu_cols(W).
+ *   Files         jpezy_transform_jpeg accepts SOF0, 8 bit, three components sampled 2x2, 1x1, 1x1 or 1x1, 1x1, 1x1 (the layouts the
+ *                 writer writes), every used quantiser entry in 1..255, Cb and Cr with tables of equal CONTENTS (ids may differ).  Y's
+ *                 table goes out as table 0, the chroma table as table 1 (one table for all three: written twice).  The source's restart
+ *                 interval and Huffman tables are read and not carried over.  Everything else -- one component, 4:2:2 and other factors,
+ *                 a 16-bit DQT, precision other than 8, different Cb / Cr tables -- is JPEZY_E_UNSUPPORTED with the reason named, and the
+ *                 context stays usable.  A coefficient outside the writer's code tables is the writer's JPEZY_E_FORMAT.
+ *   Output file   the existing writer's file (jpezy_write_jpeg_sampling) for the output size and sampling: the (transposed) source tables
+ *                 in DQT; the context's jpezy_ctx_set_huffman_optimize and jpezy_ctx_set_restart_interval settings, the interval counted in
+ *                 OUTPUT MCUs; the context's own quantiser setting is NOT used and NOT changed; comment NULL carries the source's COM text
+ *                 over (as jpezy_frame_info keeps it: at most 255 bytes), "" writes none.
+ *   NOT carried   APPn segments (EXIF, ICC) and the JFIF density fields: the header is the writer's.  The orientation tag is not read.
+ *   With JPEZY_XFORM_NONE the same path is lossless recompression: a file re-coded with per-image Huffman tables or restart intervals, not
+ *                 one coefficient changed.
+ *
+ * NOT provided: 4:2:2 and other layouts; one-component files; cropping in the coefficient domain; the multi-GPU handle; a batch form of
+ * jpezy_transform_jpeg (jpezy_coeff_transform_dev takes n_frames).
+ */
+enum jpezy_xform {
+    JPEZY_XFORM_NONE = 0, JPEZY_XFORM_HFLIP = 1, JPEZY_XFORM_VFLIP = 2, JPEZY_XFORM_TRANSPOSE = 3, JPEZY_XFORM_TRANSVERSE = 4,
+    JPEZY_XFORM_ROT90 = 5, JPEZY_XFORM_ROT180 = 6, JPEZY_XFORM_ROT270 = 7
+};
+#define JPEZY_XFORM_TRIM 1      /* flags: drop the partial MCU column / row of a mirrored axis */
+/* The edge rule alone (pure host function): Wout x Hout = the output's size, src_cols x src_rows = C x R, the source MCUs that are used.
+ * Any output pointer may be NULL.  JPEZY_E_BADARG: op outside 0..7, unknown flag bits, unknown sampling, a size outside 1..65535, nothing
+ * left after trimming; JPEZY_E_UNSUPPORTED: a mirrored axis with a partial MCU and no JPEZY_XFORM_TRIM. */
+int jpezy_transform_geometry(int op, int flags, int W, int H, int sampling, int* Wout, int* Hout, int* src_cols, int* src_rows);
+/* The kernel on device memory (jpezy_kernels_transform.hip): n_frames coefficient fields of a W x H picture (jpezy_coeff_count_sampling(W,
+ * H, sampling) elements each, consecutive) from d_in to d_out (jpezy_coeff_count_sampling(Wout, Hout, sampling) elements each).  d_out is
+ * a DIFFERENT buffer: overlapping ranges are JPEZY_E_BADARG, as are pointers that are not 16-byte aligned.  Asynchronous on `stream` and
+ * capturable: it neither allocates nor synchronises, and touches no state of the context.  Any n_frames > 0 (launches of at most 65535
+ * frames).  Arguments are checked before the context is looked at. */
+int jpezy_coeff_transform_dev(jpezy_ctx* ctx, const int16_t* d_in, int W, int H, int sampling, int op, int flags, int n_frames, int16_t* d_out,
+                              void* stream);
+/* Q'[v][u] = Q[u][v] for the operations with swap, a copy for the others (pure host function; natural order; in == out is allowed). */
+int jpezy_quant_tables_transform(int op, const uint8_t in[64], uint8_t out[64]);
+/* A .jpg in, the transformed .jpg out: the header on the host, the scan through the path jpezy_read_jpeg_gpu takes (the host decoder below
+ * jpezy_ctx_set_huffdec_min_bytes and for irregular streams, as there), the transform kernel, the GPU entropy coder.  Returns the bytes
+ * written or a negative status.  out_info receives the OUTPUT's header fields (size, MCU grid, tables, restart interval, comment).
+ * out == NULL: header and geometry only (returns 0).  A cap of jpezy_jpeg_bound_sampling(Wout, Hout, sampling) is always enough; a smaller
+ * one that does not hold the file is JPEZY_E_NOSPACE and nothing is written past it.  Synchronous; the second coefficient buffer lives in
+ * the context, and the rule of the entropy entry points (one call in flight per context) applies. */
+long jpezy_transform_jpeg(jpezy_ctx* ctx, const uint8_t* data, size_t len, int op, int flags, const char* comment, jpezy_frame_info* out_info,
+                          uint8_t* out, size_t cap);
+
 #ifdef __cplusplus
 }
 #endif

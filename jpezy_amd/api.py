@@ -160,6 +160,11 @@ ABI = [
     ("jpezy_encode_jpeg_sampling", C.c_long, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, _vp, C.c_size_t]),
     ("jpezy_encode_jpeg_sampling_packed", C.c_long, [_vp, _vp, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, _vp,
                                                      C.c_size_t]),
+    ("jpezy_transform_geometry", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                           C.POINTER(C.c_int)]),
+    ("jpezy_coeff_transform_dev", C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]),
+    ("jpezy_quant_tables_transform", C.c_int, [C.c_int, _vp, _vp]),
+    ("jpezy_transform_jpeg", C.c_long, [_vp, _vp, C.c_size_t, C.c_int, C.c_int, C.c_char_p, C.POINTER(FrameInfo), _vp, C.c_size_t]),
 ]
 
 # chroma sampling of the encoder's *_sampling entry points: 4:2:0 (the reference's 2x2 / 1x1 / 1x1, everything as without the keyword)
@@ -168,6 +173,11 @@ SAMPLING_420, SAMPLING_444 = 0, 1
 
 # enum jpezy_pixel_format: packed (interleaved) pixels, 3 or 4 bytes each
 PIX_RGB24, PIX_BGR24, PIX_RGBA32, PIX_BGRA32 = 0, 1, 2, 3
+
+# enum jpezy_xform: lossless transforms in the coefficient domain (libjpeg's JXFORM order), and the flag that lets a mirrored axis drop its
+# partial MCU column / row
+XFORM_NONE, XFORM_HFLIP, XFORM_VFLIP, XFORM_TRANSPOSE, XFORM_TRANSVERSE, XFORM_ROT90, XFORM_ROT180, XFORM_ROT270 = range(8)
+XFORM_TRIM = 1
 
 
 def pixel_bytes(fmt):
@@ -264,6 +274,22 @@ def _rect(region):
 def region_check(W, H, scale, region):
     """raises JpezyError unless region = (x, y, w, h) lies inside a W x H file decoded at 1/scale, i.e. inside scaled_size(W, H, scale)"""
     _check(load_library().jpezy_region_check(int(W), int(H), int(scale), C.byref(_rect(region))))
+
+
+def transform_geometry(op, W, H, sampling=SAMPLING_420, trim=False):
+    """(Wout, Hout, src_cols, src_rows) of the lossless transform op (XFORM_*) of a W x H picture: the output's size and the source MCUs
+    that are used; a mirrored axis with a partial MCU raises unless trim"""
+    v = [C.c_int() for _ in range(4)]
+    _check(load_library().jpezy_transform_geometry(int(op), XFORM_TRIM if trim else 0, int(W), int(H), int(sampling), *(C.byref(x) for x in v)))
+    return tuple(x.value for x in v)
+
+
+def quant_tables_transform(op, table):
+    """the quantiser table (64 entries, natural order) of the transformed file: the transpose for the operations that swap the axes"""
+    t = _table(table, "quant_tables_transform")
+    out = np.zeros(64, np.uint8)
+    _check(load_library().jpezy_quant_tables_transform(int(op), _np_ptr(t), _np_ptr(out)))
+    return out
 
 
 def ycc_chroma_size(W, H):
@@ -912,6 +938,34 @@ class Context:
             return
         stride = plane_stride if plane_stride is not None else rect.w * rect.h
         _check(load_library().jpezy_dequant_idct_region_dev(*head, n_frames, stride, d_r.data_ptr(), d_g.data_ptr(), d_b.data_ptr(), stream))
+
+    # ---- lossless transforms in the coefficient domain (include/jpezy_hip.h, LOSSLESS TRANSFORMS) ----
+    def transform_jpeg(self, data, op, trim=False, comment=None):
+        """.jpg bytes -> (.jpg bytes of the flipped / rotated / transposed picture, FrameInfo of the output): GPU Huffman decoder,
+        transform kernel, GPU entropy coder; no pixel is computed.  op: XFORM_*; trim: drop the partial MCU column / row of a mirrored
+        axis; comment None: the source's COM text is carried over, b"": none.  The context's set_huffman_optimize and
+        set_restart_interval settings act; its quantiser setting does not."""
+        lib = load_library()
+        arr = np.frombuffer(bytes(data), dtype=np.uint8)
+        info = FrameInfo()
+        flags = XFORM_TRIM if trim else 0
+        _check(lib.jpezy_transform_jpeg(self._h, _np_ptr(arr), arr.size, int(op), flags, comment, C.byref(info), None, 0))
+        cap = jpeg_bound(info.width, info.height, SAMPLING_444 if info.H[0] == 1 else SAMPLING_420)
+        buf = np.empty(cap, dtype=np.uint8)
+        n = _check(lib.jpezy_transform_jpeg(self._h, _np_ptr(arr), arr.size, int(op), flags, comment, C.byref(info), _np_ptr(buf), cap))
+        return buf[:n].tobytes(), info
+
+    def coeff_transform_dev(self, d_in, W, H, d_out, op, trim=False, sampling=SAMPLING_420, n_frames=1, stream=None):
+        """Asynchronous: n_frames coefficient fields of a W x H picture (torch int16 tensors on the device) from d_in to a different
+        tensor d_out, which holds coeff_count(Wout, Hout, sampling=) elements per frame (transform_geometry)"""
+        import torch
+        if stream is None:
+            stream = torch.cuda.current_stream(d_in.device).cuda_stream
+        wo, ho, _, _ = transform_geometry(op, W, H, sampling, trim)
+        if d_in.numel() < n_frames * coeff_count(W, H, sampling=sampling) or d_out.numel() < n_frames * coeff_count(wo, ho, sampling=sampling):
+            raise JpezyError("coeff_transform_dev: d_in / d_out are smaller than n_frames fields of the source / output size")
+        _check(load_library().jpezy_coeff_transform_dev(self._h, d_in.data_ptr(), int(W), int(H), int(sampling), int(op), XFORM_TRIM if trim else 0,
+                                                        int(n_frames), d_out.data_ptr(), stream))
 
 
 # ---- host serial tail / head ----

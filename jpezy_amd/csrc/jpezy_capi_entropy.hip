@@ -198,7 +198,7 @@ int enqueue_histogram(const jpezy_dev::entropy::Job& job, unsigned long long* d_
 
 // one pass of the host-delivered form
 int entropy_chunk(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H, int gray, int F, const char* comment, uint8_t* out,
-                  size_t cap, long* sizes, bool* any_failed, int sampling)
+                  size_t cap, long* sizes, bool* any_failed, int sampling, const uint8_t* luma, const uint8_t* chroma)
 {
     namespace E = jpezy_dev::entropy;
     hipStream_t s = c->stream;
@@ -260,7 +260,7 @@ int entropy_chunk(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H, int gray,
         for (int f = f0; f < F; f += step) {
             uint8_t* dst = out + (size_t)f * cap;
             if (status[f]) { sizes[f] = JPEZY_E_FORMAT; failed.store(1); continue; }
-            const size_t hdr = jpezy_host::write_header(W, H, comment, dst, cap, optimize ? &tabs[(size_t)f * 4] : nullptr, c->restart_interval, c->qt[0], c->qt[1], sampling);
+            const size_t hdr = jpezy_host::write_header(W, H, comment, dst, cap, optimize ? &tabs[(size_t)f * 4] : nullptr, c->restart_interval, luma, chroma, sampling);
             const size_t body = (size_t)(nbytes[f] + fftot[f]);
             if (!hdr || hdr + body + 2 > cap) { sizes[f] = JPEZY_E_NOSPACE; failed.store(1); continue; }
             std::memcpy(dst + hdr, c->e_pinned.p + (size_t)f * o_stride, body);
@@ -284,7 +284,7 @@ int entropy_chunk(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H, int gray,
 // The three GPU writers and the histogram for a sampling (jpezy_capi_sampling.hip; JPEZY_SAMPLING_420: the public entries below).
 // Device-resident, asynchronous variant: everything is enqueued on `stream`, nothing is copied to the host.
 int jpezy_internal_write_jpeg_gpu_dev(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H, int gray, int sampling, int n_frames, const char* comment,
-                                      uint8_t* d_out, size_t out_stride, long long* d_sizes, void* stream)
+                                      uint8_t* d_out, size_t out_stride, long long* d_sizes, void* stream, const uint8_t* luma, const uint8_t* chroma)
 {
     namespace E = jpezy_dev::entropy;
     if (int rc = jpezy_internal_check_dims(c, W, H, n_frames)) return rc;
@@ -301,7 +301,8 @@ int jpezy_internal_write_jpeg_gpu_dev(jpezy_ctx* c, const int16_t* d_coeffs, int
     // header bytes: cached on the device per (W, H, comment, restart interval, quantisation tables: the bytes are compared) -- uploaded outside any capture on first use; 1024 bytes hold the
     // header with the longest comment allowed (JPEZY_MAX_COMMENT; with a DRI segment JPEZY_MAX_COMMENT_RESTART)
     uint8_t hdr[1024];
-    const size_t hdr_len = jpezy_host::write_header(W, H, comment, hdr, sizeof hdr, nullptr, c->restart_interval, c->qt[0], c->qt[1], sampling);
+    const size_t hdr_len = jpezy_host::write_header(W, H, comment, hdr, sizeof hdr, nullptr, c->restart_interval, luma ? luma : c->qt[0],
+                                                    chroma ? chroma : c->qt[1], sampling);
     if (!hdr_len) return set_err(JPEZY_E_BADARG, "write_jpeg_gpu_dev: comment too long");
     if (c->e_hdr_len != hdr_len || std::memcmp(c->e_hdr_host, hdr, hdr_len)) {
         if (int rc = c->e_hdr.reserve(sizeof hdr)) return rc;
@@ -333,7 +334,7 @@ int jpezy_write_jpeg_gpu_dev(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H
 }
 
 int jpezy_internal_write_jpeg_gpu_batch(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H, int gray, int sampling, int n_frames, const char* comment,
-                                        uint8_t* out, size_t cap, long* sizes)
+                                        uint8_t* out, size_t cap, long* sizes, const uint8_t* luma, const uint8_t* chroma)
 try {
     if (int rc = jpezy_internal_check_dims(c, W, H, n_frames)) return rc;
     if (!d_coeffs || !out || !sizes) return set_err(JPEZY_E_BADARG, "write_jpeg_gpu: null pointer");
@@ -346,7 +347,8 @@ try {
     const size_t cpf = sampling == JPEZY_SAMPLING_420 ? jpezy_coeff_count(W, H, gray) : jpezy_coeff_count_sampling(W, H, sampling);
     for (int f0 = 0; f0 < n_frames; f0 += per) {
         const int F = std::min(per, n_frames - f0);
-        if (int rc = entropy_chunk(c, d_coeffs + (size_t)f0 * cpf, W, H, gray, F, comment, out + (size_t)f0 * cap, cap, sizes + f0, &any_failed, sampling))
+        if (int rc = entropy_chunk(c, d_coeffs + (size_t)f0 * cpf, W, H, gray, F, comment, out + (size_t)f0 * cap, cap, sizes + f0, &any_failed, sampling,
+                                   luma ? luma : c->qt[0], chroma ? chroma : c->qt[1]))
             return rc;
     }
     return any_failed ? set_err(JPEZY_E_FORMAT, "write_jpeg_gpu: at least one frame failed (see sizes[])") : JPEZY_OK;

@@ -3,7 +3,8 @@
 // coder's two forms, encoder::encode end to end), jpezy_capi_huffdec.hip (GPU Huffman decoding of one file, decoder::decode end to end),
 // jpezy_capi_decode_batch.hip (the batch form), jpezy_capi_packed.hip (the entry points for packed, i.e. interleaved, pixels),
 // jpezy_capi_scaled.hip (reduced-size decode), jpezy_capi_ycc.hip (planar YCbCr 4:2:0 samples in and out), jpezy_capi_sampling.hip (chroma
-// sampling as an argument of the encoder's entries), jpezy_capi_multi.hip (the multi-GPU handle).
+// sampling as an argument of the encoder's entries), jpezy_capi_transform.hip (lossless transforms in the coefficient domain),
+// jpezy_capi_multi.hip (the multi-GPU handle).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -187,6 +188,7 @@ struct jpezy_ctx {
     DevBuf e_out, e_coef;          // host-delivered form: stuffed streams; jpezy_encode_jpeg[_packed]: the frame's coefficients
     DevBuf e_tmp;                  // scratch of entropy::launch_scan_u32 (GPU Huffman decoder)
     PinBuf e_pinned;               // pinned host staging of the stuffed streams
+    DevBuf x_coef;                 // jpezy_transform_jpeg: the transformed coefficients (the source's lie in `out`)
     int huff_optimize = 0;         // 1: the host-delivered entropy entry points build every frame's own Huffman tables (jpezy_ctx_set_huffman_optimize)
     DevBuf e_hist, e_hstat;        // per-image tables: symbol counts [frames][4][256] uint64; error flags of jpezy_huffman_histogram_dev (never read)
     DevBuf e_codes_opt;            // ... and the frames' CodeTables images [frames]
@@ -261,11 +263,15 @@ JPEZY_INTERNAL int jpezy_internal_huffdec_streams(jpezy_ctx* c, const std::vecto
 JPEZY_INTERNAL bool jpezy_internal_build_dev_setup(jpezy_dev::huffdec::Setup& S, const jpezy_host::ScanSetup& setup, const jpezy_frame_info& info, unsigned total_blocks);
 JPEZY_INTERNAL StreamGeom jpezy_internal_stream_geom(const jpezy_frame_info& info);
 // the GPU entropy coder's entries for a sampling (jpezy_capi_entropy.hip): jpezy_write_jpeg_gpu_dev / _batch and jpezy_huffman_histogram_dev
-// are these at JPEZY_SAMPLING_420; with JPEZY_SAMPLING_444 gray is 0 (the callers refuse it) and d_coeffs holds 3-block MCUs
+// are these at JPEZY_SAMPLING_420; with JPEZY_SAMPLING_444 gray is 0 (the callers refuse it) and d_coeffs holds 3-block MCUs.
+// luma, chroma: the tables of the header's two DQT segments for this call (natural order, entries 1..255; both null: the context's, which
+// is what every public writer passes) -- jpezy_transform_jpeg states the source file's tables without touching the context's setting
 JPEZY_INTERNAL int jpezy_internal_write_jpeg_gpu_dev(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H, int gray, int sampling, int n_frames,
-                                                     const char* comment, uint8_t* d_out, size_t out_stride, long long* d_sizes, void* stream);
+                                                     const char* comment, uint8_t* d_out, size_t out_stride, long long* d_sizes, void* stream,
+                                                     const uint8_t* luma = nullptr, const uint8_t* chroma = nullptr);
 JPEZY_INTERNAL int jpezy_internal_write_jpeg_gpu_batch(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H, int gray, int sampling, int n_frames,
-                                                       const char* comment, uint8_t* out, size_t cap, long* sizes);
+                                                       const char* comment, uint8_t* out, size_t cap, long* sizes, const uint8_t* luma = nullptr,
+                                                       const uint8_t* chroma = nullptr);
 JPEZY_INTERNAL int jpezy_internal_huffman_histogram_dev(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H, int gray, int sampling, int n_frames,
                                                         unsigned long long* d_hist, void* stream);
 }

@@ -262,6 +262,20 @@ struct RegionDecParams {
 };
 hipError_t launch_dequant_idct_region(const RegionDecParams& p, hipStream_t stream);
 
+// lossless transforms in the coefficient domain (jpezy_kernels_transform.hip; include/jpezy_hip.h, LOSSLESS TRANSFORMS): every output
+// block is one source block, permuted (swap) and with some coefficients negated (mirror) -- pure data movement
+struct XformParams {
+    const int16_t* in;        // source frames, [src_rows][src_pitch][B][64] each
+    int16_t* out;             // destination frames, [out_rows][out_cols][B][64] each; never overlaps in
+    size_t in_frame, out_frame;   // int16 elements per frame
+    int blocks_per_mcu;       // 6 (4:2:0: Y00 Y01 Y10 Y11 Cb Cr) or 3 (4:4:4)
+    int src_pitch;            // MCU columns of the source buffer (its row pitch; >= C)
+    int C, R;                 // MCU columns / rows of the source that are used (after trimming)
+    int swap, mirror_x, mirror_y;
+    int n_frames;
+};
+hipError_t launch_coeff_transform(const XformParams& p, hipStream_t stream);
+
 #if defined(__HIPCC__)
 // The reference's sample int(sum / 4 + sl) (ref decoder/jpezy_decoder.hpp:667) as its x86-64 build executes it: cvttsd2si truncates
 // toward zero and gives INT_MIN for every value outside [-2^31, 2^31) and for NaN, where v_cvt_i32_f64 saturates (INT_MAX above the

@@ -896,6 +896,73 @@ int jpezy_quant_tables_transform(int op, const uint8_t in[64], uint8_t out[64]);
 long jpezy_transform_jpeg(jpezy_ctx* ctx, const uint8_t* data, size_t len, int op, int flags, const char* comment, jpezy_frame_info* out_info,
                           uint8_t* out, size_t cap);
 
+/*
+ * CHROMA UPSAMPLING.  The decoder brings a subsampled component up to picture size by replication, because the reference's decode_mcu
+ * does (decoder/jpezy_decoder.hpp:504-528): on a 4:2:0 file that puts 2 x 2 steps on every coloured edge and gradient.  libjpeg,
+ * libjpeg-turbo and nvJPEG interpolate 2:1 chroma with a triangle filter by default ("fancy upsampling").  upsampling selects:
+ *
+ *   JPEZY_UPSAMPLE_NEAREST = 0   today's behaviour: the call is handed to the existing entry point named with each function, under that
+ *                                entry's own rules -- the same kernels, byte for byte the existing decode
+ *   JPEZY_UPSAMPLE_SMOOTH  = 1   below.  The reference has no such mode; the definition is this project's own (restated
+ *                                in tests/smooth_model.py).  Any other value: JPEZY_E_BADARG.
+ *
+ *   Smoothed      component c with sampling (H_c, V_c) is smoothed iff hmax % H_c == 0, vmax % V_c == 0 and (fx, fy) = (hmax / H_c,
+ *                 vmax / V_c) is (2, 1), (1, 2) or (2, 2).  Every other component -- full resolution, factors 3 and 4, the reference's
+ *                 overwrite quirk for factors that do not divide -- is placed exactly as the existing decode places it.  A file with no
+ *                 smoothed component (4:4:4, one component, the chroma of 4:1:1) therefore decodes byte for byte as it does today.
+ *   Native plane  P of a smoothed component is wc x hc = ceil(W*H_c/hmax) x ceil(H*V_c/vmax) (jpezy_ycc_component_size);
+ *                 P[y][x] = min(max(sample, 0), 255) of the integer sample inverse_dct gives (:645-670), block ((x>>3) % H_c, (y>>3) % V_c)
+ *                 of MCU ((x>>3) / H_c, (y>>3) / V_c): exactly the bytes jpezy_decode_jpeg_ycc returns for that component.  Reads outside
+ *                 the plane clamp their coordinates to [0, wc-1] x [0, hc-1]: the edge is the component's true extent, not the padded block.
+ *   Filter        U(X, Y) for X < W, Y < H, with i = X>>1, j = Y>>1, integer arithmetic, >> a shift of a non-negative int:
+ *                   (2,1)  X even: (3*P(i,Y) + P(i-1,Y) + 1) >> 2          X odd: (3*P(i,Y) + P(i+1,Y) + 2) >> 2
+ *                   (1,2)  Y even: (3*P(X,j) + P(X,j-1) + 1) >> 2          Y odd: (3*P(X,j) + P(X,j+1) + 2) >> 2
+ *                   (2,2)  d = -1 for even Y, +1 for odd Y; S(i) = 3*P(i,j) + P(i,j+d);
+ *                          X even: (3*S(i) + S(i-1) + 8) >> 4              X odd: (3*S(i) + S(i+1) + 7) >> 4
+ *                 These are libjpeg's h2v1 / h1v2 / h2v2 fancy upsamplers; the coordinate clamp reproduces their special-cased first and
+ *                 last columns.  libjpeg replicates planes no wider than two samples; here the formula holds at every size.
+ *   Colour        make_rgb / revise_value and gray (:531-578, 672-676) as always, in the reference's FP64 order: a smoothed component
+ *                 enters as U, every other component as the integer sample it has today, unclamped as today.
+ *   Siting        the filter takes chroma to sit at the centre of its 2 x 2 (JFIF, libjpeg's writer).  jpezy_encode_jpeg keeps the top-left
+ *                 pixel's chroma as the reference does, so on its files the filter is half a pixel off in phase; the mode is made for
+ *                 files from elsewhere and for centred chroma fed through jpezy_encode_jpeg_ycc.
+ *   Kernels       every layout, jpezy's own included, takes the any-layout pair: generic_idct_kernel unchanged (fast path, guard band,
+ *                 jpezy_ctx_set_force_exact and the fallback counter as in jpezy_dequant_idct_generic_dev), then smooth_rgb_kernel
+ *                 (jpezy_kernels_smooth.hip) in generic_rgb_kernel's place.  jpezy_ctx_set_decode_tolerance has nothing to act on.
+ *   Refused       precision != 8 with JPEZY_UPSAMPLE_SMOOTH: JPEZY_E_UNSUPPORTED, the context stays usable.
+ *
+ * NOT provided: smooth with reduced-size or region decode; jpezy_decode_jpeg_batch; a fused one-pass kernel for jpezy's own layout (it
+ * would need a halo from the neighbouring MCUs); 12-bit files; the host-buffer jpezy_dequant_idct* entries; a box-average decimation in
+ * the encoder (the natural follow-up: it would make the encoder's own files centred).
+ */
+enum jpezy_upsampling { JPEZY_UPSAMPLE_NEAREST = 0, JPEZY_UPSAMPLE_SMOOTH = 1 };
+/* jpezy_dequant_idct_generic_batch_dev with the upsampling chosen (stands in for decoder/jpezy_decoder.hpp:504-578, 645-676; the reference
+ * replicates, the smooth definition above is this project's own): d_r, d_g, d_b planes of W*H bytes, frame f's at + f * plane_stride
+ * (n_frames > 1: >= W*H and a multiple of 4, the generic batch entry's rule).  Asynchronous on `stream` and capturable; the generic entry's
+ * table, scratch (one call in flight per context) and capture rules apply; more than 65535 frames go out as several pairs of launches.
+ * JPEZY_UPSAMPLE_NEAREST: jpezy_dequant_idct_generic_dev for one frame, jpezy_dequant_idct_generic_batch_dev for more. */
+int jpezy_dequant_idct_upsampling_dev(jpezy_ctx* ctx, const int16_t* d_coeffs, const uint16_t qt[4][64], int ncomp, const uint8_t comp_h[3],
+                                      const uint8_t comp_v[3], const uint8_t comp_tq[3], int precision, int W, int H, int gray, int upsampling,
+                                      int n_frames, size_t plane_stride, uint8_t* d_r, uint8_t* d_g, uint8_t* d_b, void* stream);
+/* The same writing packed pixels (same reference lines, same remark).  The addressing rules of the packed section apply: pixel (x, y) of
+ * frame f at d_pix + f*frame_stride + y*row_stride + x*bytes, row_stride 0 = W*bytes, frame_stride 0 = H*row_stride, only bytes
+ * [0, W*bytes) of a row are written, byte 3 of a 32-bit pixel is 0xFF; n_frames > 1 asks for a frame_stride that is a multiple of 4.
+ * JPEZY_UPSAMPLE_NEAREST: the generic kernels' packed store stage, as jpezy_dequant_idct_scaled_packed_dev reaches it at scale_denom 1. */
+int jpezy_dequant_idct_upsampling_packed_dev(jpezy_ctx* ctx, const int16_t* d_coeffs, const uint16_t qt[4][64], int ncomp,
+                                             const uint8_t comp_h[3], const uint8_t comp_v[3], const uint8_t comp_tq[3], int precision, int W,
+                                             int H, int gray, int upsampling, int format, size_t row_stride, size_t frame_stride, int n_frames,
+                                             uint8_t* d_pix, void* stream);
+/* jpezy_decode_jpeg with the upsampling chosen (decoder/jpezy_decoder.hpp:76-134 with the second stage above; the reference replicates):
+ * header parse and Huffman decoding exactly as jpezy_decode_jpeg does them (GPU decoder, host decoder for what it declines), then the two
+ * stages and a download of W*H bytes per plane.  r, g, b NULL: header only (a 12-bit file is refused there already);
+ * plane_cap < W*H: JPEZY_E_NOSPACE.  JPEZY_UPSAMPLE_NEAREST: jpezy_decode_jpeg. */
+int jpezy_decode_jpeg_upsampling(jpezy_ctx* ctx, const uint8_t* data, size_t len, int gray, int upsampling, jpezy_frame_info* info, uint8_t* r,
+                                 uint8_t* g, uint8_t* b, size_t plane_cap);
+/* The same into host packed pixels (jpezy_decode_jpeg_packed with the upsampling chosen; same reference lines and remark): pix NULL: header
+ * only; pix_cap < (H-1)*row_stride + W*bytes: JPEZY_E_NOSPACE.  JPEZY_UPSAMPLE_NEAREST: jpezy_decode_jpeg_packed. */
+int jpezy_decode_jpeg_upsampling_packed(jpezy_ctx* ctx, const uint8_t* data, size_t len, int gray, int upsampling, jpezy_frame_info* info,
+                                        int format, size_t row_stride, uint8_t* pix, size_t pix_cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -165,6 +165,13 @@ ABI = [
     ("jpezy_coeff_transform_dev", C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     ("jpezy_quant_tables_transform", C.c_int, [C.c_int, _vp, _vp]),
     ("jpezy_transform_jpeg", C.c_long, [_vp, _vp, C.c_size_t, C.c_int, C.c_int, C.c_char_p, C.POINTER(FrameInfo), _vp, C.c_size_t]),
+    ("jpezy_dequant_idct_upsampling_dev", C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                    C.c_size_t, _vp, _vp, _vp, _vp]),
+    ("jpezy_dequant_idct_upsampling_packed_dev", C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                           C.c_size_t, C.c_size_t, C.c_int, _vp, _vp]),
+    ("jpezy_decode_jpeg_upsampling", C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.c_int, C.POINTER(FrameInfo), _vp, _vp, _vp, C.c_size_t]),
+    ("jpezy_decode_jpeg_upsampling_packed", C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.c_int, C.POINTER(FrameInfo), C.c_int, C.c_size_t, _vp,
+                                                      C.c_size_t]),
 ]
 
 # chroma sampling of the encoder's *_sampling entry points: 4:2:0 (the reference's 2x2 / 1x1 / 1x1, everything as without the keyword)
@@ -178,6 +185,11 @@ PIX_RGB24, PIX_BGR24, PIX_RGBA32, PIX_BGRA32 = 0, 1, 2, 3
 # partial MCU column / row
 XFORM_NONE, XFORM_HFLIP, XFORM_VFLIP, XFORM_TRANSPOSE, XFORM_TRANSVERSE, XFORM_ROT90, XFORM_ROT180, XFORM_ROT270 = range(8)
 XFORM_TRIM = 1
+
+# enum jpezy_upsampling: how the decoder brings subsampled chroma to picture size -- replication (the reference's, the default) or the
+# triangle filter over the component's native plane (include/jpezy_hip.h, CHROMA UPSAMPLING)
+UPSAMPLE_NEAREST, UPSAMPLE_SMOOTH = 0, 1
+E_UNSUPPORTED = -4          # JPEZY_E_UNSUPPORTED
 
 
 def pixel_bytes(fmt):
@@ -571,8 +583,11 @@ class Context:
         _check(load_library().jpezy_read_jpeg_gpu(self._h, _np_ptr(arr), arr.size, C.byref(info), d_coeffs.data_ptr(), d_coeffs.numel()))
         return info
 
-    def decode_jpeg(self, data, gray=False):
-        """.jpg bytes -> (FrameInfo, r, g, b) planes of width*height bytes (decoder::decode end to end)."""
+    def decode_jpeg(self, data, gray=False, upsampling=UPSAMPLE_NEAREST):
+        """.jpg bytes -> (FrameInfo, r, g, b) planes of width*height bytes (decoder::decode end to end).  upsampling=UPSAMPLE_SMOOTH:
+        2:1 chroma through the triangle filter (decode_jpeg_upsampling)."""
+        if upsampling != UPSAMPLE_NEAREST:
+            return self.decode_jpeg_upsampling(data, upsampling, gray=gray)
         lib = load_library()
         arr = np.frombuffer(bytes(data), dtype=np.uint8)
         info = FrameInfo()
@@ -682,8 +697,11 @@ class Context:
         _check(n)
         return buf[:n].tobytes()
 
-    def decode_jpeg_packed(self, data, format=PIX_RGB24, gray=False):
-        """.jpg bytes -> (FrameInfo, uint8 array (H, W, C)) of interleaved pixels; the fourth byte of a 32-bit format is 0xFF."""
+    def decode_jpeg_packed(self, data, format=PIX_RGB24, gray=False, upsampling=UPSAMPLE_NEAREST):
+        """.jpg bytes -> (FrameInfo, uint8 array (H, W, C)) of interleaved pixels; the fourth byte of a 32-bit format is 0xFF.
+        upsampling=UPSAMPLE_SMOOTH: decode_jpeg_upsampling_packed."""
+        if upsampling != UPSAMPLE_NEAREST:
+            return self.decode_jpeg_upsampling_packed(data, upsampling, format=format, gray=gray)
         lib = load_library()
         nb = pixel_bytes(format)
         arr = np.frombuffer(bytes(data), dtype=np.uint8)
@@ -891,6 +909,54 @@ class Context:
             return
         stride = plane_stride if plane_stride is not None else Ws * Hs
         _check(load_library().jpezy_dequant_idct_scaled_dev(*head, n_frames, stride, d_r.data_ptr(), d_g.data_ptr(), d_b.data_ptr(), stream))
+
+    # ---- chroma upsampling (UPSAMPLE_NEAREST: the existing decode; UPSAMPLE_SMOOTH: the triangle filter; include/jpezy_hip.h) ----
+    def decode_jpeg_upsampling(self, data, upsampling, gray=False):
+        """.jpg bytes -> (FrameInfo, r, g, b) planes of width*height bytes with the upsampling chosen.  UPSAMPLE_NEAREST is decode_jpeg."""
+        lib = load_library()
+        arr = np.frombuffer(bytes(data), dtype=np.uint8)
+        info = FrameInfo()
+        _check(lib.jpezy_decode_jpeg_upsampling(self._h, _np_ptr(arr), arr.size, int(gray), int(upsampling), C.byref(info), None, None, None, 0))
+        n = info.width * info.height
+        r, g, b = (np.empty(n, dtype=np.uint8) for _ in range(3))
+        _check(lib.jpezy_decode_jpeg_upsampling(self._h, _np_ptr(arr), arr.size, int(gray), int(upsampling), C.byref(info), _np_ptr(r),
+                                                _np_ptr(g), _np_ptr(b), n))
+        return info, r, g, b
+
+    def decode_jpeg_upsampling_packed(self, data, upsampling, format=PIX_RGB24, gray=False):
+        """.jpg bytes -> (FrameInfo, uint8 array (H, W, C)) of interleaved pixels with the upsampling chosen."""
+        lib = load_library()
+        nb = pixel_bytes(format)
+        arr = np.frombuffer(bytes(data), dtype=np.uint8)
+        info = FrameInfo()
+        _check(lib.jpezy_decode_jpeg_upsampling_packed(self._h, _np_ptr(arr), arr.size, int(gray), int(upsampling), C.byref(info), int(format), 0,
+                                                       None, 0))
+        img = np.empty((info.height, info.width, nb), dtype=np.uint8)
+        _check(lib.jpezy_decode_jpeg_upsampling_packed(self._h, _np_ptr(arr), arr.size, int(gray), int(upsampling), C.byref(info), int(format), 0,
+                                                       _np_ptr(img), img.size))
+        return info, img
+
+    def dequant_idct_upsampling_dev(self, d_coeffs, info, d_r=None, d_g=None, d_b=None, gray=False, stream=None, n_frames=1,
+                                    plane_stride=None, d_img=None, format=PIX_RGB24, upsampling=UPSAMPLE_SMOOTH):
+        """any-layout decode with the upsampling chosen on device memory (torch tensors): coefficients as read_jpeg_gpu leaves them ->
+        planes of W*H bytes (n_frames frames plane_stride apart, default W*H), or, with d_img, packed pixels written into a uint8 tensor
+        (H, W, C) or (N, H, W, C) whose strides give the row and frame strides, as dequant_idct_packed_dev takes it"""
+        import torch
+        if stream is None:
+            stream = torch.cuda.current_stream(d_coeffs.device).cuda_stream
+        hs = (C.c_uint8 * 3)(*[max(1, info.H[i]) for i in range(3)])
+        vs = (C.c_uint8 * 3)(*[max(1, info.V[i]) for i in range(3)])
+        tq = (C.c_uint8 * 3)(*[info.Tq[i] for i in range(3)])
+        head = (self._h, d_coeffs.data_ptr(), C.byref(info.qt), info.ncomp, C.byref(hs), C.byref(vs), C.byref(tq), info.precision or 8,
+                info.width, info.height, int(gray), int(upsampling))
+        if d_img is not None:
+            n, H, W, row, frame = self._packed_layout(d_img, pixel_bytes(format), "dequant_idct_upsampling_dev")
+            if (W, H) != (info.width, info.height):
+                raise JpezyError(f"dequant_idct_upsampling_dev: d_img is {W} x {H}, the file is {info.width} x {info.height}")
+            _check(load_library().jpezy_dequant_idct_upsampling_packed_dev(*head, int(format), row, frame, n, d_img.data_ptr(), stream))
+            return
+        stride = plane_stride if plane_stride is not None else info.width * info.height
+        _check(load_library().jpezy_dequant_idct_upsampling_dev(*head, n_frames, stride, d_r.data_ptr(), d_g.data_ptr(), d_b.data_ptr(), stream))
 
     # ---- region decode (a window (x, y, w, h) of the picture at 1/scale: the scaled decode, sliced; include/jpezy_hip.h) ----
     def decode_jpeg_region(self, data, region, scale=1, gray=False):
@@ -1217,9 +1283,13 @@ class Decoder:
         self.ctx = ctx
         self.pr = None
 
-    def decode(self, gray=False, scale=1, region=None):
+    def decode(self, gray=False, scale=1, region=None, upsampling=UPSAMPLE_NEAREST):
         """scale 2, 4 or 8: planes of scaled_size(width, height, scale) (Context.decode_jpeg_scaled); region = (x, y, w, h): planes of
-        w*h bytes, that window of the picture at 1/scale (Context.decode_jpeg_region); self.pr keeps the file's size"""
+        w*h bytes, that window of the picture at 1/scale (Context.decode_jpeg_region); self.pr keeps the file's size.
+        upsampling=UPSAMPLE_SMOOTH: 2:1 chroma through the triangle filter (Context.decode_jpeg_upsampling), full size and whole
+        pictures only: together with scale != 1 or a region it raises JpezyError with status JPEZY_E_UNSUPPORTED."""
+        if upsampling != UPSAMPLE_NEAREST and (scale != 1 or region is not None):
+            raise JpezyError(f"jpezy status {E_UNSUPPORTED}: Decoder.decode: smooth upsampling is not provided with reduced-size or region decode")
         try:
             with open(self.filename, "rb") as f:
                 data = f.read()
@@ -1228,7 +1298,7 @@ class Decoder:
             if region is not None:
                 info, r, g, b = ctx.decode_jpeg_region(data, region, scale=scale, gray=gray)
             else:
-                info, r, g, b = ctx.decode_jpeg(data, gray=gray) if scale == 1 else ctx.decode_jpeg_scaled(data, scale, gray=gray)
+                info, r, g, b = ctx.decode_jpeg(data, gray=gray, upsampling=upsampling) if scale == 1 else ctx.decode_jpeg_scaled(data, scale, gray=gray)
         except (OSError, JpezyError):
             return None
         self.pr = info

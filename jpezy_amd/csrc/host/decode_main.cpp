@@ -1,9 +1,12 @@
-// jpezy_decode <input.(jpg | jpeg)> ( <output.ppm | [OPT: --gray]> | -v ) [--scale=N] [--region=WxH+X+Y]
+// jpezy_decode <input.(jpg | jpeg)> ( <output.ppm | [OPT: --gray]> | -v ) [--scale=N] [--region=WxH+X+Y] [--upsampling=smooth|nearest]
 // Same argv rules, transcript and exit codes as the reference's src/decoder/main.cpp.  --scale=N (N = 1, 2, 4, 8; this project's own
 // option, looked for in argv[3] .. argv[5] the way --gray is) writes the picture at 1/N; any other N is the usage error.
 // --region=WxH+X+Y (this project's own option, X11 geometry order, looked for in the same places) writes the W x H window whose top-left
 // pixel is (X, Y) of the picture at 1/N (jpezy_decode_jpeg_region); a malformed geometry is the usage error, a well-formed one that does
 // not lie inside the picture prints the library's message and writes no file.
+// --upsampling=smooth (this project's own option, looked for in the same places) brings 2:1 chroma to picture size with the triangle
+// filter (jpezy_decode_jpeg_upsampling; include/jpezy_hip.h, CHROMA UPSAMPLING); --upsampling=nearest is the default, replication.  Any
+// other value is the usage error; smooth together with --scale= other than 1 or with --region= prints one rule line and writes no file.
 // jpezy_decode --i420 <input.(jpg | jpeg)> <output.yuv>   (this project's own option) writes the file's own samples, without upsampling
 // or colour conversion, as raw planes: Y, then Cb, then Cr (full range: ffmpeg's yuvj420p) through jpezy_decode_jpeg_ycc.  Only a
 // 4:2:0 file (sampling 2x2, 1x1, 1x1) is such a picture: any other layout is refused with a message.
@@ -23,6 +26,7 @@ namespace {
 int disp_error()
 {
     std::cerr << "Usage: jpezy_decode <input.(jpg | jpeg)> ( <output.ppm | [OPT: --gray]> | -v ) [OPT: --scale=(1 | 2 | 4 | 8)] [OPT: --region=WxH+X+Y]"
+                 " [OPT: --upsampling=(smooth | nearest)]"
               << std::endl;
     return EXIT_FAILURE;
 }
@@ -33,9 +37,9 @@ bool has_ext(std::string_view s, std::string_view ext)
 }
 
 template <class CL, class T>
-int output(jpezy::decoder<T>& dec, const char* out, int scale, const jpezy_rect* region)
+int output(jpezy::decoder<T>& dec, const char* out, int scale, const jpezy_rect* region, int upsampling)
 {
-    auto raw_op = region ? dec.template decode<CL>(scale, *region) : dec.template decode<CL>(scale);
+    auto raw_op = region ? dec.template decode<CL>(scale, *region) : dec.template decode<CL>(scale, upsampling);
     if (!raw_op) {
         std::cerr << "decode failed" << std::endl;
         return EXIT_FAILURE;
@@ -51,11 +55,30 @@ int output(jpezy::decoder<T>& dec, const char* out, int scale, const jpezy_rect*
 }
 
 template <class T>
-int run(const char* in, const char* out, bool gray, int scale, const jpezy_rect* region)
+int run(const char* in, const char* out, bool gray, int scale, const jpezy_rect* region, int upsampling)
 {
     jpezy::disp_logo();
     jpezy::decoder<T> dec(in);
-    return gray ? output<jpezy::GRAY_MODE>(dec, out, scale, region) : output<jpezy::COLOR_MODE>(dec, out, scale, region);
+    return gray ? output<jpezy::GRAY_MODE>(dec, out, scale, region, upsampling) : output<jpezy::COLOR_MODE>(dec, out, scale, region, upsampling);
+}
+
+// the one rule of --upsampling=smooth: whole pictures at full size as P3 files
+int upsampling_rule()
+{
+    std::cerr << "jpezy_decode: --upsampling=smooth writes whole pictures at full size: it does not combine with --scale= other than 1, --region= or --i420"
+              << std::endl;
+    return EXIT_FAILURE;
+}
+
+// --upsampling=V inside an option: JPEZY_UPSAMPLE_SMOOTH / _NEAREST for smooth / nearest, -2 for anything else, -1 when the option is
+// not there
+int upsampling_of(std::string_view opt)
+{
+    constexpr std::string_view key = "--upsampling=";
+    const auto at = opt.find(key);
+    if (at == std::string_view::npos) return -1;
+    const std::string_view v = opt.substr(at + key.size());
+    return v == "smooth" ? JPEZY_UPSAMPLE_SMOOTH : v == "nearest" ? JPEZY_UPSAMPLE_NEAREST : -2;
 }
 
 // --scale=N inside an option: N when it is 1, 2, 4 or 8, 0 for anything else, 1 when the option is not there
@@ -133,6 +156,11 @@ int i420_main(const int argc, const char* argv[])
 int main(const int argc, const char* argv[])
 {
     if (argc >= 2 && std::string_view(argv[1]) == "--i420") {
+        for (int k = 2; k < argc; ++k) {
+            const int up = upsampling_of(argv[k]);
+            if (up == -2) return disp_error();
+            if (up == JPEZY_UPSAMPLE_SMOOTH) return upsampling_rule();
+        }
         try {
             return i420_main(argc, argv);
         } catch (const std::runtime_error& e) {
@@ -149,7 +177,7 @@ int main(const int argc, const char* argv[])
     if (!((has_ext(sv0, "jpeg") || has_ext(sv0, "jpg")) && has_ext(sv1, "ppm"))) return disp_error();
 
     bool gray = false, verbose = false, has_region = false;
-    int scale = 1;
+    int scale = 1, upsampling = -1;
     jpezy_rect region{};
     for (const std::string_view sv : opt) {
         gray = gray || sv.find("--gray") != std::string_view::npos;
@@ -161,10 +189,16 @@ int main(const int argc, const char* argv[])
         const int rg = region_of(sv, &r);
         if (!rg) return disp_error();
         if (rg > 0 && !has_region) { region = r; has_region = true; }
+        const int up = upsampling_of(sv);
+        if (up == -2) return disp_error();
+        if (upsampling < 0) upsampling = up;
     }
+    if (upsampling < 0) upsampling = JPEZY_UPSAMPLE_NEAREST;
+    if (upsampling == JPEZY_UPSAMPLE_SMOOTH && (scale != 1 || has_region)) return upsampling_rule();
     const jpezy_rect* rp = has_region ? &region : nullptr;
     try {
-        return verbose ? run<jpezy::Debug>(argv[1], argv[2], gray, scale, rp) : run<jpezy::Release>(argv[1], argv[2], gray, scale, rp);
+        return verbose ? run<jpezy::Debug>(argv[1], argv[2], gray, scale, rp, upsampling)
+                       : run<jpezy::Release>(argv[1], argv[2], gray, scale, rp, upsampling);
     } catch (const std::runtime_error& e) {
         std::cerr << e.what() << std::endl;
         return EXIT_FAILURE;

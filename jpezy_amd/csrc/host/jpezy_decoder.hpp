@@ -37,11 +37,13 @@ struct decoder {
     static constexpr std::size_t rgb_size = 3, block_size = 8, blocks_size = 64, mcu_size = 4;
 
     // scale_denom 2, 4, 8: the picture at 1/2, 1/4, 1/8 (jpezy_decode_jpeg_scaled; the reference has no such mode, the definition is
-    // include/jpezy_hip.h's) -- out_width x out_height is then the size of the planes' image, pr keeps the file's
+    // include/jpezy_hip.h's) -- out_width x out_height is then the size of the planes' image, pr keeps the file's.
+    // upsampling JPEZY_UPSAMPLE_SMOOTH: 2:1 chroma through the triangle filter (jpezy_decode_jpeg_upsampling; include/jpezy_hip.h, CHROMA
+    // UPSAMPLING), at full size only: with another scale_denom it is refused with a message
     template <class MODE_TAG = COLOR_MODE>
-    std::optional<std::array<std::vector<byte>, 3>> decode(int scale_denom = 1)
+    std::optional<std::array<std::vector<byte>, 3>> decode(int scale_denom = 1, int upsampling = JPEZY_UPSAMPLE_NEAREST)
     {
-        return decode_impl<MODE_TAG>(scale_denom, nullptr);
+        return decode_impl<MODE_TAG>(scale_denom, nullptr, upsampling);
     }
 
     // the window `region` of the picture at 1 / scale_denom (jpezy_decode_jpeg_region; include/jpezy_hip.h, REGION DECODE): planes of
@@ -57,9 +59,13 @@ struct decoder {
 
 private:
     template <class MODE_TAG>
-    std::optional<std::array<std::vector<byte>, 3>> decode_impl(int scale_denom, const jpezy_rect* region)
+    std::optional<std::array<std::vector<byte>, 3>> decode_impl(int scale_denom, const jpezy_rect* region, int upsampling = JPEZY_UPSAMPLE_NEAREST)
     {
         constexpr bool gray = std::is_same_v<MODE_TAG, GRAY_MODE>;
+        if (upsampling != JPEZY_UPSAMPLE_NEAREST && (scale_denom != 1 || region)) {
+            std::cerr << "decode(): smooth upsampling is not provided with reduced-size or region decode" << std::endl;
+            return {};
+        }
         raii_messenger mes("process started...");
         std::cout << '\n';
 
@@ -102,7 +108,10 @@ private:
         const auto plane = [&](int k) { return reinterpret_cast<std::uint8_t*>(rgb[static_cast<std::size_t>(k)].data()); };
         // decode_huffman + inverse_quantization + inverse_dct + upsampling + make_rgb (:504-578, 583-670) for all MCUs: one
         // C-ABI call; for jpezy_encode's own layout every stage runs on the device
-        const int rc = region ? jpezy_decode_jpeg_region(ctx, reinterpret_cast<const std::uint8_t*>(file.data()), file.size(), gray, scale_denom,
+        const auto* bytes = reinterpret_cast<const std::uint8_t*>(file.data());
+        const int rc = upsampling != JPEZY_UPSAMPLE_NEAREST
+                           ? jpezy_decode_jpeg_upsampling(ctx, bytes, file.size(), gray, upsampling, &info, plane(0), plane(1), plane(2), rgb_s)
+                       : region ? jpezy_decode_jpeg_region(ctx, reinterpret_cast<const std::uint8_t*>(file.data()), file.size(), gray, scale_denom,
                                                          region, &info, plane(0), plane(1), plane(2), rgb_s)
                               : jpezy_decode_jpeg_scaled(ctx, reinterpret_cast<const std::uint8_t*>(file.data()), file.size(), gray, scale_denom,
                                                          &info, plane(0), plane(1), plane(2), rgb_s);

@@ -610,7 +610,7 @@ JPEZY_CATCH
 int jpezy_internal_generic_dev_core(jpezy_ctx* c, const int16_t* d_coeffs, const uint16_t qt[4][64], int ncomp, const uint8_t comp_h[3],
                             const uint8_t comp_v[3], const uint8_t comp_tq[3], int W, int H, int gray, int precision, uint8_t* d_r,
                             uint8_t* d_g, uint8_t* d_b, hipStream_t s, size_t* nblk_out, int n_frames, size_t plane_stride, int pix_bytes,
-                            unsigned row_stride, int ycc_c_step, unsigned ycc_c_row_stride)
+                            unsigned row_stride, int ycc_c_step, unsigned ycc_c_row_stride, int upsampling)
 {
     if (ncomp != 1 && ncomp != 3) return set_err(JPEZY_E_UNSUPPORTED, "dimension not supported (the reference accepts 1 or 3)");
     GenericDecParams p;
@@ -658,7 +658,8 @@ int jpezy_internal_generic_dev_core(jpezy_ctx* c, const int16_t* d_coeffs, const
     p.force_exact = c->force_exact != 0;
     p.fallback_count = c->d_counter.as<unsigned long long>();
     p.r = d_r; p.g = d_g; p.b = d_b;
-    HIP_TRY(launch_dequant_idct_generic(p, s));
+    // upsampling != 0 (JPEZY_UPSAMPLE_SMOOTH, jpezy_capi_smooth.hip): smooth_rgb_kernel in generic_rgb_kernel's place
+    HIP_TRY(launch_dequant_idct_generic(p, s, upsampling ? launch_smooth_rgb : nullptr));
     return JPEZY_OK;
 }
 

@@ -4,7 +4,7 @@
 // jpezy_capi_decode_batch.hip (the batch form), jpezy_capi_packed.hip (the entry points for packed, i.e. interleaved, pixels),
 // jpezy_capi_scaled.hip (reduced-size decode), jpezy_capi_ycc.hip (planar YCbCr 4:2:0 samples in and out), jpezy_capi_sampling.hip (chroma
 // sampling as an argument of the encoder's entries), jpezy_capi_transform.hip (lossless transforms in the coefficient domain),
-// jpezy_capi_multi.hip (the multi-GPU handle).
+// jpezy_capi_smooth.hip (smooth chroma upsampling in the decoder), jpezy_capi_multi.hip (the multi-GPU handle).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -248,7 +248,8 @@ JPEZY_INTERNAL int jpezy_internal_check_dims(const jpezy_ctx* c, int W, int H, i
 JPEZY_INTERNAL int jpezy_internal_generic_dev_core(jpezy_ctx* c, const int16_t* d_coeffs, const uint16_t qt[4][64], int ncomp, const uint8_t comp_h[3],
                                                    const uint8_t comp_v[3], const uint8_t comp_tq[3], int W, int H, int gray, int precision, uint8_t* d_r,
                                                    uint8_t* d_g, uint8_t* d_b, hipStream_t s, size_t* nblk_out, int n_frames = 1, size_t plane_stride = 0,
-                                                   int pix_bytes = 0, unsigned row_stride = 0, int ycc_c_step = 0, unsigned ycc_c_row_stride = 0);
+                                                   int pix_bytes = 0, unsigned row_stride = 0, int ycc_c_step = 0, unsigned ycc_c_row_stride = 0,
+                                                   int upsampling = 0);
 // the parts of the two transform stages' kernel parameters that planar and packed entry points share, and the cached dequantiser tables
 JPEZY_INTERNAL int jpezy_internal_enc_params(jpezy_ctx* c, int W, int H, int gray, int n_frames, int16_t* d_coeffs, hipStream_t s, EncParams* out);
 JPEZY_INTERNAL void jpezy_internal_dec_params(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H, int n_frames, DecParams* out);

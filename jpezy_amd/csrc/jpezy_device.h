@@ -205,7 +205,12 @@ struct GenericDecParams {
     int ycc = 0, c_step = 1;
     unsigned c_row_stride = 0;
 };
-hipError_t launch_dequant_idct_generic(const GenericDecParams& p, hipStream_t stream);
+// stage2: a launcher that stands in for generic_rgb_kernel behind the unchanged generic_idct_kernel (same parameters, same grid:
+// 256 pixels of four rows per workgroup, the frame in grid.z); null: generic_rgb_kernel / generic_ycc_kernel
+typedef hipError_t (*GenericStage2)(const GenericDecParams& q, dim3 grid, hipStream_t stream);
+hipError_t launch_dequant_idct_generic(const GenericDecParams& p, hipStream_t stream, GenericStage2 stage2 = nullptr);
+// smooth (triangle-filter) chroma upsampling (jpezy_kernels_smooth.hip; include/jpezy_hip.h, CHROMA UPSAMPLING)
+hipError_t launch_smooth_rgb(const GenericDecParams& q, dim3 grid, hipStream_t stream);
 // frames of p's layout one pair of launches takes (the launcher loops over larger batches); 0: a frame too large for one launch
 int generic_frames_per_launch(const GenericDecParams& p);
 

@@ -311,7 +311,7 @@ int generic_frames_per_launch(const GenericDecParams& p)
     return per < 65535 ? (int)per : 65535;                 // the frame index is grid.z
 }
 
-hipError_t launch_dequant_idct_generic(const GenericDecParams& p_in, hipStream_t s)
+hipError_t launch_dequant_idct_generic(const GenericDecParams& p_in, hipStream_t s, GenericStage2 stage2)
 {
     GenericDecParams p = p_in;
     const int nfr = p.n_frames < 1 ? 1 : p.n_frames;
@@ -337,6 +337,10 @@ hipError_t launch_dequant_idct_generic(const GenericDecParams& p_in, hipStream_t
         if (q.ycc) {                                            // native component planes (one frame): no plane is larger than W x H
             hipLaunchKernelGGL(generic::generic_ycc_kernel, dim3(gx, gy, (unsigned)q.ncomp), dim3(256), 0, s, q);
             if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+            continue;
+        }
+        if (stage2) {                                           // another second stage over the same samples (smooth chroma upsampling)
+            if (hipError_t e = stage2(q, dim3(gx, gy, (unsigned)q.n_frames), s); e != hipSuccess) return e;
             continue;
         }
         if (q.pix_bytes == 3) hipLaunchKernelGGL(generic::generic_rgb_kernel<3>, dim3(gx, gy, (unsigned)q.n_frames), dim3(256), 0, s, q);

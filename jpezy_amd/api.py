@@ -463,17 +463,45 @@ class Context:
                                                  n_frames, _np_ptr(planes[0]), _np_ptr(planes[1]), _np_ptr(planes[2])))
         return planes
 
+    # ---- what the any-layout decode wrappers share ----
+    def _stage_head(self, coeffs, info, gray):
+        """the leading arguments of the any-layout transform entries: context, coefficients (a pointer), the FrameInfo's tables and
+        layout (the sampling factors of absent components as 1), precision, size, gray"""
+        hs = (C.c_uint8 * 3)(*[max(1, info.H[i]) for i in range(3)])
+        vs = (C.c_uint8 * 3)(*[max(1, info.V[i]) for i in range(3)])
+        tq = (C.c_uint8 * 3)(*[info.Tq[i] for i in range(3)])
+        return (self._h, coeffs, C.byref(info.qt), info.ncomp, C.byref(hs), C.byref(vs), C.byref(tq), info.precision or 8,
+                info.width, info.height, int(gray))
+
+    def _decode_planes(self, fn, data, args, size):
+        """a jpezy_decode_jpeg* entry that writes three planes: the header call (null planes), the allocation -- size(info) bytes a
+        plane --, the decode call.  args: the entry's arguments between len and info."""
+        arr = np.frombuffer(bytes(data), dtype=np.uint8)
+        info = FrameInfo()
+        _check(fn(self._h, _np_ptr(arr), arr.size, *args, C.byref(info), None, None, None, 0))
+        n = size(info)
+        r, g, b = (np.empty(n, dtype=np.uint8) for _ in range(3))
+        _check(fn(self._h, _np_ptr(arr), arr.size, *args, C.byref(info), _np_ptr(r), _np_ptr(g), _np_ptr(b), n))
+        return info, r, g, b
+
+    def _decode_packed(self, fn, data, args, format, size):
+        """the same for an entry that writes packed pixels: size(info) is (width, height) of the image"""
+        nb = pixel_bytes(format)
+        arr = np.frombuffer(bytes(data), dtype=np.uint8)
+        info = FrameInfo()
+        _check(fn(self._h, _np_ptr(arr), arr.size, *args, C.byref(info), int(format), 0, None, 0))
+        w, h = size(info)
+        img = np.empty((h, w, nb), dtype=np.uint8)
+        _check(fn(self._h, _np_ptr(arr), arr.size, *args, C.byref(info), int(format), 0, _np_ptr(img), img.size))
+        return info, img
+
     def dequant_idct_generic(self, coeffs, info, gray=False):
         """any baseline layout (1/3 components, sampling 1..4): info is the FrameInfo of read_jpeg"""
         coeffs = np.ascontiguousarray(coeffs, dtype=np.int16)
         W, H = info.width, info.height
-        hs = (C.c_uint8 * 3)(*[max(1, info.H[i]) for i in range(3)])
-        vs = (C.c_uint8 * 3)(*[max(1, info.V[i]) for i in range(3)])
-        tq = (C.c_uint8 * 3)(*[info.Tq[i] for i in range(3)])
         planes = [np.empty(W * H, dtype=np.uint8) for _ in range(3)]
-        _check(load_library().jpezy_dequant_idct_generic(self._h, _np_ptr(coeffs), C.byref(info.qt), info.ncomp, C.byref(hs),
-                                                         C.byref(vs), C.byref(tq), W, H, int(gray), _np_ptr(planes[0]),
-                                                         _np_ptr(planes[1]), _np_ptr(planes[2])))
+        _check(load_library().jpezy_dequant_idct_generic(*self._stage_head(_np_ptr(coeffs), info, gray)[:7], W, H, int(gray),
+                                                         _np_ptr(planes[0]), _np_ptr(planes[1]), _np_ptr(planes[2])))
         return planes
 
     def dequant_idct_generic_dev(self, d_coeffs, info, d_r, d_g, d_b, gray=False, stream=None, n_frames=1, plane_stride=None):
@@ -482,19 +510,13 @@ class Context:
         import torch
         if stream is None:
             stream = torch.cuda.current_stream(d_coeffs.device).cuda_stream
-        hs = (C.c_uint8 * 3)(*[max(1, info.H[i]) for i in range(3)])
-        vs = (C.c_uint8 * 3)(*[max(1, info.V[i]) for i in range(3)])
-        tq = (C.c_uint8 * 3)(*[info.Tq[i] for i in range(3)])
+        head = self._stage_head(d_coeffs.data_ptr(), info, gray)
         if n_frames == 1 and plane_stride is None:
-            _check(load_library().jpezy_dequant_idct_generic_dev(self._h, d_coeffs.data_ptr(), C.byref(info.qt), info.ncomp, C.byref(hs),
-                                                                 C.byref(vs), C.byref(tq), info.precision or 8, info.width, info.height,
-                                                                 int(gray), d_r.data_ptr(), d_g.data_ptr(), d_b.data_ptr(), stream))
+            _check(load_library().jpezy_dequant_idct_generic_dev(*head, d_r.data_ptr(), d_g.data_ptr(), d_b.data_ptr(), stream))
         else:       # n_frames frames of this layout: coefficients frame after frame, planes plane_stride apart
             stride = plane_stride if plane_stride is not None else info.width * info.height
-            _check(load_library().jpezy_dequant_idct_generic_batch_dev(self._h, d_coeffs.data_ptr(), C.byref(info.qt), info.ncomp, C.byref(hs),
-                                                                       C.byref(vs), C.byref(tq), info.precision or 8, info.width, info.height,
-                                                                       int(gray), n_frames, stride, d_r.data_ptr(), d_g.data_ptr(),
-                                                                       d_b.data_ptr(), stream))
+            _check(load_library().jpezy_dequant_idct_generic_batch_dev(*head, n_frames, stride, d_r.data_ptr(), d_g.data_ptr(), d_b.data_ptr(),
+                                                                       stream))
 
     # ---- device-pointer entry points (torch tensors on this context's device) ----
     def fdct_quant_dev(self, d_r, d_g, d_b, W, H, d_coeffs, gray=False, n_frames=1, plane_stride=None, stream=None, sampling=SAMPLING_420):
@@ -588,14 +610,7 @@ class Context:
         2:1 chroma through the triangle filter (decode_jpeg_upsampling)."""
         if upsampling != UPSAMPLE_NEAREST:
             return self.decode_jpeg_upsampling(data, upsampling, gray=gray)
-        lib = load_library()
-        arr = np.frombuffer(bytes(data), dtype=np.uint8)
-        info = FrameInfo()
-        _check(lib.jpezy_decode_jpeg(self._h, _np_ptr(arr), arr.size, int(gray), C.byref(info), None, None, None, 0))
-        n = info.width * info.height
-        r, g, b = (np.empty(n, dtype=np.uint8) for _ in range(3))
-        _check(lib.jpezy_decode_jpeg(self._h, _np_ptr(arr), arr.size, int(gray), C.byref(info), _np_ptr(r), _np_ptr(g), _np_ptr(b), n))
-        return info, r, g, b
+        return self._decode_planes(load_library().jpezy_decode_jpeg, data, (int(gray),), lambda info: info.width * info.height)
 
     def decode_jpeg_batch(self, files, gray=False, raise_on_error=True):
         """list of .jpg byte strings -> list of (FrameInfo, r, g, b) (None for a file that failed when raise_on_error is
@@ -702,14 +717,7 @@ class Context:
         upsampling=UPSAMPLE_SMOOTH: decode_jpeg_upsampling_packed."""
         if upsampling != UPSAMPLE_NEAREST:
             return self.decode_jpeg_upsampling_packed(data, upsampling, format=format, gray=gray)
-        lib = load_library()
-        nb = pixel_bytes(format)
-        arr = np.frombuffer(bytes(data), dtype=np.uint8)
-        info = FrameInfo()
-        _check(lib.jpezy_decode_jpeg_packed(self._h, _np_ptr(arr), arr.size, int(gray), C.byref(info), int(format), 0, None, 0))
-        img = np.empty((info.height, info.width, nb), dtype=np.uint8)
-        _check(lib.jpezy_decode_jpeg_packed(self._h, _np_ptr(arr), arr.size, int(gray), C.byref(info), int(format), 0, _np_ptr(img), img.size))
-        return info, img
+        return self._decode_packed(load_library().jpezy_decode_jpeg_packed, data, (int(gray),), format, lambda info: (info.width, info.height))
 
     @staticmethod
     def _packed_layout(d_img, nb, who):
@@ -863,29 +871,15 @@ class Context:
     def decode_jpeg_scaled(self, data, scale, gray=False):
         """.jpg bytes -> (FrameInfo, r, g, b) planes of Ws*Hs bytes, (Ws, Hs) = scaled_size(width, height, scale); the FrameInfo keeps
         the file's own width and height.  scale 1 is decode_jpeg."""
-        lib = load_library()
-        arr = np.frombuffer(bytes(data), dtype=np.uint8)
-        info = FrameInfo()
-        _check(lib.jpezy_decode_jpeg_scaled(self._h, _np_ptr(arr), arr.size, int(gray), int(scale), C.byref(info), None, None, None, 0))
-        ws, hs = scaled_size(info.width, info.height, scale)
-        n = ws * hs
-        r, g, b = (np.empty(n, dtype=np.uint8) for _ in range(3))
-        _check(lib.jpezy_decode_jpeg_scaled(self._h, _np_ptr(arr), arr.size, int(gray), int(scale), C.byref(info), _np_ptr(r), _np_ptr(g),
-                                            _np_ptr(b), n))
-        return info, r, g, b
+        def size(info):
+            ws, hs = scaled_size(info.width, info.height, scale)
+            return ws * hs
+        return self._decode_planes(load_library().jpezy_decode_jpeg_scaled, data, (int(gray), int(scale)), size)
 
     def decode_jpeg_scaled_packed(self, data, scale, format=PIX_RGB24, gray=False):
         """.jpg bytes -> (FrameInfo, uint8 array (Hs, Ws, C)) of interleaved pixels at 1/scale; the fourth byte of a 32-bit format is 0xFF."""
-        lib = load_library()
-        nb = pixel_bytes(format)
-        arr = np.frombuffer(bytes(data), dtype=np.uint8)
-        info = FrameInfo()
-        _check(lib.jpezy_decode_jpeg_scaled_packed(self._h, _np_ptr(arr), arr.size, int(gray), int(scale), C.byref(info), int(format), 0, None, 0))
-        ws, hs = scaled_size(info.width, info.height, scale)
-        img = np.empty((hs, ws, nb), dtype=np.uint8)
-        _check(lib.jpezy_decode_jpeg_scaled_packed(self._h, _np_ptr(arr), arr.size, int(gray), int(scale), C.byref(info), int(format), 0,
-                                                   _np_ptr(img), img.size))
-        return info, img
+        return self._decode_packed(load_library().jpezy_decode_jpeg_scaled_packed, data, (int(gray), int(scale)), format,
+                                   lambda info: scaled_size(info.width, info.height, scale))
 
     def dequant_idct_scaled_dev(self, d_coeffs, info, scale, d_r=None, d_g=None, d_b=None, gray=False, stream=None, n_frames=1,
                                 plane_stride=None, d_img=None, format=PIX_RGB24):
@@ -895,12 +889,8 @@ class Context:
         import torch
         if stream is None:
             stream = torch.cuda.current_stream(d_coeffs.device).cuda_stream
-        hs = (C.c_uint8 * 3)(*[max(1, info.H[i]) for i in range(3)])
-        vs = (C.c_uint8 * 3)(*[max(1, info.V[i]) for i in range(3)])
-        tq = (C.c_uint8 * 3)(*[info.Tq[i] for i in range(3)])
         Ws, Hs = scaled_size(info.width, info.height, scale)
-        head = (self._h, d_coeffs.data_ptr(), C.byref(info.qt), info.ncomp, C.byref(hs), C.byref(vs), C.byref(tq), info.precision or 8,
-                info.width, info.height, int(gray), int(scale))
+        head = (*self._stage_head(d_coeffs.data_ptr(), info, gray), int(scale))
         if d_img is not None:
             n, H, W, row, frame = self._packed_layout(d_img, pixel_bytes(format), "dequant_idct_scaled_dev")
             if (W, H) != (Ws, Hs):
@@ -913,28 +903,13 @@ class Context:
     # ---- chroma upsampling (UPSAMPLE_NEAREST: the existing decode; UPSAMPLE_SMOOTH: the triangle filter; include/jpezy_hip.h) ----
     def decode_jpeg_upsampling(self, data, upsampling, gray=False):
         """.jpg bytes -> (FrameInfo, r, g, b) planes of width*height bytes with the upsampling chosen.  UPSAMPLE_NEAREST is decode_jpeg."""
-        lib = load_library()
-        arr = np.frombuffer(bytes(data), dtype=np.uint8)
-        info = FrameInfo()
-        _check(lib.jpezy_decode_jpeg_upsampling(self._h, _np_ptr(arr), arr.size, int(gray), int(upsampling), C.byref(info), None, None, None, 0))
-        n = info.width * info.height
-        r, g, b = (np.empty(n, dtype=np.uint8) for _ in range(3))
-        _check(lib.jpezy_decode_jpeg_upsampling(self._h, _np_ptr(arr), arr.size, int(gray), int(upsampling), C.byref(info), _np_ptr(r),
-                                                _np_ptr(g), _np_ptr(b), n))
-        return info, r, g, b
+        return self._decode_planes(load_library().jpezy_decode_jpeg_upsampling, data, (int(gray), int(upsampling)),
+                                   lambda info: info.width * info.height)
 
     def decode_jpeg_upsampling_packed(self, data, upsampling, format=PIX_RGB24, gray=False):
         """.jpg bytes -> (FrameInfo, uint8 array (H, W, C)) of interleaved pixels with the upsampling chosen."""
-        lib = load_library()
-        nb = pixel_bytes(format)
-        arr = np.frombuffer(bytes(data), dtype=np.uint8)
-        info = FrameInfo()
-        _check(lib.jpezy_decode_jpeg_upsampling_packed(self._h, _np_ptr(arr), arr.size, int(gray), int(upsampling), C.byref(info), int(format), 0,
-                                                       None, 0))
-        img = np.empty((info.height, info.width, nb), dtype=np.uint8)
-        _check(lib.jpezy_decode_jpeg_upsampling_packed(self._h, _np_ptr(arr), arr.size, int(gray), int(upsampling), C.byref(info), int(format), 0,
-                                                       _np_ptr(img), img.size))
-        return info, img
+        return self._decode_packed(load_library().jpezy_decode_jpeg_upsampling_packed, data, (int(gray), int(upsampling)), format,
+                                   lambda info: (info.width, info.height))
 
     def dequant_idct_upsampling_dev(self, d_coeffs, info, d_r=None, d_g=None, d_b=None, gray=False, stream=None, n_frames=1,
                                     plane_stride=None, d_img=None, format=PIX_RGB24, upsampling=UPSAMPLE_SMOOTH):
@@ -944,11 +919,7 @@ class Context:
         import torch
         if stream is None:
             stream = torch.cuda.current_stream(d_coeffs.device).cuda_stream
-        hs = (C.c_uint8 * 3)(*[max(1, info.H[i]) for i in range(3)])
-        vs = (C.c_uint8 * 3)(*[max(1, info.V[i]) for i in range(3)])
-        tq = (C.c_uint8 * 3)(*[info.Tq[i] for i in range(3)])
-        head = (self._h, d_coeffs.data_ptr(), C.byref(info.qt), info.ncomp, C.byref(hs), C.byref(vs), C.byref(tq), info.precision or 8,
-                info.width, info.height, int(gray), int(upsampling))
+        head = (*self._stage_head(d_coeffs.data_ptr(), info, gray), int(upsampling))
         if d_img is not None:
             n, H, W, row, frame = self._packed_layout(d_img, pixel_bytes(format), "dequant_idct_upsampling_dev")
             if (W, H) != (info.width, info.height):
@@ -990,12 +961,8 @@ class Context:
         import torch
         if stream is None:
             stream = torch.cuda.current_stream(d_coeffs.device).cuda_stream
-        hs = (C.c_uint8 * 3)(*[max(1, info.H[i]) for i in range(3)])
-        vs = (C.c_uint8 * 3)(*[max(1, info.V[i]) for i in range(3)])
-        tq = (C.c_uint8 * 3)(*[info.Tq[i] for i in range(3)])
         rect = _rect(region)
-        head = (self._h, d_coeffs.data_ptr(), C.byref(info.qt), info.ncomp, C.byref(hs), C.byref(vs), C.byref(tq), info.precision or 8,
-                info.width, info.height, int(gray), int(scale), C.byref(rect))
+        head = (*self._stage_head(d_coeffs.data_ptr(), info, gray), int(scale), C.byref(rect))
         if d_img is not None:
             n, H, W, row, frame = self._packed_layout(d_img, pixel_bytes(format), "dequant_idct_region_dev")
             if (W, H) != (rect.w, rect.h):

@@ -1,6 +1,6 @@
 // jpezy_capi.hip -- the C-ABI of include/jpezy_hip.h, part 1: the per-GPU context (device id, stream, device constant tables, staging
 // buffers, fallback counter) and the two transform stages.  No CPU fallback: every compute entry point needs a HIP device.
-#include "jpezy_capi_internal.h"
+#include "jpezy_capi_decode.h"
 
 extern "C" {
 
@@ -607,58 +607,26 @@ JPEZY_CATCH
 
 // geometry + tables + the two launches of the any-layout decoder on device memory; asynchronous on stream s (the tables are
 // uploaded synchronously when they changed since the last call)
-int jpezy_internal_generic_dev_core(jpezy_ctx* c, const int16_t* d_coeffs, const uint16_t qt[4][64], int ncomp, const uint8_t comp_h[3],
-                            const uint8_t comp_v[3], const uint8_t comp_tq[3], int W, int H, int gray, int precision, uint8_t* d_r,
-                            uint8_t* d_g, uint8_t* d_b, hipStream_t s, size_t* nblk_out, int n_frames, size_t plane_stride, int pix_bytes,
-                            unsigned row_stride, int ycc_c_step, unsigned ycc_c_row_stride, int upsampling)
+int jpezy_internal_generic_dev_core(jpezy_ctx* c, const DecodeSource& src, const DecodeSink& out, hipStream_t s, int upsampling)
 {
-    if (ncomp != 1 && ncomp != 3) return set_err(JPEZY_E_UNSUPPORTED, "dimension not supported (the reference accepts 1 or 3)");
     GenericDecParams p;
-    p.W = W; p.H = H; p.ncomp = ncomp; p.gray = gray != 0;
-    p.level = precision == 8 ? 128 : 2048;                    // ref :654
-    p.hmax = p.vmax = 0;
-    p.blocks_per_mcu = 0;
-    for (int k = 0; k < 3; ++k) { p.ch[k] = p.cv[k] = 1; p.blk_start[k] = 1 << 20; }
-    for (int k = 0; k < ncomp; ++k) {
-        p.ch[k] = comp_h[k]; p.cv[k] = comp_v[k];
-        if (p.ch[k] < 1 || p.ch[k] > 4 || p.cv[k] < 1 || p.cv[k] > 4)
-            return set_err(JPEZY_E_UNSUPPORTED, "sampling factors outside 1..4 (ITU-T T.81 B.2.2)");
-        p.hmax = p.ch[k] > p.hmax ? p.ch[k] : p.hmax;
-        p.vmax = p.cv[k] > p.vmax ? p.cv[k] : p.vmax;
-        p.blk_start[k] = p.blocks_per_mcu;
-        p.blocks_per_mcu += p.ch[k] * p.cv[k];
-    }
-    const int Hblock = (W >> 3) + ((W & 7) > 0), Vblock = (H >> 3) + ((H & 7) > 0);   // get_blocks, ref :166-169
-    p.mcu_cols = Hblock / p.hmax + ((Hblock % p.hmax) ? 1 : 0);
-    p.mcu_rows = Vblock / p.vmax + ((Vblock % p.vmax) ? 1 : 0);
-    const size_t nblk = (size_t)p.mcu_cols * p.mcu_rows * p.blocks_per_mcu;
-    if (nblk_out) *nblk_out = nblk;
-    if (!d_coeffs) return JPEZY_OK;                            // geometry only
-    if (n_frames < 1 || (n_frames > 1 && (plane_stride < (size_t)W * H || (plane_stride & 3))))
+    if (int rc = decode_geometry(c, src, out, &p)) return rc;
+    p.W = src.W; p.H = src.H;
+    if (src.n_frames < 1 || (src.n_frames > 1 && (out.frame_stride < (size_t)src.W * src.H || (out.frame_stride & 3))))
         return set_err(JPEZY_E_BADARG, "generic decoder, batch form: plane stride must hold a plane and be a multiple of 4");
-    p.n_frames = n_frames;
-    p.plane_stride = plane_stride;
-    p.pix_bytes = pix_bytes;                                 // packed pixels: d_r, d_g, d_b are the channel bytes of pixel (0, 0)
-    p.row_stride = row_stride;
-    // native component planes (jpezy_decode_jpeg_ycc): d_r, d_g, d_b are sample (0, 0) of the components, null = not wanted
-    p.ycc = ycc_c_step != 0;
-    p.c_step = ycc_c_step ? ycc_c_step : 1;
-    p.c_row_stride = ycc_c_row_stride;
+    p.ycc = out.ycc;
+    p.c_step = out.c_step;
+    p.c_row_stride = out.c_row_stride;
     const int per = generic_frames_per_launch(p);            // samples scratch: the frames of one launch (launches run in stream order)
     if (per < 1) return set_err(JPEZY_E_UNSUPPORTED, "generic decoder: frame of more than 2^31 blocks");
-    if (int rc = c->scratch.reserve(nblk * 64 * sizeof(int) * (size_t)std::min(n_frames, per))) return rc;
+    if (int rc = c->scratch.reserve(geometry_blocks(p) * 64 * sizeof(int) * (size_t)std::min(src.n_frames, per))) return rc;
     // per-component dequantiser constants (fast path) and integer quantisers (reference-order path), cached in the context
-    const uint8_t tq3[3] = { comp_tq[0], (uint8_t)(ncomp > 1 ? comp_tq[1] : 0), (uint8_t)(ncomp > 2 ? comp_tq[2] : 0) };
-    if (int rc = jpezy_internal_upload_dequant(c, qt, tq3, s)) return rc;
-    p.coeffs = d_coeffs;
+    if (int rc = upload_dequant(c, src, s)) return rc;
     p.samples = c->scratch.as<int>();
-    p.qt = c->d_dqt.as<int>();
     p.dqscale = c->d_dqscale.as<double>();
     p.coef_limit = c->coef_limit;
     p.force_exact = c->force_exact != 0;
     p.fallback_count = c->d_counter.as<unsigned long long>();
-    p.r = d_r; p.g = d_g; p.b = d_b;
-    // upsampling != 0 (JPEZY_UPSAMPLE_SMOOTH, jpezy_capi_smooth.hip): smooth_rgb_kernel in generic_rgb_kernel's place
     HIP_TRY(launch_dequant_idct_generic(p, s, upsampling ? launch_smooth_rgb : nullptr));
     return JPEZY_OK;
 }
@@ -667,61 +635,47 @@ int jpezy_dequant_idct_generic_dev(jpezy_ctx* c, const int16_t* d_coeffs, const 
                                    const uint8_t comp_v[3], const uint8_t comp_tq[3], int precision, int W, int H, int gray,
                                    uint8_t* d_r, uint8_t* d_g, uint8_t* d_b, void* stream)
 {
-    if (int rc = jpezy_internal_check_dims(c, W, H, 1)) return rc;
-    if (!d_coeffs || !qt || !comp_h || !comp_v || !comp_tq || !d_r || !d_g || !d_b) return set_err(JPEZY_E_BADARG, "null pointer");
-    if (!aligned16(d_coeffs)) return set_err(JPEZY_E_BADARG, "d_coeffs must be 16-byte aligned");
+    if (int rc = dev_head(c, W, H, 1, { d_coeffs, qt, comp_h, comp_v, comp_tq, d_r, d_g, d_b }, d_coeffs)) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    return jpezy_internal_generic_dev_core(c, d_coeffs, qt, ncomp, comp_h, comp_v, comp_tq, W, H, gray, precision, d_r, d_g, d_b, (hipStream_t)stream,
-                            nullptr);
+    return jpezy_internal_generic_dev_core(c, { d_coeffs, qt, ncomp, Layout(comp_h, comp_v, comp_tq), precision, W, H, gray, 1 },
+                                           DecodeSink::planes(d_r, d_g, d_b, 0), (hipStream_t)stream, 0);
 }
 
 int jpezy_dequant_idct_generic_batch_dev(jpezy_ctx* c, const int16_t* d_coeffs, const uint16_t qt[4][64], int ncomp, const uint8_t comp_h[3],
                                          const uint8_t comp_v[3], const uint8_t comp_tq[3], int precision, int W, int H, int gray,
                                          int n_frames, size_t plane_stride, uint8_t* d_r, uint8_t* d_g, uint8_t* d_b, void* stream)
 {
-    if (int rc = jpezy_internal_check_dims(c, W, H, n_frames)) return rc;
-    if (!d_coeffs || !qt || !comp_h || !comp_v || !comp_tq || !d_r || !d_g || !d_b) return set_err(JPEZY_E_BADARG, "null pointer");
-    if (!aligned16(d_coeffs)) return set_err(JPEZY_E_BADARG, "d_coeffs must be 16-byte aligned");
+    if (int rc = dev_head(c, W, H, n_frames, { d_coeffs, qt, comp_h, comp_v, comp_tq, d_r, d_g, d_b }, d_coeffs)) return rc;
     if (plane_stride < (size_t)W * H || (plane_stride & 3)) return set_err(JPEZY_E_BADARG, "plane_stride must hold a plane and be a multiple of 4");
     HIP_TRY(hipSetDevice(c->device));
-    return jpezy_internal_generic_dev_core(c, d_coeffs, qt, ncomp, comp_h, comp_v, comp_tq, W, H, gray, precision, d_r, d_g, d_b, (hipStream_t)stream,
-                            nullptr, n_frames, plane_stride);
+    return jpezy_internal_generic_dev_core(c, { d_coeffs, qt, ncomp, Layout(comp_h, comp_v, comp_tq), precision, W, H, gray, n_frames },
+                                           DecodeSink::planes(d_r, d_g, d_b, plane_stride), (hipStream_t)stream, 0);
 }
 
-int jpezy_internal_dequant_idct_generic_impl(jpezy_ctx* c, const int16_t* coeffs, const uint16_t qt[4][64], int ncomp, const uint8_t comp_h[3],
-                                     const uint8_t comp_v[3], const uint8_t comp_tq[3], int W, int H, int gray, int precision,
-                                     uint8_t* r, uint8_t* g, uint8_t* b, bool coeffs_on_device)
+// host coefficients -> host planes through the any-layout pair (8-bit samples)
+int jpezy_dequant_idct_generic(jpezy_ctx* c, const int16_t* coeffs, const uint16_t qt[4][64], int ncomp, const uint8_t comp_h[3],
+                               const uint8_t comp_v[3], const uint8_t comp_tq[3], int W, int H, int gray, uint8_t* r, uint8_t* g,
+                               uint8_t* b)
 {
     if (int rc = jpezy_internal_check_dims(c, W, H, 1)) return rc;
-    if (!coeffs || !qt || !comp_h || !comp_v || !comp_tq || !r || !g || !b) return set_err(JPEZY_E_BADARG, "null pointer");
+    if (int rc = dev_null_check(nullptr, { coeffs, qt, comp_h, comp_v, comp_tq, r, g, b })) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    size_t nblk = 0;
-    if (int rc = jpezy_internal_generic_dev_core(c, nullptr, qt, ncomp, comp_h, comp_v, comp_tq, W, H, gray, precision, nullptr, nullptr, nullptr, c->stream,
-                                  &nblk))
-        return rc;
-    const size_t plane = (size_t)W * H;
+    DecodeSource src = { nullptr, qt, ncomp, Layout(comp_h, comp_v, comp_tq), 8, W, H, gray, 1 };
+    GenericDecParams geom;
+    if (int rc = decode_geometry(c, src, DecodeSink::planes(nullptr, nullptr, nullptr, 0), &geom)) return rc;
+    const size_t plane = (size_t)W * H, coef_bytes = geometry_blocks(geom) * 64 * sizeof(int16_t);
     for (int k = 0; k < 3; ++k)
         if (int rc = c->in[k].reserve(plane)) return rc;
-    const int16_t* d_coeffs = coeffs;
-    if (!coeffs_on_device) {
-        if (int rc = c->out.reserve(nblk * 64 * sizeof(int16_t))) return rc;
-        HIP_TRY(hipMemcpyAsync(c->out.p, coeffs, nblk * 64 * sizeof(int16_t), hipMemcpyHostToDevice, c->stream));
-        d_coeffs = (const int16_t*)c->out.p;
-    }
-    if (int rc = jpezy_internal_generic_dev_core(c, d_coeffs, qt, ncomp, comp_h, comp_v, comp_tq, W, H, gray, precision, (uint8_t*)c->in[0].p,
-                                  (uint8_t*)c->in[1].p, (uint8_t*)c->in[2].p, c->stream, nullptr))
+    if (int rc = c->out.reserve(coef_bytes)) return rc;
+    HIP_TRY(hipMemcpyAsync(c->out.p, coeffs, coef_bytes, hipMemcpyHostToDevice, c->stream));
+    src.d_coeffs = (const int16_t*)c->out.p;
+    if (int rc = jpezy_internal_generic_dev_core(c, src, DecodeSink::planes((uint8_t*)c->in[0].p, (uint8_t*)c->in[1].p, (uint8_t*)c->in[2].p, 0),
+                                                 c->stream, 0))
         return rc;
     uint8_t* dst[3] = { r, g, b };
     for (int k = 0; k < 3; ++k) HIP_TRY(hipMemcpyAsync(dst[k], c->in[k].p, plane, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return JPEZY_OK;
-}
-
-int jpezy_dequant_idct_generic(jpezy_ctx* c, const int16_t* coeffs, const uint16_t qt[4][64], int ncomp, const uint8_t comp_h[3],
-                               const uint8_t comp_v[3], const uint8_t comp_tq[3], int W, int H, int gray, uint8_t* r, uint8_t* g,
-                               uint8_t* b)
-{
-    return jpezy_internal_dequant_idct_generic_impl(c, coeffs, qt, ncomp, comp_h, comp_v, comp_tq, W, H, gray, 8, r, g, b);
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 // jpezy_capi_decode_batch.hip -- the C-ABI, part 4: jpezy_decode_jpeg_batch (files of one layout and size go through the GPU Huffman
 // decoder together), the host decoder entry point and the decoder's knobs.
-#include "jpezy_capi_internal.h"
+#include "jpezy_capi_decode.h"
 
 extern "C" {
 // ---- batch form (round 3): files of jpezy's own layout and one size go through the Huffman decoder TOGETHER ----
@@ -27,8 +27,6 @@ int decode_slice_fast(jpezy_ctx* c, const std::vector<FastFile>& files, const jp
     const int W = info.width, H = info.height;
     const unsigned bpm = (unsigned)info.blocks_per_mcu;
     const size_t nmcu = (size_t)info.mcu_cols * info.mcu_rows, cpf = nmcu * bpm * 64, plane = (size_t)W * H, pstride = (plane + 15) & ~(size_t)15;
-    const bool own_layout = info.ncomp == 3 && info.precision == 8 && info.H[0] == 2 && info.V[0] == 2 && info.H[1] == 1 && info.V[1] == 1 &&
-                            info.H[2] == 1 && info.V[2] == 1;
     ok.assign(nf, 0);
     const bool dbg = std::getenv("JPEZY_BATCH_DEBUG") != nullptr;
     auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
@@ -73,17 +71,12 @@ int decode_slice_fast(jpezy_ctx* c, const std::vector<FastFile>& files, const jp
     // dequantisation + inverse transform + colour conversion of the whole slice in one launch (a file that failed decodes to garbage nobody reads)
     if (int rc = c->b_planes[plane_buf].reserve(3 * pstride * nf)) return rc;
     uint8_t* pl = (uint8_t*)c->b_planes[plane_buf].p;
-    const uint8_t tq[3] = { (uint8_t)info.Tq[0], (uint8_t)info.Tq[1], (uint8_t)info.Tq[2] };
-    if (own_layout) {
-        if (int rc = jpezy_dequant_idct_dev(c, (const int16_t*)c->b_coef.p, info.qt, tq, pstride, W, H, gray, (int)nf, pl, pl + pstride * nf,
-                                            pl + 2 * pstride * nf, s))
+    const DecodeSource src = { (const int16_t*)c->b_coef.p, info.qt, info.ncomp, Layout(info), info.precision, W, H, gray, (int)nf };
+    if (own_layout(&info)) {
+        if (int rc = jpezy_dequant_idct_dev(c, src.d_coeffs, src.qt, src.layout.tq, pstride, W, H, gray, (int)nf, pl, pl + pstride * nf, pl + 2 * pstride * nf, s))
             return rc;
     } else {              // any other layout: the generic kernels over the slice (block loop over all frames, one plane launch with the frame as z)
-        const uint8_t hs[3] = { (uint8_t)info.H[0], (uint8_t)info.H[1], (uint8_t)info.H[2] };
-        const uint8_t vs[3] = { (uint8_t)info.V[0], (uint8_t)info.V[1], (uint8_t)info.V[2] };
-        if (int rc = jpezy_internal_generic_dev_core(c, (const int16_t*)c->b_coef.p, info.qt, info.ncomp, hs, vs, tq, W, H, gray, info.precision, pl,
-                                      pl + pstride * nf, pl + 2 * pstride * nf, s, nullptr, (int)nf, pstride))
-            return rc;
+        if (int rc = jpezy_internal_generic_dev_core(c, src, DecodeSink::planes(pl, pl + pstride * nf, pl + 2 * pstride * nf, pstride), s, 0)) return rc;
     }
     HIP_TRY(hipStreamSynchronize(s));
     lap("IDCT");

@@ -1,6 +1,6 @@
 // jpezy_capi_huffdec.hip -- the C-ABI, part 3: the Huffman head of decoder::decode on the GPU (ref decoder/jpezy_decoder.hpp:583-642;
 // SURVEY.md 8(f)-1, decode side): one file, the stream form shared with the batch, decoder::decode end to end.
-#include "jpezy_capi_internal.h"
+#include "jpezy_capi_decode.h"
 
 extern "C" {
 // ---- GPU Huffman decoding (decode side) ----
@@ -589,52 +589,83 @@ try {
 }
 JPEZY_CATCH
 
+// The one file decode behind the planar and packed host entries (jpezy_capi_decode.h): header, output size, capacity, coefficients,
+// staging, the stage, download.  Huffman decoding is on the device as for jpezy's own files (the host head for what that decoder declines).
+int jpezy_internal_decode_file(jpezy_ctx* c, const uint8_t* data, size_t len, jpezy_frame_info* info, const DecodeRequest& rq)
+{
+    const int rc = jpezy_read_jpeg_gpu(c, data, len, info, nullptr, 0);           // header only
+    if (rc < 0) return rc;
+    if (rq.stage == DecodeStage::Smooth)
+        if (int mode = upsampling_mode(rq.who, JPEZY_UPSAMPLE_SMOOTH, info->precision); mode < 0) return mode;
+    if (!rq.dst[0] || !rq.dst[1] || !rq.dst[2]) return JPEZY_OK;
+    const int W = info->width, H = info->height;
+    if (int rc2 = jpezy_internal_check_dims(c, W, H, 1)) return rc2;
+    // the output: the window, or the picture at 1 / scale_denom
+    int w, h;
+    if (rq.region) {
+        if (int rc2 = region_inside(rq.who, W, H, rq.scale_denom, rq.region)) return rc2;
+        if (whole_picture(W, H, rq.scale_denom, *rq.region))       // what a full request costs: the reduced-size entry, under its own name
+            return rq.is_packed() ? jpezy_decode_jpeg_scaled_packed(c, data, len, rq.gray, rq.scale_denom, info, rq.format, rq.row_stride, rq.dst[0], rq.cap)
+                                  : jpezy_decode_jpeg_scaled(c, data, len, rq.gray, rq.scale_denom, info, rq.dst[0], rq.dst[1], rq.dst[2], rq.cap);
+        w = rq.region->w; h = rq.region->h;
+    } else {
+        (void)jpezy_scaled_size(W, H, rq.scale_denom, &w, &h);
+    }
+    PackedLayout L = {};
+    if (rq.is_packed())
+        if (int rc2 = packed_layout(rq.who, rq.format, rq.row_stride, 0, w, h, &L)) return rc2;
+    const size_t plane = (size_t)w * h, tight = (size_t)w * L.bytes;
+    if (rq.is_packed() ? rq.cap < (size_t)(h - 1) * L.row_stride + tight : rq.cap < plane)
+        return set_err(JPEZY_E_NOSPACE, std::string(rq.who) + (rq.is_packed() ? ": pixel buffer too small" : ": plane buffers too small"));
+    if (int rc2 = read_coeffs(c, data, len, info, rq.who)) return rc2;
+    // staging: a tight packed image in in[0], or three planes; the fused kernel's planes a multiple of 16 apart
+    const bool fused = rq.stage == DecodeStage::Full && own_layout(info);
+    const size_t stride = fused ? (plane + 15) & ~(size_t)15 : plane;
+    if (rq.is_packed()) {
+        if (int rc2 = c->in[0].reserve(tight * (size_t)h)) return rc2;
+    } else {
+        for (int k = 0; k < 3; ++k)
+            if (int rc2 = c->in[k].reserve(stride)) return rc2;
+    }
+    uint8_t* d_pix = (uint8_t*)c->in[0].p;
+    const PackedLayout T = { L.bytes, { L.off[0], L.off[1], L.off[2] }, tight, 0 };       // the device image
+    const DecodeSource src = DecodeSource::file((const int16_t*)c->out.p, *info, rq.gray);
+    const DecodeSink out = rq.is_packed() ? DecodeSink::packed(T, d_pix)
+                                          : DecodeSink::planes(d_pix, (uint8_t*)c->in[1].p, (uint8_t*)c->in[2].p, stride);
+    int rc2 = JPEZY_OK;
+    switch (rq.stage) {
+    case DecodeStage::Full:
+        // jpezy's own layout: dequantisation, IDCT and colour conversion in the fused kernel; any other baseline layout decode_mcu
+        // handles (:504-528): the generic kernels
+        if (!fused) rc2 = jpezy_internal_generic_dev_core(c, src, out, c->stream, 0);
+        else if (rq.is_packed()) rc2 = jpezy_dequant_idct_packed_dev(c, src.d_coeffs, src.qt, src.layout.tq, rq.format, tight, 0, W, H, rq.gray, 1, d_pix, c->stream);
+        else rc2 = jpezy_dequant_idct_dev(c, src.d_coeffs, src.qt, src.layout.tq, stride, W, H, rq.gray, 1, out.r, out.g, out.b, c->stream);
+        break;
+    case DecodeStage::Smooth: rc2 = jpezy_internal_generic_dev_core(c, src, out, c->stream, 1); break;
+    case DecodeStage::Scaled: rc2 = jpezy_internal_scaled_dev_core(c, src, out, c->stream, log2n_of(rq.scale_denom)); break;
+    case DecodeStage::Region: rc2 = jpezy_internal_region_dev_core(c, src, out, c->stream, log2n_of(rq.scale_denom), *rq.region); break;
+    }
+    if (rc2) return rc2;
+    if (!rq.is_packed()) {
+        // three plain copies into the caller's planes: measured against bands through the pinned ring of the host-buffer entry points
+        // (tools/measure/measure_decode_single_raw.py, 4096 x 4096, planes the caller has touched before: 2.0 ms against 2.6 ms) -- the runtime's
+        // pageable path moves 50 MB in 0.9 ms when the pages exist; what a caller pays for fresh pages is page faults, in either form
+        for (int k = 0; k < 3; ++k) HIP_TRY(hipMemcpyAsync(rq.dst[k], c->in[k].p, plane, hipMemcpyDeviceToHost, c->stream));
+    } else if (L.row_stride == tight) {
+        HIP_TRY(hipMemcpyAsync(rq.dst[0], d_pix, tight * (size_t)h, hipMemcpyDeviceToHost, c->stream));
+    } else {      // only bytes [0, w * bytes) of each of the caller's rows are written
+        HIP_TRY(hipMemcpy2DAsync(rq.dst[0], L.row_stride, d_pix, tight, tight, (size_t)h, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return JPEZY_OK;
+}
+
 // decoder::decode end to end (ref decoder/jpezy_decoder.hpp:76-134): .jpg bytes in, planar r,g,b out
 int jpezy_decode_jpeg(jpezy_ctx* c, const uint8_t* data, size_t len, int gray, jpezy_frame_info* info, uint8_t* r, uint8_t* g, uint8_t* b,
                       size_t plane_cap)
 try {
     if (!c || !info) return set_err(JPEZY_E_BADARG, "decode_jpeg: bad argument");
-    int rc = jpezy_read_jpeg_gpu(c, data, len, info, nullptr, 0);           // header only
-    if (rc < 0) return rc;
-    if (!r || !g || !b) return JPEZY_OK;
-    const int W = info->width, H = info->height;
-    if (int rc2 = jpezy_internal_check_dims(c, W, H, 1)) return rc2;
-    if (plane_cap < (size_t)W * H) return set_err(JPEZY_E_NOSPACE, "decode_jpeg: plane buffers too small");
-    const size_t ncoef = (size_t)info->mcu_cols * info->mcu_rows * info->blocks_per_mcu * 64;
-    // sized from untrusted SOF0 fields: a block costs at least 2 bits of scan (1-bit DC code + 1-bit EOB code)
-    if (ncoef / 64 > 4 * len) return set_err(JPEZY_E_FORMAT, "decode_jpeg: scan too short for the declared dimensions");
-    const uint8_t tq[3] = { (uint8_t)info->Tq[0], (uint8_t)info->Tq[1], (uint8_t)info->Tq[2] };
-    const bool own_layout = info->ncomp == 3 && info->precision == 8 && info->H[0] == 2 && info->V[0] == 2 && info->H[1] == 1 &&
-                            info->V[1] == 1 && info->H[2] == 1 && info->V[2] == 1;
-    if (!own_layout) {   // any other baseline layout decode_mcu handles (:504-528): Huffman decoding on the device as for
-                         // jpezy's own files (the host head for what that decoder declines), then the generic kernels
-        HIP_TRY(hipSetDevice(c->device));
-        if (int rc2 = c->out.reserve(ncoef * sizeof(int16_t))) return rc2;
-        rc = jpezy_read_jpeg_gpu(c, data, len, info, (int16_t*)c->out.p, ncoef);
-        if (rc < 0) return rc;
-        const uint8_t hs[3] = { (uint8_t)info->H[0], (uint8_t)info->H[1], (uint8_t)info->H[2] };
-        const uint8_t vs[3] = { (uint8_t)info->V[0], (uint8_t)info->V[1], (uint8_t)info->V[2] };
-        return jpezy_internal_dequant_idct_generic_impl(c, (const int16_t*)c->out.p, info->qt, info->ncomp, hs, vs, tq, W, H, gray, info->precision, r,
-                                         g, b, true);
-    }
-    // jpezy's own layout: Huffman decoding, dequantisation, IDCT and colour conversion all on the device
-    HIP_TRY(hipSetDevice(c->device));
-    if (int rc2 = c->out.reserve(ncoef * sizeof(int16_t))) return rc2;
-    rc = jpezy_read_jpeg_gpu(c, data, len, info, (int16_t*)c->out.p, ncoef);
-    if (rc < 0) return rc;
-    const size_t plane = (size_t)W * H, stride = (plane + 15) & ~(size_t)15;
-    uint8_t* dst[3] = { r, g, b };
-    // three plain copies into the caller's planes: measured against bands through the pinned ring of the host-buffer entry points
-    // (tools/measure/measure_decode_single_raw.py, 4096 x 4096, planes the caller has touched before: 2.0 ms against 2.6 ms) -- the runtime's
-    // pageable path moves 50 MB in 0.9 ms when the pages exist; what a caller pays for fresh pages is page faults, in either form
-    for (int k = 0; k < 3; ++k)
-        if (int rc2 = c->in[k].reserve(stride)) return rc2;
-    if (int rc2 = jpezy_dequant_idct_dev(c, (const int16_t*)c->out.p, info->qt, tq, stride, W, H, gray, 1, (uint8_t*)c->in[0].p,
-                                         (uint8_t*)c->in[1].p, (uint8_t*)c->in[2].p, c->stream))
-        return rc2;
-    for (int k = 0; k < 3; ++k) HIP_TRY(hipMemcpyAsync(dst[k], c->in[k].p, plane, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return JPEZY_OK;
+    return jpezy_internal_decode_file(c, data, len, info, DecodeRequest::planes("decode_jpeg", DecodeStage::Full, gray, r, g, b, plane_cap));
 }
 JPEZY_CATCH
 

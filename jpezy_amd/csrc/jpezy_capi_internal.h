@@ -5,6 +5,8 @@
 // jpezy_capi_scaled.hip (reduced-size decode), jpezy_capi_ycc.hip (planar YCbCr 4:2:0 samples in and out), jpezy_capi_sampling.hip (chroma
 // sampling as an argument of the encoder's entries), jpezy_capi_transform.hip (lossless transforms in the coefficient domain),
 // jpezy_capi_smooth.hip (smooth chroma upsampling in the decoder), jpezy_capi_multi.hip (the multi-GPU handle).
+// What the decode entries share beyond this -- the description of a transform stage, the geometry of a layout, the file-decode driver,
+// the head of the device entries -- is in jpezy_capi_decode.h, which includes this file.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -40,6 +42,7 @@ inline int check_comment(const char* comment, const char* who)
     if (jpezy_host::comment_ok(comment)) return JPEZY_OK;
     return set_err(JPEZY_E_BADARG, std::string(who) + ": comment longer than JPEZY_MAX_COMMENT (" + std::to_string(JPEZY_MAX_COMMENT) + " bytes)");
 }
+// (at most 65535 x 65535: W * H fits in 32 bits, no caller needs a guard of its own for that)
 inline int check_wh(int W, int H)
 {
     if (W <= 0 || H <= 0 || W > 65535 || H > 65535) return set_err(JPEZY_E_BADARG, "width/height must be in 1..65535 (16-bit SOF0 fields)");
@@ -129,6 +132,7 @@ struct PackedLayout {
 };
 
 // format, strides and the 32-bit row-offset limit; before anything is touched
+// (row_stride >= W * bytes and row_stride * H fits in 32 bits: so does the tight image, no caller needs a guard of its own for that)
 inline int packed_layout(const char* who, int format, size_t row_stride, size_t frame_stride, int W, int H, PackedLayout* L)
 {
     const int bytes = jpezy_pixel_bytes(format);
@@ -244,23 +248,14 @@ struct StreamGeom {
 #define JPEZY_INTERNAL __attribute__((visibility("hidden")))
 extern "C" {
 JPEZY_INTERNAL int jpezy_internal_check_dims(const jpezy_ctx* c, int W, int H, int n_frames);
-// geometry + tables + the two launches of the any-layout decoder on device memory (jpezy_capi.hip)
-JPEZY_INTERNAL int jpezy_internal_generic_dev_core(jpezy_ctx* c, const int16_t* d_coeffs, const uint16_t qt[4][64], int ncomp, const uint8_t comp_h[3],
-                                                   const uint8_t comp_v[3], const uint8_t comp_tq[3], int W, int H, int gray, int precision, uint8_t* d_r,
-                                                   uint8_t* d_g, uint8_t* d_b, hipStream_t s, size_t* nblk_out, int n_frames = 1, size_t plane_stride = 0,
-                                                   int pix_bytes = 0, unsigned row_stride = 0, int ycc_c_step = 0, unsigned ycc_c_row_stride = 0,
-                                                   int upsampling = 0);
 // the parts of the two transform stages' kernel parameters that planar and packed entry points share, and the cached dequantiser tables
 JPEZY_INTERNAL int jpezy_internal_enc_params(jpezy_ctx* c, int W, int H, int gray, int n_frames, int16_t* d_coeffs, hipStream_t s, EncParams* out);
 JPEZY_INTERNAL void jpezy_internal_dec_params(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H, int n_frames, DecParams* out);
 JPEZY_INTERNAL int jpezy_internal_upload_dequant(jpezy_ctx* c, const uint16_t qt[4][64], const uint8_t comp_tq[3], hipStream_t s);
-JPEZY_INTERNAL int jpezy_internal_dequant_idct_generic_impl(jpezy_ctx* c, const int16_t* coeffs, const uint16_t qt[4][64], int ncomp, const uint8_t comp_h[3],
-                                                            const uint8_t comp_v[3], const uint8_t comp_tq[3], int W, int H, int gray, int precision,
-                                                            uint8_t* r, uint8_t* g, uint8_t* b, bool coeffs_on_device = false);
 // the GPU Huffman decoder over a list of independent streams, the device tables of one scan, the block structure of an MCU (jpezy_capi_huffdec.hip)
 JPEZY_INTERNAL int jpezy_internal_huffdec_streams(jpezy_ctx* c, const std::vector<DevStream>& streams, const std::vector<jpezy_dev::huffdec::Setup>& setups,
                                                   const std::vector<char>& setup_usable, const StreamGeom& geom, int16_t* d_coef, size_t coef_elems,
-                                                  std::vector<char>& ok, const std::function<void(const char*)>& lap, bool per_lane = false);
+                                                  std::vector<char>& ok, const std::function<void(const char*)>& lap, bool per_lane);
 JPEZY_INTERNAL bool jpezy_internal_build_dev_setup(jpezy_dev::huffdec::Setup& S, const jpezy_host::ScanSetup& setup, const jpezy_frame_info& info, unsigned total_blocks);
 JPEZY_INTERNAL StreamGeom jpezy_internal_stream_geom(const jpezy_frame_info& info);
 // the GPU entropy coder's entries for a sampling (jpezy_capi_entropy.hip): jpezy_write_jpeg_gpu_dev / _batch and jpezy_huffman_histogram_dev
@@ -276,28 +271,3 @@ JPEZY_INTERNAL int jpezy_internal_write_jpeg_gpu_batch(jpezy_ctx* c, const int16
 JPEZY_INTERNAL int jpezy_internal_huffman_histogram_dev(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H, int gray, int sampling, int n_frames,
                                                         unsigned long long* d_hist, void* stream);
 }
-
-// ---- what the reduced-size and the region decode share (jpezy_capi_scaled.hip, jpezy_capi_region.hip) ----
-namespace jpezy_capi {
-
-struct Layout {
-    uint8_t hs[3], vs[3], tq[3];
-    explicit Layout(const jpezy_frame_info& info)
-    {
-        for (int k = 0; k < 3; ++k) { hs[k] = (uint8_t)info.H[k]; vs[k] = (uint8_t)info.V[k]; tq[k] = (uint8_t)info.Tq[k]; }
-    }
-};
-
-// the head of jpezy_decode_jpeg: the file's coefficients into c->out (GPU Huffman decoder, or the host's for what it declines)
-inline int read_coeffs(jpezy_ctx* c, const uint8_t* data, size_t len, jpezy_frame_info* info, const char* who)
-{
-    const size_t ncoef = (size_t)info->mcu_cols * info->mcu_rows * info->blocks_per_mcu * 64;
-    // sized from untrusted SOF0 fields: a block costs at least 2 bits of scan (1-bit DC code + 1-bit EOB code)
-    if (ncoef / 64 > 4 * len) return set_err(JPEZY_E_FORMAT, std::string(who) + ": scan too short for the declared dimensions");
-    HIP_TRY(hipSetDevice(c->device));
-    if (int rc = c->out.reserve(ncoef * sizeof(int16_t))) return rc;
-    const int rc = jpezy_read_jpeg_gpu(c, data, len, info, (int16_t*)c->out.p, ncoef);
-    return rc < 0 ? rc : JPEZY_OK;
-}
-
-}  // namespace jpezy_capi

@@ -1,6 +1,6 @@
 // jpezy_capi_packed.hip -- the C-ABI of include/jpezy_hip.h, part 5: packed (interleaved) RGB / BGR / RGBA / BGRA pixels.  The same
 // kernels as the planar entry points with another first (pixel load) and last (pixel store) step; results are the planar ones'.
-#include "jpezy_capi_internal.h"
+#include "jpezy_capi_decode.h"
 
 extern "C" {
 
@@ -124,45 +124,7 @@ int jpezy_decode_jpeg_packed(jpezy_ctx* c, const uint8_t* data, size_t len, int 
 try {
     if (!c || !info) return set_err(JPEZY_E_BADARG, "decode_jpeg_packed: bad argument");
     if (jpezy_pixel_bytes(format) < 0) return set_err(JPEZY_E_BADARG, "decode_jpeg_packed: unknown pixel format");
-    int rc = jpezy_read_jpeg_gpu(c, data, len, info, nullptr, 0);           // header only
-    if (rc < 0) return rc;
-    if (!pix) return JPEZY_OK;
-    const int W = info->width, H = info->height;
-    if (int rc2 = jpezy_internal_check_dims(c, W, H, 1)) return rc2;
-    PackedLayout L;
-    if (int rc2 = packed_layout("decode_jpeg_packed", format, row_stride, 0, W, H, &L)) return rc2;
-    const size_t tight = (size_t)W * L.bytes;
-    if (pix_cap < (size_t)(H - 1) * L.row_stride + tight) return set_err(JPEZY_E_NOSPACE, "decode_jpeg_packed: pixel buffer too small");
-    const size_t ncoef = (size_t)info->mcu_cols * info->mcu_rows * info->blocks_per_mcu * 64;
-    // sized from untrusted SOF0 fields: a block costs at least 2 bits of scan (1-bit DC code + 1-bit EOB code)
-    if (ncoef / 64 > 4 * len) return set_err(JPEZY_E_FORMAT, "decode_jpeg_packed: scan too short for the declared dimensions");
-    const uint8_t tq[3] = { (uint8_t)info->Tq[0], (uint8_t)info->Tq[1], (uint8_t)info->Tq[2] };
-    const bool own_layout = info->ncomp == 3 && info->precision == 8 && info->H[0] == 2 && info->V[0] == 2 && info->H[1] == 1 &&
-                            info->V[1] == 1 && info->H[2] == 1 && info->V[2] == 1;
-    HIP_TRY(hipSetDevice(c->device));
-    if (int rc2 = c->out.reserve(ncoef * sizeof(int16_t))) return rc2;
-    rc = jpezy_read_jpeg_gpu(c, data, len, info, (int16_t*)c->out.p, ncoef);
-    if (rc < 0) return rc;
-    if (int rc2 = c->in[0].reserve(tight * (size_t)H)) return rc2;
-    uint8_t* d_pix = (uint8_t*)c->in[0].p;
-    if (own_layout) {
-        if (int rc2 = jpezy_dequant_idct_packed_dev(c, (const int16_t*)c->out.p, info->qt, tq, format, tight, 0, W, H, gray, 1, d_pix, c->stream))
-            return rc2;
-    } else {
-        const uint8_t hs[3] = { (uint8_t)info->H[0], (uint8_t)info->H[1], (uint8_t)info->H[2] };
-        const uint8_t vs[3] = { (uint8_t)info->V[0], (uint8_t)info->V[1], (uint8_t)info->V[2] };
-        if (tight * (size_t)H > 0xFFFFFFFFull) return set_err(JPEZY_E_BADARG, "decode_jpeg_packed: image of more than 2^32 bytes");
-        if (int rc2 = jpezy_internal_generic_dev_core(c, (const int16_t*)c->out.p, info->qt, info->ncomp, hs, vs, tq, W, H, gray, info->precision,
-                                                      d_pix + L.off[0], d_pix + L.off[1], d_pix + L.off[2], c->stream, nullptr, 1, 0, L.bytes,
-                                                      (unsigned)tight))
-            return rc2;
-    }
-    if (L.row_stride == tight)
-        HIP_TRY(hipMemcpyAsync(pix, d_pix, tight * (size_t)H, hipMemcpyDeviceToHost, c->stream));
-    else      // only bytes [0, W * bytes) of each of the caller's rows are written
-        HIP_TRY(hipMemcpy2DAsync(pix, L.row_stride, d_pix, tight, tight, (size_t)H, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return JPEZY_OK;
+    return jpezy_internal_decode_file(c, data, len, info, DecodeRequest::packed("decode_jpeg_packed", DecodeStage::Full, gray, format, row_stride, pix, pix_cap));
 }
 JPEZY_CATCH
 

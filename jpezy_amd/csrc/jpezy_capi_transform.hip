@@ -2,7 +2,7 @@
 // coefficient domain.  The reference has no such mode; the definition is in the header.  jpezy_transform_jpeg connects the two halves that
 // exist -- the head of jpezy_read_jpeg_gpu (header on the host, scan through the GPU Huffman decoder or the host's) and the GPU entropy
 // coder behind jpezy_write_jpeg_gpu_sampling -- with the one kernel of jpezy_kernels_transform.hip between them; no pixel is computed.
-#include "jpezy_capi_internal.h"
+#include "jpezy_capi_decode.h"
 
 namespace {
 

@@ -2,7 +2,7 @@
 // caller's planes are the file's own sample domain: the encode kernels skip the colour conversion (first step and sample stage differ),
 // the decode kernels skip replication and make_rgb (last step differs); coefficients keep their layout, so the Huffman stages, optimised
 // tables, restart intervals and the file header are the RGB entries'.
-#include "jpezy_capi_internal.h"
+#include "jpezy_capi_decode.h"
 
 namespace {
 
@@ -219,16 +219,7 @@ try {
         if (cs < (size_t)(cw[k] - 1) * c_step + 1) return set_err(JPEZY_E_BADARG, "decode_jpeg_ycc: c_stride smaller than (wc-1) * c_step + 1");
         if (c_cap < (size_t)(ch[k] - 1) * cs + (size_t)(cw[k] - 1) * c_step + 1) return set_err(JPEZY_E_NOSPACE, "decode_jpeg_ycc: chroma buffer too small");
     }
-    const size_t ncoef = (size_t)info->mcu_cols * info->mcu_rows * info->blocks_per_mcu * 64;
-    // sized from untrusted SOF0 fields: a block costs at least 2 bits of scan (1-bit DC code + 1-bit EOB code)
-    if (ncoef / 64 > 4 * len) return set_err(JPEZY_E_FORMAT, "decode_jpeg_ycc: scan too short for the declared dimensions");
-    const uint8_t tq[3] = { (uint8_t)info->Tq[0], (uint8_t)info->Tq[1], (uint8_t)info->Tq[2] };
-    const bool own_layout = info->ncomp == 3 && info->precision == 8 && info->H[0] == 2 && info->V[0] == 2 && info->H[1] == 1 &&
-                            info->V[1] == 1 && info->H[2] == 1 && info->V[2] == 1;
-    HIP_TRY(hipSetDevice(c->device));
-    if (int rc2 = c->out.reserve(ncoef * sizeof(int16_t))) return rc2;
-    rc = jpezy_read_jpeg_gpu(c, data, len, info, (int16_t*)c->out.p, ncoef);
-    if (rc < 0) return rc;
+    if (int rc2 = read_coeffs(c, data, len, info, "decode_jpeg_ycc")) return rc2;
     // device planes: Y tight in in[0]; chroma tight planes in in[1] / in[2], or one tight interleaved plane in in[1]
     const bool inter = c_step == 2 && host[1] && host[2] && (host[1] + 1 == host[2] || host[2] + 1 == host[1]) && cw[1] == cw[2] && ch[1] == ch[2] &&
                        cs >= (size_t)2 * cw[1];
@@ -247,17 +238,12 @@ try {
     }
     const int d_step = inter ? 2 : 1;
     const size_t d_cs = inter ? (size_t)2 * cw[1] : (size_t)cwm;       // (the generic pair: one chroma row stride for both components)
-    if (own_layout) {
-        if (int rc2 = jpezy_dequant_idct_ycc_dev(c, (const int16_t*)c->out.p, info->qt, tq, d[0], (size_t)cw[0], d[1], d[2], d_cs, d_step, 0, 0, W, H, 1,
-                                                 c->stream))
+    const DecodeSource src = DecodeSource::file((const int16_t*)c->out.p, *info, 0);
+    if (own_layout(info)) {
+        if (int rc2 = jpezy_dequant_idct_ycc_dev(c, src.d_coeffs, src.qt, src.layout.tq, d[0], (size_t)cw[0], d[1], d[2], d_cs, d_step, 0, 0, W, H, 1, c->stream))
             return rc2;
-    } else {
-        const uint8_t hs[3] = { (uint8_t)info->H[0], (uint8_t)info->H[1], (uint8_t)info->H[2] };
-        const uint8_t vs[3] = { (uint8_t)info->V[0], (uint8_t)info->V[1], (uint8_t)info->V[2] };
-        if ((size_t)W * (size_t)H > 0xFFFFFFFFull) return set_err(JPEZY_E_BADARG, "decode_jpeg_ycc: image of more than 2^32 bytes");
-        if (int rc2 = jpezy_internal_generic_dev_core(c, (const int16_t*)c->out.p, info->qt, info->ncomp, hs, vs, tq, W, H, 0, info->precision,
-                                                      d[0], d[1], d[2], c->stream, nullptr, 1, 0, 0, (unsigned)cw[0], d_step, (unsigned)d_cs))
-            return rc2;
+    } else if (int rc2 = jpezy_internal_generic_dev_core(c, src, DecodeSink::ycc_planes(d[0], d[1], d[2], (unsigned)cw[0], d_step, (unsigned)d_cs), c->stream, 0)) {
+        return rc2;
     }
     // only sample bytes of the caller's rows are written
     HIP_TRY(hipMemcpy2DAsync(y, ys, d[0], (size_t)cw[0], (size_t)cw[0], (size_t)ch[0], hipMemcpyDeviceToHost, c->stream));

@@ -640,8 +640,9 @@ int jpezy_decode_jpeg_scaled_packed(jpezy_ctx* ctx, const uint8_t* data, size_t 
  *                 upload and the entropy decoding of the whole file
  *   Bytes touched no byte outside the w x h output is written: never row padding, never anything between the frames of a batch
  *
- * NOT provided: several regions per call, regions in jpezy_decode_jpeg_batch, YCC-plane output of a region, skipping the Huffman decoding
- * of restart intervals outside the window.
+ * NOT provided: several regions of ONE file per call, regions in jpezy_decode_jpeg_batch (one window of each of many files in one
+ * call is the next section, BATCH OF WINDOWS), YCC-plane output of a region, skipping the Huffman decoding of restart intervals outside
+ * the window.
  */
 typedef struct jpezy_rect { int x, y, w, h; } jpezy_rect;
 /* JPEZY_OK when region lies inside a W x H file decoded at 1 / scale_denom, else JPEZY_E_BADARG and the message.  Pure host function. */
@@ -673,6 +674,59 @@ int jpezy_decode_jpeg_region(jpezy_ctx* ctx, const uint8_t* data, size_t len, in
  * pix_cap < (h-1)*row_stride + w*bytes: JPEZY_E_NOSPACE. */
 int jpezy_decode_jpeg_region_packed(jpezy_ctx* ctx, const uint8_t* data, size_t len, int gray, int scale_denom, const jpezy_rect* region,
                                     jpezy_frame_info* info, int format, size_t row_stride, uint8_t* pix, size_t pix_cap);
+
+/*
+ * BATCH OF WINDOWS (one crop window of each of n files, sizes mixed, packed pixels left in device memory).  What an input pipeline for
+ * training or inference asks of a GPU decoder: a few hundred .jpg files of DIFFERENT sizes, one crop of each, possibly at 1/2 or 1/4, side
+ * by side in device memory as one [n, h, w, bytes] tensor.  The definition is this project's own and adds no arithmetic.
+ * For file k of n:
+ *
+ *   Window        {region, scale_denom}: scale_denom one of 1, 2, 4, 8, region in the picture at that scale (REGION DECODE's coordinates).
+ *                 region.w == 0 && region.h == 0: the whole picture at that scale (x, y are then not looked at).  windows == NULL: whole
+ *                 pictures at full size
+ *   Result        every byte of the window equals what jpezy_decode_jpeg_region_packed returns for the same file, gray, scale_denom, region
+ *                 and format, in that entry's exact arithmetic (the region section's: dequantise in 32-bit int, v outer, u inner, left to
+ *                 right in binary64, int(sum / 4 + level), replication, make_rgb per pixel)
+ *   Whole picture the result equals what jpezy_decode_jpeg_scaled_packed returns -- jpezy_decode_jpeg_packed in its exact mode at
+ *                 scale_denom 1.  It is computed by the windowed kernel over the full window, at that kernel's rate
+ *   No inexact path  the result never depends on jpezy_ctx_set_decode_tolerance or jpezy_ctx_set_force_exact, and the fallback counter is
+ *                 not advanced
+ *   Output        packed pixels (JPEZY_PIX_*) in DEVICE memory: pixel (i, j) of file k's window at
+ *                 d_pix + k*slot_stride + j*row_stride + i*bytes.  Both strides are given (windows differ in size: there is no 0 = tight);
+ *                 row_stride fits in 32 bits
+ *   Fit           a window fits when w*bytes <= row_stride and (h-1)*row_stride + w*bytes <= slot_stride; n*slot_stride <= pix_cap is
+ *                 checked once for the call (JPEZY_E_NOSPACE)
+ *   Bytes touched no byte outside a file's w*bytes x h rectangle is written: not row padding, not the rest of a slot, not the slot of a
+ *                 file that failed.  Byte 3 of a 32-bit pixel is 0xFF
+ *   Per file      as in jpezy_decode_jpeg_batch: info[k] (the file's header), placed[k] (the window as decoded, w and h filled in for a
+ *                 whole picture; the array may be NULL) and status[k].  The header is read first; a window outside the picture is
+ *                 JPEZY_E_BADARG for that file, a window that does not fit its slot JPEZY_E_NOSPACE, a broken file gets the code
+ *                 jpezy_decode_jpeg_region_packed gives it; the other files are complete either way.  The call returns JPEZY_OK or the
+ *                 first failing file's code with a message that names the file
+ *   Paths         files of one layout (components, sampling factors, precision) go through the GPU Huffman decoder together, whatever
+ *                 their sizes and tables, and through one transform launch per scale; restart intervals, streams that do not settle and
+ *                 irregular streams go file by file on child contexts.  Same bytes either way.  jpezy_ctx_last_batch_fast_count: the files
+ *                 the grouped path delivered
+ *   Synchronous   on return the pixels are complete in device memory.  Refused inside a stream capture
+ *
+ * NOT provided: host-memory, planar or YCC output; smooth upsampling of windows; resizing to arbitrary sizes; skipping the Huffman decoding
+ * of MCUs outside a window (the whole scan of every file is decoded).
+ */
+typedef struct jpezy_window { jpezy_rect region; int scale_denom; } jpezy_window;
+/* Pure host function: the window of a W x H file as it will be decoded (whole-picture form resolved; win NULL: the whole picture at full
+ * size) into *placed (may be NULL), and whether it fits the slot.  JPEZY_E_BADARG: format, W, H, scale_denom, a window outside the picture
+ * (placed is then not written); JPEZY_E_NOSPACE: it does not fit row_stride / slot_stride (placed is written). */
+int jpezy_window_fit(int W, int H, const jpezy_window* win, int format, size_t row_stride, size_t slot_stride, jpezy_rect* placed);
+/* The batch (stands in for n calls of decoder/jpezy_decoder.hpp:76-134 with the region stage; the reference has no such mode, the definition
+ * above is this project's own).  data[k], len[k]: the files in host memory; windows: n of them or NULL; d_pix: device memory of pix_cap
+ * bytes.  Refused before the context is looked at, in this order: n < 0, (n == 0 is JPEZY_OK,) null arrays, format, zero strides,
+ * row_stride beyond 32 bits, n*slot_stride > pix_cap (JPEZY_E_NOSPACE). */
+int jpezy_decode_windows_dev(jpezy_ctx* ctx, int n, const uint8_t* const* data, const size_t* len, int gray, const jpezy_window* windows,
+                             int format, size_t row_stride, size_t slot_stride, uint8_t* d_pix, size_t pix_cap, jpezy_frame_info* info,
+                             jpezy_rect* placed, int* status);
+/* Files per slice of the grouped path: 0 = automatic (at most 512, coefficients + scans + decoder scratch under ~1.5 GB), 1..512 = that many.
+ * A test and measurement knob, per context; the bytes do not depend on it. */
+int jpezy_ctx_set_windows_slice_files(jpezy_ctx* ctx, int n);
 
 /*
  * PLANAR YCbCr 4:2:0 SAMPLES (I420 / YV12 / NV12 / NV21) IN AND OUT.  The file format is full-range BT.601 YCbCr sampled 2x2, 1x1, 1x1: a

@@ -39,6 +39,11 @@ class Rect(C.Structure):
     _fields_ = [("x", C.c_int), ("y", C.c_int), ("w", C.c_int), ("h", C.c_int)]
 
 
+class Window(C.Structure):
+    """jpezy_window: a region of the picture at 1/scale_denom; w == h == 0: the whole picture at that scale"""
+    _fields_ = [("region", Rect), ("scale_denom", C.c_int)]
+
+
 class MultiOut(C.Structure):
     _fields_ = [("coeffs", C.c_void_p), ("jpg", C.c_void_p), ("jpg_stride", C.c_size_t), ("jpg_sizes", C.POINTER(C.c_longlong)),
                 ("on_root_device", C.c_int)]
@@ -136,6 +141,9 @@ ABI = [
     ("jpezy_decode_jpeg_region", C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.c_int, _vp, C.POINTER(FrameInfo), _vp, _vp, _vp, C.c_size_t]),
     ("jpezy_decode_jpeg_region_packed", C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.c_int, _vp, C.POINTER(FrameInfo), C.c_int, C.c_size_t, _vp,
                                                   C.c_size_t]),
+    ("jpezy_window_fit", C.c_int, [C.c_int, C.c_int, _vp, C.c_int, C.c_size_t, C.c_size_t, _vp]),
+    ("jpezy_decode_windows_dev", C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, C.c_size_t, C.c_size_t, _vp, C.c_size_t, _vp, _vp, _vp]),
+    ("jpezy_ctx_set_windows_slice_files", C.c_int, [_vp, C.c_int]),
     ("jpezy_ycc_chroma_size", C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("jpezy_ycc_component_size", C.c_int, [C.POINTER(FrameInfo), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("jpezy_fdct_quant_ycc_dev", C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int,
@@ -286,6 +294,23 @@ def _rect(region):
 def region_check(W, H, scale, region):
     """raises JpezyError unless region = (x, y, w, h) lies inside a W x H file decoded at 1/scale, i.e. inside scaled_size(W, H, scale)"""
     _check(load_library().jpezy_region_check(int(W), int(H), int(scale), C.byref(_rect(region))))
+
+
+def _window(win):
+    """None, (x, y, w, h) or ((x, y, w, h), scale) -> Window; None: the whole picture at full size"""
+    if win is None:
+        return Window(Rect(0, 0, 0, 0), 1)
+    if len(win) == 2 and not isinstance(win[0], (int, np.integer)):
+        return Window(_rect(win[0]), int(win[1]))
+    return Window(_rect(win), 1)
+
+
+def window_fit(W, H, window, format=PIX_RGB24, row_stride=0, slot_stride=0):
+    """the window (None, (x, y, w, h) or ((x, y, w, h), scale)) of a W x H file as decode_windows_dev decodes it, as (x, y, w, h); raises
+    JpezyError when it lies outside the picture or does not fit a slot of slot_stride bytes with rows row_stride apart (jpezy_window_fit)"""
+    placed = Rect()
+    _check(load_library().jpezy_window_fit(int(W), int(H), C.byref(_window(window)), int(format), int(row_stride), int(slot_stride), C.byref(placed)))
+    return placed.x, placed.y, placed.w, placed.h
 
 
 def transform_geometry(op, W, H, sampling=SAMPLING_420, trim=False):
@@ -642,6 +667,44 @@ class Context:
             C.memmove(C.byref(fi), C.byref(infos[i]), C.sizeof(FrameInfo))
             out.append((fi, planes[i][0][: sizes[i]], planes[i][1][: sizes[i]], planes[i][2][: sizes[i]]))
         return out
+
+    def decode_windows_dev(self, files, d_out, windows=None, format=PIX_RGB24, gray=False, raise_on_error=True):
+        """one crop window of each of the .jpg byte strings in `files` (sizes mixed) as packed pixels into d_out, a torch uint8 tensor
+        [n, Hs, Ws, bytes] on this context's device with stride(3) == 1 and stride(2) == bytes; rows are stride(1) apart, slots stride(0).
+        windows: None (whole pictures at full size) or a list of None, (x, y, w, h) or ((x, y, w, h), scale), in the picture at 1/scale.
+        File k's window lands at d_out[k, :h, :w]; nothing else of d_out is written.  Returns a list of (FrameInfo, (x, y, w, h), status);
+        synchronous (jpezy_decode_windows_dev)."""
+        lib = load_library()
+        n = len(files)
+        nb = pixel_bytes(format)
+        if d_out.dim() != 4 or str(d_out.dtype) != "torch.uint8" or not d_out.is_cuda or d_out.device.index != self.device:
+            raise JpezyError("decode_windows_dev: d_out must be a uint8 tensor [n, Hs, Ws, bytes] on the context's device")
+        if d_out.shape[0] != n or d_out.shape[3] != nb or (n and (d_out.stride(3) != 1 or d_out.stride(2) != nb)):
+            raise JpezyError(f"decode_windows_dev: d_out must hold {n} slots of pixels of {nb} contiguous bytes")
+        if windows is not None and len(windows) != n:
+            raise JpezyError("decode_windows_dev: one window per file")
+        arrs = [np.frombuffer(bytes(f), dtype=np.uint8) for f in files]
+        data = (C.c_void_p * max(n, 1))(*[a.ctypes.data for a in arrs])
+        lens = (C.c_size_t * max(n, 1))(*[a.size for a in arrs])
+        wins = (Window * max(n, 1))(*[_window(w) for w in windows]) if windows is not None else None
+        infos, placed, status = (FrameInfo * max(n, 1))(), (Rect * max(n, 1))(), (C.c_int * max(n, 1))()
+        row, slot = (d_out.stride(1), d_out.stride(0)) if n else (1, 1)
+        # pix_cap: what the tensor's storage holds behind its first byte (n whole slots must lie inside it)
+        cap = d_out.untyped_storage().nbytes() - d_out.storage_offset() if n else 0
+        rc = lib.jpezy_decode_windows_dev(self._h, n, data, lens, int(gray), wins, int(format), row, slot, d_out.data_ptr() if n else None, cap,
+                                          infos, placed, status)
+        if rc != 0 and raise_on_error:
+            _check(rc)
+        out = []
+        for i in range(n):
+            fi = FrameInfo()
+            C.memmove(C.byref(fi), C.byref(infos[i]), C.sizeof(FrameInfo))
+            out.append((fi, (placed[i].x, placed[i].y, placed[i].w, placed[i].h), status[i]))
+        return out
+
+    def set_windows_slice_files(self, n):
+        """files per slice of decode_windows_dev's grouped path; 0: automatic (a test and measurement knob)"""
+        _check(load_library().jpezy_ctx_set_windows_slice_files(self._h, int(n)))
 
     def set_huffdec_min_bytes(self, n):
         load_library().jpezy_ctx_set_huffdec_min_bytes(self._h, n)

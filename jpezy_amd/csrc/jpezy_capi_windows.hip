@@ -1,0 +1,381 @@
+// jpezy_capi_windows.hip -- the C-ABI of include/jpezy_hip.h, part 13: a batch of crop windows (one window of each of n files, sizes and
+// quantiser tables mixed, packed pixels left in device memory).  Files of one LAYOUT go through the batch form of the GPU Huffman decoder
+// together, whatever their sizes (a stream carries its own block count and coefficient offset), and through ONE launch of windows_kernel
+// per scale present (jpezy_kernels_windows.hip); what that path declines goes file by file: read_coeffs and the region stage core on a
+// child context, straight into the file's slot.  Nothing is downloaded.
+#include "jpezy_capi_decode.h"
+
+namespace {
+
+const char* const kWho = "decode_windows_dev";
+
+// the window as it will be decoded (whole-picture form resolved), inside the picture, fitting its slot; W, H, bytes already checked
+int resolve_window(const char* who, int W, int H, const jpezy_window* win, int bytes, size_t row_stride, size_t slot_stride, jpezy_rect* placed)
+{
+    const int scale = win ? win->scale_denom : 1;
+    if (log2n_of(scale) < 0) return bad_scale(who);
+    jpezy_rect r = win ? win->region : jpezy_rect{ 0, 0, 0, 0 };
+    if (r.w == 0 && r.h == 0) {                    // the whole picture at that scale (x, y are not looked at)
+        r.x = r.y = 0;
+        (void)jpezy_scaled_size(W, H, scale, &r.w, &r.h);
+    }
+    if (int rc = region_inside(who, W, H, scale, &r)) return rc;
+    if (placed) *placed = r;
+    const size_t tight = (size_t)r.w * (size_t)bytes;
+    if (tight > row_stride || (size_t)(r.h - 1) * row_stride + tight > slot_stride)
+        return set_err(JPEZY_E_NOSPACE, std::string(who) + ": a window of " + std::to_string(r.w) + " x " + std::to_string(r.h) + " pixels of " +
+                                            std::to_string(bytes) + " bytes does not fit a slot of " + std::to_string(slot_stride) +
+                                            " bytes with rows " + std::to_string(row_stride) + " apart");
+    return JPEZY_OK;
+}
+
+struct Cand {
+    jpezy_host::ScanSetup setup;
+    const uint8_t* scan = nullptr;      // grouped path: the file from its first scan byte
+    size_t n = 0;
+    size_t nblk = 0;                    // blocks of the whole file
+    jpezy_rect rect = { 0, 0, 0, 0 };
+    int log2n = 3;
+    int st = JPEZY_OK;                  // < 0: decided before any device work
+    bool parsed = false, good = false;  // good: the grouped path takes it
+    std::string msg;
+};
+
+bool same_layout(const jpezy_frame_info& x, const jpezy_frame_info& y)
+{
+    if (x.ncomp != y.ncomp || x.precision != y.precision) return false;
+    for (int q = 0; q < x.ncomp; ++q)
+        if (x.H[q] != y.H[q] || x.V[q] != y.V[q]) return false;
+    return true;
+}
+
+bool same_tables(const jpezy_host::ScanSetup& a, const jpezy_host::ScanSetup& b0)
+{
+    if (std::memcmp(a.Td, b0.Td, sizeof a.Td) || std::memcmp(a.present, b0.present, sizeof a.present) || std::memcmp(a.bits, b0.bits, sizeof a.bits)) return false;
+    for (int t = 0; t < 8; ++t)
+        if (a.present[t] && (a.nvals[t] != b0.nvals[t] || std::memcmp(a.vals[t], b0.vals[t], (size_t)a.nvals[t]))) return false;
+    return true;
+}
+
+// the dequantisers of the file's (up to) three components, natural order: what jpezy_internal_upload_dequant puts into d_dqt
+void dequant_set(const jpezy_frame_info& fi, int out[192])
+{
+    for (int k = 0; k < 3; ++k) {
+        const int t = (k < fi.ncomp ? fi.Tq[k] : 0) & 3;
+        for (int i = 0; i < 64; ++i) out[k * 64 + i] = fi.qt[t][i];
+    }
+}
+
+struct SliceOut {
+    size_t row_stride, slot_stride;
+    uint8_t* d_pix;
+    int bytes, swap_rb, gray;
+};
+
+// One slice of a group (one layout; sizes, windows, scales and tables mixed): the Huffman decoding of all files in one sequence of
+// launches, then one windows_kernel launch per scale present over the files that settled.  ok[k] = 1 for those; the others are left to
+// the per-file path, whose verdict is the authoritative one.
+int decode_slice(jpezy_ctx* c, const std::vector<int>& files, const std::vector<Cand>& all, const jpezy_frame_info* info, const SliceOut& out,
+                 std::vector<char>& ok)
+{
+    namespace HD = jpezy_dev::huffdec;
+    hipStream_t s = c->stream;
+    const unsigned nf = (unsigned)files.size();
+    const jpezy_frame_info& gi = info[files[0]];
+    ok.assign(nf, 0);
+    const bool dbg = std::getenv("JPEZY_BATCH_DEBUG") != nullptr;
+    auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    double t_mark = now();
+    auto lap = [&](const char* what) {
+        if (!dbg) return;
+        (void)hipStreamSynchronize(s);
+        const double t = now();
+        std::fprintf(stderr, "  windows slice (%u files): %-28s %.3f ms\n", nf, what, (t - t_mark) * 1e3);
+        t_mark = t;
+    };
+    // Device Huffman tables once per DISTINCT set of tables.  Setup::total_blocks is read by the single-stream emit_kernel alone: every
+    // kernel this call can reach (speculate / sync / emit / DC of the batch form, the lane-per-stream kernel) takes the stream's own count
+    // from BatchFile, so files of different sizes share a Setup and the sharing is keyed on the tables only.
+    std::vector<DevStream> streams(nf);
+    std::vector<HD::Setup> setups;
+    std::vector<char> setup_usable;
+    std::vector<unsigned> first_with;
+    size_t coef_elems = 0;
+    bool small = nf > 1;
+    for (unsigned k = 0; k < nf; ++k) {
+        const Cand& cd = all[(size_t)files[k]];
+        unsigned j = (unsigned)first_with.size();
+        for (unsigned q = (unsigned)first_with.size(); q-- > 0;)
+            if (same_tables(cd.setup, all[(size_t)files[first_with[q]]].setup)) { j = q; break; }
+        if (j == first_with.size()) {
+            setups.emplace_back();
+            setup_usable.push_back(jpezy_internal_build_dev_setup(setups.back(), cd.setup, info[files[k]], (unsigned)cd.nblk) ? 1 : 0);
+            if (first_with.size() < 64) first_with.push_back(k);
+            j = (unsigned)setups.size() - 1;
+        }
+        streams[k] = { cd.scan, cd.n, (unsigned)cd.nblk, (unsigned long long)coef_elems, j };
+        coef_elems += (cd.nblk * 64 + 7) & ~(size_t)7;                  // whole files, 16-byte aligned
+        small = small && cd.n <= 4096;
+    }
+    const bool per_lane = small && setups.size() == 1;
+    if (int rc = c->b_coef.reserve(coef_elems * sizeof(int16_t))) return rc;
+    if (int rc = jpezy_internal_huffdec_streams(c, streams, setups, setup_usable, jpezy_internal_stream_geom(gi), (int16_t*)c->b_coef.p, coef_elems, ok, lap, per_lane)) return rc;
+
+    // descriptor tables: one per launch (a scale; a second one for a scale whose workgroups would not fit 32 bits), the dequantiser sets
+    // de-duplicated in front of them -- built in the context's pinned staging, one upload
+    struct Launch { int log2n; unsigned long long total; std::vector<WindowDesc> desc; };
+    std::vector<Launch> launches;
+    std::vector<int> qsets;                                           // [sets][192]
+    for (unsigned k = 0; k < nf; ++k) {
+        if (!ok[k]) continue;
+        const int i = files[k];
+        const Cand& cd = all[(size_t)i];
+        int q[192];
+        dequant_set(info[i], q);
+        size_t qs = qsets.size() / 192;
+        for (size_t t = qsets.size() / 192; t-- > 0;)
+            if (!std::memcmp(&qsets[t * 192], q, sizeof q)) { qs = t; break; }
+        if (qs == qsets.size() / 192) qsets.insert(qsets.end(), q, q + 192);
+        const int mw = info[i].hmax << cd.log2n, mh = info[i].vmax << cd.log2n;       // an MCU of the picture at this scale
+        WindowDesc d;
+        std::memset(&d, 0, sizeof d);
+        d.coeff_off = streams[k].coeff_off;
+        d.out_off = (unsigned long long)i * out.slot_stride;
+        d.qset = (int)qs;
+        d.mcu_cols = info[i].mcu_cols;
+        d.x = cd.rect.x; d.y = cd.rect.y; d.w = cd.rect.w; d.h = cd.rect.h;
+        d.ux0 = cd.rect.x / mw; d.ucols = (cd.rect.x + cd.rect.w - 1) / mw - d.ux0 + 1;
+        d.uy0 = cd.rect.y / mh;
+        const unsigned long long wgs = (unsigned long long)d.ucols * (unsigned long long)((cd.rect.y + cd.rect.h - 1) / mh - d.uy0 + 1);
+        Launch* L = nullptr;
+        for (Launch& l : launches)
+            if (l.log2n == cd.log2n && l.total + wgs <= 0xFFFFFFFFull) L = &l;
+        if (!L) { launches.push_back({ cd.log2n, 0, {} }); L = &launches.back(); }
+        d.wg0 = (unsigned)L->total;
+        L->total += wgs;
+        L->desc.push_back(d);
+    }
+    if (launches.empty()) return JPEZY_OK;
+    size_t bytes = qsets.size() * sizeof(int);                        // (a multiple of 64)
+    for (const Launch& l : launches) bytes += l.desc.size() * sizeof(WindowDesc);
+    if (int rc = c->w_pin.reserve(bytes, bytes + (bytes >> 2))) return rc;
+    if (int rc = c->w_tab.reserve(bytes)) return rc;
+    std::memcpy(c->w_pin.p, qsets.data(), qsets.size() * sizeof(int));
+    size_t at = qsets.size() * sizeof(int);
+    std::vector<size_t> desc_at;
+    for (const Launch& l : launches) {
+        std::memcpy(c->w_pin.p + at, l.desc.data(), l.desc.size() * sizeof(WindowDesc));
+        desc_at.push_back(at);
+        at += l.desc.size() * sizeof(WindowDesc);
+    }
+    HIP_TRY(hipMemcpyAsync(c->w_tab.p, c->w_pin.p, bytes, hipMemcpyHostToDevice, s));
+    WindowsParams p;
+    std::memset(&p, 0, sizeof p);
+    {
+        // the layout's geometry through the one function the stage cores use (the sizes it derives are not read here)
+        RegionDecParams g;
+        const DecodeSource src = DecodeSource::file((const int16_t*)c->b_coef.p, gi, out.gray);
+        if (int rc = decode_geometry(c, src, DecodeSink::planes(nullptr, nullptr, nullptr, 0), &g)) return rc;
+        p.ncomp = g.ncomp; p.gray = g.gray; p.level = g.level; p.hmax = g.hmax; p.vmax = g.vmax; p.blocks_per_mcu = g.blocks_per_mcu;
+        for (int k = 0; k < 3; ++k) { p.ch[k] = g.ch[k]; p.cv[k] = g.cv[k]; p.blk_start[k] = g.blk_start[k]; }
+    }
+    p.coeffs = (const int16_t*)c->b_coef.p;
+    p.qsets = (const int*)c->w_tab.p;
+    p.pix = out.d_pix;
+    p.row_stride = out.row_stride;
+    p.pix_bytes = out.bytes; p.swap_rb = out.swap_rb;
+    Event ev0, ev1;                                                   // JPEZY_BATCH_DEBUG: the kernel's own time, from device events
+    if (dbg) {
+        HIP_TRY(ev0.create(hipEventDefault));
+        HIP_TRY(ev1.create(hipEventDefault));
+    }
+    for (size_t l = 0; l < launches.size(); ++l) {
+        p.log2n = launches[l].log2n;
+        p.desc = (const WindowDesc*)((const uint8_t*)c->w_tab.p + desc_at[l]);
+        p.n_desc = (unsigned)launches[l].desc.size();
+        if (dbg) HIP_TRY(hipEventRecord(ev0, s));
+        HIP_TRY(launch_dequant_idct_windows(p, launches[l].total, s));
+        if (dbg) {
+            float ms = 0;
+            HIP_TRY(hipEventRecord(ev1, s));
+            HIP_TRY(hipEventSynchronize(ev1));
+            HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
+            std::fprintf(stderr, "  windows slice (%u files): windows_kernel<%d>, %u files, %llu workgroups: %.3f ms (device events)\n", nf, 1 << p.log2n, p.n_desc,
+                         launches[l].total, (double)ms);
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(s));                                 // (the pinned staging is the next slice's; the call is synchronous anyway)
+    lap("windows transform");
+    return JPEZY_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int jpezy_window_fit(int W, int H, const jpezy_window* win, int format, size_t row_stride, size_t slot_stride, jpezy_rect* placed)
+{
+    const char* who = "window_fit";
+    const int bytes = jpezy_pixel_bytes(format);
+    if (bytes < 0) return set_err(JPEZY_E_BADARG, std::string(who) + ": unknown pixel format");
+    if (W <= 0 || H <= 0) return set_err(JPEZY_E_BADARG, std::string(who) + ": width and height must be positive");
+    return resolve_window(who, W, H, win, bytes, row_stride, slot_stride, placed);
+}
+
+int jpezy_ctx_set_windows_slice_files(jpezy_ctx* c, int n)
+{
+    if (!c) return set_err(JPEZY_E_BADARG, "null context");
+    if (n < 0 || n > 512) return set_err(JPEZY_E_BADARG, "windows_slice_files must be 0 (automatic) or 1..512");
+    c->w_slice_files = n;
+    return JPEZY_OK;
+}
+
+int jpezy_decode_windows_dev(jpezy_ctx* c, int n, const uint8_t* const* data, const size_t* len, int gray, const jpezy_window* windows, int format,
+                             size_t row_stride, size_t slot_stride, uint8_t* d_pix, size_t pix_cap, jpezy_frame_info* info, jpezy_rect* placed,
+                             int* status)
+try {
+    const std::string who = kWho;
+    // what needs no device, before the context is looked at
+    if (n < 0) return set_err(JPEZY_E_BADARG, who + ": n must not be negative");
+    if (n == 0) return JPEZY_OK;
+    if (!data || !len || !info || !status || !d_pix) return set_err(JPEZY_E_BADARG, who + ": null pointer");
+    const int bytes = jpezy_pixel_bytes(format);
+    if (bytes < 0) return set_err(JPEZY_E_BADARG, who + ": unknown pixel format");
+    if (row_stride == 0 || slot_stride == 0)
+        return set_err(JPEZY_E_BADARG, who + ": row_stride and slot_stride must be given (windows differ in size: there is no 0 = tight)");
+    if (row_stride > 0xFFFFFFFFull) return set_err(JPEZY_E_BADARG, who + ": row_stride must fit in 32 bits");
+    if (slot_stride > pix_cap / (size_t)n) return set_err(JPEZY_E_NOSPACE, who + ": n * slot_stride exceeds pix_cap");
+    if (!c) return set_err(JPEZY_E_BADARG, "null context");
+    HIP_TRY(hipSetDevice(c->device));
+    {
+        hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(c->stream, &st) == hipSuccess && st != hipStreamCaptureStatusNone)
+            return set_err(JPEZY_E_BADARG, who + ": the call is synchronous and cannot run inside a stream capture");
+    }
+    c->b_last_fast = 0;
+    const bool blue_first = format == JPEZY_PIX_BGR24 || format == JPEZY_PIX_BGRA32;
+    std::vector<Cand> all((size_t)n);
+    std::vector<char> done((size_t)n, 0);
+
+    // ---- headers and windows, spread over host threads ----
+    auto prep = [&](int i) {
+        Cand& cd = all[(size_t)i];
+        std::memset(&info[i], 0, sizeof info[i]);
+        if (placed) placed[i] = { 0, 0, 0, 0 };
+        if (!data[i]) { cd.st = JPEZY_E_BADARG; cd.msg = "null file"; return; }
+        std::string err;
+        if (int rc = jpezy_host::parse_header(data[i], len[i], &info[i], &cd.setup, &err); rc < 0) { cd.st = rc; cd.msg = err; return; }
+        cd.parsed = true;
+        const jpezy_frame_info& fi = info[i];
+        if (int rc = check_wh(fi.width, fi.height)) { cd.st = rc; cd.msg = g_err; return; }
+        const jpezy_window* win = windows ? &windows[i] : nullptr;
+        const int fit = resolve_window(kWho, fi.width, fi.height, win, bytes, row_stride, slot_stride, &cd.rect);
+        if (placed && (fit == JPEZY_OK || fit == JPEZY_E_NOSPACE)) placed[i] = cd.rect;       // (a window inside the picture is reported, fitting or not)
+        if (fit) { cd.st = fit; cd.msg = g_err; return; }
+        cd.log2n = log2n_of(win ? win->scale_denom : 1);
+        // what the grouped path takes: jpezy_decode_jpeg_batch's rule -- every baseline layout decode_mcu handles (1 or 3 components,
+        // sampling factors 1..4, at most 48 blocks per MCU), tables present, no restart interval, the scan bounds
+        bool fits = (fi.ncomp == 1 || fi.ncomp == 3) && fi.restart_interval == 0 && fi.blocks_per_mcu >= 1 && fi.blocks_per_mcu <= 48;
+        for (int q = 0; q < fi.ncomp && fits; ++q) fits = fi.H[q] >= 1 && fi.H[q] <= 4 && fi.V[q] >= 1 && fi.V[q] <= 4;
+        if (!fits || cd.setup.scan_pos >= len[i]) return;
+        for (int q = 0; q < fi.ncomp; ++q)
+            if (!(cd.setup.Td[q] >= 0 && cd.setup.Td[q] <= 2 && cd.setup.present[cd.setup.Td[q]] && cd.setup.present[4 + cd.setup.Td[q]])) return;
+        size_t ns = len[i] - cd.setup.scan_pos;
+        const size_t nblk = (size_t)fi.mcu_cols * fi.mcu_rows * (size_t)fi.blocks_per_mcu;
+        if (ns == 0 || nblk > 4 * len[i] || nblk >= 0xFFFFFFFFull) return;
+        ns = std::min(ns, nblk * 432 + 4096);          // a long tail behind the scan is not uploaded (see jpezy_read_jpeg_gpu)
+        if (ns >= 0xFFFFFFFFull) return;
+        cd.scan = data[i] + cd.setup.scan_pos; cd.n = ns; cd.nblk = nblk;
+        cd.good = true;
+    };
+    const auto t_head = std::chrono::steady_clock::now();
+    {
+        unsigned hwp = std::thread::hardware_concurrency();
+        const int nt = (int)std::max(1u, std::min<unsigned>(std::min<unsigned>(hwp ? hwp : 4u, 8u), (unsigned)(n + 15) / 16));
+        std::atomic<int> next{ 0 };
+        auto work = [&] { for (int i = next.fetch_add(1); i < n; i = next.fetch_add(1)) prep(i); };
+        Joiner pool;
+        for (int t = 1; t < nt; ++t) pool.start(work);
+        work();
+    }
+    if (std::getenv("JPEZY_BATCH_DEBUG"))
+        std::fprintf(stderr, "  windows (%d files): %-28s %.3f ms\n", n, "headers + windows", std::chrono::duration<double>(std::chrono::steady_clock::now() - t_head).count() * 1e3);
+
+    // ---- the grouped path: by layout only; a group of one as well (no child context is needed for it, and one rule decides the path) ----
+    const SliceOut out = { row_stride, slot_stride, d_pix, bytes, blue_first ? 1 : 0, gray };
+    std::vector<char> taken((size_t)n, 0);
+    for (int a = 0; a < n; ++a) {
+        if (taken[(size_t)a] || !all[(size_t)a].good) continue;
+        std::vector<int> grp;
+        for (int k = a; k < n; ++k)
+            if (!taken[(size_t)k] && all[(size_t)k].good && same_layout(info[a], info[k])) { taken[(size_t)k] = 1; grp.push_back(k); }
+        // slices: coefficients (2 bytes each), the scan and the decoder's scratch over it (the scan, its unstuffed copy, 20 bytes of state
+        // per subsequence: below 4 bytes per scan byte) stay under ~1.5 GB, at most 512 files (jpezy_ctx_set_windows_slice_files: a fixed count)
+        const size_t max_files = c->w_slice_files > 0 ? (size_t)c->w_slice_files : 512;
+        for (size_t s0 = 0; s0 < grp.size();) {
+            std::vector<int> slice;
+            size_t mem = 0;
+            while (s0 < grp.size() && slice.size() < max_files) {
+                const Cand& cd = all[(size_t)grp[s0]];
+                const size_t need = cd.nblk * 128 + cd.n * 4 + 4096;
+                if (!slice.empty() && mem + need > ((size_t)3 << 29)) break;
+                mem += need;
+                slice.push_back(grp[s0++]);
+            }
+            std::vector<char> okv;
+            if (decode_slice(c, slice, all, info, out, okv) != JPEZY_OK) continue;          // (the per-file path reports what is wrong)
+            for (size_t k = 0; k < slice.size(); ++k)
+                if (okv[k]) { done[(size_t)slice[k]] = 1; status[slice[k]] = JPEZY_OK; ++c->b_last_fast; }
+        }
+    }
+
+    // ---- everything else file by file on the child contexts: restart intervals, streams that did not settle, irregular streams ----
+    std::vector<int> rest;
+    for (int i = 0; i < n; ++i) {
+        if (all[(size_t)i].st < 0) status[i] = all[(size_t)i].st;
+        else if (!done[(size_t)i]) rest.push_back(i);
+    }
+    if (!rest.empty()) {
+        unsigned hw = std::thread::hardware_concurrency();
+        if (hw == 0) hw = 4;
+        const int nw = (int)std::min<unsigned>(std::min<unsigned>((unsigned)rest.size(), hw), 8u);
+        while ((int)c->workers.size() < nw) {
+            jpezy_ctx* w = jpezy_ctx_create(c->device);
+            if (!w) return JPEZY_E_HIP;                                  // message set by jpezy_ctx_create
+            w->is_batch_child = true;
+            c->workers.push_back(w);
+        }
+        for (int k = 0; k < nw; ++k) {                                   // the definition has no inexact path: tolerance off, whatever the parent says
+            c->workers[(size_t)k]->h_min_bytes = c->h_min_bytes;
+            c->workers[(size_t)k]->dec_tolerance = 0;
+            c->workers[(size_t)k]->force_exact = 0;
+        }
+        auto one = [&](jpezy_ctx* w, int i) -> int {
+            const Cand& cd = all[(size_t)i];
+            if (int rc = read_coeffs(w, data[i], len[i], &info[i], kWho)) return rc;
+            const PackedLayout L = { bytes, { blue_first ? 2 : 0, 1, blue_first ? 0 : 2 }, row_stride, 0 };
+            // the region stage core, for a whole picture too (the full window): the defined arithmetic, straight into the slot
+            if (int rc = jpezy_internal_region_dev_core(w, DecodeSource::file((const int16_t*)w->out.p, info[i], gray),
+                                                        DecodeSink::packed(L, d_pix + (size_t)i * slot_stride), w->stream, cd.log2n, cd.rect))
+                return rc;
+            HIP_TRY(hipStreamSynchronize(w->stream));
+            return JPEZY_OK;
+        };
+        auto work = [&](int k) {
+            for (size_t q = (size_t)k; q < rest.size(); q += (size_t)nw) {
+                const int i = rest[q];
+                status[i] = one(c->workers[(size_t)k], i);
+                if (status[i] < 0) all[(size_t)i].msg = g_err;           // this thread's message
+            }
+        };
+        Joiner pool;
+        for (int k = 1; k < nw; ++k) pool.start(work, k);
+        work(0);
+    }
+    for (int i = 0; i < n; ++i)
+        if (status[i] < 0) return set_err(status[i], who + ": file " + std::to_string(i) + ": " + all[(size_t)i].msg);
+    return JPEZY_OK;
+}
+JPEZY_CATCH
+
+}  // extern "C"

@@ -267,6 +267,34 @@ struct RegionDecParams {
 };
 hipError_t launch_dequant_idct_region(const RegionDecParams& p, hipStream_t stream);
 
+// a batch of crop windows (jpezy_kernels_windows.hip): the windows of many files of ONE layout at ONE scale 8 / N in one launch; size, window,
+// destination and quantiser tables are per file.  One descriptor per file, 64 bytes, read with scalar loads.
+struct WindowDesc {
+    unsigned long long coeff_off;   // int16 offset of the file's first coefficient (the WHOLE file's coefficients lie there)
+    unsigned long long out_off;     // byte offset of the window's pixel (0, 0) behind WindowsParams::pix
+    int qset;                       // index of the file's dequantiser set
+    int mcu_cols;                   // MCU columns of the file
+    int x, y, w, h;                 // the window, in the coordinates of the picture at the launch's scale
+    int ux0, uy0, ucols;            // the MCUs that intersect it: columns [ux0, ux0 + ucols), rows from uy0
+    unsigned wg0;                   // index of the file's first workgroup; ascending over the table, workgroup wg0 + r * ucols + c = MCU (ux0 + c, uy0 + r)
+    unsigned pad[2];
+};
+static_assert(sizeof(WindowDesc) == 64, "one descriptor per 64-byte line");
+struct WindowsParams {
+    const int16_t* coeffs;
+    const int* qsets;               // [sets][3 comps][64] natural order: the de-duplicated dequantiser sets of the launch's files
+    const WindowDesc* desc;
+    uint8_t* pix;
+    unsigned n_desc, wg_base;       // wg_base: the first workgroup of this launch (set by the launcher)
+    size_t row_stride;
+    int log2n, ncomp, gray;
+    int ch[3], cv[3], hmax, vmax, blocks_per_mcu;
+    int blk_start[3];               // first block of each component inside an MCU
+    int level;                      // 128, or 2048 when SOF0 says precision != 8 (ref :654)
+    int pix_bytes, swap_rb;         // 3 or 4 bytes per pixel; swap_rb: blue is byte 0; byte 3 of a 32-bit pixel = 0xFF
+};
+hipError_t launch_dequant_idct_windows(const WindowsParams& p, unsigned long long total_wg, hipStream_t stream);
+
 // lossless transforms in the coefficient domain (jpezy_kernels_transform.hip; include/jpezy_hip.h, LOSSLESS TRANSFORMS): every output
 // block is one source block, permuted (swap) and with some coefficients negated (mirror) -- pure data movement
 struct XformParams {

@@ -709,8 +709,9 @@ int jpezy_decode_jpeg_region_packed(jpezy_ctx* ctx, const uint8_t* data, size_t 
  *                 the grouped path delivered
  *   Synchronous   on return the pixels are complete in device memory.  Refused inside a stream capture
  *
- * NOT provided: host-memory, planar or YCC output; smooth upsampling of windows; resizing to arbitrary sizes; skipping the Huffman decoding
- * of MCUs outside a window (the whole scan of every file is decoded).
+ * NOT provided: host-memory, planar or YCC output; smooth upsampling of windows; skipping the Huffman decoding of MCUs outside a window (the
+ * whole scan of every file is decoded).  Windows of different sizes brought to ONE output size are the section after this one, BATCH OF
+ * WINDOWS, RESIZED.
  */
 typedef struct jpezy_window { jpezy_rect region; int scale_denom; } jpezy_window;
 /* Pure host function: the window of a W x H file as it will be decoded (whole-picture form resolved; win NULL: the whole picture at full
@@ -727,6 +728,75 @@ int jpezy_decode_windows_dev(jpezy_ctx* ctx, int n, const uint8_t* const* data, 
 /* Files per slice of the grouped path: 0 = automatic (at most 512, coefficients + scans + decoder scratch under ~1.5 GB), 1..512 = that many.
  * A test and measurement knob, per context; the bytes do not depend on it. */
 int jpezy_ctx_set_windows_slice_files(jpezy_ctx* ctx, int n);
+
+/*
+ * BATCH OF WINDOWS, RESIZED (one crop window of each of n files, every window of its own size, all brought to ONE out_w x out_h and left in
+ * device memory as one [n, out_h, out_w, bytes] tensor; optionally mirrored).  What random-resized-crop, a centre crop of the short side or a
+ * thumbnail ask for: the window decode of BATCH OF WINDOWS, unchanged, and a resampling stage behind it.  The definition is this project's
+ * own (restated in tests/resize_model.py) and is integer fixed point, so that it is exact without a guard band:
+ *
+ *   Filter        separable; the triangle filter, widened by the reduction ratio where an axis shrinks (antialiased), plain two-tap
+ *                 bilinear where it grows
+ *   Weights       one axis, in_size source samples to out_size output samples, in binary64 on the host, every operation separate and in
+ *                 this order (no fused multiply-add):
+ *                     scale = in_size / out_size      fs = max(scale, 1.0)      support = fs      ss = 1.0 / fs
+ *                 output index i:
+ *                     center = (i + 0.5) * scale
+ *                     first  = max(0, (int)(center - support + 0.5))      last = min(in_size, (int)(center + support + 0.5))
+ *                     count  = last - first
+ *                 j in [0, count):
+ *                     a   = |(j + first - center + 0.5) * ss|             w_j = a < 1 ? 1 - a : 0
+ *                     k_j = w_j / sum(w) when sum(w) != 0, else w_j       K_j = (int)(0.5 + k_j * 2^22)
+ *                 jpezy_resize_taps returns exactly these tables
+ *   Passes        horizontal first: t = clip((2^21 + sum_j K_j * src[first + j]) >> 22, 0, 255) per channel, a byte; the vertical pass is
+ *                 the same formula over t.  32-bit int accumulators; they cannot overflow for sizes up to 65535: the weights of one output
+ *                 sum to at most 2^22 + count / 2, count <= 131071, and 255 * (2^22 + 65536) + 2^21 < 2^31
+ *   Byte 3        of a 32-bit pixel is 0xFF and is not resampled
+ *   Identity      in_size == out_size gives the weights (2^22, 0): a pass returns its input, with no special case
+ *   Mirror        per file: output column i of a mirrored file is column out_w - 1 - i of the unmirrored result
+ *   Result        file k's out_w x out_h pixels equal the above applied to the bytes jpezy_decode_jpeg_region_packed returns for the file's
+ *                 window, gray, scale_denom and format.  Nothing about the window decode changes; chroma of the window is replicated as
+ *                 there.  For 3-byte pixels the result equals Pillow 12's Image.resize(size, BILINEAR) of the window byte for byte (its RGBA
+ *                 mode premultiplies alpha and is not the definition)
+ *   Window        as in BATCH OF WINDOWS; windows == NULL: whole pictures at full size.  jpezy_resize_pick_window turns a source rectangle
+ *                 in full-size coordinates into the window and the largest scale_denom that still leaves at least out_w x out_h pixels
+ *   Output        packed pixels in DEVICE memory: pixel (i, j) of file k at d_pix + k*slot_stride + j*row_stride + i*bytes.  All outputs
+ *                 have one size, so both strides may be 0 = tight (row_stride = out_w*bytes, slot_stride = out_h*row_stride)
+ *   Fit           checked once for the call: out_w*bytes <= row_stride (JPEZY_E_BADARG), (out_h-1)*row_stride + out_w*bytes <= slot_stride
+ *                 and n*slot_stride <= pix_cap (JPEZY_E_NOSPACE); nothing is written then
+ *   Bytes touched no byte outside a file's out_w*bytes x out_h rectangle is written: not row padding, not the rest of a slot, not the slot
+ *                 of a file that failed
+ *   Per file      info[k], placed[k] (the SOURCE window as decoded) and status[k] as in BATCH OF WINDOWS; a window outside the picture is
+ *                 JPEZY_E_BADARG for that file, the other files are complete
+ *   Paths         those of BATCH OF WINDOWS (grouped by layout; child contexts for restart intervals, streams that do not settle and
+ *                 irregular streams), each with the resampling launch behind it: per slice of a group, per file on a child context.  Same
+ *                 bytes either way.  jpezy_ctx_last_batch_fast_count and jpezy_ctx_set_windows_slice_files act as there.  The decoded
+ *                 windows of a slice lie in a scratch of the context (rows of the slice's widest window, the sum of the windows' heights)
+ *                 that counts against the slice bound
+ *   Synchronous   on return the pixels are complete in device memory.  Refused inside a stream capture
+ *
+ * NOT provided: float or planar (CHW) output and normalisation; other filters (nearest, bicubic); a per-file output size; a vertical
+ * mirror; host-memory output; smooth chroma upsampling of the source window.
+ */
+/* Pure host function: the tables of one axis.  *ksize = 2 * (int)ceil(support) + 1 (>= every count); first[out_size], count[out_size],
+ * weight[out_size][ksize], zero behind count.  first, count and weight all NULL: *ksize only.  Sizes outside 1..65535: JPEZY_E_BADARG;
+ * weight_cap (in elements) < out_size * ksize: JPEZY_E_NOSPACE. */
+int jpezy_resize_taps(int in_size, int out_size, int* ksize, int* first, int* count, int32_t* weight, size_t weight_cap);
+/* Pure host function: src, a rectangle in the FULL-SIZE picture (inside W x H, else JPEZY_E_BADARG), as a window for an output of
+ * out_w x out_h: s = the largest of 8, 4, 2, 1 with src.w / s >= out_w and src.h / s >= out_h (integer division), else 1;
+ * *win = {{src.x / s, src.y / s, max(1, src.w / s), max(1, src.h / s)}, s}.  That window always lies inside the picture at 1/s
+ * (jpezy_scaled_size is ceil(W / s)).  Its edges are src's rounded down to the grid of s: the crop's edges move by less than s full-size
+ * pixels.  A caller that wants an exact crop passes its own jpezy_window at scale_denom 1. */
+int jpezy_resize_pick_window(int W, int H, const jpezy_rect* src, int out_w, int out_h, jpezy_window* win);
+/* The batch (stands in for n calls of decoder/jpezy_decoder.hpp:76-134 with the region stage and a resampling the reference does not have;
+ * the definition above is this project's own).  jpezy_decode_windows_dev's arguments and contracts, and: mirror_x n flags or NULL (none);
+ * every file writes exactly out_w x out_h pixels.  Refused before the context is looked at, in this order: n < 0, (n == 0 is JPEZY_OK,)
+ * null arrays, format, out_w / out_h outside 1..65535, row_stride beyond 32 bits or below out_w*bytes, slot_stride too small
+ * (JPEZY_E_NOSPACE), n*slot_stride > pix_cap (JPEZY_E_NOSPACE). */
+int jpezy_decode_windows_resized_dev(jpezy_ctx* ctx, int n, const uint8_t* const* data, const size_t* len, int gray,
+                                     const jpezy_window* windows, const uint8_t* mirror_x, int out_w, int out_h, int format, size_t row_stride,
+                                     size_t slot_stride, uint8_t* d_pix, size_t pix_cap, jpezy_frame_info* info, jpezy_rect* placed,
+                                     int* status);
 
 /*
  * PLANAR YCbCr 4:2:0 SAMPLES (I420 / YV12 / NV12 / NV21) IN AND OUT.  The file format is full-range BT.601 YCbCr sampled 2x2, 1x1, 1x1: a

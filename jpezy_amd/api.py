@@ -144,6 +144,10 @@ ABI = [
     ("jpezy_window_fit", C.c_int, [C.c_int, C.c_int, _vp, C.c_int, C.c_size_t, C.c_size_t, _vp]),
     ("jpezy_decode_windows_dev", C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, C.c_size_t, C.c_size_t, _vp, C.c_size_t, _vp, _vp, _vp]),
     ("jpezy_ctx_set_windows_slice_files", C.c_int, [_vp, C.c_int]),
+    ("jpezy_resize_taps", C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), _vp, _vp, _vp, C.c_size_t]),
+    ("jpezy_resize_pick_window", C.c_int, [C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp]),
+    ("jpezy_decode_windows_resized_dev", C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, _vp,
+                                                   C.c_size_t, _vp, _vp, _vp]),
     ("jpezy_ycc_chroma_size", C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("jpezy_ycc_component_size", C.c_int, [C.POINTER(FrameInfo), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("jpezy_fdct_quant_ycc_dev", C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int,
@@ -311,6 +315,26 @@ def window_fit(W, H, window, format=PIX_RGB24, row_stride=0, slot_stride=0):
     placed = Rect()
     _check(load_library().jpezy_window_fit(int(W), int(H), C.byref(_window(window)), int(format), int(row_stride), int(slot_stride), C.byref(placed)))
     return placed.x, placed.y, placed.w, placed.h
+
+
+def resize_taps(in_size, out_size):
+    """(first, count, weights) of one axis of decode_windows_resized_dev's resampling: int32 arrays [out_size], [out_size] and
+    [out_size, ksize] (integer weights of 22 fraction bits, zero behind count); the definition is in include/jpezy_hip.h (jpezy_resize_taps)"""
+    lib = load_library()
+    ksize = C.c_int()
+    _check(lib.jpezy_resize_taps(int(in_size), int(out_size), C.byref(ksize), None, None, None, 0))
+    first, count = np.zeros(int(out_size), np.int32), np.zeros(int(out_size), np.int32)
+    weights = np.zeros((int(out_size), ksize.value), np.int32)
+    _check(lib.jpezy_resize_taps(int(in_size), int(out_size), C.byref(ksize), _np_ptr(first), _np_ptr(count), _np_ptr(weights), weights.size))
+    return first, count, weights
+
+
+def resize_pick_window(W, H, src, out_w, out_h):
+    """((x, y, w, h), scale): the window of decode_windows_resized_dev for the rectangle src = (x, y, w, h) of the full-size W x H picture and
+    an output of out_w x out_h -- the largest scale of 8, 4, 2, 1 that leaves at least out_w x out_h pixels (jpezy_resize_pick_window)"""
+    win = Window()
+    _check(load_library().jpezy_resize_pick_window(int(W), int(H), C.byref(_rect(src)), int(out_w), int(out_h), C.byref(win)))
+    return (win.region.x, win.region.y, win.region.w, win.region.h), win.scale_denom
 
 
 def transform_geometry(op, W, H, sampling=SAMPLING_420, trim=False):
@@ -693,6 +717,43 @@ class Context:
         cap = d_out.untyped_storage().nbytes() - d_out.storage_offset() if n else 0
         rc = lib.jpezy_decode_windows_dev(self._h, n, data, lens, int(gray), wins, int(format), row, slot, d_out.data_ptr() if n else None, cap,
                                           infos, placed, status)
+        if rc != 0 and raise_on_error:
+            _check(rc)
+        out = []
+        for i in range(n):
+            fi = FrameInfo()
+            C.memmove(C.byref(fi), C.byref(infos[i]), C.sizeof(FrameInfo))
+            out.append((fi, (placed[i].x, placed[i].y, placed[i].w, placed[i].h), status[i]))
+        return out
+
+    def decode_windows_resized_dev(self, files, d_out, windows=None, mirror=None, format=PIX_RGB24, gray=False, raise_on_error=True):
+        """one crop window of each of the .jpg byte strings in `files`, every window of its own size, each resampled (triangle filter,
+        antialiased where it shrinks; include/jpezy_hip.h, BATCH OF WINDOWS, RESIZED) to the out_h x out_w of d_out, a torch uint8 tensor
+        [n, out_h, out_w, bytes] under decode_windows_dev's stride rules.  windows: as there (resize_pick_window gives the window and scale
+        for a rectangle of the full-size picture); mirror: None or one flag per file, the file's output columns reversed.  Every file writes
+        exactly d_out[k]; nothing else of d_out's storage is written.  Returns a list of (FrameInfo, (x, y, w, h), status), the rectangle
+        being the source window as decoded; synchronous (jpezy_decode_windows_resized_dev)."""
+        lib = load_library()
+        n = len(files)
+        nb = pixel_bytes(format)
+        if d_out.dim() != 4 or str(d_out.dtype) != "torch.uint8" or not d_out.is_cuda or d_out.device.index != self.device:
+            raise JpezyError("decode_windows_resized_dev: d_out must be a uint8 tensor [n, out_h, out_w, bytes] on the context's device")
+        if d_out.shape[0] != n or d_out.shape[3] != nb or (n and (d_out.stride(3) != 1 or d_out.stride(2) != nb)):
+            raise JpezyError(f"decode_windows_resized_dev: d_out must hold {n} slots of pixels of {nb} contiguous bytes")
+        if windows is not None and len(windows) != n:
+            raise JpezyError("decode_windows_resized_dev: one window per file")
+        if mirror is not None and len(mirror) != n:
+            raise JpezyError("decode_windows_resized_dev: one mirror flag per file")
+        arrs = [np.frombuffer(bytes(f), dtype=np.uint8) for f in files]
+        data = (C.c_void_p * max(n, 1))(*[a.ctypes.data for a in arrs])
+        lens = (C.c_size_t * max(n, 1))(*[a.size for a in arrs])
+        wins = (Window * max(n, 1))(*[_window(w) for w in windows]) if windows is not None else None
+        flags = (C.c_uint8 * max(n, 1))(*[1 if m else 0 for m in mirror]) if mirror is not None else None
+        infos, placed, status = (FrameInfo * max(n, 1))(), (Rect * max(n, 1))(), (C.c_int * max(n, 1))()
+        row, slot = (d_out.stride(1), d_out.stride(0)) if n else (0, 0)
+        cap = d_out.untyped_storage().nbytes() - d_out.storage_offset() if n else 0
+        rc = lib.jpezy_decode_windows_resized_dev(self._h, n, data, lens, int(gray), wins, flags, int(d_out.shape[2]), int(d_out.shape[1]), int(format),
+                                                  row, slot, d_out.data_ptr() if n else None, cap, infos, placed, status)
         if rc != 0 and raise_on_error:
             _check(rc)
         out = []

@@ -5,7 +5,7 @@
 // jpezy_capi_scaled.hip (reduced-size decode), jpezy_capi_ycc.hip (planar YCbCr 4:2:0 samples in and out), jpezy_capi_sampling.hip (chroma
 // sampling as an argument of the encoder's entries), jpezy_capi_transform.hip (lossless transforms in the coefficient domain),
 // jpezy_capi_smooth.hip (smooth chroma upsampling in the decoder), jpezy_capi_windows.hip (a batch of crop windows into device memory),
-// jpezy_capi_multi.hip (the multi-GPU handle).
+// jpezy_capi_resized.hip (the same batch resized to one output size: tap tables and the second stage), jpezy_capi_multi.hip (the multi-GPU handle).
 // What the decode entries share beyond this -- the description of a transform stage, the geometry of a layout, the file-decode driver,
 // the head of the device entries -- is in jpezy_capi_decode.h, which includes this file.
 #pragma once
@@ -216,6 +216,9 @@ struct jpezy_ctx {
     PinBuf w_pin;                  // jpezy_decode_windows_dev: pinned staging of a slice's dequantiser sets and window descriptors
     DevBuf w_tab;                  // ... and their device copy
     int w_slice_files = 0;         // files per slice of its grouped path; 0: automatic (jpezy_ctx_set_windows_slice_files)
+    DevBuf w_scr;                  // jpezy_decode_windows_resized_dev: a slice's (a child context: one file's) windows as decoded, packed pixels
+    PinBuf r_pin;                  // ... pinned staging of a launch's resample descriptors and tap tables
+    DevBuf r_tab;                  // ... and their device copy
     DevBuf e_hdr;                  // JFIF header bytes of the device-resident variant (cached per W, H, comment)
     jpezy_host::HostPipe pipe;     // staging ring of the streaming host-buffer entry points (jpezy_hostpipe.h)
     size_t host_chunk_bytes = 4u << 20;   // bytes of input per chunk of that pipeline (jpezy_ctx_set_host_chunk_bytes)

@@ -1,16 +1,29 @@
 // jpezy_capi_windows.hip -- the C-ABI of include/jpezy_hip.h, part 13: a batch of crop windows (one window of each of n files, sizes and
-// quantiser tables mixed, packed pixels left in device memory).  Files of one LAYOUT go through the batch form of the GPU Huffman decoder
+// quantiser tables mixed, packed pixels left in device memory), and part 14's entry: the same batch with every window resized to one output
+// size (jpezy_decode_windows_resized_dev; one driver serves both).  Files of one LAYOUT go through the batch form of the GPU Huffman decoder
 // together, whatever their sizes (a stream carries its own block count and coefficient offset), and through ONE launch of windows_kernel
 // per scale present (jpezy_kernels_windows.hip); what that path declines goes file by file: read_coeffs and the region stage core on a
-// child context, straight into the file's slot.  Nothing is downloaded.
+// child context, straight into the file's slot.  Nothing is downloaded.  Resized: the same launches write a context-owned scratch of packed
+// pixels, every file by its own height, and one launch of resample_kernel per slice (jpezy_kernels_resized.hip) writes the slots.
 #include "jpezy_capi_decode.h"
 
 namespace {
 
 const char* const kWho = "decode_windows_dev";
+const char* const kWhoResized = "decode_windows_resized_dev";
 
-// the window as it will be decoded (whole-picture form resolved), inside the picture, fitting its slot; W, H, bytes already checked
-int resolve_window(const char* who, int W, int H, const jpezy_window* win, int bytes, size_t row_stride, size_t slot_stride, jpezy_rect* placed)
+// the resized call's own arguments (null: jpezy_decode_windows_dev)
+struct Resize {
+    int out_w, out_h;
+    const uint8_t* mirror_x;            // [n] or null
+};
+
+inline size_t up4(size_t v) { return (v + 3) & ~(size_t)3; }
+
+// the window as it will be decoded (whole-picture form resolved), inside the picture, fitting its slot (fit: the resized call's windows
+// have no slot of their own size to fit); W, H, bytes already checked
+int resolve_window(const char* who, int W, int H, const jpezy_window* win, int bytes, size_t row_stride, size_t slot_stride, jpezy_rect* placed,
+                   bool fit = true)
 {
     const int scale = win ? win->scale_denom : 1;
     if (log2n_of(scale) < 0) return bad_scale(who);
@@ -21,6 +34,7 @@ int resolve_window(const char* who, int W, int H, const jpezy_window* win, int b
     }
     if (int rc = region_inside(who, W, H, scale, &r)) return rc;
     if (placed) *placed = r;
+    if (!fit) return JPEZY_OK;
     const size_t tight = (size_t)r.w * (size_t)bytes;
     if (tight > row_stride || (size_t)(r.h - 1) * row_stride + tight > slot_stride)
         return set_err(JPEZY_E_NOSPACE, std::string(who) + ": a window of " + std::to_string(r.w) + " x " + std::to_string(r.h) + " pixels of " +
@@ -70,11 +84,13 @@ struct SliceOut {
     size_t row_stride, slot_stride;
     uint8_t* d_pix;
     int bytes, swap_rb, gray;
+    const Resize* rz;
 };
 
 // One slice of a group (one layout; sizes, windows, scales and tables mixed): the Huffman decoding of all files in one sequence of
 // launches, then one windows_kernel launch per scale present over the files that settled.  ok[k] = 1 for those; the others are left to
-// the per-file path, whose verdict is the authoritative one.
+// the per-file path, whose verdict is the authoritative one.  Resized (out.rz): the launches write c->w_scr, rows the slice's widest window
+// (rounded up to 4 bytes) apart, every file's rows behind the file before; one resample_kernel launch then fills the slots.
 int decode_slice(jpezy_ctx* c, const std::vector<int>& files, const std::vector<Cand>& all, const jpezy_frame_info* info, const SliceOut& out,
                  std::vector<char>& ok)
 {
@@ -121,6 +137,23 @@ int decode_slice(jpezy_ctx* c, const std::vector<int>& files, const std::vector<
     if (int rc = c->b_coef.reserve(coef_elems * sizeof(int16_t))) return rc;
     if (int rc = jpezy_internal_huffdec_streams(c, streams, setups, setup_usable, jpezy_internal_stream_geom(gi), (int16_t*)c->b_coef.p, coef_elems, ok, lap, per_lane)) return rc;
 
+    // resized: where the windows go in the scratch
+    std::vector<unsigned long long> scr_off(nf, 0);
+    size_t scr_stride = 0;
+    if (out.rz) {
+        size_t wmax = 0, rows = 0;
+        for (unsigned k = 0; k < nf; ++k)
+            if (ok[k]) wmax = std::max(wmax, (size_t)all[(size_t)files[k]].rect.w);
+        scr_stride = up4(wmax * (size_t)out.bytes);
+        for (unsigned k = 0; k < nf; ++k) {
+            if (!ok[k]) continue;
+            scr_off[k] = (unsigned long long)rows * scr_stride;
+            rows += (size_t)all[(size_t)files[k]].rect.h;
+        }
+        if (rows)
+            if (int rc = c->w_scr.reserve(rows * scr_stride)) return rc;
+    }
+
     // descriptor tables: one per launch (a scale; a second one for a scale whose workgroups would not fit 32 bits), the dequantiser sets
     // de-duplicated in front of them -- built in the context's pinned staging, one upload
     struct Launch { int log2n; unsigned long long total; std::vector<WindowDesc> desc; };
@@ -140,7 +173,7 @@ int decode_slice(jpezy_ctx* c, const std::vector<int>& files, const std::vector<
         WindowDesc d;
         std::memset(&d, 0, sizeof d);
         d.coeff_off = streams[k].coeff_off;
-        d.out_off = (unsigned long long)i * out.slot_stride;
+        d.out_off = out.rz ? scr_off[k] : (unsigned long long)i * out.slot_stride;
         d.qset = (int)qs;
         d.mcu_cols = info[i].mcu_cols;
         d.x = cd.rect.x; d.y = cd.rect.y; d.w = cd.rect.w; d.h = cd.rect.h;
@@ -181,8 +214,8 @@ int decode_slice(jpezy_ctx* c, const std::vector<int>& files, const std::vector<
     }
     p.coeffs = (const int16_t*)c->b_coef.p;
     p.qsets = (const int*)c->w_tab.p;
-    p.pix = out.d_pix;
-    p.row_stride = out.row_stride;
+    p.pix = out.rz ? (uint8_t*)c->w_scr.p : out.d_pix;
+    p.row_stride = out.rz ? scr_stride : out.row_stride;
     p.pix_bytes = out.bytes; p.swap_rb = out.swap_rb;
     Event ev0, ev1;                                                   // JPEZY_BATCH_DEBUG: the kernel's own time, from device events
     if (dbg) {
@@ -204,8 +237,28 @@ int decode_slice(jpezy_ctx* c, const std::vector<int>& files, const std::vector<
                          launches[l].total, (double)ms);
         }
     }
+    if (out.rz) {
+        lap("windows transform");
+        std::vector<ResampleJob> jobs;
+        for (unsigned k = 0; k < nf; ++k) {
+            if (!ok[k]) continue;
+            const int i = files[k];
+            const jpezy_rect& r = all[(size_t)i].rect;
+            jobs.push_back({ scr_off[k], (unsigned long long)i * out.slot_stride, r.w, r.h, out.rz->mirror_x && out.rz->mirror_x[i] ? 1 : 0 });
+        }
+        if (int rc = jpezy_internal_resample(c, jobs, (const uint8_t*)c->w_scr.p, (unsigned)scr_stride, out.d_pix, out.row_stride, out.rz->out_w,
+                                             out.rz->out_h, out.bytes, s, dbg ? (hipEvent_t)ev0 : nullptr, dbg ? (hipEvent_t)ev1 : nullptr))
+            return rc;
+        if (dbg) {
+            float ms = 0;
+            HIP_TRY(hipEventSynchronize(ev1));
+            HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
+            std::fprintf(stderr, "  windows slice (%u files): tables up + resample_kernel<%d>, %zu files to %d x %d: %.3f ms (device events)\n", nf, out.bytes,
+                         jobs.size(), out.rz->out_w, out.rz->out_h, (double)ms);
+        }
+    }
     HIP_TRY(hipStreamSynchronize(s));                                 // (the pinned staging is the next slice's; the call is synchronous anyway)
-    lap("windows transform");
+    lap(out.rz ? "resample" : "windows transform");
     return JPEZY_OK;
 }
 
@@ -230,21 +283,18 @@ int jpezy_ctx_set_windows_slice_files(jpezy_ctx* c, int n)
     return JPEZY_OK;
 }
 
-int jpezy_decode_windows_dev(jpezy_ctx* c, int n, const uint8_t* const* data, const size_t* len, int gray, const jpezy_window* windows, int format,
-                             size_t row_stride, size_t slot_stride, uint8_t* d_pix, size_t pix_cap, jpezy_frame_info* info, jpezy_rect* placed,
-                             int* status)
-try {
-    const std::string who = kWho;
-    // what needs no device, before the context is looked at
-    if (n < 0) return set_err(JPEZY_E_BADARG, who + ": n must not be negative");
-    if (n == 0) return JPEZY_OK;
-    if (!data || !len || !info || !status || !d_pix) return set_err(JPEZY_E_BADARG, who + ": null pointer");
-    const int bytes = jpezy_pixel_bytes(format);
-    if (bytes < 0) return set_err(JPEZY_E_BADARG, who + ": unknown pixel format");
-    if (row_stride == 0 || slot_stride == 0)
-        return set_err(JPEZY_E_BADARG, who + ": row_stride and slot_stride must be given (windows differ in size: there is no 0 = tight)");
-    if (row_stride > 0xFFFFFFFFull) return set_err(JPEZY_E_BADARG, who + ": row_stride must fit in 32 bits");
-    if (slot_stride > pix_cap / (size_t)n) return set_err(JPEZY_E_NOSPACE, who + ": n * slot_stride exceeds pix_cap");
+}  // extern "C"
+
+namespace {
+
+// The driver of both entries, behind their own argument checks (n >= 1, arrays, format, strides, capacity): headers and windows, the grouped
+// path slice by slice, the per-file path, the verdict.  rz null: every window into its slot as it is (jpezy_decode_windows_dev); otherwise
+// every window resampled to rz->out_w x rz->out_h (jpezy_decode_windows_resized_dev).
+int windows_driver(jpezy_ctx* c, const char* who_c, int n, const uint8_t* const* data, const size_t* len, int gray, const jpezy_window* windows,
+                   int format, int bytes, size_t row_stride, size_t slot_stride, uint8_t* d_pix, jpezy_frame_info* info, jpezy_rect* placed,
+                   int* status, const Resize* rz)
+{
+    const std::string who = who_c;
     if (!c) return set_err(JPEZY_E_BADARG, "null context");
     HIP_TRY(hipSetDevice(c->device));
     {
@@ -269,7 +319,7 @@ try {
         const jpezy_frame_info& fi = info[i];
         if (int rc = check_wh(fi.width, fi.height)) { cd.st = rc; cd.msg = g_err; return; }
         const jpezy_window* win = windows ? &windows[i] : nullptr;
-        const int fit = resolve_window(kWho, fi.width, fi.height, win, bytes, row_stride, slot_stride, &cd.rect);
+        const int fit = resolve_window(who_c, fi.width, fi.height, win, bytes, row_stride, slot_stride, &cd.rect, rz == nullptr);
         if (placed && (fit == JPEZY_OK || fit == JPEZY_E_NOSPACE)) placed[i] = cd.rect;       // (a window inside the picture is reported, fitting or not)
         if (fit) { cd.st = fit; cd.msg = g_err; return; }
         cd.log2n = log2n_of(win ? win->scale_denom : 1);
@@ -302,7 +352,7 @@ try {
         std::fprintf(stderr, "  windows (%d files): %-28s %.3f ms\n", n, "headers + windows", std::chrono::duration<double>(std::chrono::steady_clock::now() - t_head).count() * 1e3);
 
     // ---- the grouped path: by layout only; a group of one as well (no child context is needed for it, and one rule decides the path) ----
-    const SliceOut out = { row_stride, slot_stride, d_pix, bytes, blue_first ? 1 : 0, gray };
+    const SliceOut out = { row_stride, slot_stride, d_pix, bytes, blue_first ? 1 : 0, gray, rz };
     std::vector<char> taken((size_t)n, 0);
     for (int a = 0; a < n; ++a) {
         if (taken[(size_t)a] || !all[(size_t)a].good) continue;
@@ -310,16 +360,18 @@ try {
         for (int k = a; k < n; ++k)
             if (!taken[(size_t)k] && all[(size_t)k].good && same_layout(info[a], info[k])) { taken[(size_t)k] = 1; grp.push_back(k); }
         // slices: coefficients (2 bytes each), the scan and the decoder's scratch over it (the scan, its unstuffed copy, 20 bytes of state
-        // per subsequence: below 4 bytes per scan byte) stay under ~1.5 GB, at most 512 files (jpezy_ctx_set_windows_slice_files: a fixed count)
+        // per subsequence: below 4 bytes per scan byte) stay under ~1.5 GB, at most 512 files (jpezy_ctx_set_windows_slice_files: a fixed count).
+        // Resized: the scratch of the slice's windows (rows of its widest window, the sum of their heights) counts against the same bound
         const size_t max_files = c->w_slice_files > 0 ? (size_t)c->w_slice_files : 512;
         for (size_t s0 = 0; s0 < grp.size();) {
             std::vector<int> slice;
-            size_t mem = 0;
+            size_t mem = 0, wmax = 0, rows = 0;
             while (s0 < grp.size() && slice.size() < max_files) {
                 const Cand& cd = all[(size_t)grp[s0]];
                 const size_t need = cd.nblk * 128 + cd.n * 4 + 4096;
-                if (!slice.empty() && mem + need > ((size_t)3 << 29)) break;
-                mem += need;
+                const size_t wm = rz ? std::max(wmax, (size_t)cd.rect.w) : 0, rw = rz ? rows + (size_t)cd.rect.h : 0;
+                if (!slice.empty() && mem + need + up4(wm * (size_t)bytes) * rw > ((size_t)3 << 29)) break;
+                mem += need; wmax = wm; rows = rw;
                 slice.push_back(grp[s0++]);
             }
             std::vector<char> okv;
@@ -352,12 +404,23 @@ try {
         }
         auto one = [&](jpezy_ctx* w, int i) -> int {
             const Cand& cd = all[(size_t)i];
-            if (int rc = read_coeffs(w, data[i], len[i], &info[i], kWho)) return rc;
-            const PackedLayout L = { bytes, { blue_first ? 2 : 0, 1, blue_first ? 0 : 2 }, row_stride, 0 };
+            if (int rc = read_coeffs(w, data[i], len[i], &info[i], who_c)) return rc;
+            // resized: the window into the child's scratch, rows rounded up to 4 bytes, then the one-entry form of the second stage
+            const size_t scr_stride = up4((size_t)cd.rect.w * (size_t)bytes);
+            if (rz)
+                if (int rc = w->w_scr.reserve(scr_stride * (size_t)cd.rect.h)) return rc;
+            const PackedLayout L = { bytes, { blue_first ? 2 : 0, 1, blue_first ? 0 : 2 }, rz ? scr_stride : row_stride, 0 };
             // the region stage core, for a whole picture too (the full window): the defined arithmetic, straight into the slot
             if (int rc = jpezy_internal_region_dev_core(w, DecodeSource::file((const int16_t*)w->out.p, info[i], gray),
-                                                        DecodeSink::packed(L, d_pix + (size_t)i * slot_stride), w->stream, cd.log2n, cd.rect))
+                                                        DecodeSink::packed(L, rz ? (uint8_t*)w->w_scr.p : d_pix + (size_t)i * slot_stride), w->stream,
+                                                        cd.log2n, cd.rect))
                 return rc;
+            if (rz) {
+                const std::vector<ResampleJob> job = { { 0, (unsigned long long)i * slot_stride, cd.rect.w, cd.rect.h, rz->mirror_x && rz->mirror_x[i] ? 1 : 0 } };
+                if (int rc = jpezy_internal_resample(w, job, (const uint8_t*)w->w_scr.p, (unsigned)scr_stride, d_pix, row_stride, rz->out_w, rz->out_h, bytes,
+                                                     w->stream))
+                    return rc;
+            }
             HIP_TRY(hipStreamSynchronize(w->stream));
             return JPEZY_OK;
         };
@@ -375,6 +438,55 @@ try {
     for (int i = 0; i < n; ++i)
         if (status[i] < 0) return set_err(status[i], who + ": file " + std::to_string(i) + ": " + all[(size_t)i].msg);
     return JPEZY_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int jpezy_decode_windows_dev(jpezy_ctx* c, int n, const uint8_t* const* data, const size_t* len, int gray, const jpezy_window* windows, int format,
+                             size_t row_stride, size_t slot_stride, uint8_t* d_pix, size_t pix_cap, jpezy_frame_info* info, jpezy_rect* placed,
+                             int* status)
+try {
+    const std::string who = kWho;
+    // what needs no device, before the context is looked at
+    if (n < 0) return set_err(JPEZY_E_BADARG, who + ": n must not be negative");
+    if (n == 0) return JPEZY_OK;
+    if (!data || !len || !info || !status || !d_pix) return set_err(JPEZY_E_BADARG, who + ": null pointer");
+    const int bytes = jpezy_pixel_bytes(format);
+    if (bytes < 0) return set_err(JPEZY_E_BADARG, who + ": unknown pixel format");
+    if (row_stride == 0 || slot_stride == 0)
+        return set_err(JPEZY_E_BADARG, who + ": row_stride and slot_stride must be given (windows differ in size: there is no 0 = tight)");
+    if (row_stride > 0xFFFFFFFFull) return set_err(JPEZY_E_BADARG, who + ": row_stride must fit in 32 bits");
+    if (slot_stride > pix_cap / (size_t)n) return set_err(JPEZY_E_NOSPACE, who + ": n * slot_stride exceeds pix_cap");
+    return windows_driver(c, kWho, n, data, len, gray, windows, format, bytes, row_stride, slot_stride, d_pix, info, placed, status, nullptr);
+}
+JPEZY_CATCH
+
+int jpezy_decode_windows_resized_dev(jpezy_ctx* c, int n, const uint8_t* const* data, const size_t* len, int gray, const jpezy_window* windows,
+                                     const uint8_t* mirror_x, int out_w, int out_h, int format, size_t row_stride, size_t slot_stride,
+                                     uint8_t* d_pix, size_t pix_cap, jpezy_frame_info* info, jpezy_rect* placed, int* status)
+try {
+    const std::string who = kWhoResized;
+    // what needs no device, before the context is looked at
+    if (n < 0) return set_err(JPEZY_E_BADARG, who + ": n must not be negative");
+    if (n == 0) return JPEZY_OK;
+    if (!data || !len || !info || !status || !d_pix) return set_err(JPEZY_E_BADARG, who + ": null pointer");
+    const int bytes = jpezy_pixel_bytes(format);
+    if (bytes < 0) return set_err(JPEZY_E_BADARG, who + ": unknown pixel format");
+    if (out_w < 1 || out_h < 1 || out_w > 65535 || out_h > 65535) return set_err(JPEZY_E_BADARG, who + ": out_w and out_h must be in 1..65535");
+    const size_t tight = (size_t)out_w * (size_t)bytes;
+    if (row_stride == 0) row_stride = tight;
+    if (row_stride > 0xFFFFFFFFull) return set_err(JPEZY_E_BADARG, who + ": row_stride must fit in 32 bits");
+    if (row_stride < tight) return set_err(JPEZY_E_BADARG, who + ": row_stride smaller than out_w * bytes per pixel");
+    if (slot_stride == 0) slot_stride = (size_t)out_h * row_stride;
+    if (slot_stride < (size_t)(out_h - 1) * row_stride + tight)
+        return set_err(JPEZY_E_NOSPACE, who + ": an output of " + std::to_string(out_w) + " x " + std::to_string(out_h) + " pixels of " + std::to_string(bytes) +
+                                            " bytes does not fit a slot of " + std::to_string(slot_stride) + " bytes with rows " +
+                                            std::to_string(row_stride) + " apart");
+    if (slot_stride > pix_cap / (size_t)n) return set_err(JPEZY_E_NOSPACE, who + ": n * slot_stride exceeds pix_cap");
+    const Resize rz = { out_w, out_h, mirror_x };
+    return windows_driver(c, kWhoResized, n, data, len, gray, windows, format, bytes, row_stride, slot_stride, d_pix, info, placed, status, &rz);
 }
 JPEZY_CATCH
 

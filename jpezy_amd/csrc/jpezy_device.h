@@ -295,6 +295,34 @@ struct WindowsParams {
 };
 hipError_t launch_dequant_idct_windows(const WindowsParams& p, unsigned long long total_wg, hipStream_t stream);
 
+// a batch of windows, resized (jpezy_kernels_resized.hip; include/jpezy_hip.h, BATCH OF WINDOWS, RESIZED): the packed pixels of MANY windows
+// of different sizes, each resampled to the launch's out_w x out_h.  One descriptor per file; a workgroup is one tile of kResampleTileW x
+// kResampleTileH output pixels of one file and finds its file as windows_kernel's do.
+constexpr int kResampleTileW = 64, kResampleTileH = 16;
+struct ResampleDesc {
+    unsigned long long src_off;     // byte offset of the source window's pixel (0, 0) behind ResampleParams::src (a multiple of 4)
+    unsigned long long dst_off;     // byte offset of the file's output pixel (0, 0) behind ResampleParams::dst
+    unsigned xfc, xw, yfc, yw;      // the file's four tap tables, as indices into ResampleParams::taps: first | count << 16 per output index,
+                                    // and the integer weights [out][k]
+    int w, h;                       // the source window (what the tables were built for; the kernel needs neither for its addresses)
+    int kx, ky;                     // weights per output column / row in the tables (ksize)
+    int mirror;                     // output column i is column out_w - 1 - i of the unmirrored result
+    unsigned wg0;                   // index of the file's first workgroup, ascending over the table
+    unsigned pad[2];
+};
+static_assert(sizeof(ResampleDesc) == 64, "one descriptor per 64-byte line");
+struct ResampleParams {
+    const uint8_t* src;             // packed pixels of pix_bytes each, rows src_stride apart (a multiple of 4), every file's by its own height
+    const int* taps;                // the launch's tap tables
+    const ResampleDesc* desc;
+    uint8_t* dst;
+    unsigned n_desc, wg_base;       // wg_base: the first workgroup of this launch (set by the launcher)
+    unsigned src_stride, dst_stride;
+    int out_w, out_h;
+    int pix_bytes;                  // 3 or 4; byte 3 of a 32-bit pixel is written as 0xFF and not read
+};
+hipError_t launch_resample(const ResampleParams& p, unsigned long long total_wg, hipStream_t stream);
+
 // lossless transforms in the coefficient domain (jpezy_kernels_transform.hip; include/jpezy_hip.h, LOSSLESS TRANSFORMS): every output
 // block is one source block, permuted (swap) and with some coefficients negated (mirror) -- pure data movement
 struct XformParams {

@@ -1055,9 +1055,10 @@ long jpezy_transform_jpeg(jpezy_ctx* ctx, const uint8_t* data, size_t len, int o
  *                 (jpezy_kernels_smooth.hip) in generic_rgb_kernel's place.  jpezy_ctx_set_decode_tolerance has nothing to act on.
  *   Refused       precision != 8 with JPEZY_UPSAMPLE_SMOOTH: JPEZY_E_UNSUPPORTED, the context stays usable.
  *
- * NOT provided: smooth with reduced-size or region decode; jpezy_decode_jpeg_batch; a fused one-pass kernel for jpezy's own layout (it
+ * NOT provided here: jpezy_decode_jpeg_batch; a fused one-pass kernel for jpezy's own layout (it
  * would need a halo from the neighbouring MCUs); 12-bit files; the host-buffer jpezy_dequant_idct* entries; a box-average decimation in
- * the encoder (the natural follow-up: it would make the encoder's own files centred).
+ * the encoder (the natural follow-up: it would make the encoder's own files centred).  Region decode, reduced sizes and the batches of
+ * windows take the mode through SMOOTH UPSAMPLING OF WINDOWS below.
  */
 enum jpezy_upsampling { JPEZY_UPSAMPLE_NEAREST = 0, JPEZY_UPSAMPLE_SMOOTH = 1 };
 /* jpezy_dequant_idct_generic_batch_dev with the upsampling chosen (stands in for decoder/jpezy_decoder.hpp:504-578, 645-676; the reference
@@ -1086,6 +1087,51 @@ int jpezy_decode_jpeg_upsampling(jpezy_ctx* ctx, const uint8_t* data, size_t len
  * only; pix_cap < (H-1)*row_stride + W*bytes: JPEZY_E_NOSPACE.  JPEZY_UPSAMPLE_NEAREST: jpezy_decode_jpeg_packed. */
 int jpezy_decode_jpeg_upsampling_packed(jpezy_ctx* ctx, const uint8_t* data, size_t len, int gray, int upsampling, jpezy_frame_info* info,
                                         int format, size_t row_stride, uint8_t* pix, size_t pix_cap);
+
+/*
+ * SMOOTH UPSAMPLING OF WINDOWS.  The chroma upsampling above as a property of the window decode: one window of one file
+ * (jpezy_*_region_upsampling*), a batch of windows and a batch of windows resized (jpezy_ctx_set_windows_upsampling), at full size and at
+ * 1/2, 1/4, 1/8, for any layout.  JPEZY_UPSAMPLE_NEAREST stays the default and is handed to the existing entry, byte for byte.  With
+ * JPEZY_UPSAMPLE_SMOOTH, let s = scale_denom in {1, 2, 4, 8}, N = 8 / s and Ws x Hs = jpezy_scaled_size(W, H, s):
+ *
+ *   Smoothed      the rule of CHROMA UPSAMPLING, unchanged: hmax % H_c == 0, vmax % V_c == 0, (fx, fy) = (hmax / H_c, vmax / V_c) one of
+ *                 (2,1), (1,2), (2,2).  Every other component is placed exactly as the (scaled) nearest decode places it: replication,
+ *                 later blocks overwrite earlier ones, unclamped samples.
+ *   Native plane  P_s of a smoothed component is wc_s x hc_s = ceil(Ws / fx) x ceil(Hs / fy) (libjpeg's downsampled_width of the reduced
+ *                 picture; at s = 1 the wc x hc above).  Block (bx, by) of the component's own block grid -- block (bx % H_c, by % V_c) of MCU
+ *                 (bx / H_c, by / V_c) -- gives the N x N samples at (bx*N, by*N); a sample is ref_int(sum / 4 + 128) over the N x N
+ *                 low-frequency corner in the reduced-size decode's order (v outer, u inner, left to right in binary64; REDUCED-SIZE DECODE),
+ *                 clamped to 0..255.  At s = 1 this is P.
+ *   Filter        the formulas above applied to P_s for X < Ws, Y < Hs; coordinates outside P_s clamp to [0, wc_s-1] x [0, hc_s-1], the
+ *                 plane's true extent, not the padded block.
+ *   Colour        make_rgb / revise_value and gray as always.
+ *   Window        {x, y, w, h} is rows y .. y+h, columns x .. x+w of that picture; the window checks are jpezy_region_check's.
+ *
+ * Consequences: at s = 1 the result is byte for byte the slice of what jpezy_decode_jpeg_upsampling[_packed] returns; a file with no smoothed
+ * component gives byte for byte the existing region decode at every scale.  12-bit files: JPEZY_E_UNSUPPORTED ("8-bit").
+ * For s != 1 NO OUTSIDE REFERENCE EXISTS: at reduced sizes libjpeg does not filter at all, it gives chroma a larger inverse DCT
+ * (jdmaster.c, per-component DCT_scaled_size).  One filter at every scale, over the planes the reduced decode already defines, is this
+ * project's own rule (restated in tests/region_smooth_model.py).
+ * Kernels: region_smooth_kernel / windows_smooth_kernel (jpezy_kernels_region_smooth.hip) in region_kernel's / windows_kernel's place: one
+ * launch, one workgroup per MCU that intersects the window, no intermediate in device memory.  A window that is the whole picture runs the
+ * same kernel (there is no smooth reduced-size entry to hand it to).
+ *
+ * NOT provided: the mode in jpezy::Decoder / the jpezy_decode CLI together with --scale / --region (they keep refusing it); planar or
+ * host-memory batches of windows; libjpeg-style IDCT-scaled chroma at reduced sizes; 12-bit files.
+ */
+/* The four region entries with the upsampling chosen -- jpezy_dequant_idct_region_upsampling_dev, jpezy_dequant_idct_region_upsampling_packed_dev,
+ * jpezy_decode_jpeg_region_upsampling, jpezy_decode_jpeg_region_upsampling_packed -- are declared in a header of their own, part of this one.
+ * The decode entries declared in THIS file are a closed set: what each of them answers to a fixed table of calls is recorded
+ * (tests/golden/decode_entry_errors.json) and replayed against every build.  The new entries' answers are pinned to the region entries'
+ * own instead, call by call (tests/test_region_smooth_abi.py). */
+#include "jpezy_hip_region_upsampling.h"
+/* The chroma upsampling of jpezy_decode_windows_dev and jpezy_decode_windows_resized_dev (no counterpart in the reference: a setting of this
+ * library's context): JPEZY_UPSAMPLE_NEAREST (the default: exactly the launches made without this setting) or JPEZY_UPSAMPLE_SMOOTH -- the
+ * grouped path launches windows_smooth_kernel, the per-file path the region stage in smooth mode; the resampling stage behind either is
+ * unchanged.  A 12-bit file then gets JPEZY_E_UNSUPPORTED for that file: its slot is untouched, the others are complete.  Any other value,
+ * or a null context: JPEZY_E_BADARG, the setting unchanged.  The getter returns the setting (JPEZY_E_BADARG for a null context). */
+int jpezy_ctx_set_windows_upsampling(jpezy_ctx* ctx, int upsampling);
+int jpezy_ctx_windows_upsampling(jpezy_ctx* ctx);
 
 #ifdef __cplusplus
 }

@@ -5,6 +5,7 @@ Naming follows the reference: `Encoder(property, r, g, b).encode(output_file, gr
 `Decoder(filename).decode(gray=...)` mirrors `jpezy::decoder<>::decode<MODE_TAG>()`
 (ref decoder/jpezy_decoder.hpp:39-134).  All compute goes through the C-ABI; nothing here touches oracle/.
 """
+import contextlib
 import ctypes as C
 import os
 from pathlib import Path
@@ -184,6 +185,21 @@ ABI = [
     ("jpezy_decode_jpeg_upsampling", C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.c_int, C.POINTER(FrameInfo), _vp, _vp, _vp, C.c_size_t]),
     ("jpezy_decode_jpeg_upsampling_packed", C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.c_int, C.POINTER(FrameInfo), C.c_int, C.c_size_t, _vp,
                                                       C.c_size_t]),
+    ("jpezy_ctx_set_windows_upsampling", C.c_int, [_vp, C.c_int]),
+    ("jpezy_ctx_windows_upsampling", C.c_int, [_vp]),
+]
+
+# include/jpezy_hip_region_upsampling.h (part of jpezy_hip.h): the region entries with the chroma upsampling as an argument.  ABI above is
+# jpezy_hip.h's own declarations, whose decode entries are a closed, recorded set (tests/decode_entry_table.py)
+ABI_REGION_UPSAMPLING = [
+    ("jpezy_dequant_idct_region_upsampling_dev", C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                           _vp, C.c_int, C.c_size_t, _vp, _vp, _vp, _vp]),
+    ("jpezy_dequant_idct_region_upsampling_packed_dev", C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                                  C.c_int, _vp, C.c_int, C.c_size_t, C.c_size_t, C.c_int, _vp, _vp]),
+    ("jpezy_decode_jpeg_region_upsampling", C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.c_int, C.c_int, _vp, C.POINTER(FrameInfo), _vp, _vp, _vp,
+                                                      C.c_size_t]),
+    ("jpezy_decode_jpeg_region_upsampling_packed", C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.c_int, C.c_int, _vp, C.POINTER(FrameInfo), C.c_int,
+                                                             C.c_size_t, _vp, C.c_size_t]),
 ]
 
 # chroma sampling of the encoder's *_sampling entry points: 4:2:0 (the reference's 2x2 / 1x1 / 1x1, everything as without the keyword)
@@ -227,7 +243,7 @@ def load_library():
         except Exception:
             pass
         lib = C.CDLL(str(_LIBPATH))
-        for name, res, args in ABI:
+        for name, res, args in ABI + ABI_REGION_UPSAMPLING:
             fn = getattr(lib, name)          # AttributeError if the library does not export the symbol
             fn.restype = res
             fn.argtypes = args
@@ -692,12 +708,16 @@ class Context:
             out.append((fi, planes[i][0][: sizes[i]], planes[i][1][: sizes[i]], planes[i][2][: sizes[i]]))
         return out
 
-    def decode_windows_dev(self, files, d_out, windows=None, format=PIX_RGB24, gray=False, raise_on_error=True):
+    def decode_windows_dev(self, files, d_out, windows=None, format=PIX_RGB24, gray=False, raise_on_error=True, upsampling=None):
         """one crop window of each of the .jpg byte strings in `files` (sizes mixed) as packed pixels into d_out, a torch uint8 tensor
         [n, Hs, Ws, bytes] on this context's device with stride(3) == 1 and stride(2) == bytes; rows are stride(1) apart, slots stride(0).
         windows: None (whole pictures at full size) or a list of None, (x, y, w, h) or ((x, y, w, h), scale), in the picture at 1/scale.
         File k's window lands at d_out[k, :h, :w]; nothing else of d_out is written.  Returns a list of (FrameInfo, (x, y, w, h), status);
-        synchronous (jpezy_decode_windows_dev)."""
+        synchronous (jpezy_decode_windows_dev).  upsampling: None (the context's setting, set_windows_upsampling) or a value that holds for
+        this call alone."""
+        if upsampling is not None:
+            with self._windows_upsampling(upsampling):
+                return self.decode_windows_dev(files, d_out, windows, format, gray, raise_on_error)
         lib = load_library()
         n = len(files)
         nb = pixel_bytes(format)
@@ -726,13 +746,18 @@ class Context:
             out.append((fi, (placed[i].x, placed[i].y, placed[i].w, placed[i].h), status[i]))
         return out
 
-    def decode_windows_resized_dev(self, files, d_out, windows=None, mirror=None, format=PIX_RGB24, gray=False, raise_on_error=True):
+    def decode_windows_resized_dev(self, files, d_out, windows=None, mirror=None, format=PIX_RGB24, gray=False, raise_on_error=True,
+                                   upsampling=None):
         """one crop window of each of the .jpg byte strings in `files`, every window of its own size, each resampled (triangle filter,
         antialiased where it shrinks; include/jpezy_hip.h, BATCH OF WINDOWS, RESIZED) to the out_h x out_w of d_out, a torch uint8 tensor
         [n, out_h, out_w, bytes] under decode_windows_dev's stride rules.  windows: as there (resize_pick_window gives the window and scale
         for a rectangle of the full-size picture); mirror: None or one flag per file, the file's output columns reversed.  Every file writes
         exactly d_out[k]; nothing else of d_out's storage is written.  Returns a list of (FrameInfo, (x, y, w, h), status), the rectangle
-        being the source window as decoded; synchronous (jpezy_decode_windows_resized_dev)."""
+        being the source window as decoded; synchronous (jpezy_decode_windows_resized_dev).  upsampling: as decode_windows_dev's (the
+        source window's chroma; the resampling behind it is the same)."""
+        if upsampling is not None:
+            with self._windows_upsampling(upsampling):
+                return self.decode_windows_resized_dev(files, d_out, windows, mirror, format, gray, raise_on_error)
         lib = load_library()
         n = len(files)
         nb = pixel_bytes(format)
@@ -766,6 +791,25 @@ class Context:
     def set_windows_slice_files(self, n):
         """files per slice of decode_windows_dev's grouped path; 0: automatic (a test and measurement knob)"""
         _check(load_library().jpezy_ctx_set_windows_slice_files(self._h, int(n)))
+
+    def set_windows_upsampling(self, upsampling):
+        """chroma upsampling of decode_windows_dev and decode_windows_resized_dev: UPSAMPLE_NEAREST (the default) or UPSAMPLE_SMOOTH
+        (jpezy_ctx_set_windows_upsampling); any other value raises and leaves the setting unchanged"""
+        _check(load_library().jpezy_ctx_set_windows_upsampling(self._h, int(upsampling)))
+
+    def windows_upsampling(self):
+        """the setting of set_windows_upsampling"""
+        return _check(load_library().jpezy_ctx_windows_upsampling(self._h))
+
+    @contextlib.contextmanager
+    def _windows_upsampling(self, upsampling):
+        """the setting for one call: set, and put back afterwards whatever the call did"""
+        before = self.windows_upsampling()
+        self.set_windows_upsampling(upsampling)
+        try:
+            yield
+        finally:
+            self.set_windows_upsampling(before)
 
     def set_huffdec_min_bytes(self, n):
         load_library().jpezy_ctx_set_huffdec_min_bytes(self._h, n)
@@ -1054,47 +1098,50 @@ class Context:
         _check(load_library().jpezy_dequant_idct_upsampling_dev(*head, n_frames, stride, d_r.data_ptr(), d_g.data_ptr(), d_b.data_ptr(), stream))
 
     # ---- region decode (a window (x, y, w, h) of the picture at 1/scale: the scaled decode, sliced; include/jpezy_hip.h) ----
-    def decode_jpeg_region(self, data, region, scale=1, gray=False):
+    def decode_jpeg_region(self, data, region, scale=1, gray=False, upsampling=UPSAMPLE_NEAREST):
         """.jpg bytes -> (FrameInfo, r, g, b) planes of w*h bytes: the window region = (x, y, w, h) of the picture at 1/scale.  The
-        FrameInfo keeps the file's own width and height."""
+        FrameInfo keeps the file's own width and height.  upsampling=UPSAMPLE_SMOOTH: 2:1 chroma through the triangle filter over its
+        plane at that scale (jpezy_decode_jpeg_region_upsampling)."""
         lib = load_library()
         arr = np.frombuffer(bytes(data), dtype=np.uint8)
         info, rect = FrameInfo(), _rect(region)
         n = max(rect.w, 0) * max(rect.h, 0)
         r, g, b = (np.empty(max(n, 1), dtype=np.uint8) for _ in range(3))
-        _check(lib.jpezy_decode_jpeg_region(self._h, _np_ptr(arr), arr.size, int(gray), int(scale), C.byref(rect), C.byref(info), _np_ptr(r),
-                                            _np_ptr(g), _np_ptr(b), n))
+        _check(lib.jpezy_decode_jpeg_region_upsampling(self._h, _np_ptr(arr), arr.size, int(gray), int(upsampling), int(scale), C.byref(rect),
+                                                       C.byref(info), _np_ptr(r), _np_ptr(g), _np_ptr(b), n))
         return info, r, g, b
 
-    def decode_jpeg_region_packed(self, data, region, scale=1, format=PIX_RGB24, gray=False):
-        """.jpg bytes -> (FrameInfo, uint8 array (h, w, C)) of interleaved pixels of the window; the fourth byte of a 32-bit format is 0xFF."""
+    def decode_jpeg_region_packed(self, data, region, scale=1, format=PIX_RGB24, gray=False, upsampling=UPSAMPLE_NEAREST):
+        """.jpg bytes -> (FrameInfo, uint8 array (h, w, C)) of interleaved pixels of the window; the fourth byte of a 32-bit format is 0xFF.
+        upsampling: as decode_jpeg_region's."""
         lib = load_library()
         nb = pixel_bytes(format)
         arr = np.frombuffer(bytes(data), dtype=np.uint8)
         info, rect = FrameInfo(), _rect(region)
         img = np.empty((max(rect.h, 1), max(rect.w, 1), nb), dtype=np.uint8)
-        _check(lib.jpezy_decode_jpeg_region_packed(self._h, _np_ptr(arr), arr.size, int(gray), int(scale), C.byref(rect), C.byref(info),
-                                                   int(format), 0, _np_ptr(img), img.size))
+        _check(lib.jpezy_decode_jpeg_region_upsampling_packed(self._h, _np_ptr(arr), arr.size, int(gray), int(upsampling), int(scale), C.byref(rect),
+                                                              C.byref(info), int(format), 0, _np_ptr(img), img.size))
         return info, img
 
     def dequant_idct_region_dev(self, d_coeffs, info, region, scale=1, d_r=None, d_g=None, d_b=None, gray=False, stream=None, n_frames=1,
-                                plane_stride=None, d_img=None, format=PIX_RGB24):
+                                plane_stride=None, d_img=None, format=PIX_RGB24, upsampling=UPSAMPLE_NEAREST):
         """the window region = (x, y, w, h) of the picture at 1/scale on device memory (torch tensors): the WHOLE frames' coefficients as
         read_jpeg_gpu leaves them -> planes of w*h bytes (n_frames frames plane_stride apart, default w*h), or, with d_img, packed pixels
-        written into a uint8 tensor (h, w, C) or (N, h, w, C) whose strides give the row and frame strides"""
+        written into a uint8 tensor (h, w, C) or (N, h, w, C) whose strides give the row and frame strides.  upsampling: as
+        decode_jpeg_region's (jpezy_dequant_idct_region_upsampling[_packed]_dev)."""
         import torch
         if stream is None:
             stream = torch.cuda.current_stream(d_coeffs.device).cuda_stream
         rect = _rect(region)
-        head = (*self._stage_head(d_coeffs.data_ptr(), info, gray), int(scale), C.byref(rect))
+        head = (*self._stage_head(d_coeffs.data_ptr(), info, gray), int(upsampling), int(scale), C.byref(rect))
         if d_img is not None:
             n, H, W, row, frame = self._packed_layout(d_img, pixel_bytes(format), "dequant_idct_region_dev")
             if (W, H) != (rect.w, rect.h):
                 raise JpezyError(f"dequant_idct_region_dev: d_img is {W} x {H}, the region is {rect.w} x {rect.h}")
-            _check(load_library().jpezy_dequant_idct_region_packed_dev(*head, int(format), row, frame, n, d_img.data_ptr(), stream))
+            _check(load_library().jpezy_dequant_idct_region_upsampling_packed_dev(*head, int(format), row, frame, n, d_img.data_ptr(), stream))
             return
         stride = plane_stride if plane_stride is not None else rect.w * rect.h
-        _check(load_library().jpezy_dequant_idct_region_dev(*head, n_frames, stride, d_r.data_ptr(), d_g.data_ptr(), d_b.data_ptr(), stream))
+        _check(load_library().jpezy_dequant_idct_region_upsampling_dev(*head, n_frames, stride, d_r.data_ptr(), d_g.data_ptr(), d_b.data_ptr(), stream))
 
     # ---- lossless transforms in the coefficient domain (include/jpezy_hip.h, LOSSLESS TRANSFORMS) ----
     def transform_jpeg(self, data, op, trim=False, comment=None):

@@ -158,8 +158,9 @@ inline int read_coeffs(jpezy_ctx* c, const uint8_t* data, size_t len, jpezy_fram
 }
 
 // Full: the fused kernel for jpezy's own layout, the any-layout pair for every other; Smooth: the any-layout pair with the smooth second
-// stage for every layout; Scaled, Region: the kernels of those parts
-enum class DecodeStage { Full, Scaled, Region, Smooth };
+// stage for every layout; Scaled, Region: the kernels of those parts; RegionSmooth: the region stage with smooth chroma upsampling
+// (jpezy_kernels_region_smooth.hip), at every scale and for the whole picture too
+enum class DecodeStage { Full, Scaled, Region, Smooth, RegionSmooth };
 
 struct DecodeRequest {
     const char* who;            // the entry: prefix of the messages
@@ -202,9 +203,10 @@ extern "C" {
 JPEZY_INTERNAL int jpezy_internal_generic_dev_core(jpezy_ctx* c, const DecodeSource& src, const DecodeSink& out, hipStream_t s, int upsampling);
 // reduced size, log2n = 2, 1, 0 (jpezy_capi_scaled.hip)
 JPEZY_INTERNAL int jpezy_internal_scaled_dev_core(jpezy_ctx* c, const DecodeSource& src, const DecodeSink& out, hipStream_t s, int log2n);
-// the window rg (inside the picture) at log2n = 3, 2, 1, 0; the sink is the window's (jpezy_capi_region.hip)
+// the window rg (inside the picture) at log2n = 3, 2, 1, 0; the sink is the window's; upsampling != 0 (JPEZY_UPSAMPLE_SMOOTH, 8-bit files):
+// region_smooth_kernel in region_kernel's place (jpezy_capi_region.hip)
 JPEZY_INTERNAL int jpezy_internal_region_dev_core(jpezy_ctx* c, const DecodeSource& src, const DecodeSink& out, hipStream_t s, int log2n,
-                                                  const jpezy_rect& rg);
+                                                  const jpezy_rect& rg, int upsampling = 0);
 // the second stage of the resized batch of windows: tap tables and descriptors of `jobs` through c->r_pin / c->r_tab, then resample_kernel
 // (jpezy_capi_resized.hip)
 JPEZY_INTERNAL int jpezy_internal_resample(jpezy_ctx* c, const std::vector<ResampleJob>& jobs, const uint8_t* d_src, unsigned src_stride,

@@ -595,7 +595,7 @@ int jpezy_internal_decode_file(jpezy_ctx* c, const uint8_t* data, size_t len, jp
 {
     const int rc = jpezy_read_jpeg_gpu(c, data, len, info, nullptr, 0);           // header only
     if (rc < 0) return rc;
-    if (rq.stage == DecodeStage::Smooth)
+    if (rq.stage == DecodeStage::Smooth || rq.stage == DecodeStage::RegionSmooth)
         if (int mode = upsampling_mode(rq.who, JPEZY_UPSAMPLE_SMOOTH, info->precision); mode < 0) return mode;
     if (!rq.dst[0] || !rq.dst[1] || !rq.dst[2]) return JPEZY_OK;
     const int W = info->width, H = info->height;
@@ -604,7 +604,7 @@ int jpezy_internal_decode_file(jpezy_ctx* c, const uint8_t* data, size_t len, jp
     int w, h;
     if (rq.region) {
         if (int rc2 = region_inside(rq.who, W, H, rq.scale_denom, rq.region)) return rc2;
-        if (whole_picture(W, H, rq.scale_denom, *rq.region))       // what a full request costs: the reduced-size entry, under its own name
+        if (rq.stage == DecodeStage::Region && whole_picture(W, H, rq.scale_denom, *rq.region))       // what a full request costs: the reduced-size entry, under its own name
             return rq.is_packed() ? jpezy_decode_jpeg_scaled_packed(c, data, len, rq.gray, rq.scale_denom, info, rq.format, rq.row_stride, rq.dst[0], rq.cap)
                                   : jpezy_decode_jpeg_scaled(c, data, len, rq.gray, rq.scale_denom, info, rq.dst[0], rq.dst[1], rq.dst[2], rq.cap);
         w = rq.region->w; h = rq.region->h;
@@ -644,6 +644,7 @@ int jpezy_internal_decode_file(jpezy_ctx* c, const uint8_t* data, size_t len, jp
     case DecodeStage::Smooth: rc2 = jpezy_internal_generic_dev_core(c, src, out, c->stream, 1); break;
     case DecodeStage::Scaled: rc2 = jpezy_internal_scaled_dev_core(c, src, out, c->stream, log2n_of(rq.scale_denom)); break;
     case DecodeStage::Region: rc2 = jpezy_internal_region_dev_core(c, src, out, c->stream, log2n_of(rq.scale_denom), *rq.region); break;
+    case DecodeStage::RegionSmooth: rc2 = jpezy_internal_region_dev_core(c, src, out, c->stream, log2n_of(rq.scale_denom), *rq.region, 1); break;
     }
     if (rc2) return rc2;
     if (!rq.is_packed()) {

@@ -54,7 +54,8 @@ bool jpezy_capi::whole_picture(int W, int H, int scale_denom, const jpezy_rect& 
 
 extern "C" {
 
-int jpezy_internal_region_dev_core(jpezy_ctx* c, const DecodeSource& src, const DecodeSink& out, hipStream_t s, int log2n, const jpezy_rect& rg)
+int jpezy_internal_region_dev_core(jpezy_ctx* c, const DecodeSource& src, const DecodeSink& out, hipStream_t s, int log2n, const jpezy_rect& rg,
+                                   int upsampling)
 {
     RegionDecParams p;
     if (int rc = decode_geometry(c, src, out, &p)) return rc;
@@ -64,6 +65,12 @@ int jpezy_internal_region_dev_core(jpezy_ctx* c, const DecodeSource& src, const 
     p.ux0 = rg.x / mw; p.ucols = (rg.x + rg.w - 1) / mw - p.ux0 + 1;
     p.uy0 = rg.y / mh; p.urows = (rg.y + rg.h - 1) / mh - p.uy0 + 1;
     if (int rc = upload_dequant(c, src, s)) return rc;
+    if (upsampling) {
+        int Ws, Hs;
+        (void)jpezy_scaled_size(src.W, src.H, 8 >> log2n, &Ws, &Hs);
+        HIP_TRY(launch_dequant_idct_region_smooth(p, Ws, Hs, s));
+        return JPEZY_OK;
+    }
     HIP_TRY(launch_dequant_idct_region(p, s));
     return JPEZY_OK;
 }
@@ -145,6 +152,93 @@ try {
     if (int rc = packed_layout(who, format, row_stride, 0, region->w, region->h, &L)) return rc;
     if (!c) return set_err(JPEZY_E_BADARG, "null context");
     DecodeRequest rq = DecodeRequest::packed(who, DecodeStage::Region, gray, format, row_stride, pix, pix_cap);
+    rq.scale_denom = scale_denom;
+    rq.region = region;
+    return jpezy_internal_decode_file(c, data, len, info, rq);
+}
+JPEZY_CATCH
+
+// ---- the same four entries with the chroma upsampling as an argument (include/jpezy_hip.h, SMOOTH UPSAMPLING OF WINDOWS).
+// JPEZY_UPSAMPLE_NEAREST is handed to the entry above as it is; JPEZY_UPSAMPLE_SMOOTH makes the same checks in the same order and runs
+// region_smooth_kernel (jpezy_kernels_region_smooth.hip) -- for the whole picture too: there is no smooth reduced-size entry to hand it to ----
+
+int jpezy_dequant_idct_region_upsampling_dev(jpezy_ctx* c, const int16_t* d_coeffs, const uint16_t qt[4][64], int ncomp, const uint8_t comp_h[3],
+                                             const uint8_t comp_v[3], const uint8_t comp_tq[3], int precision, int W, int H, int gray,
+                                             int upsampling, int scale_denom, const jpezy_rect* region, int n_frames, size_t plane_stride,
+                                             uint8_t* d_r, uint8_t* d_g, uint8_t* d_b, void* stream)
+{
+    const char* who = "dequant_idct_region_upsampling_dev";
+    const int mode = upsampling_mode(who, upsampling, precision);
+    if (mode < 0) return mode;
+    if (mode == 0)
+        return jpezy_dequant_idct_region_dev(c, d_coeffs, qt, ncomp, comp_h, comp_v, comp_tq, precision, W, H, gray, scale_denom, region, n_frames,
+                                             plane_stride, d_r, d_g, d_b, stream);
+    if (int rc = dev_null_check(who, { d_r, d_g, d_b })) return rc;
+    if (int rc = region_dev_head(who, d_coeffs, qt, comp_h, comp_v, comp_tq, W, H, scale_denom, region, n_frames)) return rc;
+    if (plane_stride < (size_t)region->w * region->h)
+        return set_err(JPEZY_E_BADARG, std::string(who) + ": plane_stride must hold a plane of w * h bytes");
+    if (int rc = dev_aligned_check(d_coeffs)) return rc;
+    if (!c) return set_err(JPEZY_E_BADARG, "null context");
+    HIP_TRY(hipSetDevice(c->device));
+    return jpezy_internal_region_dev_core(c, { d_coeffs, qt, ncomp, Layout(comp_h, comp_v, comp_tq), precision, W, H, gray, n_frames },
+                                          DecodeSink::planes(d_r, d_g, d_b, plane_stride), (hipStream_t)stream, log2n_of(scale_denom), *region, mode);
+}
+
+int jpezy_dequant_idct_region_upsampling_packed_dev(jpezy_ctx* c, const int16_t* d_coeffs, const uint16_t qt[4][64], int ncomp,
+                                                    const uint8_t comp_h[3], const uint8_t comp_v[3], const uint8_t comp_tq[3], int precision, int W,
+                                                    int H, int gray, int upsampling, int scale_denom, const jpezy_rect* region, int format,
+                                                    size_t row_stride, size_t frame_stride, int n_frames, uint8_t* d_pix, void* stream)
+{
+    const char* who = "dequant_idct_region_upsampling_packed_dev";
+    const int mode = upsampling_mode(who, upsampling, precision);
+    if (mode < 0) return mode;
+    if (mode == 0)
+        return jpezy_dequant_idct_region_packed_dev(c, d_coeffs, qt, ncomp, comp_h, comp_v, comp_tq, precision, W, H, gray, scale_denom, region, format,
+                                                    row_stride, frame_stride, n_frames, d_pix, stream);
+    if (int rc = dev_null_check(who, { d_pix })) return rc;
+    if (int rc = region_dev_head(who, d_coeffs, qt, comp_h, comp_v, comp_tq, W, H, scale_denom, region, n_frames)) return rc;
+    PackedLayout L;
+    if (int rc = packed_layout(who, format, row_stride, frame_stride, region->w, region->h, &L)) return rc;
+    if (int rc = dev_aligned_check(d_coeffs)) return rc;
+    if (!c) return set_err(JPEZY_E_BADARG, "null context");
+    HIP_TRY(hipSetDevice(c->device));
+    return jpezy_internal_region_dev_core(c, { d_coeffs, qt, ncomp, Layout(comp_h, comp_v, comp_tq), precision, W, H, gray, n_frames },
+                                          DecodeSink::packed(L, d_pix), (hipStream_t)stream, log2n_of(scale_denom), *region, mode);
+}
+
+// .jpg bytes -> the window's planes on the host; a 12-bit file is refused once its header is read (jpezy_internal_decode_file)
+int jpezy_decode_jpeg_region_upsampling(jpezy_ctx* c, const uint8_t* data, size_t len, int gray, int upsampling, int scale_denom,
+                                        const jpezy_rect* region, jpezy_frame_info* info, uint8_t* r, uint8_t* g, uint8_t* b, size_t plane_cap)
+try {
+    const char* who = "decode_jpeg_region_upsampling";
+    if (upsampling == JPEZY_UPSAMPLE_NEAREST) return jpezy_decode_jpeg_region(c, data, len, gray, scale_denom, region, info, r, g, b, plane_cap);
+    if (int mode = upsampling_mode(who, upsampling, 8); mode < 0) return mode;
+    if (!info || !region) return set_err(JPEZY_E_BADARG, std::string(who) + ": null pointer");
+    if (log2n_of(scale_denom) < 0) return bad_scale(who);
+    if (int rc = region_syntax(who, region)) return rc;
+    if (!c) return set_err(JPEZY_E_BADARG, "null context");
+    DecodeRequest rq = DecodeRequest::planes(who, DecodeStage::RegionSmooth, gray, r, g, b, plane_cap);
+    rq.scale_denom = scale_denom;
+    rq.region = region;
+    return jpezy_internal_decode_file(c, data, len, info, rq);
+}
+JPEZY_CATCH
+
+int jpezy_decode_jpeg_region_upsampling_packed(jpezy_ctx* c, const uint8_t* data, size_t len, int gray, int upsampling, int scale_denom,
+                                               const jpezy_rect* region, jpezy_frame_info* info, int format, size_t row_stride, uint8_t* pix,
+                                               size_t pix_cap)
+try {
+    const char* who = "decode_jpeg_region_upsampling_packed";
+    if (upsampling == JPEZY_UPSAMPLE_NEAREST)
+        return jpezy_decode_jpeg_region_packed(c, data, len, gray, scale_denom, region, info, format, row_stride, pix, pix_cap);
+    if (int mode = upsampling_mode(who, upsampling, 8); mode < 0) return mode;
+    if (!info || !region) return set_err(JPEZY_E_BADARG, std::string(who) + ": null pointer");
+    if (log2n_of(scale_denom) < 0) return bad_scale(who);
+    if (int rc = region_syntax(who, region)) return rc;
+    PackedLayout L;
+    if (int rc = packed_layout(who, format, row_stride, 0, region->w, region->h, &L)) return rc;
+    if (!c) return set_err(JPEZY_E_BADARG, "null context");
+    DecodeRequest rq = DecodeRequest::packed(who, DecodeStage::RegionSmooth, gray, format, row_stride, pix, pix_cap);
     rq.scale_denom = scale_denom;
     rq.region = region;
     return jpezy_internal_decode_file(c, data, len, info, rq);

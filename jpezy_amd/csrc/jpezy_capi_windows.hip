@@ -85,6 +85,7 @@ struct SliceOut {
     uint8_t* d_pix;
     int bytes, swap_rb, gray;
     const Resize* rz;
+    int smooth;                         // the context's windows upsampling: windows_smooth_kernel in windows_kernel's place
 };
 
 // One slice of a group (one layout; sizes, windows, scales and tables mixed): the Huffman decoding of all files in one sequence of
@@ -179,6 +180,12 @@ int decode_slice(jpezy_ctx* c, const std::vector<int>& files, const std::vector<
         d.x = cd.rect.x; d.y = cd.rect.y; d.w = cd.rect.w; d.h = cd.rect.h;
         d.ux0 = cd.rect.x / mw; d.ucols = (cd.rect.x + cd.rect.w - 1) / mw - d.ux0 + 1;
         d.uy0 = cd.rect.y / mh;
+        if (out.smooth) {               // the picture at this scale: the extent of the smoothed components' planes (inside the file's MCU grid)
+            int Ws, Hs;
+            (void)jpezy_scaled_size(info[i].width, info[i].height, 8 >> cd.log2n, &Ws, &Hs);
+            if (Ws > info[i].mcu_cols * mw || Hs > info[i].mcu_rows * mh) { ok[k] = 0; continue; }      // (no header gives this: left to the per-file path)
+            d.pad[0] = (unsigned)Ws; d.pad[1] = (unsigned)Hs;
+        }
         const unsigned long long wgs = (unsigned long long)d.ucols * (unsigned long long)((cd.rect.y + cd.rect.h - 1) / mh - d.uy0 + 1);
         Launch* L = nullptr;
         for (Launch& l : launches)
@@ -227,14 +234,14 @@ int decode_slice(jpezy_ctx* c, const std::vector<int>& files, const std::vector<
         p.desc = (const WindowDesc*)((const uint8_t*)c->w_tab.p + desc_at[l]);
         p.n_desc = (unsigned)launches[l].desc.size();
         if (dbg) HIP_TRY(hipEventRecord(ev0, s));
-        HIP_TRY(launch_dequant_idct_windows(p, launches[l].total, s));
+        HIP_TRY(out.smooth ? launch_dequant_idct_windows_smooth(p, launches[l].total, s) : launch_dequant_idct_windows(p, launches[l].total, s));
         if (dbg) {
             float ms = 0;
             HIP_TRY(hipEventRecord(ev1, s));
             HIP_TRY(hipEventSynchronize(ev1));
             HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
-            std::fprintf(stderr, "  windows slice (%u files): windows_kernel<%d>, %u files, %llu workgroups: %.3f ms (device events)\n", nf, 1 << p.log2n, p.n_desc,
-                         launches[l].total, (double)ms);
+            std::fprintf(stderr, "  windows slice (%u files): %s<%d>, %u files, %llu workgroups: %.3f ms (device events)\n", nf,
+                         out.smooth ? "windows_smooth_kernel" : "windows_kernel", 1 << p.log2n, p.n_desc, launches[l].total, (double)ms);
         }
     }
     if (out.rz) {
@@ -283,6 +290,21 @@ int jpezy_ctx_set_windows_slice_files(jpezy_ctx* c, int n)
     return JPEZY_OK;
 }
 
+int jpezy_ctx_set_windows_upsampling(jpezy_ctx* c, int upsampling)
+{
+    if (upsampling != JPEZY_UPSAMPLE_NEAREST && upsampling != JPEZY_UPSAMPLE_SMOOTH)
+        return set_err(JPEZY_E_BADARG, "windows_upsampling: upsampling must be JPEZY_UPSAMPLE_NEAREST or JPEZY_UPSAMPLE_SMOOTH");
+    if (!c) return set_err(JPEZY_E_BADARG, "null context");
+    c->w_upsampling = upsampling;
+    return JPEZY_OK;
+}
+
+int jpezy_ctx_windows_upsampling(jpezy_ctx* c)
+{
+    if (!c) return set_err(JPEZY_E_BADARG, "null context");
+    return c->w_upsampling;
+}
+
 }  // extern "C"
 
 namespace {
@@ -303,6 +325,7 @@ int windows_driver(jpezy_ctx* c, const char* who_c, int n, const uint8_t* const*
             return set_err(JPEZY_E_BADARG, who + ": the call is synchronous and cannot run inside a stream capture");
     }
     c->b_last_fast = 0;
+    const int smooth = c->w_upsampling == JPEZY_UPSAMPLE_SMOOTH ? 1 : 0;
     const bool blue_first = format == JPEZY_PIX_BGR24 || format == JPEZY_PIX_BGRA32;
     std::vector<Cand> all((size_t)n);
     std::vector<char> done((size_t)n, 0);
@@ -318,6 +341,8 @@ int windows_driver(jpezy_ctx* c, const char* who_c, int n, const uint8_t* const*
         cd.parsed = true;
         const jpezy_frame_info& fi = info[i];
         if (int rc = check_wh(fi.width, fi.height)) { cd.st = rc; cd.msg = g_err; return; }
+        if (smooth)                     // this file alone: its slot stays untouched, the others are decoded
+            if (int mode = upsampling_mode(who_c, JPEZY_UPSAMPLE_SMOOTH, fi.precision); mode < 0) { cd.st = mode; cd.msg = g_err; return; }
         const jpezy_window* win = windows ? &windows[i] : nullptr;
         const int fit = resolve_window(who_c, fi.width, fi.height, win, bytes, row_stride, slot_stride, &cd.rect, rz == nullptr);
         if (placed && (fit == JPEZY_OK || fit == JPEZY_E_NOSPACE)) placed[i] = cd.rect;       // (a window inside the picture is reported, fitting or not)
@@ -352,7 +377,7 @@ int windows_driver(jpezy_ctx* c, const char* who_c, int n, const uint8_t* const*
         std::fprintf(stderr, "  windows (%d files): %-28s %.3f ms\n", n, "headers + windows", std::chrono::duration<double>(std::chrono::steady_clock::now() - t_head).count() * 1e3);
 
     // ---- the grouped path: by layout only; a group of one as well (no child context is needed for it, and one rule decides the path) ----
-    const SliceOut out = { row_stride, slot_stride, d_pix, bytes, blue_first ? 1 : 0, gray, rz };
+    const SliceOut out = { row_stride, slot_stride, d_pix, bytes, blue_first ? 1 : 0, gray, rz, smooth };
     std::vector<char> taken((size_t)n, 0);
     for (int a = 0; a < n; ++a) {
         if (taken[(size_t)a] || !all[(size_t)a].good) continue;
@@ -413,7 +438,7 @@ int windows_driver(jpezy_ctx* c, const char* who_c, int n, const uint8_t* const*
             // the region stage core, for a whole picture too (the full window): the defined arithmetic, straight into the slot
             if (int rc = jpezy_internal_region_dev_core(w, DecodeSource::file((const int16_t*)w->out.p, info[i], gray),
                                                         DecodeSink::packed(L, rz ? (uint8_t*)w->w_scr.p : d_pix + (size_t)i * slot_stride), w->stream,
-                                                        cd.log2n, cd.rect))
+                                                        cd.log2n, cd.rect, smooth))
                 return rc;
             if (rz) {
                 const std::vector<ResampleJob> job = { { 0, (unsigned long long)i * slot_stride, cd.rect.w, cd.rect.h, rz->mirror_x && rz->mirror_x[i] ? 1 : 0 } };

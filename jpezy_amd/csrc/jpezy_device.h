@@ -277,7 +277,7 @@ struct WindowDesc {
     int x, y, w, h;                 // the window, in the coordinates of the picture at the launch's scale
     int ux0, uy0, ucols;            // the MCUs that intersect it: columns [ux0, ux0 + ucols), rows from uy0
     unsigned wg0;                   // index of the file's first workgroup; ascending over the table, workgroup wg0 + r * ucols + c = MCU (ux0 + c, uy0 + r)
-    unsigned pad[2];
+    unsigned pad[2];                // windows_smooth_kernel: Ws, Hs -- the file's picture at the launch's scale; windows_kernel reads neither
 };
 static_assert(sizeof(WindowDesc) == 64, "one descriptor per 64-byte line");
 struct WindowsParams {
@@ -294,6 +294,12 @@ struct WindowsParams {
     int pix_bytes, swap_rb;         // 3 or 4 bytes per pixel; swap_rb: blue is byte 0; byte 3 of a 32-bit pixel = 0xFF
 };
 hipError_t launch_dequant_idct_windows(const WindowsParams& p, unsigned long long total_wg, hipStream_t stream);
+
+// region and window-batch decode with smooth chroma upsampling (jpezy_kernels_region_smooth.hip; include/jpezy_hip.h, SMOOTH UPSAMPLING OF
+// WINDOWS): the same parameters and grids as the two launchers above, and the picture's size Ws x Hs at the launch's scale -- an argument
+// here, WindowDesc::pad[0], pad[1] of every file there.  Both must lie inside the file's MCU grid (jpezy_scaled_size of the file's size does)
+hipError_t launch_dequant_idct_region_smooth(const RegionDecParams& p, int Ws, int Hs, hipStream_t stream);
+hipError_t launch_dequant_idct_windows_smooth(const WindowsParams& p, unsigned long long total_wg, hipStream_t stream);
 
 // a batch of windows, resized (jpezy_kernels_resized.hip; include/jpezy_hip.h, BATCH OF WINDOWS, RESIZED): the packed pixels of MANY windows
 // of different sizes, each resampled to the launch's out_w x out_h.  One descriptor per file; a workgroup is one tile of kResampleTileW x

@@ -775,8 +775,9 @@ int jpezy_ctx_set_windows_slice_files(jpezy_ctx* ctx, int n);
  *                 that counts against the slice bound
  *   Synchronous   on return the pixels are complete in device memory.  Refused inside a stream capture
  *
- * NOT provided: float or planar (CHW) output and normalisation; other filters (nearest, bicubic); a per-file output size; a vertical
- * mirror; host-memory output; smooth chroma upsampling of the source window.
+ * NOT provided: other filters (nearest, bicubic); a per-file output size; a vertical mirror; host-memory output; smooth chroma upsampling
+ * of the source window.  What stood first on this list, float or planar (CHW) output and normalisation, is the section after this
+ * one: BATCH OF WINDOWS, TENSOR OUTPUT.
  */
 /* Pure host function: the tables of one axis.  *ksize = 2 * (int)ceil(support) + 1 (>= every count); first[out_size], count[out_size],
  * weight[out_size][ksize], zero behind count.  first, count and weight all NULL: *ksize only.  Sizes outside 1..65535: JPEZY_E_BADARG;
@@ -797,6 +798,58 @@ int jpezy_decode_windows_resized_dev(jpezy_ctx* ctx, int n, const uint8_t* const
                                      const jpezy_window* windows, const uint8_t* mirror_x, int out_w, int out_h, int format, size_t row_stride,
                                      size_t slot_stride, uint8_t* d_pix, size_t pix_cap, jpezy_frame_info* info, jpezy_rect* placed,
                                      int* status);
+
+/*
+ * BATCH OF WINDOWS, TENSOR OUTPUT (the resized batch written straight into the tensor a model takes: [n, C, out_h, out_w] in uint8, float32,
+ * float16 or bfloat16, planar, channels-last or any other strides, with (x/255 - mean)/std applied).  The resampling kernel holds every output
+ * pixel's three bytes in registers just before it stores them; the conversion happens there, so no second pass reads and writes the batch.
+ * Nothing about the window decode or the resampling changes.  The definition is this project's own (restated in
+ * tests/tensor_model.py):
+ *
+ *   Source bytes  for file k the out_w x out_h pixels that jpezy_decode_windows_resized_dev defines for the same files, windows, mirror flags,
+ *                 gray and windows-upsampling setting in a 3-byte format: b[k][y][x][c], c in 0..2, is byte c of the pixel.  JPEZY_PIX_RGB24
+ *                 puts R in channel 0, JPEZY_PIX_BGR24 puts B in channel 0.  The 32-bit formats are refused (JPEZY_E_BADARG): alpha is never
+ *                 a tensor channel
+ *   Shape         logical [n, C, out_h, out_w], C = channels, 3 or 1.  C == 1 needs gray != 0 (else JPEZY_E_BADARG) and is byte 0; with
+ *                 gray and C == 3 the three source bytes are equal, as they are in the packed form
+ *   Element type  JPEZY_DT_U8    the byte.  scale and bias must both be NULL (else JPEZY_E_BADARG): planar uint8
+ *                 JPEZY_DT_F32   v = (float)b * scale[c] + bias[c] in binary32, the multiplication and the addition each rounded to nearest
+ *                                even and NOT fused
+ *                 JPEZY_DT_F16   v converted to binary16, round to nearest even, subnormals kept, overflow to +-inf
+ *                 JPEZY_DT_BF16  the upper 16 bits of u + 0x7FFF + ((u >> 16) & 1), u being v's bit pattern
+ *   scale, bias   C floats each, both given or both NULL (NULL: scale 1, bias 0).  Every value is 0 or finite with a magnitude in
+ *                 [2^-100, 2^100] (else JPEZY_E_BADARG): then no binary32 step overflows or gives a subnormal, and NaN cannot occur
+ *   Placement     four strides IN ELEMENTS (sn, sc, sh, sw), all >= 0: element (k, c, y, x) lies at
+ *                 d_out + (k*sn + c*sc + y*sh + x*sw) * element size.  The strides must give every element a place of its own: of the
+ *                 dimensions of extent > 1, sorted by stride, the smallest stride is >= 1 and every other one >= the stride before it times
+ *                 that dimension's extent (else JPEZY_E_BADARG).  NCHW, NHWC, torch's channels_last, padded rows and padded slots are all
+ *                 instances of this one rule; the stride of a dimension of extent 1 is not looked at beyond its sign
+ *   Fit           sum over the dimensions of (extent - 1) * stride, + 1 <= cap_elems, else JPEZY_E_NOSPACE and nothing is written.  d_out
+ *                 is aligned to the element size (else JPEZY_E_BADARG)
+ *   Bytes touched only the elements named above: not row padding, not slot padding, not the slot of a file that failed, not the half of a
+ *                 4-byte word that belongs to a neighbouring element
+ *   Unchanged     info, placed, status, the per-file failure rule, the grouped / sliced / child-context paths, synchronisation and the
+ *                 refusal inside a stream capture are those of jpezy_decode_windows_resized_dev
+ *
+ * NOT provided: per-file output sizes; other filters; a vertical mirror; host-memory output; float output from the other decode entries.
+ */
+enum jpezy_dtype { JPEZY_DT_U8 = 0, JPEZY_DT_F32 = 1, JPEZY_DT_F16 = 2, JPEZY_DT_BF16 = 3 };
+/* Pure host function: scale[c] = (float)(1.0 / (255.0 * std[c])), bias[c] = (float)(-mean[c] / std[c]) for c < C (3 or 1), computed in binary64
+ * with every operation separate.  They are the two constants of (b/255 - mean)/std = b * (1 / (255 * std)) + (-mean / std), each evaluated in
+ * binary64 and rounded once to binary32; an element is then the multiplication and the addition above and nothing else.  It may differ in
+ * the last bits from a framework's three-step binary32 evaluation (divide by 255, subtract, divide).  JPEZY_E_BADARG: C, a null pointer, a std that is zero or not finite, a mean that is not finite (nothing
+ * is written then). */
+int jpezy_tensor_normalization(int C, const double* mean, const double* std, float* scale, float* bias);
+/* The batch (stands in for n calls of decoder/jpezy_decoder.hpp:76-134 with the region stage, a resampling and a conversion the reference does
+ * not have; the definition above is this project's own).  jpezy_decode_windows_resized_dev's arguments and contracts with the tensor's
+ * description in place of the two byte strides; d_out: device memory of cap_elems ELEMENTS.  Refused before the context is looked at, in
+ * this order: n < 0, (n == 0 is JPEZY_OK,) null arrays, an unknown format, a 32-bit format, out_w / out_h outside 1..65535, channels other
+ * than 3 or 1, channels == 1 without gray, an unknown dtype, scale without bias or bias without scale, JPEZY_DT_U8 with a scale, a scale or
+ * bias value outside the band, a negative stride, strides that overlap, cap_elems too small (JPEZY_E_NOSPACE), a misaligned d_out. */
+int jpezy_decode_windows_tensor_dev(jpezy_ctx* ctx, int n, const uint8_t* const* data, const size_t* len, int gray,
+                                    const jpezy_window* windows, const uint8_t* mirror_x, int out_w, int out_h, int format, int dtype,
+                                    int channels, const float* scale, const float* bias, int64_t sn, int64_t sc, int64_t sh, int64_t sw,
+                                    void* d_out, size_t cap_elems, jpezy_frame_info* info, jpezy_rect* placed, int* status);
 
 /*
  * PLANAR YCbCr 4:2:0 SAMPLES (I420 / YV12 / NV12 / NV21) IN AND OUT.  The file format is full-range BT.601 YCbCr sampled 2x2, 1x1, 1x1: a

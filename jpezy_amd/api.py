@@ -149,6 +149,9 @@ ABI = [
     ("jpezy_resize_pick_window", C.c_int, [C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp]),
     ("jpezy_decode_windows_resized_dev", C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, _vp,
                                                    C.c_size_t, _vp, _vp, _vp]),
+    ("jpezy_tensor_normalization", C.c_int, [C.c_int, _vp, _vp, _vp, _vp]),
+    ("jpezy_decode_windows_tensor_dev", C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp,
+                                                  C.c_int64, C.c_int64, C.c_int64, C.c_int64, _vp, C.c_size_t, _vp, _vp, _vp]),
     ("jpezy_ycc_chroma_size", C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("jpezy_ycc_component_size", C.c_int, [C.POINTER(FrameInfo), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("jpezy_fdct_quant_ycc_dev", C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int,
@@ -217,6 +220,9 @@ XFORM_TRIM = 1
 # enum jpezy_upsampling: how the decoder brings subsampled chroma to picture size -- replication (the reference's, the default) or the
 # triangle filter over the component's native plane (include/jpezy_hip.h, CHROMA UPSAMPLING)
 UPSAMPLE_NEAREST, UPSAMPLE_SMOOTH = 0, 1
+
+# enum jpezy_dtype: the element type of decode_windows_tensor_dev's output
+DT_U8, DT_F32, DT_F16, DT_BF16 = 0, 1, 2, 3
 E_UNSUPPORTED = -4          # JPEZY_E_UNSUPPORTED
 
 
@@ -351,6 +357,18 @@ def resize_pick_window(W, H, src, out_w, out_h):
     win = Window()
     _check(load_library().jpezy_resize_pick_window(int(W), int(H), C.byref(_rect(src)), int(out_w), int(out_h), C.byref(win)))
     return (win.region.x, win.region.y, win.region.w, win.region.h), win.scale_denom
+
+
+def tensor_normalization(mean, std):
+    """(scale, bias), float32 arrays of len(mean): scale[c] = 1 / (255 * std[c]) and bias[c] = -mean[c] / std[c], evaluated in binary64 and
+    rounded once -- the constants with which decode_windows_tensor_dev's byte * scale + bias is (byte / 255 - mean) / std
+    (jpezy_tensor_normalization).  mean and std: sequences of 3 or 1 numbers"""
+    mean, std = np.atleast_1d(np.asarray(mean, dtype=np.float64)), np.atleast_1d(np.asarray(std, dtype=np.float64))
+    if mean.ndim != 1 or mean.shape != std.shape:
+        raise JpezyError("tensor_normalization: mean and std must be sequences of one length")
+    scale, bias = np.zeros(mean.size, np.float32), np.zeros(mean.size, np.float32)
+    _check(load_library().jpezy_tensor_normalization(int(mean.size), _np_ptr(mean), _np_ptr(std), _np_ptr(scale), _np_ptr(bias)))
+    return scale, bias
 
 
 def transform_geometry(op, W, H, sampling=SAMPLING_420, trim=False):
@@ -779,6 +797,60 @@ class Context:
         cap = d_out.untyped_storage().nbytes() - d_out.storage_offset() if n else 0
         rc = lib.jpezy_decode_windows_resized_dev(self._h, n, data, lens, int(gray), wins, flags, int(d_out.shape[2]), int(d_out.shape[1]), int(format),
                                                   row, slot, d_out.data_ptr() if n else None, cap, infos, placed, status)
+        if rc != 0 and raise_on_error:
+            _check(rc)
+        out = []
+        for i in range(n):
+            fi = FrameInfo()
+            C.memmove(C.byref(fi), C.byref(infos[i]), C.sizeof(FrameInfo))
+            out.append((fi, (placed[i].x, placed[i].y, placed[i].w, placed[i].h), status[i]))
+        return out
+
+    def decode_windows_tensor_dev(self, files, d_out, windows=None, mirror=None, scale=None, bias=None, format=PIX_RGB24, gray=False,
+                                  raise_on_error=True, upsampling=None):
+        """decode_windows_resized_dev straight into the tensor a model takes (include/jpezy_hip.h, BATCH OF WINDOWS, TENSOR OUTPUT): d_out is a
+        torch tensor of LOGICAL shape [n, C, out_h, out_w] on this context's device, C = 3 or 1 (1 needs gray), dtype uint8, float32, float16
+        or bfloat16, with ANY strides -- torch.empty(n, 3, H, W), the same in channels_last and nhwc.permute(0, 3, 1, 2) all work; the dtype
+        and the strides are read from the tensor.  Element (k, c, y, x) is byte c of the resized pixel (format: PIX_RGB24 or PIX_BGR24), for
+        the float types byte * scale[c] + bias[c] in float32 (two roundings, never fused) converted to the dtype; scale and bias: None (1
+        and 0; required for uint8) or C numbers each, tensor_normalization(mean, std) gives them for (byte / 255 - mean) / std.  Only d_out's
+        own elements are written.  windows, mirror, upsampling and the returned list: as decode_windows_resized_dev's; synchronous
+        (jpezy_decode_windows_tensor_dev)."""
+        if upsampling is not None:
+            with self._windows_upsampling(upsampling):
+                return self.decode_windows_tensor_dev(files, d_out, windows, mirror, scale, bias, format, gray, raise_on_error)
+        import torch
+        lib = load_library()
+        n = len(files)
+        dtypes = {torch.uint8: DT_U8, torch.float32: DT_F32, torch.float16: DT_F16, torch.bfloat16: DT_BF16}
+        if d_out.dim() != 4 or d_out.dtype not in dtypes or not d_out.is_cuda or d_out.device.index != self.device:
+            raise JpezyError("decode_windows_tensor_dev: d_out must be a uint8, float32, float16 or bfloat16 tensor [n, C, out_h, out_w] on the "
+                             "context's device")
+        if d_out.shape[0] != n:
+            raise JpezyError(f"decode_windows_tensor_dev: d_out must hold {n} files")
+        if windows is not None and len(windows) != n:
+            raise JpezyError("decode_windows_tensor_dev: one window per file")
+        if mirror is not None and len(mirror) != n:
+            raise JpezyError("decode_windows_tensor_dev: one mirror flag per file")
+        if (scale is None) != (bias is None):
+            raise JpezyError("decode_windows_tensor_dev: scale and bias are given together or not at all")
+        channels = int(d_out.shape[1])
+        if scale is not None:
+            scale, bias = (np.ascontiguousarray(np.atleast_1d(np.asarray(v, dtype=np.float32))) for v in (scale, bias))
+            if scale.shape != (channels,) or bias.shape != (channels,):
+                raise JpezyError(f"decode_windows_tensor_dev: scale and bias must hold {channels} values each")
+        arrs = [np.frombuffer(bytes(f), dtype=np.uint8) for f in files]
+        data = (C.c_void_p * max(n, 1))(*[a.ctypes.data for a in arrs])
+        lens = (C.c_size_t * max(n, 1))(*[a.size for a in arrs])
+        wins = (Window * max(n, 1))(*[_window(w) for w in windows]) if windows is not None else None
+        flags = (C.c_uint8 * max(n, 1))(*[1 if m else 0 for m in mirror]) if mirror is not None else None
+        infos, placed, status = (FrameInfo * max(n, 1))(), (Rect * max(n, 1))(), (C.c_int * max(n, 1))()
+        # cap_elems: what the tensor's storage holds behind its first element
+        cap = d_out.untyped_storage().nbytes() // d_out.element_size() - d_out.storage_offset() if n else 0
+        rc = lib.jpezy_decode_windows_tensor_dev(self._h, n, data, lens, int(gray), wins, flags, int(d_out.shape[3]), int(d_out.shape[2]), int(format),
+                                                 dtypes[d_out.dtype], channels, _np_ptr(scale) if scale is not None else None,
+                                                 _np_ptr(bias) if bias is not None else None, *[int(v) for v in d_out.stride()],
+                                                 d_out.data_ptr() if n else None, cap, infos, placed, status)
         if rc != 0 and raise_on_error:
             _check(rc)
         out = []

@@ -189,6 +189,7 @@ JPEZY_INTERNAL int region_inside(const char* who, int W, int H, int scale_denom,
 JPEZY_INTERNAL bool whole_picture(int W, int H, int scale_denom, const jpezy_rect& r);
 
 // one file of a launch of resample_kernel: its w x h source pixels at src_off (a multiple of 4) behind the launch's source, its output at dst_off
+// (bytes; elements for a tensor output)
 struct ResampleJob {
     unsigned long long src_off, dst_off;
     int w, h, mirror;
@@ -208,10 +209,11 @@ JPEZY_INTERNAL int jpezy_internal_scaled_dev_core(jpezy_ctx* c, const DecodeSour
 JPEZY_INTERNAL int jpezy_internal_region_dev_core(jpezy_ctx* c, const DecodeSource& src, const DecodeSink& out, hipStream_t s, int log2n,
                                                   const jpezy_rect& rg, int upsampling = 0);
 // the second stage of the resized batch of windows: tap tables and descriptors of `jobs` through c->r_pin / c->r_tab, then resample_kernel
-// (jpezy_capi_resized.hip)
+// (jpezy_capi_resized.hip).  tensor: resample_tensor_kernel in its place -- d_dst is the tensor's first element, ResampleJob::dst_off counts
+// elements, dst_stride is not read and bytes is 3
 JPEZY_INTERNAL int jpezy_internal_resample(jpezy_ctx* c, const std::vector<ResampleJob>& jobs, const uint8_t* d_src, unsigned src_stride,
                                            uint8_t* d_dst, size_t dst_stride, int out_w, int out_h, int bytes, hipStream_t s, hipEvent_t t0 = nullptr,
-                                           hipEvent_t t1 = nullptr);
+                                           hipEvent_t t1 = nullptr, const TensorOut* tensor = nullptr);
 // header, output size, capacity, coefficients (read_coeffs), staging in c->in, the stage, download, synchronise (jpezy_capi_huffdec.hip).
 // No output pointer: header only.  c and info are not null.
 JPEZY_INTERNAL int jpezy_internal_decode_file(jpezy_ctx* c, const uint8_t* data, size_t len, jpezy_frame_info* info, const DecodeRequest& rq);

@@ -1,9 +1,11 @@
 // jpezy_capi_resized.hip -- the C-ABI of include/jpezy_hip.h, part 14: a batch of windows, resized.  The two pure host functions of the
-// section (the tap tables of one axis, the window and scale for a source rectangle) and the host side of the second stage: descriptors
+// section (the tap tables of one axis, the window and scale for a source rectangle), part 15's (scale and bias of a tensor output from mean
+// and std) and the host side of the second stage: descriptors
 // and tap tables of a launch of resample_kernel (jpezy_kernels_resized.hip), built in the context's pinned staging and uploaded in one
 // copy.  The entry itself, jpezy_decode_windows_resized_dev, shares its driver with jpezy_decode_windows_dev (jpezy_capi_windows.hip).
 #include "jpezy_capi_decode.h"
 #include "jpezy_resize_taps.h"
+#include "jpezy_tensor_layout.h"
 
 #include <map>
 #include <utility>
@@ -12,9 +14,10 @@ extern "C" {
 
 // One launch sequence over `jobs`: windows of packed pixels behind d_src (rows src_stride apart) to out_w x out_h pixels behind d_dst (rows
 // dst_stride apart).  Asynchronous on s; c->r_pin is the caller's to keep until s has passed the upload.  t0, t1 (both or neither): events
-// recorded in front of the upload and behind the last launch.
+// recorded in front of the upload and behind the last launch.  tensor: the launch is resample_tensor_kernel's, d_dst the tensor's first
+// element, ResampleJob::dst_off in elements, dst_stride not read (jpezy_device.h, TensorOut).
 int jpezy_internal_resample(jpezy_ctx* c, const std::vector<ResampleJob>& jobs, const uint8_t* d_src, unsigned src_stride, uint8_t* d_dst,
-                            size_t dst_stride, int out_w, int out_h, int bytes, hipStream_t s, hipEvent_t t0, hipEvent_t t1)
+                            size_t dst_stride, int out_w, int out_h, int bytes, hipStream_t s, hipEvent_t t0, hipEvent_t t1, const TensorOut* tensor)
 {
     if (jobs.empty()) return JPEZY_OK;
     // tap tables, one per distinct (source size, output size) of either axis: first | count << 16 per output index, then the weights
@@ -65,7 +68,7 @@ int jpezy_internal_resample(jpezy_ctx* c, const std::vector<ResampleJob>& jobs, 
     p.src_stride = src_stride; p.dst_stride = (unsigned)dst_stride;
     p.out_w = out_w; p.out_h = out_h;
     p.pix_bytes = bytes;
-    HIP_TRY(launch_resample(p, total, s));
+    HIP_TRY(tensor ? launch_resample_tensor(p, *tensor, total, s) : launch_resample(p, total, s));
     if (t1) HIP_TRY(hipEventRecord(t1, s));
     return JPEZY_OK;
 }
@@ -97,6 +100,16 @@ int jpezy_resize_pick_window(int W, int H, const jpezy_rect* src, int out_w, int
     for (int t = 8; t > 1; t >>= 1)
         if (src->w / t >= out_w && src->h / t >= out_h) { s = t; break; }
     *win = { { src->x / s, src->y / s, std::max(1, src->w / s), std::max(1, src->h / s) }, s };
+    return JPEZY_OK;
+}
+
+int jpezy_tensor_normalization(int C, const double* mean, const double* std_, float* scale, float* bias)
+{
+    const char* who = "tensor_normalization";
+    if (C != 1 && C != 3) return set_err(JPEZY_E_BADARG, std::string(who) + ": C must be 3 or 1");
+    if (!mean || !std_ || !scale || !bias) return set_err(JPEZY_E_BADARG, std::string(who) + ": null pointer");
+    if (!jpezy_host::tensor_normalization(C, mean, std_, scale, bias))
+        return set_err(JPEZY_E_BADARG, std::string(who) + ": every std must be finite and not zero, every mean finite");
     return JPEZY_OK;
 }
 

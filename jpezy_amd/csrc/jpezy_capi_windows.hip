@@ -4,18 +4,23 @@
 // together, whatever their sizes (a stream carries its own block count and coefficient offset), and through ONE launch of windows_kernel
 // per scale present (jpezy_kernels_windows.hip); what that path declines goes file by file: read_coeffs and the region stage core on a
 // child context, straight into the file's slot.  Nothing is downloaded.  Resized: the same launches write a context-owned scratch of packed
-// pixels, every file by its own height, and one launch of resample_kernel per slice (jpezy_kernels_resized.hip) writes the slots.
+// pixels, every file by its own height, and one launch of resample_kernel per slice (jpezy_kernels_resized.hip) writes the slots.  Part 15's
+// entry, jpezy_decode_windows_tensor_dev, is the resized call with resample_tensor_kernel (jpezy_kernels_resized_tensor.hip) as that launch.
 #include "jpezy_capi_decode.h"
+#include "jpezy_tensor_layout.h"
 
 namespace {
 
 const char* const kWho = "decode_windows_dev";
 const char* const kWhoResized = "decode_windows_resized_dev";
+const char* const kWhoTensor = "decode_windows_tensor_dev";
 
 // the resized call's own arguments (null: jpezy_decode_windows_dev)
 struct Resize {
     int out_w, out_h;
     const uint8_t* mirror_x;            // [n] or null
+    const TensorOut* tensor;            // null: packed pixels.  Otherwise the slots are a tensor's: d_pix is its first element, slot_stride
+                                        // its stride over files in ELEMENTS, row_stride is not read (jpezy_decode_windows_tensor_dev)
 };
 
 inline size_t up4(size_t v) { return (v + 3) & ~(size_t)3; }
@@ -254,14 +259,15 @@ int decode_slice(jpezy_ctx* c, const std::vector<int>& files, const std::vector<
             jobs.push_back({ scr_off[k], (unsigned long long)i * out.slot_stride, r.w, r.h, out.rz->mirror_x && out.rz->mirror_x[i] ? 1 : 0 });
         }
         if (int rc = jpezy_internal_resample(c, jobs, (const uint8_t*)c->w_scr.p, (unsigned)scr_stride, out.d_pix, out.row_stride, out.rz->out_w,
-                                             out.rz->out_h, out.bytes, s, dbg ? (hipEvent_t)ev0 : nullptr, dbg ? (hipEvent_t)ev1 : nullptr))
+                                             out.rz->out_h, out.bytes, s, dbg ? (hipEvent_t)ev0 : nullptr, dbg ? (hipEvent_t)ev1 : nullptr, out.rz->tensor))
             return rc;
         if (dbg) {
             float ms = 0;
             HIP_TRY(hipEventSynchronize(ev1));
             HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
-            std::fprintf(stderr, "  windows slice (%u files): tables up + resample_kernel<%d>, %zu files to %d x %d: %.3f ms (device events)\n", nf, out.bytes,
-                         jobs.size(), out.rz->out_w, out.rz->out_h, (double)ms);
+            std::fprintf(stderr, "  windows slice (%u files): tables up + %s<%d>, %zu files to %d x %d: %.3f ms (device events)\n", nf,
+                         out.rz->tensor ? "resample_tensor_kernel" : "resample_kernel", out.rz->tensor ? out.rz->tensor->dtype : out.bytes, jobs.size(),
+                         out.rz->out_w, out.rz->out_h, (double)ms);
         }
     }
     HIP_TRY(hipStreamSynchronize(s));                                 // (the pinned staging is the next slice's; the call is synchronous anyway)
@@ -311,7 +317,8 @@ namespace {
 
 // The driver of both entries, behind their own argument checks (n >= 1, arrays, format, strides, capacity): headers and windows, the grouped
 // path slice by slice, the per-file path, the verdict.  rz null: every window into its slot as it is (jpezy_decode_windows_dev); otherwise
-// every window resampled to rz->out_w x rz->out_h (jpezy_decode_windows_resized_dev).
+// every window resampled to rz->out_w x rz->out_h (jpezy_decode_windows_resized_dev; with rz->tensor into a tensor,
+// jpezy_decode_windows_tensor_dev).
 int windows_driver(jpezy_ctx* c, const char* who_c, int n, const uint8_t* const* data, const size_t* len, int gray, const jpezy_window* windows,
                    int format, int bytes, size_t row_stride, size_t slot_stride, uint8_t* d_pix, jpezy_frame_info* info, jpezy_rect* placed,
                    int* status, const Resize* rz)
@@ -443,7 +450,7 @@ int windows_driver(jpezy_ctx* c, const char* who_c, int n, const uint8_t* const*
             if (rz) {
                 const std::vector<ResampleJob> job = { { 0, (unsigned long long)i * slot_stride, cd.rect.w, cd.rect.h, rz->mirror_x && rz->mirror_x[i] ? 1 : 0 } };
                 if (int rc = jpezy_internal_resample(w, job, (const uint8_t*)w->w_scr.p, (unsigned)scr_stride, d_pix, row_stride, rz->out_w, rz->out_h, bytes,
-                                                     w->stream))
+                                                     w->stream, nullptr, nullptr, rz->tensor))
                     return rc;
             }
             HIP_TRY(hipStreamSynchronize(w->stream));
@@ -510,8 +517,59 @@ try {
                                             " bytes does not fit a slot of " + std::to_string(slot_stride) + " bytes with rows " +
                                             std::to_string(row_stride) + " apart");
     if (slot_stride > pix_cap / (size_t)n) return set_err(JPEZY_E_NOSPACE, who + ": n * slot_stride exceeds pix_cap");
-    const Resize rz = { out_w, out_h, mirror_x };
+    const Resize rz = { out_w, out_h, mirror_x, nullptr };
     return windows_driver(c, kWhoResized, n, data, len, gray, windows, format, bytes, row_stride, slot_stride, d_pix, info, placed, status, &rz);
+}
+JPEZY_CATCH
+
+int jpezy_decode_windows_tensor_dev(jpezy_ctx* c, int n, const uint8_t* const* data, const size_t* len, int gray, const jpezy_window* windows,
+                                    const uint8_t* mirror_x, int out_w, int out_h, int format, int dtype, int channels, const float* scale,
+                                    const float* bias, int64_t sn, int64_t sc, int64_t sh, int64_t sw, void* d_out, size_t cap_elems,
+                                    jpezy_frame_info* info, jpezy_rect* placed, int* status)
+try {
+    const std::string who = kWhoTensor;
+    // what needs no device, before the context is looked at, in the order include/jpezy_hip.h documents
+    if (n < 0) return set_err(JPEZY_E_BADARG, who + ": n must not be negative");
+    if (n == 0) return JPEZY_OK;
+    if (!data || !len || !info || !status || !d_out) return set_err(JPEZY_E_BADARG, who + ": null pointer");
+    const int bytes = jpezy_pixel_bytes(format);
+    if (bytes < 0) return set_err(JPEZY_E_BADARG, who + ": unknown pixel format");
+    if (bytes != 3) return set_err(JPEZY_E_BADARG, who + ": the pixel format must be JPEZY_PIX_RGB24 or JPEZY_PIX_BGR24 (alpha is never a tensor channel)");
+    if (out_w < 1 || out_h < 1 || out_w > 65535 || out_h > 65535) return set_err(JPEZY_E_BADARG, who + ": out_w and out_h must be in 1..65535");
+    if (channels != 3 && channels != 1) return set_err(JPEZY_E_BADARG, who + ": channels must be 3 or 1");
+    if (channels == 1 && !gray) return set_err(JPEZY_E_BADARG, who + ": channels == 1 needs gray != 0");
+    if (dtype != JPEZY_DT_U8 && dtype != JPEZY_DT_F32 && dtype != JPEZY_DT_F16 && dtype != JPEZY_DT_BF16)
+        return set_err(JPEZY_E_BADARG, who + ": unknown element type (dtype must be one of JPEZY_DT_*)");
+    if (!scale != !bias) return set_err(JPEZY_E_BADARG, who + ": scale and bias are given together or not at all");
+    if (dtype == JPEZY_DT_U8 && scale) return set_err(JPEZY_E_BADARG, who + ": JPEZY_DT_U8 takes no scale and bias");
+    static_assert(JPEZY_DT_U8 == kTensorU8 && JPEZY_DT_F32 == kTensorF32 && JPEZY_DT_F16 == kTensorF16 && JPEZY_DT_BF16 == kTensorBF16, "TensorOut::dtype");
+    TensorOut t;
+    std::memset(&t, 0, sizeof t);
+    for (int k = 0; k < 3; ++k) t.scale[k] = 1.0f;
+    for (int k = 0; k < channels && scale; ++k) {
+        if (!jpezy_host::tensor_value_in_band(scale[k]) || !jpezy_host::tensor_value_in_band(bias[k]))
+            return set_err(JPEZY_E_BADARG, who + ": scale and bias values must be 0 or finite with a magnitude in [2^-100, 2^100] (channel " +
+                                               std::to_string(k) + ")");
+        t.scale[k] = scale[k]; t.bias[k] = bias[k];
+    }
+    const long long extent[4] = { n, channels, out_h, out_w }, stride[4] = { sn, sc, sh, sw };
+    const size_t elem = dtype == JPEZY_DT_U8 ? 1 : dtype == JPEZY_DT_F32 ? 4 : 2;
+    switch (jpezy_host::tensor_layout_check(extent, stride, cap_elems)) {
+    case jpezy_host::kTensorNegative: return set_err(JPEZY_E_BADARG, who + ": strides must not be negative");
+    case jpezy_host::kTensorOverlap:
+        return set_err(JPEZY_E_BADARG, who + ": the strides (" + std::to_string(sn) + ", " + std::to_string(sc) + ", " + std::to_string(sh) + ", " +
+                                           std::to_string(sw) + ") do not give every element of [" + std::to_string(n) + ", " + std::to_string(channels) + ", " +
+                                           std::to_string(out_h) + ", " + std::to_string(out_w) + "] a place of its own");
+    case jpezy_host::kTensorNoSpace:
+        return set_err(JPEZY_E_NOSPACE, who + ": a tensor [" + std::to_string(n) + ", " + std::to_string(channels) + ", " + std::to_string(out_h) + ", " +
+                                            std::to_string(out_w) + "] with these strides does not fit cap_elems = " + std::to_string(cap_elems));
+    default: break;
+    }
+    if ((uintptr_t)d_out % elem) return set_err(JPEZY_E_BADARG, who + ": d_out must be aligned to the element size");
+    t.sc = (unsigned long long)sc; t.sh = (unsigned long long)sh; t.sw = (unsigned long long)sw;
+    t.dtype = dtype; t.channels = channels;
+    const Resize rz = { out_w, out_h, mirror_x, &t };
+    return windows_driver(c, kWhoTensor, n, data, len, gray, windows, format, bytes, 0, (size_t)sn, (uint8_t*)d_out, info, placed, status, &rz);
 }
 JPEZY_CATCH
 

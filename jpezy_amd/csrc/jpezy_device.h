@@ -329,6 +329,18 @@ struct ResampleParams {
 };
 hipError_t launch_resample(const ResampleParams& p, unsigned long long total_wg, hipStream_t stream);
 
+// the same stage with a tensor behind it (jpezy_kernels_resized_tensor.hip; include/jpezy_hip.h, BATCH OF WINDOWS, TENSOR OUTPUT): the three
+// bytes of an output pixel become `channels` elements of `dtype`, (float)byte * scale[c] + bias[c] for the float types, element (c, y, x) of
+// a file at dst + (ResampleDesc::dst_off + c*sc + y*sh + x*sw) * element size.  With it ResampleDesc::dst_off counts ELEMENTS (k * sn),
+// ResampleParams::pix_bytes is 3 (the source's) and dst_stride is not read.  dtype: the values of JPEZY_DT_*.
+enum { kTensorU8 = 0, kTensorF32 = 1, kTensorF16 = 2, kTensorBF16 = 3 };
+struct TensorOut {
+    float scale[3], bias[3];        // per channel; not read for kTensorU8
+    unsigned long long sc, sh, sw;  // strides in elements
+    int dtype, channels;            // channels: 3, or 1 (channel 0 alone)
+};
+hipError_t launch_resample_tensor(const ResampleParams& p, const TensorOut& t, unsigned long long total_wg, hipStream_t stream);
+
 // lossless transforms in the coefficient domain (jpezy_kernels_transform.hip; include/jpezy_hip.h, LOSSLESS TRANSFORMS): every output
 // block is one source block, permuted (swap) and with some coefficients negated (mirror) -- pure data movement
 struct XformParams {

@@ -9,79 +9,24 @@
 //       clipped), then accumulates K * t: the vertical pass over exactly the bytes a separate horizontal pass would have stored.  Both
 //       tap loops are runtime loops over the tables' counts, so every ratio runs the same code and nothing is staged in LDS: a source of
 //       4096 columns to one pixel is a loop of 8192 taps, not a tile that has to fit.  The price is that a horizontal byte is evaluated
-//       once per output row that uses it (about twice when an axis shrinks, DESIGN.md 4.15 has the count).
+//       once per output row that uses it (about twice when an axis shrinks, DESIGN.md 4.15 has the count).  All of that is
+//       resample_four of jpezy_resample_core.h, which the tensor form of this stage (jpezy_kernels_resized_tensor.hip) runs too.
 //       Stores: the four pixels as one 12- or 16-byte store when all four exist and the address is a multiple of 4, single bytes
 //       otherwise (windows_kernel's stage 2).  Byte 3 of a 32-bit pixel is 0xFF and is never read.
 // No byte outside a file's out_w * PIX x out_h rectangle is written; the source is read inside the file's w x h window only (the tables
 // hold first + count <= size, jpezy_resize_taps).
-#include "jpezy_wave.h"
+#include "jpezy_resample_core.h"
 
 namespace jpezy_dev {
 namespace resized {
 
-constexpr int kThreads = 256;
-constexpr int kGroupsX = kResampleTileW / 4;          // threads across a tile row
-static_assert(kGroupsX * kResampleTileH == kThreads, "one thread per group of four output pixels of the tile");
-
-__device__ __forceinline__ int clip8(int v) { return v < 0 ? 0 : v > 255 ? 255 : v; }
-
-// the file of workgroup wg: the last descriptor whose first workgroup is <= wg (wg0 ascending, desc[0].wg0 == first workgroup of the launch)
-__device__ __forceinline__ unsigned find_file(const ResampleDesc* __restrict__ desc, unsigned n, unsigned wg)
-{
-    unsigned lo = 0, hi = n;                      // invariant: desc[lo].wg0 <= wg, and (hi == n or desc[hi].wg0 > wg)
-    while (hi - lo > 1) {
-        const unsigned mid = lo + ((hi - lo) >> 1);
-        if (desc[mid].wg0 <= wg) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 template <int PIX>
 __global__ __launch_bounds__(kThreads) void resample_kernel(ResampleParams p)
 {
-    const unsigned wg = p.wg_base + blockIdx.x;
-    // (uniform by construction; readfirstlane tells the compiler so, and the descriptor is then read with scalar loads)
-    const unsigned fi = (unsigned)__builtin_amdgcn_readfirstlane((int)find_file(p.desc, p.n_desc, wg));
-    const ResampleDesc d = p.desc[fi];
-    const unsigned tiles_x = ((unsigned)p.out_w + kResampleTileW - 1) / kResampleTileW;
-    const unsigned local = wg - d.wg0;
-    const unsigned ty = local / tiles_x, tx = local - ty * tiles_x;
-    const int ox0 = (int)(tx * kResampleTileW + (threadIdx.x % kGroupsX) * 4);
-    const int oy = (int)(ty * kResampleTileH + threadIdx.x / kGroupsX);
-    if (ox0 >= p.out_w || oy >= p.out_h) return;
-    const int npx = min(4, p.out_w - ox0);
-
-    const uint8_t* __restrict__ const src = p.src + d.src_off;
-    const int* __restrict__ const xfc = p.taps + d.xfc;
-    const int* __restrict__ const xw = p.taps + d.xw;
-    const unsigned yfc = (unsigned)p.taps[d.yfc + (unsigned)oy];
-    const int fy = (int)(yfc & 0xFFFFu), ny = (int)(yfc >> 16);
-    const int* __restrict__ const wy = p.taps + d.yw + (size_t)oy * (unsigned)d.ky;
-
-    uint32_t w0 = 0, w1 = 0, w2 = 0;              // byte j of w0 / w1 / w2: channel byte 0 / 1 / 2 of pixel j
-    for (int j = 0; j < npx; ++j) {
-        const int col = d.mirror ? p.out_w - 1 - (ox0 + j) : ox0 + j;           // the column of the unmirrored result
-        const unsigned fc = (unsigned)xfc[col];
-        const int fx = (int)(fc & 0xFFFFu), nx = (int)(fc >> 16);
-        const int* __restrict__ const wx = xw + (size_t)col * (unsigned)d.kx;
-        int v0 = 1 << 21, v1 = 1 << 21, v2 = 1 << 21;
-        for (int jy = 0; jy < ny; ++jy) {
-            const uint8_t* __restrict__ row = src + (size_t)(fy + jy) * p.src_stride + (size_t)fx * PIX;
-            int h0 = 1 << 21, h1 = 1 << 21, h2 = 1 << 21;
-            for (int jx = 0; jx < nx; ++jx) {
-                const int k = wx[jx];
-                if (PIX == 4) {
-                    const uint32_t px = *reinterpret_cast<const uint32_t*>(row + jx * 4);       // (src_off, src_stride: multiples of 4)
-                    h0 += k * (int)(px & 0xFFu); h1 += k * (int)((px >> 8) & 0xFFu); h2 += k * (int)((px >> 16) & 0xFFu);
-                } else {
-                    h0 += k * (int)row[jx * 3]; h1 += k * (int)row[jx * 3 + 1]; h2 += k * (int)row[jx * 3 + 2];
-                }
-            }
-            const int ky = wy[jy];
-            v0 += ky * clip8(h0 >> 22); v1 += ky * clip8(h1 >> 22); v2 += ky * clip8(h2 >> 22);
-        }
-        w0 |= (uint32_t)clip8(v0 >> 22) << (8 * j); w1 |= (uint32_t)clip8(v1 >> 22) << (8 * j); w2 |= (uint32_t)clip8(v2 >> 22) << (8 * j);
-    }
+    const ResampleDesc d = workgroup_file(p);
+    int ox0, oy, npx;
+    uint32_t w0, w1, w2;                          // byte j of w0 / w1 / w2: channel byte 0 / 1 / 2 of pixel j
+    if (!resample_four<PIX>(p, d, ox0, oy, npx, w0, w1, w2)) return;
 
     uint8_t* px = p.dst + d.dst_off + (size_t)oy * p.dst_stride + (size_t)ox0 * PIX;
     auto byte = [](uint32_t w, unsigned j) { return (w >> (8 * j)) & 0xFFu; };

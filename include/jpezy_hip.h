@@ -425,6 +425,7 @@ long jpezy_encode_jpeg(jpezy_ctx* ctx, const uint8_t* r, const uint8_t* g, const
  * jpezy_encode_batch_multi: the one-shot form (create, one call, destroy; chunk_frames is clamped to the largest shard so that a
  * single large frame does not reserve a ring for sixteen) -- what jpezy_encode --gpus N calls.
  * Replaces, for a batch: the caller's loop over encoder objects; inside each frame encoder/jpezy_encoder.hpp:55-67 and :174-225.
+ * The handle's contexts are its own: it always point-samples the chroma (jpezy_ctx_set_chroma_downsampling does not reach them).
  */
 typedef struct jpezy_multi_out {
     int16_t* coeffs;
@@ -995,6 +996,38 @@ long jpezy_encode_jpeg_sampling(jpezy_ctx* ctx, const uint8_t* r, const uint8_t*
                                 const char* comment, uint8_t* out, size_t cap);
 long jpezy_encode_jpeg_sampling_packed(jpezy_ctx* ctx, const uint8_t* pix, int format, size_t row_stride, int W, int H, int sampling,
                                        int gray, const char* comment, uint8_t* out, size_t cap);
+
+/*
+ * CHROMA DOWNSAMPLING of the 4:2:0 RGB encode (opt-in context setting; default JPEZY_DOWNSAMPLE_POINT: every byte is what it was).
+ * The reference point-samples -- Cb and Cr of the top-left pixel of every 2x2 (make_YCC, encoder/jpezy_encoder.hpp:134-142) -- so the
+ * definition of the averaged mode is this project's own.  JPEZY_DOWNSAMPLE_AVERAGE changes that one step and nothing else:
+ *
+ *   Extension     the picture is extended to whole 16 x 16 MCUs by clamping pixel coordinates, as before (:101,104).
+ *   Samples       Cb and Cr of EVERY pixel from RGB::Cb / Cr in the reference's FP64 order, truncating (:249-256): the per-pixel
+ *                 samples of JPEZY_SAMPLING_444 -- signed integers, no + 128.
+ *   Average       chroma sample (x', y') = (c[2y'][2x'] + c[2y'][2x'+1] + c[2y'+1][2x'] + c[2y'+1][2x'+1] + bias(x')) >> 2 with bias 1
+ *                 for even x', 2 for odd x', and an arithmetic shift (it floors): libjpeg's h2v2_downsample (alternating bias 1, 2
+ *                 and >> 2 on unsigned samples) carried over to signed samples -- adding 128 to the four inputs adds 128 to the
+ *                 result.  A 2x2 never crosses an MCU edge; at an odd picture edge it averages the clamped duplicates.
+ *   Unchanged     luma, DCT, quantiser, zig-zag, the coefficient layout [frame][mcu_y][mcu_x][6][64], jpezy_coeff_count,
+ *                 jpezy_jpeg_bound, header and scan: the writers and both Huffman stages never learn that the mode exists.  A
+ *                 picture whose 2x2s are uniform (every pixel doubled) gives the coefficients of JPEZY_DOWNSAMPLE_POINT.
+ *   Acts on       every colour 4:2:0 RGB transform of the context: jpezy_fdct_quant[_dev], jpezy_fdct_quant_packed_dev,
+ *                 jpezy_encode_jpeg[_packed], and the *_sampling* entries called with JPEZY_SAMPLING_420, which forward to those.
+ *                 The setting is read when a transform is launched; no device table changes, so the setter waits for nothing.
+ *   Not consulted gray != 0 (no chroma is computed); JPEZY_SAMPLING_444 (nothing is decimated); the planar-YCbCr entries (*_ycc*:
+ *                 the caller's chroma samples are the file's); the lossless transforms.  None of them changes a byte.
+ *   Refused       any other mode: JPEZY_E_BADARG.  A colour 4:2:0 RGB transform with encode variant 0 (the FP64 kernel has no averaged
+ *                 stage) while the mode is JPEZY_DOWNSAMPLE_AVERAGE: JPEZY_E_UNSUPPORTED, nothing launched, the context stays usable.
+ *   Context settings  jpezy_ctx_set_force_exact (levels 0-3), _set_dc_table_lookup, _set_quality / _set_quant_tables,
+ *                 _set_huffman_optimize and _set_restart_interval act as on the point-sampled transform.
+ *
+ * The multi-GPU handle (jpezy_multi_*, jpezy_encode_batch_multi) owns its contexts and always point-samples.
+ * jpezy_ctx_chroma_downsampling returns the setting (JPEZY_E_BADARG for a null context).
+ */
+enum jpezy_downsampling { JPEZY_DOWNSAMPLE_POINT = 0, JPEZY_DOWNSAMPLE_AVERAGE = 1 };
+int jpezy_ctx_set_chroma_downsampling(jpezy_ctx* ctx, int mode);
+int jpezy_ctx_chroma_downsampling(jpezy_ctx* ctx);
 
 /*
  * LOSSLESS TRANSFORMS: flip, rotate, transpose of a picture in the COEFFICIENT domain (what jpegtran -rotate / -flip / -transpose and

@@ -101,6 +101,8 @@ ABI = [
     ("jpezy_ctx_set_quant_tables", C.c_int, [_vp, _vp, _vp]),
     ("jpezy_ctx_set_quality", C.c_int, [_vp, C.c_int]),
     ("jpezy_ctx_quant_tables", C.c_int, [_vp, _vp, _vp]),
+    ("jpezy_ctx_set_chroma_downsampling", C.c_int, [_vp, C.c_int]),
+    ("jpezy_ctx_chroma_downsampling", C.c_int, [_vp]),
     ("jpezy_write_jpeg_qt", C.c_long, [_vp, C.c_int, C.c_int, C.c_int, C.c_char_p, _vp, _vp, C.c_int, C.c_int, _vp, C.c_size_t]),
     ("jpezy_quant_tables_probe", C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(C.c_int)]),
     ("jpezy_ctx_set_dc_table_lookup", None, [_vp, C.c_int]),
@@ -208,6 +210,7 @@ ABI_REGION_UPSAMPLING = [
 # chroma sampling of the encoder's *_sampling entry points: 4:2:0 (the reference's 2x2 / 1x1 / 1x1, everything as without the keyword)
 # or 4:4:4 (8 x 8 MCUs of Y, Cb, Cr, no decimation; include/jpezy_hip.h has the definition)
 SAMPLING_420, SAMPLING_444 = 0, 1
+DOWNSAMPLE_POINT, DOWNSAMPLE_AVERAGE = 0, 1     # Context.set_chroma_downsampling: how 4:2:0 chroma is made from RGB pixels
 
 # enum jpezy_pixel_format: packed (interleaved) pixels, 3 or 4 bytes each
 PIX_RGB24, PIX_BGR24, PIX_RGBA32, PIX_BGRA32 = 0, 1, 2, 3
@@ -507,6 +510,16 @@ class Context:
         luma, chroma = np.zeros(64, np.uint8), np.zeros(64, np.uint8)
         _check(load_library().jpezy_ctx_quant_tables(self._h, _np_ptr(luma), _np_ptr(chroma)))
         return luma, chroma
+
+    def set_chroma_downsampling(self, mode):
+        """DOWNSAMPLE_POINT (default): Cb and Cr of the top-left pixel of every 2x2, the reference's rule; DOWNSAMPLE_AVERAGE: the
+        floor-averaged 2x2 with libjpeg's alternating bias (include/jpezy_hip.h, CHROMA DOWNSAMPLING).  Acts on every colour 4:2:0
+        RGB transform of the context (fdct_quant[_dev], fdct_quant_packed_dev, encode_jpeg[_packed]); gray, SAMPLING_444 and the
+        planar-YCbCr entries do not consult it.  Refused with encode variant 0 when such a transform is launched."""
+        _check(load_library().jpezy_ctx_set_chroma_downsampling(self._h, int(mode)))
+
+    def chroma_downsampling(self):
+        return _check(load_library().jpezy_ctx_chroma_downsampling(self._h))
 
     def set_dc_table_lookup(self, on):
         """test hook: the encode kernels read the quantised DC from the exact table even where the level-1 quantiser may take it"""

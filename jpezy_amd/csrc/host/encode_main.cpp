@@ -1,4 +1,4 @@
-// jpezy_encode <input.ppm> ( <output.(jpeg | jpg) [OPT: --gray] [OPT: --optimize] [OPT: --restart=N] [OPT: --quality=N]> | <output.ppm> | --debug )
+// jpezy_encode <input.ppm> ( <output.(jpeg | jpg) [OPT: --gray] [OPT: --optimize] [OPT: --restart=N] [OPT: --quality=N] [OPT: --chroma=average|point]> | <output.ppm> | --debug )
 // Same argv rules, transcript and exit codes as the reference's src/encoder/main.cpp; the codec underneath is
 // the MI355X path (jpezy_encoder.hpp).
 // Extension (not in the reference):  --optimize (single-file mode only, either side of --gray) writes the file with its own optimal
@@ -10,6 +10,10 @@
 // Extension (not in the reference):  --sampling=444|420 (single-file mode, one token, anywhere behind the output name) writes the file with
 // 4:4:4 chroma sampling (jpezy_encode_jpeg_sampling: 8 x 8 MCUs, no chroma decimation) or, the default, 4:2:0; composes with --optimize,
 // --restart, --quality and --gpus 1.  Together with --gray, --i420 or --gpus N > 1, 444 prints the rule and exits 1.
+// Extension (not in the reference):  --chroma=average|point (single-file mode, one token, anywhere behind the output name) makes the 4:2:0
+// chroma by averaging every 2x2 (jpezy_ctx_set_chroma_downsampling, JPEZY_DOWNSAMPLE_AVERAGE) or, the default, from its top-left pixel;
+// composes with --optimize, --restart, --quality, --sampling=420 and --gpus 1.  Together with --gray, --i420, --sampling=444 or
+// --gpus N > 1, average prints the rule and exits 1; point is always the file without the flag.
 // Extension (not in the reference):  jpezy_encode --gpus N [--gray] <in1.ppm> <out1.jpg> [<in2.ppm> <out2.jpg> ...]
 // encodes a list of files on up to N GPUs of this node through jpezy_encode_batch_multi: runs of consecutive inputs of one size
 // form a batch, a batch is sharded over the GPUs frame by frame.
@@ -47,22 +51,27 @@ bool has_ext(std::string_view s, std::string_view ext)
 int parse_sampling(std::string_view tok);
 int sampling_rule();
 int take_sampling(std::vector<const char*>& args, std::size_t from);
+int parse_chroma(std::string_view tok);
+int chroma_rule();
+int take_chroma(std::vector<const char*>& args, std::size_t from);
 
 int batch_main(const int argc_in, const char* argv_in[])
 {
     std::vector<const char*> args(argv_in, argv_in + argc_in);
     const int sampling = take_sampling(args, 3);
+    const int chroma = take_chroma(args, 3);
     const int argc = static_cast<int>(args.size());
     const char* const* argv = args.data();
     const int want = std::atoi(argv[2]);
     int a = 3;
     bool gray = false;
     if (a < argc && std::string_view(argv[a]) == "--gray") { gray = true; ++a; }
-    if (want <= 0 || a >= argc || (argc - a) % 2 != 0 || sampling < 0) {
+    if (want <= 0 || a >= argc || (argc - a) % 2 != 0 || sampling < 0 || chroma < 0) {
         std::cerr << "Usage: jpezy_encode --gpus N [--gray] <in1.ppm> <out1.jpg> [<in2.ppm> <out2.jpg> ...]" << std::endl;
         return EXIT_FAILURE;
     }
     if (sampling == JPEZY_SAMPLING_444 && (gray || want > 1)) return sampling_rule();
+    if (chroma == JPEZY_DOWNSAMPLE_AVERAGE && (gray || want > 1 || sampling == JPEZY_SAMPLING_444)) return chroma_rule();
     const int have = jpezy_hip_device_count();
     if (have <= 0) { std::cerr << "jpezy_encode: no HIP device (the jpezy hot path has no CPU fallback)" << std::endl; return EXIT_FAILURE; }
     std::vector<int> devices;
@@ -96,13 +105,20 @@ int batch_main(const int argc_in, const char* argv_in[])
                                                                                 sampling, 0, comment, jpg.data() + stride * static_cast<std::size_t>(i), stride);
                 if (sizes[static_cast<std::size_t>(i)] < 0) { std::cerr << "jpezy_encode_jpeg_sampling: " << jpezy_hip_last_error() << std::endl; jpezy_ctx_destroy(single); return EXIT_FAILURE; }
             }
-        } else if (n == 1) {
+        } else if (n == 1 || chroma == JPEZY_DOWNSAMPLE_AVERAGE) {
             // a run of one frame has nothing to shard: the ordinary single-file path (streams the frame band by band, no ring of
             // whole-frame slots: a 16K x 16K file would otherwise reserve several GB of pinned memory for nothing)
             if (!single) single = jpezy_ctx_create(devices[0]);
             if (!single) { std::cerr << "jpezy_ctx_create: " << jpezy_hip_last_error() << std::endl; return EXIT_FAILURE; }
-            sizes[0] = jpezy_encode_jpeg(single, r.data(), g.data(), b.data(), static_cast<int>(W), static_cast<int>(H), gray ? 1 : 0, comment, jpg.data(), stride);
-            if (sizes[0] < 0) { std::cerr << "jpezy_encode_jpeg: " << jpezy_hip_last_error() << std::endl; jpezy_ctx_destroy(single); return EXIT_FAILURE; }
+            // (--chroma=average, one GPU, checked above: the multi-GPU handle always point-samples, so every frame of the run goes this way)
+            if (jpezy_ctx_set_chroma_downsampling(single, chroma) != JPEZY_OK) { std::cerr << "jpezy_ctx_set_chroma_downsampling: " << jpezy_hip_last_error() << std::endl; jpezy_ctx_destroy(single); return EXIT_FAILURE; }
+            const std::size_t px = W * H;
+            for (int i = 0; i < n; ++i) {
+                const std::size_t o = px * static_cast<std::size_t>(i);
+                sizes[static_cast<std::size_t>(i)] = jpezy_encode_jpeg(single, r.data() + o, g.data() + o, b.data() + o, static_cast<int>(W), static_cast<int>(H), gray ? 1 : 0,
+                                                                       comment, jpg.data() + stride * static_cast<std::size_t>(i), stride);
+                if (sizes[static_cast<std::size_t>(i)] < 0) { std::cerr << "jpezy_encode_jpeg: " << jpezy_hip_last_error() << std::endl; jpezy_ctx_destroy(single); return EXIT_FAILURE; }
+            }
         } else {
             jpezy_multi_out out{ nullptr, jpg.data(), stride, sizes.data(), 0 };
             const int rc = jpezy_encode_batch_multi(devices.data(), static_cast<int>(devices.size()), r.data(), g.data(), b.data(), static_cast<int>(W),
@@ -176,6 +192,33 @@ int take_sampling(std::vector<const char*>& args, std::size_t from)
     return JPEZY_SAMPLING_420;
 }
 
+// "--chroma=average" / "--chroma=point": JPEZY_DOWNSAMPLE_*; anything else that starts like it: -1
+int parse_chroma(std::string_view tok)
+{
+    tok.remove_prefix(std::string_view("--chroma=").size());
+    return tok == "average" ? JPEZY_DOWNSAMPLE_AVERAGE : tok == "point" ? JPEZY_DOWNSAMPLE_POINT : -1;
+}
+
+int chroma_rule()
+{
+    std::cerr << "jpezy_encode: --chroma=average averages the 4:2:0 chroma of colour files from RGB input on one GPU; it cannot be combined with --gray, "
+                 "--i420, --sampling=444 or --gpus N > 1"
+              << std::endl;
+    return EXIT_FAILURE;
+}
+
+// takes the one "--chroma=..." token at or behind position `from` out of args: its value, JPEZY_DOWNSAMPLE_POINT when there is none, -1 malformed
+int take_chroma(std::vector<const char*>& args, std::size_t from)
+{
+    for (std::size_t i = from; i < args.size(); ++i)
+        if (std::string_view(args[i]).rfind("--chroma=", 0) == 0) {
+            const int s = parse_chroma(args[i]);
+            args.erase(args.begin() + static_cast<std::ptrdiff_t>(i));
+            return s;
+        }
+    return JPEZY_DOWNSAMPLE_POINT;
+}
+
 // jpezy_encode --i420=WxH in.yuv out.jpg [--gray] [--optimize] [--restart=N] [--quality=N]
 int i420_main(const int argc, const char* argv[])
 {
@@ -199,6 +242,8 @@ int i420_main(const int argc, const char* argv[])
         else if (o.rfind("--quality=", 0) == 0 && (quality = parse_quality(o)) >= 1) continue;
         else if (o.rfind("--sampling=", 0) == 0 && parse_sampling(o) == JPEZY_SAMPLING_420) continue;
         else if (o.rfind("--sampling=", 0) == 0 && parse_sampling(o) == JPEZY_SAMPLING_444) return sampling_rule();
+        else if (o.rfind("--chroma=", 0) == 0 && parse_chroma(o) == JPEZY_DOWNSAMPLE_POINT) continue;
+        else if (o.rfind("--chroma=", 0) == 0 && parse_chroma(o) == JPEZY_DOWNSAMPLE_AVERAGE) return chroma_rule();
         else return usage();
     }
     jpezy::disp_logo();
@@ -258,6 +303,8 @@ int main(const int argc_in, const char* argv_in[])
         }
     const int sampling = take_sampling(args, 3);
     if (sampling < 0) return disp_error();
+    const int chroma = take_chroma(args, 3);
+    if (chroma < 0) return disp_error();
     const int argc = static_cast<int>(args.size());
     const char* const* argv = args.data();
 
@@ -280,6 +327,8 @@ int main(const int argc_in, const char* argv_in[])
         return disp_error();
     }
     if (sampling == JPEZY_SAMPLING_444 && (m1 != Mode::JPEG || m2 == Mode::GRAY)) return m1 == Mode::JPEG ? sampling_rule() : disp_error();
+    if (chroma == JPEZY_DOWNSAMPLE_AVERAGE && (m1 != Mode::JPEG || m2 == Mode::GRAY || sampling == JPEZY_SAMPLING_444))
+        return m1 == Mode::JPEG ? chroma_rule() : disp_error();
 
     jpezy::disp_logo();
 
@@ -300,6 +349,8 @@ int main(const int argc_in, const char* argv_in[])
                 throw std::runtime_error(std::string("jpezy_ctx_set_restart_interval: ") + jpezy_hip_last_error());
             if (quality && jpezy_ctx_set_quality(jpezy::detail::device_context(), quality) != JPEZY_OK)
                 throw std::runtime_error(std::string("jpezy_ctx_set_quality: ") + jpezy_hip_last_error());
+            if (chroma && jpezy_ctx_set_chroma_downsampling(jpezy::detail::device_context(), chroma) != JPEZY_OK)
+                throw std::runtime_error(std::string("jpezy_ctx_set_chroma_downsampling: ") + jpezy_hip_last_error());
             std::ofstream ofs(argv[2], std::ios::binary);
             if (m2 == Mode::GRAY) ofs << (pnm | jpezy::to_jpeg(argv[2]) | jpezy::gray_scale);
             else ofs << (pnm | jpezy::to_jpeg(argv[2], sampling));

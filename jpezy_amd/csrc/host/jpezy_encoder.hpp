@@ -27,7 +27,8 @@ struct encoder {
 
     // sampling (not in the reference, which writes 2x2 / 1x1 / 1x1 only): JPEZY_SAMPLING_420, or JPEZY_SAMPLING_444 -- a colour file of
     // 8 x 8 MCUs without chroma decimation (jpezy_encode_jpeg_sampling; include/jpezy_hip.h has the definition); 4:4:4 with GRAY_MODE is
-    // refused with the library's message
+    // refused with the library's message.  Quality, optimised tables, restart intervals and the chroma filter
+    // (jpezy_ctx_set_chroma_downsampling: point or averaged 2x2) are settings of detail::device_context(), the context every encoder shares.
     template <class MODE_TAG = COLOR_MODE>
     std::size_t encode(const char* output_file, int sampling = JPEZY_SAMPLING_420)
     {

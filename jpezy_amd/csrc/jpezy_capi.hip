@@ -355,6 +355,37 @@ int jpezy_internal_check_dims(const jpezy_ctx* c, int W, int H, int n_frames)
     return JPEZY_OK;
 }
 
+// JPEZY_DOWNSAMPLE_AVERAGE acts on this transform: a colour 4:2:0 RGB one (the two callers: the planar and the packed entry point)
+bool jpezy_internal_averaged_chroma(const jpezy_ctx* c, int gray)
+{
+    return !gray && c->chroma_downsampling == JPEZY_DOWNSAMPLE_AVERAGE;
+}
+
+// ... and what such a transform refuses before it touches anything: encode variant 0 (the FP64 kernel has no averaged stage), the
+// rule of check_variant_444
+int jpezy_internal_check_variant_avg(const jpezy_ctx* c, bool avg, const char* who)
+{
+    if (avg && c->variant == 0)
+        return set_err(JPEZY_E_UNSUPPORTED, std::string(who) + ": encode variant 0 (FP64) has no JPEZY_DOWNSAMPLE_AVERAGE form; use variant 1 "
+                                                              "or JPEZY_DOWNSAMPLE_POINT");
+    return JPEZY_OK;
+}
+
+int jpezy_ctx_set_chroma_downsampling(jpezy_ctx* c, int mode)
+{
+    if (!c) return set_err(JPEZY_E_BADARG, "null context");
+    if (mode != JPEZY_DOWNSAMPLE_POINT && mode != JPEZY_DOWNSAMPLE_AVERAGE)
+        return set_err(JPEZY_E_BADARG, "unknown chroma downsampling (JPEZY_DOWNSAMPLE_POINT = 0, JPEZY_DOWNSAMPLE_AVERAGE = 1)");
+    c->chroma_downsampling = mode;
+    return JPEZY_OK;
+}
+
+int jpezy_ctx_chroma_downsampling(jpezy_ctx* c)
+{
+    if (!c) return set_err(JPEZY_E_BADARG, "null context");
+    return c->chroma_downsampling;
+}
+
 // Everything of EncParams that does not say where the pixels are; shared by the planar and the packed entry point.
 int jpezy_internal_enc_params(jpezy_ctx* c, int W, int H, int gray, int n_frames, int16_t* d_coeffs, hipStream_t s, EncParams* out)
 {
@@ -393,6 +424,8 @@ int jpezy_fdct_quant_dev(jpezy_ctx* c, const uint8_t* d_r, const uint8_t* d_g, c
     if (!d_r || !d_g || !d_b || !d_coeffs) return set_err(JPEZY_E_BADARG, "null device pointer");
     if (!aligned16(d_coeffs)) return set_err(JPEZY_E_BADARG, "d_coeffs must be 16-byte aligned");
     if (plane_stride < (size_t)W * H) return set_err(JPEZY_E_BADARG, "plane_stride smaller than W*H");
+    const bool avg = jpezy_internal_averaged_chroma(c, gray);
+    if (int rc = jpezy_internal_check_variant_avg(c, avg, "fdct_quant_dev")) return rc;
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
     EncParams p;
@@ -405,6 +438,11 @@ int jpezy_fdct_quant_dev(jpezy_ctx* c, const uint8_t* d_r, const uint8_t* d_g, c
         q.n_frames = n_frames - f0 < kMaxFramesPerLaunch ? n_frames - f0 : kMaxFramesPerLaunch;
         q.r += (size_t)f0 * plane_stride; q.g += (size_t)f0 * plane_stride; q.b += (size_t)f0 * plane_stride;
         q.coeffs += (size_t)f0 * p.coeffs_per_frame;
+        // JPEZY_DOWNSAMPLE_AVERAGE: the one-quad launch with the averaged chroma stage, whatever f32 variant is set (the laboratory's
+        // persistent variants 2 and 3 hand such a frame to it as they do every frame they do not cover)
+        if (avg)
+            HIP_TRY(launch_fdct_quant_f32_avg(q, c->force_exact, s));
+        else
 #ifdef JPEZY_WITH_LAB
         // the persistent kernels were measured and archived with the Annex-K tables: a context with other tables hands its frames to
         // variant 1's launch, as those variants do for the frames they do not cover
@@ -453,6 +491,7 @@ int jpezy_fdct_quant(jpezy_ctx* c, const uint8_t* r, const uint8_t* g, const uin
 try {
     if (int rc = jpezy_internal_check_dims(c, W, H, n_frames)) return rc;
     if (!r || !g || !b || !coeffs) return set_err(JPEZY_E_BADARG, "null host pointer");
+    if (int rc = jpezy_internal_check_variant_avg(c, jpezy_internal_averaged_chroma(c, gray), "fdct_quant")) return rc;   // before anything is uploaded
     HIP_TRY(hipSetDevice(c->device));
     const size_t plane = (size_t)W * H;
     const int B = gray ? 4 : 6;

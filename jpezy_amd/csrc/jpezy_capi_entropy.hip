@@ -468,6 +468,7 @@ try {
     if (int rc = jpezy_internal_check_dims(c, W, H, 1)) return rc;
     if (!r || !g || !b || !out) return set_err(JPEZY_E_BADARG, "encode_jpeg: null pointer");
     if (int rc = check_comment(comment, "encode_jpeg")) return rc;
+    if (int rc = jpezy_internal_check_variant_avg(c, jpezy_internal_averaged_chroma(c, gray), "encode_jpeg")) return rc;   // before anything is uploaded
     HIP_TRY(hipSetDevice(c->device));
     // the planes go up band by band (jpezy_hostpipe.h) while the bands before them are transformed into the frame's
     // coefficient buffer on the device; the Huffman stage then runs on the whole frame

@@ -176,6 +176,7 @@ struct jpezy_ctx {
     float dc_rq[2] = { 0, 0 }, dc_bias[2] = { 0, 0 };   // f32::dc_formula's constants; 0: the table-free DC does not reproduce the DC table (build_encode_tables)
     uint8_t qt[2][64];             // the quantisation tables d_tab was built from (natural order): the header's DQT segments, jpezy_ctx_quant_tables
     bool qt_default = true;        // ... are the Annex-K tables
+    int chroma_downsampling = 0;   // JPEZY_DOWNSAMPLE_POINT; read when a colour 4:2:0 RGB transform is launched (jpezy_ctx_set_chroma_downsampling)
     bool dc_table_lookup = false;  // test hook (jpezy_ctx_set_dc_table_lookup): the DC from DeviceTables::dcq even where the checks allow the quantiser
     DevBuf d_trace;                // JPEZY_TRACE builds: 4 words per wave + 9 phase stamps (JPEZY_TRACE=3)
     DevBuf dump_t;                 // JPEZY_DUMP_T builds: level-1 t values of the last jpezy_fdct_quant_dev call
@@ -258,6 +259,9 @@ extern "C" {
 JPEZY_INTERNAL int jpezy_internal_check_dims(const jpezy_ctx* c, int W, int H, int n_frames);
 // the parts of the two transform stages' kernel parameters that planar and packed entry points share, and the cached dequantiser tables
 JPEZY_INTERNAL int jpezy_internal_enc_params(jpezy_ctx* c, int W, int H, int gray, int n_frames, int16_t* d_coeffs, hipStream_t s, EncParams* out);
+// JPEZY_DOWNSAMPLE_AVERAGE: whether it acts on a 4:2:0 RGB transform of the context, and its refusal of encode variant 0
+JPEZY_INTERNAL bool jpezy_internal_averaged_chroma(const jpezy_ctx* c, int gray);
+JPEZY_INTERNAL int jpezy_internal_check_variant_avg(const jpezy_ctx* c, bool avg, const char* who);
 JPEZY_INTERNAL void jpezy_internal_dec_params(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H, int n_frames, DecParams* out);
 JPEZY_INTERNAL int jpezy_internal_upload_dequant(jpezy_ctx* c, const uint16_t qt[4][64], const uint8_t comp_tq[3], hipStream_t s);
 // the GPU Huffman decoder over a list of independent streams, the device tables of one scan, the block structure of an MCU (jpezy_capi_huffdec.hip)

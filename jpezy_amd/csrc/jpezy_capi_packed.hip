@@ -21,6 +21,8 @@ int jpezy_fdct_quant_packed_dev(jpezy_ctx* c, const uint8_t* d_pix, int format, 
     if (int rc = packed_layout("fdct_quant_packed_dev", format, row_stride, frame_stride, W, H, &L)) return rc;
     if (!d_pix || !d_coeffs) return set_err(JPEZY_E_BADARG, "null device pointer");
     if (!aligned16(d_coeffs)) return set_err(JPEZY_E_BADARG, "d_coeffs must be 16-byte aligned");
+    const bool avg = jpezy_internal_averaged_chroma(c, gray);
+    if (int rc = jpezy_internal_check_variant_avg(c, avg, "fdct_quant_packed_dev")) return rc;
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
     EncParams p;
@@ -39,7 +41,10 @@ int jpezy_fdct_quant_packed_dev(jpezy_ctx* c, const uint8_t* d_pix, int format, 
         q.coeffs += (size_t)f0 * p.coeffs_per_frame;
         // variant 0: the FP64 kernel's byte loop; every other variant: the f32 kernel's packed launch (the laboratory's persistent
         // variants 2 and 3 hand packed input to it as they do every frame they do not cover)
-        if (c->variant == 0)
+        // (JPEZY_DOWNSAMPLE_AVERAGE: the same launch with the averaged chroma stage; variant 0 was refused above)
+        if (avg)
+            HIP_TRY(launch_fdct_quant_f32_packed_avg(q, c->force_exact, s));
+        else if (c->variant == 0)
             HIP_TRY(launch_fdct_quant_packed(q, gray != 0, c->force_exact != 0, s));
         else
             HIP_TRY(launch_fdct_quant_f32_packed(q, gray != 0, c->force_exact, s));
@@ -86,6 +91,7 @@ try {
     if (int rc = packed_layout("encode_jpeg_packed", format, row_stride, 0, W, H, &L)) return rc;
     if (!pix || !out) return set_err(JPEZY_E_BADARG, "encode_jpeg_packed: null pointer");
     if (int rc = check_comment(comment, "encode_jpeg_packed")) return rc;
+    if (int rc = jpezy_internal_check_variant_avg(c, jpezy_internal_averaged_chroma(c, gray), "encode_jpeg_packed")) return rc;   // before anything is uploaded
     HIP_TRY(hipSetDevice(c->device));
     const int B = gray ? 4 : 6;
     if (int rc = c->e_coef.reserve(jpezy_coeff_count(W, H, gray) * sizeof(int16_t))) return rc;

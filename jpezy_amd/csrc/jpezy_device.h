@@ -156,6 +156,9 @@ hipError_t launch_fdct_quant_f32(const EncParams& p, bool gray, int force, hipSt
 hipError_t launch_fdct_quant_f32_packed(const EncParams& p, bool gray, int force, hipStream_t stream);
 hipError_t launch_fdct_quant_packed(const EncParams& p, bool gray, bool force_exact, hipStream_t stream);
 bool packed_is_aligned16(const void* pix, int W, size_t row_stride, size_t frame_stride);
+// the f32 kernel's colour launches with the averaged chroma stage (JPEZY_DOWNSAMPLE_AVERAGE; jpezy_kernels_f32_avg.hip): planes, packed pixels
+hipError_t launch_fdct_quant_f32_avg(const EncParams& p, int force, hipStream_t stream);
+hipError_t launch_fdct_quant_f32_packed_avg(const EncParams& p, int force, hipStream_t stream);
 // ... and for planar YCbCr 4:2:0 samples (EncParams::c_step != 0): no colour conversion, the planes are the file's own sample domain
 hipError_t launch_fdct_quant_f32_ycc(const EncParams& p, bool gray, int force, hipStream_t stream);
 hipError_t launch_fdct_quant_ycc(const EncParams& p, bool gray, bool force_exact, hipStream_t stream);

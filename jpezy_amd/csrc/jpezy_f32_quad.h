@@ -58,6 +58,7 @@ static __constant__ unsigned char c_zzinv[64] = JPEZY_ZZ_INV_INIT;
 #ifndef JPEZY_F32_WAVES
 #define JPEZY_F32_WAVES 5
 #endif
+constexpr int AVG_BYTELOOP_WAVES = 4;   // the byte-loop (!ALIGNED) instances with the averaged chroma stage (JPEZY_DOWNSAMPLE_AVERAGE)
 
 typedef float f2 __attribute__((ext_vector_type(2)));   // an aligned VGPR (or SGPR) pair: the operand of v_pk_*_f32
 
@@ -255,6 +256,41 @@ __device__ __forceinline__ float chroma_px_ref(uint32_t wr, uint32_t wg, uint32_
 {
     const double r = (double)ubyte<B>(wr), g = (double)ubyte<B>(wg), b = (double)ubyte<B>(wb);
     return (float)(odd ? ref_cr(r, g, b) : ref_cb(r, g, b));
+}
+
+// JPEZY_DOWNSAMPLE_AVERAGE (AVG instances only): the horizontal pair sums of BOTH components over the four pixels of one word of the
+// three planes: hn[0..1] = c[0] + c[1], c[2] + c[3] of the component the neighbouring row's lane keeps (coefficients n1..n3; Cr on
+// even-row lanes), hk[0..1] of the lane's own (k1..k3).  Every c is the exact truncated sample -- chroma_px2's estimate and guard test
+// on every pixel, chroma_px_ref where the test fires, as the 4:4:4 kernel's chroma8 -- so a sum is exact in FP32.  Both components of
+// a word together: its twelve byte conversions are shared and die here (a component at a time keeps all 48 of a lane alive).
+__device__ __forceinline__ void chroma_pairsums4(uint32_t wr, uint32_t wg, uint32_t wb, float n1, float n2, float n3, float k1, float k2,
+                                                 float k3, bool odd, float* hn, float* hk)
+{
+    f2 c[4], e[4];
+    chroma_px2<0, 1>(wr, wg, wb, wr, wg, wb, n1, n2, n3, c[0], e[0]);
+    chroma_px2<2, 3>(wr, wg, wb, wr, wg, wb, n1, n2, n3, c[1], e[1]);
+    chroma_px2<0, 1>(wr, wg, wb, wr, wg, wb, k1, k2, k3, c[2], e[2]);
+    chroma_px2<2, 3>(wr, wg, wb, wr, wg, wb, k1, k2, k3, c[3], e[3]);
+    if (JPEZY_LAB_COLOUR_VOTE(wave_any(min8(e) < CHROMA_TH))) {
+        bool f;
+        f = e[0].x < CHROMA_TH; if (f) c[0].x = chroma_px_ref<0>(wr, wg, wb, !odd);
+        f = e[0].y < CHROMA_TH; if (f) c[0].y = chroma_px_ref<1>(wr, wg, wb, !odd);
+        f = e[1].x < CHROMA_TH; if (f) c[1].x = chroma_px_ref<2>(wr, wg, wb, !odd);
+        f = e[1].y < CHROMA_TH; if (f) c[1].y = chroma_px_ref<3>(wr, wg, wb, !odd);
+        f = e[2].x < CHROMA_TH; if (f) c[2].x = chroma_px_ref<0>(wr, wg, wb, odd);
+        f = e[2].y < CHROMA_TH; if (f) c[2].y = chroma_px_ref<1>(wr, wg, wb, odd);
+        f = e[3].x < CHROMA_TH; if (f) c[3].x = chroma_px_ref<2>(wr, wg, wb, odd);
+        f = e[3].y < CHROMA_TH; if (f) c[3].y = chroma_px_ref<3>(wr, wg, wb, odd);
+    }
+    hn[0] = c[0].x + c[0].y; hn[1] = c[1].x + c[1].y;
+    hk[0] = c[2].x + c[2].y; hk[1] = c[3].x + c[3].y;
+}
+
+// one averaged sample from the lane's own pair sum, the neighbouring row's and the bias of the sample's column (1 even, 2 odd):
+// floor((a + b + bias) / 4) -- integers below 2^10 and a power-of-two scale: every step exact in FP32
+__device__ __forceinline__ float chroma_avg(float a, float b, float bias)
+{
+    return __builtin_floorf(((a + b) + bias) * 0.25f);
 }
 
 __device__ __forceinline__ double readlane_f64(double v, int src)   // src wave-uniform
@@ -508,7 +544,8 @@ struct NoHook { __device__ __forceinline__ void operator()() const {} };
 // odd-row lanes (where the chroma row pass expects them); B is not read.  Only the sample stage differs: everything from step 3 on
 // sees YL / YR / CS as before.  Samples reach -128 in chroma as they always did in luma (block sums down to -8192, the first entry of
 // the DC table; the per-lane evaluator's bytes are signed: -128 fits).
-template <bool GRAY, int FORCE, bool PS, bool DCG = false, bool YCC = false, class AFTER_PIXELS>
+// AVG: JPEZY_DOWNSAMPLE_AVERAGE, step 2b's averaged form (own kernel instances, jpezy_kernels_f32_avg.hip; never together with YCC)
+template <bool GRAY, int FORCE, bool PS, bool DCG = false, bool YCC = false, bool AVG = false, class AFTER_PIXELS>
 __device__ __forceinline__ void encode_quad_compute(const EncParams& p, const uint32_t* R, const uint32_t* G, const uint32_t* B, uint32_t* lds,
                                             int lane, int mcu_y, int quad_x, int frame, unsigned qidx, const LaneConsts* pre,
                                             const int16_t* dcq_lds, const PsTables* pst, AFTER_PIXELS after_pixels QUAD_TRACE_PARAM)
@@ -554,7 +591,38 @@ __device__ __forceinline__ void encode_quad_compute(const EncParams& p, const ui
     //         pixels (DPP row_shr:4) and computes Cr, the even-row lane Cb.  Only the samples survive, so the raw
     //         pixel registers die here.  Sample s is pixel 2s: byte 2(s & 1) of word s >> 1. ----
     if constexpr (!GRAY && YCC) ycc8(G, CS);
-    if constexpr (!GRAY && !YCC) {
+    if constexpr (!GRAY && !YCC && AVG) {
+        // JPEZY_DOWNSAMPLE_AVERAGE: sample s of chroma row row >> 1 is floor((c[2s] + c[2s+1] of both pixel rows + bias(s)) / 4), c = the
+        // component's truncated sample of EVERY pixel.  The lane converts both components of its 16 pixels, word by word, into
+        // horizontal pair sums; the eight of the component its NEIGHBOUR keeps (Cr on even-row lanes, Cb on odd-row lanes) change
+        // lanes (DPP row_shr:4 into the odd-row lanes, row_shl:4 into the even-row lanes: the two rows of a 2x2 lie 4 lanes apart
+        // inside one DPP row), the eight of its own (Cb even, Cr odd, where the chroma row pass expects them) take what arrives.
+        // A 2x2 never leaves the lane pair.  The raw pixel registers die here, as on the point path.
+        const bool odd = (row & 1) != 0;
+        // (Cb, Cr) = (-.1687 R - .3313 G + .5 B), (.5 R - .4187 G - .0813 B)   (ref :249-256): k = the lane's own, n = the neighbour's
+        const float k1 = odd ? 0.5f : -0.1687f, k2 = odd ? -0.4187f : -0.3313f, k3 = odd ? -0.0813f : 0.5f;
+        const float n1 = odd ? -0.1687f : 0.5f, n2 = odd ? -0.3313f : -0.4187f, n3 = odd ? 0.5f : -0.0813f;
+        float hn[8], hk[8];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            // the words made opaque: the compiler otherwise shares the byte conversions with the luma stage's and keeps all 48
+            // floats of the lane alive from there to here (measured: 96 VGPRs and 77 to 176 spilled registers)
+            uint32_t wr = R[k], wg = G[k], wb = B[k];
+            asm("" : "+v"(wr), "+v"(wg), "+v"(wb));
+            chroma_pairsums4(wr, wg, wb, n1, n2, n3, k1, k2, k3, odd, hn + 2 * k, hk + 2 * k);
+            PHASE_FENCE();   // a word at a time: more in flight only costs registers
+        }
+        float s[8];
+#pragma unroll
+        for (int x = 0; x < 8; ++x) {
+            const int v = __builtin_bit_cast(int, hn[x]);
+            const int up = __builtin_amdgcn_update_dpp(v, v, 0x114, 0xF, 0xA, false);     // into the odd-row lanes: the row above
+            const int nb = __builtin_amdgcn_update_dpp(up, v, 0x104, 0xF, 0x5, false);    // into the even-row lanes: the row below
+            s[x] = chroma_avg(hk[x], __builtin_bit_cast(float, nb), x & 1 ? 2.f : 1.f);
+        }
+        CS[0] = f2{ s[0], s[7] }; CS[1] = f2{ s[1], s[6] }; CS[2] = f2{ s[2], s[5] }; CS[3] = f2{ s[3], s[4] };
+    }
+    if constexpr (!GRAY && !YCC && !AVG) {
         const bool odd = (row & 1) != 0;
         uint32_t R2[4], G2[4], B2[4];
 #pragma unroll
@@ -803,12 +871,12 @@ __device__ __forceinline__ void encode_quad_store(const EncParams& p, uint32_t* 
     }
 }
 
-template <bool GRAY, int FORCE, bool PS, bool DCG = false, bool YCC = false>
+template <bool GRAY, int FORCE, bool PS, bool DCG = false, bool YCC = false, bool AVG = false>
 __device__ __forceinline__ void encode_quad(const EncParams& p, const uint32_t* R, const uint32_t* G, const uint32_t* B, uint32_t* lds,
                                             int lane, int mcu_y, int quad_x, int frame, unsigned qidx, const LaneConsts* pre,
                                             const int16_t* dcq_lds, const PsTables* pst QUAD_TRACE_PARAM)
 {
-    encode_quad_compute<GRAY, FORCE, PS, DCG, YCC>(p, R, G, B, lds, lane, mcu_y, quad_x, frame, qidx, pre, dcq_lds, pst, NoHook()
+    encode_quad_compute<GRAY, FORCE, PS, DCG, YCC, AVG>(p, R, G, B, lds, lane, mcu_y, quad_x, frame, qidx, pre, dcq_lds, pst, NoHook()
 #ifdef JPEZY_TRACE
                                          , tr
 #endif

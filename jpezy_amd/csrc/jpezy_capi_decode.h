@@ -159,7 +159,7 @@ inline int read_coeffs(jpezy_ctx* c, const uint8_t* data, size_t len, jpezy_fram
 
 // Full: the fused kernel for jpezy's own layout, the any-layout pair for every other; Smooth: the any-layout pair with the smooth second
 // stage for every layout; Scaled, Region: the kernels of those parts; RegionSmooth: the region stage with smooth chroma upsampling
-// (jpezy_kernels_region_smooth.hip), at every scale and for the whole picture too
+// (jpezy_kernels_region.hip), at every scale and for the whole picture too
 enum class DecodeStage { Full, Scaled, Region, Smooth, RegionSmooth };
 
 struct DecodeRequest {

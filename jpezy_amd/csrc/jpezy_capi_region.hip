@@ -160,7 +160,7 @@ JPEZY_CATCH
 
 // ---- the same four entries with the chroma upsampling as an argument (include/jpezy_hip.h, SMOOTH UPSAMPLING OF WINDOWS).
 // JPEZY_UPSAMPLE_NEAREST is handed to the entry above as it is; JPEZY_UPSAMPLE_SMOOTH makes the same checks in the same order and runs
-// region_smooth_kernel (jpezy_kernels_region_smooth.hip) -- for the whole picture too: there is no smooth reduced-size entry to hand it to ----
+// region_smooth_kernel (jpezy_kernels_region.hip) -- for the whole picture too: there is no smooth reduced-size entry to hand it to ----
 
 int jpezy_dequant_idct_region_upsampling_dev(jpezy_ctx* c, const int16_t* d_coeffs, const uint16_t qt[4][64], int ncomp, const uint8_t comp_h[3],
                                              const uint8_t comp_v[3], const uint8_t comp_tq[3], int precision, int W, int H, int gray,

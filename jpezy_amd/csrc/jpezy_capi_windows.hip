@@ -2,7 +2,7 @@
 // quantiser tables mixed, packed pixels left in device memory), and part 14's entry: the same batch with every window resized to one output
 // size (jpezy_decode_windows_resized_dev; one driver serves both).  Files of one LAYOUT go through the batch form of the GPU Huffman decoder
 // together, whatever their sizes (a stream carries its own block count and coefficient offset), and through ONE launch of windows_kernel
-// per scale present (jpezy_kernels_windows.hip); what that path declines goes file by file: read_coeffs and the region stage core on a
+// per scale present (jpezy_kernels_region.hip); what that path declines goes file by file: read_coeffs and the region stage core on a
 // child context, straight into the file's slot.  Nothing is downloaded.  Resized: the same launches write a context-owned scratch of packed
 // pixels, every file by its own height, and one launch of resample_kernel per slice (jpezy_kernels_resized.hip) writes the slots.  Part 15's
 // entry, jpezy_decode_windows_tensor_dev, is the resized call with resample_tensor_kernel (jpezy_kernels_resized_tensor.hip) as that launch.

@@ -270,7 +270,7 @@ struct RegionDecParams {
 };
 hipError_t launch_dequant_idct_region(const RegionDecParams& p, hipStream_t stream);
 
-// a batch of crop windows (jpezy_kernels_windows.hip): the windows of many files of ONE layout at ONE scale 8 / N in one launch; size, window,
+// a batch of crop windows (jpezy_kernels_region.hip): the windows of many files of ONE layout at ONE scale 8 / N in one launch; size, window,
 // destination and quantiser tables are per file.  One descriptor per file, 64 bytes, read with scalar loads.
 struct WindowDesc {
     unsigned long long coeff_off;   // int16 offset of the file's first coefficient (the WHOLE file's coefficients lie there)
@@ -298,7 +298,7 @@ struct WindowsParams {
 };
 hipError_t launch_dequant_idct_windows(const WindowsParams& p, unsigned long long total_wg, hipStream_t stream);
 
-// region and window-batch decode with smooth chroma upsampling (jpezy_kernels_region_smooth.hip; include/jpezy_hip.h, SMOOTH UPSAMPLING OF
+// region and window-batch decode with smooth chroma upsampling (jpezy_kernels_region.hip; include/jpezy_hip.h, SMOOTH UPSAMPLING OF
 // WINDOWS): the same parameters and grids as the two launchers above, and the picture's size Ws x Hs at the launch's scale -- an argument
 // here, WindowDesc::pad[0], pad[1] of every file there.  Both must lie inside the file's MCU grid (jpezy_scaled_size of the file's size does)
 hipError_t launch_dequant_idct_region_smooth(const RegionDecParams& p, int Ws, int Hs, hipStream_t stream);

@@ -16,6 +16,7 @@
 // No byte outside a file's out_w * PIX x out_h rectangle is written; the source is read inside the file's w x h window only (the tables
 // hold first + count <= size, jpezy_resize_taps).
 #include "jpezy_resample_core.h"
+#include "jpezy_pixel_out.h"
 
 namespace jpezy_dev {
 namespace resized {
@@ -29,32 +30,7 @@ __global__ __launch_bounds__(kThreads) void resample_kernel(ResampleParams p)
     if (!resample_four<PIX>(p, d, ox0, oy, npx, w0, w1, w2)) return;
 
     uint8_t* px = p.dst + d.dst_off + (size_t)oy * p.dst_stride + (size_t)ox0 * PIX;
-    auto byte = [](uint32_t w, unsigned j) { return (w >> (8 * j)) & 0xFFu; };
-    if (npx == 4 && ((uintptr_t)px & 3u) == 0) {
-        if (PIX == 3) {
-            typedef unsigned v3u __attribute__((ext_vector_type(3)));
-            typedef v3u v3u_a4 __attribute__((aligned(4)));
-            v3u v;
-            v.x = byte(w0, 0) | byte(w1, 0) << 8 | byte(w2, 0) << 16 | byte(w0, 1) << 24;
-            v.y = byte(w1, 1) | byte(w2, 1) << 8 | byte(w0, 2) << 16 | byte(w1, 2) << 24;
-            v.z = byte(w2, 2) | byte(w0, 3) << 8 | byte(w1, 3) << 16 | byte(w2, 3) << 24;
-            *reinterpret_cast<v3u_a4*>(px) = v;
-        } else {
-            typedef unsigned v4u __attribute__((ext_vector_type(4)));
-            typedef v4u v4u_a4 __attribute__((aligned(4)));
-            v4u v;
-            v.x = byte(w0, 0) | byte(w1, 0) << 8 | byte(w2, 0) << 16 | 0xFF000000u;
-            v.y = byte(w0, 1) | byte(w1, 1) << 8 | byte(w2, 1) << 16 | 0xFF000000u;
-            v.z = byte(w0, 2) | byte(w1, 2) << 8 | byte(w2, 2) << 16 | 0xFF000000u;
-            v.w = byte(w0, 3) | byte(w1, 3) << 8 | byte(w2, 3) << 16 | 0xFF000000u;
-            *reinterpret_cast<v4u_a4*>(px) = v;
-        }
-    } else {
-        for (int j = 0; j < npx; ++j) {
-            px[j * PIX] = (uint8_t)byte(w0, j); px[j * PIX + 1] = (uint8_t)byte(w1, j); px[j * PIX + 2] = (uint8_t)byte(w2, j);
-            if (PIX == 4) px[j * PIX + 3] = 0xFF;
-        }
-    }
+    store_packed4<PIX>(px, (unsigned)npx, w0, w1, w2);
 }
 
 }  // namespace resized

@@ -13,7 +13,7 @@
 //   scaled_rgb_kernel<PIX>: one thread per four consecutive output pixels of a row; block placement, replication, make_rgb /
 //                           revise_value and the stores of generic_rgb_kernel with N in place of 8.  An MCU is hmax*N pixels
 //                           wide -- as narrow as one pixel -- so every pixel finds its own MCU.
-#include "jpezy_wave.h"
+#include "jpezy_pixel_out.h"
 #include "../../include/jpezy_constants.h"
 
 namespace jpezy_dev {
@@ -85,8 +85,6 @@ __global__ __launch_bounds__(64) void scaled_idct_kernel(ScaledDecParams p, long
     if (live) p.samples[g0 * G::NN + lane] = ref_int(sum / 4 + p.level);              // = samples[g * NN + s]
 }
 
-__device__ __forceinline__ uint32_t revise(double v) { return (v < 0.0) ? 0u : (v > 255.0) ? 255u : (uint32_t)v; }
-
 // PIX: 0 = planes; 3 / 4 = packed (interleaved) pixels of that many bytes, as in generic_rgb_kernel.
 template <int PIX>
 __global__ __launch_bounds__(256) void scaled_rgb_kernel(ScaledDecParams p)
@@ -130,59 +128,18 @@ __global__ __launch_bounds__(256) void scaled_rgb_kernel(ScaledDecParams p)
             if (xu < (dupx << l2))
                 smp[c] = p.samples[((mcu_blk + rowblk[c] + kx) << (2 * l2)) + rowsmp[c] + fast_div(xu, p.dx_magic[c], p.dx_shift[c])];
         }
-        const double yp = smp[0], up = smp[1], vp = smp[2];
         uint32_t r, g, b;
-        if (!p.gray) {                                                                 // make_rgb, ref :531-578, 672-676
-            r = revise(yp + (vp - 0x80) * 1.4020);
-            g = revise(yp - (up - 0x80) * 0.3441 - (vp - 0x80) * 0.7139);
-            b = revise(yp + (up - 0x80) * 1.7718);
-        } else {
-            r = g = b = revise(yp);
-        }
+        make_rgb(p.gray, smp[0], smp[1], smp[2], r, g, b);                             // ref :531-578, 672-676
         rw |= r << (8 * j); gw |= g << (8 * j); bw |= b << (8 * j);
     }
-    if (PIX != 0) {
+    if constexpr (PIX != 0) {
         const bool blue_first = p.b < p.r;                       // r, g, b: the channel bytes of pixel (0, 0)
         uint8_t* px = (blue_first ? p.b : p.r) + (size_t)y * p.row_stride + (size_t)x0 * PIX;
-        const uint32_t fw = blue_first ? bw : rw, tw = blue_first ? rw : bw;
-        auto byte = [](uint32_t w, unsigned j) { return (w >> (8 * j)) & 0xFFu; };
-        if (npx == 4 && ((uintptr_t)px & 3u) == 0) {
-            if (PIX == 3) {
-                typedef unsigned v3u __attribute__((ext_vector_type(3)));
-                typedef v3u v3u_a4 __attribute__((aligned(4)));
-                v3u v;
-                v.x = byte(fw, 0) | byte(gw, 0) << 8 | byte(tw, 0) << 16 | byte(fw, 1) << 24;
-                v.y = byte(gw, 1) | byte(tw, 1) << 8 | byte(fw, 2) << 16 | byte(gw, 2) << 24;
-                v.z = byte(tw, 2) | byte(fw, 3) << 8 | byte(gw, 3) << 16 | byte(tw, 3) << 24;
-                *reinterpret_cast<v3u_a4*>(px) = v;
-            } else {
-                typedef unsigned v4u __attribute__((ext_vector_type(4)));
-                typedef v4u v4u_a4 __attribute__((aligned(4)));
-                v4u v;
-                v.x = byte(fw, 0) | byte(gw, 0) << 8 | byte(tw, 0) << 16 | 0xFF000000u;
-                v.y = byte(fw, 1) | byte(gw, 1) << 8 | byte(tw, 1) << 16 | 0xFF000000u;
-                v.z = byte(fw, 2) | byte(gw, 2) << 8 | byte(tw, 2) << 16 | 0xFF000000u;
-                v.w = byte(fw, 3) | byte(gw, 3) << 8 | byte(tw, 3) << 16 | 0xFF000000u;
-                *reinterpret_cast<v4u_a4*>(px) = v;
-            }
-        } else {
-            for (unsigned j = 0; j < npx; ++j) {
-                px[j * PIX] = (uint8_t)byte(fw, j); px[j * PIX + 1] = (uint8_t)byte(gw, j); px[j * PIX + 2] = (uint8_t)byte(tw, j);
-                if (PIX == 4) px[j * PIX + 3] = 0xFF;
-            }
-        }
-        return;
-    }
-    // planes: rows are Ws apart and frames plane_stride, neither need be a multiple of 4 -- the word store goes by the addresses
-    const size_t off = (size_t)y * p.Ws + x0;
-    if (npx == 4 && ((((uintptr_t)(p.r + off)) | ((uintptr_t)(p.g + off)) | ((uintptr_t)(p.b + off))) & 3u) == 0) {
-        *reinterpret_cast<uint32_t*>(p.r + off) = rw;
-        *reinterpret_cast<uint32_t*>(p.g + off) = gw;
-        *reinterpret_cast<uint32_t*>(p.b + off) = bw;
+        store_packed4<PIX>(px, npx, blue_first ? bw : rw, gw, blue_first ? rw : bw);
     } else {
-        for (unsigned j = 0; j < npx; ++j) {
-            p.r[off + j] = (uint8_t)(rw >> (8 * j)); p.g[off + j] = (uint8_t)(gw >> (8 * j)); p.b[off + j] = (uint8_t)(bw >> (8 * j));
-        }
+        // planes: rows are Ws apart and frames plane_stride, neither need be a multiple of 4 -- the word store goes by the addresses
+        const size_t off = (size_t)y * p.Ws + x0;
+        store_planes4(p.r, p.g, p.b, off, npx, rw, gw, bw, planes_word_aligned(p.r, p.g, p.b, off));
     }
 }
 

@@ -6,7 +6,7 @@
 // (decode_mcu replicates, ref decoder/jpezy_decoder.hpp:504-528); the definition is this project's own.  Every other component is
 // placed exactly as generic_rgb_kernel places it, and make_rgb / revise_value are the reference's FP64 expressions (ref :531-578,
 // 672-676), left to right.
-#include "jpezy_wave.h"
+#include "jpezy_pixel_out.h"
 
 namespace jpezy_dev {
 namespace smooth {
@@ -18,9 +18,6 @@ struct SmoothParams {
     unsigned ch_magic[3], ch_shift[3], cv_magic[3], cv_shift[3];   // fast_div by H_c, V_c
 };
 
-__device__ __forceinline__ uint32_t revise(double v) { return (v < 0.0) ? 0u : (v > 255.0) ? 255u : (uint32_t)v; }
-__device__ __forceinline__ int clamp8(int s) { return min(max(s, 0), 255); }
-
 // make_rgb / revise_value in the reference's FP64 order (ref :531-578, 672-676) and generic_rgb_kernel's store stage
 template <int PIX>
 __device__ __forceinline__ void colour_store(const GenericDecParams& p, const int (&smp)[3][4], unsigned x0, unsigned y, unsigned npx)
@@ -28,58 +25,17 @@ __device__ __forceinline__ void colour_store(const GenericDecParams& p, const in
     uint32_t rw = 0, gw = 0, bw = 0;
 #pragma unroll
     for (unsigned j = 0; j < 4; ++j) {
-        const double yp = smp[0][j], up = smp[1][j], vp = smp[2][j];
         uint32_t r, g, b;
-        if (!p.gray) {
-            r = revise(yp + (vp - 0x80) * 1.4020);
-            g = revise(yp - (up - 0x80) * 0.3441 - (vp - 0x80) * 0.7139);
-            b = revise(yp + (up - 0x80) * 1.7718);
-        } else {
-            r = g = b = revise(yp);
-        }
+        make_rgb(p.gray, smp[0][j], smp[1][j], smp[2][j], r, g, b);
         rw |= r << (8 * j); gw |= g << (8 * j); bw |= b << (8 * j);
     }
-    if (PIX != 0) {
+    if constexpr (PIX != 0) {
         const bool blue_first = p.b < p.r;                       // r, g, b: the channel bytes of pixel (0, 0)
         uint8_t* px = (blue_first ? p.b : p.r) + (size_t)y * p.row_stride + (size_t)x0 * PIX;
-        const uint32_t fw = blue_first ? bw : rw, tw = blue_first ? rw : bw;
-        auto byte = [](uint32_t w, unsigned j) { return (w >> (8 * j)) & 0xFFu; };
-        if (npx == 4 && ((uintptr_t)px & 3u) == 0) {
-            if (PIX == 3) {
-                typedef unsigned v3u __attribute__((ext_vector_type(3)));
-                typedef v3u v3u_a4 __attribute__((aligned(4)));
-                v3u v;
-                v.x = byte(fw, 0) | byte(gw, 0) << 8 | byte(tw, 0) << 16 | byte(fw, 1) << 24;
-                v.y = byte(gw, 1) | byte(tw, 1) << 8 | byte(fw, 2) << 16 | byte(gw, 2) << 24;
-                v.z = byte(tw, 2) | byte(fw, 3) << 8 | byte(gw, 3) << 16 | byte(tw, 3) << 24;
-                *reinterpret_cast<v3u_a4*>(px) = v;
-            } else {
-                typedef unsigned v4u __attribute__((ext_vector_type(4)));
-                typedef v4u v4u_a4 __attribute__((aligned(4)));
-                v4u v;
-                v.x = byte(fw, 0) | byte(gw, 0) << 8 | byte(tw, 0) << 16 | 0xFF000000u;
-                v.y = byte(fw, 1) | byte(gw, 1) << 8 | byte(tw, 1) << 16 | 0xFF000000u;
-                v.z = byte(fw, 2) | byte(gw, 2) << 8 | byte(tw, 2) << 16 | 0xFF000000u;
-                v.w = byte(fw, 3) | byte(gw, 3) << 8 | byte(tw, 3) << 16 | 0xFF000000u;
-                *reinterpret_cast<v4u_a4*>(px) = v;
-            }
-        } else {
-            for (unsigned j = 0; j < npx; ++j) {
-                px[j * PIX] = (uint8_t)byte(fw, j); px[j * PIX + 1] = (uint8_t)byte(gw, j); px[j * PIX + 2] = (uint8_t)byte(tw, j);
-                if (PIX == 4) px[j * PIX + 3] = 0xFF;
-            }
-        }
-        return;
-    }
-    const size_t off = (size_t)y * p.W + x0;
-    if (npx == 4 && (p.W & 3) == 0) {                           // rows start 4-byte aligned (the planes are device allocations)
-        *reinterpret_cast<uint32_t*>(p.r + off) = rw;
-        *reinterpret_cast<uint32_t*>(p.g + off) = gw;
-        *reinterpret_cast<uint32_t*>(p.b + off) = bw;
+        store_packed4<PIX>(px, npx, blue_first ? bw : rw, gw, blue_first ? rw : bw);
     } else {
-        for (unsigned j = 0; j < npx; ++j) {
-            p.r[off + j] = (uint8_t)(rw >> (8 * j)); p.g[off + j] = (uint8_t)(gw >> (8 * j)); p.b[off + j] = (uint8_t)(bw >> (8 * j));
-        }
+        const size_t off = (size_t)y * p.W + x0;
+        store_planes4(p.r, p.g, p.b, off, npx, rw, gw, bw, (p.W & 3) == 0);   // rows start 4-byte aligned (the planes are device allocations)
     }
 }
 

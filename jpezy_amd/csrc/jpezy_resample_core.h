@@ -13,17 +13,6 @@ static_assert(kGroupsX * kResampleTileH == kThreads, "one thread per group of fo
 
 __device__ __forceinline__ int clip8(int v) { return v < 0 ? 0 : v > 255 ? 255 : v; }
 
-// the file of workgroup wg: the last descriptor whose first workgroup is <= wg (wg0 ascending, desc[0].wg0 == first workgroup of the launch)
-__device__ __forceinline__ unsigned find_file(const ResampleDesc* __restrict__ desc, unsigned n, unsigned wg)
-{
-    unsigned lo = 0, hi = n;                      // invariant: desc[lo].wg0 <= wg, and (hi == n or desc[hi].wg0 > wg)
-    while (hi - lo > 1) {
-        const unsigned mid = lo + ((hi - lo) >> 1);
-        if (desc[mid].wg0 <= wg) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 // the descriptor of the workgroup's file (uniform by construction; readfirstlane tells the compiler so, and the descriptor is then read
 // with scalar loads)
 __device__ __forceinline__ const ResampleDesc& workgroup_file(const ResampleParams& p)

@@ -1,5 +1,6 @@
-// jpezy_wave.h -- the wave-level plumbing every kernel file shares (no arithmetic of the codec: see jpezy_kernels_f64.hip on why
-// the transforms, colour formulas and tables of the two encoders are NOT shared).
+// jpezy_wave.h -- the wave-level plumbing every kernel file shares.  No arithmetic of the codec: the decoders' colour and store stage is
+// shared through jpezy_pixel_out.h; the transforms, colour formulas and tables of the two encoders are NOT shared (see jpezy_kernels_f64.hip
+// on why).
 #pragma once
 #include "jpezy_device.h"
 
@@ -21,6 +22,20 @@ __device__ __forceinline__ void wave_sync()
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// A 1-D grid over the workgroups of many files (WindowDesc, ResampleDesc): the file of workgroup wg is the last descriptor whose first
+// workgroup is <= wg (wg0 ascending, desc[0].wg0 == first workgroup of the call).  The result depends on blockIdx alone; a kernel passes it
+// through readfirstlane and then reads the descriptor with scalar loads.
+template <class Desc>
+__device__ __forceinline__ unsigned find_file(const Desc* __restrict__ desc, unsigned n, unsigned wg)
+{
+    unsigned lo = 0, hi = n;                      // invariant: desc[lo].wg0 <= wg, and (hi == n or desc[hi].wg0 > wg)
+    while (hi - lo > 1) {
+        const unsigned mid = lo + ((hi - lo) >> 1);
+        if (desc[mid].wg0 <= wg) lo = mid; else hi = mid;
+    }
+    return lo;
 }
 
 // Outputs are streamed out and never re-read by the kernel: a non-temporal store leaves less dirty data in the eight

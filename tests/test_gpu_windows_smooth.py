@@ -264,3 +264,35 @@ def test_resized_large_ratio(J, torch, ctx, own_files):
     assert RM.taps(208, 3)[0] >= 139
     ctx.set_windows_upsampling(J.UPSAMPLE_SMOOTH)
     run_resized(J, torch, ctx, [f, f], [((0, 0, 208, 120), 1), ((5, 0, 1, 120), 1)], (3, 2), J.PIX_RGB24)
+
+
+@pytest.mark.parametrize("layout", ["444", "one"])
+def test_nothing_smoothed_both_smooth_entries_give_the_replicate_entries_bytes(J, torch, ctx, layout):
+    """the smooth and the replicate entries are two instances of one kernel body: on a layout that smooths nothing, at a ragged 37 x 21
+    and N = 8 and 1, the smooth region entry (planes and one packed format) and the smooth window-batch entry return byte for byte
+    what the replicate entries return -- whole buffers, padding included"""
+    assert layout in K.NOTHING_SMOOTHED
+    W, H = 37, 21
+    data = K.jpeg(layout, W, H)
+    info, d_co = ctx.read_jpeg_gpu(data)
+    fmt, nb = J.PIX_BGR24, 3
+    for scale in (1, 8):
+        ws, hs = M.scaled_size(W, H, scale)
+        for region in ((0, 0, ws, hs), (1, 1, ws - 1, hs - 1)):            # the second: an origin that is no multiple of 4
+            x, y, w, h = region
+            got = {}
+            for ups in (J.UPSAMPLE_NEAREST, J.UPSAMPLE_SMOOTH):
+                planes = [torch.full((w * h + 4,), FILL, dtype=torch.uint8, device="cuda:0") for _ in range(3)]
+                ctx.dequant_idct_region_dev(d_co, info, region, scale, *planes, upsampling=ups)
+                row = w * nb + 5
+                buf = torch.full((h * row + 4,), FILL, dtype=torch.uint8, device="cuda:0")
+                ctx.dequant_idct_region_dev(d_co, info, region, scale, d_img=buf.as_strided((h, w, nb), (row, nb, 1)), format=fmt, upsampling=ups)
+                torch.cuda.synchronize()
+                # (run: both files' status 0 and the whole buffer against the model, which replicates where nothing is smoothed)
+                batch = run(J, torch, ctx, [data, data], [(region, scale), ((0, 0, 0, 0), scale)], fmt, hs, ws, row_extra=5, upsampling=ups)[1]
+                got[ups] =[p.cpu().numpy() for p in planes] + [buf.cpu().numpy(), batch]
+            # the replicate entries against the model, so that equality is not equality of two untouched buffers
+            for a, e in zip(got[J.UPSAMPLE_NEAREST][:3], K.want(data, region, scale, False)):
+                assert np.array_equal(a[:w * h].reshape(h, w), e), (layout, scale, region)
+            for a, b in zip(got[J.UPSAMPLE_NEAREST], got[J.UPSAMPLE_SMOOTH]):
+                assert np.array_equal(a, b), (layout, scale, region)

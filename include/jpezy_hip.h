@@ -20,7 +20,10 @@
  * cached JFIF header of jpezy_write_jpeg_gpu_dev) are rewritten only when the caller's tables / comment / size
  * change; the library then waits for the WHOLE device first (launches on other streams may still read them), and it
  * refuses (JPEZY_E_BADARG) to do so while `stream` is being captured into a hipGraph: make the first call with new
- * tables outside the capture.
+ * tables outside the capture.  The same holds for the scratch that lives in the context (the samples of the any-layout and
+ * reduced-size decoders, the buffers and code tables of the entropy entry points): it grows by a free and an allocation, so a
+ * call that needs more of it than the context holds is refused with JPEZY_E_BADARG inside a capture, before anything is freed,
+ * allocated or enqueued -- make the first call of a context, and the first with larger frames or more of them, outside the capture.
  *
  * Coefficient buffer layout (both directions), per frame:
  *     int16_t coeffs[mcu_rows][mcu_cols][B][64]

@@ -658,7 +658,8 @@ int jpezy_internal_generic_dev_core(jpezy_ctx* c, const DecodeSource& src, const
     p.c_row_stride = out.c_row_stride;
     const int per = generic_frames_per_launch(p);            // samples scratch: the frames of one launch (launches run in stream order)
     if (per < 1) return set_err(JPEZY_E_UNSUPPORTED, "generic decoder: frame of more than 2^31 blocks");
-    if (int rc = c->scratch.reserve(geometry_blocks(p) * 64 * sizeof(int) * (size_t)std::min(src.n_frames, per))) return rc;
+    if (int rc = grow_outside_capture(c->scratch, geometry_blocks(p) * 64 * sizeof(int) * (size_t)std::min(src.n_frames, per), s, "generic decoder"))
+        return rc;
     // per-component dequantiser constants (fast path) and integer quantisers (reference-order path), cached in the context
     if (int rc = upload_dequant(c, src, s)) return rc;
     p.samples = c->scratch.as<int>();

@@ -60,12 +60,13 @@ void fill_code_image(jpezy_dev::entropy::CodeTables& h, const jpezy_host::HuffTa
     }
 }
 
-int ensure_code_tables(jpezy_ctx* c)
+// s: the stream the caller enqueues on -- the first call of a context allocates and copies synchronously, which a capture of s forbids
+int ensure_code_tables(jpezy_ctx* c, hipStream_t s)
 {
     if (c->d_codes.p) return JPEZY_OK;
     std::vector<jpezy_dev::entropy::CodeTables> hv(1);       // 10 KB: off the stack
     fill_code_image(hv[0], nullptr);
-    if (int rc = c->d_codes.reserve(sizeof hv[0])) return rc;
+    if (int rc = grow_outside_capture(c->d_codes, sizeof hv[0], s, "entropy coder")) return rc;
     HIP_TRY(hipMemcpy(c->d_codes.p, &hv[0], sizeof hv[0], hipMemcpyHostToDevice));
     return JPEZY_OK;
 }
@@ -127,16 +128,18 @@ struct Pass {
         s = stream;
         make_job(job, d_coeffs, W, H, gray, F, c->d_codes.as<E::CodeTables>(), c->restart_interval, sampling);
         const E::ScratchSizes z = E::scratch_sizes(job, c->huff_optimize != 0);
-        if (int rc = c->e_S.reserve(z.tile_stream)) return rc;
-        if (int rc = c->e_tt.reserve(z.tile_total)) return rc;
-        if (int rc = c->e_base.reserve(z.tile_base)) return rc;
-        if (int rc = c->e_ft.reserve(z.first_tile)) return rc;
-        if (int rc = c->e_rpad.reserve(z.restart_pad)) return rc;
-        if (int rc = c->e_U.reserve(z.U)) return rc;
-        if (int rc = c->e_cnt.reserve(z.ff_loc)) return rc;
-        if (int rc = c->e_fft.reserve(z.ff_piece)) return rc;
-        if (int rc = c->e_mk.reserve(z.markers)) return rc;
-        if (int rc = c->e_small.reserve(2 * z.bytes + z.flags)) return rc;      // [F] stream bytes | [F] added bytes | [F] flags
+        // (every buffer that must grow refuses inside a capture of s; nothing has been enqueued by then)
+        auto grow = [&](DevBuf& b, size_t n) { return grow_outside_capture(b, n, s, "entropy coder"); };
+        if (int rc = grow(c->e_S, z.tile_stream)) return rc;
+        if (int rc = grow(c->e_tt, z.tile_total)) return rc;
+        if (int rc = grow(c->e_base, z.tile_base)) return rc;
+        if (int rc = grow(c->e_ft, z.first_tile)) return rc;
+        if (int rc = grow(c->e_rpad, z.restart_pad)) return rc;
+        if (int rc = grow(c->e_U, z.U)) return rc;
+        if (int rc = grow(c->e_cnt, z.ff_loc)) return rc;
+        if (int rc = grow(c->e_fft, z.ff_piece)) return rc;
+        if (int rc = grow(c->e_mk, z.markers)) return rc;
+        if (int rc = grow(c->e_small, 2 * z.bytes + z.flags)) return rc;      // [F] stream bytes | [F] added bytes | [F] flags
         sc.tile_stream = c->e_S.as<uint32_t>();
         sc.tile_total = c->e_tt.as<uint32_t>();
         sc.tile_base = c->e_base.as<unsigned long long>();
@@ -157,7 +160,7 @@ struct Pass {
             HIP_TRY(hipMemsetAsync(sc.status, 0, z.flags, s));
         } else {
             if (c->e_status.cap < z.flags) {
-                if (int rc = c->e_status.reserve(z.flags)) return rc;
+                if (int rc = grow(c->e_status, z.flags)) return rc;
                 HIP_TRY(hipMemsetAsync(c->e_status.p, 0, c->e_status.cap, s));
             }
             sc.status = c->e_status.as<unsigned>();
@@ -191,7 +194,7 @@ struct Pass {
 // symbol counts of the job's frames (job.tables is not read)
 int enqueue_histogram(const jpezy_dev::entropy::Job& job, unsigned long long* d_hist, unsigned* d_status, hipStream_t s)
 {
-    HIP_TRY(hipMemsetAsync(d_hist, 0, (size_t)job.n_frames * 4 * 256 * sizeof(unsigned long long), s));
+    HIP_TRY(jpezy_dev::entropy::launch_zero_histogram(d_hist, job.n_frames, s));      // (not hipMemsetAsync: jpezy_huffstat.hip)
     HIP_TRY(jpezy_dev::entropy::launch_symbol_histogram(job, d_hist, d_status, s));
     return JPEZY_OK;
 }
@@ -296,8 +299,8 @@ int jpezy_internal_write_jpeg_gpu_dev(jpezy_ctx* c, const int16_t* d_coeffs, int
         return set_err(JPEZY_E_UNSUPPORTED, "write_jpeg_gpu_dev: per-image Huffman tables are built on the host and this call is asynchronous; "
                                             "use jpezy_write_jpeg_gpu[_batch] or jpezy_ctx_set_huffman_optimize(ctx, 0)");
     HIP_TRY(hipSetDevice(c->device));
-    if (int rc = ensure_code_tables(c)) return rc;
     hipStream_t s = (hipStream_t)stream;
+    if (int rc = ensure_code_tables(c, s)) return rc;
     // header bytes: cached on the device per (W, H, comment, restart interval, quantisation tables: the bytes are compared) -- uploaded outside any capture on first use; 1024 bytes hold the
     // header with the longest comment allowed (JPEZY_MAX_COMMENT; with a DRI segment JPEZY_MAX_COMMENT_RESTART)
     uint8_t hdr[1024];
@@ -305,8 +308,8 @@ int jpezy_internal_write_jpeg_gpu_dev(jpezy_ctx* c, const int16_t* d_coeffs, int
                                                     chroma ? chroma : c->qt[1], sampling);
     if (!hdr_len) return set_err(JPEZY_E_BADARG, "write_jpeg_gpu_dev: comment too long");
     if (c->e_hdr_len != hdr_len || std::memcmp(c->e_hdr_host, hdr, hdr_len)) {
-        if (int rc = c->e_hdr.reserve(sizeof hdr)) return rc;
         if (int rc = drain_before_table_rewrite(s, "write_jpeg_gpu_dev")) return rc;   // an earlier launch (any stream) may still read the old header
+        if (int rc = c->e_hdr.reserve(sizeof hdr)) return rc;                          // (behind the capture check: the first call allocates)
         HIP_TRY(hipMemcpy(c->e_hdr.p, hdr, hdr_len, hipMemcpyHostToDevice));
         std::memcpy(c->e_hdr_host, hdr, hdr_len);
         c->e_hdr_len = hdr_len;
@@ -341,7 +344,7 @@ try {
     if (int rc = check_comment(comment, "write_jpeg_gpu")) return rc;
     if (int rc = check_restart_comment(c, comment, "write_jpeg_gpu")) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    if (int rc = ensure_code_tables(c)) return rc;
+    if (int rc = ensure_code_tables(c, c->stream)) return rc;
     const int per = frames_per_pass(c, W, H, gray, n_frames, sampling);
     bool any_failed = false;
     const size_t cpf = sampling == JPEZY_SAMPLING_420 ? jpezy_coeff_count(W, H, gray) : jpezy_coeff_count_sampling(W, H, sampling);
@@ -404,8 +407,7 @@ int jpezy_internal_huffman_histogram_dev(jpezy_ctx* c, const int16_t* d_coeffs, 
     const size_t cpf = sampling == JPEZY_SAMPLING_420 ? jpezy_coeff_count(W, H, gray) : jpezy_coeff_count_sampling(W, H, sampling);
     for (int f0 = 0; f0 < n_frames; f0 += kMaxFramesPerLaunch) {
         const int F = std::min(kMaxFramesPerLaunch, n_frames - f0);
-        if (c->e_hstat.cap < sizeof(unsigned) * (size_t)F)
-            if (int rc = c->e_hstat.reserve(sizeof(unsigned) * (size_t)F)) return rc;
+        if (int rc = grow_outside_capture(c->e_hstat, sizeof(unsigned) * (size_t)F, s, "huffman_histogram_dev")) return rc;
         E::Job job;
         make_job(job, d_coeffs + (size_t)f0 * cpf, W, H, gray, F, nullptr, c->restart_interval, sampling);
         if (int rc = enqueue_histogram(job, d_hist + (size_t)f0 * 4 * 256, c->e_hstat.as<unsigned>(), s)) return rc;

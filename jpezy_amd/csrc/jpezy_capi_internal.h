@@ -64,6 +64,24 @@ inline int check_wh(int W, int H)
 // coefficient buffers are moved with 16-byte accesses (one MCU = 768 or 512 bytes, so only the base matters)
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
+inline bool stream_is_capturing(hipStream_t s)
+{
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    return hipStreamIsCapturing(s, &st) == hipSuccess && st != hipStreamCaptureStatusNone;
+}
+
+// Scratch that lives in the context grows by a hipFree and a hipMalloc.  HIP refuses both while a stream is being captured and
+// invalidates the capture over it, so a *_dev entry whose scratch must grow refuses first, with nothing freed, allocated or enqueued:
+// the first call with these arguments belongs outside the capture, as for the tables.
+inline int grow_outside_capture(DevBuf& b, size_t n, hipStream_t s, const char* what)
+{
+    if (n <= b.cap) return JPEZY_OK;
+    if (stream_is_capturing(s))
+        return set_err(JPEZY_E_BADARG, std::string(what) + ": the context's scratch cannot grow while the stream is being captured; "
+                                                            "make the first call with these arguments outside the capture");
+    return b.reserve(n);
+}
+
 // Context-wide device tables (dequantiser constants, cached JFIF header) may be read by launches still in flight on ANY
 // stream the caller drives this context with: before rewriting them, wait for the whole device; and never from inside
 // a stream capture (a synchronisation there would invalidate the capture).
@@ -71,8 +89,7 @@ inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 // that stream is enough (eight children that each stalled the whole device for every file with new tables serialised the batch).
 inline int drain_before_table_rewrite(hipStream_t s, const char* what, bool own_stream_only = false)
 {
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &st) == hipSuccess && st != hipStreamCaptureStatusNone)
+    if (stream_is_capturing(s))
         return set_err(JPEZY_E_BADARG, std::string(what) + ": new tables/header cannot be uploaded while the stream is being captured; "
                                                             "make the first call with these arguments outside the capture");
     if (own_stream_only)

@@ -13,7 +13,9 @@ int jpezy_internal_scaled_dev_core(jpezy_ctx* c, const DecodeSource& src, const 
     (void)jpezy_scaled_size(src.W, src.H, 8 >> log2n, &p.Ws, &p.Hs);
     const int per = scaled_frames_per_launch(p);             // samples scratch: the frames of one launch (launches run in stream order)
     if (per < 1) return set_err(JPEZY_E_UNSUPPORTED, "scaled decoder: frame of more than 2^31 blocks");
-    if (int rc = c->scratch.reserve((geometry_blocks(p) << (2 * log2n)) * sizeof(int) * (size_t)std::min(src.n_frames, per))) return rc;
+    if (int rc = grow_outside_capture(c->scratch, (geometry_blocks(p) << (2 * log2n)) * sizeof(int) * (size_t)std::min(src.n_frames, per), s,
+                                      "scaled decoder"))
+        return rc;
     if (int rc = upload_dequant(c, src, s)) return rc;
     p.samples = c->scratch.as<int>();
     HIP_TRY(launch_dequant_idct_scaled(p, s));

@@ -139,6 +139,8 @@ hipError_t launch_ff_frame_totals(const Job& job, const Scratch& sc, unsigned lo
 // counted as the clamped symbol with status[frame] |= 1.  hist must be zero before the launch (job.tables is not read).
 // job.restart: the DC predictors are zero at every interval's start, as the coder has them.
 hipError_t launch_symbol_histogram(const Job& job, unsigned long long* hist, unsigned* status, hipStream_t s);
+// hist[0 .. n_frames * 4 * 256) = 0 on stream s, by a kernel (a memset node does not survive the replay of a captured graph)
+hipError_t launch_zero_histogram(unsigned long long* hist, int n_frames, hipStream_t s);
 
 }  // namespace entropy
 }  // namespace jpezy_dev

@@ -102,6 +102,23 @@ __global__ __launch_bounds__(HWG) void symbol_histogram_kernel(Job job, unsigned
     }
 }
 
+// The counters are zeroed by a kernel, not by hipMemsetAsync: a memset node of a captured graph writes its value on the graph's first
+// launch only and stale bytes on every later one (seen with a bare hipMemsetAsync in a graph of one node), which made a captured
+// jpezy_huffman_histogram_dev right once and wrong on every replay (tests/test_gpu_streams.py, test_capture_replay[histogram]).
+__global__ __launch_bounds__(HWG) void zero_histogram_kernel(unsigned long long* hist, size_t n)
+{
+    const size_t i = (size_t)blockIdx.x * HWG + threadIdx.x;
+    if (i < n) hist[i] = 0;
+}
+
+hipError_t launch_zero_histogram(unsigned long long* hist, int n_frames, hipStream_t s)
+{
+    if (n_frames <= 0) return hipSuccess;
+    const size_t n = (size_t)n_frames * 4 * 256;                // at most 65535 frames a launch: 2^18 workgroups
+    hipLaunchKernelGGL(zero_histogram_kernel, dim3((unsigned)((n + HWG - 1) / HWG)), dim3(HWG), 0, s, hist, n);
+    return hipGetLastError();
+}
+
 hipError_t launch_symbol_histogram(const Job& job, unsigned long long* hist, unsigned* status, hipStream_t s)
 {
     if (!job.blocks_per_frame || job.n_frames <= 0) return hipSuccess;

@@ -779,14 +779,58 @@ int jpezy_ctx_set_windows_slice_files(jpezy_ctx* ctx, int n);
  *                 that counts against the slice bound
  *   Synchronous   on return the pixels are complete in device memory.  Refused inside a stream capture
  *
+ *   FILTERS       The above is JPEZY_FILTER_BILINEAR, the default.  jpezy_ctx_set_windows_filter chooses another filter for this entry and
+ *                 for jpezy_decode_windows_tensor_dev (restated in tests/resize_filter_model.py).  Everything above holds
+ *                 -- separable passes, horizontal first, each rounded and clipped to a byte, 22 fraction bits, 32-bit accumulators,
+ *                 byte 3, the mirror, the shapes of first / count / ksize -- and three things become functions of the filter:
+ *                     filter                   value   fsup   f(x)
+ *                     JPEZY_FILTER_BILINEAR    0       1      1 - |x| for |x| < 1, else 0
+ *                     JPEZY_FILTER_BOX         1       0.5    1 for -0.5 < x <= 0.5, else 0
+ *                     JPEZY_FILTER_BICUBIC     2       2      with a = -0.5 and x = |x|: ((a + 2) * x - (a + 3)) * x * x + 1 for x < 1;
+ *                                                             (((x - 5) * x + 8) * x - 4) * a for x < 2; else 0
+ *                     JPEZY_FILTER_LANCZOS     3       3      sinc(x) * sinc(x / 3) for -3 <= x < 3, else 0; sinc(0) = 1,
+ *                                                             sinc(x) = sin(pi * x) / (pi * x), pi * x one product with
+ *                                                             pi = 3.14159265358979323846
+ *                   Support    support = fsup * fs (fs and ss as above), ksize = 2 * (int)ceil(support) + 1; first, last and count from
+ *                              center -+ support + 0.5 exactly as above
+ *                   Weights    w_j = f((j + first - center + 0.5) * ss), k_j = w_j / sum(w) when sum(w) != 0, else w_j
+ *                   Rounding   K_j = (int)(k_j * 2^22 + 0.5) for k_j >= 0 and (int)(k_j * 2^22 - 0.5) for k_j < 0
+ *                 Every binary64 operation is separate and in the order written.  JPEZY_FILTER_LANCZOS, alone of the four, rests on the
+ *                 platform's binary64 sin (the C library's); the others are plain arithmetic.  Bicubic and Lanczos have negative weights:
+ *                 an accumulator can be negative, its shift >> 22 is arithmetic, and the clip to 0..255 follows it.  The accumulators
+ *                 cannot overflow when, for every output index, 255 * (sum of the positive K) + 2^21 < 2^31 and 255 * (sum of the
+ *                 negative K's magnitudes) <= 2^31 - 2^21.  The tables' builder checks this condition and answers JPEZY_E_UNSUPPORTED
+ *                 where it fails (jpezy_resize_taps_filter, and the two entries for the file concerned); it is a condition, not a proof,
+ *                 and has not been seen to fail: the largest sums met are 1.125 * 2^22 and 0.125 * 2^22 (bicubic), 1.279 * 2^22 and
+ *                 0.279 * 2^22 (Lanczos).  With JPEZY_FILTER_BILINEAR every table, and so every byte, is the one defined above.  For
+ *                 3-byte pixels box, bicubic and Lanczos equal Pillow 12's Image.resize(size, BOX / BICUBIC / LANCZOS) byte for byte.
+ *                 A file of a child context (Paths) is resampled with the filter of the context the call was made on.
+ *
  * NOT provided: other filters (nearest, bicubic); a per-file output size; a vertical mirror; host-memory output; smooth chroma upsampling
  * of the source window.  What stood first on this list, float or planar (CHW) output and normalisation, is the section after this
- * one: BATCH OF WINDOWS, TENSOR OUTPUT.
+ * one: BATCH OF WINDOWS, TENSOR OUTPUT.  Of the list as it stands, smooth chroma upsampling exists (jpezy_ctx_set_windows_upsampling) and
+ * so do bicubic, Lanczos and box (FILTERS above); the nearest and the Hamming filter are what is still not provided under "other filters".
  */
+enum jpezy_filter { JPEZY_FILTER_BILINEAR = 0, JPEZY_FILTER_BOX = 1, JPEZY_FILTER_BICUBIC = 2, JPEZY_FILTER_LANCZOS = 3 };
 /* Pure host function: the tables of one axis.  *ksize = 2 * (int)ceil(support) + 1 (>= every count); first[out_size], count[out_size],
  * weight[out_size][ksize], zero behind count.  first, count and weight all NULL: *ksize only.  Sizes outside 1..65535: JPEZY_E_BADARG;
  * weight_cap (in elements) < out_size * ksize: JPEZY_E_NOSPACE. */
 int jpezy_resize_taps(int in_size, int out_size, int* ksize, int* first, int* count, int32_t* weight, size_t weight_cap);
+/* The same for a filter of enum jpezy_filter (FILTERS above): jpezy_resize_taps's contract, and JPEZY_E_BADARG for an unknown filter
+ * (checked first), JPEZY_E_UNSUPPORTED when the weights of some output index fail the accumulator condition.  jpezy_resize_taps is this
+ * function at JPEZY_FILTER_BILINEAR. */
+int jpezy_resize_taps_filter(int filter, int in_size, int out_size, int* ksize, int* first, int* count, int32_t* weight, size_t weight_cap);
+/* The resampling filter of jpezy_decode_windows_resized_dev and jpezy_decode_windows_tensor_dev, per context: a value of enum jpezy_filter,
+ * JPEZY_FILTER_BILINEAR by default.  An unknown value is JPEZY_E_BADARG and leaves the setting unchanged.  The getter returns the
+ * setting. */
+int jpezy_ctx_set_windows_filter(jpezy_ctx* ctx, int filter);
+int jpezy_ctx_windows_filter(jpezy_ctx* ctx);
+/* Test and measurement knobs, per context; the bytes do not depend on them.  Box, bicubic and Lanczos run a two-pass form of the
+ * resampling kernel (the horizontal pass of a tile's source rows once, through LDS) for every file whose tiles span few enough source
+ * rows, and the direct loop of the bilinear filter for the others.  on != 0: the direct loop for every file.
+ * jpezy_ctx_last_resample_tiled_count: the files of the context's last resized or tensor call that ran the two-pass form. */
+int jpezy_ctx_set_resample_direct(jpezy_ctx* ctx, int on);
+int jpezy_ctx_last_resample_tiled_count(jpezy_ctx* ctx);
 /* Pure host function: src, a rectangle in the FULL-SIZE picture (inside W x H, else JPEZY_E_BADARG), as a window for an output of
  * out_w x out_h: s = the largest of 8, 4, 2, 1 with src.w / s >= out_w and src.h / s >= out_h (integer division), else 1;
  * *win = {{src.x / s, src.y / s, max(1, src.w / s), max(1, src.h / s)}, s}.  That window always lies inside the picture at 1/s
@@ -834,8 +878,11 @@ int jpezy_decode_windows_resized_dev(jpezy_ctx* ctx, int n, const uint8_t* const
  *                 4-byte word that belongs to a neighbouring element
  *   Unchanged     info, placed, status, the per-file failure rule, the grouped / sliced / child-context paths, synchronisation and the
  *                 refusal inside a stream capture are those of jpezy_decode_windows_resized_dev
+ *   Filter        the resampling filter is the context's (jpezy_ctx_set_windows_filter; BATCH OF WINDOWS, RESIZED, FILTERS): bilinear by
+ *                 default, box, bicubic or Lanczos
  *
- * NOT provided: per-file output sizes; other filters; a vertical mirror; host-memory output; float output from the other decode entries.
+ * NOT provided: per-file output sizes; the nearest and the Hamming filter; a vertical mirror; host-memory output; float output from the
+ * other decode entries.
  */
 enum jpezy_dtype { JPEZY_DT_U8 = 0, JPEZY_DT_F32 = 1, JPEZY_DT_F16 = 2, JPEZY_DT_BF16 = 3 };
 /* Pure host function: scale[c] = (float)(1.0 / (255.0 * std[c])), bias[c] = (float)(-mean[c] / std[c]) for c < C (3 or 1), computed in binary64

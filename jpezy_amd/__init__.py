@@ -18,6 +18,10 @@ from .api import (  # noqa: F401
     DT_U8,
     Decoder,
     Encoder,
+    FILTER_BICUBIC,
+    FILTER_BILINEAR,
+    FILTER_BOX,
+    FILTER_LANCZOS,
     FrameInfo,
     JpezyError,
     MultiEncoder,
@@ -68,6 +72,6 @@ from .api import (  # noqa: F401
 )
 
 __all__ = [
-    "Context", "DOWNSAMPLE_AVERAGE", "DOWNSAMPLE_POINT", "DT_BF16", "DT_F16", "DT_F32", "DT_U8", "Decoder", "Encoder", "FrameInfo", "JpezyError", "MultiEncoder", "PIX_BGR24", "PIX_BGRA32", "PIX_RGB24", "PIX_RGBA32", "Rect", "SAMPLING_420", "SAMPLING_444", "UPSAMPLE_NEAREST", "UPSAMPLE_SMOOTH", "Window", "XFORM_HFLIP", "XFORM_NONE", "XFORM_ROT180", "XFORM_ROT270", "XFORM_ROT90", "XFORM_TRANSPOSE", "XFORM_TRANSVERSE", "XFORM_TRIM", "XFORM_VFLIP", "coeff_count", "encode_batch_multi", "huffman_histogram", "jpeg_bound", "library_path",
+    "Context", "DOWNSAMPLE_AVERAGE", "DOWNSAMPLE_POINT", "DT_BF16", "DT_F16", "DT_F32", "DT_U8", "Decoder", "Encoder", "FILTER_BICUBIC", "FILTER_BILINEAR", "FILTER_BOX", "FILTER_LANCZOS", "FrameInfo", "JpezyError", "MultiEncoder", "PIX_BGR24", "PIX_BGRA32", "PIX_RGB24", "PIX_RGBA32", "Rect", "SAMPLING_420", "SAMPLING_444", "UPSAMPLE_NEAREST", "UPSAMPLE_SMOOTH", "Window", "XFORM_HFLIP", "XFORM_NONE", "XFORM_ROT180", "XFORM_ROT270", "XFORM_ROT90", "XFORM_TRANSPOSE", "XFORM_TRANSVERSE", "XFORM_TRIM", "XFORM_VFLIP", "coeff_count", "encode_batch_multi", "huffman_histogram", "jpeg_bound", "library_path",
     "load_library", "mcu_grid", "optimal_table", "quality_tables", "quant_tables_probe", "quant_tables_transform", "read_jpeg", "region_check", "resize_pick_window", "resize_taps", "sampling_geometry", "scaled_size", "shard_range", "tensor_normalization", "transform_geometry", "window_fit", "write_jpeg", "write_jpeg_batch", "ycc_chroma_size", "ycc_component_size",
 ]

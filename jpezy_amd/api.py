@@ -148,6 +148,11 @@ ABI = [
     ("jpezy_decode_windows_dev", C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, C.c_size_t, C.c_size_t, _vp, C.c_size_t, _vp, _vp, _vp]),
     ("jpezy_ctx_set_windows_slice_files", C.c_int, [_vp, C.c_int]),
     ("jpezy_resize_taps", C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), _vp, _vp, _vp, C.c_size_t]),
+    ("jpezy_resize_taps_filter", C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), _vp, _vp, _vp, C.c_size_t]),
+    ("jpezy_ctx_set_windows_filter", C.c_int, [_vp, C.c_int]),
+    ("jpezy_ctx_windows_filter", C.c_int, [_vp]),
+    ("jpezy_ctx_set_resample_direct", C.c_int, [_vp, C.c_int]),
+    ("jpezy_ctx_last_resample_tiled_count", C.c_int, [_vp]),
     ("jpezy_resize_pick_window", C.c_int, [C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp]),
     ("jpezy_decode_windows_resized_dev", C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, _vp,
                                                    C.c_size_t, _vp, _vp, _vp]),
@@ -223,6 +228,7 @@ XFORM_TRIM = 1
 # enum jpezy_upsampling: how the decoder brings subsampled chroma to picture size -- replication (the reference's, the default) or the
 # triangle filter over the component's native plane (include/jpezy_hip.h, CHROMA UPSAMPLING)
 UPSAMPLE_NEAREST, UPSAMPLE_SMOOTH = 0, 1
+FILTER_BILINEAR, FILTER_BOX, FILTER_BICUBIC, FILTER_LANCZOS = 0, 1, 2, 3      # enum jpezy_filter
 
 # enum jpezy_dtype: the element type of decode_windows_tensor_dev's output
 DT_U8, DT_F32, DT_F16, DT_BF16 = 0, 1, 2, 3
@@ -342,15 +348,17 @@ def window_fit(W, H, window, format=PIX_RGB24, row_stride=0, slot_stride=0):
     return placed.x, placed.y, placed.w, placed.h
 
 
-def resize_taps(in_size, out_size):
-    """(first, count, weights) of one axis of decode_windows_resized_dev's resampling: int32 arrays [out_size], [out_size] and
-    [out_size, ksize] (integer weights of 22 fraction bits, zero behind count); the definition is in include/jpezy_hip.h (jpezy_resize_taps)"""
+def resize_taps(in_size, out_size, filter=FILTER_BILINEAR):
+    """(first, count, weights) of one axis of decode_windows_resized_dev's resampling with the filter given (FILTER_*): int32 arrays
+    [out_size], [out_size] and [out_size, ksize] (integer weights of 22 fraction bits, zero behind count); the definition is in
+    include/jpezy_hip.h (jpezy_resize_taps_filter)"""
     lib = load_library()
     ksize = C.c_int()
-    _check(lib.jpezy_resize_taps(int(in_size), int(out_size), C.byref(ksize), None, None, None, 0))
+    _check(lib.jpezy_resize_taps_filter(int(filter), int(in_size), int(out_size), C.byref(ksize), None, None, None, 0))
     first, count = np.zeros(int(out_size), np.int32), np.zeros(int(out_size), np.int32)
     weights = np.zeros((int(out_size), ksize.value), np.int32)
-    _check(lib.jpezy_resize_taps(int(in_size), int(out_size), C.byref(ksize), _np_ptr(first), _np_ptr(count), _np_ptr(weights), weights.size))
+    _check(lib.jpezy_resize_taps_filter(int(filter), int(in_size), int(out_size), C.byref(ksize), _np_ptr(first), _np_ptr(count), _np_ptr(weights),
+                                        weights.size))
     return first, count, weights
 
 
@@ -778,14 +786,18 @@ class Context:
         return out
 
     def decode_windows_resized_dev(self, files, d_out, windows=None, mirror=None, format=PIX_RGB24, gray=False, raise_on_error=True,
-                                   upsampling=None):
+                                   upsampling=None, filter=None):
         """one crop window of each of the .jpg byte strings in `files`, every window of its own size, each resampled (triangle filter,
         antialiased where it shrinks; include/jpezy_hip.h, BATCH OF WINDOWS, RESIZED) to the out_h x out_w of d_out, a torch uint8 tensor
         [n, out_h, out_w, bytes] under decode_windows_dev's stride rules.  windows: as there (resize_pick_window gives the window and scale
         for a rectangle of the full-size picture); mirror: None or one flag per file, the file's output columns reversed.  Every file writes
         exactly d_out[k]; nothing else of d_out's storage is written.  Returns a list of (FrameInfo, (x, y, w, h), status), the rectangle
         being the source window as decoded; synchronous (jpezy_decode_windows_resized_dev).  upsampling: as decode_windows_dev's (the
-        source window's chroma; the resampling behind it is the same)."""
+        source window's chroma; the resampling behind it is the same).  filter: None (the context's setting, set_windows_filter) or one
+        of FILTER_* that holds for this call alone."""
+        if filter is not None:
+            with self._windows_filter(filter):
+                return self.decode_windows_resized_dev(files, d_out, windows, mirror, format, gray, raise_on_error, upsampling)
         if upsampling is not None:
             with self._windows_upsampling(upsampling):
                 return self.decode_windows_resized_dev(files, d_out, windows, mirror, format, gray, raise_on_error)
@@ -820,15 +832,18 @@ class Context:
         return out
 
     def decode_windows_tensor_dev(self, files, d_out, windows=None, mirror=None, scale=None, bias=None, format=PIX_RGB24, gray=False,
-                                  raise_on_error=True, upsampling=None):
+                                  raise_on_error=True, upsampling=None, filter=None):
         """decode_windows_resized_dev straight into the tensor a model takes (include/jpezy_hip.h, BATCH OF WINDOWS, TENSOR OUTPUT): d_out is a
         torch tensor of LOGICAL shape [n, C, out_h, out_w] on this context's device, C = 3 or 1 (1 needs gray), dtype uint8, float32, float16
         or bfloat16, with ANY strides -- torch.empty(n, 3, H, W), the same in channels_last and nhwc.permute(0, 3, 1, 2) all work; the dtype
         and the strides are read from the tensor.  Element (k, c, y, x) is byte c of the resized pixel (format: PIX_RGB24 or PIX_BGR24), for
         the float types byte * scale[c] + bias[c] in float32 (two roundings, never fused) converted to the dtype; scale and bias: None (1
         and 0; required for uint8) or C numbers each, tensor_normalization(mean, std) gives them for (byte / 255 - mean) / std.  Only d_out's
-        own elements are written.  windows, mirror, upsampling and the returned list: as decode_windows_resized_dev's; synchronous
+        own elements are written.  windows, mirror, upsampling, filter and the returned list: as decode_windows_resized_dev's; synchronous
         (jpezy_decode_windows_tensor_dev)."""
+        if filter is not None:
+            with self._windows_filter(filter):
+                return self.decode_windows_tensor_dev(files, d_out, windows, mirror, scale, bias, format, gray, raise_on_error, upsampling)
         if upsampling is not None:
             with self._windows_upsampling(upsampling):
                 return self.decode_windows_tensor_dev(files, d_out, windows, mirror, scale, bias, format, gray, raise_on_error)
@@ -895,6 +910,34 @@ class Context:
             yield
         finally:
             self.set_windows_upsampling(before)
+
+    def set_windows_filter(self, filter):
+        """resampling filter of decode_windows_resized_dev and decode_windows_tensor_dev: FILTER_BILINEAR (the default), FILTER_BOX,
+        FILTER_BICUBIC or FILTER_LANCZOS (jpezy_ctx_set_windows_filter); any other value raises and leaves the setting unchanged"""
+        _check(load_library().jpezy_ctx_set_windows_filter(self._h, int(filter)))
+
+    def windows_filter(self):
+        """the setting of set_windows_filter"""
+        return _check(load_library().jpezy_ctx_windows_filter(self._h))
+
+    @contextlib.contextmanager
+    def _windows_filter(self, filter):
+        """the setting for one call: set, and put back afterwards whatever the call did"""
+        before = self.windows_filter()
+        self.set_windows_filter(filter)
+        try:
+            yield
+        finally:
+            self.set_windows_filter(before)
+
+    def set_resample_direct(self, on):
+        """on: box, bicubic and Lanczos resample every file with the direct loop, never the two-pass tile (a test and measurement knob; the
+        bytes do not depend on it)"""
+        _check(load_library().jpezy_ctx_set_resample_direct(self._h, 1 if on else 0))
+
+    def last_resample_tiled_count(self):
+        """files of the last decode_windows_resized_dev / decode_windows_tensor_dev call that took the two-pass tile"""
+        return load_library().jpezy_ctx_last_resample_tiled_count(self._h)
 
     def set_huffdec_min_bytes(self, n):
         load_library().jpezy_ctx_set_huffdec_min_bytes(self._h, n)

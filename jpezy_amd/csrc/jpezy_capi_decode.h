@@ -194,6 +194,10 @@ struct ResampleJob {
     unsigned long long src_off, dst_off;
     int w, h, mirror;
 };
+// how a launch resamples: the filter (a value of enum jpezy_filter) and direct != 0: no file takes the two-pass tile
+struct ResampleHow {
+    int filter, direct;
+};
 
 }  // namespace jpezy_capi
 
@@ -210,10 +214,11 @@ JPEZY_INTERNAL int jpezy_internal_region_dev_core(jpezy_ctx* c, const DecodeSour
                                                   const jpezy_rect& rg, int upsampling = 0);
 // the second stage of the resized batch of windows: tap tables and descriptors of `jobs` through c->r_pin / c->r_tab, then resample_kernel
 // (jpezy_capi_resized.hip).  tensor: resample_tensor_kernel in its place -- d_dst is the tensor's first element, ResampleJob::dst_off counts
-// elements, dst_stride is not read and bytes is 3
+// elements, dst_stride is not read and bytes is 3.  how: the filter and the form, the CALL's (a child context is handed its parent's);
+// *tiled: the jobs that run the two-pass tile.  JPEZY_E_UNSUPPORTED: a table whose weights could overflow a 32-bit accumulator
 JPEZY_INTERNAL int jpezy_internal_resample(jpezy_ctx* c, const std::vector<ResampleJob>& jobs, const uint8_t* d_src, unsigned src_stride,
-                                           uint8_t* d_dst, size_t dst_stride, int out_w, int out_h, int bytes, hipStream_t s, hipEvent_t t0 = nullptr,
-                                           hipEvent_t t1 = nullptr, const TensorOut* tensor = nullptr);
+                                           uint8_t* d_dst, size_t dst_stride, int out_w, int out_h, int bytes, hipStream_t s, const ResampleHow& how,
+                                           int* tiled, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr, const TensorOut* tensor = nullptr);
 // header, output size, capacity, coefficients (read_coeffs), staging in c->in, the stage, download, synchronise (jpezy_capi_huffdec.hip).
 // No output pointer: header only.  c and info are not null.
 JPEZY_INTERNAL int jpezy_internal_decode_file(jpezy_ctx* c, const uint8_t* data, size_t len, jpezy_frame_info* info, const DecodeRequest& rq);

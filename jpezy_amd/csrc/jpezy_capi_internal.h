@@ -238,6 +238,9 @@ struct jpezy_ctx {
     DevBuf w_scr;                  // jpezy_decode_windows_resized_dev: a slice's (a child context: one file's) windows as decoded, packed pixels
     PinBuf r_pin;                  // ... pinned staging of a launch's resample descriptors and tap tables
     DevBuf r_tab;                  // ... and their device copy
+    int w_filter = 0;              // resampling filter of the resized and the tensor entry: JPEZY_FILTER_BILINEAR (jpezy_ctx_set_windows_filter)
+    int r_direct = 0;              // 1: the direct loop for every file, never the two-pass tile (jpezy_ctx_set_resample_direct)
+    int r_last_tiled = 0;          // files of the last resized / tensor call that took the two-pass tile (jpezy_ctx_last_resample_tiled_count)
     DevBuf e_hdr;                  // JFIF header bytes of the device-resident variant (cached per W, H, comment)
     jpezy_host::HostPipe pipe;     // staging ring of the streaming host-buffer entry points (jpezy_hostpipe.h)
     size_t host_chunk_bytes = 4u << 20;   // bytes of input per chunk of that pipeline (jpezy_ctx_set_host_chunk_bytes)

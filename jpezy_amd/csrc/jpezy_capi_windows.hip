@@ -21,6 +21,9 @@ struct Resize {
     const uint8_t* mirror_x;            // [n] or null
     const TensorOut* tensor;            // null: packed pixels.  Otherwise the slots are a tensor's: d_pix is its first element, slot_stride
                                         // its stride over files in ELEMENTS, row_stride is not read (jpezy_decode_windows_tensor_dev)
+    // filled in by windows_driver from the context the call was made on, so that a child context resamples as its parent would
+    ResampleHow how = {};               // the filter (jpezy_ctx_set_windows_filter) and the direct-loop knob
+    std::atomic<int>* tiled = nullptr;  // files that took the two-pass tile, counted over the call's launches
 };
 
 inline size_t up4(size_t v) { return (v + 3) & ~(size_t)3; }
@@ -258,16 +261,19 @@ int decode_slice(jpezy_ctx* c, const std::vector<int>& files, const std::vector<
             const jpezy_rect& r = all[(size_t)i].rect;
             jobs.push_back({ scr_off[k], (unsigned long long)i * out.slot_stride, r.w, r.h, out.rz->mirror_x && out.rz->mirror_x[i] ? 1 : 0 });
         }
+        int tiled = 0;
         if (int rc = jpezy_internal_resample(c, jobs, (const uint8_t*)c->w_scr.p, (unsigned)scr_stride, out.d_pix, out.row_stride, out.rz->out_w,
-                                             out.rz->out_h, out.bytes, s, dbg ? (hipEvent_t)ev0 : nullptr, dbg ? (hipEvent_t)ev1 : nullptr, out.rz->tensor))
+                                             out.rz->out_h, out.bytes, s, out.rz->how, &tiled, dbg ? (hipEvent_t)ev0 : nullptr,
+                                             dbg ? (hipEvent_t)ev1 : nullptr, out.rz->tensor))
             return rc;
+        out.rz->tiled->fetch_add(tiled);
         if (dbg) {
             float ms = 0;
             HIP_TRY(hipEventSynchronize(ev1));
             HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
-            std::fprintf(stderr, "  windows slice (%u files): tables up + %s<%d>, %zu files to %d x %d: %.3f ms (device events)\n", nf,
-                         out.rz->tensor ? "resample_tensor_kernel" : "resample_kernel", out.rz->tensor ? out.rz->tensor->dtype : out.bytes, jobs.size(),
-                         out.rz->out_w, out.rz->out_h, (double)ms);
+            std::fprintf(stderr, "  windows slice (%u files): tables up + %s<%d>, filter %d, %d of %zu files tiled, to %d x %d: %.3f ms (device events)\n", nf,
+                         out.rz->tensor ? "resample_tensor_kernel" : "resample_kernel", out.rz->tensor ? out.rz->tensor->dtype : out.bytes,
+                         out.rz->how.filter, tiled, jobs.size(), out.rz->out_w, out.rz->out_h, (double)ms);
         }
     }
     HIP_TRY(hipStreamSynchronize(s));                                 // (the pinned staging is the next slice's; the call is synchronous anyway)
@@ -311,6 +317,34 @@ int jpezy_ctx_windows_upsampling(jpezy_ctx* c)
     return c->w_upsampling;
 }
 
+int jpezy_ctx_set_windows_filter(jpezy_ctx* c, int filter)
+{
+    if (filter != JPEZY_FILTER_BILINEAR && filter != JPEZY_FILTER_BOX && filter != JPEZY_FILTER_BICUBIC && filter != JPEZY_FILTER_LANCZOS)
+        return set_err(JPEZY_E_BADARG, "windows_filter: filter must be one of JPEZY_FILTER_*");
+    if (!c) return set_err(JPEZY_E_BADARG, "null context");
+    c->w_filter = filter;
+    return JPEZY_OK;
+}
+
+int jpezy_ctx_windows_filter(jpezy_ctx* c)
+{
+    if (!c) return set_err(JPEZY_E_BADARG, "null context");
+    return c->w_filter;
+}
+
+int jpezy_ctx_set_resample_direct(jpezy_ctx* c, int on)
+{
+    if (!c) return set_err(JPEZY_E_BADARG, "null context");
+    c->r_direct = on ? 1 : 0;
+    return JPEZY_OK;
+}
+
+int jpezy_ctx_last_resample_tiled_count(jpezy_ctx* c)
+{
+    if (!c) return set_err(JPEZY_E_BADARG, "null context");
+    return c->r_last_tiled;
+}
+
 }  // extern "C"
 
 namespace {
@@ -321,10 +355,19 @@ namespace {
 // jpezy_decode_windows_tensor_dev).
 int windows_driver(jpezy_ctx* c, const char* who_c, int n, const uint8_t* const* data, const size_t* len, int gray, const jpezy_window* windows,
                    int format, int bytes, size_t row_stride, size_t slot_stride, uint8_t* d_pix, jpezy_frame_info* info, jpezy_rect* placed,
-                   int* status, const Resize* rz)
+                   int* status, const Resize* rz_call)
 {
     const std::string who = who_c;
     if (!c) return set_err(JPEZY_E_BADARG, "null context");
+    std::atomic<int> tiled{ 0 };
+    Resize rz_ctx;
+    if (rz_call) {
+        rz_ctx = *rz_call;
+        rz_ctx.how = { c->w_filter, c->r_direct };
+        rz_ctx.tiled = &tiled;
+        c->r_last_tiled = 0;
+    }
+    const Resize* const rz = rz_call ? &rz_ctx : nullptr;
     HIP_TRY(hipSetDevice(c->device));
     {
         hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
@@ -449,9 +492,11 @@ int windows_driver(jpezy_ctx* c, const char* who_c, int n, const uint8_t* const*
                 return rc;
             if (rz) {
                 const std::vector<ResampleJob> job = { { 0, (unsigned long long)i * slot_stride, cd.rect.w, cd.rect.h, rz->mirror_x && rz->mirror_x[i] ? 1 : 0 } };
+                int n_tiled = 0;                                         // the parent's filter, not the child's own setting
                 if (int rc = jpezy_internal_resample(w, job, (const uint8_t*)w->w_scr.p, (unsigned)scr_stride, d_pix, row_stride, rz->out_w, rz->out_h, bytes,
-                                                     w->stream, nullptr, nullptr, rz->tensor))
+                                                     w->stream, rz->how, &n_tiled, nullptr, nullptr, rz->tensor))
                     return rc;
+                tiled.fetch_add(n_tiled);
             }
             HIP_TRY(hipStreamSynchronize(w->stream));
             return JPEZY_OK;
@@ -467,6 +512,7 @@ int windows_driver(jpezy_ctx* c, const char* who_c, int n, const uint8_t* const*
         for (int k = 1; k < nw; ++k) pool.start(work, k);
         work(0);
     }
+    if (rz) c->r_last_tiled = tiled.load();
     for (int i = 0; i < n; ++i)
         if (status[i] < 0) return set_err(status[i], who + ": file " + std::to_string(i) + ": " + all[(size_t)i].msg);
     return JPEZY_OK;
@@ -517,7 +563,7 @@ try {
                                             " bytes does not fit a slot of " + std::to_string(slot_stride) + " bytes with rows " +
                                             std::to_string(row_stride) + " apart");
     if (slot_stride > pix_cap / (size_t)n) return set_err(JPEZY_E_NOSPACE, who + ": n * slot_stride exceeds pix_cap");
-    const Resize rz = { out_w, out_h, mirror_x, nullptr };
+    const Resize rz = { out_w, out_h, mirror_x, nullptr, {}, nullptr };
     return windows_driver(c, kWhoResized, n, data, len, gray, windows, format, bytes, row_stride, slot_stride, d_pix, info, placed, status, &rz);
 }
 JPEZY_CATCH
@@ -568,7 +614,7 @@ try {
     if ((uintptr_t)d_out % elem) return set_err(JPEZY_E_BADARG, who + ": d_out must be aligned to the element size");
     t.sc = (unsigned long long)sc; t.sh = (unsigned long long)sh; t.sw = (unsigned long long)sw;
     t.dtype = dtype; t.channels = channels;
-    const Resize rz = { out_w, out_h, mirror_x, &t };
+    const Resize rz = { out_w, out_h, mirror_x, &t, {}, nullptr };
     return windows_driver(c, kWhoTensor, n, data, len, gray, windows, format, bytes, 0, (size_t)sn, (uint8_t*)d_out, info, placed, status, &rz);
 }
 JPEZY_CATCH

@@ -308,6 +308,9 @@ hipError_t launch_dequant_idct_windows_smooth(const WindowsParams& p, unsigned l
 // of different sizes, each resampled to the launch's out_w x out_h.  One descriptor per file; a workgroup is one tile of kResampleTileW x
 // kResampleTileH output pixels of one file and finds its file as windows_kernel's do.
 constexpr int kResampleTileW = 64, kResampleTileH = 16;
+// source rows the two-pass form of the stage holds in LDS (jpezy_resample_core.h): a tile's rows span less than
+// (kResampleTileH - 1) * r + 2 * fsup * r + 1 source rows at a vertical ratio r >= 1, 42 at most for Lanczos (fsup 3) below r = 2
+constexpr int kResampleTileRows = 44;
 struct ResampleDesc {
     unsigned long long src_off;     // byte offset of the source window's pixel (0, 0) behind ResampleParams::src (a multiple of 4)
     unsigned long long dst_off;     // byte offset of the file's output pixel (0, 0) behind ResampleParams::dst
@@ -317,7 +320,9 @@ struct ResampleDesc {
     int kx, ky;                     // weights per output column / row in the tables (ksize)
     int mirror;                     // output column i is column out_w - 1 - i of the unmirrored result
     unsigned wg0;                   // index of the file's first workgroup, ascending over the table
-    unsigned pad[2];
+    unsigned tiled;                 // 1: every tile of the file spans at most kResampleTileRows source rows and runs the two-pass form
+                                    // (read by the launches of launch_resample / launch_resample_tensor with tile == true only)
+    unsigned pad;
 };
 static_assert(sizeof(ResampleDesc) == 64, "one descriptor per 64-byte line");
 struct ResampleParams {
@@ -330,7 +335,9 @@ struct ResampleParams {
     int out_w, out_h;
     int pix_bytes;                  // 3 or 4; byte 3 of a 32-bit pixel is written as 0xFF and not read
 };
-hipError_t launch_resample(const ResampleParams& p, unsigned long long total_wg, hipStream_t stream);
+// tile: the kernel instance that holds the two-pass form and takes it for the files with ResampleDesc::tiled; false: the direct loop for
+// every file, whatever the descriptors say
+hipError_t launch_resample(const ResampleParams& p, unsigned long long total_wg, hipStream_t stream, bool tile = false);
 
 // the same stage with a tensor behind it (jpezy_kernels_resized_tensor.hip; include/jpezy_hip.h, BATCH OF WINDOWS, TENSOR OUTPUT): the three
 // bytes of an output pixel become `channels` elements of `dtype`, (float)byte * scale[c] + bias[c] for the float types, element (c, y, x) of
@@ -342,7 +349,7 @@ struct TensorOut {
     unsigned long long sc, sh, sw;  // strides in elements
     int dtype, channels;            // channels: 3, or 1 (channel 0 alone)
 };
-hipError_t launch_resample_tensor(const ResampleParams& p, const TensorOut& t, unsigned long long total_wg, hipStream_t stream);
+hipError_t launch_resample_tensor(const ResampleParams& p, const TensorOut& t, unsigned long long total_wg, hipStream_t stream, bool tile = false);
 
 // lossless transforms in the coefficient domain (jpezy_kernels_transform.hip; include/jpezy_hip.h, LOSSLESS TRANSFORMS): every output
 // block is one source block, permuted (swap) and with some coefficients negated (mirror) -- pure data movement

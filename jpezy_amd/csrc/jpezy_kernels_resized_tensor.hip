@@ -13,8 +13,9 @@
 //                                       16-byte stores for F32) when all four pixels exist and the address is a multiple of 4, single
 //                                       elements otherwise
 //         any other strides             single elements
-// Only the elements named are written: no padding, and never the other half of a word that holds a neighbouring 2-byte element.  No LDS,
-// no scratch.
+// Only the elements named are written: no padding, and never the other half of a word that holds a neighbouring 2-byte element.  No
+// scratch.  resample_tensor_kernel<DT, C, true> is resample_kernel<3, true>'s counterpart: the two-pass form through static LDS for the files
+// whose descriptor says so (the filters wider than the triangle), the same store stage behind it; <DT, C, false> has no LDS.
 #include "jpezy_resample_core.h"
 
 namespace jpezy_dev {
@@ -60,14 +61,19 @@ typedef unsigned v4u __attribute__((ext_vector_type(4)));
 typedef v3u v3u_a4 __attribute__((aligned(4)));
 typedef v4u v4u_a4 __attribute__((aligned(4)));
 
-template <int DT, int C>
+template <int DT, int C, bool TILE>
 __global__ __launch_bounds__(kThreads) void resample_tensor_kernel(ResampleParams p, TensorOut t, int form)
 {
     constexpr int EB = ElemBytes<DT>::value;
     const ResampleDesc d = workgroup_file(p);
     int ox0, oy, npx;
     uint32_t w[3];                                // byte j of w[c]: channel c of pixel j
-    if (!resample_four<3>(p, d, ox0, oy, npx, w[0], w[1], w[2])) return;
+    if constexpr (TILE) {                         // resample_kernel<3, true>'s choice per file (jpezy_kernels_resized.hip)
+        __shared__ uint32_t tile[kTileWords];
+        if (!(d.tiled ? resample_four_tiled<3>(p, d, tile, ox0, oy, npx, w[0], w[1], w[2]) : resample_four<3>(p, d, ox0, oy, npx, w[0], w[1], w[2]))) return;
+    } else {
+        if (!resample_four<3>(p, d, ox0, oy, npx, w[0], w[1], w[2])) return;
+    }
 
     unsigned e[C][4];                             // the elements' bit patterns (those of pixels that do not exist are never stored)
 #pragma unroll
@@ -118,16 +124,18 @@ __global__ __launch_bounds__(kThreads) void resample_tensor_kernel(ResampleParam
 }
 
 template <int DT>
-static void launch_dt(const ResampleParams& q, const TensorOut& t, int form, unsigned n_wg, hipStream_t s)
+static void launch_dt(const ResampleParams& q, const TensorOut& t, int form, unsigned n_wg, hipStream_t s, bool tile)
 {
-    if (t.channels == 3) hipLaunchKernelGGL((resample_tensor_kernel<DT, 3>), dim3(n_wg), dim3(kThreads), 0, s, q, t, form);
-    else hipLaunchKernelGGL((resample_tensor_kernel<DT, 1>), dim3(n_wg), dim3(kThreads), 0, s, q, t, form);
+    if (t.channels == 3 && tile) hipLaunchKernelGGL((resample_tensor_kernel<DT, 3, true>), dim3(n_wg), dim3(kThreads), 0, s, q, t, form);
+    else if (t.channels == 3) hipLaunchKernelGGL((resample_tensor_kernel<DT, 3, false>), dim3(n_wg), dim3(kThreads), 0, s, q, t, form);
+    else if (tile) hipLaunchKernelGGL((resample_tensor_kernel<DT, 1, true>), dim3(n_wg), dim3(kThreads), 0, s, q, t, form);
+    else hipLaunchKernelGGL((resample_tensor_kernel<DT, 1, false>), dim3(n_wg), dim3(kThreads), 0, s, q, t, form);
 }
 
 }  // namespace resized
 
 // launch_resample's splitting rule; the store form is decided here, once per call
-hipError_t launch_resample_tensor(const ResampleParams& p, const TensorOut& t, unsigned long long total_wg, hipStream_t s)
+hipError_t launch_resample_tensor(const ResampleParams& p, const TensorOut& t, unsigned long long total_wg, hipStream_t s, bool tile)
 {
     if (p.pix_bytes != 3 || p.n_desc < 1 || total_wg < 1 || total_wg > 0xFFFFFFFFull) return hipErrorInvalidValue;
     if (p.out_w < 1 || p.out_h < 1 || p.out_w > 65535 || p.out_h > 65535 || (p.src_stride & 3u)) return hipErrorInvalidValue;
@@ -139,10 +147,10 @@ hipError_t launch_resample_tensor(const ResampleParams& p, const TensorOut& t, u
         q.wg_base = (unsigned)w0;
         const unsigned n_wg = (unsigned)(total_wg - w0 < per ? total_wg - w0 : per);
         switch (t.dtype) {
-        case kTensorU8: resized::launch_dt<kTensorU8>(q, t, form, n_wg, s); break;
-        case kTensorF32: resized::launch_dt<kTensorF32>(q, t, form, n_wg, s); break;
-        case kTensorF16: resized::launch_dt<kTensorF16>(q, t, form, n_wg, s); break;
-        default: resized::launch_dt<kTensorBF16>(q, t, form, n_wg, s); break;
+        case kTensorU8: resized::launch_dt<kTensorU8>(q, t, form, n_wg, s, tile); break;
+        case kTensorF32: resized::launch_dt<kTensorF32>(q, t, form, n_wg, s, tile); break;
+        case kTensorF16: resized::launch_dt<kTensorF16>(q, t, form, n_wg, s, tile); break;
+        default: resized::launch_dt<kTensorBF16>(q, t, form, n_wg, s, tile); break;
         }
         if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
     }

@@ -13,6 +13,11 @@ around work that ends in a device synchronise; median, minimum and spread (max -
               C  jpezy_decode_windows_dev alone on the same windows: A - C is what the second stage adds
   Also        the JPEZY_BATCH_DEBUG laps of one call of A per workload on stderr, and the largest difference between A's and B's bytes (the two
               use different arithmetic: the figure is information, not a check)
+  --filter    the resampling filter of arm A (bilinear, box, bicubic, lanczos; B keeps torch's bilinear, so A against B is then information
+              only).  With a filter other than bilinear a fourth arm D runs A with the direct loop forced (jpezy_ctx_set_resample_direct),
+              alternated with the others, and --stage-rounds rounds measure the RESAMPLING STAGE of A and D alone by the device events the
+              library records around it (the "tables up + resample" lap of JPEZY_BATCH_DEBUG, read back from stderr), alternated too
+  --direct    arm A itself runs the direct loop (and there is no arm D)
 
 Bare ctypes, buffers preallocated and touched.  Prints one line per arm and a JSON line with every figure (times in milliseconds)."""
 import argparse
@@ -20,7 +25,9 @@ import ctypes as C
 import json
 import math
 import os
+import re
 import sys
+import tempfile
 import time
 from pathlib import Path
 
@@ -61,6 +68,29 @@ class Workload:
         self.mirror = (C.c_uint8 * self.n)(*[int(rng.integers(0, 2)) for _ in range(self.n)])
         self.infos, self.placed, self.status = (api.FrameInfo * self.n)(), (api.Rect * self.n)(), (C.c_int * self.n)()
         self.Ws, self.Hs = max(r[2] for r, _ in self.wins), max(r[3] for r, _ in self.wins)
+
+
+FILTERS = {"bilinear": J.FILTER_BILINEAR, "box": J.FILTER_BOX, "bicubic": J.FILTER_BICUBIC, "lanczos": J.FILTER_LANCZOS}
+
+
+def stage_ms(fn):
+    """one call of fn with JPEZY_BATCH_DEBUG set and stderr in a file: the sum of the call's resampling-stage laps (device events)"""
+    sys.stderr.flush()
+    saved = os.dup(2)
+    with tempfile.TemporaryFile(mode="w+b") as f:
+        os.dup2(f.fileno(), 2)
+        os.environ["JPEZY_BATCH_DEBUG"] = "1"
+        try:
+            fn()
+        finally:
+            del os.environ["JPEZY_BATCH_DEBUG"]
+            os.dup2(saved, 2)
+            os.close(saved)
+        f.seek(0)
+        text = f.read().decode(errors="replace")
+    laps = [float(m) for m in re.findall(r"tables up \+ resample.*?: ([0-9.]+) ms \(device events\)", text)]
+    assert laps, text[-400:]
+    return sum(laps)
 
 
 def make_arms(lib, ctx, wl, dev):
@@ -116,8 +146,13 @@ def main():
     ap.add_argument("--rounds", type=int, default=20)
     ap.add_argument("--rounds-one-size", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--filter", choices=sorted(FILTERS), default="bilinear")
+    ap.add_argument("--direct", action="store_true", help="arm A runs the direct loop, never the two-pass tile")
+    ap.add_argument("--stage-rounds", type=int, default=15, help="rounds of the stage-only A / D measurement (a filter other than bilinear)")
     a = ap.parse_args()
     ctx = J.Context(0)
+    ctx.set_windows_filter(FILTERS[a.filter])
+    ctx.set_resample_direct(a.direct)
     lib = api.load_library()
     dev = torch.device("cuda", 0)
     n = a.files
@@ -128,16 +163,25 @@ def main():
     crop_rng = np.random.default_rng(18)
     workloads = [(Workload("mixed sizes", files, sizes, crop_rng), a.rounds),
                  (Workload("one size (1920 x 1080)", [big[k % a.distinct] for k in range(n)], [(1920, 1080)] * n, crop_rng), a.rounds_one_size)]
-    result = {"files": n, "out": OUT, "workloads": {}}
+    result = {"files": n, "out": OUT, "filter": a.filter, "direct": bool(a.direct), "workloads": {}}
     for wl, rounds in workloads:
         arms, d_a, d_b = make_arms(lib, ctx, wl, dev)
+        name_a = "A decode_windows_resized_dev"
+        if a.filter != "bilinear" and not a.direct:
+            def arm_d(arm_a=arms[name_a]):
+                ctx.set_resample_direct(1)
+                try:
+                    arm_a()
+                finally:
+                    ctx.set_resample_direct(0)
+            arms["D A with the direct loop forced"] = arm_d
         t = timed_rounds(arms, rounds, a.warmup)
         scales = {s: sum(1 for _, q in wl.wins if q == s) for s in (1, 2, 4, 8)}
         res = {"windows_per_scale": scales, "largest_window": [wl.Ws, wl.Hs], "arms": {}}
         for k, v in t.items():
             res["arms"][k] = {"median_ms": float(np.median(v)), "min_ms": float(np.min(v)), "max_ms": float(np.max(v)), "rounds": len(v)}
             print(f"{wl.name} ({wl.n} files), {k}: median {np.median(v):.2f} ms, min {np.min(v):.2f} ms, spread {np.max(v) - np.min(v):.2f} ms")
-        ra, rb, rc = (res["arms"][k] for k in arms)
+        ra, rb, rc = (res["arms"][k] for k in list(arms)[:3])
         margin = rb["median_ms"] - ra["median_ms"]
         spread = max(ra["max_ms"] - ra["min_ms"], rb["max_ms"] - rb["min_ms"])
         res["a_below_b_by_more_than_both_spreads"] = bool(margin > spread)
@@ -152,7 +196,22 @@ def main():
         arms["A decode_windows_resized_dev"]()
         del os.environ["JPEZY_BATCH_DEBUG"]
         res["grouped_files"] = int(lib.jpezy_ctx_last_batch_fast_count(ctx._h))
-        print(f"{wl.name}: {res['grouped_files']} of {wl.n} files took A's grouped path")
+        res["tiled_files"] = int(lib.jpezy_ctx_last_resample_tiled_count(ctx._h))
+        print(f"{wl.name}: {res['grouped_files']} of {wl.n} files took A's grouped path, {res['tiled_files']} the two-pass tile")
+        if "D A with the direct loop forced" in arms:
+            stage = {"tile": [], "direct": []}
+            for _ in range(a.stage_rounds):
+                stage["tile"].append(stage_ms(arms[name_a]))
+                stage["direct"].append(stage_ms(arms["D A with the direct loop forced"]))
+            res["stage_ms"] = {k: {"median_ms": float(np.median(v)), "min_ms": float(np.min(v)), "max_ms": float(np.max(v)), "rounds": len(v)}
+                               for k, v in stage.items()}
+            st, sd = res["stage_ms"]["tile"], res["stage_ms"]["direct"]
+            margin = sd["median_ms"] - st["median_ms"]
+            spread = max(st["max_ms"] - st["min_ms"], sd["max_ms"] - sd["min_ms"])
+            res["tile_below_direct_by_more_than_both_spreads"] = bool(margin > spread)
+            print(f"{wl.name}, resampling stage by device events ({a.filter}): tile median {st['median_ms']:.3f} ms ({st['min_ms']:.3f}..{st['max_ms']:.3f}), "
+                  f"direct median {sd['median_ms']:.3f} ms ({sd['min_ms']:.3f}..{sd['max_ms']:.3f}); the tile is {margin:.3f} ms below "
+                  f"(the larger spread: {spread:.3f} ms): {'holds' if margin > spread else 'DOES NOT HOLD'}")
         result["workloads"][wl.name] = res
     print(json.dumps(result))
 

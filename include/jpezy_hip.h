@@ -1269,6 +1269,17 @@ int jpezy_decode_jpeg_upsampling_packed(jpezy_ctx* ctx, const uint8_t* data, siz
 int jpezy_ctx_set_windows_upsampling(jpezy_ctx* ctx, int upsampling);
 int jpezy_ctx_windows_upsampling(jpezy_ctx* ctx);
 
+/*
+ * ORIENTED OUTPUT.  The EXIF Orientation tag, applied in the store stage of the window decode: the picture the existing decode returns --
+ * at any scale, nearest or smooth -- mirrored, rotated or transposed by one of the tag's eight values, and windows taken from THAT picture.
+ * Orientation 4 is the vertical mirror the sections above list as not provided; the other seven come from the same mechanism.  The tag's
+ * parser, the geometry helpers, the region and file entries with an orientation argument and the context setting of the window batches
+ * are declared, and the rule is spelled out, in a header of their own, part of this one -- for the reason given above
+ * jpezy_hip_region_upsampling.h: the decode entries declared in THIS file are a closed, recorded set.  Nothing declared here changes:
+ * without the new entries and with the setting at its default every launch is the one made before.
+ */
+#include "jpezy_hip_orientation.h"
+
 #ifdef __cplusplus
 }
 #endif

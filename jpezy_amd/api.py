@@ -212,6 +212,25 @@ ABI_REGION_UPSAMPLING = [
                                                              C.c_size_t, _vp, C.c_size_t]),
 ]
 
+# include/jpezy_hip_orientation.h (part of jpezy_hip.h): the EXIF orientation tag, the geometry of the eight orientations, the region and
+# file entries with an orientation argument, the orientation setting of the window batches.  Kept out of ABI for the same reason
+ABI_ORIENTATION = [
+    ("jpezy_jpeg_orientation", C.c_int, [_vp, C.c_size_t]),
+    ("jpezy_orient_size", C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    ("jpezy_orient_rect", C.c_int, [C.c_int, C.c_int, C.c_int, _vp, _vp]),
+    ("jpezy_dequant_idct_region_oriented_dev", C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                         _vp, C.c_int, C.c_int, C.c_size_t, _vp, _vp, _vp, _vp]),
+    ("jpezy_dequant_idct_region_oriented_packed_dev", C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                                C.c_int, _vp, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_int, _vp, _vp]),
+    ("jpezy_decode_jpeg_oriented", C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.POINTER(C.c_int), C.POINTER(FrameInfo),
+                                             _vp, _vp, _vp, C.c_size_t]),
+    ("jpezy_decode_jpeg_oriented_packed", C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.POINTER(C.c_int),
+                                                    C.POINTER(FrameInfo), C.c_int, C.c_size_t, _vp, C.c_size_t]),
+    ("jpezy_ctx_set_windows_orientation", C.c_int, [_vp, C.c_int]),
+    ("jpezy_ctx_windows_orientation", C.c_int, [_vp]),
+]
+ORIENT_FROM_FILE = 0        # JPEZY_ORIENT_FROM_FILE: the orientation argument of decode_jpeg_oriented[_packed] -- the file's own tag
+
 # chroma sampling of the encoder's *_sampling entry points: 4:2:0 (the reference's 2x2 / 1x1 / 1x1, everything as without the keyword)
 # or 4:4:4 (8 x 8 MCUs of Y, Cb, Cr, no decimation; include/jpezy_hip.h has the definition)
 SAMPLING_420, SAMPLING_444 = 0, 1
@@ -258,7 +277,7 @@ def load_library():
         except Exception:
             pass
         lib = C.CDLL(str(_LIBPATH))
-        for name, res, args in ABI + ABI_REGION_UPSAMPLING:
+        for name, res, args in ABI + ABI_REGION_UPSAMPLING + ABI_ORIENTATION:
             fn = getattr(lib, name)          # AttributeError if the library does not export the symbol
             fn.restype = res
             fn.argtypes = args
@@ -329,6 +348,26 @@ def _rect(region):
 def region_check(W, H, scale, region):
     """raises JpezyError unless region = (x, y, w, h) lies inside a W x H file decoded at 1/scale, i.e. inside scaled_size(W, H, scale)"""
     _check(load_library().jpezy_region_check(int(W), int(H), int(scale), C.byref(_rect(region))))
+
+
+def jpeg_orientation(data):
+    """the EXIF Orientation tag (1..8) of .jpg bytes; 1 when the file has none or anything about it is wrong (jpezy_jpeg_orientation)"""
+    arr = np.frombuffer(bytes(data), dtype=np.uint8)
+    return load_library().jpezy_jpeg_orientation(_np_ptr(arr) if arr.size else None, arr.size)
+
+
+def orient_size(orientation, W, H):
+    """(Wo, Ho) of a W x H picture shown in the orientation (1..8): swapped for 5..8 (jpezy_orient_size)"""
+    wo, ho = C.c_int(), C.c_int()
+    _check(load_library().jpezy_orient_size(int(orientation), int(W), int(H), C.byref(wo), C.byref(ho)))
+    return wo.value, ho.value
+
+
+def orient_rect(orientation, W, H, region):
+    """the rectangle (x, y, w, h) of a W x H picture that the window region = (x, y, w, h) of its oriented form shows (jpezy_orient_rect)"""
+    src = Rect()
+    _check(load_library().jpezy_orient_rect(int(orientation), int(W), int(H), C.byref(_rect(region)), C.byref(src)))
+    return src.x, src.y, src.w, src.h
 
 
 def _window(win):
@@ -1251,12 +1290,60 @@ class Context:
                                                               C.byref(info), int(format), 0, _np_ptr(img), img.size))
         return info, img
 
+    # ---- oriented output (include/jpezy_hip_orientation.h): the picture mirrored / rotated / transposed as an EXIF orientation says ----
+    def decode_jpeg_oriented(self, data, orientation=ORIENT_FROM_FILE, region=None, scale=1, gray=False, upsampling=UPSAMPLE_NEAREST):
+        """.jpg bytes -> (FrameInfo, r, g, b, (w, h), orientation_used): the window region = (x, y, w, h) of the ORIENTED picture at 1/scale
+        (None: all of it) as planes of w*h bytes.  orientation: 1..8, or ORIENT_FROM_FILE for the file's own EXIF tag.  The FrameInfo
+        keeps the file's own width and height (jpezy_decode_jpeg_oriented)."""
+        lib = load_library()
+        arr = np.frombuffer(bytes(data), dtype=np.uint8)
+        info, used = FrameInfo(), C.c_int(0)
+        rect = None if region is None else _rect(region)
+        head = (self._h, _np_ptr(arr), arr.size, int(gray), int(upsampling), int(scale), None if rect is None else C.byref(rect), int(orientation),
+                C.byref(used), C.byref(info))
+        if rect is None:
+            _check(lib.jpezy_decode_jpeg_oriented(*head, None, None, None, 0))
+            w, h = orient_size(used.value, *scaled_size(info.width, info.height, scale))
+        else:
+            w, h = max(rect.w, 0), max(rect.h, 0)
+        r, g, b = (np.empty(max(w * h, 1), dtype=np.uint8) for _ in range(3))
+        _check(lib.jpezy_decode_jpeg_oriented(*head, _np_ptr(r), _np_ptr(g), _np_ptr(b), w * h))
+        return info, r[:w * h], g[:w * h], b[:w * h], (w, h), used.value
+
+    def decode_jpeg_oriented_packed(self, data, orientation=ORIENT_FROM_FILE, region=None, scale=1, format=PIX_RGB24, gray=False,
+                                    upsampling=UPSAMPLE_NEAREST):
+        """.jpg bytes -> (FrameInfo, uint8 array (h, w, C), orientation_used): the same window as interleaved pixels"""
+        lib = load_library()
+        nb = pixel_bytes(format)
+        arr = np.frombuffer(bytes(data), dtype=np.uint8)
+        info, used = FrameInfo(), C.c_int(0)
+        rect = None if region is None else _rect(region)
+        head = (self._h, _np_ptr(arr), arr.size, int(gray), int(upsampling), int(scale), None if rect is None else C.byref(rect), int(orientation),
+                C.byref(used), C.byref(info), int(format), 0)
+        if rect is None:
+            _check(lib.jpezy_decode_jpeg_oriented_packed(*head, None, 0))
+            w, h = orient_size(used.value, *scaled_size(info.width, info.height, scale))
+        else:
+            w, h = max(rect.w, 1), max(rect.h, 1)
+        img = np.empty((h, w, nb), dtype=np.uint8)
+        _check(lib.jpezy_decode_jpeg_oriented_packed(*head, _np_ptr(img), img.size))
+        return info, img, used.value
+
+    def set_windows_orientation(self, mode):
+        """0 (default): the window batches ignore the EXIF orientation; 1: every file's own tag is honoured -- windows are then in the
+        coordinates of the oriented picture (jpezy_ctx_set_windows_orientation)"""
+        _check(load_library().jpezy_ctx_set_windows_orientation(self._h, int(mode)))
+
+    def windows_orientation(self):
+        return _check(load_library().jpezy_ctx_windows_orientation(self._h))
+
     def dequant_idct_region_dev(self, d_coeffs, info, region, scale=1, d_r=None, d_g=None, d_b=None, gray=False, stream=None, n_frames=1,
-                                plane_stride=None, d_img=None, format=PIX_RGB24, upsampling=UPSAMPLE_NEAREST):
+                                plane_stride=None, d_img=None, format=PIX_RGB24, upsampling=UPSAMPLE_NEAREST, orientation=None):
         """the window region = (x, y, w, h) of the picture at 1/scale on device memory (torch tensors): the WHOLE frames' coefficients as
         read_jpeg_gpu leaves them -> planes of w*h bytes (n_frames frames plane_stride apart, default w*h), or, with d_img, packed pixels
         written into a uint8 tensor (h, w, C) or (N, h, w, C) whose strides give the row and frame strides.  upsampling: as
-        decode_jpeg_region's (jpezy_dequant_idct_region_upsampling[_packed]_dev)."""
+        decode_jpeg_region's (jpezy_dequant_idct_region_upsampling[_packed]_dev).  orientation 1..8: region is a window of the ORIENTED
+        picture (jpezy_dequant_idct_region_oriented[_packed]_dev); None: the entries without the argument."""
         import torch
         if stream is None:
             stream = torch.cuda.current_stream(d_coeffs.device).cuda_stream
@@ -1266,9 +1353,17 @@ class Context:
             n, H, W, row, frame = self._packed_layout(d_img, pixel_bytes(format), "dequant_idct_region_dev")
             if (W, H) != (rect.w, rect.h):
                 raise JpezyError(f"dequant_idct_region_dev: d_img is {W} x {H}, the region is {rect.w} x {rect.h}")
+            if orientation is not None:
+                _check(load_library().jpezy_dequant_idct_region_oriented_packed_dev(*head, int(orientation), int(format), row, frame, n, d_img.data_ptr(),
+                                                                                    stream))
+                return
             _check(load_library().jpezy_dequant_idct_region_upsampling_packed_dev(*head, int(format), row, frame, n, d_img.data_ptr(), stream))
             return
         stride = plane_stride if plane_stride is not None else rect.w * rect.h
+        if orientation is not None:
+            _check(load_library().jpezy_dequant_idct_region_oriented_dev(*head, int(orientation), n_frames, stride, d_r.data_ptr(), d_g.data_ptr(),
+                                                                         d_b.data_ptr(), stream))
+            return
         _check(load_library().jpezy_dequant_idct_region_upsampling_dev(*head, n_frames, stride, d_r.data_ptr(), d_g.data_ptr(), d_b.data_ptr(), stream))
 
     # ---- lossless transforms in the coefficient domain (include/jpezy_hip.h, LOSSLESS TRANSFORMS) ----
@@ -1548,12 +1643,15 @@ class Decoder:
         self.filename = filename
         self.ctx = ctx
         self.pr = None
+        self.orientation, self.size = 1, None     # decode(orient=True): the orientation applied and the planes' (width, height)
 
-    def decode(self, gray=False, scale=1, region=None, upsampling=UPSAMPLE_NEAREST):
+    def decode(self, gray=False, scale=1, region=None, upsampling=UPSAMPLE_NEAREST, orient=False):
         """scale 2, 4 or 8: planes of scaled_size(width, height, scale) (Context.decode_jpeg_scaled); region = (x, y, w, h): planes of
         w*h bytes, that window of the picture at 1/scale (Context.decode_jpeg_region); self.pr keeps the file's size.
         upsampling=UPSAMPLE_SMOOTH: 2:1 chroma through the triangle filter (Context.decode_jpeg_upsampling), full size and whole
-        pictures only: together with scale != 1 or a region it raises JpezyError with status JPEZY_E_UNSUPPORTED."""
+        pictures only: together with scale != 1 or a region it raises JpezyError with status JPEZY_E_UNSUPPORTED.
+        orient=True: the file's EXIF orientation is applied (Context.decode_jpeg_oriented) -- the planes are those of the oriented picture,
+        region is a window of it, self.orientation says what was applied and self.size the planes' (width, height)."""
         if upsampling != UPSAMPLE_NEAREST and (scale != 1 or region is not None):
             raise JpezyError(f"jpezy status {E_UNSUPPORTED}: Decoder.decode: smooth upsampling is not provided with reduced-size or region decode")
         try:
@@ -1561,7 +1659,10 @@ class Decoder:
                 data = f.read()
             ctx = self.ctx or default_context()
             # Huffman head, IDCT and colour conversion on the GPU
-            if region is not None:
+            if orient:
+                info, r, g, b, self.size, self.orientation = ctx.decode_jpeg_oriented(data, ORIENT_FROM_FILE, region=region, scale=scale, gray=gray,
+                                                                                      upsampling=upsampling)
+            elif region is not None:
                 info, r, g, b = ctx.decode_jpeg_region(data, region, scale=scale, gray=gray)
             else:
                 info, r, g, b = ctx.decode_jpeg(data, gray=gray, upsampling=upsampling) if scale == 1 else ctx.decode_jpeg_scaled(data, scale, gray=gray)

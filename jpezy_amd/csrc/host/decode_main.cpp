@@ -1,4 +1,4 @@
-// jpezy_decode <input.(jpg | jpeg)> ( <output.ppm | [OPT: --gray]> | -v ) [--scale=N] [--region=WxH+X+Y] [--upsampling=smooth|nearest]
+// jpezy_decode <input.(jpg | jpeg)> ( <output.ppm | [OPT: --gray]> | -v ) [--scale=N] [--region=WxH+X+Y] [--orient] [--upsampling=smooth|nearest]
 // Same argv rules, transcript and exit codes as the reference's src/decoder/main.cpp.  --scale=N (N = 1, 2, 4, 8; this project's own
 // option, looked for in argv[3] .. argv[5] the way --gray is) writes the picture at 1/N; any other N is the usage error.
 // --region=WxH+X+Y (this project's own option, X11 geometry order, looked for in the same places) writes the W x H window whose top-left
@@ -7,6 +7,9 @@
 // --upsampling=smooth (this project's own option, looked for in the same places) brings 2:1 chroma to picture size with the triangle
 // filter (jpezy_decode_jpeg_upsampling; include/jpezy_hip.h, CHROMA UPSAMPLING); --upsampling=nearest is the default, replication.  Any
 // other value is the usage error; smooth together with --scale= other than 1 or with --region= prints one rule line and writes no file.
+// --orient (this project's own option, looked for in the same places) applies the file's EXIF orientation (jpezy_decode_jpeg_oriented;
+// include/jpezy_hip_orientation.h): the picture is written upright, --scale= and --region= then speak of the oriented picture, and
+// --upsampling=smooth composes with it as far as it composes with those.  Any other word that begins with --orient is the usage error.
 // jpezy_decode --i420 <input.(jpg | jpeg)> <output.yuv>   (this project's own option) writes the file's own samples, without upsampling
 // or colour conversion, as raw planes: Y, then Cb, then Cr (full range: ffmpeg's yuvj420p) through jpezy_decode_jpeg_ycc.  Only a
 // 4:2:0 file (sampling 2x2, 1x1, 1x1) is such a picture: any other layout is refused with a message.
@@ -26,7 +29,7 @@ namespace {
 int disp_error()
 {
     std::cerr << "Usage: jpezy_decode <input.(jpg | jpeg)> ( <output.ppm | [OPT: --gray]> | -v ) [OPT: --scale=(1 | 2 | 4 | 8)] [OPT: --region=WxH+X+Y]"
-                 " [OPT: --upsampling=(smooth | nearest)]"
+                 " [OPT: --orient] [OPT: --upsampling=(smooth | nearest)]"
               << std::endl;
     return EXIT_FAILURE;
 }
@@ -37,9 +40,9 @@ bool has_ext(std::string_view s, std::string_view ext)
 }
 
 template <class CL, class T>
-int output(jpezy::decoder<T>& dec, const char* out, int scale, const jpezy_rect* region, int upsampling)
+int output(jpezy::decoder<T>& dec, const char* out, int scale, const jpezy_rect* region, int upsampling, bool orient)
 {
-    auto raw_op = region ? dec.template decode<CL>(scale, *region) : dec.template decode<CL>(scale, upsampling);
+    auto raw_op = region ? dec.template decode<CL>(scale, *region, orient) : dec.template decode<CL>(scale, upsampling, orient);
     if (!raw_op) {
         std::cerr << "decode failed" << std::endl;
         return EXIT_FAILURE;
@@ -55,11 +58,12 @@ int output(jpezy::decoder<T>& dec, const char* out, int scale, const jpezy_rect*
 }
 
 template <class T>
-int run(const char* in, const char* out, bool gray, int scale, const jpezy_rect* region, int upsampling)
+int run(const char* in, const char* out, bool gray, int scale, const jpezy_rect* region, int upsampling, bool orient)
 {
     jpezy::disp_logo();
     jpezy::decoder<T> dec(in);
-    return gray ? output<jpezy::GRAY_MODE>(dec, out, scale, region, upsampling) : output<jpezy::COLOR_MODE>(dec, out, scale, region, upsampling);
+    return gray ? output<jpezy::GRAY_MODE>(dec, out, scale, region, upsampling, orient)
+                : output<jpezy::COLOR_MODE>(dec, out, scale, region, upsampling, orient);
 }
 
 // the one rule of --upsampling=smooth: whole pictures at full size as P3 files
@@ -176,7 +180,7 @@ int main(const int argc, const char* argv[])
 
     if (!((has_ext(sv0, "jpeg") || has_ext(sv0, "jpg")) && has_ext(sv1, "ppm"))) return disp_error();
 
-    bool gray = false, verbose = false, has_region = false;
+    bool gray = false, verbose = false, has_region = false, orient = false;
     int scale = 1, upsampling = -1;
     jpezy_rect region{};
     for (const std::string_view sv : opt) {
@@ -192,13 +196,17 @@ int main(const int argc, const char* argv[])
         const int up = upsampling_of(sv);
         if (up == -2) return disp_error();
         if (upsampling < 0) upsampling = up;
+        if (sv.substr(0, 8) == "--orient") {
+            if (sv != "--orient") return disp_error();
+            orient = true;
+        }
     }
     if (upsampling < 0) upsampling = JPEZY_UPSAMPLE_NEAREST;
     if (upsampling == JPEZY_UPSAMPLE_SMOOTH && (scale != 1 || has_region)) return upsampling_rule();
     const jpezy_rect* rp = has_region ? &region : nullptr;
     try {
-        return verbose ? run<jpezy::Debug>(argv[1], argv[2], gray, scale, rp, upsampling)
-                       : run<jpezy::Release>(argv[1], argv[2], gray, scale, rp, upsampling);
+        return verbose ? run<jpezy::Debug>(argv[1], argv[2], gray, scale, rp, upsampling, orient)
+                       : run<jpezy::Release>(argv[1], argv[2], gray, scale, rp, upsampling, orient);
     } catch (const std::runtime_error& e) {
         std::cerr << e.what() << std::endl;
         return EXIT_FAILURE;

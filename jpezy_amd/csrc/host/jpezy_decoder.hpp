@@ -39,27 +39,32 @@ struct decoder {
     // scale_denom 2, 4, 8: the picture at 1/2, 1/4, 1/8 (jpezy_decode_jpeg_scaled; the reference has no such mode, the definition is
     // include/jpezy_hip.h's) -- out_width x out_height is then the size of the planes' image, pr keeps the file's.
     // upsampling JPEZY_UPSAMPLE_SMOOTH: 2:1 chroma through the triangle filter (jpezy_decode_jpeg_upsampling; include/jpezy_hip.h, CHROMA
-    // UPSAMPLING), at full size only: with another scale_denom it is refused with a message
+    // UPSAMPLING), at full size only: with another scale_denom it is refused with a message.
+    // orient: the file's EXIF orientation is applied (jpezy_decode_jpeg_oriented; include/jpezy_hip_orientation.h) -- the planes are those
+    // of the oriented picture, `orientation` says what was applied; false, the default: the tag is ignored, as it always was
     template <class MODE_TAG = COLOR_MODE>
-    std::optional<std::array<std::vector<byte>, 3>> decode(int scale_denom = 1, int upsampling = JPEZY_UPSAMPLE_NEAREST)
+    std::optional<std::array<std::vector<byte>, 3>> decode(int scale_denom = 1, int upsampling = JPEZY_UPSAMPLE_NEAREST, bool orient = false)
     {
-        return decode_impl<MODE_TAG>(scale_denom, nullptr, upsampling);
+        return decode_impl<MODE_TAG>(scale_denom, nullptr, upsampling, orient);
     }
 
     // the window `region` of the picture at 1 / scale_denom (jpezy_decode_jpeg_region; include/jpezy_hip.h, REGION DECODE): planes of
-    // w * h, out_width x out_height = w x h; a region that does not lie inside the picture is refused with the library's message
+    // w * h, out_width x out_height = w x h; a region that does not lie inside the picture is refused with the library's message.
+    // orient: the window is one of the ORIENTED picture
     template <class MODE_TAG = COLOR_MODE>
-    std::optional<std::array<std::vector<byte>, 3>> decode(int scale_denom, const jpezy_rect& region)
+    std::optional<std::array<std::vector<byte>, 3>> decode(int scale_denom, const jpezy_rect& region, bool orient = false)
     {
-        return decode_impl<MODE_TAG>(scale_denom, &region);
+        return decode_impl<MODE_TAG>(scale_denom, &region, JPEZY_UPSAMPLE_NEAREST, orient);
     }
 
     property pr;
+    int orientation = 1;                         // the orientation the last decode applied (1: none)
     std::size_t out_width = 0, out_height = 0;   // size of the decoded picture: the file's, the scaled size, or the region's
 
 private:
     template <class MODE_TAG>
-    std::optional<std::array<std::vector<byte>, 3>> decode_impl(int scale_denom, const jpezy_rect* region, int upsampling = JPEZY_UPSAMPLE_NEAREST)
+    std::optional<std::array<std::vector<byte>, 3>> decode_impl(int scale_denom, const jpezy_rect* region, int upsampling = JPEZY_UPSAMPLE_NEAREST,
+                                                                bool orient = false)
     {
         constexpr bool gray = std::is_same_v<MODE_TAG, GRAY_MODE>;
         if (upsampling != JPEZY_UPSAMPLE_NEAREST && (scale_denom != 1 || region)) {
@@ -93,9 +98,14 @@ private:
         std::array<std::vector<byte>, 3> rgb;
         for (auto& v : rgb) v.resize(rgb_s);
         int ws = info.width, hs = info.height;
-        if (jpezy_scaled_size(info.width, info.height, scale_denom, &ws, &hs) != JPEZY_OK) return {};
+        // oriented: the picture's size, and the picture a region is held against, are the oriented ones
+        const auto* bytes = reinterpret_cast<const std::uint8_t*>(file.data());
+        orientation = orient ? jpezy_jpeg_orientation(bytes, file.size()) : 1;
+        int wo = info.width, ho = info.height;
+        if (jpezy_orient_size(orientation, info.width, info.height, &wo, &ho) != JPEZY_OK) return {};
+        if (jpezy_scaled_size(wo, ho, scale_denom, &ws, &hs) != JPEZY_OK) return {};
         if (region) {
-            if (jpezy_region_check(info.width, info.height, scale_denom, region) != JPEZY_OK) {
+            if (jpezy_region_check(wo, ho, scale_denom, region) != JPEZY_OK) {
                 std::cerr << jpezy_hip_last_error() << std::endl;
                 return {};
             }
@@ -108,8 +118,9 @@ private:
         const auto plane = [&](int k) { return reinterpret_cast<std::uint8_t*>(rgb[static_cast<std::size_t>(k)].data()); };
         // decode_huffman + inverse_quantization + inverse_dct + upsampling + make_rgb (:504-578, 583-670) for all MCUs: one
         // C-ABI call; for jpezy_encode's own layout every stage runs on the device
-        const auto* bytes = reinterpret_cast<const std::uint8_t*>(file.data());
-        const int rc = upsampling != JPEZY_UPSAMPLE_NEAREST
+        const int rc = orient ? jpezy_decode_jpeg_oriented(ctx, bytes, file.size(), gray, upsampling, scale_denom, region, orientation, nullptr, &info,
+                                                           plane(0), plane(1), plane(2), rgb_s)
+                       : upsampling != JPEZY_UPSAMPLE_NEAREST
                            ? jpezy_decode_jpeg_upsampling(ctx, bytes, file.size(), gray, upsampling, &info, plane(0), plane(1), plane(2), rgb_s)
                        : region ? jpezy_decode_jpeg_region(ctx, reinterpret_cast<const std::uint8_t*>(file.data()), file.size(), gray, scale_denom,
                                                          region, &info, plane(0), plane(1), plane(2), rgb_s)

@@ -1,8 +1,11 @@
-// jpezy_tran <input.(jpg | jpeg)> <output.(jpg | jpeg)> (--rotate=(90 | 180 | 270) | --flip=(h | v) | --transpose | --transverse | --none)
-//            [OPT: --trim] [OPT: --optimize] [OPT: --restart=N]
+// jpezy_tran <input.(jpg | jpeg)> <output.(jpg | jpeg)> (--rotate=(90 | 180 | 270) | --flip=(h | v) | --transpose | --transverse | --none |
+//            --auto-orient) [OPT: --trim] [OPT: --optimize] [OPT: --restart=N]
 // This project's own tool (the reference has none): a lossless transform of a .jpg in the coefficient domain through jpezy_transform_jpeg
 // (include/jpezy_hip.h, LOSSLESS TRANSFORMS) -- what jpegtran -rotate / -flip / -transpose / -transverse do.  Exactly one operation;
 // --none re-codes the file as it is (with --optimize: per-image Huffman tables; --restart=N: restart intervals of N MCUs, 0..65535).
+// --auto-orient is the operation whose effect on the pixels is the one the input's EXIF orientation asks for (jpezy_jpeg_orientation;
+// include/jpezy_hip_orientation.h): the output is upright, and untagged since no APPn segment is carried.  The partial-MCU rule applies to
+// it as to the operation it picks.
 // --trim drops the partial MCU column / row of a mirrored axis; without it such a file is refused with the library's message.
 // Exit codes and messages as the other two CLIs: a usage error prints the usage line and exits 1 before anything is loaded; a file the
 // library refuses prints its reason and exits 1, and no output file is written.
@@ -20,7 +23,7 @@ namespace {
 
 int disp_error()
 {
-    std::cerr << "Usage: jpezy_tran <input.(jpg | jpeg)> <output.(jpg | jpeg)> (--rotate=(90 | 180 | 270) | --flip=(h | v) | --transpose | --transverse | --none)"
+    std::cerr << "Usage: jpezy_tran <input.(jpg | jpeg)> <output.(jpg | jpeg)> (--rotate=(90 | 180 | 270) | --flip=(h | v) | --transpose | --transverse | --none | --auto-orient)"
                  " [OPT: --trim] [OPT: --optimize] [OPT: --restart=N]"
               << std::endl;
     return EXIT_FAILURE;
@@ -31,10 +34,23 @@ bool has_ext(std::string_view s, std::string_view ext)
     return s.find(ext, s.find_first_of('.')) != std::string_view::npos;
 }
 
-// the operation an option names (JPEZY_XFORM_*), -1 when it names none, -2 when it is one with a bad value
+// --auto-orient as a value of op_of: resolved once the file is read
+constexpr int kAutoOrient = 100;
+
+// the operation that turns a picture tagged `orientation` upright: orient(P, o) of include/jpezy_hip_orientation.h's table, held against
+// LOSSLESS TRANSFORMS' own table of source pixels (not against the names)
+int op_for_orientation(int orientation)
+{
+    constexpr int ops[8] = { JPEZY_XFORM_NONE, JPEZY_XFORM_HFLIP, JPEZY_XFORM_ROT180, JPEZY_XFORM_VFLIP, JPEZY_XFORM_TRANSPOSE, JPEZY_XFORM_ROT90,
+                             JPEZY_XFORM_TRANSVERSE, JPEZY_XFORM_ROT270 };
+    return ops[orientation - 1];
+}
+
+// the operation an option names (JPEZY_XFORM_*, kAutoOrient), -1 when it names none, -2 when it is one with a bad value
 int op_of(std::string_view sv)
 {
     if (sv == "--none") return JPEZY_XFORM_NONE;
+    if (sv == "--auto-orient") return kAutoOrient;
     if (sv == "--transpose") return JPEZY_XFORM_TRANSPOSE;
     if (sv == "--transverse") return JPEZY_XFORM_TRANSVERSE;
     if (sv.substr(0, 9) == "--rotate=") {
@@ -69,6 +85,7 @@ int run(const char* in, const char* out, int op, int flags, bool optimize, int r
         return EXIT_FAILURE;
     }
     const std::vector<std::uint8_t> data((std::istreambuf_iterator<char>(ifs)), std::istreambuf_iterator<char>());
+    if (op == kAutoOrient) op = op_for_orientation(jpezy_jpeg_orientation(data.data(), data.size()));
     jpezy_ctx* ctx = jpezy::detail::device_context();
     auto fail = [] {
         std::cerr << "transform failed: " << jpezy_hip_last_error() << std::endl;

@@ -6,6 +6,7 @@
 // arguments and call it.
 #pragma once
 #include "jpezy_capi_internal.h"
+#include "jpezy_exif.h"
 
 namespace jpezy_capi {
 
@@ -112,6 +113,18 @@ inline int upload_dequant(jpezy_ctx* c, const DecodeSource& src, hipStream_t s)
 inline int log2n_of(int scale_denom) { return scale_denom == 1 ? 3 : scale_denom == 2 ? 2 : scale_denom == 4 ? 1 : scale_denom == 8 ? 0 : -1; }
 inline int bad_scale(const char* who) { return set_err(JPEZY_E_BADARG, std::string(who) + ": scale_denom must be 1, 2, 4 or 8"); }
 
+// the file's size as region_inside is to see it for a window of the oriented picture: swapped for the transposed orientations
+// (jpezy_scaled_size treats the two axes alike)
+inline void oriented_wh(int orientation, int W, int H, int* Wo, int* Ho)
+{
+    const bool tr = (jpezy_exif::orient_bits(orientation) & jpezy_exif::kTranspose) != 0;
+    *Wo = tr ? H : W; *Ho = tr ? W : H;
+}
+inline int bad_orientation(const char* who, bool from_file_allowed)
+{
+    return set_err(JPEZY_E_BADARG, std::string(who) + (from_file_allowed ? ": orientation must be JPEZY_ORIENT_FROM_FILE or 1..8" : ": orientation must be 1..8"));
+}
+
 // 0: nearest (the entries hand the call to the existing entry), 1: smooth, negative: the status to return
 inline int upsampling_mode(const char* who, int upsampling, int precision)
 {
@@ -173,13 +186,17 @@ struct DecodeRequest {
     size_t row_stride;
     uint8_t* dst[3];
     size_t cap;
+    // oriented output (Region, RegionSmooth; include/jpezy_hip_orientation.h): the orientation applied, 1..8 -- region is then a window of
+    // the ORIENTED picture; whole_oriented: no region was given, the window is all of that picture
+    int orientation = 1;
+    bool whole_oriented = false;
     static DecodeRequest planes(const char* who, DecodeStage stage, int gray, uint8_t* r, uint8_t* g, uint8_t* b, size_t plane_cap)
     {
-        return { who, stage, gray, 1, nullptr, -1, 0, { r, g, b }, plane_cap };
+        return { who, stage, gray, 1, nullptr, -1, 0, { r, g, b }, plane_cap, 1, false };
     }
     static DecodeRequest packed(const char* who, DecodeStage stage, int gray, int format, size_t row_stride, uint8_t* pix, size_t pix_cap)
     {
-        return { who, stage, gray, 1, nullptr, format, row_stride, { pix, pix, pix }, pix_cap };
+        return { who, stage, gray, 1, nullptr, format, row_stride, { pix, pix, pix }, pix_cap, 1, false };
     }
     bool is_packed() const { return format >= 0; }
 };
@@ -209,9 +226,10 @@ JPEZY_INTERNAL int jpezy_internal_generic_dev_core(jpezy_ctx* c, const DecodeSou
 // reduced size, log2n = 2, 1, 0 (jpezy_capi_scaled.hip)
 JPEZY_INTERNAL int jpezy_internal_scaled_dev_core(jpezy_ctx* c, const DecodeSource& src, const DecodeSink& out, hipStream_t s, int log2n);
 // the window rg (inside the picture) at log2n = 3, 2, 1, 0; the sink is the window's; upsampling != 0 (JPEZY_UPSAMPLE_SMOOTH, 8-bit files):
-// region_smooth_kernel in region_kernel's place (jpezy_capi_region.hip)
+// region_smooth_kernel in region_kernel's place (jpezy_capi_region.hip).  orientation 2..8: rg is a window of the ORIENTED picture
+// (inside it) and the ORIENT instances of the two kernels run; 1: the launches made without the argument
 JPEZY_INTERNAL int jpezy_internal_region_dev_core(jpezy_ctx* c, const DecodeSource& src, const DecodeSink& out, hipStream_t s, int log2n,
-                                                  const jpezy_rect& rg, int upsampling = 0);
+                                                  const jpezy_rect& rg, int upsampling = 0, int orientation = 1);
 // the second stage of the resized batch of windows: tap tables and descriptors of `jobs` through c->r_pin / c->r_tab, then resample_kernel
 // (jpezy_capi_resized.hip).  tensor: resample_tensor_kernel in its place -- d_dst is the tensor's first element, ResampleJob::dst_off counts
 // elements, dst_stride is not read and bytes is 3.  how: the filter and the form, the CALL's (a child context is handed its parent's);

@@ -602,12 +602,22 @@ int jpezy_internal_decode_file(jpezy_ctx* c, const uint8_t* data, size_t len, jp
     if (int rc2 = jpezy_internal_check_dims(c, W, H, 1)) return rc2;
     // the output: the window, or the picture at 1 / scale_denom
     int w, h;
-    if (rq.region) {
-        if (int rc2 = region_inside(rq.who, W, H, rq.scale_denom, rq.region)) return rc2;
-        if (rq.stage == DecodeStage::Region && whole_picture(W, H, rq.scale_denom, *rq.region))       // what a full request costs: the reduced-size entry, under its own name
+    // oriented: the window is one of the oriented picture (all of it when the entry was given none)
+    jpezy_rect whole = { 0, 0, 0, 0 };
+    const jpezy_rect* region = rq.region;
+    int Wo, Ho;
+    oriented_wh(rq.orientation, W, H, &Wo, &Ho);
+    if (rq.whole_oriented) {
+        (void)jpezy_scaled_size(Wo, Ho, rq.scale_denom, &whole.w, &whole.h);
+        region = &whole;
+    }
+    if (region) {
+        if (int rc2 = region_inside(rq.who, Wo, Ho, rq.scale_denom, region)) return rc2;
+        // what a full request costs: the reduced-size entry, under its own name (an oriented whole picture stays with the region stage)
+        if (rq.stage == DecodeStage::Region && rq.orientation == 1 && !rq.whole_oriented && whole_picture(W, H, rq.scale_denom, *region))
             return rq.is_packed() ? jpezy_decode_jpeg_scaled_packed(c, data, len, rq.gray, rq.scale_denom, info, rq.format, rq.row_stride, rq.dst[0], rq.cap)
                                   : jpezy_decode_jpeg_scaled(c, data, len, rq.gray, rq.scale_denom, info, rq.dst[0], rq.dst[1], rq.dst[2], rq.cap);
-        w = rq.region->w; h = rq.region->h;
+        w = region->w; h = region->h;
     } else {
         (void)jpezy_scaled_size(W, H, rq.scale_denom, &w, &h);
     }
@@ -643,8 +653,8 @@ int jpezy_internal_decode_file(jpezy_ctx* c, const uint8_t* data, size_t len, jp
         break;
     case DecodeStage::Smooth: rc2 = jpezy_internal_generic_dev_core(c, src, out, c->stream, 1); break;
     case DecodeStage::Scaled: rc2 = jpezy_internal_scaled_dev_core(c, src, out, c->stream, log2n_of(rq.scale_denom)); break;
-    case DecodeStage::Region: rc2 = jpezy_internal_region_dev_core(c, src, out, c->stream, log2n_of(rq.scale_denom), *rq.region); break;
-    case DecodeStage::RegionSmooth: rc2 = jpezy_internal_region_dev_core(c, src, out, c->stream, log2n_of(rq.scale_denom), *rq.region, 1); break;
+    case DecodeStage::Region: rc2 = jpezy_internal_region_dev_core(c, src, out, c->stream, log2n_of(rq.scale_denom), *region, 0, rq.orientation); break;
+    case DecodeStage::RegionSmooth: rc2 = jpezy_internal_region_dev_core(c, src, out, c->stream, log2n_of(rq.scale_denom), *region, 1, rq.orientation); break;
     }
     if (rc2) return rc2;
     if (!rq.is_packed()) {

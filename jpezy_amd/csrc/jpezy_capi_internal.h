@@ -235,6 +235,7 @@ struct jpezy_ctx {
     DevBuf w_tab;                  // ... and their device copy
     int w_slice_files = 0;         // files per slice of its grouped path; 0: automatic (jpezy_ctx_set_windows_slice_files)
     int w_upsampling = 0;          // chroma upsampling of the two windows entries: JPEZY_UPSAMPLE_NEAREST (jpezy_ctx_set_windows_upsampling)
+    int w_orientation = 0;         // 1: the windows entries honour every file's EXIF orientation (jpezy_ctx_set_windows_orientation)
     DevBuf w_scr;                  // jpezy_decode_windows_resized_dev: a slice's (a child context: one file's) windows as decoded, packed pixels
     PinBuf r_pin;                  // ... pinned staging of a launch's resample descriptors and tap tables
     DevBuf r_tab;                  // ... and their device copy

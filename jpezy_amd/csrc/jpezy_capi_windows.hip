@@ -6,6 +6,9 @@
 // child context, straight into the file's slot.  Nothing is downloaded.  Resized: the same launches write a context-owned scratch of packed
 // pixels, every file by its own height, and one launch of resample_kernel per slice (jpezy_kernels_resized.hip) writes the slots.  Part 15's
 // entry, jpezy_decode_windows_tensor_dev, is the resized call with resample_tensor_kernel (jpezy_kernels_resized_tensor.hip) as that launch.
+// With jpezy_ctx_set_windows_orientation(ctx, 1) (include/jpezy_hip_orientation.h) every file's EXIF orientation is honoured: windows are
+// those of the oriented picture, the launches are given their source-side rectangles, and the files whose orientation is not 1 go out in
+// an oriented launch of their own per scale.
 #include "jpezy_capi_decode.h"
 #include "jpezy_tensor_layout.h"
 
@@ -56,7 +59,9 @@ struct Cand {
     const uint8_t* scan = nullptr;      // grouped path: the file from its first scan byte
     size_t n = 0;
     size_t nblk = 0;                    // blocks of the whole file
-    jpezy_rect rect = { 0, 0, 0, 0 };
+    jpezy_rect rect = { 0, 0, 0, 0 };     // the window as placed: with the orientation setting on, in the ORIENTED picture's coordinates
+    jpezy_rect src = { 0, 0, 0, 0 };      // ... and the rectangle of the decoded picture it shows (jpezy_orient_rect); rect itself otherwise
+    int orient = 1;                     // the file's orientation as applied: 1 with the setting off
     int log2n = 3;
     int st = JPEZY_OK;                  // < 0: decided before any device work
     bool parsed = false, good = false;  // good: the grouped path takes it
@@ -165,7 +170,8 @@ int decode_slice(jpezy_ctx* c, const std::vector<int>& files, const std::vector<
 
     // descriptor tables: one per launch (a scale; a second one for a scale whose workgroups would not fit 32 bits), the dequantiser sets
     // de-duplicated in front of them -- built in the context's pinned staging, one upload
-    struct Launch { int log2n; unsigned long long total; std::vector<WindowDesc> desc; };
+    // (with the orientation setting on: files whose orientation is 1 keep the un-oriented launch, the others share an oriented one)
+    struct Launch { int log2n; bool oriented; unsigned long long total; std::vector<WindowDesc> desc; };
     std::vector<Launch> launches;
     std::vector<int> qsets;                                           // [sets][192]
     for (unsigned k = 0; k < nf; ++k) {
@@ -183,22 +189,25 @@ int decode_slice(jpezy_ctx* c, const std::vector<int>& files, const std::vector<
         std::memset(&d, 0, sizeof d);
         d.coeff_off = streams[k].coeff_off;
         d.out_off = out.rz ? scr_off[k] : (unsigned long long)i * out.slot_stride;
-        d.qset = (int)qs;
+        const bool oriented = cd.orient != 1;
+        d.qset = (int)qs | (oriented ? jpezy_exif::orient_bits(cd.orient) << kWindowOrientShift : 0);      // (qs < 512: a set per file at most)
         d.mcu_cols = info[i].mcu_cols;
-        d.x = cd.rect.x; d.y = cd.rect.y; d.w = cd.rect.w; d.h = cd.rect.h;
-        d.ux0 = cd.rect.x / mw; d.ucols = (cd.rect.x + cd.rect.w - 1) / mw - d.ux0 + 1;
-        d.uy0 = cd.rect.y / mh;
+        // the kernel's rectangle is the source-side one (the window itself when un-oriented); so are the MCUs
+        const jpezy_rect& sr = cd.src;
+        d.x = sr.x; d.y = sr.y; d.w = sr.w; d.h = sr.h;
+        d.ux0 = sr.x / mw; d.ucols = (sr.x + sr.w - 1) / mw - d.ux0 + 1;
+        d.uy0 = sr.y / mh;
         if (out.smooth) {               // the picture at this scale: the extent of the smoothed components' planes (inside the file's MCU grid)
             int Ws, Hs;
             (void)jpezy_scaled_size(info[i].width, info[i].height, 8 >> cd.log2n, &Ws, &Hs);
             if (Ws > info[i].mcu_cols * mw || Hs > info[i].mcu_rows * mh) { ok[k] = 0; continue; }      // (no header gives this: left to the per-file path)
             d.pad[0] = (unsigned)Ws; d.pad[1] = (unsigned)Hs;
         }
-        const unsigned long long wgs = (unsigned long long)d.ucols * (unsigned long long)((cd.rect.y + cd.rect.h - 1) / mh - d.uy0 + 1);
+        const unsigned long long wgs = (unsigned long long)d.ucols * (unsigned long long)((sr.y + sr.h - 1) / mh - d.uy0 + 1);
         Launch* L = nullptr;
         for (Launch& l : launches)
-            if (l.log2n == cd.log2n && l.total + wgs <= 0xFFFFFFFFull) L = &l;
-        if (!L) { launches.push_back({ cd.log2n, 0, {} }); L = &launches.back(); }
+            if (l.log2n == cd.log2n && l.oriented == oriented && l.total + wgs <= 0xFFFFFFFFull) L = &l;
+        if (!L) { launches.push_back({ cd.log2n, oriented, 0, {} }); L = &launches.back(); }
         d.wg0 = (unsigned)L->total;
         L->total += wgs;
         L->desc.push_back(d);
@@ -242,14 +251,16 @@ int decode_slice(jpezy_ctx* c, const std::vector<int>& files, const std::vector<
         p.desc = (const WindowDesc*)((const uint8_t*)c->w_tab.p + desc_at[l]);
         p.n_desc = (unsigned)launches[l].desc.size();
         if (dbg) HIP_TRY(hipEventRecord(ev0, s));
-        HIP_TRY(out.smooth ? launch_dequant_idct_windows_smooth(p, launches[l].total, s) : launch_dequant_idct_windows(p, launches[l].total, s));
+        HIP_TRY(out.smooth ? launch_dequant_idct_windows_smooth(p, launches[l].total, s, launches[l].oriented)
+                           : launch_dequant_idct_windows(p, launches[l].total, s, launches[l].oriented));
         if (dbg) {
             float ms = 0;
             HIP_TRY(hipEventRecord(ev1, s));
             HIP_TRY(hipEventSynchronize(ev1));
             HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
-            std::fprintf(stderr, "  windows slice (%u files): %s<%d>, %u files, %llu workgroups: %.3f ms (device events)\n", nf,
-                         out.smooth ? "windows_smooth_kernel" : "windows_kernel", 1 << p.log2n, p.n_desc, launches[l].total, (double)ms);
+            std::fprintf(stderr, "  windows slice (%u files): %s<%d%s>, %u files, %llu workgroups: %.3f ms (device events)\n", nf,
+                         out.smooth ? "windows_smooth_kernel" : "windows_kernel", 1 << p.log2n, launches[l].oriented ? ", oriented" : "", p.n_desc,
+                         launches[l].total, (double)ms);
         }
     }
     if (out.rz) {
@@ -297,7 +308,7 @@ int jpezy_window_fit(int W, int H, const jpezy_window* win, int format, size_t r
 int jpezy_ctx_set_windows_slice_files(jpezy_ctx* c, int n)
 {
     if (!c) return set_err(JPEZY_E_BADARG, "null context");
-    if (n < 0 || n > 512) return set_err(JPEZY_E_BADARG, "windows_slice_files must be 0 (automatic) or 1..512");
+    if (n < 0 || n > kWindowMaxFiles) return set_err(JPEZY_E_BADARG, "windows_slice_files must be 0 (automatic) or 1..512");
     c->w_slice_files = n;
     return JPEZY_OK;
 }
@@ -315,6 +326,20 @@ int jpezy_ctx_windows_upsampling(jpezy_ctx* c)
 {
     if (!c) return set_err(JPEZY_E_BADARG, "null context");
     return c->w_upsampling;
+}
+
+int jpezy_ctx_set_windows_orientation(jpezy_ctx* c, int mode)
+{
+    if (mode != 0 && mode != 1) return set_err(JPEZY_E_BADARG, "windows_orientation: mode must be 0 (ignore the tag) or 1 (honour every file's own)");
+    if (!c) return set_err(JPEZY_E_BADARG, "null context");
+    c->w_orientation = mode;
+    return JPEZY_OK;
+}
+
+int jpezy_ctx_windows_orientation(jpezy_ctx* c)
+{
+    if (!c) return set_err(JPEZY_E_BADARG, "null context");
+    return c->w_orientation;
 }
 
 int jpezy_ctx_set_windows_filter(jpezy_ctx* c, int filter)
@@ -376,6 +401,7 @@ int windows_driver(jpezy_ctx* c, const char* who_c, int n, const uint8_t* const*
     }
     c->b_last_fast = 0;
     const int smooth = c->w_upsampling == JPEZY_UPSAMPLE_SMOOTH ? 1 : 0;
+    const bool honour_tag = c->w_orientation != 0;      // read once, here: a child context decodes what the call's context decided
     const bool blue_first = format == JPEZY_PIX_BGR24 || format == JPEZY_PIX_BGRA32;
     std::vector<Cand> all((size_t)n);
     std::vector<char> done((size_t)n, 0);
@@ -394,10 +420,21 @@ int windows_driver(jpezy_ctx* c, const char* who_c, int n, const uint8_t* const*
         if (smooth)                     // this file alone: its slot stays untouched, the others are decoded
             if (int mode = upsampling_mode(who_c, JPEZY_UPSAMPLE_SMOOTH, fi.precision); mode < 0) { cd.st = mode; cd.msg = g_err; return; }
         const jpezy_window* win = windows ? &windows[i] : nullptr;
-        const int fit = resolve_window(who_c, fi.width, fi.height, win, bytes, row_stride, slot_stride, &cd.rect, rz == nullptr);
+        // the file's tag, parsed once; the window is then one of the oriented picture, whose size is the file's with the axes swapped for
+        // the transposed orientations
+        cd.orient = honour_tag ? jpezy_exif::jpeg_orientation(data[i], len[i]) : 1;
+        int Wo, Ho;
+        oriented_wh(cd.orient, fi.width, fi.height, &Wo, &Ho);
+        const int fit = resolve_window(who_c, Wo, Ho, win, bytes, row_stride, slot_stride, &cd.rect, rz == nullptr);
         if (placed && (fit == JPEZY_OK || fit == JPEZY_E_NOSPACE)) placed[i] = cd.rect;       // (a window inside the picture is reported, fitting or not)
         if (fit) { cd.st = fit; cd.msg = g_err; return; }
         cd.log2n = log2n_of(win ? win->scale_denom : 1);
+        {
+            int Ws, Hs;
+            (void)jpezy_scaled_size(fi.width, fi.height, 8 >> cd.log2n, &Ws, &Hs);
+            const jpezy_exif::Rect sr = jpezy_exif::orient_rect(cd.orient, Ws, Hs, { cd.rect.x, cd.rect.y, cd.rect.w, cd.rect.h });
+            cd.src = { sr.x, sr.y, sr.w, sr.h };
+        }
         // what the grouped path takes: jpezy_decode_jpeg_batch's rule -- every baseline layout decode_mcu handles (1 or 3 components,
         // sampling factors 1..4, at most 48 blocks per MCU), tables present, no restart interval, the scan bounds
         bool fits = (fi.ncomp == 1 || fi.ncomp == 3) && fi.restart_interval == 0 && fi.blocks_per_mcu >= 1 && fi.blocks_per_mcu <= 48;
@@ -437,7 +474,7 @@ int windows_driver(jpezy_ctx* c, const char* who_c, int n, const uint8_t* const*
         // slices: coefficients (2 bytes each), the scan and the decoder's scratch over it (the scan, its unstuffed copy, 20 bytes of state
         // per subsequence: below 4 bytes per scan byte) stay under ~1.5 GB, at most 512 files (jpezy_ctx_set_windows_slice_files: a fixed count).
         // Resized: the scratch of the slice's windows (rows of its widest window, the sum of their heights) counts against the same bound
-        const size_t max_files = c->w_slice_files > 0 ? (size_t)c->w_slice_files : 512;
+        const size_t max_files = c->w_slice_files > 0 ? (size_t)c->w_slice_files : (size_t)kWindowMaxFiles;
         for (size_t s0 = 0; s0 < grp.size();) {
             std::vector<int> slice;
             size_t mem = 0, wmax = 0, rows = 0;
@@ -488,7 +525,7 @@ int windows_driver(jpezy_ctx* c, const char* who_c, int n, const uint8_t* const*
             // the region stage core, for a whole picture too (the full window): the defined arithmetic, straight into the slot
             if (int rc = jpezy_internal_region_dev_core(w, DecodeSource::file((const int16_t*)w->out.p, info[i], gray),
                                                         DecodeSink::packed(L, rz ? (uint8_t*)w->w_scr.p : d_pix + (size_t)i * slot_stride), w->stream,
-                                                        cd.log2n, cd.rect, smooth))
+                                                        cd.log2n, cd.rect, smooth, cd.orient))
                 return rc;
             if (rz) {
                 const std::vector<ResampleJob> job = { { 0, (unsigned long long)i * slot_stride, cd.rect.w, cd.rect.h, rz->mirror_x && rz->mirror_x[i] ? 1 : 0 } };

@@ -262,12 +262,19 @@ struct RegionDecParams {
     // n_frames frames of ONE layout, size and set of quantiser tables: frame f's coefficients at coeffs + f * blocks * 64, its output at
     // r/g/b + f * plane_stride (any value that holds a window)
     int n_frames = 1;
+    // oriented output (include/jpezy_hip_orientation.h): != 0 launches the ORIENT instances -- bit 0 transpose, bit 1 mirror x, bit 2 mirror
+    // y.  {x, y, w, h} is then the SOURCE-side rectangle of the oriented window (jpezy_orient_rect), the output is h x w pixels when
+    // transposed (planes: rows h apart), and output pixel (u, v) -- transposed: (v, u) -- is source pixel (x + u, y + v), a mirrored axis
+    // counted from the rectangle's far edge.  (It sits in the four bytes of padding in front of plane_stride: every other member, and the
+    // second kernel argument of the smooth form, lies where it lay.)
+    int orient = 0;
     size_t plane_stride = 0;
     // packed (interleaved) output as in ScaledDecParams: pix_bytes = 3 or 4 (0: planes, rows w apart); rows row_stride apart, frames
     // plane_stride apart; byte 3 of a 32-bit pixel = 0xFF
     int pix_bytes = 0;
     unsigned row_stride = 0;
 };
+static_assert(sizeof(RegionDecParams) == 168, "orient fills padding: the kernel arguments of the un-oriented instances do not move");
 hipError_t launch_dequant_idct_region(const RegionDecParams& p, hipStream_t stream);
 
 // a batch of crop windows (jpezy_kernels_region.hip): the windows of many files of ONE layout at ONE scale 8 / N in one launch; size, window,
@@ -275,7 +282,7 @@ hipError_t launch_dequant_idct_region(const RegionDecParams& p, hipStream_t stre
 struct WindowDesc {
     unsigned long long coeff_off;   // int16 offset of the file's first coefficient (the WHOLE file's coefficients lie there)
     unsigned long long out_off;     // byte offset of the window's pixel (0, 0) behind WindowsParams::pix
-    int qset;                       // index of the file's dequantiser set
+    int qset;                       // index of the file's dequantiser set; oriented launches: | RegionDecParams::orient's bits << kWindowOrientShift
     int mcu_cols;                   // MCU columns of the file
     int x, y, w, h;                 // the window, in the coordinates of the picture at the launch's scale
     int ux0, uy0, ucols;            // the MCUs that intersect it: columns [ux0, ux0 + ucols), rows from uy0
@@ -283,6 +290,9 @@ struct WindowDesc {
     unsigned pad[2];                // windows_smooth_kernel: Ws, Hs -- the file's picture at the launch's scale; windows_kernel reads neither
 };
 static_assert(sizeof(WindowDesc) == 64, "one descriptor per 64-byte line");
+// a launch has at most one dequantiser set per file and a slice at most 512 files (jpezy_ctx_set_windows_slice_files): qset needs 10 bits
+constexpr int kWindowMaxFiles = 512, kWindowOrientShift = 28, kWindowQsetMask = (1 << kWindowOrientShift) - 1;
+static_assert(kWindowMaxFiles <= kWindowQsetMask && (7 << kWindowOrientShift) > 0, "WindowDesc::qset holds a set index and three orientation bits");
 struct WindowsParams {
     const int16_t* coeffs;
     const int* qsets;               // [sets][3 comps][64] natural order: the de-duplicated dequantiser sets of the launch's files
@@ -296,13 +306,14 @@ struct WindowsParams {
     int level;                      // 128, or 2048 when SOF0 says precision != 8 (ref :654)
     int pix_bytes, swap_rb;         // 3 or 4 bytes per pixel; swap_rb: blue is byte 0; byte 3 of a 32-bit pixel = 0xFF
 };
-hipError_t launch_dequant_idct_windows(const WindowsParams& p, unsigned long long total_wg, hipStream_t stream);
+// oriented: the ORIENT instances -- every descriptor holds the SOURCE-side rectangle and its file's bits in qset (above)
+hipError_t launch_dequant_idct_windows(const WindowsParams& p, unsigned long long total_wg, hipStream_t stream, bool oriented = false);
 
 // region and window-batch decode with smooth chroma upsampling (jpezy_kernels_region.hip; include/jpezy_hip.h, SMOOTH UPSAMPLING OF
 // WINDOWS): the same parameters and grids as the two launchers above, and the picture's size Ws x Hs at the launch's scale -- an argument
 // here, WindowDesc::pad[0], pad[1] of every file there.  Both must lie inside the file's MCU grid (jpezy_scaled_size of the file's size does)
 hipError_t launch_dequant_idct_region_smooth(const RegionDecParams& p, int Ws, int Hs, hipStream_t stream);
-hipError_t launch_dequant_idct_windows_smooth(const WindowsParams& p, unsigned long long total_wg, hipStream_t stream);
+hipError_t launch_dequant_idct_windows_smooth(const WindowsParams& p, unsigned long long total_wg, hipStream_t stream, bool oriented = false);
 
 // a batch of windows, resized (jpezy_kernels_resized.hip; include/jpezy_hip.h, BATCH OF WINDOWS, RESIZED): the packed pixels of MANY windows
 // of different sizes, each resampled to the launch's out_w x out_h.  One descriptor per file; a workgroup is one tile of kResampleTileW x

@@ -3,7 +3,7 @@
 // each with replicated or with SMOOTH (triangle-filter) chroma.  An output pixel depends only on the MCU that covers it and, smoothed, on a
 // ring of one sample around it: the window is DEFINED as the existing (scaled) decode, sliced.  One launch, no
 // intermediate in device memory; one workgroup = one MCU that intersects a window.  Four entry kernels find their MCU and run ONE body:
-//   region_kernel<N, PIX>         : grid = (window MCU columns, window MCU rows, frame)
+//   region_kernel<N, PIX, ORIENT> : grid = (window MCU columns, window MCU rows, frame)
 //   windows_kernel<N, PIX>        : the windows of MANY files in one launch (include/jpezy_hip.h, BATCH OF WINDOWS).  The
 //                                   files share a layout and a scale; size, window, destination and quantiser tables are each file's own.
 //                                   The grid is 1-D over the sum of the files' window MCUs; a workgroup finds its file by a binary search
@@ -14,7 +14,7 @@
 //                                   native plane AT THE REQUESTED SCALE, P_s: the N x N samples of the component's own blocks, N = 8 /
 //                                   scale, cut to ceil(Ws / fx) x ceil(Hs / fy) and clamped to bytes (include/jpezy_hip.h, SMOOTH
 //                                   UPSAMPLING OF WINDOWS).  Every other component is placed by replication.
-// decode_mcu_window<N, PIX, SMOOTH>, the body:
+// decode_mcu_window<N, PIX, SMOOTH, ORIENT>, the body:
 //       stage 1   the N x N low-frequency corner of every block of the MCU is dequantised into LDS (32-bit int) with the file's own
 //                 dequantisers, then every thread evaluates samples of it: N*N terms cu*cv * (coef*Q) * cos[u*8/N][x] * cos[v*8/N][y], v
 //                 outer, u inner, left to right in FP64 -- scaled_idct_kernel's scheme, with N = 8 as well (there it is the generic pair's
@@ -35,6 +35,9 @@
 //                 then the pixel-output stage of jpezy_pixel_out.h, stored at (X - x, Y - y).  A group of four that another MCU shares, or
 //                 whose address is no multiple of 4, goes out as single bytes.
 // With SMOOTH = false stage 1b, the tile and the filter branch are not in the instance, and the workgroup's LDS is the two sample arrays.
+// ORIENT, a third property of the body and of the four entry kernels (include/jpezy_hip_orientation.h): the window is one
+// of the picture mirrored / rotated / transposed as an EXIF orientation says.  Stages 1 and 1b do not change; stage 2 walks the MCU's
+// footprint in the ORIENTED window and reads the same samples through the map.  ORIENT = false instances are the code they were.
 // Only the coefficient blocks of MCUs that intersect a window (SMOOTH: and single coefficients' blocks of their neighbours) are read; no byte
 // outside a window's w x h output is written.
 #include "jpezy_pixel_out.h"
@@ -75,7 +78,11 @@ struct McuView {
     uint8_t *out_r, *out_g, *out_b;       // planes: rows w apart; packed: the channel bytes of the first pixel, rows row_stride apart
     size_t row_stride;
     bool blue_first;                      // packed: blue is byte 0 of a pixel
+    // ORIENT instances only (include/jpezy_hip_orientation.h): {x, y, w, h} is the SOURCE-side rectangle of the oriented window, and the
+    // output pixel of source pixel (sx, sy) is (u, v) -- transposed: (v, u) -- with u = sx - x, mirrored: x + w - 1 - sx, and v likewise
+    int orient;                           // kOrientTranspose | kOrientMirrorX | kOrientMirrorY; wave-uniform
 };
+constexpr int kOrientTranspose = 1, kOrientMirrorX = 2, kOrientMirrorY = 4;
 
 // one sample (x, y) of a block: N*N terms cu*cv * d(v * N + u) * cos[u*8/N][x] * cos[v*8/N][y], v outer, u inner, left to right in FP64
 template <int N, class Get>
@@ -100,7 +107,8 @@ __device__ __forceinline__ int sample_at(Get d, int x, int y, int level)
 // p: the launch's layout constants (RegionDecParams or WindowsParams: the fields both have).  dct, smp: kMaxBlocks * N * N ints of LDS each.
 // SMOOTH: sv says which components are smoothed, tile: 3 * tile_ints(N) ints of LDS; neither is looked at otherwise.
 // PIX: 0 = planes; 3 / 4 = packed (interleaved) pixels of that many bytes, as in scaled_rgb_kernel.
-template <int N, int PIX, bool SMOOTH, class Params>
+// ORIENT: stage 2 walks the MCU's footprint in the ORIENTED window (m.orient); false: the instance is the code it was without the property.
+template <int N, int PIX, bool SMOOTH, bool ORIENT, class Params>
 __device__ __forceinline__ void decode_mcu_window(const Params& p, const McuView& m, const SmoothView& sv, int* dct, int* smp, int* tile)
 {
     constexpr int NN = N * N;
@@ -207,6 +215,74 @@ __device__ __forceinline__ void decode_mcu_window(const Params& p, const McuView
     const int X0 = max((int)ux * mw, m.x), X1 = min((int)(ux + 1) * mw, m.x + m.w);      // picture coordinates
     const int Y0 = max((int)uy * mh, m.y), Y1 = min((int)(uy + 1) * mh, m.y + m.h);
     if (X1 <= X0 || Y1 <= Y0) return;
+    if constexpr (ORIENT) {
+        // The footprint of the MCU's source pixels [X0, X1) x [Y0, Y1) in the oriented window: columns [c_lo, c_hi), rows [r_lo, r_hi) of
+        // the output -- a rectangle of mh x mw pixels at most when transposed.  A thread owns four consecutive pixels of an OUTPUT row and
+        // maps each back to its source (ix, iy) in the MCU; what the un-oriented form precomputes per row is per pixel here.
+        const bool tr = (m.orient & kOrientTranspose) != 0, fx = (m.orient & kOrientMirrorX) != 0, fy = (m.orient & kOrientMirrorY) != 0;
+        const int u_lo = fx ? m.x + m.w - X1 : X0 - m.x, u_hi = fx ? m.x + m.w - X0 : X1 - m.x;
+        const int v_lo = fy ? m.y + m.h - Y1 : Y0 - m.y, v_hi = fy ? m.y + m.h - Y0 : Y1 - m.y;
+        const int c_lo = tr ? v_lo : u_lo, c_hi = tr ? v_hi : u_hi, r_lo = tr ? u_lo : v_lo, r_hi = tr ? u_hi : v_hi;
+        const int out_w = tr ? m.h : m.w;                                               // planes: rows are the oriented window's width apart
+        const int g0 = c_lo >> 2, ng = ((c_hi - 1) >> 2) - g0 + 1, nitems = ng * (r_hi - r_lo);
+        const int sx_org = (fx ? m.x + m.w - 1 : m.x) - (int)ux * mw, sy_org = (fy ? m.y + m.h - 1 : m.y) - (int)uy * mh;   // (ix, iy) of u = 0, v = 0
+        for (int i = threadIdx.x; i < nitems; i += kThreads) {
+            const int gy = i / ng, gx = i - gy * ng;
+            const int oy = r_lo + gy;
+            const int ox0 = max((g0 + gx) * 4, c_lo), ox1 = min((g0 + gx) * 4 + 4, c_hi);
+            const unsigned npx = (unsigned)(ox1 - ox0);
+            uint32_t rw = 0, gw = 0, bw = 0;
+            for (unsigned j = 0; j < npx; ++j) {
+                const int ox = ox0 + (int)j;
+                const int u = tr ? oy : ox, v = tr ? ox : oy;
+                const unsigned ix = (unsigned)(fx ? sx_org - u : sx_org + u), iy = (unsigned)(fy ? sy_org - v : sy_org + v);    // inside the MCU
+                int sv3[3];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    sv3[c] = c ? 0x80 : 0;                                             // ref :104-105
+                    if constexpr (SMOOTH) {
+                        if (sv.fx[c] != 0) {
+                            if (c && p.gray) continue;
+                            const bool h2 = sv.fx[c] == 2, v2 = sv.fy[c] == 2, odd = (ix & 1u) != 0, oddy = (iy & 1u) != 0;
+                            const int pitch = (p.ch[c] << l2) + 2;
+                            const int ti = h2 ? (int)(ix >> 1) + 1 : (int)ix + 1, tn = h2 ? (odd ? ti + 1 : ti - 1) : ti;
+                            const int tj = v2 ? (int)(iy >> 1) + 1 : (int)iy + 1;
+                            const int trw = c * kTile + tj * pitch, trn = v2 ? trw + (oddy ? pitch : -pitch) : trw;
+                            const int a = tile[trw + ti];
+                            if (h2 && v2) {
+                                const int Si = 3 * a + tile[trn + ti], Sn = 3 * tile[trw + tn] + tile[trn + tn];
+                                sv3[c] = (3 * Si + Sn + (odd ? 7 : 8)) >> 4;
+                            } else if (h2) {
+                                sv3[c] = (3 * a + tile[trw + tn] + (odd ? 2 : 1)) >> 2;
+                            } else {
+                                sv3[c] = (3 * a + tile[trn + ti] + (oddy ? 2 : 1)) >> 2;
+                            }
+                            continue;
+                        }
+                    }
+                    // decode_mcu's placement (ref :504-528), as below, for this pixel's own row
+                    const unsigned cvv = (unsigned)p.cv[c], dupy = (unsigned)p.vmax / cvv;
+                    const unsigned ky = min(cvv - 1u, iy >> l2), yu = iy - (ky << l2);
+                    if (!(c < p.ncomp && yu < (dupy << l2))) continue;
+                    const unsigned chh = (unsigned)p.ch[c], dupx = (unsigned)p.hmax / chh;
+                    const unsigned kx = min(chh - 1u, ix >> l2), xu = ix - (kx << l2);
+                    if (xu < (dupx << l2))
+                        sv3[c] = smp[(((unsigned)p.blk_start[c] + ky * chh + kx) << (2 * l2)) + ((yu / dupy) << l2) + xu / dupx];
+                }
+                uint32_t r, g, b;
+                make_rgb(p.gray, sv3[0], sv3[1], sv3[2], r, g, b);                     // ref :531-578, 672-676
+                rw |= r << (8 * j); gw |= g << (8 * j); bw |= b << (8 * j);
+            }
+            if constexpr (PIX != 0) {
+                uint8_t* px = (m.blue_first ? m.out_b : m.out_r) + (size_t)(unsigned)oy * m.row_stride + (size_t)(unsigned)ox0 * PIX;
+                store_packed4<PIX>(px, npx, m.blue_first ? bw : rw, gw, m.blue_first ? rw : bw);
+            } else {
+                const size_t off = (size_t)(unsigned)oy * (unsigned)out_w + (unsigned)ox0;
+                store_planes4(m.out_r, m.out_g, m.out_b, off, npx, rw, gw, bw, planes_word_aligned(m.out_r, m.out_g, m.out_b, off));
+            }
+        }
+        return;
+    }
     const int ox_lo = X0 - m.x, ox_hi = X1 - m.x;                                       // output columns [ox_lo, ox_hi)
     const int g0 = ox_lo >> 2, ng = ((ox_hi - 1) >> 2) - g0 + 1, nitems = ng * (Y1 - Y0);
     uint8_t* const out_r = m.out_r;
@@ -287,6 +363,7 @@ __device__ __forceinline__ void decode_mcu_window(const Params& p, const McuView
 // ---- the MCU of a workgroup ----
 
 // region form: MCU (ux0 + blockIdx.x, uy0 + blockIdx.y) of frame blockIdx.z; r, g, b: the channel bytes of pixel (0, 0)
+template <bool ORIENT>
 __device__ __forceinline__ McuView region_view(const RegionDecParams& p)
 {
     const unsigned ux = (unsigned)p.ux0 + blockIdx.x, uy = (unsigned)p.uy0 + blockIdx.y;
@@ -294,10 +371,11 @@ __device__ __forceinline__ McuView region_view(const RegionDecParams& p)
     const int16_t* co0 = p.coeffs + f * (size_t)p.mcu_rows * (size_t)p.mcu_cols * (size_t)p.blocks_per_mcu * 64;
     const size_t mcu = (size_t)uy * (size_t)p.mcu_cols + ux;
     return { co0 + mcu * (size_t)p.blocks_per_mcu * 64, co0, p.qt, ux, uy, (unsigned)p.mcu_cols, p.x, p.y, p.w, p.h,
-             p.r + f * p.plane_stride, p.g + f * p.plane_stride, p.b + f * p.plane_stride, p.row_stride, p.b < p.r };
+             p.r + f * p.plane_stride, p.g + f * p.plane_stride, p.b + f * p.plane_stride, p.row_stride, p.b < p.r, ORIENT ? p.orient : 0 };
 }
 
 // batch form: workgroup wg of the call is MCU wg - wg0 of file d's window, row by row
+template <bool ORIENT>
 __device__ __forceinline__ McuView windows_view(const WindowsParams& p, const WindowDesc& d, unsigned wg)
 {
     const unsigned local = wg - d.wg0, ucols = (unsigned)d.ucols;
@@ -306,31 +384,34 @@ __device__ __forceinline__ McuView windows_view(const WindowsParams& p, const Wi
     const size_t mcu = (size_t)uy * (size_t)d.mcu_cols + ux;
     uint8_t* const px0 = p.pix + d.out_off;
     const int16_t* co0 = p.coeffs + d.coeff_off;
-    return { co0 + mcu * (size_t)p.blocks_per_mcu * 64, co0, p.qsets + (size_t)d.qset * 192, ux, uy, (unsigned)d.mcu_cols, d.x, d.y, d.w, d.h,
-             px0 + (p.swap_rb ? 2 : 0), px0 + 1, px0 + (p.swap_rb ? 0 : 2), p.row_stride, p.swap_rb != 0 };
+    // ORIENT: the file's three bits ride in the spare high bits of qset (WindowDesc); the un-oriented instances read the field as it is
+    const int qset = ORIENT ? (d.qset & kWindowQsetMask) : d.qset;
+    return { co0 + mcu * (size_t)p.blocks_per_mcu * 64, co0, p.qsets + (size_t)qset * 192, ux, uy, (unsigned)d.mcu_cols, d.x, d.y, d.w, d.h,
+             px0 + (p.swap_rb ? 2 : 0), px0 + 1, px0 + (p.swap_rb ? 0 : 2), p.row_stride, p.swap_rb != 0,
+             ORIENT ? (int)((unsigned)d.qset >> kWindowOrientShift) : 0 };
 }
 
-template <int N, int PIX>
+template <int N, int PIX, bool ORIENT>
 __global__ __launch_bounds__(kThreads) void region_kernel(RegionDecParams p)
 {
     constexpr int NN = N * N;
     __shared__ int dct[kMaxBlocks * NN];          // dequantised corner of every block, [block][v * N + u]
     __shared__ int smp[kMaxBlocks * NN];          // samples, [block][y * N + x]
-    decode_mcu_window<N, PIX, false>(p, region_view(p), SmoothView{}, dct, smp, nullptr);
+    decode_mcu_window<N, PIX, false, ORIENT>(p, region_view<ORIENT>(p), SmoothView{}, dct, smp, nullptr);
 }
 
-template <int N, int PIX>
+template <int N, int PIX, bool ORIENT>
 __global__ __launch_bounds__(kThreads) void region_smooth_kernel(RegionDecParams p, SmoothView sv)
 {
     constexpr int NN = N * N;
     __shared__ int dct[kMaxBlocks * NN];
     __shared__ int smp[kMaxBlocks * NN];
     __shared__ int tile[3 * tile_ints(N)];        // per smoothed component: its rectangle of P_s and the ring, clamped to bytes
-    decode_mcu_window<N, PIX, true>(p, region_view(p), sv, dct, smp, tile);
+    decode_mcu_window<N, PIX, true, ORIENT>(p, region_view<ORIENT>(p), sv, dct, smp, tile);
 }
 
 // PIX: 3 / 4 only -- the batch has no plane form, and no <N, 0> instance exists
-template <int N, int PIX>
+template <int N, int PIX, bool ORIENT>
 __global__ __launch_bounds__(kThreads) void windows_kernel(WindowsParams p)
 {
     constexpr int NN = N * N;
@@ -340,11 +421,11 @@ __global__ __launch_bounds__(kThreads) void windows_kernel(WindowsParams p)
     // (uniform by construction; readfirstlane tells the compiler so, and the descriptor is then read with scalar loads)
     const unsigned fi = (unsigned)__builtin_amdgcn_readfirstlane((int)find_file(p.desc, p.n_desc, wg));
     const WindowDesc d = p.desc[fi];
-    decode_mcu_window<N, PIX, false>(p, windows_view(p, d, wg), SmoothView{}, dct, smp, nullptr);
+    decode_mcu_window<N, PIX, false, ORIENT>(p, windows_view<ORIENT>(p, d, wg), SmoothView{}, dct, smp, nullptr);
 }
 
 // WindowDesc::pad = { Ws, Hs } of the file at the launch's scale (windows_kernel does not read them)
-template <int N, int PIX>
+template <int N, int PIX, bool ORIENT>
 __global__ __launch_bounds__(kThreads) void windows_smooth_kernel(WindowsParams p, SmoothFactors sf)
 {
     constexpr int NN = N * N;
@@ -361,7 +442,7 @@ __global__ __launch_bounds__(kThreads) void windows_smooth_kernel(WindowsParams 
         sv.wc[c] = sf.fx[c] ? ((int)d.pad[0] + sf.fx[c] - 1) / sf.fx[c] : 1;
         sv.hc[c] = sf.fx[c] ? ((int)d.pad[1] + sf.fy[c] - 1) / sf.fy[c] : 1;
     }
-    decode_mcu_window<N, PIX, true>(p, windows_view(p, d, wg), sv, dct, smp, tile);
+    decode_mcu_window<N, PIX, true, ORIENT>(p, windows_view<ORIENT>(p, d, wg), sv, dct, smp, tile);
 }
 
 // ---- launchers ----
@@ -382,11 +463,15 @@ bool smooth_factors(const Params& p, SmoothFactors* sf)
     return true;
 }
 
+// q.orient != 0: the ORIENT instances; the un-oriented ones are launched exactly as they were
 template <int N, int PIX>
 void launch_region_pix(const RegionDecParams& q, const SmoothView* sv, const dim3& grid, hipStream_t s)
 {
-    if (sv) hipLaunchKernelGGL((region_smooth_kernel<N, PIX>), grid, dim3(kThreads), 0, s, q, *sv);
-    else hipLaunchKernelGGL((region_kernel<N, PIX>), grid, dim3(kThreads), 0, s, q);
+    if (q.orient) {
+        if (sv) hipLaunchKernelGGL((region_smooth_kernel<N, PIX, true>), grid, dim3(kThreads), 0, s, q, *sv);
+        else hipLaunchKernelGGL((region_kernel<N, PIX, true>), grid, dim3(kThreads), 0, s, q);
+    } else if (sv) hipLaunchKernelGGL((region_smooth_kernel<N, PIX, false>), grid, dim3(kThreads), 0, s, q, *sv);
+    else hipLaunchKernelGGL((region_kernel<N, PIX, false>), grid, dim3(kThreads), 0, s, q);
 }
 
 template <int N>
@@ -397,18 +482,21 @@ void launch_region(const RegionDecParams& q, const SmoothView* sv, const dim3& g
     else launch_region_pix<N, 0>(q, sv, grid, s);
 }
 
-template <int N, int PIX>
+template <int N, int PIX, bool ORIENT>
 void launch_windows_pix(const WindowsParams& q, const SmoothFactors* sf, unsigned n_wg, hipStream_t s)
 {
-    if (sf) hipLaunchKernelGGL((windows_smooth_kernel<N, PIX>), dim3(n_wg), dim3(kThreads), 0, s, q, *sf);
-    else hipLaunchKernelGGL((windows_kernel<N, PIX>), dim3(n_wg), dim3(kThreads), 0, s, q);
+    if (sf) hipLaunchKernelGGL((windows_smooth_kernel<N, PIX, ORIENT>), dim3(n_wg), dim3(kThreads), 0, s, q, *sf);
+    else hipLaunchKernelGGL((windows_kernel<N, PIX, ORIENT>), dim3(n_wg), dim3(kThreads), 0, s, q);
 }
 
 template <int N>
-void launch_windows(const WindowsParams& q, const SmoothFactors* sf, unsigned n_wg, hipStream_t s)
+void launch_windows(const WindowsParams& q, const SmoothFactors* sf, unsigned n_wg, hipStream_t s, bool oriented)
 {
-    if (q.pix_bytes == 3) launch_windows_pix<N, 3>(q, sf, n_wg, s);
-    else launch_windows_pix<N, 4>(q, sf, n_wg, s);
+    if (oriented) {
+        if (q.pix_bytes == 3) launch_windows_pix<N, 3, true>(q, sf, n_wg, s);
+        else launch_windows_pix<N, 4, true>(q, sf, n_wg, s);
+    } else if (q.pix_bytes == 3) launch_windows_pix<N, 3, false>(q, sf, n_wg, s);
+    else launch_windows_pix<N, 4, false>(q, sf, n_wg, s);
 }
 
 // sv: null = replicated chroma.  The frame index is grid.z: batches above 65,535 frames go out as several launches.
@@ -435,17 +523,17 @@ hipError_t launch_region_frames(const RegionDecParams& p, const SmoothView* sv, 
 // sf: null = replicated chroma.  total_wg: the workgroups of the call, desc[k].wg0 counted from 0.  A launch takes at most 2^24 - 1 of them
 // -- far below 2^31, and its global size (workgroups x 256 threads) stays below 2^32 --, larger calls go out as several launches that start
 // at wg_base.
-hipError_t launch_windows_workgroups(const WindowsParams& p, const SmoothFactors* sf, unsigned long long total_wg, hipStream_t s)
+hipError_t launch_windows_workgroups(const WindowsParams& p, const SmoothFactors* sf, unsigned long long total_wg, hipStream_t s, bool oriented)
 {
     constexpr unsigned long long per = (1ull << 24) - 1;
     for (unsigned long long w0 = 0; w0 < total_wg; w0 += per) {
         WindowsParams q = p;
         q.wg_base = (unsigned)w0;
         const unsigned n_wg = (unsigned)(total_wg - w0 < per ? total_wg - w0 : per);
-        if (p.log2n == 3) launch_windows<8>(q, sf, n_wg, s);
-        else if (p.log2n == 2) launch_windows<4>(q, sf, n_wg, s);
-        else if (p.log2n == 1) launch_windows<2>(q, sf, n_wg, s);
-        else launch_windows<1>(q, sf, n_wg, s);
+        if (p.log2n == 3) launch_windows<8>(q, sf, n_wg, s, oriented);
+        else if (p.log2n == 2) launch_windows<4>(q, sf, n_wg, s, oriented);
+        else if (p.log2n == 1) launch_windows<2>(q, sf, n_wg, s, oriented);
+        else launch_windows<1>(q, sf, n_wg, s, oriented);
         if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
     }
     return hipSuccess;
@@ -480,22 +568,22 @@ hipError_t launch_dequant_idct_region_smooth(const RegionDecParams& p, int Ws, i
     return region::launch_region_frames(p, &sv, s);
 }
 
-hipError_t launch_dequant_idct_windows(const WindowsParams& p, unsigned long long total_wg, hipStream_t s)
+hipError_t launch_dequant_idct_windows(const WindowsParams& p, unsigned long long total_wg, hipStream_t s, bool oriented)
 {
     if (p.log2n < 0 || p.log2n > 3 || p.blocks_per_mcu < 1 || p.blocks_per_mcu > region::kMaxBlocks) return hipErrorInvalidValue;
     if ((p.pix_bytes != 3 && p.pix_bytes != 4) || p.n_desc < 1 || total_wg < 1 || total_wg > 0xFFFFFFFFull) return hipErrorInvalidValue;
-    return region::launch_windows_workgroups(p, nullptr, total_wg, s);
+    return region::launch_windows_workgroups(p, nullptr, total_wg, s, oriented);
 }
 
 // launch_dequant_idct_windows' checks and launch loop; every descriptor carries its file's Ws, Hs in pad[0], pad[1] (the caller's to set and
 // to keep inside the file's MCU grid)
-hipError_t launch_dequant_idct_windows_smooth(const WindowsParams& p, unsigned long long total_wg, hipStream_t s)
+hipError_t launch_dequant_idct_windows_smooth(const WindowsParams& p, unsigned long long total_wg, hipStream_t s, bool oriented)
 {
     if (p.log2n < 0 || p.log2n > 3 || p.blocks_per_mcu < 1 || p.blocks_per_mcu > region::kMaxBlocks) return hipErrorInvalidValue;
     if ((p.pix_bytes != 3 && p.pix_bytes != 4) || p.n_desc < 1 || total_wg < 1 || total_wg > 0xFFFFFFFFull) return hipErrorInvalidValue;
     region::SmoothFactors sf;
     if (!region::smooth_factors(p, &sf)) return hipErrorInvalidValue;
-    return region::launch_windows_workgroups(p, &sf, total_wg, s);
+    return region::launch_windows_workgroups(p, &sf, total_wg, s, oriented);
 }
 
 }  // namespace jpezy_dev

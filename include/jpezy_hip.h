@@ -979,7 +979,8 @@ int jpezy_decode_jpeg_ycc(jpezy_ctx* ctx, const uint8_t* data, size_t len, jpezy
  * with the decimation step left out.
  *
  *   sampling      JPEZY_SAMPLING_420 = 0: the entry of the same name without _sampling, gray passed on -- the same kernels, the same bytes.
- *                 JPEZY_SAMPLING_444 = 1: below.  Any other value: JPEZY_E_BADARG.
+ *                 JPEZY_SAMPLING_444 = 1: below.  JPEZY_SAMPLING_422 = 3: the block behind this one.  Any other value: JPEZY_E_BADARG
+ *                 (2 is kept free for 4:4:0, the layout a transposed 4:2:2 file would have).
  *   MCU           8 x 8 pixels; mcu_cols = ceil(W / 8), mcu_rows = ceil(H / 8); three blocks in the order Y, Cb, Cr.  The picture is
  *                 extended to whole MCUs by clamping pixel coordinates (min(x, W-1), min(y, H-1)) as make_YCC does
  *                 (encoder/jpezy_encoder.hpp:101,104).
@@ -1006,10 +1007,33 @@ int jpezy_decode_jpeg_ycc(jpezy_ctx* ctx, const uint8_t* data, size_t len, jpezy
  *
  * jpezy_encode_jpeg_sampling[_packed] run both stages on the GPU: the transform kernel, then jpezy_write_jpeg_gpu_sampling (the 4:2:0
  * entries' streaming upload in MCU-row bands is not built for 4:4:4: the picture goes up in one piece).
- * NOT provided for 4:4:4: the multi-GPU handle; planar YCbCr 4:4:4 INPUT; 4:2:2 / 4:4:0; gray; encode variant 0.
+ * NOT provided for 4:4:4: the multi-GPU handle; planar YCbCr 4:4:4 INPUT; 4:4:0; gray; encode variant 0.
+ *
+ * JPEZY_SAMPLING_422 = 3 (2x1 / 1x1 / 1x1: full vertical chroma resolution, half the horizontal).  The definition is this project's own,
+ * as for 4:4:4; everything said above holds except:
+ *
+ *   MCU           16 x 8 pixels; mcu_cols = ceil(W / 16), mcu_rows = ceil(H / 8); four blocks in the order Y-left, Y-right, Cb, Cr;
+ *                 the same clamped extension to whole MCUs.
+ *   Samples       Y of every pixel.  Point sampling (the default): chroma sample (x', y) is the Cb / Cr of pixel (min(2 x', W-1),
+ *                 min(y, H-1)) -- the reference's decimation rule (make_YCC:134-142) in the horizontal direction only.
+ *                 JPEZY_DOWNSAMPLE_AVERAGE (jpezy_ctx_set_chroma_downsampling) is honoured: (c[y][2x'] + c[y][2x'+1] + bias(x')) >> 1
+ *                 over the per-pixel samples of the clamped extension, bias 0 for even x', 1 for odd x', arithmetic shift: libjpeg's
+ *                 h2v1_downsample carried over to signed samples (adding 128 to both inputs adds 128 to the result).
+ *   Coefficients  int16 [frame][mcu_y][mcu_x][4][64]: 256 * mcu_cols * mcu_rows elements per frame.
+ *   File          SOF0 states H, V = 2,1 / 1,1 / 1,1; the scan's MCUs hold four blocks, the two luma blocks with the luma Huffman
+ *                 tables and one running predictor, Cb and Cr with the chroma ones; restart intervals are counted in 16 x 8 MCUs.
+ *   Bound         jpezy_jpeg_bound_sampling: 1024 + 1792 per 16 x 8 MCU (four blocks of at most 1661 bits = 831 bytes, 1662 stuffed,
+ *                 plus restart / pad / EOI).
+ *   Refused       gray != 0 (JPEZY_E_BADARG); encode variant 0 (JPEZY_E_UNSUPPORTED; the context stays usable).
+ *   Alignment     none required.  W % 16 == 0 with 16-byte aligned planes and plane stride (packed: 16-byte aligned base and strides)
+ *                 takes the 16-byte (48 / 64-byte) load form.
+ * NOT provided for 4:2:2: the multi-GPU handle; planar YCbCr 4:2:2 or YUY2 / UYVY INPUT; 4:4:0; gray; encode variant 0; the lossless
+ * transforms (jpezy_transform_jpeg refuses a 2x1 file, jpezy_transform_geometry / jpezy_coeff_transform_dev answer JPEZY_E_BADARG for any
+ * sampling other than 0 and 1).
  */
 #define JPEZY_SAMPLING_420 0
 #define JPEZY_SAMPLING_444 1
+#define JPEZY_SAMPLING_422 3   /* 2 is kept free for 4:4:0 and refused */
 /* mcu_cols, mcu_rows, blocks_per_mcu (any may be NULL) of a W x H frame; pure host functions.  The counts are 0 for a bad argument. */
 int jpezy_sampling_geometry(int sampling, int W, int H, int* mcu_cols, int* mcu_rows, int* blocks_per_mcu);
 size_t jpezy_coeff_count_sampling(int W, int H, int sampling);   /* int16 elements per frame */
@@ -1065,6 +1089,7 @@ long jpezy_encode_jpeg_sampling_packed(jpezy_ctx* ctx, const uint8_t* pix, int f
  *   Acts on       every colour 4:2:0 RGB transform of the context: jpezy_fdct_quant[_dev], jpezy_fdct_quant_packed_dev,
  *                 jpezy_encode_jpeg[_packed], and the *_sampling* entries called with JPEZY_SAMPLING_420, which forward to those.
  *                 The setting is read when a transform is launched; no device table changes, so the setter waits for nothing.
+ *   4:2:2         JPEZY_SAMPLING_422 consults the setting too, with its own horizontal-only rule (CHROMA SAMPLING above).
  *   Not consulted gray != 0 (no chroma is computed); JPEZY_SAMPLING_444 (nothing is decimated); the planar-YCbCr entries (*_ycc*:
  *                 the caller's chroma samples are the file's); the lossless transforms.  None of them changes a byte.
  *   Refused       any other mode: JPEZY_E_BADARG.  A colour 4:2:0 RGB transform with encode variant 0 (the FP64 kernel has no averaged

@@ -26,7 +26,7 @@ DEVICE = ["--offload-arch=gfx950", "-fno-slp-vectorize"]
 # tools/ab/ab_build.py build them in (-DJPEZY_WITH_LAB); jpezy_ctx_set_variant(ctx, 2) says JPEZY_E_UNSUPPORTED otherwise.
 LAB_SOURCES = [CSRC / "jpezy_kernels_f32_ps.hip"]
 LAB_FLAGS = ["-DJPEZY_WITH_LAB"]
-LIB_SOURCES = [CSRC / "jpezy_kernels_f64.hip", CSRC / "jpezy_kernels_decode.hip", CSRC / "jpezy_kernels_f32.hip", CSRC / "jpezy_kernels_f32_444.hip", CSRC / "jpezy_kernels_f32_avg.hip", CSRC / "jpezy_kernels_generic.hip", CSRC / "jpezy_kernels_scaled.hip", CSRC / "jpezy_kernels_region.hip", CSRC / "jpezy_kernels_resized.hip", CSRC / "jpezy_kernels_resized_tensor.hip", CSRC / "jpezy_kernels_transform.hip", CSRC / "jpezy_kernels_smooth.hip",
+LIB_SOURCES = [CSRC / "jpezy_kernels_f64.hip", CSRC / "jpezy_kernels_decode.hip", CSRC / "jpezy_kernels_f32.hip", CSRC / "jpezy_kernels_f32_444.hip", CSRC / "jpezy_kernels_f32_422.hip", CSRC / "jpezy_kernels_f32_avg.hip", CSRC / "jpezy_kernels_generic.hip", CSRC / "jpezy_kernels_scaled.hip", CSRC / "jpezy_kernels_region.hip", CSRC / "jpezy_kernels_resized.hip", CSRC / "jpezy_kernels_resized_tensor.hip", CSRC / "jpezy_kernels_transform.hip", CSRC / "jpezy_kernels_smooth.hip",
                CSRC / "jpezy_entropy.hip", CSRC / "jpezy_huffstat.hip", CSRC / "jpezy_huffdec.hip",
                CSRC / "jpezy_capi.hip", CSRC / "jpezy_capi_entropy.hip", CSRC / "jpezy_capi_huffdec.hip", CSRC / "jpezy_capi_decode_batch.hip", CSRC / "jpezy_capi_multi.hip", CSRC / "jpezy_capi_packed.hip", CSRC / "jpezy_capi_scaled.hip", CSRC / "jpezy_capi_region.hip", CSRC / "jpezy_capi_windows.hip", CSRC / "jpezy_capi_resized.hip", CSRC / "jpezy_capi_ycc.hip", CSRC / "jpezy_capi_sampling.hip", CSRC / "jpezy_capi_transform.hip", CSRC / "jpezy_capi_smooth.hip",
                CSRC / "jpezy_host_codec.cpp"]

@@ -234,7 +234,8 @@ ORIENT_FROM_FILE = 0        # JPEZY_ORIENT_FROM_FILE: the orientation argument o
 # chroma sampling of the encoder's *_sampling entry points: 4:2:0 (the reference's 2x2 / 1x1 / 1x1, everything as without the keyword)
 # or 4:4:4 (8 x 8 MCUs of Y, Cb, Cr, no decimation; include/jpezy_hip.h has the definition)
 SAMPLING_420, SAMPLING_444 = 0, 1
-DOWNSAMPLE_POINT, DOWNSAMPLE_AVERAGE = 0, 1     # Context.set_chroma_downsampling: how 4:2:0 chroma is made from RGB pixels
+SAMPLING_422 = 3                               # 2x1 / 1x1 / 1x1: 16 x 8 MCUs of Y, Y, Cb, Cr (2 is kept free for 4:4:0 and refused)
+DOWNSAMPLE_POINT, DOWNSAMPLE_AVERAGE = 0, 1     # Context.set_chroma_downsampling: how 4:2:0 and 4:2:2 chroma is made from RGB pixels
 
 # enum jpezy_pixel_format: packed (interleaved) pixels, 3 or 4 bytes each
 PIX_RGB24, PIX_BGR24, PIX_RGBA32, PIX_BGRA32 = 0, 1, 2, 3
@@ -302,14 +303,15 @@ def mcu_grid(W, H):
 def coeff_count(W, H, gray=False, sampling=SAMPLING_420):
     if sampling != SAMPLING_420:
         if gray:
-            raise JpezyError("coeff_count: gray is not available with SAMPLING_444")
+            raise JpezyError("coeff_count: gray is not available with SAMPLING_444 / SAMPLING_422")
         sampling_geometry(sampling, W, H)
         return load_library().jpezy_coeff_count_sampling(W, H, int(sampling))
     return load_library().jpezy_coeff_count(W, H, int(gray))
 
 
 def sampling_geometry(sampling, W, H):
-    """(mcu_cols, mcu_rows, blocks_per_mcu) of a W x H frame: 16 x 16 MCUs of 6 blocks (SAMPLING_420) or 8 x 8 MCUs of 3 (SAMPLING_444)"""
+    """(mcu_cols, mcu_rows, blocks_per_mcu) of a W x H frame: 16 x 16 MCUs of 6 blocks (SAMPLING_420), 8 x 8 MCUs of 3 (SAMPLING_444)
+    or 16 x 8 MCUs of 4 (SAMPLING_422)"""
     mc, mr, bpm = C.c_int(), C.c_int(), C.c_int()
     _check(load_library().jpezy_sampling_geometry(int(sampling), W, H, C.byref(mc), C.byref(mr), C.byref(bpm)))
     return mc.value, mr.value, bpm.value
@@ -561,8 +563,8 @@ class Context:
     def set_chroma_downsampling(self, mode):
         """DOWNSAMPLE_POINT (default): Cb and Cr of the top-left pixel of every 2x2, the reference's rule; DOWNSAMPLE_AVERAGE: the
         floor-averaged 2x2 with libjpeg's alternating bias (include/jpezy_hip.h, CHROMA DOWNSAMPLING).  Acts on every colour 4:2:0
-        RGB transform of the context (fdct_quant[_dev], fdct_quant_packed_dev, encode_jpeg[_packed]); gray, SAMPLING_444 and the
-        planar-YCbCr entries do not consult it.  Refused with encode variant 0 when such a transform is launched."""
+        RGB transform of the context (fdct_quant[_dev], fdct_quant_packed_dev, encode_jpeg[_packed]) and, with its own horizontal
+        (h2v1) rule, on every SAMPLING_422 one; gray, SAMPLING_444 and the planar-YCbCr entries do not consult it.  Refused with encode variant 0 when such a transform is launched."""
         _check(load_library().jpezy_ctx_set_chroma_downsampling(self._h, int(mode)))
 
     def chroma_downsampling(self):
@@ -678,7 +680,7 @@ class Context:
     def write_jpeg_gpu(self, d_coeffs, W, H, gray=False, comment=None, n_frames=1, sampling=SAMPLING_420, raise_on_error=True):
         """Device coefficients (torch int16 tensor, the output of fdct_quant_dev; its producing stream must be
         synchronised) -> list of .jpg bytes, Huffman coding + bit packing + byte stuffing on the GPU.
-        sampling=SAMPLING_444: coefficients of 3-block MCUs; raise_on_error=False (that form only): a frame that failed is its negative
+        sampling=SAMPLING_444 / SAMPLING_422: coefficients of 3- / 4-block MCUs; raise_on_error=False (that form only): a frame that failed is its negative
         status in the list instead of an exception for the whole call."""
         lib = load_library()
         if comment is None:
@@ -990,7 +992,8 @@ class Context:
         return load_library().jpezy_ctx_last_huffdec_passes(self._h)
 
     def encode_jpeg(self, r, g, b, W, H, gray=False, comment=None, sampling=SAMPLING_420):
-        """Host planes -> .jpg bytes, both stages on the GPU (encoder::encode end to end).  sampling=SAMPLING_444: a 4:4:4 file."""
+        """Host planes -> .jpg bytes, both stages on the GPU (encoder::encode end to end).  sampling=SAMPLING_444: a 4:4:4 file; SAMPLING_422: a 4:2:2 file
+        (the context's chroma-downsampling setting acts on it)."""
         lib = load_library()
         r, g, b = (np.ascontiguousarray(p, dtype=np.uint8).reshape(-1) for p in (r, g, b))
         if not (r.size == g.size == b.size == W * H):
@@ -1411,7 +1414,8 @@ def write_jpeg(coeffs, W, H, gray=False, comment=None, optimize=False, restart_i
     optimal Huffman tables instead of Annex K (same coefficients, smaller file); restart_interval: MCUs per restart interval
     (DRI segment, RSTn markers, predictors reset), 0 for none; quant_tables = (luma, chroma): the tables the DQT segments state
     (64 entries each, natural order, 1..255) instead of Annex K -- the coefficients are written as they are.
-    sampling=SAMPLING_444: coefficients of 8 x 8 MCUs of Y, Cb, Cr (coeff_count(W, H, sampling=SAMPLING_444)), a 4:4:4 file."""
+    sampling=SAMPLING_444: coefficients of 8 x 8 MCUs of Y, Cb, Cr (coeff_count(W, H, sampling=SAMPLING_444)), a 4:4:4 file;
+    SAMPLING_422: 16 x 8 MCUs of Y, Y, Cb, Cr, a 4:2:2 file."""
     lib = load_library()
     coeffs = np.ascontiguousarray(coeffs, dtype=np.int16)
     if sampling != SAMPLING_420:

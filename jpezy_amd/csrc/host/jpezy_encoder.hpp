@@ -25,9 +25,9 @@ struct encoder {
 
     static constexpr int block_size = 8;
 
-    // sampling (not in the reference, which writes 2x2 / 1x1 / 1x1 only): JPEZY_SAMPLING_420, or JPEZY_SAMPLING_444 -- a colour file of
-    // 8 x 8 MCUs without chroma decimation (jpezy_encode_jpeg_sampling; include/jpezy_hip.h has the definition); 4:4:4 with GRAY_MODE is
-    // refused with the library's message.  Quality, optimised tables, restart intervals and the chroma filter
+    // sampling (not in the reference, which writes 2x2 / 1x1 / 1x1 only): JPEZY_SAMPLING_420, JPEZY_SAMPLING_444 -- a colour file of
+    // 8 x 8 MCUs without chroma decimation -- or JPEZY_SAMPLING_422 -- 16 x 8 MCUs, chroma decimated horizontally only
+    // (jpezy_encode_jpeg_sampling; include/jpezy_hip.h has the definitions); either with GRAY_MODE is refused.  Quality, optimised tables, restart intervals and the chroma filter
     // (jpezy_ctx_set_chroma_downsampling: point or averaged 2x2) are settings of detail::device_context(), the context every encoder shares.
     template <class MODE_TAG = COLOR_MODE>
     std::size_t encode(const char* output_file, int sampling = JPEZY_SAMPLING_420)
@@ -39,8 +39,10 @@ struct encoder {
             throw std::runtime_error("encode");
         std::FILE* fp = std::fopen(output_file, "wb");
         if (!fp) throw std::runtime_error("write_header");          // jpezy_writer::write_header (:22-23)
-        if (sampling != JPEZY_SAMPLING_420 && (gray || sampling != JPEZY_SAMPLING_444))
-            throw std::runtime_error(gray ? "encode: gray is not available with 4:4:4 sampling" : "encode: unknown sampling");
+        if (sampling != JPEZY_SAMPLING_420 && (gray || (sampling != JPEZY_SAMPLING_444 && sampling != JPEZY_SAMPLING_422)))
+            throw std::runtime_error(gray ? (sampling == JPEZY_SAMPLING_422 ? "encode: gray is not available with 4:2:2 sampling"
+                                                                             : "encode: gray is not available with 4:4:4 sampling")
+                                          : "encode: unknown sampling");
         std::vector<std::uint8_t> out(jpezy_jpeg_bound_sampling(W, H, sampling));
         long n = 0;
         {
@@ -49,7 +51,7 @@ struct encoder {
         try {
             raii_messenger mes("Encoding ...");
             jpezy_ctx* ctx = detail::device_context();
-            if (sampling == JPEZY_SAMPLING_444) {
+            if (sampling != JPEZY_SAMPLING_420) {
                 n = jpezy_encode_jpeg_sampling(ctx, reinterpret_cast<const std::uint8_t*>(r.data()), reinterpret_cast<const std::uint8_t*>(g.data()),
                                                reinterpret_cast<const std::uint8_t*>(b.data()), W, H, sampling, 0,
                                                pr.template get<property::At::Comment>().c_str(), out.data(), out.size());

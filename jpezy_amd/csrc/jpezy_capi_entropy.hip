@@ -72,12 +72,12 @@ int ensure_code_tables(jpezy_ctx* c, hipStream_t s)
 }
 
 // restart: the context's setting; an interval that holds the whole frame changes the header alone, so the device is told of none
-// sampling: JPEZY_SAMPLING_420 (gray or colour) or JPEZY_SAMPLING_444 (colour; the callers have refused gray) -- the job's MCU layout
+// sampling: JPEZY_SAMPLING_420 (gray or colour) or JPEZY_SAMPLING_444 / _422 (colour; the callers have refused gray) -- the job's MCU layout
 void make_job(jpezy_dev::entropy::Job& job, const int16_t* d_coeffs, int W, int H, int gray, int F, const jpezy_dev::entropy::CodeTables* tables,
               int restart, int sampling = JPEZY_SAMPLING_420)
 {
     const jpezy_host::McuLayout L = jpezy_host::mcu_layout(sampling, gray != 0);
-    const size_t n_mcu = (size_t)((W + L.mcu_px - 1) / L.mcu_px) * (size_t)((H + L.mcu_px - 1) / L.mcu_px);
+    const size_t n_mcu = (size_t)((W + L.mcu_w - 1) / L.mcu_w) * (size_t)((H + L.mcu_h - 1) / L.mcu_h);
     job.restart = restart > 0 && (size_t)restart < n_mcu ? (unsigned)restart : 0u;
     job.coeffs = d_coeffs;
     job.coeffs_per_frame = n_mcu * (size_t)L.stored * 64;

@@ -292,7 +292,7 @@ JPEZY_INTERNAL int jpezy_internal_huffdec_streams(jpezy_ctx* c, const std::vecto
 JPEZY_INTERNAL bool jpezy_internal_build_dev_setup(jpezy_dev::huffdec::Setup& S, const jpezy_host::ScanSetup& setup, const jpezy_frame_info& info, unsigned total_blocks);
 JPEZY_INTERNAL StreamGeom jpezy_internal_stream_geom(const jpezy_frame_info& info);
 // the GPU entropy coder's entries for a sampling (jpezy_capi_entropy.hip): jpezy_write_jpeg_gpu_dev / _batch and jpezy_huffman_histogram_dev
-// are these at JPEZY_SAMPLING_420; with JPEZY_SAMPLING_444 gray is 0 (the callers refuse it) and d_coeffs holds 3-block MCUs.
+// are these at JPEZY_SAMPLING_420; with JPEZY_SAMPLING_444 / JPEZY_SAMPLING_422 gray is 0 (the callers refuse it) and d_coeffs holds 3- / 4-block MCUs.
 // luma, chroma: the tables of the header's two DQT segments for this call (natural order, entries 1..255; both null: the context's, which
 // is what every public writer passes) -- jpezy_transform_jpeg states the source file's tables without touching the context's setting
 JPEZY_INTERNAL int jpezy_internal_write_jpeg_gpu_dev(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H, int gray, int sampling, int n_frames,

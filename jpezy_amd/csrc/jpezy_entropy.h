@@ -25,15 +25,15 @@ struct Job {
     const CodeTables* tables;     // device
     size_t tables_stride = 0;     // frame f codes with tables[f * tables_stride]; 0: every frame with tables[0] (the Annex-K image)
     unsigned blocks_per_frame;    // coded blocks: `coded` per MCU (gray: the two chroma blocks are coded as zero blocks)
-    int bpm;                      // stored blocks per MCU: 6 colour, 4 gray; 3 for 4:4:4
+    int bpm;                      // stored blocks per MCU: 6 colour, 4 gray; 3 for 4:4:4; 4 for 4:2:2
     int n_frames;
     unsigned restart = 0;         // MCUs per restart interval that the DEVICE acts on: 0 for none, and 0 too for an interval that holds
                                   // the whole frame (no marker, no reset: only the header differs, and the host writes that)
     // The MCU as a layout: `coded` blocks per MCU of which the first `luma` are luma blocks, then one block each of Cb and Cr; `bpm` of
-    // them are stored.  6 / 4 (bpm 6; gray: bpm 4) is 4:2:0, 3 / 1 (bpm 3) is 4:4:4.  DC predictors: the first luma block of an MCU predicts
+    // them are stored.  6 / 4 (bpm 6; gray: bpm 4) is 4:2:0, 3 / 1 (bpm 3) is 4:4:4, 4 / 2 (bpm 4) is 4:2:2.  DC predictors: the first luma block of an MCU predicts
     // from the previous MCU's last luma block, a later luma block from the block before, a chroma block from the same index one MCU back.
     // The kernels take the pair as TEMPLATE parameters (the launchers pick the instance): the 4:2:0 instances divide by constants as
-    // they always did.  (4:2:2 would be 4 / 2; not instantiated.)
+    // they always did.
     int coded = 6, luma = 4;
 };
 
@@ -56,7 +56,7 @@ __host__ __device__ inline unsigned restart_tile_first(unsigned t, unsigned rest
     const unsigned tpi = restart_tpi<CODED>(restart);
     return (t / tpi) * (restart * CODED) + (t % tpi) * 256u;
 }
-inline unsigned restart_tpi_of(unsigned restart, unsigned coded) { return coded == 3u ? restart_tpi<3u>(restart) : restart_tpi<6u>(restart); }
+inline unsigned restart_tpi_of(unsigned restart, unsigned coded) { return coded == 3u ? restart_tpi<3u>(restart) : coded == 4u ? restart_tpi<4u>(restart) : restart_tpi<6u>(restart); }
 inline size_t restart_intervals(size_t blocks_per_frame, unsigned restart, unsigned coded = 6u) { return (blocks_per_frame / coded + restart - 1) / restart; }
 inline size_t restart_tiles(size_t blocks_per_frame, unsigned restart, unsigned coded = 6u)
 {
@@ -64,7 +64,11 @@ inline size_t restart_tiles(size_t blocks_per_frame, unsigned restart, unsigned 
     return (ni - 1) * restart_tpi_of(restart, coded) + tiles256(blocks_per_frame - (ni - 1) * restart * coded);
 }
 // the layouts the kernels are instantiated for
-inline bool layout_ok(const Job& job) { return (job.coded == 6 && job.luma == 4 && (job.bpm == 6 || job.bpm == 4)) || (job.coded == 3 && job.luma == 1 && job.bpm == 3); }
+inline bool layout_ok(const Job& job)
+{
+    return (job.coded == 6 && job.luma == 4 && (job.bpm == 6 || job.bpm == 4)) || (job.coded == 3 && job.luma == 1 && job.bpm == 3) ||
+           (job.coded == 4 && job.luma == 2 && job.bpm == 4);
+}
 // tiles of a frame, either way
 inline size_t job_tiles(const Job& job)
 {

@@ -266,7 +266,7 @@ struct DirectWriter {
 // RST (Job::restart != 0): the tiles are those of restart_tiles() -- a tile never straddles a restart interval, so an interval's bits
 // are the bits of whole tiles, and the predictors of an interval's first MCU (lanes 0..5 of its first tile) are zero.  A tile's
 // stream starts at 52 words per block in front of it in the frame, which is where the plain layout has it too.
-// CODED / LUMA: the MCU as a layout (Job::coded, Job::luma) -- 6 / 4 for 4:2:0 (gray included), 3 / 1 for 4:4:4.  With 3 blocks per MCU a
+// CODED / LUMA: the MCU as a layout (Job::coded, Job::luma) -- 6 / 4 for 4:2:0 (gray included), 3 / 1 for 4:4:4, 4 / 2 for 4:2:2.  With 3 blocks per MCU a
 // 256-block tile boundary falls inside an MCU (256 = 85 * 3 + 1): nothing special happens there, because a lane's predictor is read
 // from global memory wherever the block it names lies.
 template <bool RST, unsigned CODED = 6u, unsigned LUMA = 4u>
@@ -441,6 +441,10 @@ static_assert((unsigned)(ASM_WIN - 2) * MIN_TILE_BITS >= ASM_BITS, "assemble win
 // 4:4:4 (Job::coded = 3): a flat MCU is 6 + 4 + 4 = 14 bits, 256 consecutive blocks hold at least 85 MCUs + the cheapest block: 1194 bits
 constexpr unsigned MIN_TILE_BITS_444 = 85u * 14u + 4u;
 static_assert((unsigned)(ASM_WIN - 2) * MIN_TILE_BITS_444 >= ASM_BITS, "assemble window too small for flat 4:4:4 content");
+// 4:2:2 (Job::coded = 4): a flat MCU is 6 + 6 + 4 + 4 = 20 bits.  256 = 64 * 4, so ANY 256 consecutive blocks -- wherever in an MCU
+// the run starts -- hold each of the four positions of the MCU exactly 64 times: 64 * 20 = 1280 bits, no remainder term
+constexpr unsigned MIN_TILE_BITS_422 = 64u * 20u;
+static_assert((unsigned)(ASM_WIN - 2) * MIN_TILE_BITS_422 >= ASM_BITS, "assemble window too small for flat 4:2:2 content");
 // Per-image tables (Job::tables_stride != 0) can be shorter than Annex K: a table with one used symbol codes it in ONE bit, so a flat
 // block is at least 1 (DC) + 1 (EOB) = 2 bits and a full tile at least 512: the window is ASM_BITS / 512 + 2 = 258 tiles.
 constexpr unsigned MIN_TILE_BITS_ANY = 256u * 2u;
@@ -1130,9 +1134,12 @@ hipError_t launch_code_tiles(const Job& job, const Scratch& sc, hipStream_t s)
     if (job.restart) {
         if (job.restart > 65535u || job.blocks_per_frame % coded || job.restart >= job.blocks_per_frame / coded) return hipErrorInvalidValue;
         if (coded == 3u) hipLaunchKernelGGL((code_tiles_kernel<true, 3u, 1u>), grid, dim3(WG), 0, s, job, sc.tile_stream, sc.tile_total, sc.status);
+        else if (coded == 4u) hipLaunchKernelGGL((code_tiles_kernel<true, 4u, 2u>), grid, dim3(WG), 0, s, job, sc.tile_stream, sc.tile_total, sc.status);
         else hipLaunchKernelGGL(code_tiles_kernel<true>, grid, dim3(WG), 0, s, job, sc.tile_stream, sc.tile_total, sc.status);
     } else if (coded == 3u)
         hipLaunchKernelGGL((code_tiles_kernel<false, 3u, 1u>), grid, dim3(WG), 0, s, job, sc.tile_stream, sc.tile_total, sc.status);
+    else if (coded == 4u)
+        hipLaunchKernelGGL((code_tiles_kernel<false, 4u, 2u>), grid, dim3(WG), 0, s, job, sc.tile_stream, sc.tile_total, sc.status);
     else
         hipLaunchKernelGGL(code_tiles_kernel<false>, grid, dim3(WG), 0, s, job, sc.tile_stream, sc.tile_total, sc.status);
     return hipGetLastError();
@@ -1171,6 +1178,10 @@ hipError_t launch_assemble(const Job& job, const Scratch& sc, bool any_tables, h
     if (pieces > sc.ft_stride) return hipErrorInvalidValue;
     if (job.restart && job.coded == 3)
         hipLaunchKernelGGL(assemble_restart_kernel<3u>, grid, dim3(256), 0, s, sc.tile_stream, tiles256(job.blocks_per_frame) * (size_t)TILE_STREAM_WORDS,
+                           sc.tile_total, sc.tile_base, sc.bytes, sc.first_tile, tpf, job.restart, sc.ft_stride, sc.U, u_stride_words, sc.ff_loc,
+                           sc.ff_piece, sc.markers);
+    else if (job.restart && job.coded == 4)
+        hipLaunchKernelGGL(assemble_restart_kernel<4u>, grid, dim3(256), 0, s, sc.tile_stream, tiles256(job.blocks_per_frame) * (size_t)TILE_STREAM_WORDS,
                            sc.tile_total, sc.tile_base, sc.bytes, sc.first_tile, tpf, job.restart, sc.ft_stride, sc.U, u_stride_words, sc.ff_loc,
                            sc.ff_piece, sc.markers);
     else if (job.restart)

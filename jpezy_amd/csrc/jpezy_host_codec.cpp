@@ -160,7 +160,7 @@ inline bool put_block(BitSink& o, const int16_t* z, int& pred, const EncLut& dc,
 }
 
 void put_header(BitSink& o, int W, int H, const char* comment, const HuffTable* tabs, int restart, const uint8_t* luma, const uint8_t* chroma,
-                bool s444 = false)
+                int sampling = JPEZY_SAMPLING_420)
 {
     static const uint8_t soi_app0[] = { 0xFF, 0xD8, 0xFF, 0xE0, 0x00, 0x10, 'J', 'F', 'I', 'F', 0x00,
                                         0x01, 0x02, 0x01, 0x00, 0x60, 0x00, 0x60, 0x00, 0x00 };
@@ -187,7 +187,8 @@ void put_header(BitSink& o, int W, int H, const char* comment, const HuffTable* 
         o.raw_n(vals, (size_t)nval);
     }
     const uint8_t sof[] = { 0xFF, 0xC0, 0x00, 0x11, 0x08, (uint8_t)(H >> 8), (uint8_t)H, (uint8_t)(W >> 8), (uint8_t)W,
-                            0x03, 0x00, (uint8_t)(s444 ? 0x11 : 0x22), 0x00, 0x01, 0x11, 0x01, 0x02, 0x11, 0x01 };   // 4:4:4: H, V = 1, 1 three times
+                            0x03, 0x00, (uint8_t)(sampling == JPEZY_SAMPLING_444 ? 0x11 : sampling == JPEZY_SAMPLING_422 ? 0x21 : 0x22), 0x00,
+                            0x01, 0x11, 0x01, 0x02, 0x11, 0x01 };   // luma H, V: 2, 2; 4:4:4: 1, 1; 4:2:2: 2, 1 -- chroma 1, 1 always
     o.raw_n(sof, sizeof sof);
     if (restart > 0) {                                            // DRI: MCUs per restart interval, directly in front of SOS
         o.raw(0xFF); o.raw(0xDD); o.raw16(4); o.raw16((unsigned)restart);
@@ -213,9 +214,9 @@ size_t write_header(int W, int H, const char* comment, uint8_t* out, size_t cap,
                     const uint8_t* chroma, int sampling)
 {
     if (!comment_ok(comment) || !restart_ok(restart, comment)) return 0;
-    if (sampling != JPEZY_SAMPLING_420 && sampling != JPEZY_SAMPLING_444) return 0;
+    if (!sampling_known(sampling)) return 0;
     BitSink o(out, cap);
-    put_header(o, W, H, comment, tabs, restart, luma, chroma, sampling == JPEZY_SAMPLING_444);
+    put_header(o, W, H, comment, tabs, restart, luma, chroma, sampling);
     return o.ok() ? o.size() : 0;
 }
 
@@ -250,6 +251,13 @@ size_t jpeg_bound(int W, int H)
 
 size_t jpeg_bound_sampling(int W, int H, int sampling)
 {
+    if (sampling == JPEZY_SAMPLING_422) {
+        // Per 16 x 8 MCU of four blocks: kMaxMcuBits422 = 4 * 1661 = 6644 bits = 831 bytes, 1662 if every byte were 0xFF and stuffed; a
+        // restart interval per MCU adds at most 4 bytes, the frame's own pad and EOI 4 once: inside the 130 bytes 1662 leaves of
+        // 1792 = 4 * 64 * 7.  The header differs in one sampling byte: 1024 stands.  (static_assert: jpezy_host_codec.h)
+        const size_t nmcu = (size_t)((W + 15) / 16) * (size_t)((H + 7) / 8);
+        return 1024 + nmcu * 4 * 64 * 7;
+    }
     if (sampling != JPEZY_SAMPLING_444) return jpeg_bound(W, H);
     // The same derivation per 8 x 8 MCU of three blocks: kMaxMcuBits444 = 3 * 1661 = 4983 bits = 623 bytes, 1246 if every byte were
     // 0xFF and stuffed; a restart interval per MCU adds at most 4 bytes (pad, stuffed pad, marker), the frame's own pad and EOI 4 once:
@@ -290,7 +298,7 @@ inline bool count_block(const int16_t* z, int& pred, unsigned long long* dc, uns
 namespace {
 inline size_t layout_mcus(int W, int H, const McuLayout& L)
 {
-    return (size_t)((W + L.mcu_px - 1) / L.mcu_px) * (size_t)((H + L.mcu_px - 1) / L.mcu_px);
+    return (size_t)((W + L.mcu_w - 1) / L.mcu_w) * (size_t)((H + L.mcu_h - 1) / L.mcu_h);
 }
 bool symbol_histogram_layout(const int16_t* coeffs, int W, int H, const McuLayout& L, unsigned long long hist[4][256], int restart)
 {
@@ -319,7 +327,11 @@ bool symbol_histogram_sampling(const int16_t* coeffs, int W, int H, int sampling
     return symbol_histogram_layout(coeffs, W, H, mcu_layout(sampling, false), hist, restart);
 }
 
-int optimal_table(const unsigned long long freq_in[256], uint8_t bits_out[16], uint8_t vals[256])
+// (aligned(64): the search loops of Figure K.1 are this function's whole cost, and where they fall relative to a 64-byte line moved the
+// host side of the optimised writer by 20 % when code in front of the function grew -- 168 against 139 us per call on a 64 x 32 field,
+// the same instructions.  Starting the function on a line pins the loops' placement to the function's own code; a change INSIDE the
+// function can still move them: tools/measure/measure_optimal_table.py re-checks the figure on the CPU.)
+__attribute__((aligned(64))) int optimal_table(const unsigned long long freq_in[256], uint8_t bits_out[16], uint8_t vals[256])
 {
     // a code tree over 257 leaves is at most 256 deep (libjpeg stops at 32, which ~25 million symbols can exceed: depth d takes
     // only about Fibonacci(d + 2) of them)
@@ -373,7 +385,7 @@ int optimal_table(const unsigned long long freq_in[256], uint8_t bits_out[16], u
 }
 
 namespace {
-long write_jpeg_layout(const int16_t* coeffs, int W, int H, const McuLayout& L, const char* comment, int restart, bool optimize, uint8_t* out,
+long write_jpeg_layout(const int16_t* coeffs, int W, int H, const McuLayout& L, int sampling, const char* comment, int restart, bool optimize, uint8_t* out,
                        size_t cap, std::string* err, const uint8_t* luma, const uint8_t* chroma)
 {
     if (!coeffs || !out || W <= 0 || H <= 0 || W > 65535 || H > 65535) {
@@ -407,7 +419,7 @@ long write_jpeg_layout(const int16_t* coeffs, int W, int H, const McuLayout& L, 
     const EncTables& T = own ? *own : enc_tables();
 
     BitSink o(out, cap);
-    put_header(o, W, H, comment, optimize ? tabs : nullptr, restart, luma, chroma, L.mcu_px == 8);
+    put_header(o, W, H, comment, optimize ? tabs : nullptr, restart, luma, chroma, sampling);
 
     static const int16_t kZeroBlock[64] = { 0 };
     const size_t nmcu = layout_mcus(W, H, L);
@@ -440,17 +452,17 @@ long write_jpeg_layout(const int16_t* coeffs, int W, int H, const McuLayout& L, 
 long write_jpeg(const int16_t* coeffs, int W, int H, bool gray, const char* comment, int restart, bool optimize, uint8_t* out, size_t cap,
                 std::string* err, const uint8_t* luma, const uint8_t* chroma)
 {
-    return write_jpeg_layout(coeffs, W, H, mcu_layout(JPEZY_SAMPLING_420, gray), comment, restart, optimize, out, cap, err, luma, chroma);
+    return write_jpeg_layout(coeffs, W, H, mcu_layout(JPEZY_SAMPLING_420, gray), JPEZY_SAMPLING_420, comment, restart, optimize, out, cap, err, luma, chroma);
 }
 
 long write_jpeg_sampling(const int16_t* coeffs, int W, int H, int sampling, const char* comment, int restart, bool optimize, uint8_t* out,
                          size_t cap, std::string* err, const uint8_t* luma, const uint8_t* chroma)
 {
-    if (sampling != JPEZY_SAMPLING_420 && sampling != JPEZY_SAMPLING_444) {
+    if (!sampling_known(sampling)) {
         if (err) *err = "write_jpeg: unknown sampling";
         return JPEZY_E_BADARG;
     }
-    return write_jpeg_layout(coeffs, W, H, mcu_layout(sampling, false), comment, restart, optimize, out, cap, err, luma, chroma);
+    return write_jpeg_layout(coeffs, W, H, mcu_layout(sampling, false), sampling, comment, restart, optimize, out, cap, err, luma, chroma);
 }
 
 // ======================================================================================================

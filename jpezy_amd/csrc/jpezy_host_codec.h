@@ -25,16 +25,18 @@ size_t jpeg_bound(int W, int H);
 // ---- chroma sampling (JPEZY_SAMPLING_*, include/jpezy_hip.h) ----
 // The scan of a frame as a layout: `coded` blocks per MCU of which the first `luma` are luma blocks (luma Huffman tables, one predictor
 // running through them) and the rest one block each of Cb, Cr (chroma tables, a predictor per component); `stored` blocks per MCU lie in
-// the coefficient buffer, the coded ones beyond them are zero blocks; an MCU covers mcu_px x mcu_px pixels.
-// 4:2:0: 6 / 4 / 6 on 16 pixels, gray 6 / 4 / 4; 4:4:4: 3 / 1 / 3 on 8 pixels.  (4:2:2 would be 4 / 2 / 4; not built.)
+// the coefficient buffer, the coded ones beyond them are zero blocks; an MCU covers mcu_w x mcu_h pixels.
+// 4:2:0: 6 / 4 / 6 on 16 x 16 pixels, gray 6 / 4 / 4; 4:4:4: 3 / 1 / 3 on 8 x 8; 4:2:2: 4 / 2 / 4 on 16 x 8.
 struct McuLayout {
-    int coded, luma, stored, mcu_px;
+    int coded, luma, stored, mcu_w, mcu_h;
 };
 inline McuLayout mcu_layout(int sampling, bool gray)
 {
-    if (sampling == JPEZY_SAMPLING_444) return McuLayout{ 3, 1, 3, 8 };
-    return McuLayout{ 6, 4, gray ? 4 : 6, 16 };
+    if (sampling == JPEZY_SAMPLING_444) return McuLayout{ 3, 1, 3, 8, 8 };
+    if (sampling == JPEZY_SAMPLING_422) return McuLayout{ 4, 2, 4, 16, 8 };
+    return McuLayout{ 6, 4, gray ? 4 : 6, 16, 16 };
 }
+inline bool sampling_known(int sampling) { return sampling == JPEZY_SAMPLING_420 || sampling == JPEZY_SAMPLING_444 || sampling == JPEZY_SAMPLING_422; }
 // write_jpeg / jpeg_bound / symbol_histogram for a sampling (colour only); JPEZY_SAMPLING_420: exactly those, gray = false
 long write_jpeg_sampling(const int16_t* coeffs, int W, int H, int sampling, const char* comment, int restart, bool optimize, uint8_t* out,
                          size_t cap, std::string* err, const uint8_t* luma = nullptr, const uint8_t* chroma = nullptr);
@@ -53,7 +55,8 @@ struct HuffTable {
 // restart: MCUs per restart interval (0: none) -- a DRI segment in front of SOS; 0 is returned too for a restart interval outside
 // 0..65535 or, with one, a comment longer than JPEZY_MAX_COMMENT_RESTART
 // luma, chroma: the tables of the two DQT segments (natural order; nullptr: Annex K); the segments' length does not depend on them
-// sampling: JPEZY_SAMPLING_420 (SOF0 states 2x2, 1x1, 1x1) or JPEZY_SAMPLING_444 (1x1 three times); 0 is returned for any other value
+// sampling: JPEZY_SAMPLING_420 (SOF0 states 2x2, 1x1, 1x1), JPEZY_SAMPLING_444 (1x1 three times) or JPEZY_SAMPLING_422 (2x1, 1x1, 1x1);
+// 0 is returned for any other value
 size_t write_header(int W, int H, const char* comment, uint8_t* out, size_t cap, const HuffTable* tabs = nullptr, int restart = 0,
                     const uint8_t* luma = nullptr, const uint8_t* chroma = nullptr, int sampling = 0);
 bool restart_ok(int restart, const char* comment);
@@ -71,6 +74,9 @@ static_assert(kMaxMcuBits == 9966 && 2 * ((kMaxMcuBits + 7) / 8) + 2 + 2 <= 2688
 constexpr int kMaxMcuBits444 = 3 * kMaxBlockBits;                                     // 4983: an 8 x 8 MCU of Y, Cb, Cr
 static_assert(kMaxMcuBits444 == 4983 && 2 * ((kMaxMcuBits444 + 7) / 8) + 4 + 4 <= 1344,
               "jpeg_bound_sampling: a stuffed 4:4:4 MCU, a restart interval's pad and marker, the frame's pad and EOI within 1344 bytes");
+constexpr int kMaxMcuBits422 = 4 * kMaxBlockBits;                                     // 6644: a 16 x 8 MCU of Y, Y, Cb, Cr
+static_assert(kMaxMcuBits422 == 6644 && 2 * ((kMaxMcuBits422 + 7) / 8) + 4 + 4 <= 1792,
+              "jpeg_bound_sampling: a stuffed 4:2:2 MCU, a restart interval's pad and marker, the frame's pad and EOI within 1792 bytes");
 static_assert(kMaxDcCodeBits + 11 <= 31 && kMaxAcCodeBits + 10 <= 31, "one append of the GPU coder (code + value bits) is at most 31 bits");
 // freq[sym] -> (bits, vals) of the optimal prefix code with no code longer than 16 bits and none of all ones; returns the
 // number of symbols (those with freq != 0).  Exactly Figures K.1 - K.4, every tie in K.1 resolved toward the larger symbol

@@ -28,7 +28,8 @@ struct LdsHist {
 };
 static_assert((unsigned long long)HB * 64ull < (1ull << 32), "a workgroup's bin cannot overflow 32 bits");
 
-// CODED / LUMA: the MCU as a layout (Job::coded, Job::luma; jpezy_entropy.h) -- 6 / 4 for 4:2:0 (gray: 4 of the 6 stored), 3 / 1 for 4:4:4
+// CODED / LUMA: the MCU as a layout (Job::coded, Job::luma; jpezy_entropy.h) -- 6 / 4 for 4:2:0 (gray: 4 of the 6 stored), 3 / 1 for 4:4:4,
+// 4 / 2 for 4:2:2
 template <bool RST, unsigned CODED = 6u, unsigned LUMA = 4u>
 __global__ __launch_bounds__(HWG) void symbol_histogram_kernel(Job job, unsigned long long* hist, unsigned* status)
 {
@@ -128,6 +129,9 @@ hipError_t launch_symbol_histogram(const Job& job, unsigned long long* hist, uns
     if (job.coded == 3) {
         if (job.restart) hipLaunchKernelGGL((symbol_histogram_kernel<true, 3u, 1u>), grid, dim3(HWG), 0, s, job, hist, status);
         else hipLaunchKernelGGL((symbol_histogram_kernel<false, 3u, 1u>), grid, dim3(HWG), 0, s, job, hist, status);
+    } else if (job.coded == 4) {
+        if (job.restart) hipLaunchKernelGGL((symbol_histogram_kernel<true, 4u, 2u>), grid, dim3(HWG), 0, s, job, hist, status);
+        else hipLaunchKernelGGL((symbol_histogram_kernel<false, 4u, 2u>), grid, dim3(HWG), 0, s, job, hist, status);
     } else if (job.restart)
         hipLaunchKernelGGL(symbol_histogram_kernel<true>, grid, dim3(HWG), 0, s, job, hist, status);
     else

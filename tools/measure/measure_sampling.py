@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""4:4:4 beside 4:2:0: the transform kernel, the entropy stage and both together, on one 4096 x 4096 frame resident in device memory.
+"""4:4:4 and 4:2:2 beside 4:2:0: the transform kernel, the entropy stage and both together, on one 4096 x 4096 frame resident in device memory.
 
 Two pictures: random pixels (the benchmark's workload) and the photo-like picture of tools/measure/measure_quality.py (smooth gradients +
 mild noise).  Per sampling, the legs take turns inside every round (interleaved); median / min / max over the rounds:
@@ -10,13 +10,16 @@ mild noise).  Per sampling, the legs take turns inside every round (interleaved)
   both         fdct_quant_dev + write_jpeg_gpu_dev back to back on one stream
   opt (host)   write_jpeg_gpu with per-image Huffman tables (host-delivered form: histogram kernel, tables on the host, coder, copy),
                host clock around a call that ends synchronised
-  roofline     the transform's algorithmic traffic -- 3 bytes in and 3 (4:2:0) or 6 (4:4:4) bytes out per pixel -- over its time, as a
-               fraction of 8.0 TB/s (specification) and of 6.29 TB/s (the float4-copy figure of this GPU)
+  roofline     the transform's algorithmic traffic -- 3 bytes in and 3 (4:2:0), 4 (4:2:2) or 6 (4:4:4) bytes out per pixel -- over its
+               time, as a fraction of 8.0 TB/s (specification) and of 6.29 TB/s (the float4-copy figure of this GPU)
+
+Samplings: 420, 444, 422, and 422avg -- 4:2:2 with the context in DOWNSAMPLE_AVERAGE (the transform differs; the entropy legs see other
+coefficients of the same layout).
 
 --root DIR imports jpezy_amd from another checkout of the project (the parent commit beside this one, for the A/B of the 4:2:0 path):
-a checkout without the sampling entries runs the 4:2:0 legs only.  Nothing here is an acceptance bound.
+a checkout without a sampling runs the legs of those it has.  Nothing here is an acceptance bound.
 
-    python tools/measure/measure_sampling.py [--root DIR] [--rounds 9] [--iters 10] [--size 4096] [--samplings 420,444] [--out FILE]
+    python tools/measure/measure_sampling.py [--root DIR] [--rounds 9] [--iters 10] [--size 4096] [--samplings 420,444,422,422avg] [--out FILE]
 """
 import argparse
 import statistics
@@ -48,8 +51,10 @@ def main():
     sys.path.insert(0, str(Path(args.root).resolve()))
     import jpezy_amd as J
     W = H = args.size
-    have_444 = hasattr(J, "SAMPLING_444")
-    samplings = [s for s in args.samplings.split(",") if s == "420" or have_444]
+    # name -> (the library's constant, bytes of algorithmic traffic per pixel, MCU width, averaged chroma)
+    known = {"420": (0, 6, 16, False), "444": (getattr(J, "SAMPLING_444", None), 9, 8, False),
+             "422": (getattr(J, "SAMPLING_422", None), 7, 16, False), "422avg": (getattr(J, "SAMPLING_422", None), 7, 16, True)}
+    samplings = [s for s in args.samplings.split(",") if known[s][0] is not None]
     dev = torch.device("cuda:0")
     ctx = J.Context(0)
     lines = [f"measure_sampling: {W}x{H}, {args.rounds} interleaved rounds of {args.iters} calls per leg, {torch.cuda.get_device_name(0)}, "
@@ -61,15 +66,22 @@ def main():
         legs = {}
         state = {}
         for s in samplings:
-            kw = {} if s == "420" else {"sampling": J.SAMPLING_444}
+            const, _, mcu_w, avg = known[s]
+            kw = {} if s == "420" else {"sampling": const}
             ncoef = J.coeff_count(W, H, **kw)
-            bound = J.jpeg_bound(W, H, J.SAMPLING_444) if s == "444" else J.load_library().jpezy_jpeg_bound(W, H)
+            bound = J.jpeg_bound(W, H, const) if s != "420" else J.load_library().jpezy_jpeg_bound(W, H)
             co = torch.empty(ncoef, dtype=torch.int16, device=dev)
             out = torch.empty((1, bound), dtype=torch.uint8, device=dev)
             sizes = torch.zeros(1, dtype=torch.int64, device=dev)
-            row = (W + 15) // 16 if s == "420" else (W + 7) // 8
+            row = (W + mcu_w - 1) // mcu_w
             state[s] = (kw, co, out, sizes, row)
-            fd = lambda kw=kw, co=co: ctx.fdct_quant_dev(d[0], d[1], d[2], W, H, co, **kw)
+
+            def fd(kw=kw, co=co, avg=avg):
+                if avg:
+                    ctx.set_chroma_downsampling(J.DOWNSAMPLE_AVERAGE)
+                ctx.fdct_quant_dev(d[0], d[1], d[2], W, H, co, **kw)
+                if avg:
+                    ctx.set_chroma_downsampling(J.DOWNSAMPLE_POINT)
             en = lambda kw=kw, co=co, out=out, sizes=sizes: ctx.write_jpeg_gpu_dev(co, W, H, out, sizes, **kw)
             legs[s, "transform"] = (fd, 0, False)
             legs[s, "entropy"] = (en, 0, False)
@@ -104,7 +116,7 @@ def main():
         ctx.set_huffman_optimize(0)
         for (s, leg), v in times.items():
             med = statistics.median(v)
-            bpp = {"420": 6, "444": 9}[s]
+            bpp = known[s][1]
             roof = f"{bpp:5d} {W * H * bpp / (med * 1e-6) / 8.0e12:11.3f} {W * H * bpp / (med * 1e-6) / 6.29e12:8.3f}" if leg == "transform" else f"{'':5s} {'':11s} {'':8s}"
             size = ""
             if leg == "entropy":

@@ -1,7 +1,8 @@
 // jpezy_capi_sampling.hip -- the C-ABI of include/jpezy_hip.h, part 9: chroma sampling as an argument of the encoder's entry points.
 // JPEZY_SAMPLING_420 is the existing entry of the same name without _sampling -- the same kernels, the same bytes --; JPEZY_SAMPLING_444 is the
 // reference's per-sample arithmetic with make_YCC's decimation (encoder/jpezy_encoder.hpp:116-143) left out: 8 x 8 MCUs of Y, Cb, Cr
-// (include/jpezy_hip.h has the definition).  The transform is jpezy_kernels_f32_444.hip; the Huffman stage is the GPU entropy coder with
+// (include/jpezy_hip.h has the definition).  The transform is jpezy_kernels_f32_444.hip (the kernel body and the launcher, shared with
+// 4:2:2, are jpezy_f32_octet.h's); the Huffman stage is the GPU entropy coder with
 // the MCU layout 3 / 1 / 3 (jpezy_entropy.h, Job::coded / luma) or the host writer (jpezy_host_codec.cpp, McuLayout).
 // JPEZY_SAMPLING_422 is the same per-sample arithmetic with make_YCC's decimation applied horizontally only: 16 x 8 MCUs of Y, Y, Cb, Cr,
 // layout 4 / 2 / 4; the transform is jpezy_kernels_f32_422.hip, which also holds the averaged (h2v1) chroma stage that the context's
@@ -40,7 +41,7 @@ int check_variant(const jpezy_ctx* c, int sampling, const char* who)
 }
 
 // EncParams of a 4:4:4 / 4:2:2 launch: 8 x 8 / 16 x 8 MCUs, work units of 8 MCUs per MCU row in quads_per_row
-// (jpezy_kernels_f32_444.hip, jpezy_kernels_f32_422.hip)
+// (jpezy_f32_octet.h)
 int enc_params_sampling(jpezy_ctx* c, int sampling, int W, int H, int n_frames, int16_t* d_coeffs, hipStream_t s, EncParams* p)
 {
     if (int rc = jpezy_internal_enc_params(c, W, H, 0, n_frames, d_coeffs, s, p)) return rc;

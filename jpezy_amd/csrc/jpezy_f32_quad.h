@@ -1,7 +1,8 @@
 // jpezy_f32_quad.h -- device code of ONE quad (64 x 16 pixels, 24 blocks) of the f32 encode path, shared by the one-quad-per-wave kernel
 // (jpezy_kernels_f32.hip, encode variant 1) and the persistent kernels (jpezy_kernels_f32_ps.hip, variants 2 and 3): the packed 8-point
 // transform, the colour estimates with their guard tests, the quantiser, levels 2 and 3, and encode_quad_compute / encode_quad_store.
-// The 4:4:4 kernel (jpezy_kernels_f32_444.hip: an octet of 8 x 8 MCUs per wave) calls the same pieces below encode_quad_compute.
+// The 4:4:4 and 4:2:2 kernels (jpezy_f32_octet.h: an octet of 8 MCUs, one block high, per wave) call the same pieces below
+// encode_quad_compute.
 //
 // Level 1 (every coefficient): colour conversion as an FP32 estimate with a guard band (below), separable 8-point
 //   butterflies in FP32, written as PACKED FP32 instructions (v_pk_add/mul/fma_f32 with op_sel / neg modifiers: one
@@ -484,6 +485,39 @@ __device__ __forceinline__ void lds_column(const float* src, f2* A)
 // natural-order view of a row of samples held as fdct8p wants them: x-th sample of A[k] = (s[k], s[7-k])
 __device__ __forceinline__ float pick(const f2* A, int x) { return x < 4 ? A[x].x : A[7 - x].y; }
 
+// four samples of such a row, x0 .. x0 + 3 in natural order, as signed bytes (block_column_f64's input)
+__device__ __forceinline__ uint32_t pack4(const f2* A, int x0)
+{
+    return ((uint32_t)(int)pick(A, x0) & 0xFFu) | (((uint32_t)(int)pick(A, x0 + 1) & 0xFFu) << 8) |
+           (((uint32_t)(int)pick(A, x0 + 2) & 0xFFu) << 16) | (((uint32_t)(int)pick(A, x0 + 3) & 0xFFu) << 24);
+}
+
+// The queue-overflow evaluation of one block column by one lane: src = the block's 64 integer samples as signed bytes, row by row;
+// the lane keeps the eight running sums of its natural column j (i = 0..7) and adds (pic * cos[j][x]) * cos[i][y] for x = 0..7 to
+// each -- for every i exactly the reference's sequence (ref :146-166) -- then quantises by qt (natural order) into the staged block.
+__device__ __forceinline__ void block_column_f64(const signed char* src, int j, const int* qt, char* staged)
+{
+    const double cu = j ? 1.0 : JPEZY_S;
+    double S[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+#pragma unroll 1
+    for (int y = 0; y < 8; ++y) {
+        // x is not unrolled: this path must not raise the kernel's register count (it is never the hot one)
+#pragma unroll 1
+        for (int x = 0; x < 8; ++x) {
+            const double px = (double)(int)src[y * 8 + x] * c_cos[j * 8 + x];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) S[i] += px * c_cos[i * 8 + y];
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const double cv = i ? 1.0 : JPEZY_S;
+        const int dct = (int)(S[i] * cu * cv / 4);
+        const int qv = dct / qt[i * 8 + j];
+        *reinterpret_cast<int16_t*>(staged + 2 * (int)c_zzinv[i * 8 + j]) = (int16_t)qv;
+    }
+}
+
 // development builds (-DJPEZY_TRACE=3, tools/profile/wave_phases.py): the shader clock at the phase boundaries of every wave
 #if defined(JPEZY_TRACE) && JPEZY_TRACE >= 3
 #define PHASE_STAMP(k)                                                                                        \
@@ -751,8 +785,7 @@ __device__ __forceinline__ void encode_quad_compute(const EncParams& p, const ui
             for (int k = 0; k < 4; ++k) {
                 const f2* A = k < 2 ? YL : YR;
                 const int x0 = 4 * (k & 1);
-                w4[k] = ((uint32_t)(int)pick(A, x0) & 0xFFu) | (((uint32_t)(int)pick(A, x0 + 1) & 0xFFu) << 8) |
-                        (((uint32_t)(int)pick(A, x0 + 2) & 0xFFu) << 16) | (((uint32_t)(int)pick(A, x0 + 3) & 0xFFu) << 24);
+                w4[k] = pack4(A, x0);
             }
             const int by = row >> 3, y = row & 7;
             uint32_t* d0 = reinterpret_cast<uint32_t*>(smp + ((m * 4 + by * 2) * 64 + y * 8));
@@ -760,14 +793,14 @@ __device__ __forceinline__ void encode_quad_compute(const EncParams& p, const ui
             d0[16] = w4[2]; d0[17] = w4[3];                      // the right block, 64 bytes further
             if (!GRAY) {
 #pragma unroll
-                for (int k = 0; k < 2; ++k)
-                    w4[k] = ((uint32_t)(int)pick(CS, 4 * k) & 0xFFu) | (((uint32_t)(int)pick(CS, 4 * k + 1) & 0xFFu) << 8) |
-                            (((uint32_t)(int)pick(CS, 4 * k + 2) & 0xFFu) << 16) | (((uint32_t)(int)pick(CS, 4 * k + 3) & 0xFFu) << 24);
+                for (int k = 0; k < 2; ++k) w4[k] = pack4(CS, 4 * k);
                 uint32_t* dc = reinterpret_cast<uint32_t*>(smp + 1024 + ((m * 2 + (row & 1)) * 64 + (row >> 1) * 8));
                 dc[0] = w4[0]; dc[1] = w4[1];
             }
         }
         wave_sync();
+        // The loop body is block_column_f64's text (above), kept in place: called from here the function changes the instruction
+        // order of every 4:2:0 instance.  A change to either goes into both.
         const double cu = j ? 1.0 : JPEZY_S;
 #pragma unroll 1
         for (int bc = 0; bc < (GRAY ? 2 : 3); ++bc) {

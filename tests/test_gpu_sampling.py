@@ -1,6 +1,6 @@
 """4:4:4 chroma sampling on the GPU (include/jpezy_hip.h, CHROMA SAMPLING): the transform kernel against
 tests/sampling_model.py for equality -- planar, RGB24 and BGRA32 with a padded row stride, every force_exact level, every table set, the
-DC from the exact table --, the rare paths on a picture whose pixels sit on the colour guard bands, a batch with a padded frame stride,
+DC from the exact table --, the rare paths on a picture whose pixels sit on the colour guard bands, the queue overflow on a picture built for it, a batch with a padded frame stride,
 the end-to-end entries against the host writer, the files through our own GPU Huffman decoder, the refusals, SAMPLING_420 against the
 entries it stands for, and the GPU entropy coder on 3-block MCUs (tile seams inside an MCU, restart intervals, per-image tables, batch,
 the device-resident form, the histogram kernel) against the host writer.
@@ -13,6 +13,7 @@ from functools import lru_cache
 import numpy as np
 import pytest
 
+from exact_picture import EXACT_F, QUEUE_CAP, exact_picture
 import quant_model as QM
 import sampling_model as SM
 
@@ -161,6 +162,40 @@ def test_rare_paths_on_guard_band_pixels(J, qctx):
         _check_every_entry(J, qctx, r, g, b, W, H, want, ("guard band", name))
         if name == "q100":
             assert qctx.fallback_count() > 0
+
+
+# ---- the queue overflow, for certain ----
+def test_queue_overflow_without_the_force_hook(J, qctx):
+    """128 x 16 (four whole octets) at force_exact 0 and quality 100, tests/exact_picture.py with a chroma sample per pixel: every block
+    has 23 AC coefficients exactly on an integer -- each one on a truncation boundary at Q = 1, flagged by level 1 and queued --, 552 of an
+    octet's 1536 coefficients against a queue of 382: the queue overflows and the per-lane evaluator of the shipped instances (8-byte
+    loads, packed, and the byte loop through planes that start one byte into their allocations) runs without the hook.  Equality with
+    the model; the counter shows that every coefficient of every octet went through the evaluator."""
+    import torch
+    W, H, OCTET_COEFFS = 128, 16, 1536                                     # 24 blocks of a 4:4:4 octet
+    r, g, b, (Y, Cb, Cr) = exact_picture(W, H, 1)
+    ys, cbs, crs = SM.samples_from_rgb(r, g, b, W, H)
+    assert np.array_equal(ys, Y) and np.array_equal(cbs, Cb) and np.array_equal(crs, Cr)      # the samples ARE the pattern
+    dct = SM.dct_from_rgb(r, g, b, W, H)
+    hits = np.count_nonzero(np.array(EXACT_F)) * 24
+    assert hits > QUEUE_CAP and (np.count_nonzero(dct.reshape(-1, 64)[:, 1:], axis=1) == 23).all()
+    qctx.set_quant_tables(*QM.tables("q100"))
+    want = SM.quantise(dct, *QM.tables("q100"))
+    qctx.fallback_count()
+    entries = _dev_entries(J, qctx, r, g, b, W, H)
+    shifted = []
+    for p in (r, g, b):
+        buf = torch.full((W * H + 1,), 0xEE, dtype=torch.uint8, device="cuda")
+        buf[1:] = torch.from_numpy(p.copy()).cuda()
+        shifted.append(buf[1:])
+    co = torch.full(_shape(W, H), 0x5A5A, dtype=torch.int16, device="cuda")
+    qctx.fdct_quant_dev(*shifted, W, H, co, sampling=J.SAMPLING_444)
+    torch.cuda.synchronize()
+    entries.append(("planar base + 1", co.cpu().numpy()))
+    assert qctx.fallback_count() == len(entries) * 4 * OCTET_COEFFS        # four octets a call, each one whole through the evaluator
+    for entry, got in entries:
+        bad = np.argwhere(got != want)
+        assert bad.size == 0, (entry, len(bad), bad[:4].tolist())
 
 
 # ---- batch ----

@@ -13,6 +13,7 @@ from functools import lru_cache
 import numpy as np
 import pytest
 
+from exact_picture import EXACT_F, QUEUE_CAP, exact_picture
 import quant_model as QM
 import sampling422_model as S2
 import sampling_model as SM
@@ -228,46 +229,7 @@ def test_rare_paths_without_the_force_hook(J, qctx, mode):
 
 
 # ---- the queue overflow, for certain ----
-# an integer F that commutes with the signed permutation by which the Galois map cos t -> cos 3t acts on the rows of the DCT matrix D
-# (a signed 4-cycle on rows 1, 3, 7, 5, a signed swap of rows 2, 6, a sign flip of rows 0, 4): P = D^T F D is then rational -- here an
-# integer block with entries in -9 .. 8 -- and F = D P D^T, 23 AC entries and no DC, is its exact transform
-EXACT_F = [[0, 0, 0, 0, -16, 0, 0, 0], [0, -2, 0, 6, 0, -6, 0, 4], [0, 0, 8, 0, 0, 0, -8, 0], [0, 6, 0, -2, 0, -4, 0, -6],
-           [-8, 0, 0, 0, -16, 0, 0, 0], [0, -6, 0, 4, 0, -2, 0, -6], [0, 0, 8, 0, 0, 0, 8, 0], [0, -4, 0, -6, 0, -6, 0, -2]]
-QUEUE_CAP, UNIT_COEFFS = 382, 2048                                         # jpezy_f32_quad.h; 32 blocks of a 4:2:2 work unit
-
-
-def _rgb_for(y, cb, cr):
-    """uint8 planes whose truncated samples (the reference's FP64 order) are exactly the integer arrays y, cb, cr: a search of the 7^3
-    triples around the real inverse"""
-    r0, g0, b0 = np.round(y + 128 + 1.402 * cr), np.round(y + 128 - 0.344 * cb - 0.714 * cr), np.round(y + 128 + 1.772 * cb)
-    d = np.arange(-3, 4)
-    dr, dg, db = (a.reshape(-1) for a in np.meshgrid(d, d, d, indexing="ij"))
-    r, g, b = ((c[..., None] + e).clip(0, 255) for c, e in ((r0, dr), (g0, dg), (b0, db)))
-    ok = (np.trunc((0.2990 * r) + (0.5870 * g) + (0.1140 * b) - 128) == y[..., None]) & \
-         (np.trunc(-(0.1687 * r) - (0.3313 * g) + (0.5000 * b)) == cb[..., None]) & (np.trunc((0.5000 * r) - (0.4187 * g) - (0.0813 * b)) == cr[..., None])
-    assert ok.any(-1).all(), "a sample triple no RGB triple reaches"
-    k = ok.argmax(-1)[..., None]
-    return tuple(np.take_along_axis(c, k, -1)[..., 0].astype(np.uint8).reshape(-1) for c in (r, g, b))
-
-
-@lru_cache(maxsize=None)
-def _exact_picture(W, H):
-    """(r, g, b, samples): every luma block is k P (k = 1 .. 5 by block), every Cb block k P^T and every Cr block -k P (k = 1 .. 3); both
-    pixels of a horizontal pair carry the pair's chroma sample, so the point rule and the averaged rule see the same samples"""
-    u, x = np.arange(8)[:, None], np.arange(8)[None, :]
-    D = np.cos((2 * x + 1) * u * np.pi / 16) * 0.5
-    D[0] /= np.sqrt(2)
-    F = np.array(EXACT_F, np.float64)
-    P = D.T @ F @ D
-    assert np.abs(P - np.round(P)).max() < 1e-9 and np.abs(D @ np.round(P) @ D.T - F).max() < 1e-9
-    P = np.round(P).astype(np.int64)
-    yy, xx = np.mgrid[0:H, 0:W]
-    Y = (1 + (xx // 8 + yy // 8) % 5) * P[yy % 8, xx % 8]
-    cy, cx = np.mgrid[0:H, 0:W // 2]
-    kc = 1 + (cx // 8 + 2 * (cy // 8)) % 3
-    Cb, Cr = kc * P.T[cy % 8, cx % 8], -kc * P[cy % 8, cx % 8]
-    r, g, b = _rgb_for(Y, np.repeat(Cb, 2, 1), np.repeat(Cr, 2, 1))
-    return r, g, b, (Y, Cb, Cr)
+UNIT_COEFFS = 2048                                                         # 32 blocks of a 4:2:2 work unit
 
 
 @pytest.mark.parametrize("mode", MODES, ids=["point", "average"])
@@ -279,7 +241,7 @@ def test_queue_overflow_without_the_force_hook(J, qctx, mode):
     FP64 order does; the counter shows that every coefficient of every unit went through the evaluator."""
     import torch
     W, H = 256, 16
-    r, g, b, (Y, Cb, Cr) = _exact_picture(W, H)
+    r, g, b, (Y, Cb, Cr) = exact_picture(W, H, 2)          # both pixels of a horizontal pair carry the pair's chroma sample
     ys, cbs, crs = S2.samples_from_rgb(r, g, b, W, H, mode)
     assert np.array_equal(ys, Y) and np.array_equal(cbs, Cb) and np.array_equal(crs, Cr)      # the samples ARE the pattern, either rule
     dct = S2.dct_from_rgb(r, g, b, W, H, mode)

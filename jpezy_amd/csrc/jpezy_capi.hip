@@ -1,6 +1,9 @@
 // jpezy_capi.hip -- the C-ABI of include/jpezy_hip.h, part 1: the per-GPU context (device id, stream, device constant tables, staging
-// buffers, fallback counter) and the two transform stages.  No CPU fallback: every compute entry point needs a HIP device.
+// buffers, fallback counter) and the two transform stages: the core of every encode transform (jpezy_internal_fdct_quant_core, steered by
+// an EncodeSource), the core of the fused decode kernel (jpezy_internal_fused_dev_core, steered by a DecodeSink), the planar entries of
+// both and the any-layout decode pair.  No CPU fallback: every compute entry point needs a HIP device.
 #include "jpezy_capi_decode.h"
+#include "jpezy_capi_encode.h"
 
 extern "C" {
 
@@ -355,22 +358,6 @@ int jpezy_internal_check_dims(const jpezy_ctx* c, int W, int H, int n_frames)
     return JPEZY_OK;
 }
 
-// JPEZY_DOWNSAMPLE_AVERAGE acts on this transform: a colour 4:2:0 RGB one (the two callers: the planar and the packed entry point)
-bool jpezy_internal_averaged_chroma(const jpezy_ctx* c, int gray)
-{
-    return !gray && c->chroma_downsampling == JPEZY_DOWNSAMPLE_AVERAGE;
-}
-
-// ... and what such a transform refuses before it touches anything: encode variant 0 (the FP64 kernel has no averaged stage), the
-// rule of check_variant_444
-int jpezy_internal_check_variant_avg(const jpezy_ctx* c, bool avg, const char* who)
-{
-    if (avg && c->variant == 0)
-        return set_err(JPEZY_E_UNSUPPORTED, std::string(who) + ": encode variant 0 (FP64) has no JPEZY_DOWNSAMPLE_AVERAGE form; use variant 1 "
-                                                              "or JPEZY_DOWNSAMPLE_POINT");
-    return JPEZY_OK;
-}
-
 int jpezy_ctx_set_chroma_downsampling(jpezy_ctx* c, int mode)
 {
     if (!c) return set_err(JPEZY_E_BADARG, "null context");
@@ -386,12 +373,24 @@ int jpezy_ctx_chroma_downsampling(jpezy_ctx* c)
     return c->chroma_downsampling;
 }
 
-// Everything of EncParams that does not say where the pixels are; shared by the planar and the packed entry point.
-int jpezy_internal_enc_params(jpezy_ctx* c, int W, int H, int gray, int n_frames, int16_t* d_coeffs, hipStream_t s, EncParams* out)
+// Every encode transform: the source says where the pixels are, the sampling which MCUs they form, the context everything else.
+int jpezy_internal_fdct_quant_core(jpezy_ctx* c, const EncodeSource& src, int sampling, int W, int H, int gray, int n_frames, int16_t* d_coeffs,
+                                   hipStream_t s)
 {
-    EncParams& p = *out;
+    HIP_TRY(hipSetDevice(c->device));
+    const bool s420 = sampling == JPEZY_SAMPLING_420;
+    EncParams p;
+    p.r = src.r; p.g = src.g; p.b = src.b;
+    p.plane_stride = src.frame_stride;
+    p.pix = src.pix;
+    p.row_stride = src.row_stride;
+    p.pix_bytes = src.pix_bytes;
+    p.swap_rb = src.swap_rb;
+    p.c_row_stride = src.c_row_stride;
+    p.c_step = src.c_step;
+    p.c_frame_stride = src.c_frame_stride;
     p.coeffs = d_coeffs;
-    p.coeffs_per_frame = jpezy_coeff_count(W, H, gray);
+    p.coeffs_per_frame = s420 ? jpezy_coeff_count(W, H, gray) : jpezy_coeff_count_sampling(W, H, sampling);
     p.tab = c->d_tab.as<DeviceTables>();
     p.dcq_luma = p.tab->dcq[0];          // address arithmetic only: d_tab is a device pointer
     p.dcq_chroma = p.tab->dcq[1];
@@ -405,15 +404,53 @@ int jpezy_internal_enc_params(jpezy_ctx* c, int W, int H, int gray, int n_frames
     HIP_TRY(hipMemsetAsync(c->dump_t.p, 0, p.coeffs_per_frame * (size_t)n_frames * sizeof(float), s));
     p.dump_t = (float*)c->dump_t.p;
 #endif
-    (void)s;
     p.W = W; p.H = H;
-    p.mcu_cols = jpezy_mcu_cols(W);
-    p.mcu_rows = jpezy_mcu_rows(H);
-    p.quads_per_row = (p.mcu_cols + 3) / 4;
-    p.n_frames = n_frames;
+    // MCUs and work units per MCU row: 16 x 16 MCUs in quads of four (jpezy_f32_quad.h), or the sampling's 8 x 8 / 16 x 8 MCUs in
+    // octets of eight (jpezy_f32_octet.h)
+    if (s420) {
+        p.mcu_cols = jpezy_mcu_cols(W);
+        p.mcu_rows = jpezy_mcu_rows(H);
+        p.quads_per_row = (p.mcu_cols + 3) / 4;
+    } else {
+        jpezy_sampling_geometry(sampling, W, H, &p.mcu_cols, &p.mcu_rows, nullptr);
+        p.quads_per_row = (p.mcu_cols + 7) / 8;
+    }
     fast_div_setup((unsigned)p.quads_per_row, &p.qpr_magic, &p.qpr_shift);
     // dc_table_lookup (test hook): the launchers then take the !DCG instance and DeviceTables::dcq, as when a create-time check fails
     for (int t = 0; t < 2; ++t) { p.dc_rq[t] = c->dc_table_lookup ? 0.f : c->dc_rq[t]; p.dc_bias[t] = c->dc_table_lookup ? 0.f : c->dc_bias[t]; }
+
+    // The launcher, by (pixel kind, sampling, averaged chroma, variant).  Variant 0 is the FP64 kernel: planes, packed pixels and YCbCr at
+    // 4:2:0 with point chroma (the entries refused everything else, check_encode_variant); every other variant is the f32 kernel.  The
+    // averaged stage is read here, at launch (never YCbCr input, never 4:4:4), and 4:4:4 / 4:2:2 serve planes and packed pixels alike.
+    const bool g = gray != 0, avg = !src.is_ycc() && encode_averaged(c, sampling, gray), f64 = c->variant == 0;
+    const int force = c->force_exact;
+    auto launch = [&](const EncParams& q) -> hipError_t {
+        if (sampling == JPEZY_SAMPLING_444) return launch_fdct_quant_f32_444(q, force, s);
+        if (sampling == JPEZY_SAMPLING_422) return launch_fdct_quant_f32_422(q, force, avg, s);
+        if (src.is_ycc()) return f64 ? launch_fdct_quant_ycc(q, g, force != 0, s) : launch_fdct_quant_f32_ycc(q, g, force, s);
+        if (src.pix_bytes) {
+            if (avg) return launch_fdct_quant_f32_packed_avg(q, force, s);
+            return f64 ? launch_fdct_quant_packed(q, g, force != 0, s) : launch_fdct_quant_f32_packed(q, g, force, s);
+        }
+        if (avg) return launch_fdct_quant_f32_avg(q, force, s);
+#ifdef JPEZY_WITH_LAB
+        // the persistent kernels cover planar 4:2:0 with point chroma only, and were measured and archived with the Annex-K tables: every
+        // other frame goes to variant 1's launch
+        if (c->variant == 3 && c->qt_default) return launch_fdct_quant_f32_ps2(q, g, force, c->n_cus, s);
+        if (c->variant == 2 && c->qt_default) return launch_fdct_quant_f32_ps(q, g, force, c->n_cus, s);
+#endif
+        return f64 ? launch_fdct_quant(q, g, force != 0, s) : launch_fdct_quant_f32(q, g, force, s);
+    };
+    // the kernels put the frame index in a grid dimension: larger batches go out in chunks
+    EncodeSource at = src;
+    for (int f0 = 0; f0 < n_frames; f0 += kMaxFramesPerLaunch) {
+        EncParams q = p;
+        q.n_frames = std::min(n_frames - f0, kMaxFramesPerLaunch);
+        q.r = at.r; q.g = at.g; q.b = at.b; q.pix = at.pix;
+        q.coeffs += (size_t)f0 * p.coeffs_per_frame;
+        HIP_TRY(launch(q));
+        at.advance((size_t)q.n_frames);
+    }
     return JPEZY_OK;
 }
 
@@ -424,42 +461,9 @@ int jpezy_fdct_quant_dev(jpezy_ctx* c, const uint8_t* d_r, const uint8_t* d_g, c
     if (!d_r || !d_g || !d_b || !d_coeffs) return set_err(JPEZY_E_BADARG, "null device pointer");
     if (!aligned16(d_coeffs)) return set_err(JPEZY_E_BADARG, "d_coeffs must be 16-byte aligned");
     if (plane_stride < (size_t)W * H) return set_err(JPEZY_E_BADARG, "plane_stride smaller than W*H");
-    const bool avg = jpezy_internal_averaged_chroma(c, gray);
-    if (int rc = jpezy_internal_check_variant_avg(c, avg, "fdct_quant_dev")) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    hipStream_t s = (hipStream_t)stream;
-    EncParams p;
-    p.r = d_r; p.g = d_g; p.b = d_b;
-    p.plane_stride = plane_stride;
-    if (int rc = jpezy_internal_enc_params(c, W, H, gray, n_frames, d_coeffs, s, &p)) return rc;
-    // the f32 kernel puts the frame index in grid.y: larger batches go out in chunks
-    for (int f0 = 0; f0 < n_frames; f0 += kMaxFramesPerLaunch) {
-        EncParams q = p;
-        q.n_frames = n_frames - f0 < kMaxFramesPerLaunch ? n_frames - f0 : kMaxFramesPerLaunch;
-        q.r += (size_t)f0 * plane_stride; q.g += (size_t)f0 * plane_stride; q.b += (size_t)f0 * plane_stride;
-        q.coeffs += (size_t)f0 * p.coeffs_per_frame;
-        // JPEZY_DOWNSAMPLE_AVERAGE: the one-quad launch with the averaged chroma stage, whatever f32 variant is set (the laboratory's
-        // persistent variants 2 and 3 hand such a frame to it as they do every frame they do not cover)
-        if (avg)
-            HIP_TRY(launch_fdct_quant_f32_avg(q, c->force_exact, s));
-        else
-#ifdef JPEZY_WITH_LAB
-        // the persistent kernels were measured and archived with the Annex-K tables: a context with other tables hands its frames to
-        // variant 1's launch, as those variants do for the frames they do not cover
-        if (c->variant >= 2 && !c->qt_default)
-            HIP_TRY(launch_fdct_quant_f32(q, gray != 0, c->force_exact, s));
-        else if (c->variant == 3)
-            HIP_TRY(launch_fdct_quant_f32_ps2(q, gray != 0, c->force_exact, c->n_cus, s));
-        else if (c->variant == 2)
-            HIP_TRY(launch_fdct_quant_f32_ps(q, gray != 0, c->force_exact, c->n_cus, s));
-        else
-#endif
-        if (c->variant == 1)
-            HIP_TRY(launch_fdct_quant_f32(q, gray != 0, c->force_exact, s));
-        else
-            HIP_TRY(launch_fdct_quant(q, gray != 0, c->force_exact != 0, s));
-    }
-    return JPEZY_OK;
+    if (int rc = check_encode_variant(c, JPEZY_SAMPLING_420, gray, "fdct_quant_dev")) return rc;
+    return jpezy_internal_fdct_quant_core(c, EncodeSource::planes(d_r, d_g, d_b, plane_stride), JPEZY_SAMPLING_420, W, H, gray, n_frames, d_coeffs,
+                                          (hipStream_t)stream);
 }
 
 #ifdef JPEZY_DUMP_T
@@ -491,7 +495,7 @@ int jpezy_fdct_quant(jpezy_ctx* c, const uint8_t* r, const uint8_t* g, const uin
 try {
     if (int rc = jpezy_internal_check_dims(c, W, H, n_frames)) return rc;
     if (!r || !g || !b || !coeffs) return set_err(JPEZY_E_BADARG, "null host pointer");
-    if (int rc = jpezy_internal_check_variant_avg(c, jpezy_internal_averaged_chroma(c, gray), "fdct_quant")) return rc;   // before anything is uploaded
+    if (int rc = check_encode_variant(c, JPEZY_SAMPLING_420, gray, "fdct_quant")) return rc;   // before anything is uploaded
     HIP_TRY(hipSetDevice(c->device));
     const size_t plane = (size_t)W * H;
     const int B = gray ? 4 : 6;
@@ -500,8 +504,6 @@ try {
     size_t max_out = 0;
     for (const HostChunk& k : chunks) max_out = std::max(max_out, k.coef_bytes(W, B));
     const uint8_t* src[3] = { r, g, b };
-    int rc_kernel = JPEZY_OK;
-    std::string err;
     auto plan = [&](int i) {
         const HostChunk& k = chunks[(size_t)i];
         jpezy_host::ChunkPlan p;
@@ -509,17 +511,11 @@ try {
         p.out.push_back({ coeffs + k.coef_off(W, H, B), k.coef_bytes(W, B), 0 });
         return p;
     };
-    auto kernel = [&](int i, uint8_t* d_in, uint8_t* d_out, hipStream_t s) -> hipError_t {
+    return run_host_bands(c, chunks.size(), 3 * P, max_out, plan, [&](int i, uint8_t* d_in, uint8_t* d_out, hipStream_t s) {
         const HostChunk& k = chunks[(size_t)i];
         const int Hc = k.rows(H);
-        const int rc = jpezy_fdct_quant_dev(c, d_in, d_in + P, d_in + 2 * P, k.nf > 1 ? plane : (size_t)Hc * W, W, Hc, gray, k.nf, (int16_t*)d_out, s);
-        if (rc != JPEZY_OK) { rc_kernel = rc; return hipErrorLaunchFailure; }
-        return hipSuccess;
-    };
-    const hipError_t e = c->pipe.run(c->device, c->stream, (int)chunks.size(), 3 * P, max_out, plan, kernel, &err);
-    if (rc_kernel != JPEZY_OK) return rc_kernel;                    // message set by jpezy_fdct_quant_dev
-    if (e != hipSuccess) return set_err(JPEZY_E_HIP, err.empty() ? std::string("host pipeline: ") + hipGetErrorString(e) : err);
-    return JPEZY_OK;
+        return jpezy_fdct_quant_dev(c, d_in, d_in + P, d_in + 2 * P, k.nf > 1 ? plane : (size_t)Hc * W, W, Hc, gray, k.nf, (int16_t*)d_out, s);
+    });
 }
 JPEZY_CATCH
 
@@ -564,12 +560,15 @@ int jpezy_internal_upload_dequant(jpezy_ctx* c, const uint16_t qt[4][64], const 
     return JPEZY_OK;
 }
 
-// Everything of DecParams that does not say where the pixels go (after jpezy_internal_upload_dequant); planar and packed entry point.
-void jpezy_internal_dec_params(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H, int n_frames, DecParams* out)
+// The fused kernel over a batch: tables, parameters, the split at the launch limit, and the launch the sink asks for.
+int jpezy_internal_fused_dev_core(jpezy_ctx* c, const int16_t* d_coeffs, const uint16_t qt[4][64], const uint8_t comp_tq[3], const DecodeSink& out,
+                                  int W, int H, int gray, int n_frames, hipStream_t s)
 {
-    DecParams& p = *out;
-    p.coeffs = d_coeffs;
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = jpezy_internal_upload_dequant(c, qt, comp_tq, s)) return rc;
+    DecParams p;
     p.coeffs_per_frame = jpezy_coeff_count(W, H, 0);
+    p.plane_stride = out.frame_stride;
     p.dqscale = c->d_dqscale.as<double>();
     p.dqscale_f = c->d_dqscale_f.as<float>();
     p.dqt = c->d_dqt.as<int>();
@@ -579,7 +578,20 @@ void jpezy_internal_dec_params(jpezy_ctx* c, const int16_t* d_coeffs, int W, int
     p.mcu_cols = jpezy_mcu_cols(W);
     p.mcu_rows = jpezy_mcu_rows(H);
     p.quads_per_row = (p.mcu_cols + 3) / 4;
-    p.n_frames = n_frames;
+    p.row_stride = out.row_stride;
+    p.pix_bytes = out.pix_bytes;
+    p.swap_rb = out.pix && out.r != out.pix;                 // blue comes first
+    if (out.ycc) { p.c_row_stride = out.c_row_stride; p.c_step = out.c_step; p.c_frame_stride = out.c_frame_stride; }
+    const auto launch = out.ycc ? launch_dequant_idct_ycc : out.pix_bytes ? launch_dequant_idct_packed : launch_dequant_idct;
+    DecodeSink at = out;
+    for (int f0 = 0; f0 < n_frames; f0 += kMaxFramesPerLaunch) {
+        p.n_frames = std::min(n_frames - f0, kMaxFramesPerLaunch);
+        p.coeffs = d_coeffs + (size_t)f0 * p.coeffs_per_frame;
+        p.r = at.r; p.g = at.g; p.b = at.b; p.pix = at.pix;
+        HIP_TRY(launch(p, gray != 0, c->force_exact != 0, c->dec_tolerance != 0, s));
+        at.advance((size_t)p.n_frames);
+    }
+    return JPEZY_OK;
 }
 
 int jpezy_dequant_idct_dev(jpezy_ctx* c, const int16_t* d_coeffs, const uint16_t qt[4][64], const uint8_t comp_tq[3],
@@ -590,21 +602,8 @@ int jpezy_dequant_idct_dev(jpezy_ctx* c, const int16_t* d_coeffs, const uint16_t
     if (!d_coeffs || !qt || !comp_tq || !d_r || !d_g || !d_b) return set_err(JPEZY_E_BADARG, "null pointer");
     if (!aligned16(d_coeffs)) return set_err(JPEZY_E_BADARG, "d_coeffs must be 16-byte aligned");
     if (plane_stride < (size_t)W * H) return set_err(JPEZY_E_BADARG, "plane_stride smaller than W*H");
-    HIP_TRY(hipSetDevice(c->device));
-    hipStream_t s = (hipStream_t)stream;
-    if (int rc = jpezy_internal_upload_dequant(c, qt, comp_tq, s)) return rc;
-    DecParams p;
-    p.r = d_r; p.g = d_g; p.b = d_b;
-    p.plane_stride = plane_stride;
-    jpezy_internal_dec_params(c, d_coeffs, W, H, n_frames, &p);
-    for (int f0 = 0; f0 < n_frames; f0 += kMaxFramesPerLaunch) {
-        DecParams q = p;
-        q.n_frames = n_frames - f0 < kMaxFramesPerLaunch ? n_frames - f0 : kMaxFramesPerLaunch;
-        q.coeffs += (size_t)f0 * p.coeffs_per_frame;
-        q.r += (size_t)f0 * plane_stride; q.g += (size_t)f0 * plane_stride; q.b += (size_t)f0 * plane_stride;
-        HIP_TRY(launch_dequant_idct(q, gray != 0, c->force_exact != 0, c->dec_tolerance != 0, s));
-    }
-    return JPEZY_OK;
+    return jpezy_internal_fused_dev_core(c, d_coeffs, qt, comp_tq, DecodeSink::planes(d_r, d_g, d_b, plane_stride), W, H, gray, n_frames,
+                                         (hipStream_t)stream);
 }
 
 int jpezy_dequant_idct(jpezy_ctx* c, const int16_t* coeffs, const uint16_t qt[4][64], const uint8_t comp_tq[3], int W,
@@ -620,8 +619,6 @@ try {
     size_t max_in = 0;
     for (const HostChunk& k : chunks) max_in = std::max(max_in, k.coef_bytes(W, 6));
     uint8_t* dst[3] = { r, g, b };
-    int rc_kernel = JPEZY_OK;
-    std::string err;
     auto plan = [&](int i) {
         const HostChunk& k = chunks[(size_t)i];
         jpezy_host::ChunkPlan p;
@@ -629,18 +626,12 @@ try {
         for (int q = 0; q < 3; ++q) p.out.push_back({ dst[q] + k.plane_off(W, H), k.plane_bytes(W, H), (size_t)q * P });
         return p;
     };
-    auto kernel = [&](int i, uint8_t* d_in, uint8_t* d_out, hipStream_t s) -> hipError_t {
+    return run_host_bands(c, chunks.size(), max_in, 3 * P, plan, [&](int i, uint8_t* d_in, uint8_t* d_out, hipStream_t s) {
         const HostChunk& k = chunks[(size_t)i];
         const int Hc = k.rows(H);
-        const int rc = jpezy_dequant_idct_dev(c, (const int16_t*)d_in, qt, comp_tq, k.nf > 1 ? plane : (size_t)Hc * W, W, Hc, gray, k.nf, d_out,
-                                              d_out + P, d_out + 2 * P, s);
-        if (rc != JPEZY_OK) { rc_kernel = rc; return hipErrorLaunchFailure; }
-        return hipSuccess;
-    };
-    const hipError_t e = c->pipe.run(c->device, c->stream, (int)chunks.size(), max_in, 3 * P, plan, kernel, &err);
-    if (rc_kernel != JPEZY_OK) return rc_kernel;
-    if (e != hipSuccess) return set_err(JPEZY_E_HIP, err.empty() ? std::string("host pipeline: ") + hipGetErrorString(e) : err);
-    return JPEZY_OK;
+        return jpezy_dequant_idct_dev(c, (const int16_t*)d_in, qt, comp_tq, k.nf > 1 ? plane : (size_t)Hc * W, W, Hc, gray, k.nf, d_out, d_out + P,
+                                      d_out + 2 * P, s);
+    });
 }
 JPEZY_CATCH
 

@@ -46,7 +46,9 @@ struct DecodeSource {
 
 // where the pixels go on the device.  Planes: r, g, b, frames frame_stride apart.  Packed (pix_bytes 3 or 4): r, g, b are the channel
 // bytes of pixel (0, 0), rows row_stride apart.  Native component planes (ycc, the any-layout pair only): r, g, b are sample (0, 0) of
-// the components (null: not wanted), rows row_stride / c_row_stride apart, chroma samples c_step apart.
+// the components (null: not wanted), rows row_stride / c_row_stride apart, chroma samples c_step apart.  The fused kernel's batches
+// (jpezy_internal_fused_dev_core) also read c_frame_stride, the chroma planes' frame stride, and pix, the packed buffer's first byte;
+// the three stage cores read neither.
 struct DecodeSink {
     uint8_t *r, *g, *b;
     size_t frame_stride;
@@ -54,14 +56,26 @@ struct DecodeSink {
     unsigned row_stride;
     int ycc, c_step;
     unsigned c_row_stride;
+    size_t c_frame_stride = 0;
+    uint8_t* pix = nullptr;
     static DecodeSink planes(uint8_t* r, uint8_t* g, uint8_t* b, size_t plane_stride) { return { r, g, b, plane_stride, 0, 0, 0, 1, 0 }; }
     static DecodeSink packed(const PackedLayout& L, uint8_t* pix)
     {
-        return { pix + L.off[0], pix + L.off[1], pix + L.off[2], L.frame_stride, L.bytes, (unsigned)L.row_stride, 0, 1, 0 };
+        return { pix + L.off[0], pix + L.off[1], pix + L.off[2], L.frame_stride, L.bytes, (unsigned)L.row_stride, 0, 1, 0, 0, pix };
     }
-    static DecodeSink ycc_planes(uint8_t* y, uint8_t* cb, uint8_t* cr, unsigned y_row_stride, int c_step, unsigned c_row_stride)
+    static DecodeSink ycc_planes(uint8_t* y, uint8_t* cb, uint8_t* cr, unsigned y_row_stride, int c_step, unsigned c_row_stride,
+                                 size_t y_frame_stride = 0, size_t c_frame_stride = 0)
     {
-        return { y, cb, cr, 0, 0, y_row_stride, 1, c_step, c_row_stride };
+        return { y, cb, cr, y_frame_stride, 0, y_row_stride, 1, c_step, c_row_stride, c_frame_stride };
+    }
+    // the same sink `frames` frames on; component planes that are not wanted stay null
+    void advance(size_t frames)
+    {
+        const size_t adv = frames * frame_stride, c_adv = ycc ? frames * c_frame_stride : adv;
+        r += adv;
+        if (g) g += c_adv;
+        if (b) b += c_adv;
+        if (pix) pix += adv;
     }
 };
 
@@ -223,6 +237,11 @@ extern "C" {
 // they changed since the last call).  The arguments are the callers' to check.
 // any-layout pair; upsampling != 0 (JPEZY_UPSAMPLE_SMOOTH): smooth_rgb_kernel in generic_rgb_kernel's place (jpezy_capi.hip)
 JPEZY_INTERNAL int jpezy_internal_generic_dev_core(jpezy_ctx* c, const DecodeSource& src, const DecodeSink& out, hipStream_t s, int upsampling);
+// the fused kernel of the project's own layout (three 8-bit components, 2x2 / 1x1 / 1x1) over n_frames frames: the dequantiser upload,
+// the one place that fills a DecParams and cuts a batch at kMaxFramesPerLaunch, and the choice among the planar, packed and native-sample
+// launches by the sink (jpezy_capi.hip).  gray: luma only for a native-sample sink
+JPEZY_INTERNAL int jpezy_internal_fused_dev_core(jpezy_ctx* c, const int16_t* d_coeffs, const uint16_t qt[4][64], const uint8_t comp_tq[3],
+                                                 const DecodeSink& out, int W, int H, int gray, int n_frames, hipStream_t s);
 // reduced size, log2n = 2, 1, 0 (jpezy_capi_scaled.hip)
 JPEZY_INTERNAL int jpezy_internal_scaled_dev_core(jpezy_ctx* c, const DecodeSource& src, const DecodeSink& out, hipStream_t s, int log2n);
 // the window rg (inside the picture) at log2n = 3, 2, 1, 0; the sink is the window's; upsampling != 0 (JPEZY_UPSAMPLE_SMOOTH, 8-bit files):

@@ -1,7 +1,8 @@
 // jpezy_capi_entropy.hip -- the C-ABI, part 2: the Huffman tail of encoder::encode (ref encoder/jpezy_encoder.hpp:174-225): the host
 // writer's entry points, the GPU entropy coder in its host-delivered and its device-resident form -- one Pass (plan,
-// launch chain) for both --, encoder::encode end to end.
-#include "jpezy_capi_internal.h"
+// launch chain) for both --, and encoder::encode end to end: the file-encode driver of every pixel kind and sampling
+// (jpezy_internal_encode_file, jpezy_capi_encode.h) and its planar entry.
+#include "jpezy_capi_encode.h"
 
 extern "C" {
 size_t jpezy_jpeg_bound(int W, int H) { return jpezy_host::jpeg_bound(W, H); }
@@ -463,43 +464,75 @@ long jpezy_write_jpeg_qt(const int16_t* coeffs, int W, int H, int gray, const ch
     return host_write(coeffs, W, H, gray, comment, restart_interval, optimize, out, cap, luma, chroma);
 }
 
-// planar RGB on the host -> .jpg bytes on the host, both stages on the GPU (what encoder::encode does end to end)
+// Pixels on the host -> .jpg bytes on the host, both stages on the GPU (what encoder::encode does end to end), for every pixel kind and
+// sampling: the request says what a band's host segments are and where its pixels then lie on the device.
+long jpezy_internal_encode_file(jpezy_ctx* c, const EncodeRequest& rq)
+{
+    HIP_TRY(hipSetDevice(c->device));
+    const int W = rq.W, H = rq.H;
+    const bool s420 = rq.sampling == JPEZY_SAMPLING_420;
+    const int B = rq.gray ? 4 : 6;
+    if (int rc = c->e_coef.reserve((s420 ? jpezy_coeff_count(W, H, rq.gray) : jpezy_coeff_count_sampling(W, H, rq.sampling)) * sizeof(int16_t))) return rc;
+    // 4:2:0: the pixels go up band by band (jpezy_hostpipe.h) while the bands before them are transformed into the frame's coefficient
+    // buffer on the device.  4:4:4 / 4:2:2: the whole frame is one band
+    const std::vector<HostChunk> chunks = s420 ? plan_host_chunks(W, H, 1, rq.bytes_per_px, c->host_chunk_bytes)
+                                               : std::vector<HostChunk>{ { 0, 1, 0, jpezy_mcu_rows(H) } };
+    const size_t P = plane_pitch(chunks, W, H);
+    auto plan = [&](int i) {
+        jpezy_host::ChunkPlan p;
+        rq.segments(chunks[(size_t)i], P, p.in);
+        return p;
+    };
+    size_t max_in = 0;                          // whole 16 bytes behind the last segment: the aligned kernels stay usable
+    for (size_t i = 0; i < chunks.size(); ++i)
+        for (const jpezy_host::Segment& g : plan((int)i).in) max_in = std::max(max_in, (g.slot_off + g.bytes + 15) & ~(size_t)15);
+    auto transform = [&](int i, uint8_t* d_in, uint8_t*, hipStream_t s) {
+        const HostChunk& k = chunks[(size_t)i];
+        return jpezy_internal_fdct_quant_core(c, rq.source(k, P, d_in), rq.sampling, W, k.rows(H), rq.gray, 1,
+                                              c->e_coef.as<int16_t>() + (s420 ? k.coef_off(W, H, B) : 0), s);
+    };
+    if (s420) {
+        if (int rc = run_host_bands(c, chunks.size(), max_in, 0, plan, transform)) return rc;
+    } else {
+        // That band is uploaded directly on the context's stream, not through the pinned ring: streaming 4:4:4 / 4:2:2 frames band by band
+        // would change speed and first-call allocation, and is a feature with measurements of its own.
+        if (int rc = c->in[0].reserve(max_in)) return rc;
+        for (const jpezy_host::Segment& g : plan(0).in)
+            HIP_TRY(hipMemcpyAsync((uint8_t*)c->in[0].p + g.slot_off, g.host, g.bytes, hipMemcpyHostToDevice, c->stream));
+        if (int rc = transform(0, (uint8_t*)c->in[0].p, nullptr, c->stream)) return rc;
+    }
+    // the Huffman stage on the whole frame (the context's quantisation tables in the DQT segments, its restart interval and its optimise
+    // setting act there), through the public entries: their texts
+    if (s420) return jpezy_write_jpeg_gpu(c, c->e_coef.as<int16_t>(), W, H, rq.gray, rq.comment, rq.out, rq.cap);
+    return jpezy_write_jpeg_gpu_sampling(c, c->e_coef.as<int16_t>(), W, H, rq.sampling, 0, rq.comment, rq.out, rq.cap);
+}
+
+// planar RGB on the host -> .jpg bytes on the host
 long jpezy_encode_jpeg(jpezy_ctx* c, const uint8_t* r, const uint8_t* g, const uint8_t* b, int W, int H, int gray, const char* comment,
                        uint8_t* out, size_t cap)
 try {
     if (int rc = jpezy_internal_check_dims(c, W, H, 1)) return rc;
     if (!r || !g || !b || !out) return set_err(JPEZY_E_BADARG, "encode_jpeg: null pointer");
     if (int rc = check_comment(comment, "encode_jpeg")) return rc;
-    if (int rc = jpezy_internal_check_variant_avg(c, jpezy_internal_averaged_chroma(c, gray), "encode_jpeg")) return rc;   // before anything is uploaded
-    HIP_TRY(hipSetDevice(c->device));
-    // the planes go up band by band (jpezy_hostpipe.h) while the bands before them are transformed into the frame's
-    // coefficient buffer on the device; the Huffman stage then runs on the whole frame
-    const int B = gray ? 4 : 6;
-    if (int rc = c->e_coef.reserve(jpezy_coeff_count(W, H, gray) * sizeof(int16_t))) return rc;
-    const std::vector<HostChunk> chunks = plan_host_chunks(W, H, 1, 3, c->host_chunk_bytes);
-    const size_t P = plane_pitch(chunks, W, H);
-    const uint8_t* src[3] = { r, g, b };
-    int rc_kernel = JPEZY_OK;
-    std::string err;
-    auto plan = [&](int i) {
-        const HostChunk& k = chunks[(size_t)i];
-        jpezy_host::ChunkPlan p;
-        for (int q = 0; q < 3; ++q) p.in.push_back({ const_cast<uint8_t*>(src[q]) + k.plane_off(W, H), k.plane_bytes(W, H), (size_t)q * P });
-        return p;
-    };
-    auto kernel = [&](int i, uint8_t* d_in, uint8_t*, hipStream_t s) -> hipError_t {
-        const HostChunk& k = chunks[(size_t)i];
-        const int Hc = k.rows(H);
-        const int rc = jpezy_fdct_quant_dev(c, d_in, d_in + P, d_in + 2 * P, (size_t)Hc * W, W, Hc, gray, 1,
-                                            c->e_coef.as<int16_t>() + k.coef_off(W, H, B), s);
-        if (rc != JPEZY_OK) { rc_kernel = rc; return hipErrorLaunchFailure; }
-        return hipSuccess;
-    };
-    const hipError_t e = c->pipe.run(c->device, c->stream, (int)chunks.size(), 3 * P, 0, plan, kernel, &err);
-    if (rc_kernel != JPEZY_OK) return rc_kernel;
-    if (e != hipSuccess) return set_err(JPEZY_E_HIP, err.empty() ? std::string("host pipeline: ") + hipGetErrorString(e) : err);
-    return jpezy_write_jpeg_gpu(c, (const int16_t*)c->e_coef.p, W, H, gray, comment, out, cap);
+    if (int rc = check_encode_variant(c, JPEZY_SAMPLING_420, gray, "encode_jpeg")) return rc;   // before anything is uploaded
+    return jpezy_internal_encode_file(c, planar_encode_request(r, g, b, W, H, JPEZY_SAMPLING_420, gray, comment, out, cap));
 }
 JPEZY_CATCH
 
 }  // extern "C"
+
+namespace jpezy_capi {
+
+// What a file encode from planes hands the driver: three input segments per band, a plane pitch apart
+EncodeRequest planar_encode_request(const uint8_t* r, const uint8_t* g, const uint8_t* b, int W, int H, int sampling, int gray, const char* comment,
+                                    uint8_t* out, size_t cap)
+{
+    return { W, H, sampling, gray, comment, out, cap, 3,
+             [=](const HostChunk& k, size_t P, std::vector<jpezy_host::Segment>& in) {
+                 const uint8_t* src[3] = { r, g, b };
+                 for (int q = 0; q < 3; ++q) in.push_back({ const_cast<uint8_t*>(src[q]) + k.plane_off(W, H), k.plane_bytes(W, H), (size_t)q * P });
+             },
+             [=](const HostChunk& k, size_t P, const uint8_t* d_in) { return EncodeSource::planes(d_in, d_in + P, d_in + 2 * P, (size_t)k.rows(H) * W); } };
+}
+
+}  // namespace jpezy_capi

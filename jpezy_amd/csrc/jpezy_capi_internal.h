@@ -7,7 +7,8 @@
 // jpezy_capi_smooth.hip (smooth chroma upsampling in the decoder), jpezy_capi_windows.hip (a batch of crop windows into device memory),
 // jpezy_capi_resized.hip (the same batch resized to one output size: tap tables and the second stage), jpezy_capi_multi.hip (the multi-GPU handle).
 // What the decode entries share beyond this -- the description of a transform stage, the geometry of a layout, the file-decode driver,
-// the head of the device entries -- is in jpezy_capi_decode.h, which includes this file.
+// the head of the device entries, the fused kernel's core -- is in jpezy_capi_decode.h; what the encode entries share -- where the pixels
+// are, the transform core, the file-encode driver -- is in jpezy_capi_encode.h.  Both include this file.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -167,6 +168,33 @@ inline int packed_layout(const char* who, int format, size_t row_stride, size_t 
     return JPEZY_OK;
 }
 
+// planar YCbCr 4:2:0 samples: jpezy_capi_ycc.hip
+struct YccLayout {
+    int CW, CH;
+    size_t ys, cs, yfs, cfs;      // resolved strides
+};
+
+// c_step, strides and the 32-bit row-offset limit (W, H already checked); before the context or a device is touched
+inline int ycc_layout(const char* who, int W, int H, size_t y_stride, size_t c_stride, int c_step, size_t y_frame_stride, size_t c_frame_stride,
+                      YccLayout* L)
+{
+    if (c_step != 1 && c_step != 2) return set_err(JPEZY_E_BADARG, std::string(who) + ": c_step must be 1 (planes) or 2 (one interleaved plane)");
+    const int CW = (W + 1) / 2, CH = (H + 1) / 2;
+    const size_t ys = y_stride ? y_stride : (size_t)W;
+    const size_t c_min = (size_t)(CW - 1) * c_step + 1;
+    const size_t cs = c_stride ? c_stride : (size_t)CW * c_step;
+    if (ys < (size_t)W) return set_err(JPEZY_E_BADARG, std::string(who) + ": y_stride smaller than W");
+    if (cs < c_min) return set_err(JPEZY_E_BADARG, std::string(who) + ": c_stride smaller than (CW-1) * c_step + 1");
+    if (ys > 0xFFFFFFFFull / (size_t)H || cs > 0xFFFFFFFFull / (size_t)CH)
+        return set_err(JPEZY_E_BADARG, std::string(who) + ": y_stride * H and c_stride * CH must fit in 32 bits");
+    const size_t yfs = y_frame_stride ? y_frame_stride : (size_t)H * ys;
+    const size_t cfs = c_frame_stride ? c_frame_stride : (size_t)CH * cs;
+    if (yfs < (size_t)(H - 1) * ys + (size_t)W) return set_err(JPEZY_E_BADARG, std::string(who) + ": y_frame_stride smaller than (H-1) * y_stride + W");
+    if (cfs < (size_t)(CH - 1) * cs + c_min) return set_err(JPEZY_E_BADARG, std::string(who) + ": c_frame_stride smaller than a chroma plane");
+    *L = { CW, CH, ys, cs, yfs, cfs };
+    return JPEZY_OK;
+}
+
 }  // namespace jpezy_capi
 using namespace jpezy_capi;
 
@@ -259,6 +287,25 @@ struct jpezy_ctx {
     }
 };
 
+// The chunks of a streaming host-buffer entry through the context's staging ring (jpezy_hostpipe.h).  plan(i): the host segments of
+// chunk i; transform(i, d_in, d_out, stream): its stage on the staged buffers, a C status.  The status of a failed stage, and its
+// message, win over the pipeline's error.
+template <class Plan, class Transform>
+int run_host_bands(jpezy_ctx* c, size_t chunks, size_t max_in, size_t max_out, Plan plan, Transform transform)
+{
+    int rc_stage = JPEZY_OK;
+    std::string err;
+    auto stage = [&](int i, uint8_t* d_in, uint8_t* d_out, hipStream_t s) -> hipError_t {
+        const int rc = transform(i, d_in, d_out, s);
+        if (rc != JPEZY_OK) { rc_stage = rc; return hipErrorLaunchFailure; }
+        return hipSuccess;
+    };
+    const hipError_t e = c->pipe.run(c->device, c->stream, (int)chunks, max_in, max_out, plan, stage, &err);
+    if (rc_stage != JPEZY_OK) return rc_stage;
+    if (e != hipSuccess) return set_err(JPEZY_E_HIP, err.empty() ? std::string("host pipeline: ") + hipGetErrorString(e) : err);
+    return JPEZY_OK;
+}
+
 // ---- helpers shared by the translation units (C linkage, hidden: not part of the ABI) ----
 // streams of the batch form of the GPU Huffman decoder (jpezy_capi_huffdec.hip)
 // A stream is an entropy-coded segment that starts in the known state (bit 0, block 0, DC, predictors 0): the scan of a file
@@ -278,12 +325,7 @@ struct StreamGeom {
 #define JPEZY_INTERNAL __attribute__((visibility("hidden")))
 extern "C" {
 JPEZY_INTERNAL int jpezy_internal_check_dims(const jpezy_ctx* c, int W, int H, int n_frames);
-// the parts of the two transform stages' kernel parameters that planar and packed entry points share, and the cached dequantiser tables
-JPEZY_INTERNAL int jpezy_internal_enc_params(jpezy_ctx* c, int W, int H, int gray, int n_frames, int16_t* d_coeffs, hipStream_t s, EncParams* out);
-// JPEZY_DOWNSAMPLE_AVERAGE: whether it acts on a 4:2:0 RGB transform of the context, and its refusal of encode variant 0
-JPEZY_INTERNAL bool jpezy_internal_averaged_chroma(const jpezy_ctx* c, int gray);
-JPEZY_INTERNAL int jpezy_internal_check_variant_avg(const jpezy_ctx* c, bool avg, const char* who);
-JPEZY_INTERNAL void jpezy_internal_dec_params(jpezy_ctx* c, const int16_t* d_coeffs, int W, int H, int n_frames, DecParams* out);
+// the cached dequantiser tables
 JPEZY_INTERNAL int jpezy_internal_upload_dequant(jpezy_ctx* c, const uint16_t qt[4][64], const uint8_t comp_tq[3], hipStream_t s);
 // the GPU Huffman decoder over a list of independent streams, the device tables of one scan, the block structure of an MCU (jpezy_capi_huffdec.hip)
 JPEZY_INTERNAL int jpezy_internal_huffdec_streams(jpezy_ctx* c, const std::vector<DevStream>& streams, const std::vector<jpezy_dev::huffdec::Setup>& setups,

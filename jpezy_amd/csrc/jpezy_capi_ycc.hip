@@ -3,36 +3,7 @@
 // the decode kernels skip replication and make_rgb (last step differs); coefficients keep their layout, so the Huffman stages, optimised
 // tables, restart intervals and the file header are the RGB entries'.
 #include "jpezy_capi_decode.h"
-
-namespace {
-
-struct YccLayout {
-    int CW, CH;
-    size_t ys, cs, yfs, cfs;      // resolved strides
-};
-
-// c_step, strides and the 32-bit row-offset limit (W, H already checked); before the context or a device is touched
-int ycc_layout(const char* who, int W, int H, size_t y_stride, size_t c_stride, int c_step, size_t y_frame_stride, size_t c_frame_stride,
-               YccLayout* L)
-{
-    if (c_step != 1 && c_step != 2) return set_err(JPEZY_E_BADARG, std::string(who) + ": c_step must be 1 (planes) or 2 (one interleaved plane)");
-    const int CW = (W + 1) / 2, CH = (H + 1) / 2;
-    const size_t ys = y_stride ? y_stride : (size_t)W;
-    const size_t c_min = (size_t)(CW - 1) * c_step + 1;
-    const size_t cs = c_stride ? c_stride : (size_t)CW * c_step;
-    if (ys < (size_t)W) return set_err(JPEZY_E_BADARG, std::string(who) + ": y_stride smaller than W");
-    if (cs < c_min) return set_err(JPEZY_E_BADARG, std::string(who) + ": c_stride smaller than (CW-1) * c_step + 1");
-    if (ys > 0xFFFFFFFFull / (size_t)H || cs > 0xFFFFFFFFull / (size_t)CH)
-        return set_err(JPEZY_E_BADARG, std::string(who) + ": y_stride * H and c_stride * CH must fit in 32 bits");
-    const size_t yfs = y_frame_stride ? y_frame_stride : (size_t)H * ys;
-    const size_t cfs = c_frame_stride ? c_frame_stride : (size_t)CH * cs;
-    if (yfs < (size_t)(H - 1) * ys + (size_t)W) return set_err(JPEZY_E_BADARG, std::string(who) + ": y_frame_stride smaller than (H-1) * y_stride + W");
-    if (cfs < (size_t)(CH - 1) * cs + c_min) return set_err(JPEZY_E_BADARG, std::string(who) + ": c_frame_stride smaller than a chroma plane");
-    *L = { CW, CH, ys, cs, yfs, cfs };
-    return JPEZY_OK;
-}
-
-}  // namespace
+#include "jpezy_capi_encode.h"
 
 extern "C" {
 
@@ -67,31 +38,8 @@ int jpezy_fdct_quant_ycc_dev(jpezy_ctx* c, const uint8_t* d_y, size_t y_stride, 
     if (!d_y || !d_coeffs || (!gray && (!d_cb || !d_cr))) return set_err(JPEZY_E_BADARG, "fdct_quant_ycc_dev: null device pointer");
     if (int rc = jpezy_internal_check_dims(c, W, H, n_frames)) return rc;
     if (!aligned16(d_coeffs)) return set_err(JPEZY_E_BADARG, "d_coeffs must be 16-byte aligned");
-    HIP_TRY(hipSetDevice(c->device));
-    hipStream_t s = (hipStream_t)stream;
-    EncParams p;
-    p.r = d_y;
-    p.g = gray ? nullptr : d_cb; p.b = gray ? nullptr : d_cr;            // gray: the chroma pointers are not read
-    p.plane_stride = L.yfs;
-    p.row_stride = (unsigned)L.ys;
-    p.c_row_stride = (unsigned)L.cs;
-    p.c_step = c_step;
-    p.c_frame_stride = L.cfs;
-    if (int rc = jpezy_internal_enc_params(c, W, H, gray, n_frames, d_coeffs, s, &p)) return rc;
-    for (int f0 = 0; f0 < n_frames; f0 += kMaxFramesPerLaunch) {
-        EncParams q = p;
-        q.n_frames = n_frames - f0 < kMaxFramesPerLaunch ? n_frames - f0 : kMaxFramesPerLaunch;
-        q.r += (size_t)f0 * L.yfs;
-        if (!gray) { q.g += (size_t)f0 * L.cfs; q.b += (size_t)f0 * L.cfs; }
-        q.coeffs += (size_t)f0 * p.coeffs_per_frame;
-        // variant 0: the FP64 kernel's byte loop; every other variant: the f32 kernel's YCC launch (the laboratory's persistent variants
-        // 2 and 3 hand YCC input to it as they do every frame they do not cover)
-        if (c->variant == 0)
-            HIP_TRY(launch_fdct_quant_ycc(q, gray != 0, c->force_exact != 0, s));
-        else
-            HIP_TRY(launch_fdct_quant_f32_ycc(q, gray != 0, c->force_exact, s));
-    }
-    return JPEZY_OK;
+    return jpezy_internal_fdct_quant_core(c, EncodeSource::ycc(d_y, d_cb, d_cr, L, c_step, gray), JPEZY_SAMPLING_420, W, H, gray, n_frames, d_coeffs,
+                                          (hipStream_t)stream);
 }
 
 int jpezy_dequant_idct_ycc_dev(jpezy_ctx* c, const int16_t* d_coeffs, const uint16_t qt[4][64], const uint8_t comp_tq[3], uint8_t* d_y,
@@ -104,32 +52,12 @@ int jpezy_dequant_idct_ycc_dev(jpezy_ctx* c, const int16_t* d_coeffs, const uint
     if (!d_coeffs || !qt || !comp_tq || !d_y) return set_err(JPEZY_E_BADARG, "dequant_idct_ycc_dev: null pointer");
     if (int rc = jpezy_internal_check_dims(c, W, H, n_frames)) return rc;
     if (!aligned16(d_coeffs)) return set_err(JPEZY_E_BADARG, "d_coeffs must be 16-byte aligned");
-    HIP_TRY(hipSetDevice(c->device));
-    hipStream_t s = (hipStream_t)stream;
-    if (int rc = jpezy_internal_upload_dequant(c, qt, comp_tq, s)) return rc;
-    const bool luma_only = !d_cb && !d_cr;
-    DecParams p;
-    p.r = d_y; p.g = d_cb; p.b = d_cr;
-    p.plane_stride = L.yfs;
-    p.row_stride = (unsigned)L.ys;
-    p.c_row_stride = (unsigned)L.cs;
-    p.c_step = c_step;
-    p.c_frame_stride = L.cfs;
-    jpezy_internal_dec_params(c, d_coeffs, W, H, n_frames, &p);
-    for (int f0 = 0; f0 < n_frames; f0 += kMaxFramesPerLaunch) {
-        DecParams q = p;
-        q.n_frames = n_frames - f0 < kMaxFramesPerLaunch ? n_frames - f0 : kMaxFramesPerLaunch;
-        q.coeffs += (size_t)f0 * p.coeffs_per_frame;
-        q.r += (size_t)f0 * L.yfs;
-        if (q.g) q.g += (size_t)f0 * L.cfs;
-        if (q.b) q.b += (size_t)f0 * L.cfs;
-        HIP_TRY(launch_dequant_idct_ycc(q, luma_only, c->force_exact != 0, c->dec_tolerance != 0, s));
-    }
-    return JPEZY_OK;
+    return jpezy_internal_fused_dev_core(c, d_coeffs, qt, comp_tq, DecodeSink::ycc_planes(d_y, d_cb, d_cr, (unsigned)L.ys, c_step, (unsigned)L.cs, L.yfs, L.cfs),
+                                         W, H, !d_cb && !d_cr, n_frames, (hipStream_t)stream);
 }
 
-// host planes -> .jpg bytes on the host: jpezy_encode_jpeg with up to three input segments per band (the Y rows, and the chroma rows as
-// two planes or as one interleaved plane)
+// host planes -> .jpg bytes on the host: a file encode (jpezy_internal_encode_file) with up to three input segments per band (the Y rows,
+// and the chroma rows as two planes or as one interleaved plane)
 long jpezy_encode_jpeg_ycc(jpezy_ctx* c, const uint8_t* y, size_t y_stride, const uint8_t* cb, const uint8_t* cr, size_t c_stride, int c_step,
                            int W, int H, int gray, const char* comment, uint8_t* out, size_t cap)
 try {
@@ -139,52 +67,34 @@ try {
     if (!y || !out || (!gray && (!cb || !cr))) return set_err(JPEZY_E_BADARG, "encode_jpeg_ycc: null pointer");
     if (int rc = jpezy_internal_check_dims(c, W, H, 1)) return rc;
     if (int rc = check_comment(comment, "encode_jpeg_ycc")) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    const int B = gray ? 4 : 6;
-    if (int rc = c->e_coef.reserve(jpezy_coeff_count(W, H, gray) * sizeof(int16_t))) return rc;
-    const std::vector<HostChunk> chunks = plan_host_chunks(W, H, 1, gray ? 1 : 2, c->host_chunk_bytes);
     // one interleaved plane (Cb and Cr neighbours) travels as one segment: its rows hold 2 * CW sample bytes from the lower pointer
     const bool inter = !gray && c_step == 2 && (cb + 1 == cr || cr + 1 == cb);
     const uint8_t* c_lo = inter ? std::min(cb, cr) : nullptr;
     const size_t c_row_bytes = inter ? (size_t)2 * L.CW : (size_t)(L.CW - 1) * c_step + 1;
     // a band goes up as it lies in the caller's buffers, row padding included, up to the last sample byte of its last row
-    auto y_bytes = [&](const HostChunk& k) { return (size_t)(k.rows(H) - 1) * L.ys + (size_t)W; };
-    auto c_rows = [&](const HostChunk& k) { return (k.rows(H) + 1) / 2; };
-    auto c_bytes = [&](const HostChunk& k) { return (size_t)(c_rows(k) - 1) * L.cs + c_row_bytes; };
+    auto y_bytes = [=](const HostChunk& k) { return (size_t)(k.rows(H) - 1) * L.ys + (size_t)W; };
+    auto c_bytes = [=](const HostChunk& k) { return (size_t)((k.rows(H) + 1) / 2 - 1) * L.cs + c_row_bytes; };
     auto pad16 = [](size_t n) { return (n + 15) & ~(size_t)15; };
-    size_t max_in = 0;
-    for (const HostChunk& k : chunks) max_in = std::max(max_in, pad16(y_bytes(k)) + (gray ? 0 : (inter ? 1 : 2) * pad16(c_bytes(k))));
-    int rc_kernel = JPEZY_OK;
-    std::string err;
-    auto plan = [&](int i) {
-        const HostChunk& k = chunks[(size_t)i];
-        jpezy_host::ChunkPlan p;
-        p.in.push_back({ const_cast<uint8_t*>(y) + (size_t)k.y0 * 16 * L.ys, y_bytes(k), 0 });
-        if (!gray) {
+    return jpezy_internal_encode_file(c, { W, H, JPEZY_SAMPLING_420, gray, comment, out, cap, (size_t)(gray ? 1 : 2),
+        [&](const HostChunk& k, size_t, std::vector<jpezy_host::Segment>& in) {
+            in.push_back({ const_cast<uint8_t*>(y) + (size_t)k.y0 * 16 * L.ys, y_bytes(k), 0 });
+            if (gray) return;
             const size_t coff = (size_t)k.y0 * 8 * L.cs, o1 = pad16(y_bytes(k)), o2 = o1 + pad16(c_bytes(k));
             if (inter) {
-                p.in.push_back({ const_cast<uint8_t*>(c_lo) + coff, c_bytes(k), o1 });
+                in.push_back({ const_cast<uint8_t*>(c_lo) + coff, c_bytes(k), o1 });
             } else {
-                p.in.push_back({ const_cast<uint8_t*>(cb) + coff, c_bytes(k), o1 });
-                p.in.push_back({ const_cast<uint8_t*>(cr) + coff, c_bytes(k), o2 });
+                in.push_back({ const_cast<uint8_t*>(cb) + coff, c_bytes(k), o1 });
+                in.push_back({ const_cast<uint8_t*>(cr) + coff, c_bytes(k), o2 });
             }
-        }
-        return p;
-    };
-    auto kernel = [&](int i, uint8_t* d_in, uint8_t*, hipStream_t s) -> hipError_t {
-        const HostChunk& k = chunks[(size_t)i];
-        const size_t o1 = pad16(y_bytes(k)), o2 = o1 + pad16(c_bytes(k));
-        const uint8_t* d_cb = gray ? nullptr : inter ? d_in + o1 + (cb > cr ? 1 : 0) : d_in + o1;
-        const uint8_t* d_cr = gray ? nullptr : inter ? d_in + o1 + (cr > cb ? 1 : 0) : d_in + o2;
-        const int rc = jpezy_fdct_quant_ycc_dev(c, d_in, L.ys, d_cb, d_cr, L.cs, c_step, 0, 0, W, k.rows(H), gray, 1,
-                                                c->e_coef.as<int16_t>() + k.coef_off(W, H, B), s);
-        if (rc != JPEZY_OK) { rc_kernel = rc; return hipErrorLaunchFailure; }
-        return hipSuccess;
-    };
-    const hipError_t e = c->pipe.run(c->device, c->stream, (int)chunks.size(), max_in, 0, plan, kernel, &err);
-    if (rc_kernel != JPEZY_OK) return rc_kernel;
-    if (e != hipSuccess) return set_err(JPEZY_E_HIP, err.empty() ? std::string("host pipeline: ") + hipGetErrorString(e) : err);
-    return jpezy_write_jpeg_gpu(c, (const int16_t*)c->e_coef.p, W, H, gray, comment, out, cap);
+        },
+        [&](const HostChunk& k, size_t, const uint8_t* d_in) {
+            const size_t o1 = pad16(y_bytes(k)), o2 = o1 + pad16(c_bytes(k));
+            YccLayout band = L;
+            band.yfs = (size_t)k.rows(H) * L.ys;            // the tight frame strides of the band's rows
+            band.cfs = (size_t)((k.rows(H) + 1) / 2) * L.cs;
+            return EncodeSource::ycc(d_in, inter ? d_in + o1 + (cb > cr ? 1 : 0) : d_in + o1, inter ? d_in + o1 + (cr > cb ? 1 : 0) : d_in + o2, band,
+                                     c_step, gray);
+        } });
 }
 JPEZY_CATCH
 

@@ -162,6 +162,10 @@ hipError_t launch_fdct_quant_f32_packed_avg(const EncParams& p, int force, hipSt
 // ... and for planar YCbCr 4:2:0 samples (EncParams::c_step != 0): no colour conversion, the planes are the file's own sample domain
 hipError_t launch_fdct_quant_f32_ycc(const EncParams& p, bool gray, int force, hipStream_t stream);
 hipError_t launch_fdct_quant_ycc(const EncParams& p, bool gray, bool force_exact, hipStream_t stream);
+// 4:4:4 (8 x 8 MCUs of Y, Cb, Cr) and 4:2:2 (16 x 8 MCUs of Y, Y, Cb, Cr; average: the averaged h2v1 chroma stage) from planes or packed
+// pixels alike: quads_per_row counts work units of 8 MCUs (jpezy_f32_octet.h; jpezy_kernels_f32_444.hip, jpezy_kernels_f32_422.hip)
+hipError_t launch_fdct_quant_f32_444(const EncParams& p, int force, hipStream_t stream);
+hipError_t launch_fdct_quant_f32_422(const EncParams& p, int force, bool average, hipStream_t stream);
 // variant 2: the same arithmetic in persistent workgroups with LDS-DMA loader waves (jpezy_kernels_f32_ps.hip); frames whose rows do
 // not divide into groups of four quads, or unaligned planes, go to variant 1's launch.  n_cus: compute units of the device.
 hipError_t launch_fdct_quant_f32_ps(const EncParams& p, bool gray, int force, int n_cus, hipStream_t stream);

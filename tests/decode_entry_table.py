@@ -31,7 +31,7 @@ HOST_ENTRIES = [*HOST_PLANAR, *HOST_PACKED, "decode_jpeg_ycc"]
 DEV_ENTRIES = [*DEV_PLANAR, *DEV_PACKED]
 ENTRIES = HOST_ENTRIES + DEV_ENTRIES
 # decode entries of api.ABI this table leaves alone: the batch (a list of files with a status each) and the three fused entries for the
-# project's own layout, which have no host twin here and which the host-layer driver does not restructure
+# project's own layout, which tests/fused_entry_table.py drives beside the encoder's entries
 NOT_IN_TABLE = {"jpezy_decode_jpeg_batch", "jpezy_dequant_idct_dev", "jpezy_dequant_idct_packed_dev", "jpezy_dequant_idct_ycc_dev"}
 
 REGION = (3, 2, 5, 4)           # inside the 20 x 12 picture of scale_denom 2 (the default scale of every row)

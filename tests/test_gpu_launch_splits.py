@@ -205,6 +205,139 @@ def test_generic_batch_decode_across_launch_split(J, ctx, oracle):
             assert (got[:, 64:] == 0x5A).all(), f"gray={gray} plane {q}: bytes between the planes were written"
 
 
+# ---- the entries of the other pixel kinds: their own frame advances across the seam ----
+_SHARED = {}
+
+
+def _shared_coeffs(oracle):
+    """the coefficients of N1 16x16 frames for the fused decode cases: computed once, read-only"""
+    if "co" not in _SHARED:
+        co = _oracle_coeffs(oracle, N1, 29)
+        d_co = _dev(co.reshape(-1))
+        co.setflags(write=False)
+        _SHARED["co"] = (co, d_co)
+    return _SHARED["co"]
+
+
+def _packed(pl, n, W, H, format):
+    """_planes as an (n, H, W, C) picture of the format: the frame stride is the tensor's"""
+    nb, blue_first = (3, False) if format == 0 else (4, True)
+    img = np.full((n, H * W, nb), 0xFF, np.uint8)
+    for q in range(3):
+        img[:, :, 2 - q if blue_first else q] = pl[q]
+    return img.reshape(n, H, W, nb)
+
+
+def _rows(t, n, frames):
+    """frames `frames` of a device tensor of n frames, on the host"""
+    import torch
+    return t.view(n, -1)[torch.as_tensor(frames, device=t.device)].cpu().numpy()
+
+
+def _encode_case(J, ctx, oracle, case):
+    """-> (variants, W, H, launch(out), want(f)) of one encode entry over n = N1 frames of one MCU"""
+    import sampling422_model as S422
+    import sampling_model as S444
+    import ycc_model as YM
+    n = N1
+    kind, _, sub = case.partition("-")
+    if kind == "packed":
+        W = H = 16
+        fmt = {"rgb24": J.api.PIX_RGB24, "bgra32": J.api.PIX_BGRA32}[sub]
+        pl = _planes(n, W, H, 31)
+        d_img = _dev(_packed(pl, n, W, H, fmt))
+        return ((0, 1), (False, True), J.coeff_count, W, H,
+                lambda out, gray: ctx.fdct_quant_packed_dev(d_img, out, format=fmt, gray=gray),
+                lambda f, gray: oracle.encode_coeffs(pl[0, f], pl[1, f], pl[2, f], W, H, gray))
+    if kind == "ycc":
+        W = H = 16
+        pl = _planes(n, W, H, 37)
+        y, cb, cr = pl[0].reshape(n, 16, 16), pl[1][:, :64].reshape(n, 8, 8), pl[2][:, :64].reshape(n, 8, 8)
+        d_y = _dev(y)
+        if sub == "planes":
+            d_cb, d_cr = _dev(cb), _dev(cr)
+        else:                                                    # one interleaved chroma plane: Cb and Cr neighbours, c_step 2
+            d_uv = _dev(np.stack([cb, cr], axis=-1))
+            d_cb, d_cr = d_uv[..., 0], d_uv[..., 1]
+        return ((0, 1), (False, True), J.coeff_count, W, H,
+                lambda out, gray: ctx.fdct_quant_ycc_dev(d_y, d_cb, d_cr, out, gray=gray),
+                lambda f, gray: YM.encode_coeffs(y[f], cb[f], cr[f], gray))
+    sampling, model, (W, H) = {"444": (J.api.SAMPLING_444, S444, (8, 8)), "422": (J.api.SAMPLING_422, S422, (16, 8))}[kind]
+    luma, chroma = ctx.quant_tables()
+    pl = _planes(n, W, H, 41 + W)
+    count = lambda W, H, gray: J.coeff_count(W, H, sampling=sampling)
+    want = lambda f, gray: model.encode_coeffs(pl[0, f], pl[1, f], pl[2, f], W, H, luma, chroma)
+    if sub == "planes":
+        d = [_dev(pl[q].reshape(-1)) for q in range(3)]
+        return ((1,), (False,), count, W, H, lambda out, gray: ctx.fdct_quant_dev(d[0], d[1], d[2], W, H, out, n_frames=n, sampling=sampling), want)
+    d_img = _dev(_packed(pl, n, W, H, J.api.PIX_RGB24))
+    return ((1,), (False,), count, W, H, lambda out, gray: ctx.fdct_quant_packed_dev(d_img, out, sampling=sampling), want)
+
+
+def _decode_case(J, ctx, oracle, case, frames):
+    """runs one fused decode entry over N1 16x16 frames and compares the sampled frames"""
+    import torch
+    import ycc_model as YM
+    n, W, H = N1, 16, 16
+    co, d_co = _shared_coeffs(oracle)
+    info = oracle.make_info(W, H)
+    kind, _, sub = case.partition("-")
+    if kind == "decode_packed":
+        fmt = {"rgb24": J.api.PIX_RGB24, "bgra32": J.api.PIX_BGRA32}[sub]
+        nb = J.api.pixel_bytes(fmt)
+        for gray in (False, True):
+            d_img = torch.zeros((n, H, W, nb), dtype=torch.uint8, device="cuda")
+            ctx.dequant_idct_packed_dev(d_co, d_img, format=fmt, gray=gray)
+            torch.cuda.synchronize()
+            got = _rows(d_img, n, frames).reshape(len(frames), H * W, nb)
+            for i, f in enumerate(frames):
+                want = _packed(np.stack(oracle.decode_planes(co[f], info, gray))[:, None, :], 1, W, H, fmt).reshape(H * W, nb)
+                assert np.array_equal(got[i], want), f"{case} gray={gray} frame {f}"
+        return
+    for luma_only in (False, True):
+        d_y = torch.zeros((n, H, W), dtype=torch.uint8, device="cuda")
+        d_uv = torch.zeros((n, 2, H // 2, W // 2) if sub == "planes" else (n, H // 2, W // 2, 2), dtype=torch.uint8, device="cuda")
+        d_cb, d_cr = (d_uv[:, 0], d_uv[:, 1]) if sub == "planes" else (d_uv[..., 0], d_uv[..., 1])
+        ctx.dequant_idct_ycc_dev(d_co, d_y, None if luma_only else d_cb, None if luma_only else d_cr)
+        torch.cuda.synchronize()
+        got = [_rows(t.contiguous(), n, frames) for t in (d_y, d_cb, d_cr)]
+        for i, f in enumerate(frames):
+            want = YM.decode_planes(co[f], info)
+            for q in range(1 if luma_only else 3):
+                assert np.array_equal(got[q][i], want[q].reshape(-1)), f"{case} luma_only={luma_only} component {q} frame {f}"
+            if luma_only:
+                assert not got[1][i].any() and not got[2][i].any(), f"{case}: chroma of frame {f} written by a luma-only call"
+
+
+@pytest.mark.parametrize("case", ["packed-rgb24", "packed-bgra32", "ycc-planes", "ycc-interleaved", "444-planes", "444-packed", "422-planes",
+                                  "422-packed", "decode_packed-rgb24", "decode_packed-bgra32", "decode_ycc-planes", "decode_ycc-interleaved"])
+def test_other_pixel_kinds_across_the_launch_split(J, ctx, oracle, case):
+    """65537 frames of one MCU through the entries whose frame advances are not the planar 4:2:0 ones': the packed buffer's frame stride,
+    the two strides of the YCbCr planes, the coefficients per frame of 4:4:4 and 4:2:2, and the fused decoder's packed and native-sample
+    outputs.  Expected values: the oracle and the CPU models, for the frames around the seam and a random sample"""
+    import torch
+    n = N1
+    frames = _sample(n, [SPLIT])
+    if case.startswith("decode"):
+        _decode_case(J, ctx, oracle, case, frames)
+        return
+    variants, grays, count, W, H, launch, want = _encode_case(J, ctx, oracle, case)
+    try:
+        for gray in grays:
+            cpf = count(W, H, gray)
+            expect = {f: np.asarray(want(f, gray)).reshape(-1) for f in frames}
+            for variant in variants:
+                ctx.set_variant(variant)
+                out = torch.full((n * cpf,), -32768, dtype=torch.int16, device="cuda")
+                launch(out, gray)
+                torch.cuda.synchronize()
+                got = _rows(out, n, frames)
+                for i, f in enumerate(frames):
+                    assert np.array_equal(got[i], expect[f]), f"{case} gray={gray} variant={variant} frame {f}"
+    finally:
+        ctx.set_variant(1)
+
+
 # ---- the GPU Huffman writer ----
 def _host_batch(J, co, W, H, n, gray=False, cap=None, comment=b"Encoded by jpezy"):
     """jpezy_write_jpeg_batch with a caller-chosen cap (the Python wrapper reserves jpezy_jpeg_bound per frame)"""

@@ -962,8 +962,13 @@ constexpr int STUFF_WG = 256;
 // every workgroup works out whether the frame failed (a coefficient outside the tables: JPEZY_E_FORMAT = -5) or does not fit
 // (JPEZY_E_NOSPACE = -6) and leaves at once if so; workgroup 0 of the frame reports the size, writes EOI and copies the header.
 // RST (plan.markers != nullptr): restart intervals.  The counts in ff_loc / ff_tile_total then include two bytes per RSTn marker, a
-// thread places its chunk's markers behind the bytes plan.markers names (an interval is at least two bytes long, so a chunk holds at
-// most 32 of them: 192 bytes of staging per chunk), and a marker's 0xFF is never stuffed.
+// thread places its chunk's markers behind the bytes plan.markers names, and a marker's 0xFF is never stuffed.  An interval can be ONE
+// byte long (per-image tables code a flat 4:4:4 MCU in 6 bits and a flat 4:2:2 MCU in 8), so a chunk holds up to 64 markers.  The
+// staging bound of three bytes per data byte still holds for a piece: a data byte gains at most two bytes (one 0x00 or one marker); it
+// gains three only as an 0xFF that ends an interval (FF 00 FF Dn), and such an interval is at least two bytes long, because every
+// code holds a zero bit and a one-byte interval therefore is never 0xFF -- the byte in front of it gains at most one.  A whole piece
+// of one-byte intervals fills the buffer to exactly 256 x 192 bytes plus the alignment shift; an interval-ending 0xFF as the piece's
+// first byte adds one more, which the four spare words take.
 template <bool RST>
 __global__ __launch_bounds__(STUFF_WG) void stuff_kernel(const uint32_t* U, size_t u_stride_words, const unsigned long long* frame_bytes,
                                                         const uint32_t* ff_loc, const uint32_t* ff_tile_total, uint8_t* out, size_t out_stride,

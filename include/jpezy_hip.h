@@ -941,8 +941,9 @@ int jpezy_decode_windows_tensor_dev(jpezy_ctx* ctx, int n, const uint8_t* const*
  *                 laboratory's variants 2 and 3 hand YCC input to variant 1's launch
  *
  * NOT provided in YCC form: jpezy_decode_jpeg_batch, the multi-GPU handle, reduced-size decode, region decode, the host-buffer jpezy_fdct_quant /
- * jpezy_dequant_idct, the jpezy::encoder / decoder class surface, 4:2:2 / 4:4:4 INPUT, limited-range (16-235) video levels: the caller's
- * planes are taken as the file's full-range samples.
+ * jpezy_dequant_idct, the jpezy::encoder / decoder class surface, 4:4:4 INPUT, limited-range (16-235) video levels: the caller's
+ * planes are taken as the file's full-range samples.  (4:2:2 input and output -- I422 / NV16 planes, YUY2 / UYVY / YVYU macropixels -- has
+ * entries of its own: jpezy_hip_ycc422.h, included at the end of this file.)
  */
 /* CW, CH (either may be NULL) of a W x H picture; JPEZY_E_BADARG for a size outside 1..65535.  Pure host function (stands in for the
  * decimation of encoder/jpezy_encoder.hpp:134-142). */
@@ -1304,6 +1305,13 @@ int jpezy_ctx_windows_upsampling(jpezy_ctx* ctx);
  * without the new entries and with the setting at its default every launch is the one made before.
  */
 #include "jpezy_hip_orientation.h"
+
+/*
+ * YCbCr 4:2:2 SAMPLES IN AND OUT (planar I422 / NV16, packed YUY2 / UYVY / YVYU): the 4:2:2 counterpart of the planar 4:2:0 section above.
+ * The definition and the entries are in a header of their own, part of this one, for the reason given above
+ * jpezy_hip_region_upsampling.h.  Nothing declared here changes.
+ */
+#include "jpezy_hip_ycc422.h"
 
 #ifdef __cplusplus
 }

@@ -26,12 +26,12 @@ DEVICE = ["--offload-arch=gfx950", "-fno-slp-vectorize"]
 # tools/ab/ab_build.py build them in (-DJPEZY_WITH_LAB); jpezy_ctx_set_variant(ctx, 2) says JPEZY_E_UNSUPPORTED otherwise.
 LAB_SOURCES = [CSRC / "jpezy_kernels_f32_ps.hip"]
 LAB_FLAGS = ["-DJPEZY_WITH_LAB"]
-LIB_SOURCES = [CSRC / "jpezy_kernels_f64.hip", CSRC / "jpezy_kernels_decode.hip", CSRC / "jpezy_kernels_f32.hip", CSRC / "jpezy_kernels_f32_444.hip", CSRC / "jpezy_kernels_f32_422.hip", CSRC / "jpezy_kernels_f32_avg.hip", CSRC / "jpezy_kernels_generic.hip", CSRC / "jpezy_kernels_scaled.hip", CSRC / "jpezy_kernels_region.hip", CSRC / "jpezy_kernels_resized.hip", CSRC / "jpezy_kernels_resized_tensor.hip", CSRC / "jpezy_kernels_transform.hip", CSRC / "jpezy_kernels_smooth.hip",
+LIB_SOURCES = [CSRC / "jpezy_kernels_f64.hip", CSRC / "jpezy_kernels_decode.hip", CSRC / "jpezy_kernels_f32.hip", CSRC / "jpezy_kernels_f32_444.hip", CSRC / "jpezy_kernels_f32_422.hip", CSRC / "jpezy_kernels_f32_422_ycc.hip", CSRC / "jpezy_kernels_f32_avg.hip", CSRC / "jpezy_kernels_generic.hip", CSRC / "jpezy_kernels_scaled.hip", CSRC / "jpezy_kernels_region.hip", CSRC / "jpezy_kernels_resized.hip", CSRC / "jpezy_kernels_resized_tensor.hip", CSRC / "jpezy_kernels_transform.hip", CSRC / "jpezy_kernels_smooth.hip",
                CSRC / "jpezy_entropy.hip", CSRC / "jpezy_huffstat.hip", CSRC / "jpezy_huffdec.hip",
-               CSRC / "jpezy_capi.hip", CSRC / "jpezy_capi_entropy.hip", CSRC / "jpezy_capi_huffdec.hip", CSRC / "jpezy_capi_decode_batch.hip", CSRC / "jpezy_capi_multi.hip", CSRC / "jpezy_capi_packed.hip", CSRC / "jpezy_capi_scaled.hip", CSRC / "jpezy_capi_region.hip", CSRC / "jpezy_capi_windows.hip", CSRC / "jpezy_capi_resized.hip", CSRC / "jpezy_capi_ycc.hip", CSRC / "jpezy_capi_sampling.hip", CSRC / "jpezy_capi_transform.hip", CSRC / "jpezy_capi_smooth.hip",
+               CSRC / "jpezy_capi.hip", CSRC / "jpezy_capi_entropy.hip", CSRC / "jpezy_capi_huffdec.hip", CSRC / "jpezy_capi_decode_batch.hip", CSRC / "jpezy_capi_multi.hip", CSRC / "jpezy_capi_packed.hip", CSRC / "jpezy_capi_scaled.hip", CSRC / "jpezy_capi_region.hip", CSRC / "jpezy_capi_windows.hip", CSRC / "jpezy_capi_resized.hip", CSRC / "jpezy_capi_ycc.hip", CSRC / "jpezy_capi_ycc422.hip", CSRC / "jpezy_capi_sampling.hip", CSRC / "jpezy_capi_transform.hip", CSRC / "jpezy_capi_smooth.hip",
                CSRC / "jpezy_host_codec.cpp"]
 LIB_DEPS = LIB_SOURCES + LAB_SOURCES + [CSRC / "jpezy_lab.h", CSRC / "jpezy_device.h", CSRC / "jpezy_wave.h", CSRC / "jpezy_pixel_out.h", CSRC / "jpezy_f32_quad.h", CSRC / "jpezy_f32_onequad.h", CSRC / "jpezy_f32_octet.h", CSRC / "jpezy_capi_internal.h", CSRC / "jpezy_capi_decode.h", CSRC / "jpezy_capi_encode.h", CSRC / "jpezy_owners.h", CSRC / "jpezy_experiment.h", CSRC / "jpezy_hostpipe.h", CSRC / "jpezy_host_codec.h", CSRC / "jpezy_entropy.h", CSRC / "jpezy_huffdec.h", CSRC / "jpezy_huffdec_core.h", CSRC / "jpezy_resize_taps.h", CSRC / "jpezy_resample_core.h", CSRC / "jpezy_tensor_layout.h", CSRC / "jpezy_exif.h",
-                          ROOT / "include" / "jpezy_hip.h", ROOT / "include" / "jpezy_hip_region_upsampling.h", ROOT / "include" / "jpezy_hip_orientation.h", ROOT / "include" / "jpezy_constants.h"]
+                          ROOT / "include" / "jpezy_hip.h", ROOT / "include" / "jpezy_hip_region_upsampling.h", ROOT / "include" / "jpezy_hip_orientation.h", ROOT / "include" / "jpezy_hip_ycc422.h", ROOT / "include" / "jpezy_constants.h"]
 CLI = {"jpezy_encode": CSRC / "host" / "encode_main.cpp", "jpezy_decode": CSRC / "host" / "decode_main.cpp",
        "jpezy_tran": CSRC / "host" / "tran_main.cpp"}
 

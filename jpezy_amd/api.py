@@ -231,6 +231,22 @@ ABI_ORIENTATION = [
 ]
 ORIENT_FROM_FILE = 0        # JPEZY_ORIENT_FROM_FILE: the orientation argument of decode_jpeg_oriented[_packed] -- the file's own tag
 
+# include/jpezy_hip_ycc422.h (part of jpezy_hip.h): YCbCr 4:2:2 samples in and out -- planar I422 / NV16 and packed YUY2 / UYVY / YVYU.
+# Kept out of ABI for the same reason
+ABI_YCC422 = [
+    ("jpezy_yuv422_row_bytes", C.c_int, [C.c_int]),
+    ("jpezy_ycc422_chroma_size", C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    ("jpezy_fdct_quant_ycc422_dev", C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int,
+                                              _vp, _vp]),
+    ("jpezy_encode_jpeg_ycc422", C.c_long, [_vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_char_p, _vp, C.c_size_t]),
+    ("jpezy_fdct_quant_yuv422_dev", C.c_int, [_vp, _vp, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, _vp, _vp]),
+    ("jpezy_encode_jpeg_yuv422", C.c_long, [_vp, _vp, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_char_p, _vp, C.c_size_t]),
+    ("jpezy_dequant_idct_generic_yuv422_dev", C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t,
+                                                        C.c_size_t, C.c_int, _vp, _vp]),
+    ("jpezy_decode_jpeg_yuv422", C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(FrameInfo), C.c_int, C.c_size_t, _vp, C.c_size_t]),
+]
+YUV_YUY2, YUV_UYVY, YUV_YVYU = 0, 1, 2          # JPEZY_YUV_*: Y0 Cb Y1 Cr / Cb Y0 Cr Y1 / Y0 Cr Y1 Cb
+
 # chroma sampling of the encoder's *_sampling entry points: 4:2:0 (the reference's 2x2 / 1x1 / 1x1, everything as without the keyword)
 # or 4:4:4 (8 x 8 MCUs of Y, Cb, Cr, no decimation; include/jpezy_hip.h has the definition)
 SAMPLING_420, SAMPLING_444 = 0, 1
@@ -278,7 +294,7 @@ def load_library():
         except Exception:
             pass
         lib = C.CDLL(str(_LIBPATH))
-        for name, res, args in ABI + ABI_REGION_UPSAMPLING + ABI_ORIENTATION:
+        for name, res, args in ABI + ABI_REGION_UPSAMPLING + ABI_ORIENTATION + ABI_YCC422:
             fn = getattr(lib, name)          # AttributeError if the library does not export the symbol
             fn.restype = res
             fn.argtypes = args
@@ -451,6 +467,18 @@ def ycc_component_size(info, comp):
     w, h = C.c_int(), C.c_int()
     _check(load_library().jpezy_ycc_component_size(C.byref(info), int(comp), C.byref(w), C.byref(h)))
     return w.value, h.value
+
+
+def yuv422_row_bytes(W):
+    """4 * ceil(W/2): the bytes of a row of packed YCbCr 4:2:2 macropixels (YUY2 / UYVY / YVYU)"""
+    return _check(load_library().jpezy_yuv422_row_bytes(int(W)))
+
+
+def ycc422_chroma_size(W, H):
+    """(CW, CH) = (ceil(W/2), H): the chroma planes of a W x H picture in planar YCbCr 4:2:2 (I422 / NV16)"""
+    cw, ch = C.c_int(), C.c_int()
+    _check(load_library().jpezy_ycc422_chroma_size(int(W), int(H), C.byref(cw), C.byref(ch)))
+    return cw.value, ch.value
 
 
 def _np_ptr(a):
@@ -1204,6 +1232,121 @@ class Context:
         _check(load_library().jpezy_dequant_idct_ycc_dev(self._h, d_coeffs.data_ptr(), C.byref(qtab), C.byref(tq), d_y.data_ptr(), ys,
                                                          d_cb.data_ptr() if d_cb is not None else None, d_cr.data_ptr() if d_cr is not None else None,
                                                          cs, step, yfs, cfs, W, H, n, stream))
+
+    # ---- YCbCr 4:2:2 samples (planar I422 / YV16 / NV16 / NV61, packed YUY2 / UYVY / YVYU; include/jpezy_hip_ycc422.h) ----
+    def encode_jpeg_ycc422(self, y, cb, cr, comment=None):
+        """2-D numpy uint8 planes -> the bytes of a 4:2:2 .jpg: y (H, W), cb and cr (H, ceil(W/2)).  Strides and c_step are read from the
+        arrays, so uv[..., 0], uv[..., 1] of an NV16 plane (H, W/2, 2) encode in place."""
+        lib = load_library()
+        y = np.asarray(y)
+        if y.dtype != np.uint8 or y.ndim != 2:
+            raise JpezyError("encode_jpeg_ycc422: y must be a 2-D uint8 array")
+        H, W = y.shape
+        if y.strides[1] != 1 or y.strides[0] < W:
+            y = np.ascontiguousarray(y)
+        cw, ch = ycc422_chroma_size(W, H)
+        cb, cr = np.asarray(cb), np.asarray(cr)
+        for c in (cb, cr):
+            if c.dtype != np.uint8 or c.shape != (ch, cw):
+                raise JpezyError(f"encode_jpeg_ycc422: cb and cr must be uint8 arrays of shape ({ch}, {cw})")
+        if not (cb.strides == cr.strides and cb.strides[1] in (1, 2) and cb.strides[0] >= (cw - 1) * cb.strides[1] + 1):
+            cb, cr = np.ascontiguousarray(cb), np.ascontiguousarray(cr)
+        c_stride, c_step = (cb.strides[0] if ch > 1 else 0), (cb.strides[1] if cw > 1 else 1)
+        if comment is None:
+            comment = b"Encoded by jpezy"
+        cap = jpeg_bound(W, H, SAMPLING_422)
+        buf = np.empty(cap, dtype=np.uint8)
+        n = _check(lib.jpezy_encode_jpeg_ycc422(self._h, _np_ptr(y), y.strides[0] if H > 1 else 0, _np_ptr(cb), _np_ptr(cr), c_stride, c_step, W, H,
+                                                comment, _np_ptr(buf), cap))
+        return buf[:n].tobytes()
+
+    def fdct_quant_ycc422_dev(self, d_luma, d_cb, d_cr, d_coeffs):
+        """device Y (d_luma), Cb, Cr samples (torch uint8 (H, W) and (H, CW), or with a leading frame dimension; strides are the tensors', so the two
+        views of an interleaved NV16 plane work) -> d_coeffs in the 4:2:2 layout, on torch's current stream of the tensors' device"""
+        import torch
+        who = "fdct_quant_ycc422_dev"
+        if d_luma.dtype != torch.uint8 or d_luma.dim() not in (2, 3) or (d_luma.shape[-1] > 1 and d_luma.stride(-1) != 1):
+            raise JpezyError(f"{who}: d_luma must be a uint8 tensor (H, W) or (N, H, W) whose rows are contiguous")
+        H, W = int(d_luma.shape[-2]), int(d_luma.shape[-1])
+        n = int(d_luma.shape[0]) if d_luma.dim() == 3 else 1
+        cw, ch = ycc422_chroma_size(W, H)
+        for c in (d_cb, d_cr):
+            if c.dtype != torch.uint8 or c.dim() != d_luma.dim() or tuple(c.shape[-2:]) != (ch, cw) or (c.dim() == 3 and int(c.shape[0]) != n):
+                raise JpezyError(f"{who}: chroma tensors must be uint8 of shape ({ch}, {cw}) with d_luma's frame dimension")
+        if d_cb.stride() != d_cr.stride():
+            raise JpezyError(f"{who}: d_cb and d_cr must have the same strides")
+        ys = int(d_luma.stride(-2)) if H > 1 else 0
+        yfs = int(d_luma.stride(0)) if d_luma.dim() == 3 and n > 1 else 0
+        step = int(d_cb.stride(-1)) if cw > 1 else 1
+        cs = int(d_cb.stride(-2)) if ch > 1 else 0
+        cfs = int(d_cb.stride(0)) if d_cb.dim() == 3 and n > 1 else 0
+        stream = torch.cuda.current_stream(d_luma.device).cuda_stream
+        _check(load_library().jpezy_fdct_quant_ycc422_dev(self._h, d_luma.data_ptr(), ys, d_cb.data_ptr(), d_cr.data_ptr(), cs, step, yfs, cfs, W, H, n,
+                                                          d_coeffs.data_ptr(), stream))
+
+    def encode_jpeg_yuv422(self, img, W=None, format=YUV_YUY2, comment=None):
+        """numpy uint8 (H, >= row_bytes) packed macropixels with contiguous rows -> the bytes of a 4:2:2 .jpg.  W defaults to
+        img.shape[1] // 2; strides[0] becomes row_stride, so a view with padded rows encodes in place."""
+        lib = load_library()
+        img = np.asarray(img)
+        if img.dtype != np.uint8 or img.ndim != 2:
+            raise JpezyError("encode_jpeg_yuv422: a 2-D uint8 array (H, row bytes) is expected")
+        H = img.shape[0]
+        W = img.shape[1] // 2 if W is None else int(W)
+        if img.shape[1] < yuv422_row_bytes(W):
+            raise JpezyError(f"encode_jpeg_yuv422: rows of {img.shape[1]} bytes hold fewer than W = {W} pixels")
+        if img.strides[1] != 1 or img.strides[0] < img.shape[1]:
+            img = np.ascontiguousarray(img)
+        if comment is None:
+            comment = b"Encoded by jpezy"
+        cap = jpeg_bound(W, H, SAMPLING_422)
+        buf = np.empty(cap, dtype=np.uint8)
+        n = _check(lib.jpezy_encode_jpeg_yuv422(self._h, _np_ptr(img), int(format), img.strides[0] if H > 1 else 0, W, H, comment, _np_ptr(buf), cap))
+        return buf[:n].tobytes()
+
+    @staticmethod
+    def _yuv422_layout(d_pix, W, who):
+        """(n_frames, H, W, row_stride, frame_stride) of a torch uint8 tensor (H, B) or (N, H, B) of packed macropixels"""
+        import torch
+        if d_pix.dtype != torch.uint8 or d_pix.dim() not in (2, 3) or (d_pix.shape[-1] > 1 and d_pix.stride(-1) != 1):
+            raise JpezyError(f"{who}: a uint8 tensor (H, B) or (N, H, B) whose rows are contiguous is expected")
+        H, B = int(d_pix.shape[-2]), int(d_pix.shape[-1])
+        W = B // 2 if W is None else int(W)
+        if B < yuv422_row_bytes(W):
+            raise JpezyError(f"{who}: rows of {B} bytes hold fewer than W = {W} pixels")
+        n = int(d_pix.shape[0]) if d_pix.dim() == 3 else 1
+        row = int(d_pix.stride(-2)) if H > 1 else 0
+        frame = int(d_pix.stride(0)) if d_pix.dim() == 3 and n > 1 else 0
+        return n, H, W, row, frame
+
+    def fdct_quant_yuv422_dev(self, d_pix, d_coeffs, W=None, format=YUV_YUY2):
+        """device packed macropixels (torch uint8 (H, B) or (N, H, B); row and frame strides are the tensor's; W defaults to B // 2)
+        -> d_coeffs in the 4:2:2 layout, on torch's current stream of the tensor's device"""
+        import torch
+        n, H, W, row, frame = self._yuv422_layout(d_pix, W, "fdct_quant_yuv422_dev")
+        stream = torch.cuda.current_stream(d_pix.device).cuda_stream
+        _check(load_library().jpezy_fdct_quant_yuv422_dev(self._h, d_pix.data_ptr(), int(format), row, frame, W, H, n, d_coeffs.data_ptr(), stream))
+
+    def decode_jpeg_yuv422(self, data, format=YUV_YUY2):
+        """.jpg bytes of any layout -> (FrameInfo, uint8 array (H, row_bytes)) of packed macropixels"""
+        lib = load_library()
+        arr = np.frombuffer(bytes(data), dtype=np.uint8)
+        info = FrameInfo()
+        _check(lib.jpezy_decode_jpeg_yuv422(self._h, _np_ptr(arr), arr.size, C.byref(info), int(format), 0, None, 0))
+        img = np.empty((info.height, yuv422_row_bytes(info.width)), dtype=np.uint8)
+        _check(lib.jpezy_decode_jpeg_yuv422(self._h, _np_ptr(arr), arr.size, C.byref(info), int(format), 0, _np_ptr(img), img.size))
+        return info, img
+
+    def dequant_idct_generic_yuv422_dev(self, d_coeffs, info, d_pix, format=YUV_YUY2):
+        """any-layout decode on device memory: coefficients as read_jpeg_gpu leaves them (frame after frame) -> packed macropixels written
+        into d_pix (torch uint8 (H, B) or (N, H, B), B >= row_bytes; strides are the tensor's), on torch's current stream of the device"""
+        import torch
+        n, H, W, row, frame = self._yuv422_layout(d_pix, info.width, "dequant_idct_generic_yuv422_dev")
+        if H != info.height:
+            raise JpezyError(f"dequant_idct_generic_yuv422_dev: the tensor has {H} rows, the picture {info.height}")
+        stream = torch.cuda.current_stream(d_coeffs.device).cuda_stream
+        head = self._stage_head(d_coeffs.data_ptr(), info, False)[:10]
+        _check(load_library().jpezy_dequant_idct_generic_yuv422_dev(*head, int(format), row, frame, n, d_pix.data_ptr(), stream))
 
     # ---- reduced-size decode (scale 1, 2, 4, 8: an N x N inverse transform per block, N = 8 / scale; include/jpezy_hip.h) ----
     def decode_jpeg_scaled(self, data, scale, gray=False):

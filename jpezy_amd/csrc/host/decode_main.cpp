@@ -13,6 +13,9 @@
 // jpezy_decode --i420 <input.(jpg | jpeg)> <output.yuv>   (this project's own option) writes the file's own samples, without upsampling
 // or colour conversion, as raw planes: Y, then Cb, then Cr (full range: ffmpeg's yuvj420p) through jpezy_decode_jpeg_ycc.  Only a
 // 4:2:0 file (sampling 2x2, 1x1, 1x1) is such a picture: any other layout is refused with a message.
+// jpezy_decode --yuy2 | --uyvy <input.(jpg | jpeg)> <output.yuv>   (this project's own option) writes a file of any layout as packed
+// YCbCr 4:2:2 macropixels, tight rows (full range: ffmpeg's rawvideo yuyv422 / uyvy422) through jpezy_decode_jpeg_yuv422
+// (include/jpezy_hip_ycc422.h).  Exactly these four arguments: --gray, --scale=, --region=, --upsampling=, --orient are usage errors.
 #include <cstdlib>
 #include <fstream>
 #include <iostream>
@@ -155,10 +158,48 @@ int i420_main(const int argc, const char* argv[])
     return EXIT_SUCCESS;
 }
 
+// jpezy_decode --yuy2 | --uyvy in.jpg out.yuv: a file of any layout as packed YCbCr 4:2:2 macropixels, tight rows (ffmpeg's rawvideo
+// yuyv422 / uyvy422), through jpezy_decode_jpeg_yuv422; exactly four arguments, every other option is a usage error
+int yuv422_main(const int argc, const char* argv[], const int format)
+{
+    if (argc != 4) {
+        std::cerr << "Usage: jpezy_decode --yuy2 | --uyvy <input.(jpg | jpeg)> <output.yuv>" << std::endl;
+        return EXIT_FAILURE;
+    }
+    jpezy::disp_logo();
+    std::ifstream ifs(argv[2], std::ios::binary);
+    const std::vector<std::uint8_t> data((std::istreambuf_iterator<char>(ifs)), std::istreambuf_iterator<char>());
+    jpezy_ctx* ctx = jpezy::detail::device_context();
+    jpezy_frame_info info;
+    if (!ifs.is_open() || jpezy_decode_jpeg_yuv422(ctx, data.data(), data.size(), &info, format, 0, nullptr, 0) != JPEZY_OK) {
+        std::cerr << "decode failed" << std::endl;
+        return EXIT_FAILURE;
+    }
+    std::vector<std::uint8_t> out(static_cast<std::size_t>(jpezy_yuv422_row_bytes(info.width)) * info.height);
+    if (jpezy_decode_jpeg_yuv422(ctx, data.data(), data.size(), &info, format, 0, out.data(), out.size()) != JPEZY_OK) {
+        std::cerr << "decode failed: " << jpezy_hip_last_error() << std::endl;
+        return EXIT_FAILURE;
+    }
+    std::ofstream ofs(argv[3], std::ios::binary | std::ios::trunc);
+    ofs.write(reinterpret_cast<const char*>(out.data()), static_cast<std::streamsize>(out.size()));
+    if (!ofs) { std::cerr << "output_file" << std::endl; return EXIT_FAILURE; }
+    std::cout << "Decoded image: raw packed YCbCr 4:2:2 (" << (format == JPEZY_YUV_UYVY ? "UYVY" : "YUY2") << "), size = " << info.width << " x "
+              << info.height << std::endl;
+    return EXIT_SUCCESS;
+}
+
 }  // namespace
 
 int main(const int argc, const char* argv[])
 {
+    if (argc >= 2 && (std::string_view(argv[1]) == "--yuy2" || std::string_view(argv[1]) == "--uyvy")) {
+        try {
+            return yuv422_main(argc, argv, std::string_view(argv[1]) == "--uyvy" ? JPEZY_YUV_UYVY : JPEZY_YUV_YUY2);
+        } catch (const std::runtime_error& e) {
+            std::cerr << e.what() << std::endl;
+            return EXIT_FAILURE;
+        }
+    }
     if (argc >= 2 && std::string_view(argv[1]) == "--i420") {
         for (int k = 2; k < argc; ++k) {
             const int up = upsampling_of(argv[k]);

@@ -20,6 +20,9 @@
 // Extension (not in the reference):  jpezy_encode --i420=WxH <in.yuv> <out.jpg> [--gray] [--optimize] [--restart=N] [--quality=N]
 // encodes a raw planar YCbCr 4:2:0 file -- the W x H Y plane, then the ceil(W/2) x ceil(H/2) Cb and Cr planes, full range (ffmpeg's
 // yuvj420p) -- through jpezy_encode_jpeg_ycc: the samples go into the file as they are, without a colour conversion.
+// Extension (not in the reference):  jpezy_encode --yuy2=WxH | --uyvy=WxH <in.yuv> <out.jpg> [--optimize] [--restart=N] [--quality=N]
+// encodes raw packed YCbCr 4:2:2 macropixels, tight rows of 4 * ceil(W/2) bytes, full range (ffmpeg's rawvideo yuyv422 / uyvy422) into a
+// 4:2:2 file through jpezy_encode_jpeg_yuv422, on the --i420 code path; every other option there is a usage error.
 #include <cstdlib>
 #include <fstream>
 #include <iostream>
@@ -220,14 +223,18 @@ int take_chroma(std::vector<const char*>& args, std::size_t from)
 }
 
 // jpezy_encode --i420=WxH in.yuv out.jpg [--gray] [--optimize] [--restart=N] [--quality=N]
-int i420_main(const int argc, const char* argv[])
+// yuv >= 0 (JPEZY_YUV_YUY2 / JPEZY_YUV_UYVY): jpezy_encode --yuy2=WxH | --uyvy=WxH in.yuv out.jpg [--optimize] [--restart=N] [--quality=N]
+int i420_main(const int argc, const char* argv[], const int yuv = -1)
 {
-    const auto usage = [] {
-        std::cerr << "Usage: jpezy_encode --i420=WxH <input.yuv> <output.(jpeg | jpg)> [OPT: --gray] [OPT: --optimize] [OPT: --restart=N] [OPT: --quality=N]" << std::endl;
+    const auto usage = [yuv] {
+        if (yuv >= 0)
+            std::cerr << "Usage: jpezy_encode --yuy2=WxH | --uyvy=WxH <input.yuv> <output.(jpeg | jpg)> [OPT: --optimize] [OPT: --restart=N] [OPT: --quality=N]" << std::endl;
+        else
+            std::cerr << "Usage: jpezy_encode --i420=WxH <input.yuv> <output.(jpeg | jpg)> [OPT: --gray] [OPT: --optimize] [OPT: --restart=N] [OPT: --quality=N]" << std::endl;
         return EXIT_FAILURE;
     };
     std::string_view dims = argv[1];
-    dims.remove_prefix(std::string_view("--i420=").size());
+    dims.remove_prefix(std::string_view("--i420=").size());      // (--yuy2= and --uyvy= are as long)
     const auto x = dims.find('x');
     if (x == std::string_view::npos || argc < 4) return usage();
     const int W = parse_u16(dims.substr(0, x)), H = parse_u16(dims.substr(x + 1));
@@ -236,10 +243,11 @@ int i420_main(const int argc, const char* argv[])
     int restart = 0, quality = 0;
     for (int i = 4; i < argc; ++i) {
         const std::string_view o = argv[i];
-        if (o == "--gray") gray = true;
+        if (o == "--gray" && yuv < 0) gray = true;
         else if (o == "--optimize") optimize = true;
         else if (o.rfind("--restart=", 0) == 0 && (restart = parse_restart(o)) >= 0) continue;
         else if (o.rfind("--quality=", 0) == 0 && (quality = parse_quality(o)) >= 1) continue;
+        else if (yuv >= 0) return usage();                         // no gray form, one sampling, the caller's chroma
         else if (o.rfind("--sampling=", 0) == 0 && parse_sampling(o) == JPEZY_SAMPLING_420) continue;
         else if (o.rfind("--sampling=", 0) == 0 && parse_sampling(o) == JPEZY_SAMPLING_444) return sampling_rule();
         else if (o.rfind("--chroma=", 0) == 0 && parse_chroma(o) == JPEZY_DOWNSAMPLE_POINT) continue;
@@ -252,7 +260,14 @@ int i420_main(const int argc, const char* argv[])
     const std::size_t ny = static_cast<std::size_t>(W) * H, nc = static_cast<std::size_t>(CW) * CH;
     std::ifstream ifs(argv[2], std::ios::binary);
     std::vector<std::uint8_t> buf((std::istreambuf_iterator<char>(ifs)), std::istreambuf_iterator<char>());
-    if (!ifs.is_open() || buf.size() != ny + 2 * nc) {
+    if (yuv >= 0) {
+        const std::size_t need = static_cast<std::size_t>(jpezy_yuv422_row_bytes(W)) * H;
+        if (!ifs.is_open() || buf.size() != need) {
+            std::cerr << "jpezy_encode: " << argv[2] << " must hold " << need << " bytes (rows of " << jpezy_yuv422_row_bytes(W) << " bytes of a " << W
+                      << " x " << H << " picture), it holds " << buf.size() << std::endl;
+            return EXIT_FAILURE;
+        }
+    } else if (!ifs.is_open() || buf.size() != ny + 2 * nc) {
         std::cerr << "jpezy_encode: " << argv[2] << " must hold " << ny + 2 * nc << " bytes (Y, Cb, Cr planes of a " << W << " x " << H
                   << " picture), it holds " << buf.size() << std::endl;
         return EXIT_FAILURE;
@@ -262,10 +277,11 @@ int i420_main(const int argc, const char* argv[])
         if (optimize && jpezy_ctx_set_huffman_optimize(ctx, 1) != JPEZY_OK) throw std::runtime_error(std::string("jpezy_ctx_set_huffman_optimize: ") + jpezy_hip_last_error());
         if (restart && jpezy_ctx_set_restart_interval(ctx, restart) != JPEZY_OK) throw std::runtime_error(std::string("jpezy_ctx_set_restart_interval: ") + jpezy_hip_last_error());
         if (quality && jpezy_ctx_set_quality(ctx, quality) != JPEZY_OK) throw std::runtime_error(std::string("jpezy_ctx_set_quality: ") + jpezy_hip_last_error());
-        std::vector<std::uint8_t> jpg(jpezy_jpeg_bound(W, H));
-        const long n = jpezy_encode_jpeg_ycc(ctx, buf.data(), 0, buf.data() + ny, buf.data() + ny + nc, 0, 1, W, H, gray ? 1 : 0,
-                                             gray ? "Encoded by JPEZY" : "Encoded by jpezy", jpg.data(), jpg.size());
-        if (n < 0) throw std::runtime_error(std::string("jpezy_encode_jpeg_ycc: ") + jpezy_hip_last_error());
+        std::vector<std::uint8_t> jpg(yuv >= 0 ? jpezy_jpeg_bound_sampling(W, H, JPEZY_SAMPLING_422) : jpezy_jpeg_bound(W, H));
+        const long n = yuv >= 0 ? jpezy_encode_jpeg_yuv422(ctx, buf.data(), yuv, 0, W, H, "Encoded by jpezy", jpg.data(), jpg.size())
+                                : jpezy_encode_jpeg_ycc(ctx, buf.data(), 0, buf.data() + ny, buf.data() + ny + nc, 0, 1, W, H, gray ? 1 : 0,
+                                                        gray ? "Encoded by JPEZY" : "Encoded by jpezy", jpg.data(), jpg.size());
+        if (n < 0) throw std::runtime_error(std::string(yuv >= 0 ? "jpezy_encode_jpeg_yuv422: " : "jpezy_encode_jpeg_ycc: ") + jpezy_hip_last_error());
         std::ofstream ofs(argv[3], std::ios::binary);
         ofs.write(reinterpret_cast<const char*>(jpg.data()), static_cast<std::streamsize>(n));
         if (!ofs) throw std::runtime_error("output_file");
@@ -283,6 +299,8 @@ int main(const int argc_in, const char* argv_in[])
 {
     if (argc_in >= 3 && std::string_view(argv_in[1]) == "--gpus") return batch_main(argc_in, argv_in);
     if (argc_in >= 2 && std::string_view(argv_in[1]).rfind("--i420=", 0) == 0) return i420_main(argc_in, argv_in);
+    if (argc_in >= 2 && std::string_view(argv_in[1]).rfind("--yuy2=", 0) == 0) return i420_main(argc_in, argv_in, JPEZY_YUV_YUY2);
+    if (argc_in >= 2 && std::string_view(argv_in[1]).rfind("--uyvy=", 0) == 0) return i420_main(argc_in, argv_in, JPEZY_YUV_UYVY);
     if (argc_in < 3) return disp_error();
     // the one --restart=N and the one --quality=N token are taken out; what is left is read as before
     std::vector<const char*> args(argv_in, argv_in + argc_in);

@@ -389,6 +389,8 @@ int jpezy_internal_fdct_quant_core(jpezy_ctx* c, const EncodeSource& src, int sa
     p.c_row_stride = src.c_row_stride;
     p.c_step = src.c_step;
     p.c_frame_stride = src.c_frame_stride;
+    p.y_step = src.y_step;
+    p.yuv_format = src.yuv_format;
     p.coeffs = d_coeffs;
     p.coeffs_per_frame = s420 ? jpezy_coeff_count(W, H, gray) : jpezy_coeff_count_sampling(W, H, sampling);
     p.tab = c->d_tab.as<DeviceTables>();
@@ -426,6 +428,7 @@ int jpezy_internal_fdct_quant_core(jpezy_ctx* c, const EncodeSource& src, int sa
     const int force = c->force_exact;
     auto launch = [&](const EncParams& q) -> hipError_t {
         if (sampling == JPEZY_SAMPLING_444) return launch_fdct_quant_f32_444(q, force, s);
+        if (sampling == JPEZY_SAMPLING_422 && src.is_ycc()) return launch_fdct_quant_f32_422_ycc(q, force, s);     // YCbCr 4:2:2 samples
         if (sampling == JPEZY_SAMPLING_422) return launch_fdct_quant_f32_422(q, force, avg, s);
         if (src.is_ycc()) return f64 ? launch_fdct_quant_ycc(q, g, force != 0, s) : launch_fdct_quant_f32_ycc(q, g, force, s);
         if (src.pix_bytes) {
@@ -642,7 +645,8 @@ int jpezy_internal_generic_dev_core(jpezy_ctx* c, const DecodeSource& src, const
     GenericDecParams p;
     if (int rc = decode_geometry(c, src, out, &p)) return rc;
     p.W = src.W; p.H = src.H;
-    if (src.n_frames < 1 || (src.n_frames > 1 && (out.frame_stride < (size_t)src.W * src.H || (out.frame_stride & 3))))
+    // (a packed 4:2:2 sink's frames may be any number of bytes apart: its entry checked the stride against a frame's bytes)
+    if (src.n_frames < 1 || (src.n_frames > 1 && !out.yuv422 && (out.frame_stride < (size_t)src.W * src.H || (out.frame_stride & 3))))
         return set_err(JPEZY_E_BADARG, "generic decoder, batch form: plane stride must hold a plane and be a multiple of 4");
     p.ycc = out.ycc;
     p.c_step = out.c_step;
@@ -658,7 +662,7 @@ int jpezy_internal_generic_dev_core(jpezy_ctx* c, const DecodeSource& src, const
     p.coef_limit = c->coef_limit;
     p.force_exact = c->force_exact != 0;
     p.fallback_count = c->d_counter.as<unsigned long long>();
-    HIP_TRY(launch_dequant_idct_generic(p, s, upsampling ? launch_smooth_rgb : nullptr));
+    HIP_TRY(launch_dequant_idct_generic(p, s, out.yuv422 ? launch_generic_yuv422 : upsampling ? launch_smooth_rgb : nullptr));
     return JPEZY_OK;
 }
 

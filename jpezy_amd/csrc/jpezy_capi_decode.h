@@ -48,7 +48,8 @@ struct DecodeSource {
 // bytes of pixel (0, 0), rows row_stride apart.  Native component planes (ycc, the any-layout pair only): r, g, b are sample (0, 0) of
 // the components (null: not wanted), rows row_stride / c_row_stride apart, chroma samples c_step apart.  The fused kernel's batches
 // (jpezy_internal_fused_dev_core) also read c_frame_stride, the chroma planes' frame stride, and pix, the packed buffer's first byte;
-// the three stage cores read neither.
+// the three stage cores read neither.  Packed YCbCr 4:2:2 macropixels (yuv422, the any-layout pair only): r, g, b are the Y0, Cb, Cr
+// bytes of macropixel (0, 0), rows row_stride, frames frame_stride (any value) apart.
 struct DecodeSink {
     uint8_t *r, *g, *b;
     size_t frame_stride;
@@ -58,6 +59,7 @@ struct DecodeSink {
     unsigned c_row_stride;
     size_t c_frame_stride = 0;
     uint8_t* pix = nullptr;
+    int yuv422 = 0;             // packed YCbCr 4:2:2 macropixels (the any-layout pair only): r, g, b are the Y0, Cb, Cr bytes of macropixel (0, 0)
     static DecodeSink planes(uint8_t* r, uint8_t* g, uint8_t* b, size_t plane_stride) { return { r, g, b, plane_stride, 0, 0, 0, 1, 0 }; }
     static DecodeSink packed(const PackedLayout& L, uint8_t* pix)
     {
@@ -67,6 +69,11 @@ struct DecodeSink {
                                  size_t y_frame_stride = 0, size_t c_frame_stride = 0)
     {
         return { y, cb, cr, y_frame_stride, 0, y_row_stride, 1, c_step, c_row_stride, c_frame_stride };
+    }
+    // y_off, cb_off, cr_off: where the three bytes lie inside a macropixel (the format); rows row_stride, frames frame_stride apart
+    static DecodeSink yuv422_packed(uint8_t* pix, int y_off, int cb_off, int cr_off, unsigned row_stride, size_t frame_stride)
+    {
+        return { pix + y_off, pix + cb_off, pix + cr_off, frame_stride, 2, row_stride, 0, 1, 0, 0, pix, 1 };
     }
     // the same sink `frames` frames on; component planes that are not wanted stay null
     void advance(size_t frames)

@@ -22,6 +22,9 @@ struct EncodeSource {
     unsigned c_row_stride;
     int c_step;
     size_t c_frame_stride;
+    // YCbCr 4:2:2 samples (JPEZY_SAMPLING_422 only): the planar description with CH = H, or (y_step 2) packed macropixels -- r, g, b the
+    // Y0, Cb, Cr bytes of macropixel (0, 0), c_step 4, pix the buffer's first byte, both row and both frame strides the buffer's
+    int y_step = 1, yuv_format = 0;
     static EncodeSource planes(const uint8_t* r, const uint8_t* g, const uint8_t* b, size_t plane_stride)
     {
         return { r, g, b, plane_stride, nullptr, 0, 0, 0, 0, 0, 0 };
@@ -33,6 +36,12 @@ struct EncodeSource {
     static EncodeSource ycc(const uint8_t* y, const uint8_t* cb, const uint8_t* cr, const YccLayout& L, int c_step, int gray)
     {
         return { y, gray ? nullptr : cb, gray ? nullptr : cr, L.yfs, nullptr, 0, (unsigned)L.ys, 0, (unsigned)L.cs, c_step, L.cfs };
+    }
+    static EncodeSource ycc422(const uint8_t* y, const uint8_t* cb, const uint8_t* cr, const YccLayout& L, int c_step) { return ycc(y, cb, cr, L, c_step, 0); }
+    static EncodeSource yuv422(const Yuv422Layout& L, int format, const uint8_t* pix)
+    {
+        return { pix + L.off[0], pix + L.off[1], pix + L.off[2], L.frame_stride, pix, 0, (unsigned)L.row_stride, 0, (unsigned)L.row_stride, 4,
+                 L.frame_stride, 2, format };
     }
     bool is_ycc() const { return c_step != 0; }
     // the same source `frames` frames on; chroma planes that are not there stay null

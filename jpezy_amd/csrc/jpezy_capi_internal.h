@@ -2,7 +2,8 @@
 // jpezy_capi.hip (context, the two transform stages), jpezy_capi_entropy.hip (Huffman coding: the host writer's entry points, the GPU
 // coder's two forms, encoder::encode end to end), jpezy_capi_huffdec.hip (GPU Huffman decoding of one file, decoder::decode end to end),
 // jpezy_capi_decode_batch.hip (the batch form), jpezy_capi_packed.hip (the entry points for packed, i.e. interleaved, pixels),
-// jpezy_capi_scaled.hip (reduced-size decode), jpezy_capi_ycc.hip (planar YCbCr 4:2:0 samples in and out), jpezy_capi_sampling.hip (chroma
+// jpezy_capi_scaled.hip (reduced-size decode), jpezy_capi_ycc.hip (planar YCbCr 4:2:0 samples in and out), jpezy_capi_ycc422.hip (YCbCr
+// 4:2:2 samples in and out: planes and packed macropixels), jpezy_capi_sampling.hip (chroma
 // sampling as an argument of the encoder's entries), jpezy_capi_transform.hip (lossless transforms in the coefficient domain),
 // jpezy_capi_smooth.hip (smooth chroma upsampling in the decoder), jpezy_capi_windows.hip (a batch of crop windows into device memory),
 // jpezy_capi_resized.hip (the same batch resized to one output size: tap tables and the second stage), jpezy_capi_multi.hip (the multi-GPU handle).
@@ -175,11 +176,12 @@ struct YccLayout {
 };
 
 // c_step, strides and the 32-bit row-offset limit (W, H already checked); before the context or a device is touched
+// chroma_rows: the chroma planes' height where it is not ceil(H/2) -- H for 4:2:2 samples (jpezy_capi_ycc422.hip)
 inline int ycc_layout(const char* who, int W, int H, size_t y_stride, size_t c_stride, int c_step, size_t y_frame_stride, size_t c_frame_stride,
-                      YccLayout* L)
+                      YccLayout* L, int chroma_rows = 0)
 {
     if (c_step != 1 && c_step != 2) return set_err(JPEZY_E_BADARG, std::string(who) + ": c_step must be 1 (planes) or 2 (one interleaved plane)");
-    const int CW = (W + 1) / 2, CH = (H + 1) / 2;
+    const int CW = (W + 1) / 2, CH = chroma_rows ? chroma_rows : (H + 1) / 2;
     const size_t ys = y_stride ? y_stride : (size_t)W;
     const size_t c_min = (size_t)(CW - 1) * c_step + 1;
     const size_t cs = c_stride ? c_stride : (size_t)CW * c_step;
@@ -192,6 +194,29 @@ inline int ycc_layout(const char* who, int W, int H, size_t y_stride, size_t c_s
     if (yfs < (size_t)(H - 1) * ys + (size_t)W) return set_err(JPEZY_E_BADARG, std::string(who) + ": y_frame_stride smaller than (H-1) * y_stride + W");
     if (cfs < (size_t)(CH - 1) * cs + c_min) return set_err(JPEZY_E_BADARG, std::string(who) + ": c_frame_stride smaller than a chroma plane");
     *L = { CW, CH, ys, cs, yfs, cfs };
+    return JPEZY_OK;
+}
+
+// packed YCbCr 4:2:2 macropixels (YUY2 / UYVY / YVYU): jpezy_capi_ycc422.hip
+struct Yuv422Layout {
+    int off[3];                // byte of Y0, Cb, Cr inside a macropixel (Y1 two behind Y0)
+    size_t row_bytes, row_stride, frame_stride;
+};
+
+// format, strides and the 32-bit row-offset limit (W, H already checked); before the context or a device is touched
+inline int yuv422_layout(const char* who, int format, size_t row_stride, size_t frame_stride, int W, int H, Yuv422Layout* L)
+{
+    if (format != JPEZY_YUV_YUY2 && format != JPEZY_YUV_UYVY && format != JPEZY_YUV_YVYU)
+        return set_err(JPEZY_E_BADARG, std::string(who) + ": format must be JPEZY_YUV_YUY2, JPEZY_YUV_UYVY or JPEZY_YUV_YVYU");
+    const size_t row_bytes = (size_t)4 * ((W + 1) / 2);
+    const size_t rs = row_stride ? row_stride : row_bytes;
+    if (rs < row_bytes) return set_err(JPEZY_E_BADARG, std::string(who) + ": row_stride smaller than 4 * ceil(W/2)");
+    if (rs > 0xFFFFFFFFull / (size_t)H) return set_err(JPEZY_E_BADARG, std::string(who) + ": row_stride * H must fit in 32 bits");
+    const size_t fs = frame_stride ? frame_stride : (size_t)H * rs;
+    if (fs < (size_t)(H - 1) * rs + row_bytes)
+        return set_err(JPEZY_E_BADARG, std::string(who) + ": frame_stride smaller than (H-1) * row_stride + 4 * ceil(W/2)");
+    const bool uyvy = format == JPEZY_YUV_UYVY, yvyu = format == JPEZY_YUV_YVYU;
+    *L = { { uyvy ? 1 : 0, uyvy ? 0 : yvyu ? 3 : 1, uyvy ? 2 : yvyu ? 1 : 3 }, row_bytes, rs, fs };
     return JPEZY_OK;
 }
 

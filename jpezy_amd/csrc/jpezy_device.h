@@ -99,6 +99,12 @@ struct EncParams {
     unsigned c_row_stride = 0;
     int c_step = 0;
     size_t c_frame_stride = 0;
+    // YCbCr 4:2:2 input, jpezy_fdct_quant_ycc422_dev / jpezy_fdct_quant_yuv422_dev (jpezy_kernels_f32_422_ycc.hip only): the fields above
+    // with CH = H.  y_step: bytes between the Y samples of a row -- 1 (planes) or 2 (packed macropixels: r, g, b then are the Y0, Cb, Cr
+    // bytes of macropixel (0, 0), c_step is 4, both row strides and both frame strides are the buffer's and pix is its first byte).
+    // yuv_format: the packed format (enum JPEZY_YUV_*), which picks the aligned load's v_perm selectors.  Behind every field the other
+    // instances read, with defaults: their argument offsets are what they were.
+    int y_step = 1, yuv_format = 0;
 #ifdef JPEZY_TRACE
     unsigned long long* trace;       // development builds only (tools/profile/wave_trace.py): 4 words per wave
 #endif
@@ -166,6 +172,9 @@ hipError_t launch_fdct_quant_ycc(const EncParams& p, bool gray, bool force_exact
 // pixels alike: quads_per_row counts work units of 8 MCUs (jpezy_f32_octet.h; jpezy_kernels_f32_444.hip, jpezy_kernels_f32_422.hip)
 hipError_t launch_fdct_quant_f32_444(const EncParams& p, int force, hipStream_t stream);
 hipError_t launch_fdct_quant_f32_422(const EncParams& p, int force, bool average, hipStream_t stream);
+// 4:2:2 from YCbCr 4:2:2 samples, planar (EncParams::y_step 1, c_step 1 or 2) or packed macropixels (y_step 2): the same octets without
+// a colour conversion (jpezy_kernels_f32_422_ycc.hip)
+hipError_t launch_fdct_quant_f32_422_ycc(const EncParams& p, int force, hipStream_t stream);
 // variant 2: the same arithmetic in persistent workgroups with LDS-DMA loader waves (jpezy_kernels_f32_ps.hip); frames whose rows do
 // not divide into groups of four quads, or unaligned planes, go to variant 1's launch.  n_cus: compute units of the device.
 hipError_t launch_fdct_quant_f32_ps(const EncParams& p, bool gray, int force, int n_cus, hipStream_t stream);
@@ -218,6 +227,9 @@ typedef hipError_t (*GenericStage2)(const GenericDecParams& q, dim3 grid, hipStr
 hipError_t launch_dequant_idct_generic(const GenericDecParams& p, hipStream_t stream, GenericStage2 stage2 = nullptr);
 // smooth (triangle-filter) chroma upsampling (jpezy_kernels_smooth.hip; include/jpezy_hip.h, CHROMA UPSAMPLING)
 hipError_t launch_smooth_rgb(const GenericDecParams& q, dim3 grid, hipStream_t stream);
+// packed YCbCr 4:2:2 macropixels in generic_rgb_kernel's place (jpezy_kernels_generic.hip; include/jpezy_hip_ycc422.h): q.r, q.g, q.b are the
+// Y0, Cb, Cr bytes of macropixel (0, 0), rows q.row_stride, frames q.plane_stride apart
+hipError_t launch_generic_yuv422(const GenericDecParams& q, dim3 grid, hipStream_t stream);
 // frames of p's layout one pair of launches takes (the launcher loops over larger batches); 0: a frame too large for one launch
 int generic_frames_per_launch(const GenericDecParams& p);
 

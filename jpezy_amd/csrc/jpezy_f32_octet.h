@@ -12,6 +12,7 @@
 //     WAVES  waves per SIMD the register allocation aims at (the kernel's launch bound)
 //     load_packed<PIX>(src, swap_rb, R, G, B)    4 NW packed pixels (PIX bytes each) -> NW words per channel
 //     samples<COMP>(R, G, B, S)                  the lane's 8 samples of pass COMP into S[COMP], A[k] = (s[k], s[7-k]) as fdct8p takes them
+// (a unit whose input is not RGB pixels has OWN_SOURCE and load<ALIGNED>(..) in load_packed's place: the source hook, OwnSource below).
 // A wave makes BPM passes, each over the eight blocks of one kind: the lane's 8 samples -> row pass -> transpose tile -> column pass ->
 // quantiser -> staged block; then the queued coefficients, then BPM whole-line stores per lane: 8 BPM blocks, 1 KB x BPM of contiguous
 // output per wave.  The integer samples of all passes stay in registers (8 BPM) for levels 2 and 3, as YL / YR / CS do in the quad.
@@ -21,6 +22,7 @@
 // pass at a time; behind it the staging area of 8 BPM blocks x STG_BLK; behind that the queue.  4:4:4: 6400 bytes, the quad's; 4:2:2:
 // 7552 bytes, 30208 per workgroup: five workgroups, 20 waves, fit the CU's 160 KB -- more than the 12 the register allocation admits.
 #pragma once
+#include <type_traits>
 #include <utility>
 #include "jpezy_f32_onequad.h"   // load_packed16
 
@@ -75,6 +77,15 @@ __device__ __forceinline__ void load_packed8(const uint8_t* src, bool swap_rb, u
         }
     }
 }
+
+// The source hook: a unit whose pixels are not three channels of NW words each (YCbCr 4:2:2 samples, jpezy_kernels_f32_422_ycc.hip) says
+// OWN_SOURCE and supplies the load step itself,
+//     load<ALIGNED>(p, frame, mcu_x, y, R, G, B)    the lane's row segment of row y (clamped) of MCU mcu_x (clamped) -> what samples<> reads
+// and, for the launcher, its family's own alignment rule K::aligned(p).  Every other unit takes the load step below.
+template <class U, class = void>
+struct OwnSource : std::false_type {};
+template <class U>
+struct OwnSource<U, std::enable_if_t<U::OWN_SOURCE>> : std::true_type {};
 
 // what a lane keeps from pass to pass
 struct OctetLane {
@@ -168,36 +179,40 @@ __device__ __forceinline__ void encode_octet(const EncParams& p, uint32_t* lds_a
     uint32_t R[NW], G[NW], B[NW];
     {
         const int y = min(mcu_y * 8 + row, H - 1);                        // clamped extension to whole MCUs, ref :101
-        const bool packed = p.pix_bytes != 0;                             // wave-uniform
-        // W, H <= 65535 and row_stride * H < 2^32 (the entry points): fits 32 bits
-        const unsigned rowoff = (unsigned)y * (PIX != 0 || packed ? p.row_stride : (unsigned)W);
-        const size_t fo = (size_t)frame * p.plane_stride;
-        if (ALIGNED && PIX != 0) {
-            U::template load_packed<PIX>(p.pix + fo + (rowoff + (unsigned)mcu_x * (unsigned)(4 * NW * PIX)), p.swap_rb != 0, R, G, B);
-        } else if (ALIGNED) {
-            typedef uint32_t words __attribute__((ext_vector_type(NW)));
-            const unsigned off = rowoff + (unsigned)mcu_x * (unsigned)(4 * NW);
-            const words vr = *reinterpret_cast<const words*>(p.r + fo + off);
-            const words vg = *reinterpret_cast<const words*>(p.g + fo + off);
-            const words vb = *reinterpret_cast<const words*>(p.b + fo + off);
-#pragma unroll
-            for (int k = 0; k < NW; ++k) { R[k] = vr[k]; G[k] = vg[k]; B[k] = vb[k]; }
+        if constexpr (OwnSource<U>::value) {
+            U::template load<ALIGNED>(p, frame, mcu_x, y, R, G, B);
         } else {
-            const uint8_t* pr = p.r + fo + rowoff;
-            const uint8_t* pg = p.g + fo + rowoff;
-            const uint8_t* pb = p.b + fo + rowoff;
-            const unsigned step = packed ? (unsigned)p.pix_bytes : 1u;
+            const bool packed = p.pix_bytes != 0;                             // wave-uniform
+            // W, H <= 65535 and row_stride * H < 2^32 (the entry points): fits 32 bits
+            const unsigned rowoff = (unsigned)y * (PIX != 0 || packed ? p.row_stride : (unsigned)W);
+            const size_t fo = (size_t)frame * p.plane_stride;
+            if (ALIGNED && PIX != 0) {
+                U::template load_packed<PIX>(p.pix + fo + (rowoff + (unsigned)mcu_x * (unsigned)(4 * NW * PIX)), p.swap_rb != 0, R, G, B);
+            } else if (ALIGNED) {
+                typedef uint32_t words __attribute__((ext_vector_type(NW)));
+                const unsigned off = rowoff + (unsigned)mcu_x * (unsigned)(4 * NW);
+                const words vr = *reinterpret_cast<const words*>(p.r + fo + off);
+                const words vg = *reinterpret_cast<const words*>(p.g + fo + off);
+                const words vb = *reinterpret_cast<const words*>(p.b + fo + off);
 #pragma unroll
-            for (int w = 0; w < NW; ++w) {
-                uint32_t ar = 0, ag = 0, ab = 0;
+                for (int k = 0; k < NW; ++k) { R[k] = vr[k]; G[k] = vg[k]; B[k] = vb[k]; }
+            } else {
+                const uint8_t* pr = p.r + fo + rowoff;
+                const uint8_t* pg = p.g + fo + rowoff;
+                const uint8_t* pb = p.b + fo + rowoff;
+                const unsigned step = packed ? (unsigned)p.pix_bytes : 1u;
 #pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const unsigned x = (unsigned)min(mcu_x * (4 * NW) + w * 4 + k, W - 1) * step;   // ref :104
-                    ar |= (uint32_t)pr[x] << (8 * k);
-                    ag |= (uint32_t)pg[x] << (8 * k);
-                    ab |= (uint32_t)pb[x] << (8 * k);
+                for (int w = 0; w < NW; ++w) {
+                    uint32_t ar = 0, ag = 0, ab = 0;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const unsigned x = (unsigned)min(mcu_x * (4 * NW) + w * 4 + k, W - 1) * step;   // ref :104
+                        ar |= (uint32_t)pr[x] << (8 * k);
+                        ag |= (uint32_t)pg[x] << (8 * k);
+                        ab |= (uint32_t)pb[x] << (8 * k);
+                    }
+                    R[w] = ar; G[w] = ag; B[w] = ab;
                 }
-                R[w] = ar; G[w] = ag; B[w] = ab;
             }
         }
     }
@@ -315,7 +330,8 @@ static hipError_t launch_octets(const EncParams& p0, int force, hipStream_t stre
     if (p.pix_bytes != 0 && p.pix_bytes != 3 && p.pix_bytes != 4) return hipErrorInvalidValue;
     if (p.n_frames > 65535) return hipErrorInvalidValue;                  // grid.y limit; callers chunk larger batches
     bool al;
-    if (p.pix_bytes) al = p.W % MCU_W == 0 && p.row_stride % 16 == 0 && p.plane_stride % 16 == 0 && (uintptr_t)p.pix % 16 == 0;
+    if constexpr (f32::OwnSource<typename K::Unit>::value) al = K::aligned(p);
+    else if (p.pix_bytes) al = p.W % MCU_W == 0 && p.row_stride % 16 == 0 && p.plane_stride % 16 == 0 && (uintptr_t)p.pix % 16 == 0;
     else al = p.W % MCU_W == 0 && p.plane_stride % MCU_W == 0 && (((uintptr_t)p.r | (uintptr_t)p.g | (uintptr_t)p.b) % MCU_W == 0);
     p.groups_per_row = (p.quads_per_row + f32::OWPB - 1) / f32::OWPB;
     const long groups = (long)p.mcu_rows * p.groups_per_row;

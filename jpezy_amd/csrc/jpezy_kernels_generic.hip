@@ -9,7 +9,8 @@
 //                         ((cu*cv) * (coef*Q)) * cos[u][x] * cos[v][y], v outer, u inner, and stores int(sum/4 + sl),
 //                         sl = 128 (2048 if precision != 8)                 (ref decoder/jpezy_decoder.hpp:645-670)
 //   generic_rgb_kernel  : one lane per pixel; block placement of each component exactly as decode_mcu does it (ref
-//                         :504-528), then make_rgb / revise_value in the reference's FP64 order (ref :531-578, 672-676)
+//                         :504-528), then make_rgb / revise_value in the reference's FP64 order (ref :531-578, 672-676);
+//                         its instance generic_yuv422_kernel writes packed YCbCr 4:2:2 macropixels instead, without make_rgb
 // The fused kernel covers jpezy_encode's own 2x2,1x1,1x1 layout in one pass; this pair exists so that every file the
 // reference decodes also decodes here, at about a third of the fused kernel's speed.
 #include "jpezy_pixel_out.h"
@@ -156,9 +157,19 @@ __global__ __launch_bounds__(64) void generic_idct_kernel(GenericDecParams p, lo
 // One thread: four consecutive pixels of a row (one 4-byte store per plane when the row allows it); a workgroup: 256 pixels
 // of four rows.  Everything that depends on the row only (MCU row, the component's block row, whether decode_mcu ever
 // writes that row of the component's plane) is computed once per thread.
-// PIX: 0 = planes; 3 / 4 = packed (interleaved) pixels of that many bytes -- the thread's four pixels are 12 or 16 contiguous bytes,
+// The second stages share that thread: the per-layout sample fetch -- smp[c][j], the integer sample of component c that the
+// nearest-neighbour decode feeds make_rgb for pixel (x0 + j, y) -- and behind it the sink's store, chosen at compile time.  (The fetch as
+// a __forceinline__ function of its own, called from two kernels, moved the instructions of the three RGB instances -- it is optimised
+// once on its own before it is inlined --; as one template the instances 0 / 3 / 4 are the machine code they were.)
+// SINK: 0 = planes; 3 / 4 = packed (interleaved) pixels of that many bytes -- the thread's four pixels are 12 or 16 contiguous bytes,
 // one 12- or 16-byte store when they start on a 4-byte boundary and all four exist, single bytes otherwise.
-template <int PIX = 0>
+// SINK_YUV422: packed YCbCr 4:2:2 macropixels (include/jpezy_hip_ycc422.h) -- the thread's four pixels are two macropixels, 8 contiguous
+// bytes.  The Y byte of a pixel is revise_value of its luma sample, the Cb / Cr bytes of a macropixel those of the samples fetched for its
+// EVEN pixel (pixels 0 and 2 of the thread); no make_rgb.  p.r, p.g, p.b: the Y0, Cb, Cr bytes of macropixel (0, 0) -- the format is
+// their order --, rows p.row_stride, frames p.plane_stride apart.  One 8-byte store when the address is a multiple of 8 and all four
+// pixels exist, single bytes otherwise; with an odd W the last macropixel's second Y byte repeats its first.
+constexpr int SINK_YUV422 = 2;
+template <int SINK = 0>
 __global__ __launch_bounds__(256) void generic_rgb_kernel(GenericDecParams p)
 {
     const unsigned x0 = (blockIdx.x * 64u + (threadIdx.x & 63u)) * 4u;
@@ -215,22 +226,46 @@ __global__ __launch_bounds__(256) void generic_rgb_kernel(GenericDecParams p)
             }
         }
     }
-    uint32_t rw = 0, gw = 0, bw = 0;
+    if constexpr (SINK == SINK_YUV422) {
+        uint8_t* base = p.r < p.g ? p.r : p.g;                   // the macropixel's first byte: Y0 or Cb
+        const unsigned sy = 8u * (unsigned)(p.r - base), sb = 8u * (unsigned)(p.g - base), sr = 8u * (unsigned)(p.b - base);
+        uint32_t w[2];
 #pragma unroll
-    for (unsigned j = 0; j < 4; ++j) {
-        uint32_t r, g, b;
-        make_rgb(p.gray, smp[0][j], smp[1][j], smp[2][j], r, g, b);
-        rw |= r << (8 * j); gw |= g << (8 * j); bw |= b << (8 * j);
-    }
-    if constexpr (PIX != 0) {
-        const bool blue_first = p.b < p.r;                       // r, g, b: the channel bytes of pixel (0, 0)
-        uint8_t* px = (blue_first ? p.b : p.r) + (size_t)y * p.row_stride + (size_t)x0 * PIX;
-        store_packed4<PIX>(px, npx, blue_first ? bw : rw, gw, blue_first ? rw : bw);
+        for (unsigned q = 0; q < 2; ++q) {
+            const uint32_t y0 = (uint32_t)clamp8(smp[0][2 * q]), y1 = 2 * q + 1 < npx ? (uint32_t)clamp8(smp[0][2 * q + 1]) : y0;
+            w[q] = y0 << sy | y1 << (sy + 16u) | (uint32_t)clamp8(smp[1][2 * q]) << sb | (uint32_t)clamp8(smp[2][2 * q]) << sr;
+        }
+        uint8_t* px = base + (size_t)y * p.row_stride + (size_t)x0 * 2u;
+        if (npx == 4 && ((uintptr_t)px & 7u) == 0) {
+            *reinterpret_cast<uint2*>(px) = make_uint2(w[0], w[1]);
+        } else {
+            const unsigned nb = npx > 2 ? 8u : 4u;
+#pragma unroll
+            for (unsigned j = 0; j < 8; ++j)
+                if (j < nb) px[j] = (uint8_t)(w[j >> 2] >> (8u * (j & 3u)));
+        }
     } else {
-        const size_t off = (size_t)y * p.W + x0;
-        store_planes4(p.r, p.g, p.b, off, npx, rw, gw, bw, (p.W & 3) == 0);   // rows start 4-byte aligned (the planes are device allocations)
+        constexpr int PIX = SINK;
+        uint32_t rw = 0, gw = 0, bw = 0;
+#pragma unroll
+        for (unsigned j = 0; j < 4; ++j) {
+            uint32_t r, g, b;
+            make_rgb(p.gray, smp[0][j], smp[1][j], smp[2][j], r, g, b);
+            rw |= r << (8 * j); gw |= g << (8 * j); bw |= b << (8 * j);
+        }
+        if constexpr (PIX != 0) {
+            const bool blue_first = p.b < p.r;                       // r, g, b: the channel bytes of pixel (0, 0)
+            uint8_t* px = (blue_first ? p.b : p.r) + (size_t)y * p.row_stride + (size_t)x0 * PIX;
+            store_packed4<PIX>(px, npx, blue_first ? bw : rw, gw, blue_first ? rw : bw);
+        } else {
+            const size_t off = (size_t)y * p.W + x0;
+            store_planes4(p.r, p.g, p.b, off, npx, rw, gw, bw, (p.W & 3) == 0);   // rows start 4-byte aligned (the planes are device allocations)
+        }
     }
 }
+
+// the packed 4:2:2 second stage: that template's instance with the macropixel sink
+constexpr auto generic_yuv422_kernel = generic_rgb_kernel<SINK_YUV422>;
 
 // Native component planes (GenericDecParams::ycc, jpezy_decode_jpeg_ycc on a layout that is not this project's own): component c comes
 // out at its own sampling, ceil(W * H_c / hmax) x ceil(H * V_c / vmax) samples, block (kx, ky) of MCU (ux, uy) at ((ux * H_c + kx) * 8,
@@ -259,6 +294,13 @@ __global__ __launch_bounds__(256) void generic_ycc_kernel(GenericDecParams p)
 }
 
 }  // namespace generic
+
+// the second stage of launch_dequant_idct_generic for a packed 4:2:2 sink: q is what generic_rgb_kernel would be launched with
+hipError_t launch_generic_yuv422(const GenericDecParams& q, dim3 grid, hipStream_t s)
+{
+    hipLaunchKernelGGL(generic::generic_yuv422_kernel, grid, dim3(256), 0, s, q);
+    return hipGetLastError();
+}
 
 int generic_frames_per_launch(const GenericDecParams& p)
 {

@@ -14,7 +14,9 @@ mild noise).  Per sampling, the legs take turns inside every round (interleaved)
                time, as a fraction of 8.0 TB/s (specification) and of 6.29 TB/s (the float4-copy figure of this GPU)
 
 Samplings: 420, 444, 422, and 422avg -- 4:2:2 with the context in DOWNSAMPLE_AVERAGE (the transform differs; the entropy legs see other
-coefficients of the same layout).
+coefficients of the same layout).  422i422, 422nv16, 422yuy2, 422uyvy: the 4:2:2 transform from YCbCr 4:2:2 samples -- planes, one
+interleaved chroma plane, packed macropixels (fdct_quant_ycc422_dev / fdct_quant_yuv422_dev; 2 bytes in and 4 out per pixel) --, the
+transform leg only.
 
 --root DIR imports jpezy_amd from another checkout of the project (the parent commit beside this one, for the A/B of the 4:2:0 path):
 a checkout without a sampling runs the legs of those it has.  Nothing here is an acceptance bound.
@@ -29,6 +31,9 @@ from pathlib import Path
 
 import numpy as np
 import torch
+
+
+YCC422 = ("422i422", "422nv16", "422yuy2", "422uyvy")
 
 
 def pictures(W, H):
@@ -54,7 +59,8 @@ def main():
     # name -> (the library's constant, bytes of algorithmic traffic per pixel, MCU width, averaged chroma)
     known = {"420": (0, 6, 16, False), "444": (getattr(J, "SAMPLING_444", None), 9, 8, False),
              "422": (getattr(J, "SAMPLING_422", None), 7, 16, False), "422avg": (getattr(J, "SAMPLING_422", None), 7, 16, True)}
-    samplings = [s for s in args.samplings.split(",") if known[s][0] is not None]
+    known.update({s: (getattr(J, "SAMPLING_422", None), 6, 16, False) for s in YCC422})     # 2 bytes in, 4 out per pixel
+    samplings = [s for s in args.samplings.split(",") if s not in YCC422 and known[s][0] is not None]
     dev = torch.device("cuda:0")
     ctx = J.Context(0)
     lines = [f"measure_sampling: {W}x{H}, {args.rounds} interleaved rounds of {args.iters} calls per leg, {torch.cuda.get_device_name(0)}, "
@@ -88,6 +94,23 @@ def main():
             legs[s, "entropy rst"] = (en, row, False)
             legs[s, "both"] = (lambda fd=fd, en=en: (fd(), en()), 0, False)
             legs[s, "opt (host)"] = (lambda kw=kw, co=co: ctx.write_jpeg_gpu(co, W, H, **kw), 0, True)
+            fd()
+            torch.cuda.synchronize()
+        # YCbCr 4:2:2 samples in (include/jpezy_hip_ycc422.h): the transform alone -- its coefficients have 4:2:2's layout, so the entropy
+        # legs above are theirs too.  The picture's first plane as Y, every second column of the other two as Cb, Cr: any byte is a sample.
+        for s in [x for x in args.samplings.split(",") if x in YCC422 and hasattr(ctx, "fdct_quant_ycc422_dev")]:
+            co = torch.empty(J.coeff_count(W, H, sampling=J.SAMPLING_422), dtype=torch.int16, device=dev)
+            cb, cr = d[1][:, 0::2].contiguous(), d[2][:, 0::2].contiguous()
+            if s == "422i422":
+                fd = lambda co=co, cb=cb, cr=cr: ctx.fdct_quant_ycc422_dev(d[0], cb, cr, co)
+            elif s == "422nv16":
+                uv = torch.stack([cb, cr], -1).contiguous()
+                fd = lambda co=co, uv=uv: ctx.fdct_quant_ycc422_dev(d[0], uv[..., 0], uv[..., 1], co)
+            else:
+                fmt = J.YUV_UYVY if s == "422uyvy" else J.YUV_YUY2
+                mp = torch.stack([cb, d[0][:, 0::2], cr, d[0][:, 1::2]] if s == "422uyvy" else [d[0][:, 0::2], cb, d[0][:, 1::2], cr], -1).reshape(H, 2 * W).contiguous()
+                fd = lambda co=co, mp=mp, fmt=fmt: ctx.fdct_quant_yuv422_dev(mp, co, format=fmt)
+            legs[s, "transform"] = (fd, 0, False)
             fd()
             torch.cuda.synchronize()
         times = {k: [] for k in legs}

@@ -177,6 +177,18 @@ void jpezy_ctx_set_force_exact(jpezy_ctx* ctx, int on);
  * faster than variant 1 (docs/ROUND5.md), so the shipped library does not contain them: it answers JPEZY_E_UNSUPPORTED and keeps
  * the context's kernel.  Returns JPEZY_OK, JPEZY_E_BADARG (no such variant) or JPEZY_E_UNSUPPORTED.  tests/test_gpu_persistent.py. */
 int jpezy_ctx_set_variant(jpezy_ctx* ctx, int variant);
+/* Workgroup form of encode variant 1's launch for planar RGB / gray 4:2:0 frames with point-sampled chroma (jpezy_fdct_quant[_dev],
+ * jpezy_encode_jpeg; no other launch consults it).  AUTO (default): chosen per launch from the frame's geometry.  The other three force
+ * one form, for tests and A/B measurements -- the results are the same bits in every form:
+ *   4_COOP    four quads per workgroup, pixels fetched cooperatively in 256-byte row pieces; legal where W % 16 == 0, the planes and
+ *             their stride are 16-byte aligned and the quads of a row divide by four
+ *   2_COOP    two quads per workgroup, fetched cooperatively in 128-byte row pieces; legal under the same alignment, any quad count
+ *   2_DIRECT  two quads per workgroup, every lane loads its own 16 pixels; always legal
+ * The setter returns JPEZY_E_BADARG for a value that names no form; a launch whose frame the forced form is not legal for returns
+ * JPEZY_E_BADARG and launches nothing.  tests/test_gpu_encode_groups.py. */
+enum jpezy_encode_groups { JPEZY_ENCODE_GROUPS_AUTO = 0, JPEZY_ENCODE_GROUPS_4_COOP = 1, JPEZY_ENCODE_GROUPS_2_COOP = 2, JPEZY_ENCODE_GROUPS_2_DIRECT = 3 };
+int jpezy_ctx_set_encode_groups(jpezy_ctx* ctx, int groups);
+int jpezy_ctx_encode_groups(const jpezy_ctx* ctx);
 /*
  * Decode tolerance (opt-in; default 0).  BASELINE.json's north_star asks of the decoder "PPM output within +-1 LSB per
  * channel"; the default kernels deliver more (every byte equal to the reference's truncating FP64 arithmetic,

@@ -106,6 +106,8 @@ ABI = [
     ("jpezy_write_jpeg_qt", C.c_long, [_vp, C.c_int, C.c_int, C.c_int, C.c_char_p, _vp, _vp, C.c_int, C.c_int, _vp, C.c_size_t]),
     ("jpezy_quant_tables_probe", C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(C.c_int)]),
     ("jpezy_ctx_set_dc_table_lookup", None, [_vp, C.c_int]),
+    ("jpezy_ctx_set_encode_groups", C.c_int, [_vp, C.c_int]),
+    ("jpezy_ctx_encode_groups", C.c_int, [_vp]),
     ("jpezy_encode_jpeg", C.c_long, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_char_p, _vp, C.c_size_t]),
     ("jpezy_shard_range", None, [C.c_long, C.c_int, C.c_int, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
     ("jpezy_encode_batch_multi", C.c_int, [C.POINTER(C.c_int), C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p,
@@ -251,6 +253,7 @@ YUV_YUY2, YUV_UYVY, YUV_YVYU = 0, 1, 2          # JPEZY_YUV_*: Y0 Cb Y1 Cr / Cb 
 # or 4:4:4 (8 x 8 MCUs of Y, Cb, Cr, no decimation; include/jpezy_hip.h has the definition)
 SAMPLING_420, SAMPLING_444 = 0, 1
 SAMPLING_422 = 3                               # 2x1 / 1x1 / 1x1: 16 x 8 MCUs of Y, Y, Cb, Cr (2 is kept free for 4:4:0 and refused)
+ENCODE_GROUPS_AUTO, ENCODE_GROUPS_4_COOP, ENCODE_GROUPS_2_COOP, ENCODE_GROUPS_2_DIRECT = 0, 1, 2, 3   # Context.set_encode_groups
 DOWNSAMPLE_POINT, DOWNSAMPLE_AVERAGE = 0, 1     # Context.set_chroma_downsampling: how 4:2:0 and 4:2:2 chroma is made from RGB pixels
 
 # enum jpezy_pixel_format: packed (interleaved) pixels, 3 or 4 bytes each
@@ -601,6 +604,15 @@ class Context:
     def set_dc_table_lookup(self, on):
         """test hook: the encode kernels read the quantised DC from the exact table even where the level-1 quantiser may take it"""
         load_library().jpezy_ctx_set_dc_table_lookup(self._h, int(on))
+
+    def set_encode_groups(self, groups):
+        """ENCODE_GROUPS_AUTO (default): the workgroup form of the planar RGB / gray 4:2:0 encode launch is chosen from the frame's
+        geometry; ENCODE_GROUPS_4_COOP, _2_COOP, _2_DIRECT force one form (tests, A/B measurements: the same bits in every form).
+        A launch whose frame the forced form is not legal for raises JpezyError (JPEZY_E_BADARG); include/jpezy_hip.h has the rules."""
+        _check(load_library().jpezy_ctx_set_encode_groups(self._h, int(groups)))
+
+    def encode_groups(self):
+        return _check(load_library().jpezy_ctx_encode_groups(self._h))
 
     def stream(self):
         """the context's own hipStream_t as an integer"""

@@ -221,6 +221,20 @@ void jpezy_ctx_set_dc_table_lookup(jpezy_ctx* c, int on)
     if (c) c->dc_table_lookup = on != 0;
 }
 
+static_assert(JPEZY_ENCODE_GROUPS_AUTO == ENC_GROUPS_AUTO && JPEZY_ENCODE_GROUPS_4_COOP == ENC_GROUPS_4_COOP &&
+              JPEZY_ENCODE_GROUPS_2_COOP == ENC_GROUPS_2_COOP && JPEZY_ENCODE_GROUPS_2_DIRECT == ENC_GROUPS_2_DIRECT,
+              "enum jpezy_encode_groups and the launcher's values");
+
+int jpezy_ctx_set_encode_groups(jpezy_ctx* c, int groups)
+{
+    if (!c) return set_err(JPEZY_E_BADARG, "null context");
+    if (groups < JPEZY_ENCODE_GROUPS_AUTO || groups > JPEZY_ENCODE_GROUPS_2_DIRECT) return set_err(JPEZY_E_BADARG, "set_encode_groups: no such workgroup form");
+    c->encode_groups = groups;
+    return JPEZY_OK;
+}
+
+int jpezy_ctx_encode_groups(const jpezy_ctx* c) { return c ? c->encode_groups : set_err(JPEZY_E_BADARG, "null context"); }
+
 int jpezy_quality_tables(int quality, uint8_t luma[64], uint8_t chroma[64])
 {
     if (!luma || !chroma) return set_err(JPEZY_E_BADARG, "quality_tables: null pointer");
@@ -426,7 +440,9 @@ int jpezy_internal_fdct_quant_core(jpezy_ctx* c, const EncodeSource& src, int sa
     // averaged stage is read here, at launch (never YCbCr input, never 4:4:4), and 4:4:4 / 4:2:2 serve planes and packed pixels alike.
     const bool g = gray != 0, avg = !src.is_ycc() && encode_averaged(c, sampling, gray), f64 = c->variant == 0;
     const int force = c->force_exact;
-    auto launch = [&](const EncParams& q) -> hipError_t {
+    // the forced workgroup form acts on variant 1's planar launch alone (the last line of the lambda)
+    const int groups = (s420 && !src.is_ycc() && !src.pix_bytes && !avg && c->variant == 1) ? c->encode_groups : JPEZY_ENCODE_GROUPS_AUTO;
+    auto launch =[&](const EncParams& q) -> hipError_t {
         if (sampling == JPEZY_SAMPLING_444) return launch_fdct_quant_f32_444(q, force, s);
         if (sampling == JPEZY_SAMPLING_422 && src.is_ycc()) return launch_fdct_quant_f32_422_ycc(q, force, s);     // YCbCr 4:2:2 samples
         if (sampling == JPEZY_SAMPLING_422) return launch_fdct_quant_f32_422(q, force, avg, s);
@@ -442,8 +458,10 @@ int jpezy_internal_fdct_quant_core(jpezy_ctx* c, const EncodeSource& src, int sa
         if (c->variant == 3 && c->qt_default) return launch_fdct_quant_f32_ps2(q, g, force, c->n_cus, s);
         if (c->variant == 2 && c->qt_default) return launch_fdct_quant_f32_ps(q, g, force, c->n_cus, s);
 #endif
-        return f64 ? launch_fdct_quant(q, g, force != 0, s) : launch_fdct_quant_f32(q, g, force, s);
+        return f64 ? launch_fdct_quant(q, g, force != 0, s) : launch_fdct_quant_f32(q, g, force, s, groups);
     };
+    if (groups != JPEZY_ENCODE_GROUPS_AUTO && !fdct_quant_f32_groups_legal(p, groups))
+        return set_err(JPEZY_E_BADARG, "the workgroup form forced by jpezy_ctx_set_encode_groups is not legal for this frame");
     // the kernels put the frame index in a grid dimension: larger batches go out in chunks
     EncodeSource at = src;
     for (int f0 = 0; f0 < n_frames; f0 += kMaxFramesPerLaunch) {

@@ -248,6 +248,7 @@ struct jpezy_ctx {
     bool qt_default = true;        // ... are the Annex-K tables
     int chroma_downsampling = 0;   // JPEZY_DOWNSAMPLE_POINT; read when a colour 4:2:0 RGB transform is launched (jpezy_ctx_set_chroma_downsampling)
     bool dc_table_lookup = false;  // test hook (jpezy_ctx_set_dc_table_lookup): the DC from DeviceTables::dcq even where the checks allow the quantiser
+    int encode_groups = 0;         // JPEZY_ENCODE_GROUPS_AUTO; a forced workgroup form of variant 1's planar launch (jpezy_ctx_set_encode_groups)
     DevBuf d_trace;                // JPEZY_TRACE builds: 4 words per wave + 9 phase stamps (JPEZY_TRACE=3)
     DevBuf dump_t;                 // JPEZY_DUMP_T builds: level-1 t values of the last jpezy_fdct_quant_dev call
     DevBuf in[3], out, scratch;    // staging for the host-buffer entry points; scratch: samples of the generic decoder

@@ -156,7 +156,11 @@ hipError_t launch_fdct_quant(const EncParams& p, bool gray, bool force_exact, hi
 // variant 1: FP32 first level, FP64 second level, reference-order third level.  force: 0 normal, 1 every
 // coefficient through the reference-order chain, 2 every coefficient through the FP64 second level, 3 every quad
 // through the per-lane evaluator of the queue-overflow case.
-hipError_t launch_fdct_quant_f32(const EncParams& p, bool gray, int force, hipStream_t stream);
+// groups: the workgroup form, the values of enum jpezy_encode_groups (include/jpezy_hip.h; jpezy_capi.hip asserts that they agree).
+// AUTO: the launcher's rule by the frame's geometry; a form that is not legal for the frame (fdct_quant_f32_groups_legal) is refused.
+enum { ENC_GROUPS_AUTO = 0, ENC_GROUPS_4_COOP = 1, ENC_GROUPS_2_COOP = 2, ENC_GROUPS_2_DIRECT = 3 };
+hipError_t launch_fdct_quant_f32(const EncParams& p, bool gray, int force, hipStream_t stream, int groups = ENC_GROUPS_AUTO);
+bool fdct_quant_f32_groups_legal(const EncParams& p, int groups);
 // the same two kernels for packed (interleaved) pixels (EncParams::pix_bytes != 0): the f32 one with a 16-byte load form that separates
 // the channels in registers, the FP64 one through its byte loop
 hipError_t launch_fdct_quant_f32_packed(const EncParams& p, bool gray, int force, hipStream_t stream);

@@ -7,12 +7,16 @@
 namespace jpezy_dev {
 namespace f32 {
 
-template <bool GRAY, bool ALIGNED, int FORCE, int EWPB, bool DCG, bool AVG = false>
+// COOP: the workgroup's waves fetch its pixels together (below).  Four-wave workgroups always do, two-wave workgroups where the
+// launcher asks for it (jpezy_kernels_f32.hip: three forms -- {4 waves, cooperative}, {2 waves, cooperative}, {2 waves, direct}).
+template <bool GRAY, bool ALIGNED, int FORCE, int EWPB, bool DCG, bool AVG = false, bool COOP = ALIGNED && EWPB == 4>
 __global__ __launch_bounds__(64 * EWPB, AVG && !ALIGNED ? AVG_BYTELOOP_WAVES : JPEZY_F32_WAVES) void fdct_quant_f32_kernel(EncParams p)
 {
     __shared__ __attribute__((aligned(16))) uint32_t lds_all[EWPB][WAVE_LDS_DWORDS];
-    constexpr bool COOP = ALIGNED && EWPB == 4;     // (the cooperative load is written for 4 waves: 4 x 4 rows of 256 bytes)
-    static_assert(!COOP || 3 * 4096 <= EWPB * WAVE_LDS_DWORDS * 4, "the pixel staging area lies over the waves' slices");
+    static_assert(!COOP || (ALIGNED && (EWPB == 4 || EWPB == 2)), "the cooperative load is written for 4 x 4 rows of 256 bytes and 2 x 8 rows of 128");
+    // geometry of the staged image: a row of the workgroup is 64 * EWPB bytes = COOP_LPR pieces of 16, a wave fetches COOP_RPW rows
+    constexpr int COOP_LPR = 4 * EWPB, COOP_RPW = 64 / COOP_LPR, COOP_ROW = 64 * EWPB, COOP_PLANE = 16 * COOP_ROW;
+    static_assert(!COOP || 3 * COOP_PLANE <= EWPB * WAVE_LDS_DWORDS * 4, "the pixel staging area lies over the waves' slices");
 
     // WPB waves per workgroup; the wave index is made an SGPR so that everything derived from it (quad position, plane
     // and coefficient base addresses, the LDS slice) is computed once on the scalar unit
@@ -58,24 +62,30 @@ __global__ __launch_bounds__(64 * EWPB, AVG && !ALIGNED ? AVG_BYTELOOP_WAVES : J
         // c ^ 4(r & 3) -- the swizzle is applied to the SOURCE address -- so that the 16-byte reads below, whose 16-lane
         // groups span the rows {0,3,5,6} / {1,2,4,7} of one quad, hit 16 different bank groups.  The area lies over the
         // waves' slices: a second barrier before anybody writes a slice.
+        // Two waves: 128 x 16 pixels, wave w fetches rows 8w .. 8w+7, 8 lanes per row (8 rows of 128 bytes = whole 128-byte lines
+        // per row), and piece c of row r lies at position c ^ (r & 4): a 16-lane read group holds the wave's four pieces of two
+        // even and two odd rows, each pair one with and one without bit 2 ({0,6} {3,5} / {2,4} {1,7}), and a row's parity picks
+        // the half of the 64 banks -- 16 different bank groups again (tools/profile/lds_bank_model.py: 12 cycles for the 3 reads).
         char* stg = reinterpret_cast<char*>(&lds_all[0][0]);
         {
-            const int lr = lane >> 4, cp = lane & 15;
-            const int y = min(mcu_y * 16 + wave * 4 + lr, H - 1);                     // edge replication, ref :101
-            const int piece = min(gx * 16 + (cp ^ (4 * lr)), p.mcu_cols - 1);         // W % 16 == 0 here: a piece is an MCU column
+            const int lr = lane / COOP_LPR, cp = lane % COOP_LPR;
+            const int swz = EWPB == 4 ? 4 * lr : (lr & 4);
+            const int y = min(mcu_y * 16 + wave * COOP_RPW + lr, H - 1);              // edge replication, ref :101
+            const int piece = min(gx * COOP_LPR + (cp ^ swz), p.mcu_cols - 1);        // W % 16 == 0 here: a piece is an MCU column
             const unsigned off = (unsigned)y * (unsigned)W + (unsigned)piece * 16u;   // W, H <= 65535 (launcher): fits 32 bits
             typedef __attribute__((address_space(1))) const void* gptr;
             typedef __attribute__((address_space(3))) void* lptr;
             __builtin_amdgcn_global_load_lds((gptr)(pr + off), (lptr)(stg + wave * 1024), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((gptr)(pg + off), (lptr)(stg + 4096 + wave * 1024), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((gptr)(pb + off), (lptr)(stg + 8192 + wave * 1024), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((gptr)(pg + off), (lptr)(stg + COOP_PLANE + wave * 1024), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((gptr)(pb + off), (lptr)(stg + 2 * COOP_PLANE + wave * 1024), 16, 0, 0);
         }
-        __syncthreads();                                   // waits for this wave's DMA (vmcnt) and for the other three
+        __syncthreads();                                   // waits for this wave's DMA (vmcnt) and for the other waves
         {
-            const char* src = stg + row * 256 + (((wave * 4 + m) ^ (4 * (row & 3))) * 16);
+            const int swz = EWPB == 4 ? 4 * (row & 3) : (row & 4);
+            const char* src = stg + row * COOP_ROW + (((wave * 4 + m) ^ swz) * 16);
             const uint4 vr = *reinterpret_cast<const uint4*>(src);
-            const uint4 vg = *reinterpret_cast<const uint4*>(src + 4096);
-            const uint4 vb = *reinterpret_cast<const uint4*>(src + 8192);
+            const uint4 vg = *reinterpret_cast<const uint4*>(src + COOP_PLANE);
+            const uint4 vb = *reinterpret_cast<const uint4*>(src + 2 * COOP_PLANE);
             R[0] = vr.x; R[1] = vr.y; R[2] = vr.z; R[3] = vr.w;
             G[0] = vg.x; G[1] = vg.y; G[2] = vg.z; G[3] = vg.w;
             B[0] = vb.x; B[1] = vb.y; B[2] = vb.z; B[3] = vb.w;

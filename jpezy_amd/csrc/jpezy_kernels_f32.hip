@@ -125,47 +125,83 @@ hipError_t launch_fdct_quant_f32_ycc(const EncParams& p0, bool gray, int force, 
     return hipGetLastError();
 }
 
-template <bool GRAY, bool ALIGNED, int EW, bool DCG>
+template <bool GRAY, bool ALIGNED, int EW, bool DCG, bool COOP>
 static void enc_f32_launch3(const EncParams& p, int force, dim3 grid, hipStream_t s)
 {
     if (force == 1)
-        hipLaunchKernelGGL((f32::fdct_quant_f32_kernel<GRAY, ALIGNED, 1, EW, DCG>), grid, dim3(64 * EW), 0, s, p);
+        hipLaunchKernelGGL((f32::fdct_quant_f32_kernel<GRAY, ALIGNED, 1, EW, DCG, false, COOP>), grid, dim3(64 * EW), 0, s, p);
     else if (force == 2)
-        hipLaunchKernelGGL((f32::fdct_quant_f32_kernel<GRAY, ALIGNED, 2, EW, DCG>), grid, dim3(64 * EW), 0, s, p);
+        hipLaunchKernelGGL((f32::fdct_quant_f32_kernel<GRAY, ALIGNED, 2, EW, DCG, false, COOP>), grid, dim3(64 * EW), 0, s, p);
     else if (force == 3)
-        hipLaunchKernelGGL((f32::fdct_quant_f32_kernel<GRAY, ALIGNED, 3, EW, DCG>), grid, dim3(64 * EW), 0, s, p);
+        hipLaunchKernelGGL((f32::fdct_quant_f32_kernel<GRAY, ALIGNED, 3, EW, DCG, false, COOP>), grid, dim3(64 * EW), 0, s, p);
     else
-        hipLaunchKernelGGL((f32::fdct_quant_f32_kernel<GRAY, ALIGNED, 0, EW, DCG>), grid, dim3(64 * EW), 0, s, p);
+        hipLaunchKernelGGL((f32::fdct_quant_f32_kernel<GRAY, ALIGNED, 0, EW, DCG, false, COOP>), grid, dim3(64 * EW), 0, s, p);
 }
 
-template <bool GRAY, bool ALIGNED, int EW>
+template <bool GRAY, bool ALIGNED, int EW, bool COOP>
 static void enc_f32_launch2(const EncParams& p, int force, dim3 grid, hipStream_t s)
 {
     // the DC through the generic quantiser where jpezy_ctx_create verified it for this build's constants (both tables), else on its
     // own path from the exact table -- a second instance of the kernel, so that the common one carries no trace of the DC path
-    if (p.dc_rq[0] != 0.f && p.dc_rq[1] != 0.f) enc_f32_launch3<GRAY, ALIGNED, EW, true>(p, force, grid, s);
-    else enc_f32_launch3<GRAY, ALIGNED, EW, false>(p, force, grid, s);
+    if (p.dc_rq[0] != 0.f && p.dc_rq[1] != 0.f) enc_f32_launch3<GRAY, ALIGNED, EW, true, COOP>(p, force, grid, s);
+    else enc_f32_launch3<GRAY, ALIGNED, EW, false, COOP>(p, force, grid, s);
 }
 
-hipError_t launch_fdct_quant_f32(const EncParams& p0, bool gray, int force, hipStream_t stream)
+static bool enc_f32_aligned16(const EncParams& p)
+{
+    return (p.W % 16 == 0) && (p.plane_stride % 16 == 0) && (((uintptr_t)p.r | (uintptr_t)p.g | (uintptr_t)p.b) % 16 == 0);
+}
+
+// The workgroup form of a launch (enum jpezy_encode_groups in include/jpezy_hip.h): both cooperative forms need 16-byte pieces (al),
+// the four-wave one also rows of quads that divide by four (its waves all compute); the direct form serves everything.
+bool fdct_quant_f32_groups_legal(const EncParams& p, int groups)
+{
+    const bool al = enc_f32_aligned16(p);
+    switch (groups) {
+    case ENC_GROUPS_AUTO: case ENC_GROUPS_2_DIRECT: return true;
+    case ENC_GROUPS_4_COOP: return al && p.quads_per_row % 4 == 0;
+    case ENC_GROUPS_2_COOP: return al;
+    default: return false;
+    }
+}
+
+#ifndef JPEZY_ENC_GROUPS_DEFAULT
+#define JPEZY_ENC_GROUPS_DEFAULT ENC_GROUPS_AUTO     // A/B builds (tools/ab/ab_build.py) pin a form here
+#endif
+
+static int enc_f32_pick_groups(const EncParams& p, bool al)
+{
+    // the record behind every line is profiles/r26_two_wave_coop.txt (interleaved A/B against the form of the line before it)
+    if (!al) return ENC_GROUPS_2_DIRECT;                              // no 16-byte pieces: the only legal form
+    // rows that divide into groups of four quads (4096 and 7680 wide) took four cooperative waves; two cooperative waves release
+    // their LDS sooner and won every round on encode4096 (-0.5 / -0.6 us of 26.3 / 26.75) and gray8k (-0.8 us of 38.1)
+    if (p.quads_per_row % 4 == 0) return ENC_GROUPS_2_COOP;
+    // every other row (1920 wide: 30 quads) keeps direct loads: batch1080p was 1.4 us of 87 SLOWER in every round with cooperative ones
+    return ENC_GROUPS_2_DIRECT;
+}
+
+hipError_t launch_fdct_quant_f32(const EncParams& p0, bool gray, int force, hipStream_t stream, int groups)
 {
     EncParams p = p0;
-    const bool al = (p.W % 16 == 0) && (p.plane_stride % 16 == 0) &&
-                    (((uintptr_t)p.r | (uintptr_t)p.g | (uintptr_t)p.b) % 16 == 0);
-    // four quads per workgroup with the cooperative load where the rows divide evenly, two with direct loads elsewhere
-    const int ew = (al && p.quads_per_row % 4 == 0) ? 4 : 2;
+    const bool al = enc_f32_aligned16(p);
+    if (groups == ENC_GROUPS_AUTO && fdct_quant_f32_groups_legal(p, JPEZY_ENC_GROUPS_DEFAULT)) groups = JPEZY_ENC_GROUPS_DEFAULT;
+    if (!fdct_quant_f32_groups_legal(p, groups)) return hipErrorInvalidValue;      // (jpezy_internal_fdct_quant_core refuses it first)
+    if (groups == ENC_GROUPS_AUTO) groups = enc_f32_pick_groups(p, al);
+    const int ew = groups == ENC_GROUPS_4_COOP ? 4 : 2;
     p.groups_per_row = (p.quads_per_row + ew - 1) / ew;
-    const long groups = (long)p.mcu_rows * p.groups_per_row;
-    if (groups <= 0 || p.n_frames <= 0) return hipSuccess;
+    const long ngroups = (long)p.mcu_rows * p.groups_per_row;
+    if (ngroups <= 0 || p.n_frames <= 0) return hipSuccess;
     if (p.n_frames > 65535) return hipErrorInvalidValue;               // grid.y limit; callers chunk larger batches
     fast_div_setup((unsigned)p.groups_per_row, &p.gpr_magic, &p.gpr_shift);
-    const dim3 grid((unsigned)groups, (unsigned)p.n_frames);
-    if (ew == 4) {
-        if (gray) enc_f32_launch2<true, true, 4>(p, force, grid, stream); else enc_f32_launch2<false, true, 4>(p, force, grid, stream);
+    const dim3 grid((unsigned)ngroups, (unsigned)p.n_frames);
+    if (groups == ENC_GROUPS_4_COOP) {
+        if (gray) enc_f32_launch2<true, true, 4, true>(p, force, grid, stream); else enc_f32_launch2<false, true, 4, true>(p, force, grid, stream);
+    } else if (groups == ENC_GROUPS_2_COOP) {
+        if (gray) enc_f32_launch2<true, true, 2, true>(p, force, grid, stream); else enc_f32_launch2<false, true, 2, true>(p, force, grid, stream);
     } else if (gray) {
-        if (al) enc_f32_launch2<true, true, 2>(p, force, grid, stream); else enc_f32_launch2<true, false, 2>(p, force, grid, stream);
+        if (al) enc_f32_launch2<true, true, 2, false>(p, force, grid, stream); else enc_f32_launch2<true, false, 2, false>(p, force, grid, stream);
     } else {
-        if (al) enc_f32_launch2<false, true, 2>(p, force, grid, stream); else enc_f32_launch2<false, false, 2>(p, force, grid, stream);
+        if (al) enc_f32_launch2<false, true, 2, false>(p, force, grid, stream); else enc_f32_launch2<false, false, 2, false>(p, force, grid, stream);
     }
     return hipGetLastError();
 }

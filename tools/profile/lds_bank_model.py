@@ -115,6 +115,26 @@ def decode_model(stage="zigzag", blk_pitch=128, dh_pitch=20, dh_mcu=336, c_pitch
     return out
 
 
+def encode_coop_model(ewpb, swizzle=True):
+    """the three 16-byte read-backs of the encode kernel's cooperative pixel load (jpezy_f32_onequad.h, COOP): a workgroup of ewpb
+    waves stages 16 rows of 64 * ewpb bytes per plane, lane (row, m) of wave w reads piece 4w + m of its row at position
+    piece ^ swz(row); swz = 4 * (row & 3) for four waves, row & 4 for two.  Returns the worst wave's (cycles, conflict-free cycles)."""
+    row_bytes, plane = 64 * ewpb, 16 * 64 * ewpb
+    worst = (0, 0)
+    for w in range(ewpb):
+        tot = ide = 0
+        for pl in range(3):
+            addr = []
+            for l in range(64):
+                row, m = l >> 2, l & 3
+                swz = (4 * (row & 3) if ewpb == 4 else (row & 4)) if swizzle else 0
+                addr.append(pl * plane + row * row_bytes + ((4 * w + m) ^ swz) * 16)
+            c, i = cycles("ds_read_b128", addr)
+            tot += c; ide += i
+        worst = max(worst, (tot, ide))
+    return worst
+
+
 def show(title, res):
     tot = sum(c for c, _ in res.values())
     ide = sum(i for _, i in res.values())
@@ -135,3 +155,7 @@ if __name__ == "__main__":
     print("best MCU strides for the transposed tiles:", best)
     show(f"natural-order staging, 144-byte blocks, MCU strides {best[1]} / {best[2]}", decode_model(stage="natural", blk_pitch=144, dh_mcu=best[1], c_mcu=best[2]))
     show(f"zig-zag staging kept, MCU strides {best[1]} / {best[2]}", decode_model(dh_mcu=best[1], c_mcu=best[2]))
+    for ewpb in (4, 2):
+        for swz in (False, True):
+            c, i = encode_coop_model(ewpb, swz)
+            print(f"encode cooperative load, {ewpb} waves, {'swizzled' if swz else 'plain'}: {c} LDS cycles per wave for the three read-backs (conflict-free {i})")
